@@ -111,3 +111,42 @@ def test_bench_refuses_more_ranks_than_gpus():
 def test_bench_gpus_must_match_world_size():
     r = _run_bench("--gpus", "1", "--rehearse-cpu", "--steps", "1", "--warmup", "0", "--mib", "1", env={"WORLD_SIZE": "2", "RANK": "0"})
     assert r.returncode != 0 and "must agree" in r.stderr
+
+
+def test_bench_dump_outputs_on_cpu_ranks(tmp_path):
+    # --dump-outputs writes the buffer of the last timed step as float32 byte values: a fixed, seeded sample of a large one
+    sys.path.insert(0, ROOT)
+    import bench
+    r = _run_bench("--gpus", "1", "--rehearse-cpu", "--steps", "2", "--warmup", "0", "--mib", "8", "--dump-outputs", str(tmp_path))
+    assert r.returncode == 0, r.stderr[-2000:]
+    x = np.load(tmp_path / "copy.npy")
+    assert x.dtype == np.float32 and x.size == bench.DUMP_SAMPLE and (x == 0).all()
+    assert np.load(tmp_path / "sizes.npy").tolist() == [8 << 20]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_full_run_and_dump(hb, tmp_path):
+    # A plain run prints the headline only and dumps what its last timed step computed: the decoded bytes equal the input at the
+    # sampled positions.  --full adds the stage times, the roofline and the other decode paths.
+    import json
+    sys.path.insert(0, ROOT)
+    import bench
+    n = 64 << 20
+
+    def line(*extra):
+        r = _run_bench("--gpus", "1", "--steps", "3", "--warmup", "1", "--mib", "64", *extra)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1, r.stdout
+        return json.loads(lines[0])
+    d = line("--dump-outputs", str(tmp_path))
+    assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] == pytest.approx(n / (d["ms_per_step"] * 1e-3) / 1e9, rel=1e-2)
+    assert not {"stage_ms", "roofline", "with_header_readback", "cpu_baseline"} & set(d)
+    cbytes, total, dec = np.load(tmp_path / "sizes.npy").tolist()
+    assert dec == n and 16 < cbytes <= total
+    idx = np.sort(np.random.default_rng(0).integers(0, n, bench.DUMP_SAMPLE))
+    assert np.array_equal(np.load(tmp_path / "decompressed.npy"), bench.synth_host("f32", n, 0)[idx].astype(np.float32))
+    f = np.load(tmp_path / "frame.npy")
+    assert f.dtype == np.float32 and f.size == bench.DUMP_SAMPLE and 0 <= f.min() and f.max() <= 255
+    d = line("--full", "--no-cpu", "--no-multi")
+    assert {"stage_ms", "roofline", "with_header_readback", "default_frame_no_trailer"} <= set(d)
