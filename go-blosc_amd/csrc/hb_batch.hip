@@ -154,11 +154,13 @@ int hb_frames_batch_headers_dev(int nframes, const void *const *d_frame, const s
     if (nframes == 0) return HB_OK;
     if (scratch_bytes < (size_t)nframes * 32 + 256) return HB_ERR_SHORT_BUFFER;
     hipStream_t s = (hipStream_t)stream;
+    // 16-byte records first (from the first 16-byte boundary of the scratch, which need not be aligned), then the pointers and the flags:
+    // at most 15 + 25 * nframes bytes, inside the documented 32 * nframes + 256
     uint8_t *w = (uint8_t *)d_scratch;
-    const uint8_t **d_ptrs = (const uint8_t **)w;
-    uint8_t *d_valid = w + al256((size_t)nframes * 8);
-    u32x4 *d_out = (u32x4 *)(d_valid + al256((size_t)nframes));
-    if ((size_t)((uint8_t *)(d_out + nframes) - w) > scratch_bytes) return HB_ERR_SHORT_BUFFER;
+    u32x4 *d_out = (u32x4 *)(w + ((16u - ((uintptr_t)w & 15u)) & 15u));
+    const uint8_t **d_ptrs = (const uint8_t **)(d_out + nframes);
+    uint8_t *d_valid = (uint8_t *)(d_ptrs + nframes);
+    if ((size_t)((d_valid + nframes) - w) > scratch_bytes) return HB_ERR_SHORT_BUFFER;
     std::vector<uint8_t> valid((size_t)nframes), raw((size_t)nframes * HB_HEADER_SIZE);
     for (int k = 0; k < nframes; k++) {
         rc[k] = (n[k] < HB_HEADER_SIZE) ? HB_ERR_INVALID_HEADER : (d_frame[k] ? HB_OK : HB_ERR_BAD_ARG);      // blosc.go:297-299
@@ -174,15 +176,30 @@ int hb_frames_batch_headers_dev(int nframes, const void *const *d_frame, const s
     return HB_OK;
 }
 
+// A frame whose index the batch may rebuild (whether it brings one is not in the header): every frame hb_decompress_frames_batch_dev
+// rebuilds is one of these, with the same stream length.
+static bool rg_candidate(const hb_header &h) {
+    return !(h.flags & HB_FLAG_MEMCPY) && h.cbytes >= HB_HEADER_SIZE && hb_lz4_region_batch_wanted((size_t)h.cbytes - HB_HEADER_SIZE, h.nbytes);
+}
+// region size of the batch's discovery jobs: about 16384 regions over the candidates' streams (what one large frame gets), never below the
+// one-frame path's 4 KiB, at most 64 KiB.  A function of the headers alone, so that the workspace and the call lay every job out alike
+// (a job's scratch is not monotone in its region size: longer regions have fewer, larger token stores).
+static uint64_t rg_batch_rs_min(int nframes, const hb_header *hdrs) {
+    size_t stream = 0;
+    for (int k = 0; k < nframes; k++)
+        if (rg_candidate(hdrs[k])) stream += (size_t)hdrs[k].cbytes - HB_HEADER_SIZE;
+    return std::min<uint64_t>(65536, std::max<uint64_t>(4096, stream / 16384));
+}
+
 size_t hb_decompress_frames_batch_workspace(int nframes, const hb_header *hdrs) {
     if (nframes <= 0 || !hdrs) return 256;
     size_t units = 0, staged = 0, rg = 0, rgi = 0;
+    const uint64_t rs_min = rg_batch_rs_min(nframes, hdrs);
     for (int k = 0; k < nframes; k++) {
         units = (units + 31) / 32 * 32 + ((size_t)hdrs[k].nbytes + HB_CHUNK - 1) / HB_CHUNK;
         staged += al256((size_t)hdrs[k].nbytes + 64);
-        // (whether a frame brings its index is not in the header: room for every LZ4 frame's discovery)
-        if (!(hdrs[k].flags & HB_FLAG_MEMCPY) && hdrs[k].cbytes >= HB_HEADER_SIZE && hb_lz4_region_batch_wanted((size_t)hdrs[k].cbytes - HB_HEADER_SIZE, hdrs[k].nbytes)) {
-            rg += rg_batch_layout((size_t)hdrs[k].cbytes - HB_HEADER_SIZE).total;
+        if (rg_candidate(hdrs[k])) {
+            rg += rg_batch_layout((size_t)hdrs[k].cbytes - HB_HEADER_SIZE, rs_min).total;
             rgi += al256(hb_lz4_index_bound(hdrs[k].nbytes));
         }
     }
@@ -204,8 +221,9 @@ int hb_decompress_frames_batch_dev(int nframes, const hb_header *hdrs, const voi
     // frames the host refuses (blosc.go:385-390, :403-407; short destination) keep their place in the arrays as presets
     std::vector<DecBatchFrame> h((size_t)nframes);
     std::vector<int> unf((size_t)nframes, -1), tsv((size_t)nframes, 1);
-    size_t staged_total = 0, rg_total = 0, rgi_total = 0, rg_stream = 0;
-    std::vector<size_t> rg_off((size_t)nframes, (size_t)-1), rgi_off((size_t)nframes, 0);      // frames whose index is rebuilt on the device: offsets of their scratch / index
+    size_t staged_total = 0, rg_total = 0, rgi_total = 0;
+    std::vector<size_t> rg_off((size_t)nframes, (size_t)-1), rg_len((size_t)nframes, 0), rgi_off((size_t)nframes, 0);   // frames whose index is rebuilt on the device: their scratch / index
+    const uint64_t rs_min = rg_batch_rs_min(nframes, hdrs);
     for (int k = 0; k < nframes; k++) {
         const hb_header &hd = hdrs[k];
         DecBatchFrame &f = h[(size_t)k];
@@ -242,8 +260,7 @@ int hb_decompress_frames_batch_dev(int nframes, const hb_header *hdrs, const voi
         // out (or that was not written chunk-locally) is left to the stream decoder below, as before
         const bool rebuilt = !stored_index && hb_lz4_region_batch_wanted((size_t)f.n_src, hd.nbytes);
         if (rebuilt) {
-            rg_off[(size_t)k] = rg_total; rg_total += rg_batch_layout((size_t)f.n_src).total;      // (sized for the smallest regions; the job may use fewer, longer ones)
-            rg_stream += (size_t)f.n_src;
+            rg_off[(size_t)k] = rg_total; rg_len[(size_t)k] = rg_batch_layout((size_t)f.n_src, rs_min).total; rg_total += rg_len[(size_t)k];
             rgi_off[(size_t)k] = rgi_total; rgi_total += al256(hb_lz4_index_bound(hd.nbytes));
             f.nunits = (uint32_t)(((size_t)hd.nbytes + HB_CHUNK - 1) / HB_CHUNK);
         }
@@ -259,15 +276,13 @@ int hb_decompress_frames_batch_dev(int nframes, const hb_header *hdrs, const voi
     // jobs of the token discovery: scratch and index of frame k at rgwork + rg_off[k]
     std::vector<RgJob> rgj;
     uint32_t rg_maxreg = 0;
-    // region size of the batch: about 16384 regions in all (what one large frame gets), never below the one-frame path's 4 KiB, at most 64 KiB
-    const uint64_t rs_min = std::min<uint64_t>(65536, std::max<uint64_t>(4096, rg_stream / 16384));
     for (int k = 0; k < nframes; k++) {
         if (rg_off[(size_t)k] == (size_t)-1) continue;
         DecBatchFrame &f = h[(size_t)k];
         uint8_t *base = w + L.rgwork + rg_off[(size_t)k];
         uint8_t *idx = w + L.rgidx + rgi_off[(size_t)k];
         RgJob j;
-        hb_lz4_region_batch_job(base, idx, f.src, (size_t)f.n_src, (size_t)f.nbytes, &j, rs_min);
+        if (!hb_lz4_region_batch_job(base, rg_len[(size_t)k], idx, f.src, (size_t)f.n_src, (size_t)f.nbytes, &j, rs_min)) return HB_ERR_SHORT_BUFFER;
         rg_maxreg = std::max(rg_maxreg, j.nreg);
         rgj.push_back(j);
         f.index = idx; f.index_bytes = hb_lz4_index_bound((size_t)f.nbytes);

@@ -103,7 +103,8 @@ static inline RgBatchLayout rg_batch_layout(size_t n_src, uint64_t rs_min = 0) {
 }
 bool hb_lz4_region_batch_wanted(size_t n_src, size_t cap);
 size_t hb_lz4_region_batch_bytes(size_t n_src, size_t cap);
-void hb_lz4_region_batch_job(uint8_t *w, uint8_t *idx, const uint8_t *src, size_t n_src, size_t cap, RgJob *j, uint64_t rs_min = 0);
+// false (nothing written) when the job's layout does not fit the w_bytes reserved for it
+bool hb_lz4_region_batch_job(uint8_t *w, size_t w_bytes, uint8_t *idx, const uint8_t *src, size_t n_src, size_t cap, RgJob *j, uint64_t rs_min = 0);
 int hb_launch_lz4_region_index_batch(const RgJob *d_jobs, int njobs, uint32_t max_nreg, hipStream_t s);
 
 #define RFL(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))

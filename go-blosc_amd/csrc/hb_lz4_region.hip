@@ -1200,14 +1200,16 @@ size_t hb_lz4_region_batch_bytes(size_t n_src, size_t cap) {
     if (!hb_lz4_region_batch_wanted(n_src, cap)) return 0;
     return rg_batch_layout(n_src).total + ((hb_lz4_index_bound(cap) + 255) & ~(size_t)255);
 }
-void hb_lz4_region_batch_job(uint8_t *w, uint8_t *idx, const uint8_t *src, size_t n_src, size_t cap, RgJob *j, uint64_t rs_min) {
+bool hb_lz4_region_batch_job(uint8_t *w, size_t w_bytes, uint8_t *idx, const uint8_t *src, size_t n_src, size_t cap, RgJob *j, uint64_t rs_min) {
     const RgBatchLayout L = rg_batch_layout(n_src, rs_min);
+    if (L.total > w_bytes) return false;
     uint64_t rs; uint32_t nreg;
     rg_regions_min(n_src, rs_min, &rs, &nreg);
     j->src = src; j->n_src = n_src; j->cap = cap;
     j->plan = (RgPlan *)(w + L.plan); j->reg = (RgRegion *)(w + L.reg); j->pmax = (uint32_t *)(w + L.pmax);
     j->traces = (uint2 *)(w + L.trace); j->tok = (uint2 *)(w + L.tok); j->idx = idx;
     j->tokcap = rg_tokcap(rs); j->nreg = nreg; j->rs = (uint32_t)rs; j->pad = 0;
+    return true;
 }
 int hb_launch_lz4_region_index_batch(const RgJob *d_jobs, int njobs, uint32_t max_nreg, hipStream_t s) {
     if (njobs <= 0) return HB_OK;

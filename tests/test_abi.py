@@ -100,3 +100,37 @@ def test_sizes_beyond_uint32_are_refused(hbmod):
         assert rc == -6, (n, rc)
     assert L.hb_compress_frame(ctypes.addressof(a), 64, ctypes.addressof(b), 64, 77, 5, 0, 1, 0, 0) == -4    # codec first
     assert L.hb_strerror(-6) == b"blosc: data too large"
+
+
+def test_every_dev_entry_point_is_called_by_the_contract_tests():
+    # every `_dev` entry point of the header goes through tests/test_gpu_dev_api.py (guards, exact sizes, odd alignments, stale workspaces)
+    text = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hipblosc.h")).read(), flags=re.S)
+    dev = sorted(set(re.findall(r"\b(hb_[a-z0-9_]*_dev(?:_[a-z0-9]+)?)\s*\(", text)))
+    assert len(dev) >= 11, dev
+    tests = open(os.path.join(ROOT, "tests", "test_gpu_dev_api.py")).read()
+    missing = [s for s in dev if not re.search(r"\bL\." + s + r"\(", tests)]
+    assert not missing, missing
+
+
+def test_devmem_layout():
+    # the placement arithmetic of tests/devmem.py: guards never overlap a buffer or each other, each misalignment is what was asked
+    # for, every source has exactly 16 bytes behind it before the next guard or the end of the allocation
+    import devmem as D
+    specs = [D.src("a", 1000, 1), D.out("b", 17, 7), D.src("c", 0, 13), D.out("w", 4096 * 3 + 1, 0), D.out("d", 1, 13), D.src("e", 65537, 0)]
+    slots, total = D.layout(specs)
+    assert [s.source for s in slots] == sorted(s.source for s in slots)          # sources last
+    spans = []
+    for s in slots:
+        want = dict((n, m) for n, _, m, _ in specs)[s.name]
+        assert s.off % 256 == want and (s.off - want) % 256 == 0
+        assert s.off - s.lo >= D.GUARD
+        assert s.hi - (s.off + s.nbytes) == (D.SRC_TAIL if s.source else D.GUARD)
+        spans += [(s.lo, s.off), (s.off, s.off + s.nbytes), (s.off + s.nbytes, s.hi)]
+    spans.sort()
+    for (a0, a1), (b0, b1) in zip(spans, spans[1:]):
+        assert a1 <= b0, (a0, a1, b0, b1)
+    assert spans[0][0] == 0 and spans[-1][1] == total
+    assert slots[-1].source and slots[-1].hi == total                         # the last source ends SRC_TAIL bytes before the end
+    for mis in range(16):
+        (s,), t = D.layout([D.out("x", 5, mis)])
+        assert s.off % 16 == mis and t == s.off + 5 + D.GUARD

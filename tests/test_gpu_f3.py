@@ -12,6 +12,8 @@ import struct
 import numpy as np
 import pytest
 
+import devmem
+
 pytestmark = pytest.mark.gpu
 
 
@@ -218,17 +220,8 @@ def test_foreign_snappy_frames_through_both_workspaces(hb, O):
     with elements: any stream whose offsets fit 16 bits).  A stream with copies ACROSS the 64 KiB units tells them apart:
     the single wavefront with the small workspace, in parallel with the large one; same bytes every time."""
     L = hb.lib()
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    hip.hipMemset.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t]
-    hip.hipFree.argtypes = [ctypes.c_void_p]
-    H2D, D2H = 1, 2
-
-    def dmalloc(nb):
-        ptr = ctypes.c_void_p()
-        assert hip.hipMalloc(ctypes.byref(ptr), nb) == 0
-        return ptr
+    hip = devmem.hip()
+    H2D, D2H, dmalloc = devmem.H2D, devmem.D2H, devmem.dmalloc
 
     rng = np.random.default_rng(5)
     x = O.synth(O.D_F32, (8 << 20) // 4)

@@ -15,6 +15,8 @@ import struct
 import numpy as np
 import pytest
 
+import devmem
+
 pytestmark = pytest.mark.gpu
 
 
@@ -90,17 +92,8 @@ def test_foreign_frames_need_the_larger_workspace(hb, O):
     # hb_decompress_frame_workspace_foreign() to the symbolic decoder; same bytes.  (Device buffers through the HIP runtime the
     # library itself is linked to -- a second runtime in the process, e.g. torch's, would not see the GPU.)
     L = hb.lib()
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    hip.hipMemset.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t]
-    hip.hipFree.argtypes = [ctypes.c_void_p]
-    H2D, D2H = 1, 2
-
-    def dmalloc(nb):
-        ptr = ctypes.c_void_p()
-        assert hip.hipMalloc(ctypes.byref(ptr), nb) == 0
-        return ptr
+    hip = devmem.hip()
+    H2D, D2H, dmalloc = devmem.H2D, devmem.D2H, devmem.dmalloc
 
     x = O.synth(O.D_F32, (8 << 20) // 4)
     f = O.compress_frame(x, shuffle=1, typesize=4)
@@ -134,17 +127,8 @@ def test_rebuilt_index_is_the_same_from_stored_tokens_and_from_bucket_records(hb
     # discovery's bucket records (k_rg_index_fast) + the wave walk, with the larger one from the tokens the first parse stored (k_rg_index_tok,
     # csrc/hb_lz4_region.hip).  Same bytes out, and the SAME index in the workspace (its place: tools/region_debug.py --save-index).
     L = hb.lib()
-    hip = ctypes.CDLL("libamdhip64.so")
-    hip.hipMalloc.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.c_size_t]
-    hip.hipMemcpy.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int]
-    hip.hipMemset.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_size_t]
-    hip.hipFree.argtypes = [ctypes.c_void_p]
-    H2D, D2H = 1, 2
-
-    def dmalloc(nb):
-        ptr = ctypes.c_void_p()
-        assert hip.hipMalloc(ctypes.byref(ptr), nb) == 0
-        return ptr
+    hip = devmem.hip()
+    H2D, D2H, dmalloc = devmem.H2D, devmem.D2H, devmem.dmalloc
 
     al = lambda v: (v + 255) & ~255
     for x, shuffle, ts in ((O.synth(O.D_F32, (48 << 20) // 4), 1, 4), (O.synth(O.D_I32, (24 << 20) // 4), 2, 4), (O.synth(O.D_F64, (32 << 20) // 8), 1, 8)):
