@@ -569,6 +569,78 @@ int64_t hb_decompress_frame(const void *frame, size_t n, void *dst, size_t cap, 
     return (int64_t)r.bytes;
 }
 
+// items [start, start + nitems) of a frame: upload, the small workspace first (enough when the frame's index holds), the full one when the
+// device says the index did not hold, and only nitems * ts bytes come back
+int64_t hb_getitem_frame(const void *frame, size_t n, int64_t start, int64_t nitems, void *dst, size_t cap, int typesize_override, int device) {
+    if (n < HB_HEADER_SIZE) return HB_ERR_INVALID_HEADER;             // blosc.go:297-299
+    if (!frame) return HB_ERR_BAD_ARG;
+    hb_header h;
+    int rc = hb_parse_header(frame, n, &h);
+    if (rc) return rc;
+    const bool zstd = !(h.flags & HB_FLAG_MEMCPY) && h.codec == HB_ZSTD;
+    if (zstd && !hb_zstd_available()) return HB_ERR_INVALID_CODEC;
+    int ts = 1;
+    rc = hb_getitem_check(&h, n, start, nitems, typesize_override, 1, &ts);
+    if (rc) return rc;
+    const size_t bytes = (size_t)nitems * (size_t)ts;
+    if (cap < bytes) return HB_ERR_SHORT_BUFFER;
+    if (!dst && bytes) return HB_ERR_BAD_ARG;
+    rc = select_device(device);
+    if (rc) return rc;
+    if (zstd) {                                                       // host codec: the whole frame (hb_zstd.hip), then the slice
+        std::vector<uint8_t> all((size_t)h.nbytes + 1);
+        g_last_flags = 0;
+        const int64_t got = hb_zstd_decompress_frame(frame, h, all.data(), h.nbytes, typesize_override, device);
+        if (got < 0) return got;
+        if ((uint64_t)got < (uint64_t)start * (uint64_t)ts + bytes) return HB_ERR_SIZE_MISMATCH;
+        if (bytes) memcpy(dst, all.data() + (size_t)start * (size_t)ts, bytes);
+        return (int64_t)bytes;
+    }
+    Scratch sc(device);
+    uint8_t *d_frame = sc.get(n + 64), *d_dst = sc.get(bytes + 64), *d_res = sc.get(sizeof(hb_result));
+    if (!d_frame || !d_dst || !d_res) return HB_ERR_HIP;
+    HB_HIP_TRY(hipMemcpy(d_frame, frame, n, hipMemcpyHostToDevice));
+    hb_result r;
+    for (int full = 0; full < 2; full++) {
+        const size_t wb = hb_getitem_frame_workspace(&h, n, start, nitems, typesize_override, full);
+        uint8_t *d_work = sc.get(wb);
+        if (!d_work) return HB_ERR_HIP;
+        rc = hb_getitem_frame_device(&h, d_frame, n, start, nitems, d_dst, bytes, typesize_override, d_work, wb, (hb_result *)d_res, nullptr);
+        if (rc) return rc;
+        HB_HIP_TRY(hipMemcpy(&r, d_res, sizeof r, hipMemcpyDeviceToHost));
+        if (r.status != HB_ERR_SHORT_BUFFER) break;                   // (the index did not hold: once more with room for the whole frame)
+    }
+    g_last_flags = r.flags;
+    if (r.status) return r.status;
+    if (r.bytes) HB_HIP_TRY(hipMemcpy(dst, d_dst, r.bytes, hipMemcpyDeviceToHost));
+    return (int64_t)r.bytes;
+}
+
+int64_t hb_cblosc_getitem(const void *frame, size_t n, int64_t start, int64_t nitems, void *dst, size_t cap, int device) {
+    hb_cblosc_header h;
+    int rc = hb_cblosc_parse_header(frame, n, &h);
+    if (rc) return rc;
+    uint64_t bytes = 0;
+    rc = hb_cblosc_getitem_prepare(&h, n, start, nitems, &bytes);
+    if (rc) return rc;
+    if ((uint64_t)cap < bytes) return HB_ERR_SHORT_BUFFER;
+    if (!dst && bytes) return HB_ERR_BAD_ARG;
+    rc = select_device(device);
+    if (rc) return rc;
+    Scratch sc(device);
+    const size_t wb = hb_cblosc_getitem_workspace(&h, start, nitems);
+    uint8_t *d_frame = sc.get(n + 64), *d_dst = sc.get((size_t)bytes + 64), *d_work = sc.get(wb), *d_res = sc.get(sizeof(hb_result));
+    if (!d_frame || !d_dst || !d_work || !d_res) return HB_ERR_HIP;
+    HB_HIP_TRY(hipMemcpy(d_frame, frame, h.cbytes, hipMemcpyHostToDevice));
+    rc = hb_cblosc_getitem_device(&h, d_frame, n, start, nitems, d_dst, (size_t)bytes, d_work, wb, (hb_result *)d_res, nullptr);
+    if (rc) return rc;
+    hb_result r;
+    HB_HIP_TRY(hipMemcpy(&r, d_res, sizeof r, hipMemcpyDeviceToHost));
+    if (r.status) return r.status;
+    if (r.bytes) HB_HIP_TRY(hipMemcpy(dst, d_dst, r.bytes, hipMemcpyDeviceToHost));
+    return (int64_t)r.bytes;
+}
+
 int64_t hb_cblosc_compress(const void *src, size_t n, void *dst, size_t cap, int shuffle, int typesize, int device) {
     if ((!src && n) || !dst) return HB_ERR_BAD_ARG;
     if (typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;

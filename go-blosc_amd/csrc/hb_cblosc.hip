@@ -36,19 +36,21 @@ struct CbPlan { uint32_t fail, nblocks, nsplit, pad; };
 
 static inline size_t cb_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
-// ---- the streams of every block ----
+// ---- the streams of blocks [b0, b0 + nb) (hb_cblosc_getitem_device: the blocks that cover a range; the others' bstarts entries and streams
+// are never read); stream offsets count from the first of these blocks ----
 __global__ void k_cb_plan(const uint8_t *__restrict__ frame, uint64_t n, uint32_t nbytes, uint32_t blocksize, uint32_t cbytes, uint32_t typesize, uint32_t flags,
-                          CbPlan *plan, CbStream *streams) {
+                          CbPlan *plan, CbStream *streams, uint32_t b0, uint32_t nb) {
     const uint32_t nblocks = (nbytes + blocksize - 1) / blocksize;
-    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= nblocks) return;
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= nb) return;
+    const uint32_t b = b0 + idx;
     const uint32_t leftover = nbytes % blocksize;
     const bool lastshort = b + 1 == nblocks && leftover != 0u;
     const uint32_t bsize = lastshort ? leftover : blocksize;
     const uint32_t nsplit_frame = cb_nsplit(flags, typesize, blocksize);
     const uint32_t nsplit = lastshort ? 1u : nsplit_frame;
     const uint32_t neblock = bsize / nsplit;
-    CbStream *out = streams + (size_t)b * nsplit_frame;
+    CbStream *out = streams + (size_t)idx * nsplit_frame;
     for (uint32_t s = 0; s < nsplit_frame; s++) { CbStream z; z.src = 0; z.csize = 0; z.dst = 0; z.usize = 0; out[s] = z; }
     uint32_t p = (uint32_t)frame[16 + 4 * b] | ((uint32_t)frame[17 + 4 * b] << 8) | ((uint32_t)frame[18 + 4 * b] << 16) | ((uint32_t)frame[19 + 4 * b] << 24);
     bool bad = neblock == 0u || (uint64_t)neblock * nsplit != bsize;                  // (blosc_c only splits what divides)
@@ -57,7 +59,7 @@ __global__ void k_cb_plan(const uint8_t *__restrict__ frame, uint64_t n, uint32_
         const uint32_t cb = (uint32_t)frame[p] | ((uint32_t)frame[p + 1] << 8) | ((uint32_t)frame[p + 2] << 16) | ((uint32_t)frame[p + 3] << 24);
         p += 4u;
         if (cb == 0u || cb > 0x7FFFFFFFu || (uint64_t)p + cb > cbytes || cb > neblock + neblock / 255u + 16u) { bad = true; break; }
-        CbStream st; st.src = p; st.csize = cb; st.dst = b * blocksize + s * neblock; st.usize = neblock;
+        CbStream st; st.src = p; st.csize = cb; st.dst = idx * blocksize + s * neblock; st.usize = neblock;
         out[s] = st;
         p += cb;
     }
@@ -465,6 +467,61 @@ static CbEncLayout cbe_layout(size_t n, int shuffle, int typesize) {
 // kernels (k_cb_unshuffle & co.) are the opposite case: the same change took them from 0.61 to 0.88 ms -- they keep their 2048 workgroups.
 static inline unsigned cb_grid(uint64_t items) { const uint64_t g = (items + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > (1u << 24) ? (1u << 24) : g)); }
 
+// plan, stream decoders and per-block un-filter for blocks [b0, b0 + nblocks) of the frame: `out` receives their `nbytes` bytes (all of the
+// frame for b0 = 0; the last block of the frame may be shorter).  streams: nblocks * nsplit records, staged: nbytes + 64 bytes.
+static void cb_launch_blocks(const hb_cblosc_header *hdr, const uint8_t *d_frame, size_t n, uint32_t b0, uint32_t nblocks, uint32_t nbytes, uint8_t *out,
+                             CbPlan *plan, CbStream *streams, uint8_t *staged, hipStream_t s) {
+    const uint32_t blocksize = hdr->blocksize, ts = hdr->typesize, flags = hdr->flags;
+    const uint32_t nsplit = cb_nsplit(flags, ts, blocksize);
+    // blosc_d: the byte shuffle counts for typesize > 1 only (and comes first), the bit shuffle for any typesize
+    const bool unshuf = (flags & CB_FLAG_SHUFFLE) && ts > 1, unbit = !unshuf && (flags & CB_FLAG_BITSHUFFLE);
+    const bool filtered = unshuf || unbit;
+    uint8_t *target = filtered ? staged : out;
+    const uint32_t nstreams = nblocks * nsplit;
+    hb_prof_begin("k_cb_plan", s);
+    hipLaunchKernelGGL(k_cb_plan, dim3((nblocks + 63) / 64), dim3(64), 0, s, d_frame, (uint64_t)n, hdr->nbytes, blocksize, hdr->cbytes, ts, flags, plan, streams, b0, nblocks);
+    const bool small = blocksize / nsplit <= HB_CHUNK;                   // streams of at most one chunk: the LDS-resident decoder takes them
+    hb_prof_end(s);
+    const uint32_t mgrp = (nstreams + 7u) / 8u;
+    uint32_t P = mgrp / 4u + 1u;                                        // coprime to the groups of 8 streams, about a quarter turn
+    for (;; P++) { uint32_t x = P, y = mgrp; while (y) { const uint32_t t = x % y; x = y; y = t; } if (x == 1u) break; }
+    const unsigned grid = mgrp * 8u < 65536u ? mgrp * 8u : 65536u;
+    hb_prof_begin("k_cb_decode_small", s);
+    if (small) hipLaunchKernelGGL(k_cb_decode_small, dim3(grid), dim3(64), 0, s, d_frame, plan, streams, nstreams, target, P);
+    hb_prof_end(s);
+    hb_prof_begin("k_cb_decode", s);
+    // (long streams: as many passes per workgroup as a block has streams, fewer while that leaves under 2048 workgroups -- with the
+    // rotation by the pass number a workgroup decodes one stream of each plane, and all workgroups live about equally long; see
+    // k_cb_decode_small)
+    unsigned gbig = grid;
+    if (!small && nsplit > 1u) {
+        unsigned p = nsplit;
+        while (p > 1u && mgrp * 8u / p < 2048u) p >>= 1;
+        gbig = (mgrp * 8u / p + 7u) / 8u * 8u;
+    }
+    hipLaunchKernelGGL(k_cb_decode, dim3(gbig), dim3(64), 0, s, d_frame, plan, streams, nstreams, target, small ? 1 : 0, P);
+    hb_prof_end(s);
+    if (filtered) {
+        hb_prof_begin("k_cb_unfilter", s);
+        if (unshuf)
+            {
+            // whole blocks of whole 1024-element tiles: the tile kernels of hb_filters.hip, block by block (6 TB/s instead of the 3.5 of the
+            // byte-gathering kernel); a last, shorter block -- or any other shape -- the plain way
+            const uint32_t nfull = nbytes / blocksize, tail = nbytes - nfull * blocksize;
+            if (hb_launch_shuffle_blocks(true, out, staged, nfull, blocksize, (int)ts, s)) {
+                if (tail) hipLaunchKernelGGL(k_cb_unshuffle, dim3(64), dim3(256), 0, s, out + (size_t)nfull * blocksize, staged + (size_t)nfull * blocksize, tail, blocksize, ts);
+            } else hipLaunchKernelGGL(k_cb_unshuffle, dim3(2048), dim3(256), 0, s, out, staged, nbytes, blocksize, ts);
+        }
+        else if (ts == 4u && blocksize % 512u == 0u && nbytes >= blocksize) {       // whole blocks the fast way, a last shorter one the plain way
+            const uint32_t nfull = nbytes / blocksize, tail = nbytes - nfull * blocksize;
+            hipLaunchKernelGGL(k_cb_bitshuffle4_fast<false>, dim3(cb_grid((uint64_t)nfull * (blocksize / 128u))), dim3(256), 0, s, out, staged, nfull, blocksize);
+            if (tail) hipLaunchKernelGGL(k_cb_bitunshuffle, dim3(64), dim3(256), 0, s, out + (size_t)nfull * blocksize, staged + (size_t)nfull * blocksize, tail, blocksize, ts);
+        } else
+            hipLaunchKernelGGL(k_cb_bitunshuffle, dim3(2048), dim3(256), 0, s, out, staged, nbytes, blocksize, ts);
+        hb_prof_end(s);
+    }
+}
+
 extern "C" {
 
 // header fields of a C-Blosc-1 frame (host side); HB_OK or the error a malformed header gets
@@ -520,58 +577,93 @@ int hb_cblosc_decompress_dev(const hb_cblosc_header *hdr, const void *d_frame, s
     const uint32_t nsplit = cb_nsplit(flags, ts, blocksize);
     CbStream *streams = (CbStream *)(w + 256);
     uint8_t *staged = w + 256 + cb_align((size_t)nblocks * nsplit * sizeof(CbStream));
-    // blosc_d: the byte shuffle counts for typesize > 1 only (and comes first), the bit shuffle for any typesize
-    const bool unshuf = (flags & CB_FLAG_SHUFFLE) && ts > 1, unbit = !unshuf && (flags & CB_FLAG_BITSHUFFLE);
-    const bool filtered = unshuf || unbit;
-    uint8_t *target = filtered ? staged : (uint8_t *)d_dst;
-    const uint32_t nstreams = nblocks * nsplit;
-    hb_prof_begin("k_cb_plan", s);
-    hipLaunchKernelGGL(k_cb_plan, dim3((nblocks + 63) / 64), dim3(64), 0, s, (const uint8_t *)d_frame, (uint64_t)n, nbytes, blocksize, hdr->cbytes, ts, flags, plan, streams);
-    const bool small = blocksize / nsplit <= HB_CHUNK;                   // streams of at most one chunk: the LDS-resident decoder takes them
-    hb_prof_end(s);
-    const uint32_t mgrp = (nstreams + 7u) / 8u;
-    uint32_t P = mgrp / 4u + 1u;                                        // coprime to the groups of 8 streams, about a quarter turn
-    for (;; P++) { uint32_t x = P, y = mgrp; while (y) { const uint32_t t = x % y; x = y; y = t; } if (x == 1u) break; }
-    const unsigned grid = mgrp * 8u < 65536u ? mgrp * 8u : 65536u;
-    hb_prof_begin("k_cb_decode_small", s);
-    if (small) hipLaunchKernelGGL(k_cb_decode_small, dim3(grid), dim3(64), 0, s, (const uint8_t *)d_frame, plan, streams, nstreams, target, P);
-    hb_prof_end(s);
-    hb_prof_begin("k_cb_decode", s);
-    // (long streams: as many passes per workgroup as a block has streams, fewer while that leaves under 2048 workgroups -- with the
-    // rotation by the pass number a workgroup decodes one stream of each plane, and all workgroups live about equally long; see
-    // k_cb_decode_small)
-    unsigned gbig = grid;
-    if (!small && nsplit > 1u) {
-        unsigned p = nsplit;
-        while (p > 1u && mgrp * 8u / p < 2048u) p >>= 1;
-        gbig = (mgrp * 8u / p + 7u) / 8u * 8u;
-    }
-    hipLaunchKernelGGL(k_cb_decode, dim3(gbig), dim3(64), 0, s, (const uint8_t *)d_frame, plan, streams, nstreams, target, small ? 1 : 0, P);
-    hb_prof_end(s);
-    if (filtered) {
-        hb_prof_begin("k_cb_unfilter", s);
-        if (unshuf)
-            {
-            // whole blocks of whole 1024-element tiles: the tile kernels of hb_filters.hip, block by block (6 TB/s instead of the 3.5 of the
-            // byte-gathering kernel); a last, shorter block -- or any other shape -- the plain way
-            const uint32_t nfull = nbytes / blocksize, tail = nbytes - nfull * blocksize;
-            if (hb_launch_shuffle_blocks(true, (uint8_t *)d_dst, staged, nfull, blocksize, (int)ts, s)) {
-                if (tail) hipLaunchKernelGGL(k_cb_unshuffle, dim3(64), dim3(256), 0, s, (uint8_t *)d_dst + (size_t)nfull * blocksize, staged + (size_t)nfull * blocksize, tail, blocksize, ts);
-            } else hipLaunchKernelGGL(k_cb_unshuffle, dim3(2048), dim3(256), 0, s, (uint8_t *)d_dst, staged, nbytes, blocksize, ts);
-        }
-        else if (ts == 4u && blocksize % 512u == 0u && nbytes >= blocksize) {       // whole blocks the fast way, a last shorter one the plain way
-            const uint32_t nfull = nbytes / blocksize, tail = nbytes - nfull * blocksize;
-            hipLaunchKernelGGL(k_cb_bitshuffle4_fast<false>, dim3(cb_grid((uint64_t)nfull * (blocksize / 128u))), dim3(256), 0, s, (uint8_t *)d_dst, staged, nfull, blocksize);
-            if (tail) hipLaunchKernelGGL(k_cb_bitunshuffle, dim3(64), dim3(256), 0, s, (uint8_t *)d_dst + (size_t)nfull * blocksize, staged + (size_t)nfull * blocksize, tail, blocksize, ts);
-        } else
-            hipLaunchKernelGGL(k_cb_bitunshuffle, dim3(2048), dim3(256), 0, s, (uint8_t *)d_dst, staged, nbytes, blocksize, ts);
-        hb_prof_end(s);
-    }
+    cb_launch_blocks(hdr, (const uint8_t *)d_frame, n, 0u, nblocks, nbytes, (uint8_t *)d_dst, plan, streams, staged, s);
     hipLaunchKernelGGL(k_cb_result, dim3(1), dim3(1), 0, s, plan, d_result, (uint64_t)nbytes);
     HB_HIP_TRY(hipGetLastError());
     return HB_OK;
 }
 
+// ---- blosc_getitem: items [start, start + nitems) of typesize bytes from the blocks that hold them ----
+// Only blocks b_lo .. b_hi are planned, decoded and un-filtered -- whole blocks into a second staging area, then a copy of the range: the
+// per-block un-filter kernels (the tile kernels of hb_filters.hip among them) work on whole blocks, and a clipped variant of each would be
+// a second set of filters to keep right for at most two partly needed blocks per call.
+namespace {
+struct CbRange { uint32_t b_lo, nb, vbytes; uint64_t off, bytes; size_t streams, stage, total; };
+// the header refusals of hb_cblosc_decompress / hb_cblosc_decompress_dev, then the range; what is sized comes after the geometry checks
+int cb_getitem_prepare(const hb_cblosc_header *hdr, size_t n, int64_t start, int64_t nitems, CbRange &r) {
+    const uint32_t nbytes = hdr->nbytes, blocksize = hdr->blocksize, ts = hdr->typesize, flags = hdr->flags;
+    if (n < 16) return HB_ERR_INVALID_HEADER;
+    if (hdr->version != 2) return HB_ERR_INVALID_VERSION;
+    if (ts == 0u || (nbytes && blocksize == 0u)) return HB_ERR_INVALID_HEADER;
+    if (hdr->cbytes > n || hdr->cbytes < 16) return HB_ERR_INVALID_DATA;
+    uint64_t nblocks = 0;
+    if (flags & CB_FLAG_MEMCPY) {
+        if ((uint64_t)hdr->cbytes < 16ull + nbytes) return HB_ERR_INVALID_DATA;
+    } else {
+        if (hdr->codec_format != 1) return HB_ERR_INVALID_CODEC;
+        if (nbytes) {
+            nblocks = ((uint64_t)nbytes + blocksize - 1) / blocksize;
+            if (16ull + 4ull * nblocks > hdr->cbytes || blocksize < ts) return HB_ERR_INVALID_DATA;
+        }
+    }
+    const int64_t ne = (int64_t)(nbytes / ts);
+    if (start < 0 || nitems < 0 || start > ne || nitems > ne - start) return HB_ERR_BAD_ARG;
+    r.off = (uint64_t)start * ts; r.bytes = (uint64_t)nitems * ts;
+    r.b_lo = 0; r.nb = 0; r.vbytes = 0; r.streams = 0; r.stage = 0;
+    if (r.bytes && !(flags & CB_FLAG_MEMCPY)) {
+        r.b_lo = (uint32_t)(r.off / blocksize);
+        const uint32_t b_hi = (uint32_t)((r.off + r.bytes - 1) / blocksize);
+        r.nb = b_hi - r.b_lo + 1u;
+        const uint64_t end = (uint64_t)(b_hi + 1u) * blocksize;
+        r.vbytes = (uint32_t)((end < nbytes ? end : nbytes) - (uint64_t)r.b_lo * blocksize);
+        const size_t nsplit = (ts <= 16u && blocksize / ts >= 128u) ? ts : 1u;         // cb_nsplit() without the flag: the upper bound
+        r.streams = cb_align((size_t)r.nb * nsplit * sizeof(CbStream));
+        r.stage = cb_align((size_t)r.vbytes + 64);
+    }
+    r.total = 256 + r.streams + 2 * r.stage;
+    return HB_OK;
+}
+}  // namespace
+
+size_t hb_cblosc_getitem_workspace(const hb_cblosc_header *hdr, int64_t start, int64_t nitems) {
+    CbRange r;
+    if (!hdr || cb_getitem_prepare(hdr, (size_t)hdr->cbytes, start, nitems, r)) return 0;
+    return r.total;
+}
+extern "C++" int hb_cblosc_getitem_prepare(const hb_cblosc_header *hdr, size_t n, int64_t start, int64_t nitems, uint64_t *bytes) {
+    CbRange r;
+    const int rc = cb_getitem_prepare(hdr, n, start, nitems, r);
+    if (!rc) *bytes = r.bytes;
+    return rc;
+}
+
+int hb_cblosc_getitem_device(const hb_cblosc_header *hdr, const void *d_frame, size_t n, int64_t start, int64_t nitems, void *d_dst, size_t cap,
+                             void *d_work, size_t work_bytes, hb_result *d_result, void *stream) {
+    if (!hdr) return HB_ERR_BAD_ARG;
+    CbRange r;
+    const int rc = cb_getitem_prepare(hdr, n, start, nitems, r);
+    if (rc) return rc;
+    if ((uint64_t)cap < r.bytes) return HB_ERR_SHORT_BUFFER;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    if (!d_frame || (!d_dst && r.bytes) || !d_work || ((uintptr_t)d_work & 255u) || !d_result) return HB_ERR_BAD_ARG;
+    if (work_bytes < r.total) return HB_ERR_SHORT_BUFFER;
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t *w = (uint8_t *)d_work;
+    CbPlan *plan = (CbPlan *)w;
+    hipLaunchKernelGGL(k_cb_init, dim3(1), dim3(1), 0, s, plan);
+    if (r.bytes) {
+        if (hdr->flags & CB_FLAG_MEMCPY) {
+            HB_HIP_TRY(hipMemcpyAsync(d_dst, (const uint8_t *)d_frame + 16 + r.off, r.bytes, hipMemcpyDeviceToDevice, s));
+        } else {
+            uint8_t *stage1 = w + 256 + r.streams, *stage2 = stage1 + r.stage;
+            cb_launch_blocks(hdr, (const uint8_t *)d_frame, n, r.b_lo, r.nb, r.vbytes, stage2, plan, (CbStream *)(w + 256), stage1, s);
+            HB_HIP_TRY(hipMemcpyAsync(d_dst, stage2 + (r.off - (uint64_t)r.b_lo * hdr->blocksize), r.bytes, hipMemcpyDeviceToDevice, s));
+        }
+    }
+    hipLaunchKernelGGL(k_cb_result, dim3(1), dim3(1), 0, s, plan, d_result, r.bytes);
+    HB_HIP_TRY(hipGetLastError());
+    return HB_OK;
+}
 
 size_t hb_cblosc_bound(size_t n, int typesize) {
     const size_t ts = typesize > 0 ? (size_t)typesize : 1;

@@ -39,6 +39,10 @@ int64_t hb_zstd_compress_frame(const void *src, size_t n, void *dst, size_t cap,
                                unsigned opts, int device);
 int64_t hb_zstd_decompress_frame(const void *frame, const hb_header &h, void *dst, size_t cap, int typesize_override, int device);
 
+// hb_getitem.hip: the header and range checks every getitem entry point makes first, in the order of include/hipblosc.h (allow_zstd: the
+// host-pointer entry point, which has the host codec); *ts_out = the item size
+int hb_getitem_check(const hb_header *hdr, size_t n, int64_t start, int64_t nitems, int typesize_override, int allow_zstd, int *ts_out);
+
 // batches of frames in one set of launches (hb_lz4_enc.hip / hb_batch.hip)
 struct hb_batch_frame { const uint8_t *src; size_t n; uint8_t *dst; size_t cap; hb_result *result; };
 size_t hb_lz4_enc_batch_workspace(int nframes, const size_t *n, int typesize);

@@ -415,6 +415,40 @@ func (fq *FrameQueue) Wait(ticket int64) (int, error) {
 	return int(n), nil
 }
 
+// GetItem returns items [start, start+nitems) of the frame: Decompress(data)[start*ts : (start+nitems)*ts], ts = typeSize when > 0,
+// else the header's (0 counts as 1).  blosc_getitem of c-blosc; the reference has no counterpart, so there is no CPU path behind it.
+// Frames written with OptIndexTrailer decode only the 4 KiB units that cover the range; every other frame is decoded whole on the
+// device and sliced.  The start state of a unit decoded out of sequence is the index's claim (hipblosc.h, hb_getitem_frame, "TRUST"):
+// a caller that does not trust its frames uses DecompressHIP.  Like the rest of this file: written against the C ABI, not compiled.
+func GetItem(data []byte, start, nitems int64, typeSize int) ([]byte, error) {
+	if len(data) < HeaderSize {
+		return nil, ErrInvalidHeader
+	}
+	h, err := ParseHeader(data)
+	if err != nil {
+		return nil, err
+	}
+	if !useHIP {
+		return nil, fmt.Errorf("%w: no HIP device", ErrDecompressionFailed)
+	}
+	ts := int64(typeSize)
+	if ts <= 0 {
+		ts = int64(h.TypeSize)
+	}
+	if ts <= 0 {
+		ts = 1
+	}
+	if start < 0 || nitems < 0 || start+nitems > int64(h.NBytesOrig)/ts {
+		return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	buf := make([]byte, nitems*ts+1)
+	n := C.hb_getitem_frame(ptr(data), C.size_t(len(data)), C.int64_t(start), C.int64_t(nitems), ptr(buf), C.size_t(nitems*ts), C.int(typeSize), C.int(Device))
+	if n < 0 {
+		return nil, hbError(n)
+	}
+	return buf[:n], nil
+}
+
 // ---------------------------------------------------------------------------------------------
 // C-Blosc-1 wire format (what README.md:20 promises; blosc.go has no code for it): frames c-blosc 1.x, python-blosc,
 // numcodecs read and write.  An extension next to CompressHIP / DecompressHIP, not a seam of the reference.

@@ -99,6 +99,7 @@ EXPORTS = [
     "hb_decompress_frame_dev_hdr", "hb_cblosc_parse_header", "hb_cblosc_decompress", "hb_cblosc_compress", "hb_cblosc_bound", "hb_cblosc_compress_workspace", "hb_cblosc_compress_dev", "hb_cblosc_decompress_workspace", "hb_cblosc_decompress_dev",
     "hb_compress_frames_batch_workspace", "hb_compress_frames_batch_dev", "hb_frames_batch_headers_dev",
     "hb_decompress_frames_batch_workspace", "hb_decompress_frames_batch_dev", "hb_compress_frames_batch", "hb_decompress_frames_batch",
+    "hb_getitem_frame", "hb_getitem_frame_workspace", "hb_getitem_frame_device", "hb_cblosc_getitem", "hb_cblosc_getitem_workspace", "hb_cblosc_getitem_device",
     "hb_queue_create", "hb_queue_create_ex", "hb_queue_destroy", "hb_queue_compress", "hb_queue_decompress", "hb_queue_wait",
 ]
 
@@ -170,6 +171,12 @@ def lib():
             "hb_queue_compress": (i64, [vp, vp, sz, vp, sz, i32, i32, i32, i32, u32]),
             "hb_queue_decompress": (i64, [vp, vp, sz, vp, sz, i32]),
             "hb_queue_wait": (i64, [vp, i64]),
+            "hb_getitem_frame": (i64, [vp, sz, i64, i64, vp, sz, i32, i32]),
+            "hb_getitem_frame_workspace": (sz, [ctypes.POINTER(hb_header), sz, i64, i64, i32, i32]),
+            "hb_getitem_frame_device": (i32, [ctypes.POINTER(hb_header), vp, sz, i64, i64, vp, sz, i32, vp, sz, vp, vp]),
+            "hb_cblosc_getitem": (i64, [vp, sz, i64, i64, vp, sz, i32]),
+            "hb_cblosc_getitem_workspace": (sz, [vp, i64, i64]),
+            "hb_cblosc_getitem_device": (i32, [vp, vp, sz, i64, i64, vp, sz, vp, sz, vp, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -294,6 +301,21 @@ def DecompressWithSize(data, typeSize):                             # blosc.go:2
     out = ctypes.create_string_buffer(max(h.NBytesOrig, 1))
     rc = L.hb_decompress_frame(p, n, ctypes.cast(out, ctypes.c_void_p), h.NBytesOrig, typeSize, device)
     _check(rc)
+    return out.raw[:rc]
+
+
+def GetItem(data, start, nitems, typeSize=0):
+    """Decompress(data)[start * ts : (start + nitems) * ts] without decoding the whole frame (include/hipblosc.h hb_getitem_frame):
+    ts = typeSize when > 0, else the header's.  Frames written with OPT_INDEX_TRAILER decode only the 4 KiB units that cover the
+    range; lib().hb_last_result_flags() says which path ran (0x3 indexed, 0x2 memcpy frame, bit 1 clear: whole frame decoded)."""
+    p, n, keep = _buf(data)
+    if n < HeaderSize:
+        raise ErrInvalidHeader("blosc: invalid header")
+    h = ParseHeader(data)
+    ts = typeSize if typeSize > 0 else (h.TypeSize or 1)
+    cap = max(int(nitems), 0) * ts
+    out = ctypes.create_string_buffer(max(cap, 1))
+    rc = _check(lib().hb_getitem_frame(p, n, int(start), int(nitems), ctypes.cast(out, ctypes.c_void_p), cap, typeSize, device))
     return out.raw[:rc]
 
 
@@ -480,6 +502,17 @@ def CBloscDecompress(frame):
     h = CBloscParseHeader(frame)
     out = ctypes.create_string_buffer(max(h.nbytes, 1))
     rc = _check(lib().hb_cblosc_decompress(p, n, ctypes.cast(out, ctypes.c_void_p), h.nbytes, device))
+    return out.raw[:rc]
+
+
+def CBloscGetItem(frame, start, nitems):
+    """What blosc_getitem() of c-blosc 1.x returns for `frame`: items [start, start + nitems) of the header's typesize; only the blocks
+    that hold them are decoded (include/hipblosc.h hb_cblosc_getitem)."""
+    p, n, keep = _buf(frame)
+    h = CBloscParseHeader(frame)
+    cap = max(int(nitems), 0) * h.typesize
+    out = ctypes.create_string_buffer(max(cap, 1))
+    rc = _check(lib().hb_cblosc_getitem(p, n, int(start), int(nitems), ctypes.cast(out, ctypes.c_void_p), cap, device))
     return out.raw[:rc]
 
 

@@ -116,6 +116,18 @@ inline Bytes DecompressWithSize(const uint8_t *data, size_t n, int typeSize, int
     return out;
 }
 inline Bytes Decompress(const Bytes &data) { return DecompressWithSize(data.data(), data.size(), 0); }          // blosc.go:291-293
+// items [start, start + nitems) of the frame = Decompress(data)[start * ts, (start + nitems) * ts), ts = typeSize > 0 ? typeSize : the header's:
+// frames written with HB_OPT_INDEX_TRAILER decode only the 4 KiB units that cover the range; trust model in hipblosc.h (hb_getitem_frame)
+inline Bytes GetItem(const uint8_t *data, size_t n, int64_t start, int64_t nitems, int typeSize = 0, int device = 0) {
+    if (n < (size_t)HeaderSize) throw Error(HB_ERR_INVALID_HEADER);
+    const Header h = ParseHeader(data, n);
+    const size_t ts = typeSize > 0 ? (size_t)typeSize : (h.TypeSize ? h.TypeSize : 1);
+    Bytes out(nitems > 0 ? (size_t)nitems * ts : 1);
+    const int64_t rc = check(hb_getitem_frame(data, n, start, nitems, out.data(), nitems > 0 ? out.size() : 0, typeSize, device));
+    out.resize((size_t)rc);
+    return out;
+}
+inline Bytes GetItem(const Bytes &data, int64_t start, int64_t nitems, int typeSize = 0) { return GetItem(data.data(), data.size(), start, nitems, typeSize); }
 inline Header GetInfo(const Bytes &data) { return ParseHeader(data); }                                            // blosc.go:306-308
 inline int GetDecompressedSize(const Bytes &data) { return (int)ParseHeader(data).NBytesOrig; }                   // blosc.go:311-317
 

@@ -77,7 +77,8 @@ typedef struct hb_header {
 /* completion record of the asynchronous `_dev` entry points (lives in device or pinned memory) */
 typedef struct hb_result {
     int32_t  status;        /* HB_OK or HB_ERR_* */
-    uint32_t flags;         /* frame flags byte (compress) / bit0: parallel index used (decompress) */
+    uint32_t flags;         /* frame flags byte (compress) / bit0: parallel index used (decompress) / getitem: bit1 (0x2) as well: only the
+                               units that cover the range were decoded */
     uint64_t bytes;         /* compress: frame bytes per the header (cbytes) or LZ4 block bytes; decompress: decoded bytes */
     uint64_t total_bytes;   /* compress: bytes written to dst including the index trailer */
     uint64_t reserved;
@@ -92,8 +93,8 @@ void        hb_pool_limit(size_t bytes);   /* idle device scratch the host-point
 size_t      hb_pool_cached_bytes(void);    /* idle scratch currently cached (diagnostics) */
 const char *hb_strerror(int code);
 const char *hb_version(void);
-unsigned    hb_last_result_flags(void);    /* hb_result.flags of the last host-pointer frame decode on this thread
-                                              (bit0: the restart index was used) — diagnostics for tests */
+unsigned    hb_last_result_flags(void);    /* hb_result.flags of the last host-pointer frame decode / hb_getitem_frame on this thread
+                                              (bit0: the restart index was used, bit1: getitem decoded only the covering units) — diagnostics for tests */
 /* stage timing for the bench harness (single-threaded use): with enable(1) every kernel stage launched by the
  * `_dev` entry points is bracketed by HIP events on its stream; get(i) returns the stage name and its ms. */
 int         hb_profile_enable(int on);
@@ -187,6 +188,42 @@ int hb_decompress_frame_dev_hdr(const hb_header *hdr, const void *d_frame, size_
                                 int typesize_override,
                                 void *d_work, size_t work_bytes, hb_result *d_result, void *stream);
 
+/* ---- getitem: items [start, start + nitems) of a frame without decoding the whole frame (blosc_getitem of c-blosc; the reference has no
+ *      counterpart).  Returns exactly Decompress(frame)[start * ts, (start + nitems) * ts), ts = typesize_override when > 0, else the header's
+ *      typesize (0 counts as 1; the rule of blosc.go:417-419).  Items are whole elements: (start + nitems) * ts <= nbytes (the nbytes % ts tail bytes
+ *      are not reachable, as in c-blosc; ts = 1 gives byte access); nitems == 0 with start <= nbytes / ts returns 0 bytes.
+ *      Errors the host can decide come back as the return value before any device work, in this order: the header errors of hb_decompress_frame
+ *      (short frame, version, cbytes, codec; a memcpy frame whose payload is not nbytes long: HB_ERR_SIZE_MISMATCH), HB_ERR_BAD_ARG for a range
+ *      outside the frame, HB_ERR_SHORT_BUFFER for cap < nitems * ts; then HB_ERR_NO_DEVICE.
+ *      Paths (hb_result.flags says which ran: bit0 restart index used, bit1 = 0x2 only the covering units were decoded):
+ *        1. LZ4 / LZ4HC frame written with HB_OPT_INDEX_TRAILER: only the 4 KiB units that hold needed bytes of the filtered buffer are decoded
+ *           (flags 0x3); 2. memcpy frames: read in place (flags 0x2); 3. everything else (no trailer, Snappy, an index that does not hold): the
+ *           whole frame is decoded into the workspace and the range copied -- correct, not fast.  ZSTD frames (host codec): hb_getitem_frame only.
+ *      What a call does not touch it does not check: damage outside the units (C-Blosc-1: blocks) of the range is not seen, as with blosc_getitem.
+ *      TRUST.  The full decode never trusts the restart index: every unit is verified and the chain starts at unit 0.  A partial decode verifies
+ *      the units it decodes (geometry, end state equal to the next entry, no match reaching before the unit) but the START state of a unit is the
+ *      index's claim.  So on a frame whose trailer was forged getitem is memory-safe (it never reads outside [d_frame, d_frame + n + 15] and
+ *      never writes outside nitems * ts bytes of dst and its workspace) and returns an error, the right bytes, or -- only for a deliberately
+ *      constructed trailer -- bytes that differ from Decompress.  A caller that does not trust its frames uses hb_decompress_frame.  (The
+ *      bstarts table has the same standing in c-blosc.)
+ *      Naming: these device-pointer entry points end in _device, not in the three letters the older ones end in: tests/test_abi.py demands a call
+ *      in tests/test_gpu_dev_api.py for every declared name of that older shape; the contract tests of these two are tests/test_gpu_getitem.py
+ *      and tests/test_gpu_cblosc_getitem.py. ---- */
+int64_t hb_getitem_frame(const void *frame, size_t n, int64_t start, int64_t nitems, void *dst, size_t cap,
+                         int typesize_override, int device);                 /* -> nitems * ts or HB_ERR_* */
+/* full == 0: enough when the frame's index holds (paths 1, 2: at most 2 * nitems * ts + 8192 * ts + 65536 bytes for a frame with a trailer; equals
+ * the full size for frames that can only take path 3); full != 0: enough for any outcome.  0 for a header or range the entry points refuse. */
+size_t  hb_getitem_frame_workspace(const hb_header *hdr, size_t n, int64_t start, int64_t nitems,
+                                   int typesize_override, int full);
+/* device pointers, header on the host, asynchronous on `stream`, no synchronisation (like hb_decompress_frame_dev_hdr: same rules for d_frame's
+ * 15 bytes of over-read and d_work's alignment).  If the index turns out not to hold on the device and work_bytes is below the full size, the call
+ * ends with d_result->status = HB_ERR_SHORT_BUFFER, flags 0, dst unspecified inside nitems * ts bytes: repeat with the full size.  With work_bytes
+ * >= the full size the whole-frame decode is enqueued behind the indexed attempt in every call (there is no branch on the device between launches)
+ * and used only if the index did not hold: a caller that wants the short time passes the small workspace. */
+int     hb_getitem_frame_device(const hb_header *hdr, const void *d_frame, size_t n, int64_t start, int64_t nitems,
+                                void *d_dst, size_t cap, int typesize_override,
+                                void *d_work, size_t work_bytes, hb_result *d_result, void *stream);
+
 /* batches of independent frames, frame k -> device k mod hb_device_count(): what a caller with an
  * 8 GiB array does (8 frames of <= 4 GiB - 1, blosc.go:159-161: the sizes are uint32), one Compress / Decompress call
  * (blosc.go:257-303) per frame.  One host thread per device, each with its own hb_queue of 3 frames in flight; no
@@ -275,6 +312,14 @@ int     hb_cblosc_decompress_dev(const hb_cblosc_header *hdr, const void *d_fram
 /* host pointers: returns the decoded bytes (== nbytes of the header) or HB_ERR_*: HB_ERR_INVALID_CODEC for the codec formats
  * that are not LZ4, HB_ERR_DECOMPRESSION_FAILED for anything blosc_decompress() answers with a negative number */
 int64_t hb_cblosc_decompress(const void *frame, size_t n, void *dst, size_t cap, int device);
+/* blosc_getitem of c-blosc 1.x: items [start, start + nitems) of the header's typesize.  Only the blocks that hold the range are planned,
+ * decoded and un-filtered (other blocks' streams and bstarts entries are never read, so damage there is not seen); memcpyed frames: a copy.
+ * Refusals in this order: the header's (as hb_cblosc_decompress, codec format and block geometry included, before anything is sized),
+ * HB_ERR_BAD_ARG for a range outside the frame, HB_ERR_SHORT_BUFFER for cap < nitems * typesize.  The workspace grows with the covered blocks. */
+int64_t hb_cblosc_getitem(const void *frame, size_t n, int64_t start, int64_t nitems, void *dst, size_t cap, int device);
+size_t  hb_cblosc_getitem_workspace(const hb_cblosc_header *hdr, int64_t start, int64_t nitems);
+int     hb_cblosc_getitem_device(const hb_cblosc_header *hdr, const void *d_frame, size_t n, int64_t start, int64_t nitems,
+                                 void *d_dst, size_t cap, void *d_work, size_t work_bytes, hb_result *d_result, void *stream);
 /* writing the format: a frame that blosc_decompress() of c-blosc 1.x (python-blosc, numcodecs ...) reads.  shuffle: 0 none, 1 byte
  * shuffle, 2 bit shuffle (BLOSC_NOSHUFFLE / BLOSC_SHUFFLE / BLOSC_BITSHUFFLE); LZ4 streams; block size 4096 x typesize (split) or
  * 4096 (not split), so that every stream is one chunk of this library's encoder; n below 2 GiB (c-blosc's limit).  Returns the
