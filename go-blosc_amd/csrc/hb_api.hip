@@ -2,7 +2,7 @@
 // host-pointer entry points (stage H2D -> kernels -> D2H) and the thin `_dev` wrappers.
 // No CPU fallback anywhere: without a HIP device every compute entry point fails loudly.
 #include "hb_common.h"
-#include "hb_lz4.h"
+#include "hb_frame_plan.h"
 
 #include <atomic>
 #include <mutex>
@@ -78,19 +78,6 @@ void pool_put(int dev, void *p, size_t bytes) {
     pool_trim_locked(g_pool_limit);
 }
 
-struct Scratch {     // RAII over pool buffers for one host-API call
-    int dev;
-    std::vector<std::pair<void *, size_t>> held;
-    explicit Scratch(int d) : dev(d) {}
-    uint8_t *get(size_t bytes) {
-        size_t got = 0;
-        void *p = pool_get(dev, bytes, &got);
-        if (p) held.push_back({p, got});
-        return (uint8_t *)p;
-    }
-    ~Scratch() { for (auto &h : held) pool_put(dev, h.first, h.second); }
-};
-
 int select_device(int device) {
     std::call_once(g_once, do_init);
     if (g_ndev <= 0) return HB_ERR_NO_DEVICE;
@@ -111,6 +98,36 @@ thread_local unsigned g_last_flags = 0;   // hb_result.flags of the last host-po
 bool overlap(const void *a, size_t na, const void *b, size_t nb) {
     const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
     return x < y + nb && y < x + na;
+}
+
+// ---- one host-pointer call: pool buffers (input, output, workspace, result record -- always taken in this order), upload, launch, the
+// result record back, its status as the return value, else the download of what it says was produced.  `launch(d_in, d_out, d_work, d_res)`
+// enqueues on the null stream and returns an HB_ERR_* or HB_OK; the read-back of the record synchronises with it.  The entry points keep
+// their own argument checks, their device selection, and the sizes: `up` bytes of `src` go up into a buffer of `in_bytes` (the slack
+// behind the data is what the kernels' wide loads may touch), `out_bytes` and `work_bytes` are the other two buffers. ----
+enum StagedOut {
+    OUT_BYTES,            // r.bytes from the start of the output buffer
+    OUT_TOTAL_BYTES,      // r.total_bytes: a frame with its index trailer (HB_OPT_INDEX_TRAILER)
+    OUT_PAYLOAD           // r.bytes - 16 from behind the 16 header bytes: the bare block inside a frame (hb_codec_compress)
+};
+template <class Launch>
+int64_t staged_call(int device, const void *src, size_t up, size_t in_bytes, void *dst, size_t cap, size_t out_bytes, size_t work_bytes,
+                    Launch launch, StagedOut what = OUT_BYTES, bool keep_flags = false) {
+    Scratch sc(device);
+    uint8_t *d_in = sc.get(in_bytes), *d_out = sc.get(out_bytes), *d_work = sc.get(work_bytes), *d_res = sc.get(sizeof(hb_result));
+    if (!d_in || !d_out || !d_work || !d_res) return HB_ERR_HIP;
+    if (up) HB_HIP_TRY(hipMemcpy(d_in, src, up, hipMemcpyHostToDevice));
+    const int rc = launch(d_in, d_out, d_work, (hb_result *)d_res);
+    if (rc) return rc;
+    hb_result r;
+    HB_HIP_TRY(hipMemcpy(&r, d_res, sizeof r, hipMemcpyDeviceToHost));
+    if (keep_flags) g_last_flags = r.flags;                           // (hb_last_result_flags(): of a failed decode too)
+    if (r.status) return r.status;
+    const size_t off = what == OUT_PAYLOAD ? HB_HEADER_SIZE : 0;
+    const size_t len = (what == OUT_TOTAL_BYTES ? (size_t)r.total_bytes : (size_t)r.bytes) - off;
+    if (len > cap) return HB_ERR_SHORT_BUFFER;                        // (a decoder never produces more than the capacity it was launched with)
+    if (len) HB_HIP_TRY(hipMemcpy(dst, d_out + off, len, hipMemcpyDeviceToHost));
+    return (int64_t)len;
 }
 
 }  // namespace
@@ -229,7 +246,7 @@ int hb_filter(int op, void *dst, const void *src, size_t n, int typesize, int de
     if (op < 0 || op > 3) return HB_ERR_BAD_ARG;
     if (n == 0) return HB_OK;
     if (!dst || !src || overlap(dst, n, src, n)) return HB_ERR_BAD_ARG;
-    Scratch sc(device);
+    Scratch sc(device);                                               // (no workspace and no result record: not a staged_call)
     uint8_t *d_src = sc.get(n), *d_dst = sc.get(n);
     if (!d_src || !d_dst) return HB_ERR_HIP;
     HB_HIP_TRY(hipMemcpy(d_src, src, n, hipMemcpyHostToDevice));
@@ -250,7 +267,7 @@ int hb_lz4_compress_dev(const void *d_src, size_t n, void *d_dst, size_t cap, vo
                         void *d_work, size_t work_bytes, hb_result *d_result, void *stream) {
     if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
     if (!d_src || !d_dst || !d_work || ((uintptr_t)d_work & 255u) || !d_result) return HB_ERR_BAD_ARG;
-    if (n > 0xFFFFFFFFull - n / 255 - 64) return HB_ERR_DATA_TOO_LARGE;
+    if (hb_block_too_large(n)) return HB_ERR_DATA_TOO_LARGE;
     if (cap < hb_lz4_bound(n)) return HB_ERR_SHORT_BUFFER;
     if (work_bytes < hb_lz4_enc_workspace(n)) return HB_ERR_SHORT_BUFFER;
     if (d_index && index_cap < hb_lz4_index_bound(n)) return HB_ERR_SHORT_BUFFER;
@@ -278,21 +295,12 @@ int64_t hb_lz4_compress(const void *src, size_t n, void *dst, size_t cap, int de
     int rc = select_device(device);
     if (rc) return rc;
     if ((!src && n) || !dst) return HB_ERR_BAD_ARG;
-    if (n > 0xFFFFFFFFull - n / 255 - 64) return HB_ERR_DATA_TOO_LARGE;
+    if (hb_block_too_large(n)) return HB_ERR_DATA_TOO_LARGE;
     if (cap < hb_lz4_bound(n)) return HB_ERR_SHORT_BUFFER;
-    Scratch sc(device);
-    const size_t wb = hb_lz4_enc_workspace(n);
-    uint8_t *d_src = sc.get(n + 16), *d_dst = sc.get(hb_lz4_bound(n) + 64), *d_work = sc.get(wb), *d_res = sc.get(sizeof(hb_result));
-    if (!d_src || !d_dst || !d_work || !d_res) return HB_ERR_HIP;
-    if (n) HB_HIP_TRY(hipMemcpy(d_src, src, n, hipMemcpyHostToDevice));
-    rc = hb_lz4_compress_dev(d_src, n, d_dst, hb_lz4_bound(n) + 64, nullptr, 0, d_work, wb, (hb_result *)d_res, nullptr);
-    if (rc) return rc;
-    hb_result r;
-    HB_HIP_TRY(hipMemcpy(&r, d_res, sizeof r, hipMemcpyDeviceToHost));
-    if (r.status) return r.status;
-    if (r.bytes > cap) return HB_ERR_SHORT_BUFFER;
-    HB_HIP_TRY(hipMemcpy(dst, d_dst, r.bytes, hipMemcpyDeviceToHost));
-    return (int64_t)r.bytes;
+    const size_t ob = hb_lz4_bound(n) + 64, wb = hb_lz4_enc_workspace(n);
+    return staged_call(device, src, n, n + 16, dst, cap, ob, wb, [&](uint8_t *d_src, uint8_t *d_dst, uint8_t *d_work, hb_result *d_res) {
+        return hb_lz4_compress_dev(d_src, n, d_dst, ob, nullptr, 0, d_work, wb, d_res, nullptr);
+    });
 }
 
 int64_t hb_lz4_decompress(const void *src, size_t n, void *dst, size_t cap, int device) {
@@ -300,18 +308,10 @@ int64_t hb_lz4_decompress(const void *src, size_t n, void *dst, size_t cap, int 
     if (rc) return rc;
     if ((!src && n) || (!dst && cap)) return HB_ERR_BAD_ARG;
     if (n == 0) return 0;                                             // UncompressBlock: empty src -> 0, nil
-    Scratch sc(device);
     const size_t wb = hb_indexless_parallel(n, cap) ? hb_lz4_decompress_workspace_foreign(cap) : hb_lz4_dec_workspace(cap);   // (a bare block never has an index)
-    uint8_t *d_src = sc.get(n + 64), *d_dst = sc.get(cap + 64), *d_work = sc.get(wb), *d_res = sc.get(sizeof(hb_result));
-    if (!d_src || !d_dst || !d_work || !d_res) return HB_ERR_HIP;
-    HB_HIP_TRY(hipMemcpy(d_src, src, n, hipMemcpyHostToDevice));
-    rc = hb_lz4_decompress_dev(d_src, n, d_dst, cap, nullptr, 0, d_work, wb, (hb_result *)d_res, nullptr);
-    if (rc) return rc;
-    hb_result r;
-    HB_HIP_TRY(hipMemcpy(&r, d_res, sizeof r, hipMemcpyDeviceToHost));
-    if (r.status) return r.status;
-    if (r.bytes) HB_HIP_TRY(hipMemcpy(dst, d_dst, r.bytes, hipMemcpyDeviceToHost));
-    return (int64_t)r.bytes;
+    return staged_call(device, src, n, n + 64, dst, cap, cap + 64, wb, [&](uint8_t *d_src, uint8_t *d_dst, uint8_t *d_work, hb_result *d_res) {
+        return hb_lz4_decompress_dev(d_src, n, d_dst, cap, nullptr, 0, d_work, wb, d_res, nullptr);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -329,24 +329,14 @@ int64_t hb_codec_compress(int codec, int level, const void *src, size_t n, void 
         *(uint8_t *)dst = 0;
         return 1;
     }
-    if (n > 0xFFFFFFFFull - HB_HEADER_SIZE - n / 255 - 64) return HB_ERR_DATA_TOO_LARGE;
+    if (hb_frame_too_large(n)) return HB_ERR_DATA_TOO_LARGE;
     int rc = select_device(device);
     if (rc) return rc;
-    Scratch sc(device);
-    const size_t fb = hb_frame_bound(n), wb = hb_compress_frame_workspace(n);
-    uint8_t *d_src = sc.get(n + 16), *d_frame = sc.get(fb + 64), *d_work = sc.get(wb), *d_res = sc.get(sizeof(hb_result));
-    if (!d_src || !d_frame || !d_work || !d_res) return HB_ERR_HIP;
-    HB_HIP_TRY(hipMemcpy(d_src, src, n, hipMemcpyHostToDevice));
+    const size_t fb = hb_frame_bound(n) + 64, wb = hb_compress_frame_workspace(n);
     // the frame path without a filter and without the memcpy rule: the payload behind the 16 header bytes is the block
-    rc = hb_compress_frame_dev(d_src, n, d_frame, fb + 64, codec, level, HB_NOSHUFFLE, 1, HB_OPT_INTERNAL_BLOCK, d_work, wb, (hb_result *)d_res, nullptr);
-    if (rc) return rc;
-    hb_result r;
-    HB_HIP_TRY(hipMemcpy(&r, d_res, sizeof r, hipMemcpyDeviceToHost));
-    if (r.status) return r.status;
-    const size_t c = (size_t)r.bytes - HB_HEADER_SIZE;
-    if (c > cap) return HB_ERR_SHORT_BUFFER;
-    HB_HIP_TRY(hipMemcpy(dst, d_frame + HB_HEADER_SIZE, c, hipMemcpyDeviceToHost));
-    return (int64_t)c;
+    return staged_call(device, src, n, n + 16, dst, cap, fb, wb, [&](uint8_t *d_src, uint8_t *d_frame, uint8_t *d_work, hb_result *d_res) {
+        return hb_compress_frame_dev(d_src, n, d_frame, fb, codec, level, HB_NOSHUFFLE, 1, HB_OPT_INTERNAL_BLOCK, d_work, wb, d_res, nullptr);
+    }, OUT_PAYLOAD);
 }
 
 int64_t hb_codec_decompress(int codec, const void *src, size_t n, void *dst, size_t cap, int device) {
@@ -356,22 +346,15 @@ int64_t hb_codec_decompress(int codec, const void *src, size_t n, void *dst, siz
     if (n == 0) return HB_ERR_DECOMPRESSION_FAILED;                     // snappy.Decode of an empty slice: corrupt (no length)
     int rc = select_device(device);
     if (rc) return rc;
-    Scratch sc(device);
     const bool par = hb_indexless_parallel(n, cap);                   // (a bare block never has an index: room for the symbolic decoder when it is worth it)
     const size_t wb = par ? hb_lz4_decompress_workspace_foreign(cap) : hb_lz4_dec_workspace(cap);
-    uint8_t *d_src = sc.get(n + 64), *d_dst = sc.get(cap + 64), *d_work = sc.get(wb), *d_res = sc.get(sizeof(hb_result));
-    if (!d_src || !d_dst || !d_work || !d_res) return HB_ERR_HIP;
-    HB_HIP_TRY(hipMemcpy(d_src, src, n, hipMemcpyHostToDevice));
-    hb_dec_args a{};
-    a.src = d_src; a.n = n; a.dst = d_dst; a.cap = cap; a.work = d_work; a.result = (hb_result *)d_res; a.frame = 0;
-    if (par) a.sym_work = d_work + ((hb_lz4_dec_workspace(cap) + 255) & ~(size_t)255);
-    rc = hb_launch_snappy_decode(a, nullptr);
-    if (rc) return rc;
-    hb_result r;
-    HB_HIP_TRY(hipMemcpy(&r, d_res, sizeof r, hipMemcpyDeviceToHost));
-    if (r.status) return r.status;                                      // (a declared length above cap: HB_ERR_SHORT_BUFFER)
-    if (r.bytes) HB_HIP_TRY(hipMemcpy(dst, d_dst, r.bytes, hipMemcpyDeviceToHost));
-    return (int64_t)r.bytes;
+    // (a declared length above cap comes back as the record's status: HB_ERR_SHORT_BUFFER)
+    return staged_call(device, src, n, n + 64, dst, cap, cap + 64, wb, [&](uint8_t *d_src, uint8_t *d_dst, uint8_t *d_work, hb_result *d_res) {
+        hb_dec_args a{};
+        a.src = d_src; a.n = n; a.dst = d_dst; a.cap = cap; a.work = d_work; a.result = d_res; a.frame = 0;
+        if (par) a.sym_work = d_work + ((hb_lz4_dec_workspace(cap) + 255) & ~(size_t)255);
+        return hb_launch_snappy_decode(a, nullptr);
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -393,7 +376,7 @@ int hb_compress_frame_dev(const void *d_src, size_t n, void *d_frame, size_t cap
     if (level > 9) level = 9;                                         // :280-282
     // device codecs: LZ4 (codec.go:59-84), LZ4HC (:90-128, same block format, deeper search by level), Snappy (:228-244)
     if (!hb_device_codec(codec)) return HB_ERR_INVALID_CODEC;
-    if (n > 0xFFFFFFFFull - HB_HEADER_SIZE - n / 255 - 64) return HB_ERR_DATA_TOO_LARGE;
+    if (hb_frame_too_large(n)) return HB_ERR_DATA_TOO_LARGE;
     if (cap < hb_frame_bound(n)) return HB_ERR_SHORT_BUFFER;
     if (work_bytes < hb_compress_frame_workspace(n)) return HB_ERR_SHORT_BUFFER;
     hipStream_t s = (hipStream_t)stream;
@@ -448,51 +431,36 @@ int hb_decompress_frame_dev_hdr(const hb_header *hdr, const void *d_frame, size_
     if (!hdr || !d_frame || !d_work || ((uintptr_t)d_work & 255u) || !d_result || (!d_dst && cap)) return HB_ERR_BAD_ARG;
     const hb_header &h = *hdr;
     hipStream_t s = (hipStream_t)stream;
-    int rc;
-    if (n < HB_HEADER_SIZE) return HB_ERR_INVALID_HEADER;
-    if (h.version != HB_FORMAT_VERSION) return HB_ERR_INVALID_VERSION; // blosc.go:179-182 (a caller may have built the record itself)
-    if ((size_t)h.cbytes > n) return HB_ERR_INVALID_DATA;             // blosc.go:385-387
-    if (h.cbytes < HB_HEADER_SIZE) return HB_ERR_INVALID_DATA;        // blosc.go:388-390
-    if (!(h.flags & HB_FLAG_MEMCPY) && !hb_device_codec(h.codec)) return HB_ERR_INVALID_CODEC;   // :403-407
-    if ((size_t)h.nbytes > cap) return HB_ERR_SHORT_BUFFER;
-    const bool snappy = h.codec == HB_SNAPPY && !(h.flags & HB_FLAG_MEMCPY);
+    int rc = hb_frame_refuse(h, n, cap, HB_CARRY_DEVICE);
+    if (rc) return rc;
+    const bool snappy = h.codec == HB_SNAPPY && !hb_frame_is_memcpy(h);
     if (work_bytes < hb_decompress_frame_workspace(h.nbytes)) return HB_ERR_SHORT_BUFFER;
-    const int ts = typesize_override > 0 ? typesize_override : (int)h.typesize;   // blosc.go:417-419
-    int unf = -1;
-    if ((h.flags & HB_FLAG_BITSHUFFLE) && ts > 1) unf = HB_OP_BITUNSHUFFLE;       // blosc.go:422-423 (bitshuffle wins)
-    else if ((h.flags & HB_FLAG_SHUFFLE) && ts > 1) unf = HB_OP_UNSHUFFLE;        // blosc.go:424-425
+    const int ts = hb_frame_item_size(h, typesize_override);
+    int unf = hb_frame_unfilter(h, ts);
     uint8_t *work = (uint8_t *)d_work;
     uint8_t *staged = work;
     uint8_t *dec_work = work + (((size_t)h.nbytes + 255) & ~(size_t)255) + 256;
-    // bit-unshuffle with typesize 4 works inside 32-byte windows: fused into the indexed decoder when there are only
-    // whole windows (the serial fallback still goes through `staged` + a gated un-filter pass, hb_lz4_dec.hip)
-    // restart index, if any, sits after cbytes (ignored by the reference decoder, blosc.go:385-393); without one there is nothing
-    // to fuse the un-filter into (the serial / region decoders produce the filtered bytes)
-    const size_t ioff = ((size_t)h.cbytes + 7) & ~(size_t)7;
-    // (a frame without the trailer gets its index rebuilt on the device when its payload is large enough, hb_lz4_region.hip; the
-    // fused un-filter is then armed the same way: if the rebuilt index does not hold, the serial path + the gated pass take over)
-    const bool has_index = !(h.flags & HB_FLAG_MEMCPY) && (n > ioff + 32 || (hb_indexless_parallel((size_t)h.cbytes - HB_HEADER_SIZE, h.nbytes) && !snappy));
-    const bool stored_index = !(h.flags & HB_FLAG_MEMCPY) && n > ioff + 32;
-    const bool fused_bun = unf == HB_OP_BITUNSHUFFLE && ts == 4 && (h.nbytes % 32u) == 0 && !(h.flags & HB_FLAG_MEMCPY) &&
-                           ((uintptr_t)d_dst & 15u) == 0 && !snappy && has_index;
-    // byte un-shuffle: fused into the indexed decoder (byte-strided stores) when the frame is whole planes of whole chunks
-    // (typesize 8: every 128-byte line would be completed by 8 different waves -- measured 0.2 ms per GiB SLOWER than the
-    // separate pass, while typesize 2 and 4 win 0.2 ms)
+    // The indexed LZ4 decoder runs on a stored index, or on one rebuilt on the device when the frame comes without the trailer and its
+    // payload is large enough (hb_lz4_region.hip).  The un-filter is fused into it where hb_frame_plan.h says so, armed alike in both
+    // cases: if the index does not hold, the serial path goes through `staged` + a gated un-filter pass (hb_lz4_dec.hip).
+    const bool stored_index = hb_frame_stored_index(h, n);
+    const bool rebuilt = !hb_frame_is_memcpy(h) && hb_indexless_parallel((size_t)h.cbytes - HB_HEADER_SIZE, h.nbytes);
+    const bool indexed = (stored_index || rebuilt) && !snappy;
+    const bool fused_bun = hb_frame_fuse_bitunshuffle4(h, unf, ts, d_dst, indexed);
     static const int ush_max = [] { const char *e = getenv("HIPBLOSC_DEBUG_FUSED_UNSHUFFLE_MAX_TS"); return e && *e ? atoi(e) : 4; }();   // A/B (lab): 8 = typesize 8 fused too
-    const bool fused_ush = unf == HB_OP_UNSHUFFLE && ts <= ush_max && (ts == 2 || ts == 4 || ts == 8) && (h.nbytes % (uint32_t)ts) == 0 &&
-                           ((h.nbytes / (uint32_t)ts) % HB_CHUNK) == 0 && !(h.flags & HB_FLAG_MEMCPY) && !g_no_dec_fusion && !snappy && has_index;
+    const bool fused_ush = !g_no_dec_fusion && hb_frame_fuse_unshuffle(h, unf, ts, indexed, ush_max, true);
     uint8_t *target = (unf >= 0 && !fused_bun && !fused_ush) ? staged : (uint8_t *)d_dst;
     const uint8_t *payload = (const uint8_t *)d_frame + HB_HEADER_SIZE;
     const size_t plen = h.cbytes - HB_HEADER_SIZE;
     hb_dec_args a{};
     a.src = payload; a.n = plen; a.dst = target; a.cap = h.nbytes;
     a.work = dec_work; a.result = d_result; a.frame = 1; a.expect = h.nbytes;
-    a.memcpy_payload = (h.flags & HB_FLAG_MEMCPY) ? 1 : 0;            // blosc.go:398-400
+    a.memcpy_payload = hb_frame_is_memcpy(h) ? 1 : 0;
     a.fused_bitunshuffle4 = fused_bun ? 1 : 0;
     a.fused_unshuffle_ts = fused_ush ? ts : 0;
     a.staged = staged;
     if (fused_bun || fused_ush) unf = -1;                             // nothing left to do after the decoder
-    if (stored_index) { a.index = (const uint8_t *)d_frame + ioff; a.index_bytes = n - ioff; }
+    if (stored_index) { const size_t ioff = hb_frame_index_offset(h); a.index = (const uint8_t *)d_frame + ioff; a.index_bytes = n - ioff; }
     if (work_bytes >= hb_decompress_frame_workspace_foreign(h.nbytes))
         a.sym_work = work + ((hb_decompress_frame_workspace(h.nbytes) + 255) & ~(size_t)255);
     rc = snappy ? hb_launch_snappy_decode(a, s) : hb_launch_lz4_decode(a, s);
@@ -512,25 +480,14 @@ int64_t hb_compress_frame(const void *src, size_t n, void *dst, size_t cap, int 
     if (!src || !dst) return HB_ERR_BAD_ARG;
     if (!hb_device_codec(codec) && !(codec == HB_ZSTD && hb_zstd_available())) return HB_ERR_INVALID_CODEC;   // blosc.go:322-325
     // the header fields are uint32 (blosc.go:159-161); the reference truncates silently (:363-365), this does not
-    if (n > 0xFFFFFFFFull - HB_HEADER_SIZE - n / 255 - 64) return HB_ERR_DATA_TOO_LARGE;
+    if (hb_frame_too_large(n)) return HB_ERR_DATA_TOO_LARGE;
     int rc = select_device(device);
     if (rc) return rc;
     if (codec == HB_ZSTD) return hb_zstd_compress_frame(src, n, dst, cap, level, shuffle, typesize, opts, device);
-    Scratch sc(device);
-    const size_t fb = hb_frame_bound(n), wb = hb_compress_frame_workspace(n);
-    uint8_t *d_src = sc.get(n + 16), *d_frame = sc.get(fb + 64), *d_work = sc.get(wb), *d_res = sc.get(sizeof(hb_result));
-    if (!d_src || !d_frame || !d_work || !d_res) return HB_ERR_HIP;
-    HB_HIP_TRY(hipMemcpy(d_src, src, n, hipMemcpyHostToDevice));
-    rc = hb_compress_frame_dev(d_src, n, d_frame, fb + 64, codec, level, shuffle, typesize, opts, d_work, wb,
-                               (hb_result *)d_res, nullptr);
-    if (rc) return rc;
-    hb_result r;
-    HB_HIP_TRY(hipMemcpy(&r, d_res, sizeof r, hipMemcpyDeviceToHost));
-    if (r.status) return r.status;
-    const size_t out = (opts & HB_OPT_INDEX_TRAILER) ? r.total_bytes : r.bytes;
-    if (out > cap) return HB_ERR_SHORT_BUFFER;
-    HB_HIP_TRY(hipMemcpy(dst, d_frame, out, hipMemcpyDeviceToHost));
-    return (int64_t)out;
+    const size_t fb = hb_frame_bound(n) + 64, wb = hb_compress_frame_workspace(n);
+    return staged_call(device, src, n, n + 16, dst, cap, fb, wb, [&](uint8_t *d_src, uint8_t *d_frame, uint8_t *d_work, hb_result *d_res) {
+        return hb_compress_frame_dev(d_src, n, d_frame, fb, codec, level, shuffle, typesize, opts, d_work, wb, d_res, nullptr);
+    }, (opts & HB_OPT_INDEX_TRAILER) ? OUT_TOTAL_BYTES : OUT_BYTES);
 }
 
 int64_t hb_decompress_frame(const void *frame, size_t n, void *dst, size_t cap, int typesize_override, int device) {
@@ -539,34 +496,21 @@ int64_t hb_decompress_frame(const void *frame, size_t n, void *dst, size_t cap, 
     hb_header h;
     int rc = hb_parse_header(frame, n, &h);
     if (rc) return rc;
-    if ((size_t)h.cbytes > n || h.cbytes < HB_HEADER_SIZE) return HB_ERR_INVALID_DATA;
-    if (!(h.flags & HB_FLAG_MEMCPY) && h.codec == HB_ZSTD) {           // config 5: host codec, device un-filter (hb_zstd.hip)
-        if (!hb_zstd_available()) return HB_ERR_INVALID_CODEC;
-        rc = select_device(device);
-        if (rc) return rc;
+    const bool zstd = hb_frame_host_codec(h);                         // config 5: host codec, device un-filter (hb_zstd.hip)
+    rc = hb_frame_refuse_header(h, n, zstd && hb_zstd_available() ? HB_CARRY_DEVICE_AND_ZSTD : HB_CARRY_DEVICE);
+    if (rc) return rc;
+    rc = select_device(device);
+    if (rc) return rc;
+    if (zstd) {
         g_last_flags = 0;
         return hb_zstd_decompress_frame(frame, h, dst, cap, typesize_override, device);
     }
-    if (!(h.flags & HB_FLAG_MEMCPY) && !hb_device_codec(h.codec)) return HB_ERR_INVALID_CODEC;
-    rc = select_device(device);
+    rc = hb_frame_refuse_cap(h, cap);                                 // (the destination is looked at after the device selection)
     if (rc) return rc;
-    if ((size_t)h.nbytes > cap) return HB_ERR_SHORT_BUFFER;
-    Scratch sc(device);
-    // an LZ4 / Snappy frame without an index behind NBytesComp may be anybody's: room for the symbolic decoder as well
-    const bool maybe_foreign = !(h.flags & HB_FLAG_MEMCPY) && hb_indexless_parallel((size_t)h.cbytes - HB_HEADER_SIZE, h.nbytes) &&
-                               n <= (((size_t)h.cbytes + 7) & ~(size_t)7) + 32;
-    const size_t wb = maybe_foreign ? hb_decompress_frame_workspace_foreign(h.nbytes) : hb_decompress_frame_workspace(h.nbytes);
-    uint8_t *d_frame = sc.get(n + 64), *d_dst = sc.get((size_t)h.nbytes + 64), *d_work = sc.get(wb), *d_res = sc.get(sizeof(hb_result));
-    if (!d_frame || !d_dst || !d_work || !d_res) return HB_ERR_HIP;
-    HB_HIP_TRY(hipMemcpy(d_frame, frame, n, hipMemcpyHostToDevice));
-    rc = hb_decompress_frame_dev_hdr(&h, d_frame, n, d_dst, h.nbytes, typesize_override, d_work, wb, (hb_result *)d_res, nullptr);
-    if (rc) return rc;
-    hb_result r;
-    HB_HIP_TRY(hipMemcpy(&r, d_res, sizeof r, hipMemcpyDeviceToHost));
-    g_last_flags = r.flags;
-    if (r.status) return r.status;
-    if (r.bytes) HB_HIP_TRY(hipMemcpy(dst, d_dst, r.bytes, hipMemcpyDeviceToHost));
-    return (int64_t)r.bytes;
+    const size_t wb = hb_frame_maybe_foreign(h, n) ? hb_decompress_frame_workspace_foreign(h.nbytes) : hb_decompress_frame_workspace(h.nbytes);
+    return staged_call(device, frame, n, n + 64, dst, cap, (size_t)h.nbytes + 64, wb, [&](uint8_t *d_frame, uint8_t *d_dst, uint8_t *d_work, hb_result *d_res) {
+        return hb_decompress_frame_dev_hdr(&h, d_frame, n, d_dst, h.nbytes, typesize_override, d_work, wb, d_res, nullptr);
+    }, OUT_BYTES, true);
 }
 
 // items [start, start + nitems) of a frame: upload, the small workspace first (enough when the frame's index holds), the full one when the
@@ -577,8 +521,8 @@ int64_t hb_getitem_frame(const void *frame, size_t n, int64_t start, int64_t nit
     hb_header h;
     int rc = hb_parse_header(frame, n, &h);
     if (rc) return rc;
-    const bool zstd = !(h.flags & HB_FLAG_MEMCPY) && h.codec == HB_ZSTD;
-    if (zstd && !hb_zstd_available()) return HB_ERR_INVALID_CODEC;
+    const bool zstd = hb_frame_host_codec(h);
+    if (zstd && !hb_zstd_available()) return HB_ERR_INVALID_CODEC;    // (before the other header refusals, unlike hb_decompress_frame)
     int ts = 1;
     rc = hb_getitem_check(&h, n, start, nitems, typesize_override, 1, &ts);
     if (rc) return rc;
@@ -596,7 +540,7 @@ int64_t hb_getitem_frame(const void *frame, size_t n, int64_t start, int64_t nit
         if (bytes) memcpy(dst, all.data() + (size_t)start * (size_t)ts, bytes);
         return (int64_t)bytes;
     }
-    Scratch sc(device);
+    Scratch sc(device);                                               // (two passes over one upload: spelled out, not a staged_call)
     uint8_t *d_frame = sc.get(n + 64), *d_dst = sc.get(bytes + 64), *d_res = sc.get(sizeof(hb_result));
     if (!d_frame || !d_dst || !d_res) return HB_ERR_HIP;
     HB_HIP_TRY(hipMemcpy(d_frame, frame, n, hipMemcpyHostToDevice));
@@ -627,18 +571,11 @@ int64_t hb_cblosc_getitem(const void *frame, size_t n, int64_t start, int64_t ni
     if (!dst && bytes) return HB_ERR_BAD_ARG;
     rc = select_device(device);
     if (rc) return rc;
-    Scratch sc(device);
     const size_t wb = hb_cblosc_getitem_workspace(&h, start, nitems);
-    uint8_t *d_frame = sc.get(n + 64), *d_dst = sc.get((size_t)bytes + 64), *d_work = sc.get(wb), *d_res = sc.get(sizeof(hb_result));
-    if (!d_frame || !d_dst || !d_work || !d_res) return HB_ERR_HIP;
-    HB_HIP_TRY(hipMemcpy(d_frame, frame, h.cbytes, hipMemcpyHostToDevice));
-    rc = hb_cblosc_getitem_device(&h, d_frame, n, start, nitems, d_dst, (size_t)bytes, d_work, wb, (hb_result *)d_res, nullptr);
-    if (rc) return rc;
-    hb_result r;
-    HB_HIP_TRY(hipMemcpy(&r, d_res, sizeof r, hipMemcpyDeviceToHost));
-    if (r.status) return r.status;
-    if (r.bytes) HB_HIP_TRY(hipMemcpy(dst, d_dst, r.bytes, hipMemcpyDeviceToHost));
-    return (int64_t)r.bytes;
+    // (cbytes go up, not n: what lies behind the frame is not the library's to read)
+    return staged_call(device, frame, h.cbytes, n + 64, dst, cap, (size_t)bytes + 64, wb, [&](uint8_t *d_frame, uint8_t *d_dst, uint8_t *d_work, hb_result *d_res) {
+        return hb_cblosc_getitem_device(&h, d_frame, n, start, nitems, d_dst, (size_t)bytes, d_work, wb, d_res, nullptr);
+    });
 }
 
 int64_t hb_cblosc_compress(const void *src, size_t n, void *dst, size_t cap, int shuffle, int typesize, int device) {
@@ -646,19 +583,10 @@ int64_t hb_cblosc_compress(const void *src, size_t n, void *dst, size_t cap, int
     if (typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
     int rc = select_device(device);
     if (rc) return rc;
-    Scratch sc(device);
-    const size_t fb = hb_cblosc_bound(n, typesize), wb = hb_cblosc_compress_workspace(n, shuffle, typesize);
-    uint8_t *d_src = sc.get(n + 64), *d_frame = sc.get(fb + 64), *d_work = sc.get(wb), *d_res = sc.get(sizeof(hb_result));
-    if (!d_src || !d_frame || !d_work || !d_res) return HB_ERR_HIP;
-    if (n) HB_HIP_TRY(hipMemcpy(d_src, src, n, hipMemcpyHostToDevice));
-    rc = hb_cblosc_compress_dev(d_src, n, d_frame, fb + 64, shuffle, typesize, d_work, wb, (hb_result *)d_res, nullptr);
-    if (rc) return rc;
-    hb_result r;
-    HB_HIP_TRY(hipMemcpy(&r, d_res, sizeof r, hipMemcpyDeviceToHost));
-    if (r.status) return r.status;
-    if (r.bytes > cap) return HB_ERR_SHORT_BUFFER;
-    HB_HIP_TRY(hipMemcpy(dst, d_frame, r.bytes, hipMemcpyDeviceToHost));
-    return (int64_t)r.bytes;
+    const size_t fb = hb_cblosc_bound(n, typesize) + 64, wb = hb_cblosc_compress_workspace(n, shuffle, typesize);
+    return staged_call(device, src, n, n + 64, dst, cap, fb, wb, [&](uint8_t *d_src, uint8_t *d_frame, uint8_t *d_work, hb_result *d_res) {
+        return hb_cblosc_compress_dev(d_src, n, d_frame, fb, shuffle, typesize, d_work, wb, d_res, nullptr);
+    });
 }
 
 int64_t hb_cblosc_decompress(const void *frame, size_t n, void *dst, size_t cap, int device) {
@@ -676,18 +604,10 @@ int64_t hb_cblosc_decompress(const void *frame, size_t n, void *dst, size_t cap,
     }
     rc = select_device(device);
     if (rc) return rc;
-    Scratch sc(device);
     const size_t wb = hb_cblosc_decompress_workspace(h.nbytes, h.blocksize, h.typesize);
-    uint8_t *d_frame = sc.get(n + 64), *d_dst = sc.get((size_t)h.nbytes + 64), *d_work = sc.get(wb), *d_res = sc.get(sizeof(hb_result));
-    if (!d_frame || !d_dst || !d_work || !d_res) return HB_ERR_HIP;
-    HB_HIP_TRY(hipMemcpy(d_frame, frame, h.cbytes, hipMemcpyHostToDevice));
-    rc = hb_cblosc_decompress_dev(&h, d_frame, n, d_dst, h.nbytes, d_work, wb, (hb_result *)d_res, nullptr);
-    if (rc) return rc;
-    hb_result r;
-    HB_HIP_TRY(hipMemcpy(&r, d_res, sizeof r, hipMemcpyDeviceToHost));
-    if (r.status) return r.status;
-    if (r.bytes) HB_HIP_TRY(hipMemcpy(dst, d_dst, r.bytes, hipMemcpyDeviceToHost));
-    return (int64_t)r.bytes;
+    return staged_call(device, frame, h.cbytes, n + 64, dst, cap, (size_t)h.nbytes + 64, wb, [&](uint8_t *d_frame, uint8_t *d_dst, uint8_t *d_work, hb_result *d_res) {
+        return hb_cblosc_decompress_dev(&h, d_frame, n, d_dst, h.nbytes, d_work, wb, d_res, nullptr);
+    });
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 //              and errors of lz4.UncompressBlock, codec.go:77-84); then the batched un-filter.  Error semantics per frame are
 //              those of hb_decompress_frame_dev (blosc.go:377-434).
 #include "hb_sym_decode.h"
+#include "hb_frame_plan.h"
 #include <vector>
 #include <algorithm>
 #include <cstring>
@@ -133,12 +134,12 @@ int hb_compress_frames_batch_dev(int nframes, const void *const *d_src, const si
     if (typesize <= 0) typesize = 1;                                  // blosc.go:274-276
     if (level < 1) level = 1;                                         // :277-282
     if (level > 9) level = 9;
-    if (codec != HB_LZ4 && codec != HB_LZ4HC) return HB_ERR_INVALID_CODEC;      // the batch carries the LZ4 block format; Snappy / ZSTD: one call per frame
+    if (!hb_codec_carried(codec, HB_CARRY_LZ4)) return HB_ERR_INVALID_CODEC;    // the batch carries the LZ4 block format; Snappy / ZSTD: one call per frame
     std::vector<hb_batch_frame> fr((size_t)nframes);
     for (int k = 0; k < nframes; k++) {
         if (n[k] == 0) return HB_ERR_INVALID_DATA;                    // blosc.go:269-271 (the whole batch is refused: nothing has been launched)
         if (!d_src[k] || !d_frame[k]) return HB_ERR_BAD_ARG;
-        if (n[k] > 0xFFFFFFFFull - HB_HEADER_SIZE - n[k] / 255 - 64) return HB_ERR_DATA_TOO_LARGE;
+        if (hb_frame_too_large(n[k])) return HB_ERR_DATA_TOO_LARGE;
         if (cap[k] < hb_frame_bound(n[k])) return HB_ERR_SHORT_BUFFER;
         fr[(size_t)k] = hb_batch_frame{(const uint8_t *)d_src[k], n[k], (uint8_t *)d_frame[k], cap[k], d_results + k};
     }
@@ -179,7 +180,7 @@ int hb_frames_batch_headers_dev(int nframes, const void *const *d_frame, const s
 // A frame whose index the batch may rebuild (whether it brings one is not in the header): every frame hb_decompress_frames_batch_dev
 // rebuilds is one of these, with the same stream length.
 static bool rg_candidate(const hb_header &h) {
-    return !(h.flags & HB_FLAG_MEMCPY) && h.cbytes >= HB_HEADER_SIZE && hb_lz4_region_batch_wanted((size_t)h.cbytes - HB_HEADER_SIZE, h.nbytes);
+    return !hb_frame_is_memcpy(h) && h.cbytes >= HB_HEADER_SIZE && hb_lz4_region_batch_wanted((size_t)h.cbytes - HB_HEADER_SIZE, h.nbytes);
 }
 // region size of the batch's discovery jobs: about 16384 regions over the candidates' streams (what one large frame gets), never below the
 // one-frame path's 4 KiB, at most 64 KiB.  A function of the headers alone, so that the workspace and the call lay every job out alike
@@ -230,30 +231,21 @@ int hb_decompress_frames_batch_dev(int nframes, const hb_header *hdrs, const voi
         f = DecBatchFrame{};
         f.result = d_results + k;
         f.nbytes = hd.nbytes;
-        int st = HB_OK;
-        if (!d_frame[k] || (!d_dst[k] && cap[k])) st = HB_ERR_BAD_ARG;
-        else if (n[k] < HB_HEADER_SIZE) st = HB_ERR_INVALID_HEADER;
-        else if (hd.version != HB_FORMAT_VERSION) st = HB_ERR_INVALID_VERSION;
-        else if ((size_t)hd.cbytes > n[k] || hd.cbytes < HB_HEADER_SIZE) st = HB_ERR_INVALID_DATA;           // blosc.go:385-390
-        else if (!(hd.flags & HB_FLAG_MEMCPY) && hd.codec != HB_LZ4 && hd.codec != HB_LZ4HC) st = HB_ERR_INVALID_CODEC;   // (Snappy / ZSTD frames: one call per frame)
-        else if ((size_t)hd.nbytes > cap[k]) st = HB_ERR_SHORT_BUFFER;
+        const int st = (!d_frame[k] || (!d_dst[k] && cap[k])) ? HB_ERR_BAD_ARG : hb_frame_refuse(hd, n[k], cap[k], HB_CARRY_LZ4);
         if (st != HB_OK) { f.preset = st; f.nbytes = 0; continue; }
-        const int ts = typesize_override > 0 ? typesize_override : (int)hd.typesize;                          // blosc.go:417-419
-        int u = -1;
-        if ((hd.flags & HB_FLAG_BITSHUFFLE) && ts > 1) u = HB_OP_BITUNSHUFFLE;                                // blosc.go:422-426
-        else if ((hd.flags & HB_FLAG_SHUFFLE) && ts > 1) u = HB_OP_UNSHUFFLE;
-        if (u >= 0 && hd.nbytes < (uint32_t)ts) u = -1;                                                       // shuffle.go:17-19: identity
+        const int ts = hb_frame_item_size(hd, typesize_override);
+        const int u = hb_frame_unfilter(hd, ts, true);
         unf[(size_t)k] = u; tsv[(size_t)k] = ts;
         f.src = (const uint8_t *)d_frame[k] + HB_HEADER_SIZE;
         f.n_src = hd.cbytes - HB_HEADER_SIZE;
         staged_total += al256((size_t)hd.nbytes + 64);
-        if (hd.flags & HB_FLAG_MEMCPY) {
-            f.preset = f.n_src != hd.nbytes ? HB_ERR_SIZE_MISMATCH : HB_OK;                                   // blosc.go:398-400, :429-431
+        if (hb_frame_is_memcpy(hd)) {
+            f.preset = hb_frame_memcpy_length_ok(hd) ? HB_OK : HB_ERR_SIZE_MISMATCH;
             continue;
         }
         f.preset = 1;
-        const size_t ioff = ((size_t)hd.cbytes + 7) & ~(size_t)7;
-        const bool stored_index = n[k] > ioff + 32;
+        const size_t ioff = hb_frame_index_offset(hd);
+        const bool stored_index = hb_frame_stored_index(hd, n[k]);
         if (stored_index) { f.index = (const uint8_t *)d_frame[k] + ioff; f.index_bytes = n[k] - ioff; f.nunits = (uint32_t)(((size_t)hd.nbytes + HB_CHUNK - 1) / HB_CHUNK); }
         // no index behind NBytesComp (the default frame shape, blosc.go:369-371): the token discovery rebuilds it for all such frames of the batch
         // in one set of launches (hb_lz4_region.hip `_b` kernels); it is trusted no more than a stored one, and a frame whose chain does not check
@@ -265,8 +257,8 @@ int hb_decompress_frames_batch_dev(int nframes, const hb_header *hdrs, const voi
             f.nunits = (uint32_t)(((size_t)hd.nbytes + HB_CHUNK - 1) / HB_CHUNK);
         }
         const bool have_index = stored_index || rebuilt;
-        f.bun4 = (u == HB_OP_BITUNSHUFFLE && ts == 4 && (hd.nbytes % 32u) == 0 && ((uintptr_t)d_dst[k] & 15u) == 0 && have_index) ? 1 : 0;
-        f.ush = (u == HB_OP_UNSHUFFLE && ts <= 4 && (hd.nbytes % (uint32_t)ts) == 0 && ((hd.nbytes / (uint32_t)ts) % HB_CHUNK) == 0 && have_index) ? ts : 0;
+        f.bun4 = hb_frame_fuse_bitunshuffle4(hd, u, ts, d_dst[k], have_index) ? 1 : 0;
+        f.ush = hb_frame_fuse_unshuffle(hd, u, ts, have_index, 4, false) ? ts : 0;       // (no debug switches here: fixed limit, any typesize up to it)
         f.post_needed = (u >= 0) ? 1 : 0;
     }
     std::vector<uint32_t> unit0((size_t)nframes);
@@ -386,12 +378,6 @@ bool exactly_adjacent(const std::vector<int> &idx, const void *const *p, const s
         if ((const uint8_t *)p[idx[i]] + len[idx[i]] != (const uint8_t *)p[idx[i + 1]]) return false;
     return idx.size() > 1;
 }
-struct Held {
-    int dev; std::vector<std::pair<void *, size_t>> v;
-    explicit Held(int d) : dev(d) {}
-    uint8_t *get(size_t bytes) { size_t got = 0; void *p = hb_pool_take(dev, bytes, &got); if (p) v.push_back({p, got}); return (uint8_t *)p; }
-    ~Held() { for (auto &h : v) hb_pool_give(dev, h.first, h.second); }
-};
 }
 
 int hb_compress_frames_batch(int nframes, const void *const *src, const size_t *n, void *const *dst, const size_t *cap, int64_t *rc,
@@ -403,7 +389,7 @@ int hb_compress_frames_batch(int nframes, const void *const *src, const size_t *
     // frames the batch takes; the others get their answer from the one-frame entry point (argument errors, other codecs)
     std::vector<int> idx;
     for (int k = 0; k < nframes; k++) {
-        const bool ok = (codec == HB_LZ4 || codec == HB_LZ4HC) && src[k] && dst[k] && n[k] != 0 && n[k] <= 0xFFFFFFFFull - HB_HEADER_SIZE - n[k] / 255 - 64;
+        const bool ok = hb_codec_carried(codec, HB_CARRY_LZ4) && src[k] && dst[k] && n[k] != 0 && !hb_frame_too_large(n[k]);
         if (ok) idx.push_back(k); else rc[k] = hb_compress_frame(src[k], n[k], dst[k], cap[k], codec, level, shuffle, typesize, opts, device);
     }
     const int m = (int)idx.size();
@@ -415,7 +401,7 @@ int hb_compress_frames_batch(int nframes, const void *const *src, const size_t *
         ioff[(size_t)i] = in_bytes; ooff[(size_t)i] = out_bytes;
         in_bytes += al256(ns[(size_t)i] + 16); out_bytes += al256(caps[(size_t)i]);
     }
-    Held sc(device);
+    Scratch sc(device);
     const size_t wb = hb_compress_frames_batch_workspace(m, ns.data(), typesize);
     const bool span_in = exactly_adjacent(idx, src, n);
     if (span_in) { in_bytes = 0; for (int i = 0; i < m; i++) { ioff[(size_t)i] = in_bytes; in_bytes += ns[(size_t)i]; } }      // the device copy mirrors the host span
@@ -482,9 +468,8 @@ int hb_decompress_frames_batch(int nframes, const void *const *frame, const size
     std::vector<hb_header> hd;
     for (int k = 0; k < nframes; k++) {
         hb_header h;
-        bool ok = frame[k] && n[k] >= HB_HEADER_SIZE && hb_parse_header(frame[k], n[k], &h) == HB_OK;
-        ok = ok && (size_t)h.cbytes <= n[k] && h.cbytes >= HB_HEADER_SIZE && ((h.flags & HB_FLAG_MEMCPY) || h.codec == HB_LZ4 || h.codec == HB_LZ4HC) &&
-             (size_t)h.nbytes <= cap[k] && (dst[k] || !h.nbytes);
+        const bool ok = frame[k] && n[k] >= HB_HEADER_SIZE && hb_parse_header(frame[k], n[k], &h) == HB_OK &&
+                        hb_frame_refuse(h, n[k], cap[k], HB_CARRY_LZ4) == HB_OK && (dst[k] || !h.nbytes);
         if (ok) { idx.push_back(k); hd.push_back(h); } else rc[k] = hb_decompress_frame(frame[k], n[k], dst[k], cap[k], typesize_override, device);
     }
     const int m = (int)idx.size();
@@ -496,7 +481,7 @@ int hb_decompress_frames_batch(int nframes, const void *const *frame, const size
         ioff[(size_t)i] = in_bytes; ooff[(size_t)i] = out_bytes;
         in_bytes += al256(ns[(size_t)i] + 64); out_bytes += al256(caps[(size_t)i] + 64);
     }
-    Held sc(device);
+    Scratch sc(device);
     const size_t wb = hb_decompress_frames_batch_workspace(m, hd.data());
     // frames that follow each other exactly go up in one copy (see hb_compress_frames_batch); destinations that follow each other inside
     // their own capacities (dst[k+1] in [dst[k] + nbytes, dst[k] + cap[k]]) get a device image of the same layout and come down in one

@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <utility>
+#include <vector>
 #include "../../include/hipblosc.h"
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -128,6 +130,18 @@ void hb_prof_end(hipStream_t s);
 
 void *hb_pool_take(int dev, size_t bytes, size_t *got);  // hb_api.hip: cached device scratch of the host-pointer entry points
 void hb_pool_give(int dev, void *p, size_t bytes);
+struct Scratch {     // RAII over pool buffers for one host-API call
+    int dev;
+    std::vector<std::pair<void *, size_t>> held;
+    explicit Scratch(int d) : dev(d) {}
+    uint8_t *get(size_t bytes) {
+        size_t got = 0;
+        void *p = hb_pool_take(dev, bytes, &got);
+        if (p) held.push_back({p, got});
+        return (uint8_t *)p;
+    }
+    ~Scratch() { for (auto &h : held) hb_pool_give(dev, h.first, h.second); }
+};
 int hb_select_device(int device);                        // hipSetDevice with the ABI's error codes
 unsigned hb_dbg_plane_mask();                            // hb_debug_plane_mask(): byte planes the fused LZ4 kernels work on (timing only)
 

@@ -15,7 +15,7 @@
 // no match before its own output, end state equal to the next entry -- and its entry must sit on the 4 KiB grid, but the state it
 // STARTS in is the index's claim; the full decode has it by induction from unit 0.  Memory-safe on any input; a forged trailer can make
 // the bytes differ from Decompress.  Any failed check sets plan->fail: path 3 takes over when the workspace has room for it.
-#include "hb_lz4.h"
+#include "hb_frame_plan.h"
 #include "hb_dec_common.h"
 #include "hb_dec_unit.h"
 
@@ -244,8 +244,8 @@ int gi_prepare(const hb_header &h, size_t n, int64_t start, int64_t nitems, int 
     const uint32_t ts = (uint32_t)c.ts;
     GiGeom &g = c.g;
     g.ts = ts; g.nbytes = h.nbytes; g.ne = h.nbytes / ts; g.start = (uint32_t)start; g.nitems = (uint32_t)nitems;
-    g.mode = GI_NONE;
-    if (ts > 1 && h.nbytes >= ts) g.mode = (h.flags & HB_FLAG_BITSHUFFLE) ? GI_BIT : (h.flags & HB_FLAG_SHUFFLE) ? GI_BYTE : GI_NONE;   // blosc.go:422-425
+    const int unf = hb_frame_unfilter(h, c.ts, true);
+    g.mode = unf == HB_OP_BITUNSHUFFLE ? GI_BIT : unf == HB_OP_UNSHUFFLE ? GI_BYTE : GI_NONE;
     const uint32_t e = g.start + g.nitems;
     g.nplanes = g.mode == GI_BYTE ? ts : 1u;
     g.flo = g.start * ts; g.fhi = e * ts;                                 // (e * ts <= nbytes: no overflow)
@@ -258,16 +258,14 @@ int gi_prepare(const hb_header &h, size_t n, int64_t start, int64_t nitems, int 
     g.upp = 0;
     if (g.nitems) g.upp = g.mode == GI_BYTE ? (g.nitems + HB_CHUNK - 2u) / HB_CHUNK + 1u : (g.fhi - 1u) / HB_CHUNK - g.flo / HB_CHUNK + 1u;
     c.bytes = (uint64_t)g.nitems * ts;
-    const size_t ioff = ((size_t)h.cbytes + 7) & ~(size_t)7;
-    const bool lz4 = h.codec == HB_LZ4 || h.codec == HB_LZ4HC;
-    c.path = (h.flags & HB_FLAG_MEMCPY) ? 2 : (lz4 && n > ioff + 32) ? 1 : 3;
+    // (path 1 decodes single units with the LZ4 unit decoder: a Snappy frame's stored index is the whole-frame decode's business)
+    c.path = hb_frame_is_memcpy(h) ? 2 : (hb_codec_carried(h.codec, HB_CARRY_LZ4) && hb_frame_stored_index(h, n)) ? 1 : 3;
     c.stage = c.path == 1 ? gi_align((size_t)g.nplanes * g.upp * HB_CHUNK) + 256 : 0;
     c.small = GI_OFF_STAGE + c.stage;
     // the whole-frame decode sees an LZ4 frame whose index did not hold WITHOUT its trailer: a frame with no index gets one rebuilt on the
     // device (hb_lz4_region.hip) and decodes in parallel, one with an index that fails goes to a single wavefront
     c.n3 = c.path == 1 ? (size_t)h.cbytes : n;
-    const bool foreign = c.path != 2 && hb_indexless_parallel((size_t)h.cbytes - HB_HEADER_SIZE, h.nbytes) && c.n3 <= ioff + 32;
-    c.wb3 = foreign ? hb_decompress_frame_workspace_foreign(h.nbytes) : hb_decompress_frame_workspace(h.nbytes);
+    c.wb3 = hb_frame_maybe_foreign(h, c.n3) ? hb_decompress_frame_workspace_foreign(h.nbytes) : hb_decompress_frame_workspace(h.nbytes);
     c.dst3 = c.small;
     c.work3 = c.dst3 + gi_align((size_t)h.nbytes) + 256;
     c.full = c.path == 2 ? c.small : c.work3 + gi_align(c.wb3);
@@ -276,21 +274,6 @@ int gi_prepare(const hb_header &h, size_t n, int64_t start, int64_t nitems, int 
 }
 
 }  // namespace
-
-// header and range checks of every getitem entry point, in the order include/hipblosc.h states; *ts_out = the item size
-int hb_getitem_check(const hb_header *hdr, size_t n, int64_t start, int64_t nitems, int typesize_override, int allow_zstd, int *ts_out) {
-    const hb_header &h = *hdr;
-    if (n < HB_HEADER_SIZE) return HB_ERR_INVALID_HEADER;             // blosc.go:297-299
-    if (h.version != HB_FORMAT_VERSION) return HB_ERR_INVALID_VERSION; // blosc.go:179-182
-    if ((size_t)h.cbytes > n || h.cbytes < HB_HEADER_SIZE) return HB_ERR_INVALID_DATA;   // blosc.go:385-390
-    if (!(h.flags & HB_FLAG_MEMCPY) && !hb_device_codec(h.codec) && !(allow_zstd && h.codec == HB_ZSTD)) return HB_ERR_INVALID_CODEC;   // :403-407
-    if ((h.flags & HB_FLAG_MEMCPY) && h.cbytes - HB_HEADER_SIZE != h.nbytes) return HB_ERR_SIZE_MISMATCH;   // blosc.go:398-400 -> :429-431
-    const int ts = typesize_override > 0 ? typesize_override : (h.typesize ? (int)h.typesize : 1);          // blosc.go:417-419
-    const int64_t ne = (int64_t)(h.nbytes / (uint32_t)ts);
-    if (start < 0 || nitems < 0 || start > ne || nitems > ne - start) return HB_ERR_BAD_ARG;
-    *ts_out = ts;
-    return HB_OK;
-}
 
 extern "C" {
 
@@ -324,7 +307,7 @@ int hb_getitem_frame_device(const hb_header *hdr, const void *d_frame, size_t n,
         const int staged = c.path == 1;
         const uint8_t *base = staged ? w + GI_OFF_STAGE : payload;
         if (c.path == 1) {
-            const size_t ioff = ((size_t)h.cbytes + 7) & ~(size_t)7;
+            const size_t ioff = hb_frame_index_offset(h);
             const uint8_t *index = (const uint8_t *)d_frame + ioff;
             hb_prof_begin("k_gi_plan", s);
             hipLaunchKernelGGL(k_gi_plan, dim3(1), dim3(1), 0, s, index, (uint64_t)(n - ioff), (uint64_t)(h.cbytes - HB_HEADER_SIZE), h.nbytes, plan, d_result);

@@ -39,10 +39,6 @@ int64_t hb_zstd_compress_frame(const void *src, size_t n, void *dst, size_t cap,
                                unsigned opts, int device);
 int64_t hb_zstd_decompress_frame(const void *frame, const hb_header &h, void *dst, size_t cap, int typesize_override, int device);
 
-// hb_getitem.hip: the header and range checks every getitem entry point makes first, in the order of include/hipblosc.h (allow_zstd: the
-// host-pointer entry point, which has the host codec); *ts_out = the item size
-int hb_getitem_check(const hb_header *hdr, size_t n, int64_t start, int64_t nitems, int typesize_override, int allow_zstd, int *ts_out);
-
 // batches of frames in one set of launches (hb_lz4_enc.hip / hb_batch.hip)
 struct hb_batch_frame { const uint8_t *src; size_t n; uint8_t *dst; size_t cap; hb_result *result; };
 size_t hb_lz4_enc_batch_workspace(int nframes, const size_t *n, int typesize);
@@ -63,6 +59,11 @@ static inline bool hb_device_codec(int codec) { return codec == HB_LZ4 || codec 
 static inline bool hb_indexless_parallel(size_t payload, size_t nbytes) {
     return payload >= (256u << 10) || (payload >= (16u << 10) && nbytes >= (2u << 20));
 }
+// Too large for the uint32 fields of an index / a frame header (blosc.go:159-161; the reference truncates silently, :363-365, this refuses):
+// the worst-case stream of n bytes (n + n / 255 + 16, codec.go:65) and the slack the kernels write behind it must stay below 2^32 --
+// a bare block, and a frame, which has its 16 header bytes in front.
+static inline bool hb_block_too_large(size_t n) { return n > 0xFFFFFFFFull - n / 255 - 64; }
+static inline bool hb_frame_too_large(size_t n) { return n > 0xFFFFFFFFull - HB_HEADER_SIZE - n / 255 - 64; }
 
 // ---- small device helpers shared by encoder and decoder ----
 __device__ __forceinline__ uint32_t lz4_ext_bytes(uint32_t x) { return x < 15u ? 0u : 1u + (x - 15u) / 255u; }

@@ -6,7 +6,7 @@
 // k+1 overlaps the kernels of frame k and the download of frame k-1 (the two PCIe directions and the compute queue are
 // independent engines), which is what the one-call API of hb_api.hip cannot do.
 #include "hb_common.h"
-#include "hb_lz4.h"
+#include "hb_frame_plan.h"
 #include "hb_ticket_ring.h"
 
 #include <vector>
@@ -14,18 +14,6 @@
 #include <new>
 #include <thread>
 #include <algorithm>
-
-extern "C" {
-size_t hb_frame_bound(size_t n);
-size_t hb_compress_frame_workspace(size_t n);
-size_t hb_decompress_frame_workspace(size_t n_out);
-size_t hb_decompress_frame_workspace_foreign(size_t n_out);
-int64_t hb_compress_frame(const void *src, size_t n, void *dst, size_t cap, int codec, int level, int shuffle, int typesize,
-                          unsigned opts, int device);
-int64_t hb_decompress_frame(const void *frame, size_t n, void *dst, size_t cap, int typesize_override, int device);
-int hb_compress_frame_dev(const void *d_src, size_t n, void *d_frame, size_t cap, int codec, int level, int shuffle,
-                          int typesize, unsigned opts, void *d_work, size_t work_bytes, hb_result *d_result, void *stream);
-}
 
 namespace {
 enum SlotState { SLOT_FREE = 0, SLOT_BUSY = 1, SLOT_DONE = 2 };
@@ -96,7 +84,7 @@ hb_queue *hb_queue_create(int device, int depth, size_t max_nbytes) { return hb_
 
 hb_queue *hb_queue_create_ex(int device, int depth, size_t max_nbytes, unsigned flags) {
     if (hb_init() != HB_OK || device < 0 || device >= hb_device_count() || depth < 1 || depth > 64 || max_nbytes == 0) return nullptr;
-    if (max_nbytes > 0xFFFFFFFFull - HB_HEADER_SIZE - max_nbytes / 255 - 64) return nullptr;
+    if (hb_frame_too_large(max_nbytes)) return nullptr;
     if (hipSetDevice(device) != hipSuccess) return nullptr;
     hb_queue *q = new (std::nothrow) hb_queue();
     if (!q) return nullptr;
@@ -161,10 +149,11 @@ int64_t hb_queue_decompress(hb_queue *q, const void *frame, size_t n, void *dst,
     hb_header h;
     int rc = hb_parse_header(frame, n, &h);                               // the frame is in host memory: no read-back
     if (rc) return rc;
-    if ((size_t)h.cbytes > n || h.cbytes < HB_HEADER_SIZE) return HB_ERR_INVALID_DATA;           // blosc.go:385-390
-    if (!(h.flags & HB_FLAG_MEMCPY) && !hb_device_codec(h.codec)) return HB_ERR_INVALID_CODEC;
-    if ((size_t)h.nbytes > q->max_n || n > q->in_bytes) return HB_ERR_DATA_TOO_LARGE;
-    if ((size_t)h.nbytes > cap) return HB_ERR_SHORT_BUFFER;
+    rc = hb_frame_refuse_header(h, n, HB_CARRY_DEVICE);                   // the queue carries the device codecs only
+    if (rc) return rc;
+    if ((size_t)h.nbytes > q->max_n || n > q->in_bytes) return HB_ERR_DATA_TOO_LARGE;   // (the slots' size comes before the caller's)
+    rc = hb_frame_refuse_cap(h, cap);
+    if (rc) return rc;
     if (hipSetDevice(q->device) != hipSuccess) return HB_ERR_HIP;
     int64_t ticket;
     Slot *s = take_slot(q, &ticket);
@@ -260,7 +249,7 @@ int hb_compress_frames_multi(int nframes, const void *const *src, const size_t *
             size_t max_n = 0;
             if (hb_device_codec(codec))
                 for (int k = d; k < nframes; k += nd)
-                    if (!batched[(size_t)k] && n[k] <= 0xFFFFFFFFull - HB_HEADER_SIZE - n[k] / 255 - 64) max_n = std::max(max_n, n[k]);
+                    if (!batched[(size_t)k] && !hb_frame_too_large(n[k])) max_n = std::max(max_n, n[k]);
             run_device(d, nd, nframes, max_n, 0u, rc, batched,
                        [&](hb_queue *q, int k) -> int64_t {
                            if (!hb_device_codec(codec) || !src[k] || !dst[k] || n[k] == 0) return HB_ERR_BAD_ARG;
@@ -297,7 +286,7 @@ int hb_decompress_frames_multi(int nframes, const void *const *frame, const size
                 };
                 for (int k = d; k < nframes; k += nd) {
                     hb_header h;
-                    if (!frame[k] || hb_parse_header(frame[k], n[k], &h) != HB_OK || (size_t)h.nbytes > MULTI_SMALL || (size_t)h.nbytes > cap[k] || (!dst[k] && cap[k])) continue;
+                    if (!frame[k] || hb_parse_header(frame[k], n[k], &h) != HB_OK || (size_t)h.nbytes > MULTI_SMALL || hb_frame_refuse_cap(h, cap[k]) || (!dst[k] && cap[k])) continue;
                     batched[(size_t)k] = 1; ks.push_back(k); bytes += h.nbytes;
                     if (bytes >= MULTI_BATCH_BYTES) flush();
                 }
@@ -308,17 +297,15 @@ int hb_decompress_frames_multi(int nframes, const void *const *frame, const size
             for (int k = d; k < nframes; k += nd) {
                 hb_header h;
                 if (batched[(size_t)k]) continue;
-                // frames whose header asks for more than the caller gave (nbytes above cap[k], cbytes above n[k]) never reach a queue slot:
-                // they must not size the slots either (one forged NBytesOrig made every device allocate 3 x ~3 x 4 GiB); the
-                // one-call path answers them with the reference's error
-                if (frame[k] && hb_parse_header(frame[k], n[k], &h) == HB_OK && (hb_device_codec(h.codec) || (h.flags & HB_FLAG_MEMCPY)) &&
-                    (size_t)h.nbytes <= cap[k] && (size_t)h.cbytes <= n[k]) {
+                // frames hb_queue_decompress refuses (a header that asks for more than the caller gave: nbytes above cap[k], cbytes above n[k] ...)
+                // never reach a queue slot: they must not size the slots either (one forged NBytesOrig made every device allocate
+                // 3 x ~3 x 4 GiB); the one-call path answers them with the reference's error
+                if (frame[k] && hb_parse_header(frame[k], n[k], &h) == HB_OK && hb_frame_refuse(h, n[k], cap[k], HB_CARRY_DEVICE) == HB_OK) {
                     max_n = std::max(max_n, std::max<size_t>(h.nbytes, 1));
-                    if (!(h.flags & HB_FLAG_MEMCPY) && h.cbytes >= HB_HEADER_SIZE && hb_indexless_parallel((size_t)h.cbytes - HB_HEADER_SIZE, h.nbytes) &&
-                        n[k] <= (((size_t)h.cbytes + 7) & ~(size_t)7) + 32) qflags = HB_QUEUE_FOREIGN_FRAMES;
+                    if (hb_frame_maybe_foreign(h, n[k])) qflags = HB_QUEUE_FOREIGN_FRAMES;
                 }
             }
-            if (max_n > 0xFFFFFFFFull - HB_HEADER_SIZE - max_n / 255 - 64) max_n = 0;
+            if (hb_frame_too_large(max_n)) max_n = 0;
             run_device(d, nd, nframes, max_n, qflags, rc, batched,
                        [&](hb_queue *q, int k) -> int64_t {
                            if (!frame[k] || (!dst[k] && cap[k])) return HB_ERR_BAD_ARG;

@@ -9,7 +9,7 @@
 // libzstd is loaded at run time (dlopen); without it the codec reports HB_ERR_INVALID_CODEC, like an
 // unregistered codec in the reference (blosc.go:322-325).
 #include "hb_common.h"
-#include "hb_lz4.h"
+#include "hb_frame_plan.h"
 
 #include <dlfcn.h>
 #include <atomic>
@@ -198,11 +198,9 @@ int64_t hb_zstd_decompress_frame(const void *frame, const hb_header &h, void *ds
     if (!z) return HB_ERR_INVALID_CODEC;
     const uint8_t *p = (const uint8_t *)frame + HB_HEADER_SIZE;
     const size_t plen = h.cbytes - HB_HEADER_SIZE, n = h.nbytes;
-    if (n > cap) return HB_ERR_SHORT_BUFFER;
-    const int ts = typesize_override > 0 ? typesize_override : (int)h.typesize;            // blosc.go:417-419
-    int unf = -1;
-    if ((h.flags & HB_FLAG_BITSHUFFLE) && ts > 1) unf = HB_OP_BITUNSHUFFLE;                // blosc.go:422-426
-    else if ((h.flags & HB_FLAG_SHUFFLE) && ts > 1) unf = HB_OP_UNSHUFFLE;
+    if (hb_frame_refuse_cap(h, cap)) return HB_ERR_SHORT_BUFFER;
+    const int ts = hb_frame_item_size(h, typesize_override);
+    const int unf = hb_frame_unfilter(h, ts);
     uint8_t *h_f = nullptr, *d_a = nullptr, *d_b = nullptr;
     size_t b_h = 0, b_a = 0, b_b = 0;
     uint8_t *target = (uint8_t *)dst;
