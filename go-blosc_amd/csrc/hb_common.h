@@ -67,6 +67,32 @@ __device__ __forceinline__ uint32_t wave_incl_scan_dpp(uint32_t v) {
     return v;
 }
 
+// number of set bits of a wave-uniform mask below my lane: where my lane goes when the set lanes are compacted in lane order
+__device__ __forceinline__ uint32_t wave_rank(unsigned long long mask) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
+// Follows a chain through the wave on the scalar side: succ = the lane my lane points at, the chain starts at lane `first` and ends at
+// the lane that points at itself.  One s_bitset1_b64 + one v_readlane per link: returns the mask of the visited lanes, lastj = the
+// last of them.  Unrolled by 4: the walk stands still at its last lane, and setting the last bit again is harmless.
+__device__ __forceinline__ unsigned long long wave_chain_walk(const uint32_t succ, const uint32_t first, uint32_t &lastj) {
+    unsigned long long mask = 0;
+    uint32_t j = first;
+    for (;;) {
+        asm volatile("s_bitset1_b64 %0, %1" : "+s"(mask) : "s"(j));
+        const uint32_t j1 = __builtin_amdgcn_readlane(succ, (int)j);
+        asm volatile("s_bitset1_b64 %0, %1" : "+s"(mask) : "s"(j1));
+        const uint32_t j2 = __builtin_amdgcn_readlane(succ, (int)j1);
+        asm volatile("s_bitset1_b64 %0, %1" : "+s"(mask) : "s"(j2));
+        const uint32_t j3 = __builtin_amdgcn_readlane(succ, (int)j2);
+        asm volatile("s_bitset1_b64 %0, %1" : "+s"(mask) : "s"(j3));
+        j = __builtin_amdgcn_readlane(succ, (int)j3);
+        lastj = j3;
+        if (j == j3) break;
+    }
+    return mask;
+}
+
 // 4x4 byte transpose: in e[i] = bytes of row i; out p[j] = {e0.bj, e1.bj, e2.bj, e3.bj}.  Involution.
 __device__ __forceinline__ void transpose4x4(uint32_t e0, uint32_t e1, uint32_t e2, uint32_t e3,
                                              uint32_t &p0, uint32_t &p1, uint32_t &p2, uint32_t &p3) {

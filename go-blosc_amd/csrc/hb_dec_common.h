@@ -129,6 +129,54 @@ __device__ __forceinline__ void dec_match_copy(uint8_t *s_out, uint32_t md, uint
     }
 }
 
+// ---- pieces of the window parsers (dec_fill, dec_fill_lean; sn_rg_fill, sn_fill, rg_fill of hb_lz4_region.h) ----
+// Every lane has parsed "as if a token started at my byte": nrel = where the next token would start, relative to the window's first byte (>= 64:
+// behind the window), succ = that as a lane, or my own lane where the chain ends with me; cmask = lanes whose token the parser does not take.
+// The real chain from lane 0 on the scalar side (wave_chain_walk): tmask gets the lanes of the real tokens, the return value is the position
+// behind the last of them -- or that of the first one the parser does not take (at most the last visited lane), with `stop` set.
+__device__ __forceinline__ uint32_t dec_walk(const uint32_t succ, const uint32_t nrel, const uint32_t base, const unsigned long long cmask,
+                                             unsigned long long &tmask, bool &stop) {
+    uint32_t lastj;
+    tmask = wave_chain_walk(succ, 0u, lastj);
+    uint32_t cur = base + __builtin_amdgcn_readlane(nrel, (int)lastj);
+    const unsigned long long cm = tmask & cmask;  // at most the last visited lane
+    if (cm) { tmask &= ~cm; cur = base + (uint32_t)__builtin_ctzll(cm); stop = true; }
+    return cur;
+}
+// The chain WITHOUT a scalar walk (one s_bitset + s_nop + v_readlane per token: the decoder issues more scalar than vector instructions, and
+// half of them were this walk): successor tables by pointer doubling (S2 = S1 o S1, ... S16: four ds_bpermute), then lane k composes the powers
+// its bits name -- c_k = S1^k(lane 0), five more -- and holds the lane of the k-th token of the window: the caller writes its queue compacted, no
+// rank computation either.  A window holds at most 22 tokens (3 bytes each).  Returns c; ntok = tokens in the window, lastj = the last one's lane.
+__device__ __forceinline__ uint32_t dec_chain_doubling(const uint32_t succ, const int lane, uint32_t &ntok, uint32_t &lastj) {
+    const uint32_t s1 = succ;
+    const uint32_t s2 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(s1 << 2), (int)s1);
+    const uint32_t s4 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(s2 << 2), (int)s2);
+    const uint32_t s8 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(s4 << 2), (int)s4);
+    const uint32_t s16 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(s8 << 2), (int)s8);
+    uint32_t c = 0;
+    { const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(c << 2), (int)s1); c = (lane & 1) ? y : c; }
+    { const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(c << 2), (int)s2); c = (lane & 2) ? y : c; }
+    { const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(c << 2), (int)s4); c = (lane & 4) ? y : c; }
+    { const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(c << 2), (int)s8); c = (lane & 8) ? y : c; }
+    { const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(c << 2), (int)s16); c = (lane & 16) ? y : c; }
+    // c_k repeats once the chain has reached its last lane: the tokens are the lanes whose c differs from their left neighbour's
+    const uint32_t left = wave_shr1(c, 0xFFFFFFFFu);
+    const unsigned long long distinct = hb_ballot(c != left) | 0xFFFFFFFF00000000ull;   // (lanes 32.. take no part)
+    ntok = (uint32_t)__builtin_ctzll(~distinct | (1ull << 32));                          // leading run of distinct lanes (lane 0 always is)
+    lastj = __builtin_amdgcn_readlane(c, (int)ntok - 1);
+    return c;
+}
+// The 64 tokens at the front of the queue (cntb of them when fewer were queued) are done: what is queued behind them moves to the front.
+// In two halves for the walkers whose callback runs in between (the read is then under way while the batch is decoded).
+__device__ __forceinline__ uint2 dec_queue_rest(const uint2 *s_tq, const int lane) { return s_tq[64 + lane < DTQ ? 64 + lane : 0]; }
+__device__ __forceinline__ void dec_queue_shift(uint2 *s_tq, uint32_t &nq, const uint32_t cntb, const uint2 rest, const int lane) {
+    nq -= cntb;
+    if ((uint32_t)lane < nq) s_tq[lane] = rest;
+}
+__device__ __forceinline__ void dec_queue_shift(uint2 *s_tq, uint32_t &nq, const uint32_t cntb, const int lane) {
+    dec_queue_shift(s_tq, nq, cntb, dec_queue_rest(s_tq, lane), lane);
+}
+
 // DRAIN: one queued token per lane, while 64 are queued (or `stop` and any are).  out[0] is the first byte of the image,
 // `hist` bytes before it are valid match sources, `outlen` is the room.  A token that does not fit is not decoded:
 // `rewound` is set and si goes back to that token.  Returns false on a match that reaches before out[-hist] or has offset 0.
@@ -247,9 +295,7 @@ __device__ __forceinline__ bool dec_drain(const uint8_t *in, const int inoff, ui
             nq -= cntb;
             ((uint16_t *)s_tq)[lane] = rest;                    // (every lane: the slots behind nq are free)
         } else {
-            const uint2 rest = s_tq[64 + lane < DTQ ? 64 + lane : 0];
-            nq -= cntb;
-            if ((uint32_t)lane < nq) s_tq[lane] = rest;
+            dec_queue_shift(s_tq, nq, cntb, lane);
         }
     }
     return ok;
@@ -331,29 +377,11 @@ __device__ __forceinline__ bool dec_fill(const uint8_t *s_in, const uint32_t sh,
         // "complex" lane ends the walk (its successor is >= 64)
         const unsigned long long cmask = hb_ballot(cplx);
         unsigned long long tmask = 0;
-        uint32_t cur;
-        {
-            const uint32_t nrel = cplx ? 64u : nxt - base;
-            const uint32_t succ = nrel < 64u ? nrel : (uint32_t)lane;   // the last token of the window points at itself
-            uint32_t j = 0, lastj;
-            for (;;) {                                       // unrolled by 4: setting the last bit again is harmless
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j));
-                const uint32_t j1 = __builtin_amdgcn_readlane(succ, (int)j);
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j1));
-                const uint32_t j2 = __builtin_amdgcn_readlane(succ, (int)j1);
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j2));
-                const uint32_t j3 = __builtin_amdgcn_readlane(succ, (int)j2);
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j3));
-                j = __builtin_amdgcn_readlane(succ, (int)j3);
-                lastj = j3;
-                if (j == j3) break;
-            }
-            cur = base + __builtin_amdgcn_readlane(nrel, (int)lastj);
-            const unsigned long long cm = tmask & cmask;  // at most the last visited lane
-            if (cm) { tmask &= ~cm; cur = base + (uint32_t)__builtin_ctzll(cm); stop = true; }
-        }
+        const uint32_t nrel = cplx ? 64u : nxt - base;
+        const uint32_t succ = nrel < 64u ? nrel : (uint32_t)lane;   // the last token of the window points at itself
+        const uint32_t cur = dec_walk(succ, nrel, base, cmask, tmask, stop);
         // queue the real tokens, compacted in stream order: {lsrc | lit << 13 | mlen << 22, offset | tokpos << 16}
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(tmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tmask, 0u));
+        const uint32_t rank = wave_rank(tmask);
         if ((tmask >> lane) & 1ull) {
             uint2 e; e.x = lsrc | (lit << 13) | (mlen << 22); e.y = offv | (p << 16);
             s_tq[nq + rank] = e;
@@ -390,26 +418,9 @@ __device__ __forceinline__ bool dec_fill_lean(const uint8_t *s_in, const uint32_
         const uint32_t succ = hb_lane_in(selfm) ? (uint32_t)lane : nrel;              // the last token of the window points at itself
 #if DEC_BPERM_WALK
         if (last_ntok >= DEC_BPERM_MIN) {
-            // The chain WITHOUT a scalar walk (one s_bitset + s_nop + v_readlane per token: the decoder issues more scalar than vector
-            // instructions, and half of them were this walk): successor tables by pointer doubling (S2 = S1 o S1, ... S16: four
-            // ds_bpermute), then lane k composes the powers its bits name -- c_k = S1^k(lane 0), five more -- and holds the k-th token of
-            // the window: the queue is written compacted, no rank computation either.  A window holds at most 22 tokens (3 bytes each).
-            const uint32_t s1 = succ;
-            const uint32_t s2 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(s1 << 2), (int)s1);
-            const uint32_t s4 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(s2 << 2), (int)s2);
-            const uint32_t s8 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(s4 << 2), (int)s4);
-            const uint32_t s16 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(s8 << 2), (int)s8);
-            uint32_t c = 0;
-            { const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(c << 2), (int)s1); c = (lane & 1) ? y : c; }
-            { const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(c << 2), (int)s2); c = (lane & 2) ? y : c; }
-            { const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(c << 2), (int)s4); c = (lane & 4) ? y : c; }
-            { const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(c << 2), (int)s8); c = (lane & 8) ? y : c; }
-            { const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(c << 2), (int)s16); c = (lane & 16) ? y : c; }
-            // c_k repeats once the chain has reached its last lane: the tokens are the lanes whose c differs from their left neighbour's
-            const uint32_t left = wave_shr1(c, 0xFFFFFFFFu);
-            const unsigned long long distinct = hb_ballot(c != left) | 0xFFFFFFFF00000000ull;   // (lanes 32.. take no part)
-            uint32_t ntok = (uint32_t)__builtin_ctzll(~distinct | (1ull << 32));                 // leading run of distinct lanes (lane 0 always is)
-            const uint32_t lastj = __builtin_amdgcn_readlane(c, (int)ntok - 1);
+            // the chain of a token-dense window by pointer doubling: lane k holds the k-th token's lane
+            uint32_t ntok, lastj;
+            const uint32_t c = dec_chain_doubling(succ, lane, ntok, lastj);
             cur = base + __builtin_amdgcn_readlane(nrel, (int)lastj);
             if ((cmask >> lastj) & 1ull) { ntok--; cur = base + lastj; stop = true; }           // a token this parser does not take ends the walk
             ((uint16_t *)s_tq)[(uint32_t)lane < ntok ? nq + (uint32_t)lane : (uint32_t)(DTQ - 1)] = (uint16_t)(base + c);
@@ -419,25 +430,8 @@ __device__ __forceinline__ bool dec_fill_lean(const uint8_t *s_in, const uint32_
             continue;
         }
 #endif
-        {
-            uint32_t j = 0, lastj;
-            for (;;) {                                       // unrolled by 4: setting the last bit again is harmless
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j));
-                const uint32_t j1 = __builtin_amdgcn_readlane(succ, (int)j);
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j1));
-                const uint32_t j2 = __builtin_amdgcn_readlane(succ, (int)j1);
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j2));
-                const uint32_t j3 = __builtin_amdgcn_readlane(succ, (int)j2);
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j3));
-                j = __builtin_amdgcn_readlane(succ, (int)j3);
-                lastj = j3;
-                if (j == j3) break;
-            }
-            cur = base + __builtin_amdgcn_readlane(nrel, (int)lastj);
-            const unsigned long long cm = tmask & cmask;  // at most the last visited lane
-            if (cm) { tmask &= ~cm; cur = base + (uint32_t)__builtin_ctzll(cm); stop = true; }
-        }
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(tmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tmask, 0u));
+        cur = dec_walk(succ, nrel, base, cmask, tmask, stop);
+        const uint32_t rank = wave_rank(tmask);
         ((uint16_t *)s_tq)[hb_select_lane(tmask, nq + rank, (uint32_t)(DTQ - 1))] = (uint16_t)p;
         last_ntok = (uint32_t)__builtin_popcountll(tmask);
         nq += last_ntok;

@@ -314,6 +314,32 @@ __device__ __forceinline__ void match_chunk(const uint8_t *s_data, const uint32_
             }
         };
 
+        // literal runs of more than LITCAP bytes (the lanes of lm): the whole wave copies each from the chunk to its place in s_out
+        auto copy_long_literals = [&](unsigned long long lm, const uint32_t prev, const uint32_t litdst, const uint32_t lit) __attribute__((always_inline)) {
+            while (lm) {
+                const int l = __builtin_ctzll(lm);
+                const uint32_t s = __builtin_amdgcn_readlane(prev, l), dq = __builtin_amdgcn_readlane(litdst, l);
+                const uint32_t ln = __builtin_amdgcn_readlane(lit, l);
+                for (uint32_t k = lane * 4u; k < ln; k += 256u) {
+                    if (k + 4u <= ln) ((hb_u32u *)(s_out + dq + k))->v = ((const hb_u32u *)(data + s + k))->v;
+                    else for (uint32_t r = k; r < ln; r++) s_out[dq + r] = data[s + r];
+                }
+                lm &= lm - 1;
+            }
+        };
+
+        // the end of both emitters (flush, flush_sn): cnt sequences were emitted; the record's whole blocks go out, what is queued behind them (r0, r1)
+        // moves to the front
+        auto flush_end = [&](const uint32_t end, const int cnt, const uint2 r0, const uint2 r1) __attribute__((always_inline)) {
+            batch_anchor = __builtin_amdgcn_readlane(end, cnt - 1);
+            nseq += cnt;
+            drain(false);
+            nq -= cnt;
+            if (lane < nq) s_q[lane] = r0;
+            if (lane + 64 < nq) s_q[lane + 64] = r1;
+            st_state();
+        };
+
         // emit queued sequences, one per lane: as many of the first min(nq, 64) as fit into s_out
         auto flush = [&]() __attribute__((always_inline)) {
             ld_state();
@@ -387,26 +413,10 @@ __device__ __forceinline__ void match_chunk(const uint8_t *s_data, const uint32_
                         s_out[q++] = (uint8_t)((mcode - 15u) - 255u * (nbm - 1));
                     }
                 }
-                unsigned long long lm = hb_ballot(act && lit > LITCAP);
-                while (lm) {                                   // long literal runs: the whole wave copies
-                    const int l = __builtin_ctzll(lm);
-                    const uint32_t s = __builtin_amdgcn_readlane(prev, l), dq = __builtin_amdgcn_readlane(litdst, l);
-                    const uint32_t ln = __builtin_amdgcn_readlane(lit, l);
-                    for (uint32_t k = lane * 4u; k < ln; k += 256u) {
-                        if (k + 4u <= ln) ((hb_u32u *)(s_out + dq + k))->v = ((const hb_u32u *)(data + s + k))->v;
-                        else for (uint32_t r = k; r < ln; r++) s_out[dq + r] = data[s + r];
-                    }
-                    lm &= lm - 1;
-                }
+                copy_long_literals(hb_ballot(act && lit > LITCAP), prev, litdst, lit);
                 opend += (uint32_t)__builtin_amdgcn_readlane(incl, cnt - 1);
             }
-            batch_anchor = __builtin_amdgcn_readlane(end, cnt - 1);
-            nseq += cnt;
-            drain(false);
-            nq -= cnt;
-            if (lane < nq) s_q[lane] = r0;
-            if (lane + 64 < nq) s_q[lane + 64] = r1;
-            st_state();
+            flush_end(end, cnt, r0, r1);
         };
 
         // ---- Snappy emitter (SNAPPY): [literal element][copy elements] per queued sequence; format_description.txt of Snappy:
@@ -468,26 +478,10 @@ __device__ __forceinline__ void match_chunk(const uint8_t *s_data, const uint32_
                     q += lit;
                     sn_copies(q, q_ml, q_off);
                 }
-                unsigned long long lm = hb_ballot(act && lit > LITCAP);
-                while (lm) {                                       // long literal runs: the whole wave copies
-                    const int l = __builtin_ctzll(lm);
-                    const uint32_t sp = __builtin_amdgcn_readlane(prev, l), dq = __builtin_amdgcn_readlane(litdst, l);
-                    const uint32_t ln = __builtin_amdgcn_readlane(lit, l);
-                    for (uint32_t k = lane * 4u; k < ln; k += 256u) {
-                        if (k + 4u <= ln) ((hb_u32u *)(s_out + dq + k))->v = ((const hb_u32u *)(data + sp + k))->v;
-                        else for (uint32_t r = k; r < ln; r++) s_out[dq + r] = data[sp + r];
-                    }
-                    lm &= lm - 1;
-                }
+                copy_long_literals(hb_ballot(act && lit > LITCAP), prev, litdst, lit);
                 opend += (uint32_t)__builtin_amdgcn_readlane(incl, cnt - 1);
             }
-            batch_anchor = __builtin_amdgcn_readlane(end, cnt - 1);
-            nseq += cnt;
-            drain(false);
-            nq -= cnt;
-            if (lane < nq) s_q[lane] = r0;
-            if (lane + 64 < nq) s_q[lane + 64] = r1;
-            st_state();
+            flush_end(end, cnt, r0, r1);
         };
         DBG_DECL();
         unsigned long long dbg_flush = 0;
@@ -581,7 +575,7 @@ __device__ __forceinline__ void match_chunk(const uint8_t *s_data, const uint32_
                         }
                         if (lane == lastj) ml = (uint32_t)mlj;
                     }
-                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(sel >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sel, 0u));
+                    const uint32_t rank = wave_rank(sel);
                     {   // every lane stores: the lanes that are not selected to the spare slot behind the queue (a v_cndmask on the mask itself where
                         // a predicated store costs three scalar instructions -- the step loop issues as many scalar as vector instructions)
                         uint2 e; e.x = (uint32_t)p | (ml << 16); e.y = 1u;
@@ -728,28 +722,15 @@ __device__ __forceinline__ void match_chunk(const uint8_t *s_data, const uint32_
                 int last_end = anchor;
                 if (lmask == 0) {
                     // all lengths known: every hit lane computes its successor (first hit at or after the end of
-                    // its match; the last one points at itself) and the walk is one bit-set + one readlane per
-                    // sequence, unrolled by 4 (setting the bit of the last lane again is harmless)
+                    // its match; the last one points at itself) and the walk is wave_chain_walk's
                     const uint32_t x = (uint32_t)lane + ml;
                     uint32_t succ = (uint32_t)lane;
                     if (x < 64u) {
                         const unsigned long long m = mask >> x;
                         if (m) succ = x + (uint32_t)__builtin_ctzll(m);
                     }
-                    uint32_t j = (uint32_t)__builtin_ctzll(mask);
                     uint32_t lastj;
-                    for (;;) {
-                        asm volatile("s_bitset1_b64 %0, %1" : "+s"(sel) : "s"(j));
-                        const uint32_t j1 = __builtin_amdgcn_readlane(succ, (int)j);
-                        asm volatile("s_bitset1_b64 %0, %1" : "+s"(sel) : "s"(j1));
-                        const uint32_t j2 = __builtin_amdgcn_readlane(succ, (int)j1);
-                        asm volatile("s_bitset1_b64 %0, %1" : "+s"(sel) : "s"(j2));
-                        const uint32_t j3 = __builtin_amdgcn_readlane(succ, (int)j2);
-                        asm volatile("s_bitset1_b64 %0, %1" : "+s"(sel) : "s"(j3));
-                        j = __builtin_amdgcn_readlane(succ, (int)j3);
-                        lastj = j3;
-                        if (j == j3) break;
-                    }
+                    sel = wave_chain_walk(succ, (uint32_t)__builtin_ctzll(mask), lastj);
                     last_end = pos + (int)lastj + (int)__builtin_amdgcn_readlane(ml, (int)lastj);
                     mask = 0;
                 }
@@ -794,7 +775,7 @@ __device__ __forceinline__ void match_chunk(const uint8_t *s_data, const uint32_
                 lab_dummy ^= sel ^ ml ^ cand;
                 anchor = last_end;
 #else
-                const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(sel >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sel, 0u));
+                const uint32_t rank = wave_rank(sel);
                 {
                     uint2 e; e.x = (uint32_t)p | (ml << 16); e.y = (uint32_t)p - cand;
                     s_q[hb_select_lane(sel, (uint32_t)nq + rank, (uint32_t)QCAP)] = e;       // (the spare slot: see the run step)
@@ -825,6 +806,17 @@ __device__ __forceinline__ void match_chunk(const uint8_t *s_data, const uint32_
 #ifdef LAB_ENC
         if (lab_dummy == 0x1234567ull) s_out[lane] = 1;     // keeps the ablated computations alive
 #endif
+        // the end of a chunk whose record is complete in itself (SNAPPY, SELF): the rest of s_out goes out, the descriptor says how long the record is
+        auto finish_whole = [&]() __attribute__((always_inline)) {
+            const uint32_t total = rec_done + opend;
+            drain(true);
+            if (lane == 0) {
+                ChunkDesc d;
+                d.lead = 0u; d.enc_len = total; d.last_end = (uint32_t)len; d.mcode0 = 0u;
+                *dsc = d;
+            }
+            wave_sync();
+        };
         if constexpr (SNAPPY) {
             // the rest of the chunk is one literal element; the record is the chunk's complete element stream
             const uint32_t tl = (uint32_t)(len - anchor);
@@ -835,14 +827,7 @@ __device__ __forceinline__ void match_chunk(const uint8_t *s_data, const uint32_
                 wave_sync();
                 stream_literals((uint32_t)anchor, tl);
             }
-            const uint32_t total = rec_done + opend;
-            drain(true);
-            if (lane == 0) {
-                ChunkDesc d;
-                d.lead = 0u; d.enc_len = total; d.last_end = (uint32_t)len; d.mcode0 = 0u;
-                *dsc = d;
-            }
-            wave_sync();
+            finish_whole();
             return;
         }
         if constexpr (SELF) {
@@ -858,14 +843,7 @@ __device__ __forceinline__ void match_chunk(const uint8_t *s_data, const uint32_
             opend += 1u + nb;
             wave_sync();
             stream_literals((uint32_t)anchor, tl);
-            const uint32_t total = rec_done + opend;
-            drain(true);
-            if (lane == 0) {
-                ChunkDesc d;
-                d.lead = 0u; d.enc_len = total; d.last_end = (uint32_t)len; d.mcode0 = 0u;
-                *dsc = d;
-            }
-            wave_sync();
+            finish_whole();
             return;
         }
         const uint32_t enc = rec_done + opend;             // record bytes without the trailing literals

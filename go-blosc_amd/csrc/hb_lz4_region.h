@@ -210,27 +210,9 @@ __device__ __forceinline__ bool sn_rg_fill(const uint8_t *s_in, const uint32_t s
         const uint32_t nrel = cplx ? 64u : (uint32_t)lane + hdr + lit;
         const unsigned long long cmask = hb_ballot(cplx);
         unsigned long long tmask = 0;
-        uint32_t cur;
-        {
-            const uint32_t succ = nrel < 64u ? nrel : (uint32_t)lane;
-            uint32_t j = 0, lastj;
-            for (;;) {
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j));
-                const uint32_t j1 = __builtin_amdgcn_readlane(succ, (int)j);
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j1));
-                const uint32_t j2 = __builtin_amdgcn_readlane(succ, (int)j1);
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j2));
-                const uint32_t j3 = __builtin_amdgcn_readlane(succ, (int)j2);
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j3));
-                j = __builtin_amdgcn_readlane(succ, (int)j3);
-                lastj = j3;
-                if (j == j3) break;
-            }
-            cur = base + __builtin_amdgcn_readlane(nrel, (int)lastj);
-            const unsigned long long cm = tmask & cmask;
-            if (cm) { tmask &= ~cm; cur = base + (uint32_t)__builtin_ctzll(cm); stop = true; }
-        }
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(tmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tmask, 0u));
+        const uint32_t succ = nrel < 64u ? nrel : (uint32_t)lane;
+        const uint32_t cur = dec_walk(succ, nrel, base, cmask, tmask, stop);
+        const uint32_t rank = wave_rank(tmask);
         if ((tmask >> lane) & 1ull) { uint2 e; e.x = p | (hop ? 0x80000000u : 0u); e.y = olen; s_tq[nq + rank] = e; }
         nq += (uint32_t)__builtin_popcountll(tmask);
         si = cur;
@@ -264,28 +246,10 @@ __device__ __forceinline__ bool sn_fill(const uint8_t *s_in, const uint32_t sh, 
         if (nxt > lim) cplx = true;
         const unsigned long long cmask = hb_ballot(cplx);
         unsigned long long tmask = 0;
-        uint32_t cur;
-        {
-            const uint32_t nrel = cplx ? 64u : nxt - base;
-            const uint32_t succ = nrel < 64u ? nrel : (uint32_t)lane;
-            uint32_t j = 0, lastj;
-            for (;;) {
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j));
-                const uint32_t j1 = __builtin_amdgcn_readlane(succ, (int)j);
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j1));
-                const uint32_t j2 = __builtin_amdgcn_readlane(succ, (int)j1);
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j2));
-                const uint32_t j3 = __builtin_amdgcn_readlane(succ, (int)j2);
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j3));
-                j = __builtin_amdgcn_readlane(succ, (int)j3);
-                lastj = j3;
-                if (j == j3) break;
-            }
-            cur = base + __builtin_amdgcn_readlane(nrel, (int)lastj);
-            const unsigned long long cm = tmask & cmask;
-            if (cm) { tmask &= ~cm; cur = base + (uint32_t)__builtin_ctzll(cm); stop = true; }
-        }
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(tmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tmask, 0u));
+        const uint32_t nrel = cplx ? 64u : nxt - base;
+        const uint32_t succ = nrel < 64u ? nrel : (uint32_t)lane;
+        const uint32_t cur = dec_walk(succ, nrel, base, cmask, tmask, stop);
+        const uint32_t rank = wave_rank(tmask);
         if ((tmask >> lane) & 1ull) {
             uint2 e; e.x = lsrc | (lit << 13) | (mlen << 22); e.y = offv | (p << 16);
             s_tq[nq + rank] = e;
@@ -342,10 +306,9 @@ __device__ __forceinline__ bool sn_walk(const uint8_t *__restrict__ src, const u
                 if (cont) mlen = 0u;
                 else if (cp) mlen = incl_end - (incl - mlen);
             }
-            const uint2 rest = s_tq[64 + lane < DTQ ? 64 + lane : 0];
+            const uint2 rest = dec_queue_rest(s_tq, lane);
             if (!batch(cntb, (uint32_t)wpos + tw, (uint32_t)wpos + lw, lit, mlen, off, wsh + lw)) return false;
-            nq -= cntb;
-            if ((uint32_t)lane < nq) s_tq[lane] = rest;
+            dec_queue_shift(s_tq, nq, cntb, rest, lane);
         }
         return true;
     };
@@ -444,21 +407,8 @@ __device__ __forceinline__ bool rg_fill(const uint8_t *s_in, const uint32_t sh, 
         if (last_ntok >= DEC_BPERM_MIN) {
             // the chain of a token-dense window by pointer doubling, as dec_fill_lean follows it (hb_dec_common.h): lane k ends up holding the k-th
             // token's lane and fetches that lane's entry -- the queue is written compacted, no scalar walk, no rank computation
-            const uint32_t s1 = succ;
-            const uint32_t s2 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(s1 << 2), (int)s1);
-            const uint32_t s4 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(s2 << 2), (int)s2);
-            const uint32_t s8 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(s4 << 2), (int)s4);
-            const uint32_t s16 = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(s8 << 2), (int)s8);
-            uint32_t c = 0;
-            { const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(c << 2), (int)s1); c = (lane & 1) ? y : c; }
-            { const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(c << 2), (int)s2); c = (lane & 2) ? y : c; }
-            { const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(c << 2), (int)s4); c = (lane & 4) ? y : c; }
-            { const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(c << 2), (int)s8); c = (lane & 8) ? y : c; }
-            { const uint32_t y = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(c << 2), (int)s16); c = (lane & 16) ? y : c; }
-            const uint32_t left = wave_shr1(c, 0xFFFFFFFFu);
-            const unsigned long long distinct = hb_ballot(c != left) | 0xFFFFFFFF00000000ull;
-            uint32_t ntok = (uint32_t)__builtin_ctzll(~distinct | (1ull << 32));
-            const uint32_t lastj = __builtin_amdgcn_readlane(c, (int)ntok - 1);
+            uint32_t ntok, lastj;
+            const uint32_t c = dec_chain_doubling(succ, lane, ntok, lastj);
             cur = base + __builtin_amdgcn_readlane(nrel, (int)lastj);
             if ((cmask >> lastj) & 1ull) { ntok--; cur = base + lastj; stop = true; }
             uint2 e;
@@ -471,25 +421,8 @@ __device__ __forceinline__ bool rg_fill(const uint8_t *s_in, const uint32_t sh, 
             continue;
         }
 #endif
-        {
-            uint32_t j = 0, lastj;
-            for (;;) {
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j));
-                const uint32_t j1 = __builtin_amdgcn_readlane(succ, (int)j);
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j1));
-                const uint32_t j2 = __builtin_amdgcn_readlane(succ, (int)j1);
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j2));
-                const uint32_t j3 = __builtin_amdgcn_readlane(succ, (int)j2);
-                asm volatile("s_bitset1_b64 %0, %1" : "+s"(tmask) : "s"(j3));
-                j = __builtin_amdgcn_readlane(succ, (int)j3);
-                lastj = j3;
-                if (j == j3) break;
-            }
-            cur = base + __builtin_amdgcn_readlane(nrel, (int)lastj);
-            const unsigned long long cm = tmask & cmask;
-            if (cm) { tmask &= ~cm; cur = base + (uint32_t)__builtin_ctzll(cm); stop = true; }
-        }
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(tmask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)tmask, 0u));
+        cur = dec_walk(succ, nrel, base, cmask, tmask, stop);
+        const uint32_t rank = wave_rank(tmask);
         if ((tmask >> lane) & 1ull) { uint2 e; e.x = p | (nbl << 16); e.y = lit | (mlen << 16); s_tq[nq + rank] = e; }
         last_ntok = (uint32_t)__builtin_popcountll(tmask);
         nq += last_ntok;
@@ -545,10 +478,9 @@ __device__ __forceinline__ bool rg_walk(const uint8_t *__restrict__ src, const u
             const uint32_t tw = e.x & 0xFFFFu, lw = tw + 1u + (e.x >> 16);       // token / first literal, window-relative
             uint32_t off = 0;
             if ((uint32_t)lane < cntb) off = (uint32_t)s_win[wsh + lw + lit] | ((uint32_t)s_win[wsh + lw + lit + 1u] << 8);
-            const uint2 rest = s_tq[64 + lane < DTQ ? 64 + lane : 0];
+            const uint2 rest = dec_queue_rest(s_tq, lane);
             if (!batch(cntb, (uint32_t)wpos + tw, (uint32_t)wpos + lw, lit, mlen, off, wsh + lw)) return false;
-            nq -= cntb;
-            if ((uint32_t)lane < nq) s_tq[lane] = rest;
+            dec_queue_shift(s_tq, nq, cntb, rest, lane);
         }
         return true;
     };

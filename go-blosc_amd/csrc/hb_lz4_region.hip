@@ -161,8 +161,7 @@ __device__ __forceinline__ void rg_parse_region(const uint8_t *__restrict__ src,
                     const bool hit = k < span && s_win[wsh + k] == 0xF4u;
                     const unsigned long long m = hb_ballot(hit);
                     if (!m) continue;
-                    const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-                    if (hit) cl[ncand + rank] = (uint32_t)at + k;
+                    if (hit) cl[ncand + wave_rank(m)] = (uint32_t)at + k;
                     ncand += (uint32_t)__builtin_popcountll(m);
                     if (ncand >= 64u) {
                         wave_sync();
@@ -376,9 +375,7 @@ __device__ __forceinline__ void rg_parse_region(const uint8_t *__restrict__ src,
                     nq -= cntb;
                     ((uint16_t *)s_tq)[lane] = rest;
                 } else {
-                    const uint2 rest = s_tq[64 + lane < DTQ ? 64 + lane : 0];
-                    nq -= cntb;
-                    if ((uint32_t)lane < nq) s_tq[lane] = rest;
+                    dec_queue_shift(s_tq, nq, cntb, lane);
                 }
             }
             if (done) break;
@@ -935,8 +932,7 @@ __device__ __forceinline__ void k_rg_index_fast_body(const uint8_t *__restrict__
             uint2 t = tr[b0 + lane];
             const bool ok = t.x != RG_INVALID && t.x >= pad0 && t.x > start && t.x < exitp;
             const unsigned long long m = hb_ballot(ok);
-            const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-            if (ok) { t.y += adj; s_tr[nu + rank] = t; }
+            if (ok) { t.y += adj; s_tr[nu + wave_rank(m)] = t; }
             nu += (uint32_t)__builtin_popcountll(m);
         }
     }

@@ -221,7 +221,7 @@ __global__ __launch_bounds__(1024) void k_sy_compact(SyPlan *sy, const SyUnit *_
     for (int k = 0; k < 16; k++) { const uint32_t c = s_c[k]; if (k < w) o += c; total += c; }
     for (uint32_t i = 0; i < steps; i++) {
         const unsigned long long m = s_m[w][i];
-        if ((m >> lane) & 1ull) list[o + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = r0 + i * 64u + (uint32_t)lane;
+        if ((m >> lane) & 1ull) list[o + wave_rank(m)] = r0 + i * 64u + (uint32_t)lane;
         o += (uint32_t)__builtin_popcountll(m);
     }
     if (t == 0) {

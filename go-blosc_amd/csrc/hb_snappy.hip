@@ -145,17 +145,12 @@ __global__ __launch_bounds__(64) void k_sn_dec_indexed(const uint8_t *__restrict
 }
 
 // ------------------------------------------------------------------------------------------------------------
-// k_sn_dec_serial: one wavefront, whole block, front to back
+// k_sn_dec_serial: one wavefront, whole block, front to back (window, history and page sized like the LZ4 serial decoder's: SER_* of hb_dec_common.h)
 // ------------------------------------------------------------------------------------------------------------
-#define SNS_WIN   8192u
-#define SNS_HIST  65536u
-#define SNS_PAGE  32768u
-#define SNS_SOFT  16384u
-
 __global__ __launch_bounds__(64) void k_sn_dec_serial(const uint8_t *__restrict__ src, uint64_t n_src, uint8_t *__restrict__ dst, uint64_t cap,
                                                       SnPlan *plan, hb_result *result, int frame, uint32_t expect) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_win[SNS_WIN + 128];
-    __shared__ __attribute__((aligned(16))) uint8_t s_img[SNS_HIST + SNS_PAGE + 1024];
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[SER_WIN + 128];
+    __shared__ __attribute__((aligned(16))) uint8_t s_img[SER_HIST + SER_PAGE + 1024];
     __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
     const int lane = threadIdx.x;
     if ((plan->mode == 1 || plan->mode == 2) && !plan->fail) {
@@ -175,14 +170,14 @@ __global__ __launch_bounds__(64) void k_sn_dec_serial(const uint8_t *__restrict_
         if (lane == 0) { result->flags = 0; result->total_bytes = 0; result->bytes = dlen; result->status = frame ? HB_ERR_SIZE_MISMATCH : HB_ERR_SHORT_BUFFER; }
         return;
     }
-    uint8_t *out = s_img + SNS_HIST;
+    uint8_t *out = s_img + SER_HIST;
     uint64_t gbase = 0, si = hl, wpos = 0;
     uint32_t di = 0, wlen = 0, wsh = 0, nq = 0;
     auto refill = [&](uint64_t at) __attribute__((always_inline)) {
         const uint8_t *g = src + at;
         wsh = (uint32_t)((uintptr_t)g & 15u);
         const uint64_t left = n_src - at;
-        wlen = (uint32_t)(left < (uint64_t)(SNS_WIN - 16u) ? left : (uint64_t)(SNS_WIN - 16u));
+        wlen = (uint32_t)(left < (uint64_t)(SER_WIN - 16u) ? left : (uint64_t)(SER_WIN - 16u));
         const u32x4 *ga = (const u32x4 *)(g - wsh);
         const uint32_t nv = (wsh + wlen + 15u) >> 4;
         wave_sync();
@@ -199,7 +194,7 @@ __global__ __launch_bounds__(64) void k_sn_dec_serial(const uint8_t *__restrict_
         const uint32_t tail0 = fl & ~15u;
         if (tail0 + lane < fl) o[tail0 + lane] = out[tail0 + lane];
         if (!all) {
-            const uint32_t mv = SNS_HIST + (di - fl);
+            const uint32_t mv = SER_HIST + (di - fl);
             for (uint32_t k = lane * 16u; k < mv; k += 1024u) { const u32x4 v = *(const u32x4 *)(s_img + fl + k); *(u32x4 *)(s_img + k) = v; }
             wave_sync();
         }
@@ -209,14 +204,14 @@ __global__ __launch_bounds__(64) void k_sn_dec_serial(const uint8_t *__restrict_
     if (!err) { if (si < n_src) refill(si); else fin = true; }
     while (!err && !fin) {
         if (gbase + di > dlen) { err = 1; break; }
-        if (di >= SNS_SOFT) flush(false);
+        if (di >= SER_SOFT) flush(false);
         if (si == n_src) { fin = true; break; }
         if (si < wpos || si - wpos + 1024u > wlen) { if (si != wpos || wlen == 0) refill(si); }
         uint32_t rel = (uint32_t)(si - wpos);
-        const uint32_t hist = (uint32_t)(gbase < (uint64_t)SNS_HIST ? gbase : (uint64_t)SNS_HIST);
+        const uint32_t hist = (uint32_t)(gbase < (uint64_t)SER_HIST ? gbase : (uint64_t)SER_HIST);
         // ---- fast path: window-parallel parse, lane-parallel copies (offsets inside the LDS history) ----
         const uint64_t left_out = dlen - gbase;
-        const uint32_t room = (uint32_t)(left_out < (uint64_t)SNS_PAGE ? left_out : (uint64_t)SNS_PAGE);
+        const uint32_t room = (uint32_t)(left_out < (uint64_t)SER_PAGE ? left_out : (uint64_t)SER_PAGE);
         const bool stop = sn_fill(s_win, wsh, wlen, rel, nq, s_tq, lane);
         bool rewound = false;
         const uint32_t di0 = di;
@@ -229,7 +224,7 @@ __global__ __launch_bounds__(64) void k_sn_dec_serial(const uint8_t *__restrict_
         } else {
             si = wpos + rel;
             if (rewound) {                                       // an element that does not fit: the page is full, or it passes the declared length
-                if (room < SNS_PAGE) { err = 1; break; }
+                if (room < SER_PAGE) { err = 1; break; }
                 flush(false);
                 continue;
             }
@@ -247,7 +242,7 @@ __global__ __launch_bounds__(64) void k_sn_dec_serial(const uint8_t *__restrict_
             if (e.lit > n_src - si || e.lit > dlen - (gbase + di)) { err = 1; break; }
             uint64_t lrem = e.lit;
             while (lrem) {
-                const uint32_t rm = SNS_PAGE - di;
+                const uint32_t rm = SER_PAGE - di;
                 const uint32_t take = (uint32_t)(lrem < (uint64_t)rm ? lrem : (uint64_t)rm);
                 if (take == 0) { flush(false); continue; }
                 const uint8_t *g = src + si;
@@ -262,12 +257,12 @@ __global__ __launch_bounds__(64) void k_sn_dec_serial(const uint8_t *__restrict_
                 for (uint32_t k = k0 + lane; k < take; k += 64) out[di + k] = g[k];
                 si += take; di += take; lrem -= take;
                 wave_sync();
-                if (di >= SNS_SOFT) flush(false);
+                if (di >= SER_SOFT) flush(false);
             }
         } else {
             const uint64_t produced = gbase + di;
             if (e.off == 0 || e.off > produced || (uint64_t)e.mlen > dlen - produced) { err = 1; break; }
-            if (SNS_PAGE - di < e.mlen) flush(false);
+            if (SER_PAGE - di < e.mlen) flush(false);
             if (e.off <= (uint64_t)di + hist) {
                 wave_sync();
                 dec_match_copy(out, di, (uint32_t)e.off, e.mlen, lane);
@@ -338,9 +333,7 @@ __device__ __forceinline__ bool snr_walk(const uint8_t *__restrict__ src, const 
             f(cnt, ap, olen, out + (incl - olen));
             out += (uint32_t)__builtin_amdgcn_readlane(incl, 63);
             if (over) return true;
-            const uint2 rest = s_tq[64 + lane < DTQ ? 64 + lane : 0];
-            nq -= cntb;
-            if ((uint32_t)lane < nq) s_tq[lane] = rest;
+            dec_queue_shift(s_tq, nq, cntb, lane);
         }
         const bool moved = (wpos + rel) != si;
         si = wpos + rel;
