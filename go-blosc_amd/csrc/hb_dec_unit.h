@@ -60,30 +60,123 @@ struct DecCtx {
     uint32_t nbytes, nunits;
     int bun4, ush;
 };
-// lab ablations of the fused un-shuffle flush (tools/lab/ab.py; the frames decode to garbage under 1 / 2: timing only)
-#if defined(LAB_DEC_FLUSH) && LAB_DEC_FLUSH == 1
-#define LAB_FLUSH_USH() do { } while (0)
-#elif defined(LAB_DEC_FLUSH) && LAB_DEC_FLUSH == 2
-#define LAB_FLUSH_USH() do { for (uint32_t i = lane * 16u; i < outlen; i += 1024u) st16u(dst + d0 + i, *(const u32x4 *)(s_out + i)); } while (0)
-#else
-// (unrolled by eight: the loop control of 64 single-byte rounds is 200 scalar instructions per unit otherwise -- the decoder issues more scalar than vector instructions)
-#define LAB_FLUSH_USH() do { \
-        uint32_t i_ = lane; \
-        for (; i_ + 448u < outlen; i_ += 512u) { \
-            _Pragma("unroll") for (uint32_t k_ = 0; k_ < 8u; k_++) udst[(size_t)(i_ + 64u * k_) * (uint32_t)ush] = s_out[i_ + 64u * k_]; \
-        } \
-        for (; i_ < outlen; i_ += 64) udst[(size_t)i_ * (uint32_t)ush] = s_out[i_]; \
-    } while (0)
+#ifndef DEC_PREFETCH
+#define DEC_PREFETCH 0                   // 1: a unit fetches ahead for the unit its wave takes next (DecPre); built, off until it is measured
 #endif
-__device__ __forceinline__ void dec_unit(const DecCtx &c, const uint32_t u, uint8_t *s_in, uint8_t *s_out, uint2 *s_tq, const int lane) {
+#define DEC_NO_UNIT 0xFFFFFFFFu
+// What a unit fetched ahead for the unit its wave takes next (k_dec_indexed: `it + gridDim.x`), so that a unit does not begin with three
+// memory round trips in a row behind the acknowledgements of the 64 byte stores before it (entries, first window, first parse):
+//   e   : that unit's two index entries, read through the scalar data cache at the head of the unit before it;
+//   win : its first window is in s_in already -- loaded into registers BEFORE the flush stores (the counter of outstanding vector memory
+//         operations is waited for in order: what is issued ahead of the stores does not wait for them), written to s_in after them,
+//         when the parse that used s_in is over.
+// The index is not trusted here either: no address is formed from the entries before the geometry checks of dec_unit have passed on them
+// (a unit whose entries fail gets no window and raises plan->fail on its own turn), and the window is what stage(0) would read.
+struct DecPre {
+    uint32_t u;                              // the unit all this is for, or DEC_NO_UNIT
+    uint32_t e[8];
+    uint32_t win;
+};
+// Wave-uniform reads of memory that nobody writes while the kernel runs (the index, the stream) through the scalar data cache: they are not
+// queued behind the wave's vector stores.  Aligned dwords and shifts, so any byte address; reads at most 3 bytes past the last byte asked
+// for and at most 3 in front of the first.  (Where the compiler cannot see that the address is uniform these are ordinary vector loads.)
+typedef const __attribute__((address_space(4))) uint32_t *dec_cu32p;
+__device__ __forceinline__ void dec_ld_uniform16(const uint8_t *p, uint32_t *o) {
+    const uintptr_t a = (uintptr_t)p;
+    const dec_cu32p q = (dec_cu32p)(a & ~(uintptr_t)3);
+    const uint32_t sh = ((uint32_t)a & 3u) * 8u;
+    const uint32_t w0 = q[0], w1 = q[1], w2 = q[2], w3 = q[3];
+    uint32_t w4 = w3;
+    if (sh != 0u) w4 = q[4];
+    const uint32_t r0 = sh ? (uint32_t)((((uint64_t)w1 << 32) | w0) >> sh) : w0, r1 = sh ? (uint32_t)((((uint64_t)w2 << 32) | w1) >> sh) : w1;
+    const uint32_t r2 = sh ? (uint32_t)((((uint64_t)w3 << 32) | w2) >> sh) : w2, r3 = sh ? (uint32_t)((((uint64_t)w4 << 32) | w3) >> sh) : w3;
+    // (the callers' state machines run on the scalar side: the values are uniform whether the compiler can see it or not)
+    o[0] = (uint32_t)__builtin_amdgcn_readfirstlane((int)r0); o[1] = (uint32_t)__builtin_amdgcn_readfirstlane((int)r1);
+    o[2] = (uint32_t)__builtin_amdgcn_readfirstlane((int)r2); o[3] = (uint32_t)__builtin_amdgcn_readfirstlane((int)r3);
+}
+__device__ __forceinline__ uint32_t dec_ld_uniform1(const uint8_t *p) {
+    const uintptr_t a = (uintptr_t)p;
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)((*(dec_cu32p)(a & ~(uintptr_t)3) >> (((uint32_t)a & 3u) * 8u)) & 255u));
+}
+
+// The fused un-shuffle flush: byte i of the chunk image goes to udst[i * ush].  The address is affine in the lane -- udst + lane * ush,
+// then 64 * ush further per round -- so one 64-bit base serves a group of DEC_FLUSH_GROUP stores whose distances are immediate offsets when
+// the typesize is known at compile time (USH > 0; the offsets stay below the 4 KiB an instruction can carry), and nothing is multiplied
+// per store.  USH < 0: the typesize is a run-time value (`ush`); the base advances by additions.
+// (groups, not one loop of 64 single-byte rounds: the loop control would be 200 scalar instructions per unit -- the decoder issues more
+// scalar than vector instructions)
+// lab ablations (tools/lab/ab.py; the frames decode to garbage under them: timing only): LAB_DEC_FLUSH 1 = no flush, 2 = 16-byte stores
+// `after()` runs behind the last store on every path (dec_unit: the prefetched window goes to s_in).  A whole unit -- every unit of a
+// well-formed frame -- is flushed without a loop: the number of stores between a load issued before the flush and after() is then a
+// constant the compiler can wait by.
+template <int USH, class F>
+__device__ __forceinline__ void dec_flush_ush(uint8_t *udst, const uint8_t *s_out, const uint32_t outlen, const int lane, const uint32_t ush_rt, F &&after) {
+#if defined(LAB_DEC_FLUSH) && LAB_DEC_FLUSH == 1
+    after();
+#elif defined(LAB_DEC_FLUSH) && LAB_DEC_FLUSH == 2
+    for (uint32_t i = lane * 16u; i < outlen; i += 1024u) st16u(udst + i, *(const u32x4 *)(s_out + i));
+    after();
+#else
+    const uint32_t ush = USH > 0 ? (uint32_t)USH : ush_rt;
+    constexpr uint32_t G = USH == 4 ? 8u : 16u;             // stores per base: 8 * 64 * 4 = 2 KiB, 16 * 64 * 2 = 2 KiB
+    const uint32_t step = 64u * ush;
+    uint8_t *p = udst + (uint32_t)lane * ush;
+    const uint8_t *q = s_out + lane;
+#if DEC_PREFETCH
+    if (USH > 0 && outlen == DEC_OUT_MAX) {
+#pragma unroll
+        for (uint32_t g = 0; g < DEC_OUT_MAX / (64u * G); g++) {
+#pragma unroll
+            for (uint32_t k = 0; k < G; k++) p[k * step] = q[64u * k];
+            p += G * step; q += 64u * G;
+        }
+        after();
+        return;
+    }
+#endif
+    uint32_t i = 0;
+    for (; i + 64u * G <= outlen; i += 64u * G) {
+#pragma unroll
+        for (uint32_t k = 0; k < G; k++) p[k * step] = q[64u * k];
+        p += G * step; q += 64u * G;
+    }
+    for (i += (uint32_t)lane; i < outlen; i += 64u) { *p = *q; p += step; q += 64; }
+    after();
+#endif
+}
+// USH / BUN4: the un-filter that is fused into the unit's flush, known at compile time (USH = 0, 2, 4: byte un-shuffle with that typesize;
+// BUN4: bit-unshuffle with typesize 4), or -1 / -1: whatever the context says (batches mix frames; k_dec_indexed's other typesizes).
+// u_next: the unit of the same context that this wave takes next, or DEC_NO_UNIT; pre: in, what the unit before fetched (for `u`, or it is
+// not used); out, what this unit fetched for u_next.
+template <int USH, int BUN4>
+__device__ __forceinline__ void dec_unit(const DecCtx &c, const uint32_t u, uint8_t *s_in, uint8_t *s_out, uint2 *s_tq, const int lane,
+                                         const uint32_t u_next, DecPre &pre) {
     const uint8_t *const src = c.src; const uint64_t n_src = c.n_src; uint8_t *const dst = c.dst; const uint8_t *const ent = c.ent;
-    DecPlan *const plan = c.plan; const uint32_t nbytes = c.nbytes, nunits = c.nunits; const int bun4 = c.bun4, ush = c.ush;
-    const u32x4 e0 = ld16u(ent + 16 * (size_t)u), e1 = ld16u(ent + 16 * (size_t)(u + 1));
+    DecPlan *const plan = c.plan; const uint32_t nbytes = c.nbytes, nunits = c.nunits;
+    const int bun4 = BUN4 < 0 ? c.bun4 : BUN4, ush = USH < 0 ? c.ush : USH;
     // wave-uniform values that come out of vector loads are moved to scalar registers: the compiler cannot know
     // they are uniform, and would otherwise run the whole state machine on the vector side under exec masks
 #define RFL(x) ((uint32_t)__builtin_amdgcn_readfirstlane((int)(x)))
+#if DEC_PREFETCH
+#define DEC_LD_BYTE(p) dec_ld_uniform1(p)
+    uint32_t e[8];
+    const bool have = pre.u == u;
+    const bool staged0 = have && pre.win != 0u;             // stage(0) is done
+    if (have) { for (int k = 0; k < 8; k++) e[k] = pre.e[k]; }
+    else { dec_ld_uniform16(ent + 16 * (size_t)u, e); dec_ld_uniform16(ent + 16 * (size_t)(u + 1), e + 4); }
+    pre.u = DEC_NO_UNIT; pre.win = 0u;
+    const uint32_t s0 = e[0], d0 = e[1], s1 = e[4], d1 = e[5], rem1 = e[6], tok1 = e[7];
+    uint32_t rem = e[2], tokpos = e[3];
+    // the next unit's entries: under way while this unit works (u_next < nunits: both lie inside the nunits + 1 entries)
+    uint32_t en[8];
+    if (u_next != DEC_NO_UNIT) { dec_ld_uniform16(ent + 16 * (size_t)u_next, en); dec_ld_uniform16(ent + 16 * (size_t)(u_next + 1u), en + 4); }
+#else
+#define DEC_LD_BYTE(p) RFL((uint32_t)*(p))
+    const bool staged0 = false;
+    const u32x4 e0 = ld16u(ent + 16 * (size_t)u), e1 = ld16u(ent + 16 * (size_t)(u + 1));
     const uint32_t s0 = RFL(e0.x), d0 = RFL(e0.y), s1 = RFL(e1.x), d1 = RFL(e1.y), rem1 = RFL(e1.z), tok1 = RFL(e1.w);
     uint32_t rem = RFL(e0.z), tokpos = RFL(e0.w);
+#endif
     const bool last = (u + 1 == nunits);
     bool ok = s0 <= s1 && s1 <= n_src && d0 <= d1 && d1 <= nbytes && (d1 - d0) <= DEC_OUT_MAX;
     if (u == 0) ok = ok && s0 == 0 && d0 == 0 && rem == HB_IDX_AT_TOKEN;
@@ -97,6 +190,36 @@ __device__ __forceinline__ void dec_unit(const DecCtx &c, const uint32_t u, uint
     if (!ok) { if (lane == 0) atomicExch(&plan->fail, 1u); return; }
     const uint32_t slen = s1 - s0, outlen = d1 - d0;
     const uint8_t *g = src + s0;
+    // fetch ahead: pf_issue() before this unit's stores, pf_commit() behind them, when s_in is no longer read (DecPre)
+    u32x4 pv0 = {0u, 0u, 0u, 0u}, pv1 = {0u, 0u, 0u, 0u};
+    uint32_t pnv = 0;                                       // vectors of the next unit's first window that are under way
+    auto pf_issue = [&]() __attribute__((always_inline)) {
+#if DEC_PREFETCH
+        if (u_next == DEC_NO_UNIT) return;
+        pre.u = u_next;
+        for (int k = 0; k < 8; k++) pre.e[k] = en[k];
+        const uint32_t ns0 = en[0], nd0 = en[1], nrem = en[2], ns1 = en[4], nd1 = en[5];
+        if (!(ns0 <= ns1 && ns1 <= n_src && nd0 <= nd1 && nd1 <= nbytes && (nd1 - nd0) <= DEC_OUT_MAX)) return;   // not a slice of src: no address from it
+        if (nrem != HB_IDX_AT_TOKEN && nrem >= nd1 - nd0) return;                                                  // literal-only: stages nothing
+        const uint8_t *ng = src + ns0;                      // exactly stage(0)'s vectors: aligned, at most 15 bytes past the slice
+        const uint32_t nsh = (uint32_t)((uintptr_t)ng & 15u);
+        const uint32_t avail = nsh + (ns1 - ns0);
+        pnv = ((avail < DEC_IN_WIN ? avail : DEC_IN_WIN) + 15u) >> 4;
+        const u32x4 *ga = (const u32x4 *)(ng - nsh);
+        if ((uint32_t)lane < pnv) pv0 = ga[lane];
+        if ((uint32_t)lane + 64u < pnv) pv1 = ga[lane + 64];
+#endif
+    };
+    auto pf_commit = [&]() __attribute__((always_inline)) {
+#if DEC_PREFETCH
+        if (pnv == 0u) return;
+        wave_sync();
+        if ((uint32_t)lane < pnv) ((u32x4 *)s_in)[lane] = pv0;
+        if ((uint32_t)lane + 64u < pnv) ((u32x4 *)s_in)[lane + 64] = pv1;
+        pre.win = 1u;
+        wave_sync();
+#endif
+    };
 
     // the whole unit lies inside one literal run (incompressible chunk): HBM -> HBM, no LDS
     if (rem != HB_IDX_AT_TOKEN && rem >= outlen) {
@@ -104,7 +227,7 @@ __device__ __forceinline__ void dec_unit(const DecCtx &c, const uint32_t u, uint
         bool fine = slen == outlen;
         // a block that ends inside/after a literal run is accepted only if that token announces no match
         // (UncompressBlock: si == len(src) && matchNibble == 0; oracle/blosc_oracle.c ob_lz4_decompress) -- else the serial decoder decides
-        if (last) fine = fine && left == 0 && (RFL((uint32_t)src[tokpos]) & 15u) == 0u; else fine = fine && rem1 == left && tok1 == tokpos;
+        if (last) fine = fine && left == 0 && (DEC_LD_BYTE(src + tokpos) & 15u) == 0u; else fine = fine && rem1 == left && tok1 == tokpos;
         if (!fine) { if (lane == 0) atomicExch(&plan->fail, 1u); return; }
         if (ush) {                                          // wide loads (any alignment) into the image, then the strided stores
             for (uint32_t i = lane * 16u; i < outlen; i += 1024u) {
@@ -112,10 +235,13 @@ __device__ __forceinline__ void dec_unit(const DecCtx &c, const uint32_t u, uint
                 else for (uint32_t r = i; r < outlen; r++) s_out[r] = g[r];
             }
             wave_sync();
-            LAB_FLUSH_USH();
+            pf_issue();
+            dec_flush_ush<USH>(udst, s_out, outlen, lane, (uint32_t)ush, pf_commit);
             wave_sync();
+            return;
         }
-        else if (!bun4) wave_copy_g2g(dst + d0, g, outlen, lane);
+        pf_issue();
+        if (!bun4) wave_copy_g2g(dst + d0, g, outlen, lane);
         else {
             for (uint32_t w = lane; w < outlen / 32u; w += 64) {
                 u32x4 oa, ob;
@@ -124,6 +250,7 @@ __device__ __forceinline__ void dec_unit(const DecCtx &c, const uint32_t u, uint
                 st16u(dst + d0 + 32u * w + 16u, ob);
             }
         }
+        pf_commit();
         return;
     }
 
@@ -132,22 +259,22 @@ __device__ __forceinline__ void dec_unit(const DecCtx &c, const uint32_t u, uint
     const uint32_t sh = (uint32_t)((uintptr_t)g & 15u);
     uint32_t wlo = 0, staged = 0;                           // the window holds slice positions [wlo, staged)
     int shw = 0;                                            // LDS index of slice position p = p + shw
-    auto stage = [&](const uint32_t at) __attribute__((always_inline)) {
+    auto stage = [&](const uint32_t at, const bool there = false) __attribute__((always_inline)) {     // there: the unit before did the loads
         wave_sync();
         const uint32_t a16 = (sh + at) & ~15u;
         const uint32_t avail = sh + slen - a16;
         const uint32_t cnt = avail < DEC_IN_WIN ? avail : DEC_IN_WIN;
         const u32x4 *ga = (const u32x4 *)(g - sh + a16);
         const uint32_t nv = (cnt + 15u) >> 4;
-        for (uint32_t i = lane; i < nv; i += 64) ((u32x4 *)s_in)[i] = ga[i];
+        if (!there) for (uint32_t i = lane; i < nv; i += 64) ((u32x4 *)s_in)[i] = ga[i];
         wlo = a16 > sh ? a16 - sh : 0u;
         staged = a16 + cnt - sh;
         shw = (int)sh - (int)a16;
         wave_sync();
     };
-    stage(0u);
+    stage(0u, staged0);
     uint32_t tok = 0;
-    if (rem != HB_IDX_AT_TOKEN) tok = RFL((uint32_t)src[tokpos]);
+    if (rem != HB_IDX_AT_TOKEN) tok = DEC_LD_BYTE(src + tokpos);
 #define INB(i) s_in[(uint32_t)((int)(i) + shw)]              /* stream byte at slice position i (inside the window) */
     uint32_t si = 0, di = 0;
     bool at_token = false;       // state when the unit stops
@@ -230,6 +357,7 @@ __device__ __forceinline__ void dec_unit(const DecCtx &c, const uint32_t u, uint
     }
     if (!ok) { if (lane == 0) atomicExch(&plan->fail, 1u); wave_sync(); return; }
     wave_sync();
+    pf_issue();
     if (bun4) {                                             // fused bit-unshuffle: every window in place
         for (uint32_t w = lane; w < outlen / 32u; w += 64) {
             u32x4 oa, ob;
@@ -241,7 +369,7 @@ __device__ __forceinline__ void dec_unit(const DecCtx &c, const uint32_t u, uint
     }
     // flush the chunk image
     if (ush) {
-        LAB_FLUSH_USH();
+        dec_flush_ush<USH>(udst, s_out, outlen, lane, (uint32_t)ush, pf_commit);
     } else {
         uint8_t *o = dst + d0;
         uint32_t head = (uint32_t)((16u - ((uintptr_t)o & 15u)) & 15u);
@@ -262,6 +390,8 @@ __device__ __forceinline__ void dec_unit(const DecCtx &c, const uint32_t u, uint
         }
         const uint32_t done_b = head + body * 16u;
         if (done_b + lane < outlen) o[done_b + lane] = s_out[done_b + lane];
+        pf_commit();
     }
     wave_sync();
 }
+#undef DEC_LD_BYTE

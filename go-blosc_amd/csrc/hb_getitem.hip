@@ -78,7 +78,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEC_WAVES)))
         DecCtx c; c.src = src; c.n_src = n_src; c.ent = ent; c.plan = plan; c.nbytes = g.nbytes; c.nunits = nunits; c.bun4 = 0; c.ush = 0;
         // dec_unit writes unit u to dst + dst_off(u) = dst + 4096 u: slot k of range j
         c.dst = (uint8_t *)((uintptr_t)stage + ((size_t)j * g.upp + k) * HB_CHUNK - (size_t)HB_CHUNK * u);
-        dec_unit(c, u, s_in, s_out, s_tq, lane);
+        DecPre pre; pre.u = DEC_NO_UNIT; pre.win = 0u;
+        dec_unit<0, 0>(c, u, s_in, s_out, s_tq, lane, DEC_NO_UNIT, pre);
     }
 }
 

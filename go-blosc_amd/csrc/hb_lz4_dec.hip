@@ -36,9 +36,12 @@ __global__ void k_dec_plan(const uint8_t *__restrict__ index, uint64_t index_byt
     dec_plan_check(index, index_bytes, n_src, cap, plan, result);
 }
 
+// USH / BUN4: the fused un-filter as template arguments (dec_unit): the launcher picks the instantiation; <-1, -1> takes the two arguments
+template <int USH, int BUN4>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEC_WAVES))) void k_dec_indexed(const uint8_t *__restrict__ src, uint64_t n_src,
                                                     uint8_t *__restrict__ dst, const uint8_t *__restrict__ index,
-                                                    DecPlan *plan, int bun4, int ush, uint32_t plane_mask) {
+                                                    DecPlan *plan, int bun4_rt, int ush_rt, uint32_t plane_mask) {
+    const int bun4 = BUN4 < 0 ? bun4_rt : BUN4, ush = USH < 0 ? ush_rt : USH;
     // ush != 0: the frame was byte-shuffled with typesize `ush` and has only whole planes of whole chunks; the un-shuffle is
     // fused: a unit is a piece of ONE byte plane j, and its byte i goes straight to dst[(e0 + i) * ush + j] with byte
     // stores (64 lanes cover 64 * ush bytes; the other planes' waves fill in the rest of those lines, and the
@@ -66,10 +69,12 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEC_WAVES)))
     // units are independent.
     const uint32_t P = plan->stride;                        // computed once by k_dec_plan
     const uint32_t mgrp = (nunits + 7u) / 8u;
-    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
+    // the unit of work item `it`, or DEC_NO_UNIT (padding of the last group of 8, a masked plane, past the end)
+    auto unit_of = [&](const uint32_t it) __attribute__((always_inline)) -> uint32_t {
+        if (it >= mgrp * 8u) return DEC_NO_UNIT;
         uint32_t u = (uint32_t)(((uint64_t)(it >> 3) * P) % mgrp) * 8u + ((it + (it >> 3)) & 7u);
         const bool fused_order = ush && nunits % (uint32_t)ush == 0u && (gridDim.x % (8u * (uint32_t)ush) == 0u || gridDim.x >= nunits);
-        if (fused_order ? it >= nunits : u >= nunits) continue;
+        if (fused_order ? it >= nunits : u >= nunits) return DEC_NO_UNIT;
         if (fused_order) {
             // fused un-shuffle: the `ush` units that make up one 4096-element block write interleaved bytes of the same
             // lines, so they get workgroup ids that are equal mod 8 (same XCD under round-robin placement: the
@@ -83,10 +88,18 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEC_WAVES)))
                 b = grp * 8u + k % nb; j = k / nb;
             }
             u = j * nblk + b;
-            if (!((plane_mask >> j) & 1u)) continue;            // hb_debug_plane_mask: per-plane timing
+            if (!((plane_mask >> j) & 1u)) return DEC_NO_UNIT;  // hb_debug_plane_mask: per-plane timing
         }
-        DecCtx c; c.src = src; c.n_src = n_src; c.dst = dst; c.ent = ent; c.plan = plan; c.nbytes = nbytes; c.nunits = nunits; c.bun4 = bun4; c.ush = ush;
-        dec_unit(c, u, s_in, s_out, s_tq, lane);
+        return u;
+    };
+    DecCtx c; c.src = src; c.n_src = n_src; c.dst = dst; c.ent = ent; c.plan = plan; c.nbytes = nbytes; c.nunits = nunits; c.bun4 = bun4; c.ush = ush;
+    DecPre pre; pre.u = DEC_NO_UNIT; pre.win = 0u;
+    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
+        const uint32_t u = unit_of(it);
+        if (u == DEC_NO_UNIT) continue;
+        // the unit this wave takes next is known now: this one fetches ahead for it (DecPre)
+        const uint32_t u_next = DEC_PREFETCH ? unit_of(it + gridDim.x) : DEC_NO_UNIT;
+        dec_unit<USH, BUN4>(c, u, s_in, s_out, s_tq, lane, u_next, pre);
     }
 }
 
@@ -134,7 +147,8 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEC_WAVES)))
             u = j * nblk + b;
         }
         if (u >= c.nunits) continue;
-        dec_unit(c, u, s_in, s_out, s_tq, lane);
+        DecPre pre; pre.u = DEC_NO_UNIT; pre.win = 0u;
+        dec_unit<-1, -1>(c, u, s_in, s_out, s_tq, lane, DEC_NO_UNIT, pre);         // (a batch mixes frames: the fused mode is the frame's; no fetching ahead across them)
     }
 }
 
@@ -254,8 +268,17 @@ int hb_launch_lz4_decode(const hb_dec_args &a, hipStream_t s) {
             if (g2) grid = g2;
         }
         hb_prof_begin("k_dec_indexed", s);
-        hipLaunchKernelGGL(k_dec_indexed, dim3(grid), dim3(64), 0, s, a.src, (uint64_t)a.n, a.dst, index, plan,
-                           a.fused_bitunshuffle4, a.fused_unshuffle_ts, hb_dbg_plane_mask());
+        // one instantiation per fused mode that frames have (at most one of the two un-filters is fused); any other typesize (the lab's
+        // typesize-8 switch) goes through the run-time one
+#define HB_LAUNCH_DEC(USH, BUN4) hipLaunchKernelGGL((k_dec_indexed<USH, BUN4>), dim3(grid), dim3(64), 0, s, a.src, (uint64_t)a.n, a.dst, index, plan, \
+                                                    a.fused_bitunshuffle4, a.fused_unshuffle_ts, hb_dbg_plane_mask())
+        if (a.fused_bitunshuffle4 && !a.fused_unshuffle_ts) HB_LAUNCH_DEC(0, 1);
+        else if (a.fused_bitunshuffle4) HB_LAUNCH_DEC(-1, -1);
+        else if (a.fused_unshuffle_ts == 0) HB_LAUNCH_DEC(0, 0);
+        else if (a.fused_unshuffle_ts == 2) HB_LAUNCH_DEC(2, 0);
+        else if (a.fused_unshuffle_ts == 4) HB_LAUNCH_DEC(4, 0);
+        else HB_LAUNCH_DEC(-1, -1);
+#undef HB_LAUNCH_DEC
         hb_prof_end(s);
     }
     // with a fused un-filter the indexed decoder wrote FINAL bytes to a.dst; the serial decoder (if it has to run)
