@@ -528,4 +528,76 @@ int hb_decompress_frames_batch(int nframes, const void *const *frame, const size
     return HB_OK;
 }
 
+// Many ranges of many frames (include/hipblosc.h): the frames that a job reads go up once each, the device form runs once, the result records
+// come down in one copy and the ranges in one copy (their device buffer is packed: job j's bytes follow job j - 1's).  Whatever did not end
+// with status 0 on the device -- refusals, hand-overs, ZSTD frames -- is answered by hb_getitem_frame, so that rc[j] is its answer in every case.
+int hb_getitem_frames_batch(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_getitem_job *jobs, void *const *dst, const size_t *cap,
+                            int64_t *rc, uint32_t *flags, int typesize_override, int device) {
+    if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
+    if (njobs == 0) return HB_OK;
+    if (!frame || !n || !jobs || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
+    for (int j = 0; j < njobs; j++)
+        if (jobs[j].frame >= (uint32_t)nframes || jobs[j].reserved != 0u) return HB_ERR_BAD_ARG;
+    auto single = [&](int j) {
+        const hb_getitem_job &q = jobs[j];
+        rc[j] = hb_getitem_frame(frame[q.frame], n[q.frame], q.start, q.nitems, dst[j], cap[j], typesize_override, device);
+        if (flags) flags[j] = rc[j] >= 0 ? hb_last_result_flags() : 0u;
+    };
+    auto all_single = [&]() { for (int j = 0; j < njobs; j++) single(j); return HB_OK; };
+    // headers (a frame that does not parse keeps a zeroed record, which the device form refuses job by job), and which frames are read at all
+    std::vector<hb_header> hd((size_t)nframes, hb_header{});
+    std::vector<uint8_t> parsed((size_t)nframes, 0), used((size_t)nframes, 0);
+    for (int k = 0; k < nframes; k++)
+        parsed[(size_t)k] = frame[k] && n[k] >= HB_HEADER_SIZE && hb_parse_header(frame[k], n[k], &hd[(size_t)k]) == HB_OK && !hb_frame_host_codec(hd[(size_t)k]);
+    // bytes of every job the device can take: place in the packed destination
+    std::vector<size_t> ooff((size_t)njobs, 0), nb((size_t)njobs, 0);
+    size_t out_bytes = 0;
+    bool any = false;
+    for (int j = 0; j < njobs; j++) {
+        const hb_getitem_job &q = jobs[j];
+        int ts = 1;
+        if (!parsed[q.frame] || hb_getitem_check(&hd[q.frame], n[q.frame], q.start, q.nitems, typesize_override, 0, &ts) != HB_OK) continue;
+        nb[(size_t)j] = (size_t)q.nitems * (size_t)ts;
+        if (cap[j] < nb[(size_t)j] || (!dst[j] && nb[(size_t)j])) { nb[(size_t)j] = 0; continue; }
+        ooff[(size_t)j] = out_bytes; out_bytes += nb[(size_t)j];
+        used[q.frame] = 1; any = true;
+    }
+    if (!any || hb_select_device(device) != HB_OK) return all_single();
+    std::vector<int> idx;
+    for (int k = 0; k < nframes; k++) if (used[(size_t)k]) idx.push_back(k);
+    const bool span_in = exactly_adjacent(idx, frame, n);
+    std::vector<size_t> ioff((size_t)nframes, 0);
+    size_t in_bytes = 0;
+    for (int k : idx) { ioff[(size_t)k] = in_bytes; in_bytes += span_in ? n[k] : al256(n[k] + 64); }
+    const size_t wb = hb_getitem_frames_batch_workspace(nframes, hd.data(), n, njobs, jobs, typesize_override);
+    if (!wb) return all_single();                                       // (a batch beyond the 32-bit limits: one call per job is still right)
+    Scratch sc(device);
+    uint8_t *d_in = sc.get(in_bytes + 256), *d_out = sc.get(out_bytes + 256), *d_work = sc.get(wb), *d_res = sc.get((size_t)njobs * sizeof(hb_result));
+    auto fail_all = [&]() { for (int j = 0; j < njobs; j++) { rc[j] = HB_ERR_HIP; if (flags) flags[j] = 0; } return HB_OK; };
+    if (!d_in || !d_out || !d_work || !d_res) return fail_all();
+    if (span_in && hipMemcpyAsync(d_in, frame[idx[0]], in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
+    std::vector<const void *> pf((size_t)nframes, nullptr);
+    for (int k : idx) {
+        pf[(size_t)k] = d_in + ioff[(size_t)k];
+        if (!span_in && hipMemcpyAsync(d_in + ioff[(size_t)k], frame[k], n[k], hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
+    }
+    // (a frame that is not uploaded keeps a NULL pointer: its jobs end with a status on the device and are answered one by one)
+    std::vector<void *> pd((size_t)njobs, nullptr);
+    for (int j = 0; j < njobs; j++) if (nb[(size_t)j] || (dst[j] && used[jobs[j].frame])) pd[(size_t)j] = d_out + ooff[(size_t)j];
+    const int st = hb_getitem_frames_batch_device(nframes, hd.data(), pf.data(), n, njobs, jobs, pd.data(), cap, typesize_override, d_work, wb, (hb_result *)d_res, nullptr);
+    if (st) { for (int j = 0; j < njobs; j++) { rc[j] = st; if (flags) flags[j] = 0; } return HB_OK; }
+    std::vector<hb_result> res((size_t)njobs);
+    if (hipMemcpy(res.data(), d_res, (size_t)njobs * sizeof(hb_result), hipMemcpyDeviceToHost) != hipSuccess) return fail_all();
+    std::vector<uint8_t> host(out_bytes);
+    if (out_bytes && hipMemcpy(host.data(), d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail_all();
+    for (int j = 0; j < njobs; j++) {
+        const hb_result &r = res[(size_t)j];
+        if (r.status != HB_OK) { single(j); continue; }
+        if (r.bytes) memcpy(dst[j], host.data() + ooff[(size_t)j], (size_t)r.bytes);
+        rc[j] = (int64_t)r.bytes;
+        if (flags) flags[j] = r.flags;
+    }
+    return HB_OK;
+}
+
 }  // extern "C"

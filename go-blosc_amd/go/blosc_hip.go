@@ -449,6 +449,107 @@ func GetItem(data []byte, start, nitems int64, typeSize int) ([]byte, error) {
 	return buf[:n], nil
 }
 
+// GetItemJob is one range of GetItemBatchHIP: items [Start, Start+NItems) of frames[Frame].
+type GetItemJob struct {
+	Frame         int
+	Start, NItems int64
+}
+
+// GetItemBatchHIP answers many GetItem calls through ONE set of kernel launches (hb_getitem_frames_batch): what a chunked array store asks
+// for -- a slice crosses hundreds of chunk frames with one range in each, a fancy index asks for hundreds of small ranges of the same few
+// frames.  Every frame goes up once however many jobs read it; out[j] / errs[j] are what GetItem(frames[Frame], Start, NItems, typeSize) would
+// have returned for job j.  Go memory is borrowed for the call only (pinned slabs and C arrays, never Go pointers in C memory).  Like the rest
+// of this file: written against the C ABI, it has never met a compiler.
+func GetItemBatchHIP(frames [][]byte, jobs []GetItemJob, typeSize int) ([][]byte, []error) {
+	nj, nf := len(jobs), len(frames)
+	out := make([][]byte, nj)
+	errs := make([]error, nj)
+	if nj == 0 {
+		return out, errs
+	}
+	single := func() ([][]byte, []error) {
+		for j, q := range jobs {
+			if q.Frame < 0 || q.Frame >= nf {
+				errs[j] = hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+				continue
+			}
+			out[j], errs[j] = GetItem(frames[q.Frame], q.Start, q.NItems, typeSize)
+		}
+		return out, errs
+	}
+	if !useHIP || nf == 0 {
+		return single()
+	}
+	for _, q := range jobs {
+		if q.Frame < 0 || q.Frame >= nf {
+			return single()
+		}
+	}
+	ptrBytes := C.size_t(unsafe.Sizeof(uintptr(0)))
+	srcs := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(nf) * ptrBytes))[:nf:nf]
+	dsts := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(nj) * ptrBytes))[:nj:nj]
+	defer C.free(unsafe.Pointer(&srcs[0]))
+	defer C.free(unsafe.Pointer(&dsts[0]))
+	lens := make([]C.size_t, nf)
+	caps := make([]C.size_t, nj)
+	rcs := make([]C.int64_t, nj)
+	jt := make([]C.hb_getitem_job, nj)
+	var inBytes, outBytes C.size_t
+	for k, f := range frames {
+		lens[k] = C.size_t(len(f))
+		inBytes += lens[k] // tightly packed: frames that follow each other exactly go up in ONE copy
+	}
+	for j, q := range jobs {
+		ts := int64(typeSize)
+		if ts <= 0 && len(frames[q.Frame]) >= HeaderSize {
+			ts = int64(frames[q.Frame][3])
+		}
+		if ts <= 0 {
+			ts = 1
+		}
+		if q.NItems > 0 && q.NItems <= (1<<32)/ts { // (a range no frame can hold is refused by the library: no room is needed for it)
+			caps[j] = C.size_t(q.NItems * ts)
+		}
+		outBytes += caps[j] + 1
+		jt[j].frame = C.uint32_t(q.Frame)
+		jt[j].start = C.int64_t(q.Start)
+		jt[j].nitems = C.int64_t(q.NItems)
+	}
+	slabIn, slabOut := C.hb_host_alloc(inBytes+64), C.hb_host_alloc(outBytes+64)
+	if slabIn == nil || slabOut == nil {
+		C.hb_host_free(slabIn)
+		C.hb_host_free(slabOut)
+		return single()
+	}
+	defer C.hb_host_free(slabIn)
+	defer C.hb_host_free(slabOut)
+	var io, oo C.size_t
+	for k, f := range frames {
+		srcs[k] = unsafe.Add(slabIn, uintptr(io))
+		copy(unsafe.Slice((*byte)(srcs[k]), len(f)), f)
+		io += lens[k]
+	}
+	for j := range jobs {
+		dsts[j] = unsafe.Add(slabOut, uintptr(oo))
+		oo += caps[j] + 1
+	}
+	if rc := C.hb_getitem_frames_batch(C.int(nf), &srcs[0], &lens[0], C.int(nj), &jt[0], &dsts[0], &caps[0], &rcs[0], nil,
+		C.int(typeSize), C.int(Device)); rc != C.HB_OK {
+		for j := range jobs {
+			errs[j] = hbError(C.int64_t(rc))
+		}
+		return out, errs
+	}
+	for j := range jobs {
+		if rcs[j] < 0 {
+			errs[j] = hbError(rcs[j])
+		} else {
+			out[j] = append([]byte(nil), unsafe.Slice((*byte)(dsts[j]), int(rcs[j]))...)
+		}
+	}
+	return out, errs
+}
+
 // ---------------------------------------------------------------------------------------------
 // C-Blosc-1 wire format (what README.md:20 promises; blosc.go has no code for it): frames c-blosc 1.x, python-blosc,
 // numcodecs read and write.  An extension next to CompressHIP / DecompressHIP, not a seam of the reference.

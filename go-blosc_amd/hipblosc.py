@@ -100,6 +100,7 @@ EXPORTS = [
     "hb_compress_frames_batch_workspace", "hb_compress_frames_batch_dev", "hb_frames_batch_headers_dev",
     "hb_decompress_frames_batch_workspace", "hb_decompress_frames_batch_dev", "hb_compress_frames_batch", "hb_decompress_frames_batch",
     "hb_getitem_frame", "hb_getitem_frame_workspace", "hb_getitem_frame_device", "hb_cblosc_getitem", "hb_cblosc_getitem_workspace", "hb_cblosc_getitem_device",
+    "hb_getitem_frames_batch_workspace", "hb_getitem_frames_batch_device", "hb_getitem_frames_batch",
     "hb_queue_create", "hb_queue_create_ex", "hb_queue_destroy", "hb_queue_compress", "hb_queue_decompress", "hb_queue_wait",
 ]
 
@@ -113,6 +114,10 @@ class hb_header(ctypes.Structure):
 class hb_result(ctypes.Structure):
     _fields_ = [("status", ctypes.c_int32), ("flags", ctypes.c_uint32), ("bytes", ctypes.c_uint64),
                 ("total_bytes", ctypes.c_uint64), ("reserved", ctypes.c_uint64)]
+
+
+class hb_getitem_job(ctypes.Structure):
+    _fields_ = [("frame", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("start", ctypes.c_int64), ("nitems", ctypes.c_int64)]
 
 
 _lib = None
@@ -177,6 +182,9 @@ def lib():
             "hb_cblosc_getitem": (i64, [vp, sz, i64, i64, vp, sz, i32]),
             "hb_cblosc_getitem_workspace": (sz, [vp, i64, i64]),
             "hb_cblosc_getitem_device": (i32, [vp, vp, sz, i64, i64, vp, sz, vp, sz, vp, vp]),
+            "hb_getitem_frames_batch_workspace": (sz, [i32, vp, vp, i32, vp, i32]),
+            "hb_getitem_frames_batch_device": (i32, [i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, sz, vp, vp]),
+            "hb_getitem_frames_batch": (i32, [i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -317,6 +325,31 @@ def GetItem(data, start, nitems, typeSize=0):
     out = ctypes.create_string_buffer(max(cap, 1))
     rc = _check(lib().hb_getitem_frame(p, n, int(start), int(nitems), ctypes.cast(out, ctypes.c_void_p), cap, typeSize, device))
     return out.raw[:rc]
+
+
+def GetItemBatch(frames, jobs, typeSize=0, dev=None):
+    """Many GetItem calls through one set of launches (include/hipblosc.h hb_getitem_frames_batch): `jobs` are (frame_index, start, nitems)
+    tuples over `frames`; the i-th result is what GetItem(frames[f], start, nitems, typeSize) would have returned for the i-th job -- the
+    bytes, or the error (returned, not raised, as DecompressBatch does)."""
+    jobs = list(jobs)
+    nj, nf = len(jobs), len(frames)
+    if nj == 0:
+        return []
+    keep = [_buf(f) for f in frames]
+    caps = []
+    for f, start, nitems in jobs:
+        ts = typeSize if typeSize > 0 else 1
+        if typeSize <= 0 and 0 <= f < nf and keep[f][1] >= HeaderSize:
+            ts = bytes(keep[f][2][3:4])[0] or 1
+        caps.append(max(int(nitems), 0) * ts)
+    outs = [(ctypes.c_char * max(c, 1))() for c in caps]
+    jt = (hb_getitem_job * nj)(*[hb_getitem_job(int(f), 0, int(s), int(k)) for f, s, k in jobs])
+    fr = (ctypes.c_void_p * max(nf, 1))(*[k[0].value for k in keep])
+    ns = (ctypes.c_size_t * max(nf, 1))(*[k[1] for k in keep])
+    dsts = (ctypes.c_void_p * nj)(*[ctypes.addressof(o) for o in outs])
+    rcs = (ctypes.c_int64 * nj)()
+    _check(lib().hb_getitem_frames_batch(nf, fr, ns, nj, jt, dsts, (ctypes.c_size_t * nj)(*caps), rcs, None, int(typeSize), device if dev is None else dev))
+    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(nj)]
 
 
 def GetInfo(data):                                                  # blosc.go:306-308

@@ -128,6 +128,29 @@ inline Bytes GetItem(const uint8_t *data, size_t n, int64_t start, int64_t nitem
     return out;
 }
 inline Bytes GetItem(const Bytes &data, int64_t start, int64_t nitems, int typeSize = 0) { return GetItem(data.data(), data.size(), start, nitems, typeSize); }
+// many GetItem calls through one set of launches (hb_getitem_frames_batch): job j = items [start, start + nitems) of frames[frame]; out[j] is
+// what GetItem would have returned for it, rc[j] the byte count or the HB_ERR_* code GetItem would have thrown (nothing is thrown per job)
+struct GetItemJob { uint32_t frame; int64_t start, nitems; };
+inline std::vector<Bytes> GetItemBatch(const std::vector<Bytes> &frames, const std::vector<GetItemJob> &jobs, std::vector<int64_t> &rc, int typeSize = 0, int device = 0) {
+    const size_t nf = frames.size(), nj = jobs.size();
+    std::vector<Bytes> out(nj);
+    rc.assign(nj, 0);
+    if (!nj) return out;
+    std::vector<const void *> fr(nf); std::vector<size_t> ns(nf);
+    for (size_t k = 0; k < nf; k++) { fr[k] = frames[k].data(); ns[k] = frames[k].size(); }
+    std::vector<hb_getitem_job> jt(nj); std::vector<void *> dst(nj); std::vector<size_t> cap(nj);
+    for (size_t j = 0; j < nj; j++) {
+        jt[j] = hb_getitem_job{jobs[j].frame, 0u, jobs[j].start, jobs[j].nitems};
+        size_t ts = typeSize > 0 ? (size_t)typeSize : 1;
+        if (typeSize <= 0 && jobs[j].frame < nf && ns[jobs[j].frame] >= (size_t)HeaderSize && frames[jobs[j].frame][3]) ts = frames[jobs[j].frame][3];
+        cap[j] = jobs[j].nitems > 0 ? (size_t)jobs[j].nitems * ts : 0;
+        out[j].resize(cap[j] ? cap[j] : 1);
+        dst[j] = out[j].data();
+    }
+    check(hb_getitem_frames_batch((int)nf, fr.data(), ns.data(), (int)nj, jt.data(), dst.data(), cap.data(), rc.data(), nullptr, typeSize, device));
+    for (size_t j = 0; j < nj; j++) out[j].resize(rc[j] > 0 ? (size_t)rc[j] : 0);
+    return out;
+}
 inline Header GetInfo(const Bytes &data) { return ParseHeader(data); }                                            // blosc.go:306-308
 inline int GetDecompressedSize(const Bytes &data) { return (int)ParseHeader(data).NBytesOrig; }                   // blosc.go:311-317
 

@@ -224,6 +224,46 @@ int     hb_getitem_frame_device(const hb_header *hdr, const void *d_frame, size_
                                 void *d_dst, size_t cap, int typesize_override,
                                 void *d_work, size_t work_bytes, hb_result *d_result, void *stream);
 
+/* ---- batched getitem: many item ranges of many go-blosc frames through ONE set of launches (plan, units, one gather per kind that occurs,
+ *      finish -- the same number of launches for 4 jobs and for 4096).  What chunked array stores ask for: a slice crosses hundreds of chunk
+ *      frames with one range in each, a fancy index asks for hundreds of small ranges of the same few frames; one hb_getitem_frame call per
+ *      range is launch-bound.  Job j = items [start, start + nitems) of frame `frame` (an index into the frame arrays, which are thereby the
+ *      de-duplication: a frame that many jobs read is passed, and uploaded, once).
+ *      Device form (rules of hb_getitem_frame_device: d_frame / d_dst are HOST arrays of device pointers, asynchronous on `stream`, no
+ *      synchronisation, no caller pointer kept, sources may be read up to 15 bytes past their end, d_work 256-byte aligned).  d_results: njobs
+ *      records in device or pinned memory.  Job j writes exactly nitems * ts bytes of d_dst[j] and nothing else; jobs whose destinations overlap
+ *      are the caller's error.  The outcome of job j is defined against hb_getitem_frame_device(&hdrs[f], d_frame[f], n[f], start, nitems,
+ *      d_dst[j], cap[j], typesize_override, <small workspace>):
+ *        - what that call refuses as its return value (header errors in their order, HB_ERR_BAD_ARG for the range, HB_ERR_SHORT_BUFFER for the
+ *          capacity, HB_ERR_BAD_ARG for a NULL d_frame[f] / d_dst[j]) is d_results[j].status, flags and bytes 0; the other jobs are not disturbed;
+ *        - path 1 (LZ4 / LZ4HC frame with the trailer) and path 2 (memcpy frame): the bytes, status 0, flags 0x3 / 0x2;
+ *        - a frame that can only take path 3 (no trailer, Snappy) and a path-1 job whose index or units do not verify on the device: status
+ *          HB_ERR_SHORT_BUFFER, flags 0, d_dst[j] unspecified inside nitems * ts bytes -- the hand-over of the one-job call: take THIS job
+ *          through hb_getitem_frame_device with the full workspace.  The whole-frame decode is never enqueued inside the batch.
+ *      The fail state is per job, not per frame: a damaged unit spoils the jobs that need it and no other job, also not on the same frame
+ *      ("what a call does not touch it does not check", job by job).  Ranges of different jobs that overlap decode their shared units twice.
+ *      The call itself returns HB_ERR_BAD_ARG for NULL arrays, nframes / njobs < 0, a job whose frame >= nframes or whose reserved != 0, a
+ *      misaligned d_work, or a batch beyond HB_GETITEM_BATCH_MAX_WORK (split it); HB_ERR_SHORT_BUFFER for work_bytes below the workspace query;
+ *      then HB_ERR_NO_DEVICE; HB_OK for njobs == 0 (nothing is launched).
+ *      Workspace: the job records, one plan per job and the staging areas of the path-1 jobs: at most the sum of hb_getitem_frame_workspace(full = 0)
+ *      over the jobs + HB_GETITEM_BATCH_JOB_BYTES * njobs; it does not grow with nbytes for frames with a trailer.  0 when the call would
+ *      return an error as a whole.
+ *      Host form: every frame that a job reads goes up once, the device form runs once, all result records come down in one copy and all ranges
+ *      in one copy from a packed device buffer.  Every job that did not end with status 0 there (refusals, hand-overs, ZSTD frames) is then
+ *      answered by hb_getitem_frame, one call each: rc[j] is always exactly what hb_getitem_frame returns for that job, flags[j] (flags may be
+ *      NULL) its hb_result.flags (0 for a job that failed).  Returns HB_OK unless the arguments as a whole are unusable. ---- */
+#define HB_GETITEM_BATCH_MAX_WORK  0x7FFFFFFFu   /* work items of the unit kernel (units x planes over all jobs), and blocks of any one gather kind: 32-bit prefixes */
+#define HB_GETITEM_BATCH_JOB_BYTES 2048          /* workspace per job beyond its one-job small size */
+typedef struct hb_getitem_job { uint32_t frame; uint32_t reserved; int64_t start, nitems; } hb_getitem_job;   /* frame: index into the frame arrays; reserved: 0 */
+size_t hb_getitem_frames_batch_workspace(int nframes, const hb_header *hdrs, const size_t *n,
+                                         int njobs, const hb_getitem_job *jobs, int typesize_override);
+int    hb_getitem_frames_batch_device(int nframes, const hb_header *hdrs, const void *const *d_frame, const size_t *n,
+                                      int njobs, const hb_getitem_job *jobs, void *const *d_dst, const size_t *cap,
+                                      int typesize_override, void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
+int    hb_getitem_frames_batch(int nframes, const void *const *frame, const size_t *n,
+                               int njobs, const hb_getitem_job *jobs, void *const *dst, const size_t *cap,
+                               int64_t *rc, uint32_t *flags /* may be NULL */, int typesize_override, int device);
+
 /* batches of independent frames, frame k -> device k mod hb_device_count(): what a caller with an
  * 8 GiB array does (8 frames of <= 4 GiB - 1, blosc.go:159-161: the sizes are uint32), one Compress / Decompress call
  * (blosc.go:257-303) per frame.  One host thread per device, each with its own hb_queue of 3 frames in flight; no
