@@ -18,6 +18,7 @@
 //              those of hb_decompress_frame_dev (blosc.go:377-434).
 #include "hb_sym_decode.h"
 #include "hb_frame_plan.h"
+#include "hb_cblosc_batch.h"
 #include <vector>
 #include <algorithm>
 #include <cstring>
@@ -597,6 +598,58 @@ int hb_getitem_frames_batch(int nframes, const void *const *frame, const size_t 
         rc[j] = (int64_t)r.bytes;
         if (flags) flags[j] = r.flags;
     }
+    return HB_OK;
+}
+
+// Many C-Blosc-1 frames (include/hipblosc.h).  cbb_host_plan (hb_cblosc_batch.h) says which frames the batch carries and where they lie; whatever
+// it does not carry, and whatever did not end with status 0 on the device, is answered by hb_cblosc_decompress, so that rc[k] is its answer
+// in every case.
+int hb_cblosc_decompress_frames_batch(int nframes, const void *const *frame, const size_t *n, void *const *dst, const size_t *cap, int64_t *rc, int device) {
+    if (nframes < 0) return HB_ERR_BAD_ARG;
+    if (nframes == 0) return HB_OK;
+    if (!frame || !n || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
+    auto single = [&](int k) { rc[k] = hb_cblosc_decompress(frame[k], n[k], dst[k], cap[k], device); };
+    CbbHostPlan P;
+    cbb_host_plan(nframes, frame, n, dst, cap, P);
+    const int m = (int)P.idx.size();
+    std::vector<uint8_t> carried((size_t)nframes, 0);
+    for (int k : P.idx) carried[(size_t)k] = 1;
+    for (int k = 0; k < nframes; k++) if (!carried[(size_t)k]) single(k);
+    if (m == 0) return HB_OK;
+    auto rest_single = [&]() { for (int k : P.idx) single(k); return HB_OK; };
+    if (hb_select_device(device) != HB_OK) return rest_single();
+    const size_t wb = hb_cblosc_decompress_frames_batch_workspace(m, P.hd.data(), P.ns.data());
+    if (!wb) return rest_single();                                       // (a batch beyond the 32-bit limits: one call per frame is still right)
+    auto fail_all = [&]() { for (int k : P.idx) rc[k] = HB_ERR_HIP; return HB_OK; };
+    Scratch sc(device);
+    uint8_t *d_in = sc.get(P.in_bytes + 256), *d_out = sc.get(P.out_bytes + 256), *d_work = sc.get(wb), *d_res = sc.get((size_t)m * sizeof(hb_result));
+    if (!d_in || !d_out || !d_work || !d_res) return fail_all();
+    if (P.span_in && hipMemcpyAsync(d_in, frame[P.idx[0]], P.in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
+    if (P.span_out && P.span_bytes && hipMemsetAsync(d_out, 0, P.span_bytes, nullptr) != hipSuccess) return fail_all();
+    std::vector<const void *> pf((size_t)m); std::vector<void *> pd((size_t)m);
+    for (int i = 0; i < m; i++) {
+        pf[(size_t)i] = d_in + P.ioff[(size_t)i]; pd[(size_t)i] = d_out + P.ooff[(size_t)i];
+        if (!P.span_in && hipMemcpyAsync(d_in + P.ioff[(size_t)i], frame[P.idx[(size_t)i]], P.ns[(size_t)i], hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
+    }
+    const int st = hb_cblosc_decompress_frames_batch_device(m, P.hd.data(), pf.data(), P.ns.data(), pd.data(), P.caps.data(), d_work, wb, (hb_result *)d_res, nullptr);
+    if (st) { for (int k : P.idx) rc[k] = st; return HB_OK; }
+    std::vector<hb_result> res((size_t)m);
+    if (hipMemcpy(res.data(), d_res, (size_t)m * sizeof(hb_result), hipMemcpyDeviceToHost) != hipSuccess) return fail_all();
+    bool all_ok = true;
+    for (int i = 0; i < m; i++) all_ok = all_ok && res[(size_t)i].status == HB_OK;
+    if (P.span_out && all_ok) {                                           // (a failed frame's buffer must keep what the caller had in it: copy per frame then)
+        if (P.span_bytes && hipMemcpy(dst[P.idx[0]], d_out, P.span_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail_all();
+        for (int i = 0; i < m; i++) rc[P.idx[(size_t)i]] = (int64_t)res[(size_t)i].bytes;
+        return HB_OK;
+    }
+    for (int i = 0; i < m; i++) {
+        const int k = P.idx[(size_t)i];
+        const hb_result &r = res[(size_t)i];
+        rc[k] = r.status ? (int64_t)r.status : (int64_t)r.bytes;
+        if (r.status == HB_OK && r.bytes && hipMemcpyAsync(dst[k], pd[(size_t)i], (size_t)r.bytes, hipMemcpyDeviceToHost, nullptr) != hipSuccess) rc[k] = HB_ERR_HIP;
+    }
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return fail_all();
+    for (int i = 0; i < m; i++) if (res[(size_t)i].status != HB_OK) single(P.idx[(size_t)i]);
     return HB_OK;
 }
 

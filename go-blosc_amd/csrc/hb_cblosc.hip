@@ -19,30 +19,14 @@
 // only: the other codec formats are entropy coders or blosclz.
 #include "hb_sym_decode.h"
 
-#define CB_FLAG_SHUFFLE    0x01u
-#define CB_FLAG_MEMCPY     0x02u
-#define CB_FLAG_BITSHUFFLE 0x04u
-#define CB_FLAG_DONTSPLIT  0x10u
-
-// blosc_d of c-blosc 1.x splits a block into `typesize` streams only when ALL of these hold (the rule from before the 0x10 flag existed stays
-// in force next to it: frames of c-blosc < 1.15 have the bit clear and large typesizes / small blocks unsplit; checked against libblosc 1.21):
-// not-split bit clear, typesize <= MAX_SPLITS (16), blocksize / typesize >= MIN_BUFFERSIZE (128), not the last, shorter block.
-__host__ __device__ static inline uint32_t cb_nsplit(uint32_t flags, uint32_t typesize, uint32_t blocksize) {
-    return (!(flags & 0x10u) && typesize >= 1u && typesize <= 16u && blocksize / typesize >= 128u) ? typesize : 1u;
-}
-
-struct CbStream { uint32_t src, csize, dst, usize; };
-struct CbPlan { uint32_t fail, nblocks, nsplit, pad; };
-
-static inline size_t cb_align(size_t b) { return (b + 255) & ~(size_t)255; }
+#include <cstring>
+#include "hb_cblosc_batch.h"       // the flags, cb_nsplit, CbStream / CbPlan, and the host side of the batch
 
 // ---- the streams of blocks [b0, b0 + nb) (hb_cblosc_getitem_device: the blocks that cover a range; the others' bstarts entries and streams
 // are never read); stream offsets count from the first of these blocks ----
-__global__ void k_cb_plan(const uint8_t *__restrict__ frame, uint64_t n, uint32_t nbytes, uint32_t blocksize, uint32_t cbytes, uint32_t typesize, uint32_t flags,
-                          CbPlan *plan, CbStream *streams, uint32_t b0, uint32_t nb) {
+__device__ __forceinline__ void cb_plan_block(const uint8_t *__restrict__ frame, uint32_t nbytes, uint32_t blocksize, uint32_t cbytes, uint32_t typesize, uint32_t flags,
+                                              CbPlan *plan, CbStream *streams, uint32_t b0, uint32_t idx) {
     const uint32_t nblocks = (nbytes + blocksize - 1) / blocksize;
-    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= nb) return;
     const uint32_t b = b0 + idx;
     const uint32_t leftover = nbytes % blocksize;
     const bool lastshort = b + 1 == nblocks && leftover != 0u;
@@ -65,12 +49,43 @@ __global__ void k_cb_plan(const uint8_t *__restrict__ frame, uint64_t n, uint32_
     }
     if (bad) atomicExch(&plan->fail, 1u);
 }
+__global__ void k_cb_plan(const uint8_t *__restrict__ frame, uint64_t n, uint32_t nbytes, uint32_t blocksize, uint32_t cbytes, uint32_t typesize, uint32_t flags,
+                          CbPlan *plan, CbStream *streams, uint32_t b0, uint32_t nb) {
+    const uint32_t idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= nb) return;
+    cb_plan_block(frame, nbytes, blocksize, cbytes, typesize, flags, plan, streams, b0, idx);
+}
 
 #define CB_SMALL_IN 3072u        // longest stream k_cb_decode_small stages (see there)
 // ---- one wavefront per stream ----
+// (the bodies are device functions: the one-frame kernels pass their own frame, plan and target, the batch kernels k_cbb_* those of the frame
+// that owns the stream.  Everything they are given is wave-uniform, and so is every way out of them.)
+// stream i of the permuted order: stream i is byte plane i % typesize of its block, workgroup it runs on XCD it % 8, and the planes differ
+// several times in cost -- in stream order two XCDs would get all the streams of the token-dense plane (measured: 3.1 ms against 1.5).
+// Workgroup (step k = it / 8, XCD x = it % 8) takes stream 8 * (k * P mod m) + (x + k) % 8; grid a multiple of 8.
+__device__ __forceinline__ uint32_t cb_stream_of(uint32_t it, uint32_t mgrp, uint32_t P) {
+    return (uint32_t)(((uint64_t)(it >> 3) * P) % mgrp) * 8u + ((it + (it >> 3) + it / gridDim.x) & 7u);
+}
+__device__ __forceinline__ CbStream cb_load_stream(const CbStream *__restrict__ streams, uint32_t i) {
+    CbStream st = streams[i];                                                  // wave-uniform, but it comes out of a vector load: to scalar registers
+    st.src = RFL(st.src); st.csize = RFL(st.csize); st.dst = RFL(st.dst); st.usize = RFL(st.usize);
+    return st;
+}
 // The decoder is pass A of the symbolic decoder without the symbols (hb_sym_decode.h): 13 KiB of LDS per wavefront -- an image of the last
 // 4 KiB of output, older sources read back from HBM -- so that a dozen streams per CU are in flight.  (First version: the serial
 // block decoder with its 64 KiB history in LDS, one wavefront per CU: 21 GB/s on 256 MiB of float32.)
+__device__ __forceinline__ void cb_decode_stream(const uint8_t *__restrict__ frame, CbPlan *plan, const CbStream st, uint8_t *dst, int small_elsewhere,
+                                                 uint8_t *s_win, uint2 *s_tq, uint8_t *s_d, int lane) {
+    if (st.usize == 0u) return;
+    if (st.csize == st.usize) { wave_copy_g2g(dst + st.dst, frame + st.src, st.usize, lane); return; }      // stored
+    if (small_elsewhere && st.usize <= HB_CHUNK && st.csize <= CB_SMALL_IN) return;      // k_cb_decode_small has it
+    uint32_t out = st.dst;
+    bool parked;
+    const bool ok = sy_decode_unit<false>(frame + st.src, (uint64_t)st.csize, 0u, st.csize, st.dst, st.dst, out, dst, nullptr, s_win, s_tq, s_d, nullptr,
+                                          lane, 1, 0u, 0u, nullptr, nullptr, nullptr, parked, st.dst + st.usize);
+    if ((!ok || out != st.dst + st.usize) && lane == 0) atomicExch(&plan->fail, 1u);     // blosc_d: "nbytes != neblock -> -2"
+    wave_sync();
+}
 __global__ __launch_bounds__(64) void k_cb_decode(const uint8_t *__restrict__ frame, CbPlan *plan, const CbStream *__restrict__ streams, uint32_t nstreams,
                                                    uint8_t *dst, int small_elsewhere, uint32_t P) {
     __shared__ __attribute__((aligned(16))) uint8_t s_win[RG_PWIN + 128];
@@ -78,24 +93,12 @@ __global__ __launch_bounds__(64) void k_cb_decode(const uint8_t *__restrict__ fr
     __shared__ __attribute__((aligned(16))) uint8_t s_d[SY_IMG + 64];
     const int lane = threadIdx.x;
     if (plan->fail) return;
-    // stream order: see k_cb_decode_small (stream i is byte plane i % typesize of its block, workgroup i runs on XCD i % 8, and the
-    // planes differ several times in cost); one stream per workgroup up to 65536 streams, so that a finished cheap stream makes
-    // room for the next one
+    // one stream per workgroup up to 65536 streams, so that a finished cheap stream makes room for the next one
     const uint32_t mgrp = (nstreams + 7u) / 8u;
     for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
-        const uint32_t i = (uint32_t)(((uint64_t)(it >> 3) * P) % mgrp) * 8u + ((it + (it >> 3) + it / gridDim.x) & 7u);
+        const uint32_t i = cb_stream_of(it, mgrp, P);
         if (i >= nstreams) continue;
-        CbStream st = streams[i];                                              // wave-uniform, but it comes out of a vector load: to scalar registers
-        st.src = RFL(st.src); st.csize = RFL(st.csize); st.dst = RFL(st.dst); st.usize = RFL(st.usize);
-        if (st.usize == 0u) continue;
-        if (st.csize == st.usize) { wave_copy_g2g(dst + st.dst, frame + st.src, st.usize, lane); continue; }      // stored
-        if (small_elsewhere && st.usize <= HB_CHUNK && st.csize <= CB_SMALL_IN) continue;   // k_cb_decode_small has it
-        uint32_t out = st.dst;
-        bool parked;
-        const bool ok = sy_decode_unit<false>(frame + st.src, (uint64_t)st.csize, 0u, st.csize, st.dst, st.dst, out, dst, nullptr, s_win, s_tq, s_d, nullptr,
-                                              lane, 1, 0u, 0u, nullptr, nullptr, nullptr, parked, st.dst + st.usize);
-        if ((!ok || out != st.dst + st.usize) && lane == 0) atomicExch(&plan->fail, 1u);     // blosc_d: "nbytes != neblock -> -2"
-        wave_sync();
+        cb_decode_stream(frame, plan, cb_load_stream(streams, i), dst, small_elsewhere, s_win, s_tq, s_d, lane);
     }
 }
 
@@ -103,6 +106,53 @@ __global__ __launch_bounds__(64) void k_cb_decode(const uint8_t *__restrict__ fr
 // fit into LDS, so the chunk decoder's machinery applies as it is -- window-parallel token parser, one token per lane, copies inside
 // the LDS image in dependency rounds (hb_dec_common.h) -- at 17 wavefronts per CU.  k_cb_decode leaves these streams alone.
 #define CB_SMALL HB_CHUNK
+__device__ __forceinline__ void cb_decode_small_stream(const uint8_t *__restrict__ frame, CbPlan *plan, const CbStream st, uint8_t *__restrict__ dst,
+                                                       uint8_t *s_in, uint8_t *s_out, uint2 *s_tq, int lane) {
+    if (st.usize == 0u || st.usize > CB_SMALL || st.csize == st.usize || st.csize > CB_SMALL_IN) return;      // (stored streams: k_cb_decode copies them)
+    const uint8_t *g = frame + st.src;
+    const uint32_t sh = (uint32_t)((uintptr_t)g & 15u), slen = st.csize;           // slen < usize <= 4096
+    wave_sync();
+    {
+        const u32x4 *ga = (const u32x4 *)(g - sh);
+        const uint32_t nv = (sh + slen + 15u) >> 4;
+        for (uint32_t k = lane; k < nv; k += 64) ((u32x4 *)s_in)[k] = ga[k];
+    }
+    wave_sync();
+    uint32_t si = 0, di = 0, nq = 0;
+    bool ok = true, done = false;
+    while (ok && !done) {
+        const bool stop = dec_fill(s_in, sh, slen, slen, si, nq, s_tq, lane);
+        bool rewound = false;
+        if (!dec_drain(s_in, (int)sh, s_out, st.usize, 0u, di, si, nq, s_tq, stop, rewound, lane) || rewound) { ok = false; break; }      // (64 at a time; all of them when the parser stopped)
+        if (si == slen) { done = true; break; }
+        if (!stop) continue;
+        // one sequence the slow way: a length extension of several bytes, or the end of the stream
+        const uint32_t tok = RFL((uint32_t)s_in[sh + si]);
+        si++;
+        uint32_t ll = tok >> 4;
+        if (ll == 15u && !dec_read_ext(s_in, (int)sh, 0u, slen, g, slen, si, ll, lane)) { ok = false; break; }
+        if (ll > slen - si || ll > st.usize - di) { ok = false; break; }
+        for (uint32_t k = lane; k < ll; k += 64) s_out[di + k] = s_in[sh + si + k];
+        si += ll; di += ll;
+        if (si == slen) { if (tok & 15u) ok = false; done = true; break; }            // the final, literal-only sequence
+        if (slen - si < 2u) { ok = false; break; }
+        const uint32_t off = RFL((uint32_t)s_in[sh + si] | ((uint32_t)s_in[sh + si + 1u] << 8));
+        si += 2u;
+        uint32_t ml = (tok & 15u) + 4u;
+        if ((tok & 15u) == 15u && !dec_read_ext(s_in, (int)sh, 0u, slen, g, slen, si, ml, lane)) { ok = false; break; }
+        if (off == 0u || off > di || ml > st.usize - di) { ok = false; break; }
+        wave_sync();
+        dec_match_copy(s_out, di, off, ml, lane);
+        di += ml;
+        wave_sync();
+    }
+    if (!ok || di != st.usize) { if (lane == 0) atomicExch(&plan->fail, 1u); return; }
+    wave_sync();
+    uint8_t *o = dst + st.dst;
+    for (uint32_t k = (uint32_t)lane * 16u; k + 16u <= st.usize; k += 1024u) st16u(o + k, *(const u32x4 *)(s_out + k));
+    const uint32_t t0 = st.usize & ~15u;
+    if (t0 + (uint32_t)lane < st.usize) o[t0 + lane] = s_out[t0 + lane];
+}
 __global__ __launch_bounds__(64) void k_cb_decode_small(const uint8_t *__restrict__ frame, CbPlan *plan, const CbStream *__restrict__ streams, uint32_t nstreams,
                                                          uint8_t *__restrict__ dst, uint32_t P) {
     __shared__ __attribute__((aligned(16))) uint8_t s_in[CB_SMALL_IN + 64 + 128];
@@ -110,68 +160,22 @@ __global__ __launch_bounds__(64) void k_cb_decode_small(const uint8_t *__restric
     __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
     const int lane = threadIdx.x;
     if (plan->fail) return;
-    // stream order as in k_dec_indexed (hb_lz4_dec.hip): the streams of a split block are its byte planes, stream i = plane i % typesize,
-    // and workgroup i runs on XCD i % 8 -- in stream order two XCDs would get all the streams of the token-dense plane (measured: 3.1 ms
-    // against 1.5).  Workgroup (step k = it / 8, XCD x = it % 8) takes stream 8 * (k * P mod m) + (x + k) % 8; grid a multiple of 8.
-    const uint32_t mgrp = (nstreams + 7u) / 8u;
+    const uint32_t mgrp = (nstreams + 7u) / 8u;                                // (stream order as in k_dec_indexed, hb_lz4_dec.hip: cb_stream_of)
     for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
-        const uint32_t i = (uint32_t)(((uint64_t)(it >> 3) * P) % mgrp) * 8u + ((it + (it >> 3) + it / gridDim.x) & 7u);
+        const uint32_t i = cb_stream_of(it, mgrp, P);
         if (i >= nstreams) continue;
-        CbStream st = streams[i];                                              // wave-uniform, but it comes out of a vector load: to scalar registers
-        st.src = RFL(st.src); st.csize = RFL(st.csize); st.dst = RFL(st.dst); st.usize = RFL(st.usize);
-        if (st.usize == 0u || st.usize > CB_SMALL || st.csize == st.usize || st.csize > CB_SMALL_IN) continue;      // (stored streams: k_cb_decode copies them)
-        const uint8_t *g = frame + st.src;
-        const uint32_t sh = (uint32_t)((uintptr_t)g & 15u), slen = st.csize;           // slen < usize <= 4096
-        wave_sync();
-        {
-            const u32x4 *ga = (const u32x4 *)(g - sh);
-            const uint32_t nv = (sh + slen + 15u) >> 4;
-            for (uint32_t k = lane; k < nv; k += 64) ((u32x4 *)s_in)[k] = ga[k];
-        }
-        wave_sync();
-        uint32_t si = 0, di = 0, nq = 0;
-        bool ok = true, done = false;
-        while (ok && !done) {
-            const bool stop = dec_fill(s_in, sh, slen, slen, si, nq, s_tq, lane);
-            bool rewound = false;
-            if (!dec_drain(s_in, (int)sh, s_out, st.usize, 0u, di, si, nq, s_tq, stop, rewound, lane) || rewound) { ok = false; break; }      // (64 at a time; all of them when the parser stopped)
-            if (si == slen) { done = true; break; }
-            if (!stop) continue;
-            // one sequence the slow way: a length extension of several bytes, or the end of the stream
-            const uint32_t tok = RFL((uint32_t)s_in[sh + si]);
-            si++;
-            uint32_t ll = tok >> 4;
-            if (ll == 15u && !dec_read_ext(s_in, (int)sh, 0u, slen, g, slen, si, ll, lane)) { ok = false; break; }
-            if (ll > slen - si || ll > st.usize - di) { ok = false; break; }
-            for (uint32_t k = lane; k < ll; k += 64) s_out[di + k] = s_in[sh + si + k];
-            si += ll; di += ll;
-            if (si == slen) { if (tok & 15u) ok = false; done = true; break; }            // the final, literal-only sequence
-            if (slen - si < 2u) { ok = false; break; }
-            const uint32_t off = RFL((uint32_t)s_in[sh + si] | ((uint32_t)s_in[sh + si + 1u] << 8));
-            si += 2u;
-            uint32_t ml = (tok & 15u) + 4u;
-            if ((tok & 15u) == 15u && !dec_read_ext(s_in, (int)sh, 0u, slen, g, slen, si, ml, lane)) { ok = false; break; }
-            if (off == 0u || off > di || ml > st.usize - di) { ok = false; break; }
-            wave_sync();
-            dec_match_copy(s_out, di, off, ml, lane);
-            di += ml;
-            wave_sync();
-        }
-        if (!ok || di != st.usize) { if (lane == 0) atomicExch(&plan->fail, 1u); continue; }
-        wave_sync();
-        uint8_t *o = dst + st.dst;
-        for (uint32_t k = (uint32_t)lane * 16u; k + 16u <= st.usize; k += 1024u) st16u(o + k, *(const u32x4 *)(s_out + k));
-        const uint32_t t0 = st.usize & ~15u;
-        if (t0 + (uint32_t)lane < st.usize) o[t0 + lane] = s_out[t0 + lane];
+        cb_decode_small_stream(frame, plan, cb_load_stream(streams, i), dst, s_in, s_out, s_tq, lane);
     }
 }
 
 // ---- the per-block filters, undone ----
+// (bodies with their workgroup index `bx` and grid size `gx`: the one-frame kernels pass blockIdx.x / gridDim.x, k_cbb_unfilter the workgroup's
+// place among those of its frame)
 // byte shuffle: block bytes [plane 0 | plane 1 | ...] -> elements; one thread per element (typesize 4 / 8: one store)
-__global__ void k_cb_unshuffle(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nbytes, uint32_t blocksize, uint32_t ts) {
+__device__ __forceinline__ void cb_unshuffle(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nbytes, uint32_t blocksize, uint32_t ts, uint32_t bx, uint32_t gx) {
     const uint32_t nblocks = (nbytes + blocksize - 1) / blocksize;
     const uint32_t per = blocksize / ts + 1u;                                          // threads per block: elements + one for the tail
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (uint64_t)nblocks * per; i += (uint64_t)gridDim.x * blockDim.x) {
+    for (uint64_t i = (uint64_t)bx * blockDim.x + threadIdx.x; i < (uint64_t)nblocks * per; i += (uint64_t)gx * blockDim.x) {
         const uint32_t b = (uint32_t)(i / per), e = (uint32_t)(i % per);
         const uint32_t base = b * blocksize, bsize = nbytes - base < blocksize ? nbytes - base : blocksize, nel = bsize / ts;
         if (e < nel) {
@@ -184,11 +188,14 @@ __global__ void k_cb_unshuffle(uint8_t *__restrict__ dst, const uint8_t *__restr
         }
     }
 }
+__global__ void k_cb_unshuffle(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nbytes, uint32_t blocksize, uint32_t ts) {
+    cb_unshuffle(dst, src, nbytes, blocksize, ts, blockIdx.x, gridDim.x);
+}
 // bit shuffle: one thread per group of 8 elements
-__global__ void k_cb_bitunshuffle(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nbytes, uint32_t blocksize, uint32_t ts) {
+__device__ __forceinline__ void cb_bitunshuffle(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nbytes, uint32_t blocksize, uint32_t ts, uint32_t bx, uint32_t gx) {
     const uint32_t nblocks = (nbytes + blocksize - 1) / blocksize;
     const uint32_t per = blocksize / (8u * ts) + 1u;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (uint64_t)nblocks * per; i += (uint64_t)gridDim.x * blockDim.x) {
+    for (uint64_t i = (uint64_t)bx * blockDim.x + threadIdx.x; i < (uint64_t)nblocks * per; i += (uint64_t)gx * blockDim.x) {
         const uint32_t b = (uint32_t)(i / per), g = (uint32_t)(i % per);
         const uint32_t base = b * blocksize, bsize = nbytes - base < blocksize ? nbytes - base : blocksize, nel = bsize / ts;
         if (nel % 8u != 0u) {                                                           // not filtered at all: the threads of the block copy it
@@ -211,6 +218,9 @@ __global__ void k_cb_bitunshuffle(uint8_t *__restrict__ dst, const uint8_t *__re
         }
     }
 }
+__global__ void k_cb_bitunshuffle(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nbytes, uint32_t blocksize, uint32_t ts) {
+    cb_bitunshuffle(dst, src, nbytes, blocksize, ts, blockIdx.x, gridDim.x);
+}
 
 // 8 x 8 bit transpose: out byte i, bit k = in byte k, bit i
 __device__ __forceinline__ uint64_t cb_transpose8(uint64_t x) {
@@ -221,39 +231,42 @@ __device__ __forceinline__ uint64_t cb_transpose8(uint64_t x) {
 }
 // typesize 4, whole blocks of a multiple of 32 elements (what every writer's block size is): one thread per 32 elements -- 32 dword
 // loads (4 groups of every bit row at once), 8 x 16-byte stores -- instead of one byte per access
+// one work item of the inverse: 32 elements, group q of 4 bytes of every bit row of the block at `base` (ng = bytes per bit row)
+__device__ __forceinline__ void cb_bitunshuffle4_item(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, size_t base, uint32_t ng, uint32_t q) {
+        uint64_t x[4][4];                                                   // [byte j][group]: byte e = byte j of element 8 (4 q + group) + e
+#pragma unroll
+        for (int j = 0; j < 4; j++) {
+            uint32_t r[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) r[k] = ld4u(src + base + (size_t)(8 * j + k) * ng + 4u * q);
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                uint64_t v = 0;
+#pragma unroll
+                for (int k = 0; k < 8; k++) v |= (uint64_t)((r[k] >> (8 * g)) & 255u) << (8 * k);
+                x[j][g] = cb_transpose8(v);
+            }
+        }
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            uint32_t w[8];
+#pragma unroll
+            for (int e = 0; e < 8; e++)
+                w[e] = (uint32_t)((x[0][g] >> (8 * e)) & 255u) | ((uint32_t)((x[1][g] >> (8 * e)) & 255u) << 8) |
+                       ((uint32_t)((x[2][g] >> (8 * e)) & 255u) << 16) | ((uint32_t)((x[3][g] >> (8 * e)) & 255u) << 24);
+            u32x4 a, bb; a.x = w[0]; a.y = w[1]; a.z = w[2]; a.w = w[3]; bb.x = w[4]; bb.y = w[5]; bb.z = w[6]; bb.w = w[7];
+            st16u(dst + base + (size_t)(32u * q + 8u * g) * 4u, a);
+            st16u(dst + base + (size_t)(32u * q + 8u * g) * 4u + 16u, bb);
+        }
+}
 template <bool FWD>
 __global__ void k_cb_bitshuffle4_fast(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nfull, uint32_t blocksize) {
     const uint32_t ng = blocksize / 32u, per = ng / 4u;
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (uint64_t)nfull * per; i += (uint64_t)gridDim.x * blockDim.x) {
         const uint32_t b = (uint32_t)(i / per), q = (uint32_t)(i % per);
         const size_t base = (size_t)b * blocksize;
-        if (!FWD) {
-            uint64_t x[4][4];                                                   // [byte j][group]: byte e = byte j of element 8 (4 q + group) + e
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-                uint32_t r[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) r[k] = ld4u(src + base + (size_t)(8 * j + k) * ng + 4u * q);
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    uint64_t v = 0;
-#pragma unroll
-                    for (int k = 0; k < 8; k++) v |= (uint64_t)((r[k] >> (8 * g)) & 255u) << (8 * k);
-                    x[j][g] = cb_transpose8(v);
-                }
-            }
-#pragma unroll
-            for (int g = 0; g < 4; g++) {
-                uint32_t w[8];
-#pragma unroll
-                for (int e = 0; e < 8; e++)
-                    w[e] = (uint32_t)((x[0][g] >> (8 * e)) & 255u) | ((uint32_t)((x[1][g] >> (8 * e)) & 255u) << 8) |
-                           ((uint32_t)((x[2][g] >> (8 * e)) & 255u) << 16) | ((uint32_t)((x[3][g] >> (8 * e)) & 255u) << 24);
-                u32x4 a, bb; a.x = w[0]; a.y = w[1]; a.z = w[2]; a.w = w[3]; bb.x = w[4]; bb.y = w[5]; bb.z = w[6]; bb.w = w[7];
-                st16u(dst + base + (size_t)(32u * q + 8u * g) * 4u, a);
-                st16u(dst + base + (size_t)(32u * q + 8u * g) * 4u + 16u, bb);
-            }
-        } else {
+        if (!FWD) cb_bitunshuffle4_item(dst, src, base, ng, q);
+        else {
             uint32_t r[4][8];                                                   // [byte j][bit k]: 4 bytes = groups 4 q .. 4 q + 3 of row 8 j + k
 #pragma unroll
             for (int j = 0; j < 4; j++)
@@ -280,13 +293,110 @@ __global__ void k_cb_bitshuffle4_fast(uint8_t *__restrict__ dst, const uint8_t *
         }
     }
 }
+// the inverse over the workgroups [0, gx) of one frame (k_cbb_unfilter)
+__device__ __forceinline__ void cb_bitunshuffle4_fast(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nfull, uint32_t blocksize, uint32_t bx, uint32_t gx) {
+    const uint32_t ng = blocksize / 32u, per = ng / 4u;
+    for (uint64_t i = (uint64_t)bx * blockDim.x + threadIdx.x; i < (uint64_t)nfull * per; i += (uint64_t)gx * blockDim.x)
+        cb_bitunshuffle4_item(dst, src, (size_t)(uint32_t)(i / per) * blocksize, ng, (uint32_t)(i % per));
+}
 
-__global__ void k_cb_result(const CbPlan *plan, hb_result *result, uint64_t nbytes) {
+__device__ __forceinline__ void cb_result(const CbPlan *plan, hb_result *result, uint64_t nbytes) {
     result->flags = 1; result->total_bytes = nbytes; result->reserved = 0;
     if (plan->fail) { result->status = HB_ERR_DECOMPRESSION_FAILED; result->bytes = 0; }
     else { result->status = HB_OK; result->bytes = nbytes; }
 }
+__global__ void k_cb_result(const CbPlan *plan, hb_result *result, uint64_t nbytes) { cb_result(plan, result, nbytes); }
 __global__ void k_cb_init(CbPlan *plan) { plan->fail = 0; }
+
+// ---- batches (hb_cblosc_decompress_frames_batch_device): many frames through ONE set of launches.  Blocks and streams are as independent
+// across frames as inside one, so the same bodies run over flat spaces; the records, prefixes and kinds are hb_cblosc_batch.h's. ----
+// one thread per block of the flat block space
+__global__ __launch_bounds__(64) void k_cbb_plan(const CbbFrame *__restrict__ frames, CbPlan *plans, const uint32_t *__restrict__ blk0, uint32_t nframes,
+                                                  uint32_t nblocks, CbStream *streams) {
+    const uint32_t x = blockIdx.x * 64u + threadIdx.x;
+    if (x >= nblocks) return;
+    const uint32_t k = hb_owner(blk0, nframes, x);
+    const CbbFrame &F = frames[k];
+    cb_plan_block(F.frame, F.nbytes, F.blocksize, F.cbytes, F.typesize, F.flags, plans + k, streams + F.stream0, F.b0, x - blk0[k]);
+}
+
+// one wavefront per stream of the flat stream space, in the permuted order over all of it.  The stream's frame gives the plan to read and to
+// fail, the source and the target (its staged copy, or its destination when there is no filter to undo).  A stream goes to the small decoder
+// exactly when hb_cblosc_decompress_dev would send it there: its frame's streams are at most one chunk, and it is short enough and not stored.
+__global__ __launch_bounds__(64) void k_cbb_decode(const CbbFrame *__restrict__ frames, CbPlan *plans, const uint32_t *__restrict__ str0, uint32_t nframes,
+                                                    const CbStream *__restrict__ streams, uint32_t nstreams, uint8_t *work, int small_launched, uint32_t P) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[RG_PWIN + 128];
+    __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
+    __shared__ __attribute__((aligned(16))) uint8_t s_d[SY_IMG + 64];
+    const int lane = threadIdx.x;
+    const uint32_t mgrp = (nstreams + 7u) / 8u;
+    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
+        const uint32_t i = cb_stream_of(it, mgrp, P);
+        if (i >= nstreams) continue;
+        const uint32_t k = RFL(hb_owner(str0, nframes, i));
+        CbPlan *plan = plans + k;
+        if (RFL(plan->fail)) continue;                                         // (one value for the whole wave: nobody is left behind at a wave_sync)
+        const CbbFrame &F = frames[k];
+        uint8_t *target = F.stage_off ? work + F.stage_off : F.dst;
+        cb_decode_stream(F.frame, plan, cb_load_stream(streams, i), target, small_launched && F.small, s_win, s_tq, s_d, lane);
+    }
+}
+__global__ __launch_bounds__(64) void k_cbb_decode_small(const CbbFrame *__restrict__ frames, CbPlan *plans, const uint32_t *__restrict__ str0, uint32_t nframes,
+                                                          const CbStream *__restrict__ streams, uint32_t nstreams, uint8_t *work, uint32_t P) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_in[CB_SMALL_IN + 64 + 128];
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[CB_SMALL + 64];
+    __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
+    const int lane = threadIdx.x;
+    const uint32_t mgrp = (nstreams + 7u) / 8u;
+    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
+        const uint32_t i = cb_stream_of(it, mgrp, P);
+        if (i >= nstreams) continue;
+        const uint32_t k = RFL(hb_owner(str0, nframes, i));
+        const CbbFrame &F = frames[k];
+        if (!F.small) continue;
+        CbPlan *plan = plans + k;
+        if (RFL(plan->fail)) continue;
+        uint8_t *target = F.stage_off ? work + F.stage_off : F.dst;
+        cb_decode_small_stream(F.frame, plan, cb_load_stream(streams, i), target, s_in, s_out, s_tq, lane);
+    }
+}
+
+// one launch per kind that occurs: ufrm / ublk = the frames of this kind and the prefix of their workgroup counts (every frame has at least one).
+// CBK_COPY is the memcpyed frames' copy: one wavefront per 4 KiB piece.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_cbb_unfilter(const CbbFrame *__restrict__ frames, const uint32_t *__restrict__ ufrm, const uint32_t *__restrict__ ublk,
+                                                       uint32_t nkind, uint8_t *work) {
+    const uint32_t i = hb_owner(ublk, nkind, blockIdx.x);
+    const CbbFrame &F = frames[ufrm[i]];
+    const uint32_t bx = blockIdx.x - ublk[i], gx = F.ngrid;
+    uint8_t *dst = F.dst;
+    if constexpr (KIND == CBK_COPY) {
+        const uint32_t off = (bx * 4u + (threadIdx.x >> 6)) * HB_CHUNK;        // (ngrid = ceil(nbytes / 16 KiB): every piece has its wavefront)
+        if (off < F.nbytes) wave_copy_g2g(dst + off, F.frame + 16 + off, F.nbytes - off < HB_CHUNK ? F.nbytes - off : HB_CHUNK, (int)(threadIdx.x & 63u));
+    } else {
+        const uint8_t *src = work + F.stage_off;
+        if constexpr (KIND == CBK_UNSHUFFLE) cb_unshuffle(dst, src, F.nbytes, F.blocksize, F.typesize, bx, gx);
+        else if constexpr (KIND == CBK_BITUN) cb_bitunshuffle(dst, src, F.nbytes, F.blocksize, F.typesize, bx, gx);
+        else {
+            const uint32_t nfull = F.nbytes / F.blocksize;
+            if (bx < F.nfast) cb_bitunshuffle4_fast(dst, src, nfull, F.blocksize, bx, F.nfast);
+            else {                                                             // the last, shorter block the plain way
+                const size_t done = (size_t)nfull * F.blocksize;
+                cb_bitunshuffle(dst + done, src + done, F.nbytes - (uint32_t)done, F.blocksize, F.typesize, bx - F.nfast, gx - F.nfast);
+            }
+        }
+    }
+}
+
+// one thread per frame: what the host decided, or k_cb_result's record
+__global__ __launch_bounds__(64) void k_cbb_finish(const CbbFrame *__restrict__ frames, const CbPlan *plans, hb_result *results, uint32_t nframes) {
+    const uint32_t k = blockIdx.x * 64u + threadIdx.x;
+    if (k >= nframes) return;
+    const CbbFrame &F = frames[k];
+    hb_result *r = results + k;
+    if (F.mode == CBB_REFUSED) { r->status = F.status; r->flags = 0; r->bytes = 0; r->total_bytes = 0; r->reserved = 0; return; }
+    cb_result(plans + k, r, (uint64_t)F.nbytes);
+}
 
 // =====================================================================================================================
 // Writing the format.  A stream has to be ONE LZ4 block, and this library's encoder makes blocks of 4 KiB chunks that are
@@ -525,26 +635,9 @@ static void cb_launch_blocks(const hb_cblosc_header *hdr, const uint8_t *d_frame
 extern "C" {
 
 // header fields of a C-Blosc-1 frame (host side); HB_OK or the error a malformed header gets
-int hb_cblosc_parse_header(const void *frame, size_t n, hb_cblosc_header *out) {
-    if (!frame || !out) return HB_ERR_BAD_ARG;
-    if (n < 16) return HB_ERR_INVALID_HEADER;
-    const uint8_t *f = (const uint8_t *)frame;
-    auto rd = [&](int at) { return (uint32_t)f[at] | ((uint32_t)f[at + 1] << 8) | ((uint32_t)f[at + 2] << 16) | ((uint32_t)f[at + 3] << 24); };
-    out->version = f[0]; out->versionlz = f[1]; out->flags = f[2]; out->typesize = f[3];
-    out->nbytes = rd(4); out->blocksize = rd(8); out->cbytes = rd(12);
-    out->codec_format = f[2] >> 5;
-    if (out->version != 2) return HB_ERR_INVALID_VERSION;                              // BLOSC_VERSION_FORMAT
-    if (out->typesize == 0) return HB_ERR_INVALID_HEADER;
-    if (out->cbytes < 16 || out->cbytes > n) return HB_ERR_INVALID_DATA;
-    if (out->nbytes && out->blocksize == 0) return HB_ERR_INVALID_HEADER;
-    return HB_OK;
-}
+int hb_cblosc_parse_header(const void *frame, size_t n, hb_cblosc_header *out) { return cb_parse_header(frame, n, out); }
 
-size_t hb_cblosc_decompress_workspace(size_t nbytes, size_t blocksize, size_t typesize) {
-    const size_t nblocks = blocksize ? (nbytes + blocksize - 1) / blocksize : 0;
-    const size_t nsplit = (typesize >= 1 && typesize <= 16 && blocksize / typesize >= 128) ? typesize : 1;      // cb_nsplit() without the flag: the upper bound
-    return 256 + cb_align(nblocks * nsplit * sizeof(CbStream)) + cb_align(nbytes + 64);
-}
+size_t hb_cblosc_decompress_workspace(size_t nbytes, size_t blocksize, size_t typesize) { return cb_decompress_workspace(nbytes, blocksize, typesize); }
 
 // d_frame: the frame in device memory (n bytes available), d_dst: hdr.nbytes bytes.  Asynchronous on `stream`; *d_result says how it went.
 int hb_cblosc_decompress_dev(const hb_cblosc_header *hdr, const void *d_frame, size_t n, void *d_dst, size_t cap, void *d_work, size_t work_bytes,
@@ -579,6 +672,87 @@ int hb_cblosc_decompress_dev(const hb_cblosc_header *hdr, const void *d_frame, s
     uint8_t *staged = w + 256 + cb_align((size_t)nblocks * nsplit * sizeof(CbStream));
     cb_launch_blocks(hdr, (const uint8_t *)d_frame, n, 0u, nblocks, nbytes, (uint8_t *)d_dst, plan, streams, staged, s);
     hipLaunchKernelGGL(k_cb_result, dim3(1), dim3(1), 0, s, plan, d_result, (uint64_t)nbytes);
+    HB_HIP_TRY(hipGetLastError());
+    return HB_OK;
+}
+
+// ---- many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_batch.h) ----
+size_t hb_cblosc_decompress_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n) {
+    CbbBatch B;
+    if (cbb_prepare(nframes, hdrs, nullptr, n, nullptr, nullptr, B)) return 0;
+    return B.L.total ? B.L.total : 256;                                   // (never 0 for a batch that is accepted)
+}
+
+int hb_cblosc_decompress_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, void *const *d_dst,
+                                             const size_t *cap, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    if (nframes < 0) return HB_ERR_BAD_ARG;
+    if (nframes == 0) return HB_OK;
+    if (!hdrs || !d_frame || !n || !d_dst || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
+    CbbBatch B;
+    const int rc = cbb_prepare(nframes, hdrs, d_frame, n, d_dst, cap, B);
+    if (rc) return rc;
+    const CbbLayout &L = B.L;
+    if (work_bytes < L.total) return HB_ERR_SHORT_BUFFER;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t *w = (uint8_t *)d_work;
+    const size_t nf = (size_t)nframes;
+    // the frame records, the prefixes and the cleared plans go up in one copy (the buffer is read before the call returns, as with hb_batch.hip's)
+    std::vector<uint8_t> up(L.upload, 0);
+    memcpy(up.data() + L.frames, B.tab.data(), nf * sizeof(CbbFrame));
+    memcpy(up.data() + L.pre, B.pre.data(), nf * 16);
+    memcpy(up.data() + L.plans, B.plans.data(), nf * sizeof(CbPlan));
+    hb_prof_begin("cbb_upload", s);
+    HB_HIP_TRY(hipMemcpyAsync(w, up.data(), L.upload, hipMemcpyHostToDevice, s));
+    hb_prof_end(s);
+    const CbbFrame *d_frames = (const CbbFrame *)(w + L.frames);
+    CbPlan *d_plans = (CbPlan *)(w + L.plans);
+    const uint32_t *d_blk0 = (const uint32_t *)(w + L.pre), *d_str0 = d_blk0 + nf, *d_ufrm = d_str0 + nf, *d_ublk = d_ufrm + nf;
+    CbStream *d_streams = (CbStream *)(w + L.streams);
+    if (B.nstreams) {
+        const uint32_t nblocks = (uint32_t)B.nblocks, nstreams = (uint32_t)B.nstreams;
+        hb_prof_begin("k_cbb_plan", s);
+        hipLaunchKernelGGL(k_cbb_plan, dim3((nblocks + 63u) / 64u), dim3(64), 0, s, d_frames, d_plans, d_blk0, (uint32_t)nframes, nblocks, d_streams);
+        hb_prof_end(s);
+        const uint32_t mgrp = (nstreams + 7u) / 8u;
+        uint32_t P = mgrp / 4u + 1u;                                    // coprime to the groups of 8 streams, about a quarter turn (cb_launch_blocks)
+        for (;; P++) { uint32_t x = P, y = mgrp; while (y) { const uint32_t t = x % y; x = y; y = t; } if (x == 1u) break; }
+        const unsigned grid = mgrp * 8u < 65536u ? mgrp * 8u : 65536u;
+        if (B.any_small) {
+            hb_prof_begin("k_cbb_decode_small", s);
+            hipLaunchKernelGGL(k_cbb_decode_small, dim3(grid), dim3(64), 0, s, d_frames, d_plans, d_str0, (uint32_t)nframes, (const CbStream *)d_streams, nstreams, w, P);
+            hb_prof_end(s);
+        }
+        // (any frame with streams can have stored ones: the general decoder always runs.  Its passes per workgroup as in cb_launch_blocks, when
+        // no frame has short streams and all split alike)
+        unsigned gbig = grid;
+        if (!B.any_small && B.nsplit_all > 1u) {
+            unsigned p = B.nsplit_all;
+            while (p > 1u && mgrp * 8u / p < 2048u) p >>= 1;
+            gbig = (mgrp * 8u / p + 7u) / 8u * 8u;
+            if (gbig > 65536u) gbig = 65536u;
+        }
+        hb_prof_begin("k_cbb_decode", s);
+        hipLaunchKernelGGL(k_cbb_decode, dim3(gbig), dim3(64), 0, s, d_frames, d_plans, d_str0, (uint32_t)nframes, (const CbStream *)d_streams, nstreams, w, (int)B.any_small, P);
+        hb_prof_end(s);
+    }
+    for (int k = 0; k < CBK_COUNT; k++) {
+        const uint32_t k0 = B.kind0[k], nk = B.kind0[k + 1] - k0, blocks = B.kblocks[k];
+        if (!nk) continue;
+        hb_prof_begin(k == CBK_COPY ? "k_cbb_copy" : "k_cbb_unfilter", s);
+#define CBB_LAUNCH(K) hipLaunchKernelGGL(k_cbb_unfilter<K>, dim3(blocks), dim3(256), 0, s, d_frames, d_ufrm + k0, d_ublk + k0, nk, w)
+        switch (k) {
+        case CBK_UNSHUFFLE: CBB_LAUNCH(CBK_UNSHUFFLE); break;
+        case CBK_BITUN: CBB_LAUNCH(CBK_BITUN); break;
+        case CBK_BITUN4: CBB_LAUNCH(CBK_BITUN4); break;
+        default: CBB_LAUNCH(CBK_COPY); break;
+        }
+#undef CBB_LAUNCH
+        hb_prof_end(s);
+    }
+    hb_prof_begin("k_cbb_finish", s);
+    hipLaunchKernelGGL(k_cbb_finish, dim3((unsigned)((nf + 63) / 64)), dim3(64), 0, s, d_frames, (const CbPlan *)d_plans, d_results, (uint32_t)nframes);
+    hb_prof_end(s);
     HB_HIP_TRY(hipGetLastError());
     return HB_OK;
 }

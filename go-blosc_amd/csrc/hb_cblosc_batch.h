@@ -1,0 +1,260 @@
+// hb_cblosc_batch.h — the host side of the batched C-Blosc-1 decode (hb_cblosc_decompress_frames_batch*): what a frame's header gets refused
+// for, the frame records and prefixes that go up to the device, the layout of the workspace, and the staging plan of the host form.
+// Plain C++, no HIP: hb_cblosc.hip and hb_batch.hip include it, and so does the sanitizer build tests/tools/cblosc_batch_asan_check.cpp.
+#pragma once
+#include <stddef.h>
+#include <stdint.h>
+#include <vector>
+#include "../../include/hipblosc.h"
+#include "hb_format.h"
+
+#if defined(__HIPCC__)
+#define CB_HD __host__ __device__
+#else
+#define CB_HD
+#endif
+
+#define CB_FLAG_SHUFFLE    0x01u
+#define CB_FLAG_MEMCPY     0x02u
+#define CB_FLAG_BITSHUFFLE 0x04u
+#define CB_FLAG_DONTSPLIT  0x10u
+
+// blosc_d of c-blosc 1.x splits a block into `typesize` streams only when ALL of these hold (the rule from before the 0x10 flag existed stays
+// in force next to it: frames of c-blosc < 1.15 have the bit clear and large typesizes / small blocks unsplit; checked against libblosc 1.21):
+// not-split bit clear, typesize <= MAX_SPLITS (16), blocksize / typesize >= MIN_BUFFERSIZE (128), not the last, shorter block.
+CB_HD static inline uint32_t cb_nsplit(uint32_t flags, uint32_t typesize, uint32_t blocksize) {
+    return (!(flags & 0x10u) && typesize >= 1u && typesize <= 16u && blocksize / typesize >= 128u) ? typesize : 1u;
+}
+
+struct CbStream { uint32_t src, csize, dst, usize; };
+struct CbPlan { uint32_t fail, nblocks, nsplit, pad; };
+
+static inline size_t cb_align(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// hb_cblosc_decompress_workspace: the plan, the stream records (cb_nsplit() without the flag: the upper bound), the staged copy
+static inline size_t cb_decompress_workspace(size_t nbytes, size_t blocksize, size_t typesize) {
+    const size_t nblocks = blocksize ? (nbytes + blocksize - 1) / blocksize : 0;
+    const size_t nsplit = (typesize >= 1 && typesize <= 16 && blocksize / typesize >= 128) ? typesize : 1;
+    return 256 + cb_align(nblocks * nsplit * sizeof(CbStream)) + cb_align(nbytes + 64);
+}
+
+// header fields of a C-Blosc-1 frame; HB_OK or the error a malformed header gets (hb_cblosc_parse_header)
+static inline int cb_parse_header(const void *frame, size_t n, hb_cblosc_header *out) {
+    if (!frame || !out) return HB_ERR_BAD_ARG;
+    if (n < 16) return HB_ERR_INVALID_HEADER;
+    const uint8_t *f = (const uint8_t *)frame;
+    auto rd = [&](int at) { return (uint32_t)f[at] | ((uint32_t)f[at + 1] << 8) | ((uint32_t)f[at + 2] << 16) | ((uint32_t)f[at + 3] << 24); };
+    out->version = f[0]; out->versionlz = f[1]; out->flags = f[2]; out->typesize = f[3];
+    out->nbytes = rd(4); out->blocksize = rd(8); out->cbytes = rd(12);
+    out->codec_format = f[2] >> 5;
+    if (out->version != 2) return HB_ERR_INVALID_VERSION;                              // BLOSC_VERSION_FORMAT
+    if (out->typesize == 0) return HB_ERR_INVALID_HEADER;
+    if (out->cbytes < 16 || out->cbytes > n) return HB_ERR_INVALID_DATA;
+    if (out->nbytes && out->blocksize == 0) return HB_ERR_INVALID_HEADER;
+    return HB_OK;
+}
+
+// ---- the batch: frame k owns the blocks [blk0[k], blk0[k + 1]) of k_cbb_plan's flat space, the streams [str0[k], str0[k + 1]) of the decoders'
+// and, in the launch of its un-filter kind, the workgroups [ublk[i], ublk[i + 1]).  Every frame has its own CbPlan: a stream that fails spoils
+// its own frame and no other. ----
+enum { CBB_REFUSED = 0, CBB_STREAMS = 1, CBB_MEMCPY = 2, CBB_EMPTY = 3 };
+enum { CBK_UNSHUFFLE = 0, CBK_BITUN, CBK_BITUN4, CBK_COPY, CBK_COUNT };
+struct CbbFrame {
+    const uint8_t *frame;                // d_frame[k] (n bytes, cbytes of them the frame itself)
+    uint8_t *dst;
+    uint64_t n, stage_off;               // stage_off: the frame's staged copy inside the workspace; 0: no filter, the streams decode into dst
+    uint32_t nbytes, blocksize, cbytes, typesize, flags, nsplit;
+    uint32_t b0, nblocks;                // the blocks of this record: all of the frame's (b0 = 0) -- a record for "blocks [b0, b0 + nb)" fits as it is
+    uint32_t stream0;                    // its first stream record (= str0[k])
+    uint32_t small;                      // every stream is at most one chunk: k_cbb_decode_small takes those that are not stored
+    int32_t mode, kind, status;          // CBB_*; CBK_* or -1; mode CBB_REFUSED: `status` is what the host decided
+    uint32_t ngrid, nfast;               // workgroups in the launch of its kind; CBK_BITUN4: the first nfast run the fast path, the rest the last, shorter block
+    uint32_t pad;
+};
+static_assert(sizeof(CbbFrame) == 96, "CbbFrame is uploaded as it is");
+static_assert(sizeof(CbbFrame) + sizeof(CbPlan) + 16 + 3 * 255 <= HB_CBLOSC_BATCH_FRAME_BYTES, "the per-frame constant of include/hipblosc.h");
+
+// what hb_cblosc_decompress_dev returns for this header, in its order (the workspace apart); HB_OK: *mode says what there is to do.
+// have_ptrs == 0: the workspace query, which knows neither pointers nor capacities.
+static inline int cbb_refusal(const hb_cblosc_header &h, int have_ptrs, const void *d_frame, const void *d_dst, size_t n, size_t cap, int *mode) {
+    const uint32_t nbytes = h.nbytes, blocksize = h.blocksize, ts = h.typesize;
+    *mode = CBB_REFUSED;
+    if (have_ptrs && (!d_frame || (!d_dst && cap))) return HB_ERR_BAD_ARG;
+    if (h.version != 2) return HB_ERR_INVALID_VERSION;
+    if (ts == 0u || (nbytes && blocksize == 0u)) return HB_ERR_INVALID_HEADER;
+    if (h.cbytes > n || h.cbytes < 16) return HB_ERR_INVALID_DATA;
+    if (have_ptrs && nbytes > cap) return HB_ERR_SHORT_BUFFER;
+    if (nbytes == 0) { *mode = CBB_EMPTY; return HB_OK; }
+    if (h.flags & CB_FLAG_MEMCPY) {
+        if ((uint64_t)h.cbytes < 16ull + nbytes) return HB_ERR_INVALID_DATA;
+        *mode = CBB_MEMCPY;
+        return HB_OK;
+    }
+    if (h.codec_format != 1) return HB_ERR_INVALID_CODEC;
+    const uint64_t nblocks = ((uint64_t)nbytes + blocksize - 1) / blocksize;
+    if (16ull + 4ull * nblocks > h.cbytes) return HB_ERR_INVALID_DATA;
+    if (blocksize < ts) return HB_ERR_INVALID_DATA;
+    *mode = CBB_STREAMS;
+    return HB_OK;
+}
+
+struct CbbLayout { size_t frames, pre, plans, upload, streams, stage, total; };      // pre: blk0, str0, ufrm, ublk, nframes words each
+static inline CbbLayout cbb_layout(size_t nframes, uint64_t nstreams, size_t stage_bytes) {
+    CbbLayout L{};
+    size_t o = 0;
+    auto take = [&](size_t b) { size_t at = o; o += cb_align(b); return at; };
+    L.frames = take(nframes * sizeof(CbbFrame));                          // (the first three go up in one copy)
+    L.pre = take(nframes * 16);
+    L.plans = take(nframes * sizeof(CbPlan));
+    L.upload = o;
+    L.streams = take((size_t)nstreams * sizeof(CbStream));
+    L.stage = take(stage_bytes);
+    L.total = o;
+    return L;
+}
+
+struct CbbBatch {
+    std::vector<CbbFrame> tab;
+    std::vector<CbPlan> plans;
+    std::vector<uint32_t> pre;           // blk0 | str0 | ufrm | ublk
+    uint32_t kind0[CBK_COUNT + 1];       // frames of kind k: ufrm[kind0[k], kind0[k + 1])
+    uint32_t kblocks[CBK_COUNT];
+    uint64_t nblocks, nstreams;
+    size_t stage;
+    uint32_t any_small, nsplit_all;      // some frame's streams are at most one chunk; the nsplit that all frames with streams share, else 1
+    CbbLayout L;
+};
+
+static inline uint32_t cbb_grid(uint64_t items, uint32_t per_group, uint32_t most) {
+    const uint64_t g = (items + per_group - 1) / per_group;
+    return (uint32_t)(g < 1 ? 1 : (g > most ? most : g));
+}
+
+// HB_OK, or what the call as a whole answers.  d_frame / d_dst / cap == NULL: the workspace query.
+static inline int cbb_prepare(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, void *const *d_dst, const size_t *cap,
+                              CbbBatch &B) {
+    if (nframes < 0) return HB_ERR_BAD_ARG;
+    B.nblocks = 0; B.nstreams = 0; B.stage = 0; B.any_small = 0; B.nsplit_all = 0;
+    for (int k = 0; k < CBK_COUNT; k++) B.kblocks[k] = 0;
+    for (int k = 0; k <= CBK_COUNT; k++) B.kind0[k] = 0;
+    B.L = cbb_layout(0, 0, 0);
+    if (nframes == 0) return HB_OK;
+    if (!hdrs || !n) return HB_ERR_BAD_ARG;
+    const int have = d_frame != nullptr;
+    if (have && (!d_dst || !cap)) return HB_ERR_BAD_ARG;
+    const size_t nf = (size_t)nframes;
+    B.tab.assign(nf, CbbFrame{});
+    B.plans.assign(nf, CbPlan{});
+    B.pre.assign(4 * nf, 0u);
+    uint32_t *blk0 = B.pre.data(), *str0 = blk0 + nf, *ufrm = str0 + nf, *ublk = ufrm + nf;
+    uint64_t kb[CBK_COUNT] = {0};
+    for (size_t k = 0; k < nf; k++) {
+        const hb_cblosc_header &h = hdrs[k];
+        CbbFrame &F = B.tab[k];
+        blk0[k] = (uint32_t)B.nblocks; str0[k] = (uint32_t)B.nstreams;
+        F.kind = -1;
+        int mode = CBB_REFUSED;
+        F.status = cbb_refusal(h, have, have ? d_frame[k] : nullptr, have ? d_dst[k] : nullptr, n[k], have ? cap[k] : 0, &mode);
+        F.mode = mode;
+        if (mode == CBB_REFUSED) continue;
+        F.frame = have ? (const uint8_t *)d_frame[k] : nullptr; F.dst = have ? (uint8_t *)d_dst[k] : nullptr;
+        F.n = n[k];
+        F.nbytes = h.nbytes; F.blocksize = h.blocksize; F.cbytes = h.cbytes; F.typesize = h.typesize; F.flags = h.flags;
+        if (mode == CBB_EMPTY) continue;
+        if (mode == CBB_MEMCPY) {
+            F.kind = CBK_COPY;
+            F.ngrid = cbb_grid(h.nbytes, 16384u, 1u << 20);
+        } else {
+            const uint32_t ts = h.typesize, bs = h.blocksize;
+            F.nsplit = cb_nsplit(h.flags, ts, bs);
+            F.b0 = 0; F.nblocks = (uint32_t)(((uint64_t)h.nbytes + bs - 1) / bs);
+            F.stream0 = (uint32_t)B.nstreams;
+            F.small = bs / F.nsplit <= HB_CHUNK ? 1u : 0u;
+            B.nblocks += F.nblocks;
+            B.nstreams += (uint64_t)F.nblocks * F.nsplit;
+            B.plans[k].nblocks = F.nblocks; B.plans[k].nsplit = F.nsplit;
+            if (F.small) B.any_small = 1;
+            B.nsplit_all = B.nsplit_all == 0 || B.nsplit_all == F.nsplit ? F.nsplit : 1u;
+            // blosc_d: the byte shuffle counts for typesize > 1 only (and comes first), the bit shuffle for any typesize
+            const bool unshuf = (h.flags & CB_FLAG_SHUFFLE) && ts > 1, unbit = !unshuf && (h.flags & CB_FLAG_BITSHUFFLE);
+            if (unshuf) {
+                F.kind = CBK_UNSHUFFLE;
+                F.ngrid = cbb_grid((uint64_t)F.nblocks * (bs / ts + 1u), 256u, 2048u);
+            } else if (unbit && ts == 4u && bs % 512u == 0u && h.nbytes >= bs) {      // whole blocks the fast way, a last shorter one the plain way
+                const uint32_t nfull = h.nbytes / bs, tail = h.nbytes - nfull * bs;
+                F.kind = CBK_BITUN4;
+                F.nfast = cbb_grid((uint64_t)nfull * (bs / 128u), 256u, 1u << 24);
+                F.ngrid = F.nfast + (tail ? cbb_grid(bs / 32u + 1u, 256u, 64u) : 0u);
+            } else if (unbit) {
+                F.kind = CBK_BITUN;
+                F.ngrid = cbb_grid((uint64_t)F.nblocks * (bs / (8u * ts) + 1u), 256u, 2048u);
+            }
+            if (F.kind >= 0) { F.stage_off = B.stage; B.stage += cb_align((size_t)h.nbytes + 64); }      // (relative: the layout is added below)
+        }
+        if (F.kind >= 0) kb[F.kind] += F.ngrid;
+        if (B.nblocks > HB_CBLOSC_BATCH_MAX_WORK || B.nstreams > HB_CBLOSC_BATCH_MAX_WORK || (F.kind >= 0 && kb[F.kind] > HB_CBLOSC_BATCH_MAX_WORK)) return HB_ERR_BAD_ARG;
+    }
+    if (B.nsplit_all == 0) B.nsplit_all = 1;
+    B.L = cbb_layout(nf, B.nstreams, B.stage);
+    uint32_t at = 0;
+    for (int kind = 0; kind < CBK_COUNT; kind++) {
+        B.kind0[kind] = at;
+        uint32_t blk = 0;
+        for (size_t k = 0; k < nf; k++) {
+            CbbFrame &F = B.tab[k];
+            if (F.mode == CBB_REFUSED || F.kind != kind) continue;
+            if (kind != CBK_COPY) F.stage_off += B.L.stage;
+            ufrm[at] = (uint32_t)k; ublk[at] = blk; blk += F.ngrid; at++;
+        }
+        B.kblocks[kind] = blk;
+    }
+    B.kind0[CBK_COUNT] = at;
+    return HB_OK;
+}
+
+// ---- the host form: which frames the batch carries and where they and their outputs lie in the device buffers ----
+// Frames that follow each other exactly in host memory go up in one copy (the device image mirrors the span), every other frame lies at a
+// 16-byte-aligned offset with 64 bytes of slack.  Destinations that follow each other inside their own capacities (dst[k+1] in
+// [dst[k] + nbytes, dst[k] + cap[k]]) get a device image of the same layout and come down in one copy.
+struct CbbHostPlan {
+    std::vector<int> idx;                // the frames the batch carries, in order
+    std::vector<hb_cblosc_header> hd;
+    std::vector<size_t> ns, caps, ioff, ooff;
+    size_t in_bytes, out_bytes, span_bytes;
+    bool span_in, span_out;
+};
+static inline void cbb_host_plan(int nframes, const void *const *frame, const size_t *n, void *const *dst, const size_t *cap, CbbHostPlan &P) {
+    P.idx.clear(); P.hd.clear(); P.ns.clear(); P.caps.clear(); P.ioff.clear(); P.ooff.clear();
+    P.in_bytes = P.out_bytes = P.span_bytes = 0; P.span_in = P.span_out = false;
+    for (int k = 0; k < nframes; k++) {
+        hb_cblosc_header h;
+        int mode = CBB_REFUSED;
+        // (a NULL destination is hb_cblosc_decompress's to answer, unless the frame is empty: the device gets a buffer of its own either way)
+        const bool ok = frame[k] && cb_parse_header(frame[k], n[k], &h) == HB_OK && (dst[k] || !h.nbytes) &&
+                        cbb_refusal(h, 1, frame[k], frame[k], n[k], cap[k], &mode) == HB_OK;
+        if (ok) { P.idx.push_back(k); P.hd.push_back(h); }
+    }
+    const size_t m = P.idx.size();
+    if (m == 0) return;
+    P.ns.resize(m); P.caps.resize(m); P.ioff.resize(m); P.ooff.resize(m);
+    P.span_in = m > 1;
+    for (size_t i = 0; P.span_in && i + 1 < m; i++)
+        P.span_in = (const uint8_t *)frame[P.idx[i]] + n[P.idx[i]] == (const uint8_t *)frame[P.idx[i + 1]];
+    P.span_out = m > 1;
+    for (size_t i = 0; P.span_out && i + 1 < m; i++) {
+        const uint8_t *a = (const uint8_t *)dst[P.idx[i]], *b = (const uint8_t *)dst[P.idx[i + 1]];
+        P.span_out = a && b && b >= a + P.hd[i].nbytes && b <= a + cap[P.idx[i]];
+    }
+    for (size_t i = 0; i < m; i++) {
+        P.ns[i] = n[P.idx[i]]; P.caps[i] = P.hd[i].nbytes;
+        P.ioff[i] = P.in_bytes; P.ooff[i] = P.out_bytes;
+        P.in_bytes += P.span_in ? P.ns[i] : (P.ns[i] + 64 + 15) & ~(size_t)15;
+        P.out_bytes += cb_align(P.caps[i] + 64);
+    }
+    if (P.span_out) {
+        const uint8_t *base = (const uint8_t *)dst[P.idx[0]];
+        for (size_t i = 0; i < m; i++) P.ooff[i] = (size_t)((const uint8_t *)dst[P.idx[i]] - base);
+        P.span_bytes = P.ooff[m - 1] + P.hd[m - 1].nbytes;
+        P.out_bytes = P.span_bytes + 64;
+    }
+}

@@ -267,17 +267,6 @@ struct GiJob {
 };
 static_assert(sizeof(GiJob) == 96, "GiJob is uploaded as it is");
 
-// the owner of x in a prefix array (pre[0] == 0, non-decreasing): the LAST i < n with pre[i] <= x.  Where neighbours are equal (jobs without work)
-// that is the one behind them, whose count is not 0.  Wave-uniform: x comes from the block index.
-__device__ __forceinline__ uint32_t gi_owner(const uint32_t *__restrict__ pre, uint32_t n, uint32_t x) {
-    uint32_t lo = 0, hi = n;                                              // pre[lo] <= x; hi == n or pre[hi] > x
-    while (hi - lo > 1u) {
-        const uint32_t mid = lo + (hi - lo) / 2u;
-        if (pre[mid] <= x) lo = mid; else hi = mid;
-    }
-    return lo;
-}
-
 // one thread per job: k_gi_plan's check for the jobs of path 1 (the others get a plan that says "no index")
 __global__ __launch_bounds__(64) void k_gib_plan(const GiJob *__restrict__ jobs, DecPlan *plans, hb_result *results, uint32_t njobs) {
     const uint32_t j = blockIdx.x * 64u + threadIdx.x;
@@ -297,7 +286,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEC_WAVES)))
     __shared__ __attribute__((aligned(16))) uint2 s_tq[DEC_LEAN ? DTQ / 4 : DTQ];
     const int lane = threadIdx.x;
     for (uint32_t it = blockIdx.x; it < total; it += gridDim.x) {
-        const uint32_t j = gi_owner(item0, njobs, it);
+        const uint32_t j = hb_owner(item0, njobs, it);
         DecPlan *plan = plans + j;
         if (plan->mode != DEC_INDEXED) continue;
         const GiJob &J = jobs[j];
@@ -311,7 +300,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEC_WAVES)))
 template <int KIND>
 __global__ __launch_bounds__(256) void k_gib_gather(const GiJob *__restrict__ jobs, const DecPlan *plans, const uint32_t *__restrict__ gjob,
                                                      const uint32_t *__restrict__ gblk, uint32_t nkind, uint8_t *stage) {
-    const uint32_t i = gi_owner(gblk, nkind, blockIdx.x), j = gjob[i];
+    const uint32_t i = hb_owner(gblk, nkind, blockIdx.x), j = gjob[i];
     const GiJob &J = jobs[j];
     const int staged = J.path == 1;
     if (!gi_gate(staged ? plans + j : nullptr, nullptr)) return;

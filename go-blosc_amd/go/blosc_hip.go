@@ -727,3 +727,71 @@ func DecompressBatchHIP(frames [][]byte) ([][]byte, []error) {
 	}
 	return out, errs
 }
+
+// CBloscDecompressBatchHIP: many DecompressCBlosc calls through ONE set of kernel launches (hb_cblosc_decompress_frames_batch): what a chunked
+// array store holds is one c-blosc frame per chunk.  out[k], errs[k] are what DecompressCBlosc gives for frames[k].  The frames are packed
+// tightly into one pinned slab (one upload), the results spaced by their sizes (one download).
+func CBloscDecompressBatchHIP(frames [][]byte) ([][]byte, []error) {
+	n := len(frames)
+	out := make([][]byte, n)
+	errs := make([]error, n)
+	if n == 0 {
+		return out, errs
+	}
+	if !useHIP {
+		for k, f := range frames {
+			out[k], errs[k] = DecompressCBlosc(f)
+		}
+		return out, errs
+	}
+	srcs := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(uintptr(0)))))[:n:n]
+	dsts := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(uintptr(0)))))[:n:n]
+	defer C.free(unsafe.Pointer(&srcs[0]))
+	defer C.free(unsafe.Pointer(&dsts[0]))
+	lens := make([]C.size_t, n)
+	caps := make([]C.size_t, n)
+	rcs := make([]C.int64_t, n)
+	var inBytes, outBytes C.size_t
+	for k, f := range frames {
+		lens[k] = C.size_t(len(f))
+		var h C.hb_cblosc_header
+		if rc := C.hb_cblosc_parse_header(ptr(f), lens[k], &h); rc == 0 {
+			caps[k] = C.size_t(h.nbytes) // (untrusted: a forged size only costs pinned memory, hb_host_alloc answers nil when there is none)
+		}
+		inBytes += lens[k]
+		outBytes += caps[k]
+	}
+	slabIn, slabOut := C.hb_host_alloc(inBytes+64), C.hb_host_alloc(outBytes+64)
+	if slabIn == nil || slabOut == nil {
+		C.hb_host_free(slabIn)
+		C.hb_host_free(slabOut)
+		for k, f := range frames {
+			out[k], errs[k] = DecompressCBlosc(f)
+		}
+		return out, errs
+	}
+	defer C.hb_host_free(slabIn)
+	defer C.hb_host_free(slabOut)
+	var io, oo C.size_t
+	for k, f := range frames {
+		srcs[k] = unsafe.Add(slabIn, uintptr(io))
+		dsts[k] = unsafe.Add(slabOut, uintptr(oo))
+		copy(unsafe.Slice((*byte)(srcs[k]), len(f)), f)
+		io += lens[k]
+		oo += caps[k]
+	}
+	if rc := C.hb_cblosc_decompress_frames_batch(C.int(n), &srcs[0], &lens[0], &dsts[0], &caps[0], &rcs[0], C.int(Device)); rc != C.HB_OK {
+		for k := range frames {
+			errs[k] = hbError(C.int64_t(rc))
+		}
+		return out, errs
+	}
+	for k := range frames {
+		if rcs[k] < 0 {
+			errs[k] = hbError(rcs[k])
+		} else {
+			out[k] = append([]byte(nil), unsafe.Slice((*byte)(dsts[k]), int(rcs[k]))...)
+		}
+	}
+	return out, errs
+}

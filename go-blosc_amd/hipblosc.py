@@ -101,6 +101,7 @@ EXPORTS = [
     "hb_decompress_frames_batch_workspace", "hb_decompress_frames_batch_dev", "hb_compress_frames_batch", "hb_decompress_frames_batch",
     "hb_getitem_frame", "hb_getitem_frame_workspace", "hb_getitem_frame_device", "hb_cblosc_getitem", "hb_cblosc_getitem_workspace", "hb_cblosc_getitem_device",
     "hb_getitem_frames_batch_workspace", "hb_getitem_frames_batch_device", "hb_getitem_frames_batch",
+    "hb_cblosc_decompress_frames_batch_workspace", "hb_cblosc_decompress_frames_batch_device", "hb_cblosc_decompress_frames_batch",
     "hb_queue_create", "hb_queue_create_ex", "hb_queue_destroy", "hb_queue_compress", "hb_queue_decompress", "hb_queue_wait",
 ]
 
@@ -185,6 +186,9 @@ def lib():
             "hb_getitem_frames_batch_workspace": (sz, [i32, vp, vp, i32, vp, i32]),
             "hb_getitem_frames_batch_device": (i32, [i32, vp, vp, vp, i32, vp, vp, vp, i32, vp, sz, vp, vp]),
             "hb_getitem_frames_batch": (i32, [i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32]),
+            "hb_cblosc_decompress_frames_batch_workspace": (sz, [i32, vp, vp]),
+            "hb_cblosc_decompress_frames_batch_device": (i32, [i32, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
+            "hb_cblosc_decompress_frames_batch": (i32, [i32, vp, vp, vp, vp, vp, i32]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -536,6 +540,27 @@ def CBloscDecompress(frame):
     out = ctypes.create_string_buffer(max(h.nbytes, 1))
     rc = _check(lib().hb_cblosc_decompress(p, n, ctypes.cast(out, ctypes.c_void_p), h.nbytes, device))
     return out.raw[:rc]
+
+
+def CBloscDecompressBatch(frames, dev=None):
+    """Many CBloscDecompress calls through one set of launches (include/hipblosc.h hb_cblosc_decompress_frames_batch): the i-th result is what
+    CBloscDecompress(frames[i]) would have returned -- the bytes, or the error (returned, not raised, as DecompressBatch does)."""
+    n = len(frames)
+    if n == 0:
+        return []
+    L = lib()
+    keep = [_buf(f) for f in frames]
+    caps = []
+    for p, k, _ in keep:
+        h = CBloscHeader()
+        caps.append(h.nbytes if L.hb_cblosc_parse_header(p, k, ctypes.byref(h)) == 0 else 0)
+    outs = [(ctypes.c_char * max(c, 1))() for c in caps]
+    vp, sz, i64 = ctypes.c_void_p * n, ctypes.c_size_t * n, ctypes.c_int64 * n
+    srcs = vp(*[k[0].value for k in keep])
+    dsts = vp(*[ctypes.addressof(o) for o in outs])
+    rcs = i64()
+    _check(L.hb_cblosc_decompress_frames_batch(n, srcs, sz(*[k[1] for k in keep]), dsts, sz(*caps), rcs, device if dev is None else dev))
+    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(n)]
 
 
 def CBloscGetItem(frame, start, nitems):

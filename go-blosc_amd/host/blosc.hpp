@@ -151,6 +151,25 @@ inline std::vector<Bytes> GetItemBatch(const std::vector<Bytes> &frames, const s
     for (size_t j = 0; j < nj; j++) out[j].resize(rc[j] > 0 ? (size_t)rc[j] : 0);
     return out;
 }
+// many C-Blosc-1 frames through one set of launches (hb_cblosc_decompress_frames_batch): out[k] is what hb_cblosc_decompress gives for frames[k],
+// rc[k] the byte count or its HB_ERR_* code (nothing is thrown per frame)
+inline std::vector<Bytes> CBloscDecompressBatch(const std::vector<Bytes> &frames, std::vector<int64_t> &rc, int device = 0) {
+    const size_t nf = frames.size();
+    std::vector<Bytes> out(nf);
+    rc.assign(nf, 0);
+    if (!nf) return out;
+    std::vector<const void *> fr(nf); std::vector<void *> dst(nf); std::vector<size_t> ns(nf), cap(nf);
+    for (size_t k = 0; k < nf; k++) {
+        hb_cblosc_header h;
+        fr[k] = frames[k].data(); ns[k] = frames[k].size();
+        cap[k] = hb_cblosc_parse_header(fr[k], ns[k], &h) == HB_OK ? h.nbytes : 0;
+        out[k].resize(cap[k] ? cap[k] : 1);
+        dst[k] = out[k].data();
+    }
+    check(hb_cblosc_decompress_frames_batch((int)nf, fr.data(), ns.data(), dst.data(), cap.data(), rc.data(), device));
+    for (size_t k = 0; k < nf; k++) out[k].resize(rc[k] > 0 ? (size_t)rc[k] : 0);
+    return out;
+}
 inline Header GetInfo(const Bytes &data) { return ParseHeader(data); }                                            // blosc.go:306-308
 inline int GetDecompressedSize(const Bytes &data) { return (int)ParseHeader(data).NBytesOrig; }                   // blosc.go:311-317
 

@@ -352,6 +352,41 @@ int     hb_cblosc_decompress_dev(const hb_cblosc_header *hdr, const void *d_fram
 /* host pointers: returns the decoded bytes (== nbytes of the header) or HB_ERR_*: HB_ERR_INVALID_CODEC for the codec formats
  * that are not LZ4, HB_ERR_DECOMPRESSION_FAILED for anything blosc_decompress() answers with a negative number */
 int64_t hb_cblosc_decompress(const void *frame, size_t n, void *dst, size_t cap, int device);
+/* ---- batched C-Blosc-1 decode: many whole frames through ONE set of launches (plan, the stream decoders, one un-filter per kind that occurs,
+ *      one copy for the memcpyed frames, finish -- the same launches for 4 frames and for 4096).  What a chunked array store holds is one
+ *      c-blosc frame per chunk, 100 KB to 1 MiB each: one hb_cblosc_decompress_dev call per frame is five to seven launches for 8-256 streams
+ *      of work.
+ *      Device form (rules of hb_decompress_frames_batch_dev / hb_getitem_frames_batch_device: d_frame / d_dst are HOST arrays of device pointers,
+ *      asynchronous on `stream`, no synchronisation, no caller pointer kept, sources may be read up to 15 bytes past their end, d_work 256-byte
+ *      aligned; its name ends in _device for the reason given with hb_getitem_frame_device).  d_results: nframes records in device or pinned
+ *      memory.  The outcome of frame k is defined against hb_cblosc_decompress_dev(&hdrs[k], d_frame[k], n[k], d_dst[k], cap[k], ...):
+ *        - what that call refuses as its return value, in its order (HB_ERR_BAD_ARG for a NULL d_frame[k] or a NULL d_dst[k] with cap[k] != 0,
+ *          version, header, cbytes, HB_ERR_SHORT_BUFFER for cap[k] < nbytes, a memcpyed frame with too few bytes, codec format != 1, a bstarts
+ *          table beyond cbytes, blocksize < typesize) is d_results[k].status with bytes, total_bytes and flags 0; the other frames are not
+ *          disturbed.  All of it is decided on the host, before the device is looked for;
+ *        - everything else gives the bytes and the record of that call: flags 1, total_bytes = nbytes, status 0 with bytes = nbytes -- or, on
+ *          any plan or stream failure of THAT frame, HB_ERR_DECOMPRESSION_FAILED with bytes 0.  The fail state is per frame: a damaged frame
+ *          spoils no other.  Frame k writes at most nbytes bytes of d_dst[k] and its own part of the workspace.
+ *      The call itself returns HB_ERR_BAD_ARG for NULL arrays, nframes < 0, a misaligned d_work, or a batch with more than
+ *      HB_CBLOSC_BATCH_MAX_WORK blocks or streams (split it); HB_ERR_SHORT_BUFFER for work_bytes below the workspace query; then
+ *      HB_ERR_NO_DEVICE; HB_OK for nframes == 0 (nothing is launched).
+ *      Workspace: the frame records, one plan per frame, the prefixes, and per accepted frame its stream records and -- only when a filter is on
+ *      -- its staged copy: at most the sum of hb_cblosc_decompress_workspace() over the accepted frames + HB_CBLOSC_BATCH_FRAME_BYTES * nframes
+ *      (a refused frame adds nothing beyond the constant; the query knows no capacities, so it may count a frame the call then refuses).  0 when
+ *      the call would return an error as a whole; 256 for nframes == 0.
+ *      Host form: the frames the host can accept go up once (in ONE copy when they follow each other exactly in host memory), the device form
+ *      runs once, the result records come down in one copy and the outputs in one copy when the destinations follow each other inside their
+ *      capacities (else one per frame; a failed frame's buffer keeps what the caller had in it).  Every frame the batch did not carry or that did
+ *      not end with status 0 is answered by hb_cblosc_decompress, one call each: rc[k] is always exactly what that call returns for the frame,
+ *      HB_ERR_INVALID_CODEC for blosclz frames included.  Returns HB_OK unless the arguments as a whole are unusable. ---- */
+#define HB_CBLOSC_BATCH_MAX_WORK    0x7FFFFFFFu  /* blocks, streams, and workgroups of any one un-filter kind over all frames: 32-bit prefixes */
+#define HB_CBLOSC_BATCH_FRAME_BYTES 2048         /* workspace per frame beyond its one-frame size */
+size_t  hb_cblosc_decompress_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n);
+int     hb_cblosc_decompress_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n,
+                                                 void *const *d_dst, const size_t *cap,
+                                                 void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
+int     hb_cblosc_decompress_frames_batch(int nframes, const void *const *frame, const size_t *n,
+                                          void *const *dst, const size_t *cap, int64_t *rc, int device);
 /* blosc_getitem of c-blosc 1.x: items [start, start + nitems) of the header's typesize.  Only the blocks that hold the range are planned,
  * decoded and un-filtered (other blocks' streams and bstarts entries are never read, so damage there is not seen); memcpyed frames: a copy.
  * Refusals in this order: the header's (as hb_cblosc_decompress, codec format and block geometry included, before anything is sized),
