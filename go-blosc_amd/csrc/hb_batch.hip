@@ -19,6 +19,7 @@
 #include "hb_sym_decode.h"
 #include "hb_frame_plan.h"
 #include "hb_cblosc_batch.h"
+#include "hb_cblosc_enc_batch.h"
 #include <vector>
 #include <algorithm>
 #include <cstring>
@@ -650,6 +651,82 @@ int hb_cblosc_decompress_frames_batch(int nframes, const void *const *frame, con
     }
     if (hipStreamSynchronize(nullptr) != hipSuccess) return fail_all();
     for (int i = 0; i < m; i++) if (res[(size_t)i].status != HB_OK) single(P.idx[(size_t)i]);
+    return HB_OK;
+}
+
+// Many inputs to C-Blosc-1 frames (include/hipblosc.h).  cbe_host_plan (hb_cblosc_enc_batch.h) says which inputs the batch carries and where they
+// and their frames lie on the device; whatever it does not carry, and whatever did not end with status 0 on the device, is answered by
+// hb_cblosc_compress, so that rc[k] is its answer in every case.
+int hb_cblosc_compress_frames_batch(int nframes, const void *const *src, const size_t *n, void *const *dst, const size_t *cap, int64_t *rc,
+                                    int shuffle, int typesize, int device) {
+    if (nframes < 0) return HB_ERR_BAD_ARG;
+    if (nframes == 0) return HB_OK;
+    if (!src || !n || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
+    auto single = [&](int k) { rc[k] = hb_cblosc_compress(src[k], n[k], dst[k], cap[k], shuffle, typesize, device); };
+    CbeHostPlan P;
+    if (typesize >= 1 && typesize <= 255 && shuffle >= 0 && shuffle <= 2) cbe_host_plan(nframes, src, n, dst, typesize, P);      // (else: every call refuses)
+    const int m = (int)P.idx.size();
+    std::vector<uint8_t> carried((size_t)nframes, 0);
+    for (int k : P.idx) carried[(size_t)k] = 1;
+    for (int k = 0; k < nframes; k++) if (!carried[(size_t)k]) single(k);
+    if (m == 0) return HB_OK;
+    auto rest_single = [&]() { for (int k : P.idx) single(k); return HB_OK; };
+    if (hb_select_device(device) != HB_OK) return rest_single();
+    const size_t wb = hb_cblosc_compress_frames_batch_workspace(m, P.ns.data(), shuffle, typesize);
+    if (!wb) return rest_single();                                       // (a batch beyond the 32-bit limits: one call per input is still right)
+    auto fail_all = [&]() { for (int k : P.idx) rc[k] = HB_ERR_HIP; return HB_OK; };
+    Scratch sc(device);
+    uint8_t *d_in = sc.get(P.in_bytes + 256), *d_out = sc.get(P.out_bytes + 256), *d_work = sc.get(wb), *d_res = sc.get((size_t)m * sizeof(hb_result));
+    if (!d_in || !d_out || !d_work || !d_res) return fail_all();
+    d_in += (16u - ((uintptr_t)d_in & 15u)) & 15u;                       // (the plan's offsets are multiples of 16: so are the addresses)
+    if (P.span_in && hipMemcpyAsync(d_in, src[P.idx[0]], P.in_bytes - 64, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
+    std::vector<const void *> ps((size_t)m); std::vector<void *> pf((size_t)m);
+    for (int i = 0; i < m; i++) {
+        ps[(size_t)i] = d_in + P.ioff[(size_t)i]; pf[(size_t)i] = d_out + P.ooff[(size_t)i];
+        if (!P.span_in && P.ns[(size_t)i] && hipMemcpyAsync(d_in + P.ioff[(size_t)i], src[P.idx[(size_t)i]], P.ns[(size_t)i], hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
+    }
+    const int st = hb_cblosc_compress_frames_batch_device(m, ps.data(), P.ns.data(), pf.data(), P.caps.data(), shuffle, typesize, d_work, wb, (hb_result *)d_res, nullptr);
+    if (st) { for (int k : P.idx) rc[k] = st; return HB_OK; }
+    std::vector<hb_result> res((size_t)m);
+    if (hipMemcpy(res.data(), d_res, (size_t)m * sizeof(hb_result), hipMemcpyDeviceToHost) != hipSuccess) return fail_all();
+    // download as in hb_compress_frames_batch: many small frames are packed on the device and come down in ONE copy, large ones one copy each
+    size_t total_out = 0;
+    std::vector<size_t> outs((size_t)m, 0), poff((size_t)m, 0);
+    std::vector<uint8_t> again((size_t)m, 0);
+    for (int i = 0; i < m; i++) {
+        const int k = P.idx[(size_t)i];
+        const hb_result &r = res[(size_t)i];
+        if (r.status) { again[(size_t)i] = 1; rc[k] = r.status; continue; }
+        if (r.bytes > cap[k]) { rc[k] = HB_ERR_SHORT_BUFFER; continue; }  // (what hb_cblosc_compress answers when the frame does not fit)
+        outs[(size_t)i] = (size_t)r.bytes; poff[(size_t)i] = total_out; total_out += (size_t)r.bytes; rc[k] = (int64_t)r.bytes;
+    }
+    const bool packed = m >= 16 && total_out / (size_t)m < ((size_t)256 << 10);
+    if (packed && total_out) {
+        std::vector<PackJob> jobs((size_t)m);
+        size_t mx = 0;
+        for (int i = 0; i < m; i++) { jobs[(size_t)i] = PackJob{(const uint8_t *)pf[(size_t)i], (uint64_t)poff[(size_t)i], (uint64_t)outs[(size_t)i]}; mx = std::max(mx, outs[(size_t)i]); }
+        uint8_t *d_pack = sc.get(total_out + 256), *d_jobs = sc.get((size_t)m * sizeof(PackJob));
+        std::vector<uint8_t> host(total_out);
+        bool good = d_pack && d_jobs && hipMemcpyAsync(d_jobs, jobs.data(), (size_t)m * sizeof(PackJob), hipMemcpyHostToDevice, nullptr) == hipSuccess;
+        for (int j0 = 0; good && j0 < m; j0 += 65535) {
+            const unsigned ny = (unsigned)std::min(65535, m - j0), gx = (unsigned)std::min<size_t>(16, (mx + 65535) / 65536);
+            hipLaunchKernelGGL(k_bt_pack, dim3(gx ? gx : 1, ny), dim3(256), 0, nullptr, (const PackJob *)d_jobs + j0, d_pack);
+        }
+        good = good && hipMemcpy(host.data(), d_pack, total_out, hipMemcpyDeviceToHost) == hipSuccess;
+        for (int i = 0; i < m; i++) {
+            const int k = P.idx[(size_t)i];
+            if (rc[k] < 0) continue;
+            if (good) memcpy(dst[k], host.data() + poff[(size_t)i], outs[(size_t)i]); else rc[k] = HB_ERR_HIP;
+        }
+    } else {
+        for (int i = 0; i < m; i++) {
+            const int k = P.idx[(size_t)i];
+            if (rc[k] < 0) continue;
+            if (hipMemcpyAsync(dst[k], pf[(size_t)i], outs[(size_t)i], hipMemcpyDeviceToHost, nullptr) != hipSuccess) rc[k] = HB_ERR_HIP;
+        }
+        if (hipStreamSynchronize(nullptr) != hipSuccess) return fail_all();
+    }
+    for (int i = 0; i < m; i++) if (again[(size_t)i]) single(P.idx[(size_t)i]);
     return HB_OK;
 }
 

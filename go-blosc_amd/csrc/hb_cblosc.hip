@@ -21,6 +21,7 @@
 
 #include <cstring>
 #include "hb_cblosc_batch.h"       // the flags, cb_nsplit, CbStream / CbPlan, and the host side of the batch
+#include "hb_cblosc_enc_batch.h"   // the geometry of a written frame, and the host side of the batched encode
 
 // ---- the streams of blocks [b0, b0 + nb) (hb_cblosc_getitem_device: the blocks that cover a range; the others' bstarts entries and streams
 // are never read); stream offsets count from the first of these blocks ----
@@ -293,7 +294,39 @@ __global__ void k_cb_bitshuffle4_fast(uint8_t *__restrict__ dst, const uint8_t *
         }
     }
 }
-// the inverse over the workgroups [0, gx) of one frame (k_cbb_unfilter)
+// one work item of the forward direction for k_cbeb_filter: the loop body of k_cb_bitshuffle4_fast<true> once more -- that kernel keeps its own
+// copy, because calling a function from its loop costs it 24 VGPRs (66 -> 90, occupancy 7 -> 5)
+__device__ __forceinline__ void cb_bitshuffle4_item(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, size_t base, uint32_t ng, uint32_t q) {
+            uint32_t r[4][8];                                                   // [byte j][bit k]: 4 bytes = groups 4 q .. 4 q + 3 of row 8 j + k
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+#pragma unroll
+                for (int k = 0; k < 8; k++) r[j][k] = 0;
+#pragma unroll
+            for (int g = 0; g < 4; g++) {
+                const u32x4 a = ld16u(src + base + (size_t)(32u * q + 8u * g) * 4u), bb = ld16u(src + base + (size_t)(32u * q + 8u * g) * 4u + 16u);
+                const uint32_t w[8] = {a.x, a.y, a.z, a.w, bb.x, bb.y, bb.z, bb.w};
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    uint64_t v = 0;
+#pragma unroll
+                    for (int e = 0; e < 8; e++) v |= (uint64_t)((w[e] >> (8 * j)) & 255u) << (8 * e);
+                    v = cb_transpose8(v);                                       // byte k = bit k of byte j of the 8 elements
+#pragma unroll
+                    for (int k = 0; k < 8; k++) r[j][k] |= (uint32_t)((v >> (8 * k)) & 255u) << (8 * g);
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; j++)
+#pragma unroll
+                for (int k = 0; k < 8; k++) st4u(dst + base + (size_t)(8 * j + k) * ng + 4u * q, r[j][k]);
+}
+// either direction over the workgroups [0, gx) of one frame (k_cbb_unfilter, k_cbeb_filter)
+__device__ __forceinline__ void cb_bitshuffle4_fast(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nfull, uint32_t blocksize, uint32_t bx, uint32_t gx) {
+    const uint32_t ng = blocksize / 32u, per = ng / 4u;
+    for (uint64_t i = (uint64_t)bx * blockDim.x + threadIdx.x; i < (uint64_t)nfull * per; i += (uint64_t)gx * blockDim.x)
+        cb_bitshuffle4_item(dst, src, (size_t)(uint32_t)(i / per) * blocksize, ng, (uint32_t)(i % per));
+}
 __device__ __forceinline__ void cb_bitunshuffle4_fast(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nfull, uint32_t blocksize, uint32_t bx, uint32_t gx) {
     const uint32_t ng = blocksize / 32u, per = ng / 4u;
     for (uint64_t i = (uint64_t)bx * blockDim.x + threadIdx.x; i < (uint64_t)nfull * per; i += (uint64_t)gx * blockDim.x)
@@ -406,12 +439,12 @@ __global__ __launch_bounds__(64) void k_cbb_finish(const CbbFrame *__restrict__ 
 // k_cb_bitshuffle, the mirrors of the kernels above), a stream that does not shrink is stored (cbytes == its size, like
 // blosc_c), the last, shorter block is one stored stream.  Ratio = the chunk-local encoder's + 4 bytes per stream.
 // =====================================================================================================================
-struct CbEncPlan { uint32_t total, pad[3]; };
-
-__global__ void k_cb_shuffle(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nbytes, uint32_t blocksize, uint32_t ts) {
+// (CbEncPlan: hb_cblosc_enc_batch.h.  The filters' bodies with their workgroup index `bx` and grid size `gx`, as above: k_cbeb_filter passes
+// the workgroup's place among those of its frame)
+__device__ __forceinline__ void cb_shuffle(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nbytes, uint32_t blocksize, uint32_t ts, uint32_t bx, uint32_t gx) {
     const uint32_t nblocks = (nbytes + blocksize - 1) / blocksize;
     const uint32_t per = blocksize / ts + 1u;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (uint64_t)nblocks * per; i += (uint64_t)gridDim.x * blockDim.x) {
+    for (uint64_t i = (uint64_t)bx * blockDim.x + threadIdx.x; i < (uint64_t)nblocks * per; i += (uint64_t)gx * blockDim.x) {
         const uint32_t b = (uint32_t)(i / per), e = (uint32_t)(i % per);
         const uint32_t base = b * blocksize, bsize = nbytes - base < blocksize ? nbytes - base : blocksize, nel = bsize / ts;
         if (e < nel) {
@@ -423,10 +456,13 @@ __global__ void k_cb_shuffle(uint8_t *__restrict__ dst, const uint8_t *__restric
         }
     }
 }
-__global__ void k_cb_bitshuffle(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nbytes, uint32_t blocksize, uint32_t ts) {
+__global__ void k_cb_shuffle(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nbytes, uint32_t blocksize, uint32_t ts) {
+    cb_shuffle(dst, src, nbytes, blocksize, ts, blockIdx.x, gridDim.x);
+}
+__device__ __forceinline__ void cb_bitshuffle(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nbytes, uint32_t blocksize, uint32_t ts, uint32_t bx, uint32_t gx) {
     const uint32_t nblocks = (nbytes + blocksize - 1) / blocksize;
     const uint32_t per = blocksize / (8u * ts) + 1u;
-    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < (uint64_t)nblocks * per; i += (uint64_t)gridDim.x * blockDim.x) {
+    for (uint64_t i = (uint64_t)bx * blockDim.x + threadIdx.x; i < (uint64_t)nblocks * per; i += (uint64_t)gx * blockDim.x) {
         const uint32_t b = (uint32_t)(i / per), g = (uint32_t)(i % per);
         const uint32_t base = b * blocksize, bsize = nbytes - base < blocksize ? nbytes - base : blocksize, nel = bsize / ts;
         if (nel % 8u != 0u) { for (uint32_t k = g; k < bsize; k += per) dst[base + k] = src[base + k]; continue; }
@@ -445,6 +481,9 @@ __global__ void k_cb_bitshuffle(uint8_t *__restrict__ dst, const uint8_t *__rest
         }
     }
 }
+__global__ void k_cb_bitshuffle(uint8_t *__restrict__ dst, const uint8_t *__restrict__ src, uint32_t nbytes, uint32_t blocksize, uint32_t ts) {
+    cb_bitshuffle(dst, src, nbytes, blocksize, ts, blockIdx.x, gridDim.x);
+}
 
 struct CbChunkDesc { uint32_t lead, enc_len, last_end, mcode0; };       // = ChunkDesc of hb_lz4_enc.hip
 // bytes of stream c in the frame: 4 + the block, or 4 + the chunk itself when the block is no smaller
@@ -452,18 +491,23 @@ __device__ __forceinline__ uint32_t cb_stream_bytes(const CbChunkDesc &d) { retu
 // exclusive prefix sum of the stream sizes, 1024 chunks per tile: tile sums, one workgroup over the tiles, offsets
 // (fused_nblk != 0: the descriptors / records come from the fused shuffle + match kernel, stream (block b, plane j) at index j * nblk + b)
 __device__ __forceinline__ uint32_t cb_desc_index(uint32_t c, uint32_t nsplit, uint32_t fused_nblk) { return fused_nblk ? (c % nsplit) * fused_nblk + c / nsplit : c; }
-__global__ __launch_bounds__(256) void k_cbe_tiles(const CbChunkDesc *__restrict__ desc, uint32_t nchunks, uint32_t nsplit, uint32_t fused_nblk, uint32_t *__restrict__ tile_sum) {
-    __shared__ uint32_t s[256];
-    const uint32_t t0 = blockIdx.x * 1024u;
+// (bodies with the tile index `bx` among the frame's tiles and their LDS handed in: the one-frame kernels pass blockIdx.x, the batch kernels
+// k_cbeb_* the tile's place in its frame and that frame's descriptors, tile sums and plan)
+__device__ __forceinline__ void cbe_tiles(const CbChunkDesc *__restrict__ desc, uint32_t nchunks, uint32_t nsplit, uint32_t fused_nblk, uint32_t *__restrict__ tile_sum, uint32_t bx,
+                                          uint32_t *s) {
+    const uint32_t t0 = bx * 1024u;
     uint32_t sum = 0;
     for (uint32_t k = 0; k < 4u; k++) { const uint32_t c = t0 + k * 256u + threadIdx.x; if (c < nchunks) sum += cb_stream_bytes(desc[cb_desc_index(c, nsplit, fused_nblk)]); }
     s[threadIdx.x] = sum;
     __syncthreads();
     for (int d = 128; d > 0; d >>= 1) { if ((int)threadIdx.x < d) s[threadIdx.x] += s[threadIdx.x + d]; __syncthreads(); }
-    if (threadIdx.x == 0) tile_sum[blockIdx.x] = s[0];
+    if (threadIdx.x == 0) tile_sum[bx] = s[0];
 }
-__global__ __launch_bounds__(1024) void k_cbe_scan(uint32_t *tile_sum, uint32_t ntiles, CbEncPlan *plan) {
-    __shared__ uint32_t s[1024];
+__global__ __launch_bounds__(256) void k_cbe_tiles(const CbChunkDesc *__restrict__ desc, uint32_t nchunks, uint32_t nsplit, uint32_t fused_nblk, uint32_t *__restrict__ tile_sum) {
+    __shared__ uint32_t s[256];
+    cbe_tiles(desc, nchunks, nsplit, fused_nblk, tile_sum, blockIdx.x, s);
+}
+__device__ __forceinline__ void cbe_scan(uint32_t *tile_sum, uint32_t ntiles, CbEncPlan *plan, uint32_t *s) {
     const int t = threadIdx.x;
     // (ntiles <= 1024: inputs below 4 GiB)
     const uint32_t v = (uint32_t)t < ntiles ? tile_sum[t] : 0u;
@@ -473,20 +517,23 @@ __global__ __launch_bounds__(1024) void k_cbe_scan(uint32_t *tile_sum, uint32_t 
     if ((uint32_t)t < ntiles) tile_sum[t] = s[t] - v;
     if (t == 1023) plan->total = s[1023];
 }
+__global__ __launch_bounds__(1024) void k_cbe_scan(uint32_t *tile_sum, uint32_t ntiles, CbEncPlan *plan) {
+    __shared__ uint32_t s[1024];
+    cbe_scan(tile_sum, ntiles, plan, s);
+}
 // one wavefront per chunk writes { cbytes, block or chunk }; the first chunk of a block also writes the block's bstarts entry.
 // 1024 chunks per workgroup of 16 wavefronts: latency-bound small copies, so as many of them in flight as the chip takes.
-__global__ __launch_bounds__(1024) void k_cbe_pack(const CbChunkDesc *__restrict__ desc, const uint8_t *__restrict__ records, const uint8_t *__restrict__ filtered,
-                                                   const uint32_t *__restrict__ tile_off, uint32_t nchunks, uint32_t nsplit, uint32_t fused_nblk, uint32_t data0, uint8_t *__restrict__ frame) {
-    __shared__ uint32_t s[1024];
-    __shared__ uint32_t s_off[1024];
-    const uint32_t t0 = blockIdx.x * 1024u;
+__device__ __forceinline__ void cbe_pack(const CbChunkDesc *__restrict__ desc, const uint8_t *__restrict__ records, const uint8_t *__restrict__ filtered,
+                                         const uint32_t *__restrict__ tile_off, uint32_t nchunks, uint32_t nsplit, uint32_t fused_nblk, uint32_t data0, uint8_t *__restrict__ frame,
+                                         uint32_t bx, uint32_t *s, uint32_t *s_off) {
+    const uint32_t t0 = bx * 1024u;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const uint32_t c_mine = t0 + (uint32_t)t;
     const uint32_t mine = c_mine < nchunks ? cb_stream_bytes(desc[cb_desc_index(c_mine, nsplit, fused_nblk)]) : 0u;
     s[t] = mine;
     __syncthreads();
     for (int d = 1; d < 1024; d <<= 1) { const uint32_t y = t >= d ? s[t - d] : 0u; __syncthreads(); s[t] += y; __syncthreads(); }
-    s_off[t] = data0 + tile_off[blockIdx.x] + s[t] - mine;
+    s_off[t] = data0 + tile_off[bx] + s[t] - mine;
     __syncthreads();
     for (uint32_t k = w; k < 1024u; k += 16u) {
         const uint32_t c = t0 + k;
@@ -519,17 +566,22 @@ __global__ __launch_bounds__(1024) void k_cbe_pack(const CbChunkDesc *__restrict
         } else wave_copy_g2g(frame + at + 4u, stored ? filtered + (size_t)c * HB_CHUNK : records + (size_t)ci * HB_RSTRIDE, cb, lane);
     }
 }
-// header, the last (shorter) block as one stored stream, the result
-__global__ __launch_bounds__(64) void k_cbe_finish(const CbEncPlan *plan, const uint8_t *__restrict__ filtered, uint32_t nbytes, uint32_t blocksize, uint32_t ts, uint32_t flags,
-                                                   uint32_t nfull_blocks, uint32_t data0, uint8_t *__restrict__ frame, uint64_t cap, hb_result *result) {
-    const int lane = threadIdx.x;
+__global__ __launch_bounds__(1024) void k_cbe_pack(const CbChunkDesc *__restrict__ desc, const uint8_t *__restrict__ records, const uint8_t *__restrict__ filtered,
+                                                   const uint32_t *__restrict__ tile_off, uint32_t nchunks, uint32_t nsplit, uint32_t fused_nblk, uint32_t data0, uint8_t *__restrict__ frame) {
+    __shared__ uint32_t s[1024];
+    __shared__ uint32_t s_off[1024];
+    cbe_pack(desc, records, filtered, tile_off, nchunks, nsplit, fused_nblk, data0, frame, blockIdx.x, s, s_off);
+}
+// header, the last (shorter) block as one stored stream (its filtered bytes at `last`), the result
+__device__ __forceinline__ void cbe_finish(const CbEncPlan *plan, const uint8_t *__restrict__ last, uint32_t nbytes, uint32_t blocksize, uint32_t ts, uint32_t flags,
+                                           uint32_t nfull_blocks, uint32_t data0, uint8_t *__restrict__ frame, uint64_t cap, hb_result *result, int lane) {
     const uint32_t leftover = nbytes - nfull_blocks * blocksize;
     const uint32_t at = data0 + plan->total;
     const uint64_t cbytes = (uint64_t)at + (leftover ? 4u + leftover : 0u);
     if (cbytes > cap || cbytes > 0xFFFFFFFFull) { if (lane == 0) { result->status = HB_ERR_SHORT_BUFFER; result->bytes = 0; result->total_bytes = 0; result->flags = 0; result->reserved = 0; } return; }
     if (leftover) {
         if (lane < 4) { frame[at + lane] = (uint8_t)(leftover >> (8 * lane)); frame[16u + 4u * nfull_blocks + lane] = (uint8_t)(at >> (8 * lane)); }
-        wave_copy_g2g(frame + at + 4u, filtered + (size_t)nfull_blocks * blocksize, leftover, lane);
+        wave_copy_g2g(frame + at + 4u, last, leftover, lane);
     }
     if (lane == 0) {
         frame[0] = 2; frame[1] = 1; frame[2] = (uint8_t)flags; frame[3] = (uint8_t)ts;                  // BLOSC_VERSION_FORMAT, LZ4 version format
@@ -538,29 +590,105 @@ __global__ __launch_bounds__(64) void k_cbe_finish(const CbEncPlan *plan, const 
     }
 }
 
+__global__ __launch_bounds__(64) void k_cbe_finish(const CbEncPlan *plan, const uint8_t *__restrict__ filtered, uint32_t nbytes, uint32_t blocksize, uint32_t ts, uint32_t flags,
+                                                   uint32_t nfull_blocks, uint32_t data0, uint8_t *__restrict__ frame, uint64_t cap, hb_result *result) {
+    cbe_finish(plan, filtered + (size_t)nfull_blocks * blocksize, nbytes, blocksize, ts, flags, nfull_blocks, data0, frame, cap, result, (int)threadIdx.x);
+}
+
 // inputs below one chunk: a memcpyed frame (what c-blosc itself writes for buffers it cannot shrink)
-__global__ void k_cbe_memcpy_header(uint8_t *frame, uint32_t nbytes, uint32_t ts, uint32_t flags, hb_result *result) {
+__device__ __forceinline__ void cbe_memcpy_header(uint8_t *frame, uint32_t nbytes, uint32_t ts, uint32_t flags, hb_result *result) {
     const uint32_t cbytes = 16u + nbytes;
     uint32_t bs = nbytes - nbytes % ts; if (bs == 0u) bs = nbytes ? 1u : 0u;
     frame[0] = 2; frame[1] = 1; frame[2] = (uint8_t)flags; frame[3] = (uint8_t)ts;
     for (int q = 0; q < 4; q++) { frame[4 + q] = (uint8_t)(nbytes >> (8 * q)); frame[8 + q] = (uint8_t)(bs >> (8 * q)); frame[12 + q] = (uint8_t)(cbytes >> (8 * q)); }
     result->status = HB_OK; result->bytes = cbytes; result->total_bytes = cbytes; result->flags = 0; result->reserved = 0;
 }
+__global__ void k_cbe_memcpy_header(uint8_t *frame, uint32_t nbytes, uint32_t ts, uint32_t flags, hb_result *result) { cbe_memcpy_header(frame, nbytes, ts, flags, result); }
+
+// ---- batches (hb_cblosc_compress_frames_batch_device): many frames through ONE set of launches; the records, prefixes and routes are
+// hb_cblosc_enc_batch.h's.  Chunks, tiles and blocks are as independent across frames as inside one, so the bodies above run over flat spaces. ----
+// one workgroup per frame: whose every chunk of the map is (gap chunks: nobody's)
+__global__ __launch_bounds__(64) void k_cbeb_map(const CbeFrame *__restrict__ frames, uint32_t *__restrict__ chunk_frame) {
+    const CbeFrame &F = frames[blockIdx.x];
+    for (uint32_t c = threadIdx.x; c < F.mspan; c += 64u) chunk_frame[F.mchunk0 + c] = c < F.nchunks ? blockIdx.x : 0xFFFFFFFFu;
+}
+// the filter over the flat workgroup space: a frame's first fmain workgroups take its whole blocks (only a frame that is not fused has any),
+// the other ftail its last, shorter block
+template <bool BITS>
+__global__ __launch_bounds__(256) void k_cbeb_filter(const CbeFrame *__restrict__ frames, const uint32_t *__restrict__ fblk, uint32_t nframes, uint8_t *work) {
+    const uint32_t k = hb_owner(fblk, nframes, blockIdx.x);
+    const CbeFrame &F = frames[k];
+    uint32_t bx = blockIdx.x - fblk[k];
+    const uint32_t done = F.nfull * F.blocksize;
+    if (bx < F.fmain) {
+        uint8_t *dst = work + F.fsrc_off;
+        if constexpr (BITS) {
+            if (F.ffast) cb_bitshuffle4_fast(dst, F.src, F.nfull, F.blocksize, bx, F.fmain);
+            else cb_bitshuffle(dst, F.src, done, F.blocksize, F.typesize, bx, F.fmain);
+        } else cb_shuffle(dst, F.src, done, F.blocksize, F.typesize, bx, F.fmain);
+    } else {
+        bx -= F.fmain;
+        if constexpr (BITS) cb_bitshuffle(work + F.tail_off, F.src + done, F.nbytes - done, F.blocksize, F.typesize, bx, F.ftail);
+        else cb_shuffle(work + F.tail_off, F.src + done, F.nbytes - done, F.blocksize, F.typesize, bx, F.ftail);
+    }
+}
+// one workgroup per tile of the flat tile space (tiles never span two frames)
+__global__ __launch_bounds__(256) void k_cbeb_tiles(const CbeFrame *__restrict__ frames, const uint32_t *__restrict__ tile0, uint32_t nframes,
+                                                    const CbChunkDesc *__restrict__ desc, uint32_t *__restrict__ tile_sum) {
+    __shared__ uint32_t s[256];
+    const uint32_t k = hb_owner(tile0, nframes, blockIdx.x);
+    const CbeFrame &F = frames[k];
+    cbe_tiles(desc + F.desc0, F.nchunks, F.nsplit, F.mode == CBE_FUSED ? F.nfull : 0u, tile_sum + F.tile0, blockIdx.x - F.tile0, s);
+}
+// one workgroup per frame over its tiles (at most 1024 of them: inputs below 2 GiB)
+__global__ __launch_bounds__(1024) void k_cbeb_scan(const CbeFrame *__restrict__ frames, uint32_t *tile_sum, CbEncPlan *plans) {
+    __shared__ uint32_t s[1024];
+    const CbeFrame &F = frames[blockIdx.x];
+    if (F.ntiles == 0u) return;                                            // (refused, memcpyed: the plan stays cleared)
+    cbe_scan(tile_sum + F.tile0, F.ntiles, plans + blockIdx.x, s);
+}
+__global__ __launch_bounds__(1024) void k_cbeb_pack(const CbeFrame *__restrict__ frames, const uint32_t *__restrict__ tile0, uint32_t nframes,
+                                                    const CbChunkDesc *__restrict__ desc, const uint8_t *__restrict__ records, const uint32_t *__restrict__ tile_off,
+                                                    const uint8_t *work) {
+    __shared__ uint32_t s[1024];
+    __shared__ uint32_t s_off[1024];
+    const uint32_t k = hb_owner(tile0, nframes, blockIdx.x);
+    const CbeFrame &F = frames[k];
+    const bool fused = F.mode == CBE_FUSED;
+    const uint8_t *filtered = F.fsrc_off ? work + F.fsrc_off : F.src;      // (fused: the input itself, the stored planes are gathered from it)
+    cbe_pack(desc + F.desc0, records + (size_t)F.desc0 * HB_RSTRIDE, filtered, tile_off + F.tile0, F.nchunks, F.nsplit, fused ? F.nfull : 0u, 16u + 4u * F.nblocks, F.dst,
+             blockIdx.x - F.tile0, s, s_off);
+}
+// one wavefront per frame: what the host decided, the memcpyed frame, or k_cbe_finish's header, last block and record
+__global__ __launch_bounds__(64) void k_cbeb_finish(const CbeFrame *__restrict__ frames, const CbEncPlan *plans, const uint8_t *work, hb_result *results) {
+    const uint32_t k = blockIdx.x;
+    const int lane = threadIdx.x;
+    const CbeFrame &F = frames[k];
+    hb_result *r = results + k;
+    if (F.mode == CBE_REFUSED) {
+        if (lane == 0) { r->status = F.status; r->flags = 0; r->bytes = 0; r->total_bytes = 0; r->reserved = 0; }
+        return;
+    }
+    if (F.mode == CBE_MEMCPY) {
+        wave_copy_g2g(F.dst + 16, F.src, F.nbytes, lane);
+        if (lane == 0) cbe_memcpy_header(F.dst, F.nbytes, F.typesize, F.flags, r);
+        return;
+    }
+    const uint8_t *last = F.tail_off ? work + F.tail_off : F.src + (size_t)F.nfull * F.blocksize;
+    cbe_finish(plans + k, last, F.nbytes, F.blocksize, F.typesize, F.flags, F.nfull, 16u + 4u * F.nblocks, F.dst, F.cap, r, lane);
+}
 
 void hb_launch_match_selfcontained(const uint8_t *src, size_t n, void *desc, uint8_t *records, uint32_t nchunks, int accel, hipStream_t s);   // hb_lz4_enc.hip
 bool hb_launch_match_fused_selfcontained(const uint8_t *src, int typesize, void *desc, uint8_t *records, uint32_t nblk, int accel, hipStream_t s);
+void hb_launch_match_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, void *desc, uint8_t *records, uint32_t total_chunks, int accel, hipStream_t s);
+bool hb_launch_match_fused_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, int typesize, void *desc, uint8_t *records, uint32_t total_items, int accel,
+                                               hipStream_t s);
 
 struct CbEncLayout { size_t plan, tiles, desc, records, filtered, total; uint32_t blocksize, nsplit, nblocks, nfull, nchunks, ntiles; };
 static CbEncLayout cbe_layout(size_t n, int shuffle, int typesize) {
     CbEncLayout L;
-    const bool filt = (shuffle == 1 && typesize > 1) || shuffle == 2;
-    L.nsplit = (filt && typesize <= 16) ? (uint32_t)typesize : 1u;
-    if (n < (size_t)HB_CHUNK * L.nsplit) L.nsplit = 1u;                   // (c-blosc refuses a blocksize above nbytes)
-    L.blocksize = HB_CHUNK * L.nsplit;
-    L.nblocks = (uint32_t)((n + L.blocksize - 1) / L.blocksize);
-    L.nfull = (uint32_t)(n / L.blocksize);
-    L.nchunks = L.nfull * L.nsplit;
-    L.ntiles = (L.nchunks + 1023u) / 1024u;
+    const CbeGeom G = cbe_geom(n, shuffle, typesize);                     // (hb_cblosc_enc_batch.h: one geometry for this call and for the batch)
+    L.nsplit = G.nsplit; L.blocksize = G.blocksize; L.nblocks = G.nblocks; L.nfull = G.nfull; L.nchunks = G.nchunks; L.ntiles = G.ntiles;
     size_t o = 0;
     auto take = [&](size_t b) { size_t at = o; o += cb_align(b); return at; };
     L.plan = take(sizeof(CbEncPlan));
@@ -840,8 +968,7 @@ int hb_cblosc_getitem_device(const hb_cblosc_header *hdr, const void *d_frame, s
 }
 
 size_t hb_cblosc_bound(size_t n, int typesize) {
-    const size_t ts = typesize > 0 ? (size_t)typesize : 1;
-    return 16 + 4 * (n / HB_CHUNK + 2) + n + 4 * (n / HB_CHUNK + ts + 2) + 64;
+    return cbe_bound(n, typesize);
 }
 size_t hb_cblosc_compress_workspace(size_t n, int shuffle, int typesize) { return cbe_layout(n, shuffle, typesize > 0 ? typesize : 1).total; }
 
@@ -870,9 +997,8 @@ int hb_cblosc_compress_dev(const void *d_src, size_t n, void *d_frame, size_t ca
         return HB_OK;
     }
     const uint8_t *fsrc = (const uint8_t *)d_src;
-    // byte shuffle with typesize 2 / 4 / 8 and split blocks: a C-Blosc block of 4096 elements IS the unit of the fused shuffle + match
-    // kernel (hb_lz4_enc.hip), only the order of the chunks differs -- no filtered buffer, except for the last, shorter block
-    const bool fuse = unshuf && L.nsplit == (uint32_t)typesize && (typesize == 2 || typesize == 4 || typesize == 8) && L.nfull != 0u && ((uintptr_t)d_src & 15u) == 0;
+    // the fused shuffle + match route (cbe_fuse, hb_cblosc_enc_batch.h): no filtered buffer, except for the last, shorter block
+    const bool fuse = cbe_fuse(cbe_geom(n, shuffle, typesize), typesize, d_src);
     const uint32_t tail = (uint32_t)(n - (size_t)L.nfull * L.blocksize);
     hb_prof_begin("k_cb_filter", s);
     if (fuse) {
@@ -905,6 +1031,85 @@ int hb_cblosc_compress_dev(const void *d_src, size_t n, void *d_frame, size_t ca
     }
     hipLaunchKernelGGL(k_cbe_finish, dim3(1), dim3(64), 0, s, plan, fuse ? (const uint8_t *)filtered : fsrc, (uint32_t)n, L.blocksize, (uint32_t)typesize, flags, L.nfull, 16u + 4u * L.nblocks, (uint8_t *)d_frame,
                        (uint64_t)cap, d_result);
+    HB_HIP_TRY(hipGetLastError());
+    return HB_OK;
+}
+// ---- many inputs, one set of launches (include/hipblosc.h; the host side is hb_cblosc_enc_batch.h) ----
+size_t hb_cblosc_compress_frames_batch_workspace(int nframes, const size_t *n, int shuffle, int typesize) {
+    CbeBatch B;
+    if (cbe_prepare(nframes, nullptr, n, nullptr, nullptr, shuffle, typesize, nullptr, B)) return 0;
+    return B.query;
+}
+
+int hb_cblosc_compress_frames_batch_device(int nframes, const void *const *d_src, const size_t *n, void *const *d_frame, const size_t *cap, int shuffle, int typesize,
+                                           void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    if (nframes < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
+    if (nframes == 0) return HB_OK;
+    if (!d_src || !n || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
+    uint8_t *w = (uint8_t *)d_work;
+    CbeBatch B;
+    const int rc = cbe_prepare(nframes, d_src, n, d_frame, cap, shuffle, typesize, w, B);
+    if (rc) return rc;
+    const CbeLayout &L = B.L;
+    if (work_bytes < B.query || B.query < L.total) return HB_ERR_SHORT_BUFFER;      // (the layout never exceeds the query: hb_cblosc_enc_batch.h)
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nf = (size_t)nframes;
+    // the frame records, the matcher's records, the prefixes and the cleared plans go up in one copy (the buffer is read before the call returns)
+    std::vector<uint8_t> up(L.upload, 0);
+    memcpy(up.data() + L.frames, B.tab.data(), nf * sizeof(CbeFrame));
+    memcpy(up.data() + L.bf, B.bf.data(), nf * sizeof(BatchFrame));
+    memcpy(up.data() + L.pre, B.pre.data(), nf * 8);
+    memcpy(up.data() + L.plans, B.plans.data(), nf * sizeof(CbEncPlan));
+    hb_prof_begin("cbeb_upload", s);
+    HB_HIP_TRY(hipMemcpyAsync(w, up.data(), L.upload, hipMemcpyHostToDevice, s));
+    hb_prof_end(s);
+    const CbeFrame *d_frames = (const CbeFrame *)(w + L.frames);
+    const BatchFrame *d_bf = (const BatchFrame *)(w + L.bf);
+    const uint32_t *d_tile0 = (const uint32_t *)(w + L.pre), *d_fblk = d_tile0 + nf;
+    CbEncPlan *d_plans = (CbEncPlan *)(w + L.plans);
+    uint32_t *d_map = (uint32_t *)(w + L.map), *d_tiles = (uint32_t *)(w + L.tiles);
+    CbChunkDesc *d_desc = (CbChunkDesc *)(w + L.desc);
+    uint8_t *d_records = w + L.records;
+    const uint32_t plain = (uint32_t)B.plain_chunks, fused = (uint32_t)B.fused_chunks, ntiles = (uint32_t)B.ntiles;
+    if (B.map_chunks) {
+        hb_prof_begin("k_cbeb_map", s);
+        hipLaunchKernelGGL(k_cbeb_map, dim3((unsigned)nframes), dim3(64), 0, s, d_frames, d_map);
+        hb_prof_end(s);
+    }
+    if (B.fblocks) {
+        hb_prof_begin("k_cbeb_filter", s);
+        if (shuffle == 2) hipLaunchKernelGGL(k_cbeb_filter<true>, dim3((unsigned)B.fblocks), dim3(256), 0, s, d_frames, d_fblk, (uint32_t)nframes, w);
+        else hipLaunchKernelGGL(k_cbeb_filter<false>, dim3((unsigned)B.fblocks), dim3(256), 0, s, d_frames, d_fblk, (uint32_t)nframes, w);
+        hb_prof_end(s);
+    }
+    if (fused) {
+        hb_prof_begin("k_match_fused", s);
+        hb_launch_match_fused_selfcontained_batch(d_bf, d_map, typesize, d_desc + plain, d_records + (size_t)plain * HB_RSTRIDE, fused, 64, s);
+        hb_prof_end(s);
+    }
+    if (plain) {
+        hb_prof_begin("k_match", s);
+        // with a filter the whole blocks of these frames lie chunk after chunk in one area: one long buffer of self-contained chunks, no map
+        if (B.filtered) hb_launch_match_selfcontained(w + L.filt, (size_t)plain * HB_CHUNK, d_desc, d_records, plain, 64, s);
+        else hb_launch_match_selfcontained_batch(d_bf, d_map, d_desc, d_records, plain, 64, s);
+        hb_prof_end(s);
+    }
+    if (ntiles) {
+        hb_prof_begin("k_cbeb_tiles", s);
+        hipLaunchKernelGGL(k_cbeb_tiles, dim3(ntiles), dim3(256), 0, s, d_frames, d_tile0, (uint32_t)nframes, (const CbChunkDesc *)d_desc, d_tiles);
+        hb_prof_end(s);
+        hb_prof_begin("k_cbeb_scan", s);
+        hipLaunchKernelGGL(k_cbeb_scan, dim3((unsigned)nframes), dim3(1024), 0, s, d_frames, d_tiles, d_plans);
+        hb_prof_end(s);
+        hb_prof_begin("k_cbeb_pack", s);
+        hipLaunchKernelGGL(k_cbeb_pack, dim3(ntiles), dim3(1024), 0, s, d_frames, d_tile0, (uint32_t)nframes, (const CbChunkDesc *)d_desc, (const uint8_t *)d_records,
+                           (const uint32_t *)d_tiles, (const uint8_t *)w);
+        hb_prof_end(s);
+    }
+    hb_prof_begin("k_cbeb_finish", s);
+    hipLaunchKernelGGL(k_cbeb_finish, dim3((unsigned)nframes), dim3(64), 0, s, d_frames, (const CbEncPlan *)d_plans, (const uint8_t *)w, d_results);
+    hb_prof_end(s);
     HB_HIP_TRY(hipGetLastError());
     return HB_OK;
 }

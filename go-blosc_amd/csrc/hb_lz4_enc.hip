@@ -39,6 +39,7 @@
 // Algorithmic HBM bytes: n (read) + C (write).  Extra traffic: records (~C written + read) and the literal
 // bytes of the source read a second time by k_stitch; see DESIGN.md.
 #include "hb_lz4.h"
+#include "hb_lz4_batch_frame.h"
 #include <cstdlib>
 #include <vector>
 #include <type_traits>
@@ -100,22 +101,7 @@ struct EncPlan {
     uint64_t pad[4];
 };
 
-// ---- batches of frames in ONE set of launches (hb_compress_frames_batch_dev; SURVEY §8 f1 "frame batches") ----
-// Chunks are independent and the scan is per frame, so K frames are K segments of one flat chunk space: global chunk g belongs to
-// frame chunk_frame[g] and is that frame's chunk g - chunk0; scan tiles never span two frames (tile_frame[t]); descriptors, records
-// and tile summaries are indexed globally, positions and stream offsets stay frame-local.  The single-frame launches pass bf = NULL
-// and compile to what they were.
-struct BatchFrame {
-    const uint8_t *src;          // what the matcher reads: the filtered bytes, or the raw input when the filter is fused
-    uint8_t *dst;                // frame start
-    const uint8_t *memcpy_src;   // what a memcpy frame stores (NULL: the gated batch filter writes the payload)
-    hb_result *result;
-    EncPlan *plan;
-    uint64_t n;
-    uint32_t chunk0, nchunks;    // first global chunk / chunks of this frame
-    uint32_t tile0, ntiles;      // first global scan tile / tiles of this frame
-    uint32_t nblk, pad;          // fused byte shuffle: element blocks of the frame (nchunks = nblk * typesize)
-};
+// (BatchFrame, the frame record of the batched launches: hb_lz4_batch_frame.h)
 
 // workspace layout
 struct EncLayout {
@@ -1426,6 +1412,10 @@ static void launch_match(const hb_enc_args &a, unsigned grid, ChunkDesc *desc, u
     else HB_LAUNCH_MATCH(4, false);
 }
 
+// granule of a frame's first global chunk: with the fused byte shuffle the planes of an element block sit 8 work items apart and must
+// keep their workgroup id mod 8 (XCD), so every frame starts at a multiple of 8 * typesize (the gap chunks belong to no frame)
+static inline uint32_t batch_granule(bool fused_ts, int typesize) { return fused_ts ? 8u * (uint32_t)typesize : 1u; }
+
 // every HB_CHUNK bytes of src become an LZ4 block of their own (hb_cblosc.hip): records + descriptors only, nothing is stitched
 void hb_launch_match_selfcontained(const uint8_t *src, size_t n, void *desc, uint8_t *records, uint32_t nchunks, int accel, hipStream_t s) {
     const unsigned grid = nchunks < 256u * 256u ? nchunks : 256u * 256u;
@@ -1442,6 +1432,31 @@ bool hb_launch_match_fused_selfcontained(const uint8_t *src, int typesize, void 
     case 8: hipLaunchKernelGGL((k_match_fused<8, 1, 2>), dim3(grid), dim3(64), 0, s, src, (ChunkDesc *)desc, records, nblk, 0xFFFFFFFFu, accel, (const BatchFrame *)nullptr, (const uint32_t *)nullptr, 0u); return true;
     default: return false;
     }
+}
+
+// the two self-contained matchers over the flat chunk space of a batch (hb_cblosc.hip, hb_cblosc_compress_frames_batch_device): frame k's
+// chunks start at bf[k].chunk0, chunk_frame says whose every chunk is.  The grid of the fused launch as hb_launch_lz4_encode_batch sizes it.
+void hb_launch_match_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, void *desc, uint8_t *records, uint32_t total_chunks, int accel, hipStream_t s) {
+    const unsigned grid = total_chunks < 256u * 256u ? total_chunks : 256u * 256u;
+    hipLaunchKernelGGL((k_match<1, 2>), dim3(grid), dim3(64), 0, s, (const uint8_t *)nullptr, (uint64_t)0, (ChunkDesc *)desc, records, total_chunks, 0, 0, accel, bf, chunk_frame);
+}
+bool hb_launch_match_fused_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, int typesize, void *desc, uint8_t *records, uint32_t total_items, int accel,
+                                               hipStream_t s) {
+    if (typesize != 2 && typesize != 4 && typesize != 8) return false;
+    const uint32_t granule = batch_granule(true, typesize);
+    unsigned grid = total_items < 256u * 256u ? total_items : 256u * 256u;
+    if (total_items > 256u * 16u) {                                  // `typesize` passes per workgroup where the batch is large; a multiple of the granule
+        grid = total_items / (unsigned)typesize / granule * granule;
+        if (total_items > 256u * 64u && grid < 256u * 64u) grid = 256u * 64u;
+        if (grid > 256u * 256u) grid = 256u * 256u;
+        if (grid == 0) grid = total_items;
+    }
+    switch (typesize) {
+    case 2: hipLaunchKernelGGL((k_match_fused<2, 1, 2>), dim3(grid), dim3(64), 0, s, (const uint8_t *)nullptr, (ChunkDesc *)desc, records, 0u, 0xFFFFFFFFu, accel, bf, chunk_frame, total_items); break;
+    case 4: hipLaunchKernelGGL((k_match_fused<4, 1, 2>), dim3(grid), dim3(64), 0, s, (const uint8_t *)nullptr, (ChunkDesc *)desc, records, 0u, 0xFFFFFFFFu, accel, bf, chunk_frame, total_items); break;
+    default: hipLaunchKernelGGL((k_match_fused<8, 1, 2>), dim3(grid), dim3(64), 0, s, (const uint8_t *)nullptr, (ChunkDesc *)desc, records, 0u, 0xFFFFFFFFu, accel, bf, chunk_frame, total_items); break;
+    }
+    return true;
 }
 
 int hb_launch_lz4_encode(const hb_enc_args &a, hipStream_t s) {
@@ -1531,9 +1546,6 @@ struct EncBatchLayout {
     size_t frames, plans, jobs, chunk_frame, tile_frame, desc, tile_agg, tile_nf, tile_pre, tile_suf, records, filtered, total;
     uint32_t total_chunks, total_tiles;
 };
-// granule of a frame's first global chunk: with the fused byte shuffle the planes of an element block sit 8 work items apart and must
-// keep their workgroup id mod 8 (XCD), so every frame starts at a multiple of 8 * typesize (the gap chunks belong to no frame)
-static inline uint32_t batch_granule(bool fused_ts, int typesize) { return fused_ts ? 8u * (uint32_t)typesize : 1u; }
 
 static EncBatchLayout enc_batch_layout(int nframes, const size_t *n, uint32_t granule, bool need_filtered) {
     EncBatchLayout L{};

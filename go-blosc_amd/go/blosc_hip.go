@@ -795,3 +795,69 @@ func CBloscDecompressBatchHIP(frames [][]byte) ([][]byte, []error) {
 	}
 	return out, errs
 }
+
+// CBloscCompressBatchHIP: many CompressCBlosc calls through ONE set of kernel launches (hb_cblosc_compress_frames_batch): what a chunked array
+// store writes is one c-blosc frame per chunk, all with one shuffle and typeSize.  out[k], errs[k] are what CompressCBlosc gives for
+// datas[k].  The inputs are packed into one pinned slab, each at a 16-byte-aligned offset: they follow each other exactly while their lengths
+// are multiples of 16 (one upload), and every frame takes the route CompressCBlosc takes; the frames come back into a second pinned slab.
+func CBloscCompressBatchHIP(datas [][]byte, shuffle Shuffle, typeSize int) ([][]byte, []error) {
+	n := len(datas)
+	out := make([][]byte, n)
+	errs := make([]error, n)
+	if n == 0 {
+		return out, errs
+	}
+	if !useHIP {
+		for k, d := range datas {
+			out[k], errs[k] = CompressCBlosc(d, shuffle, typeSize)
+		}
+		return out, errs
+	}
+	srcs := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(uintptr(0)))))[:n:n]
+	dsts := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(n) * C.size_t(unsafe.Sizeof(uintptr(0)))))[:n:n]
+	defer C.free(unsafe.Pointer(&srcs[0]))
+	defer C.free(unsafe.Pointer(&dsts[0]))
+	lens := make([]C.size_t, n)
+	caps := make([]C.size_t, n)
+	rcs := make([]C.int64_t, n)
+	var inBytes, outBytes C.size_t
+	for k, d := range datas {
+		lens[k] = C.size_t(len(d))
+		caps[k] = C.hb_cblosc_bound(lens[k], C.int(typeSize))
+		inBytes += (lens[k] + 15) &^ 15
+		outBytes += caps[k]
+	}
+	slabIn, slabOut := C.hb_host_alloc(inBytes+64), C.hb_host_alloc(outBytes+64)
+	if slabIn == nil || slabOut == nil {
+		C.hb_host_free(slabIn)
+		C.hb_host_free(slabOut)
+		for k, d := range datas {
+			out[k], errs[k] = CompressCBlosc(d, shuffle, typeSize)
+		}
+		return out, errs
+	}
+	defer C.hb_host_free(slabIn)
+	defer C.hb_host_free(slabOut)
+	var io, oo C.size_t
+	for k, d := range datas {
+		srcs[k] = unsafe.Add(slabIn, uintptr(io))
+		dsts[k] = unsafe.Add(slabOut, uintptr(oo))
+		copy(unsafe.Slice((*byte)(srcs[k]), len(d)), d)
+		io += (lens[k] + 15) &^ 15
+		oo += caps[k]
+	}
+	if rc := C.hb_cblosc_compress_frames_batch(C.int(n), &srcs[0], &lens[0], &dsts[0], &caps[0], &rcs[0], C.int(shuffle), C.int(typeSize), C.int(Device)); rc != C.HB_OK {
+		for k := range datas {
+			errs[k] = hbError(C.int64_t(rc))
+		}
+		return out, errs
+	}
+	for k := range datas {
+		if rcs[k] < 0 {
+			errs[k] = hbError(rcs[k])
+		} else {
+			out[k] = append([]byte(nil), unsafe.Slice((*byte)(dsts[k]), int(rcs[k]))...)
+		}
+	}
+	return out, errs
+}

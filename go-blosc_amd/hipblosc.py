@@ -102,6 +102,7 @@ EXPORTS = [
     "hb_getitem_frame", "hb_getitem_frame_workspace", "hb_getitem_frame_device", "hb_cblosc_getitem", "hb_cblosc_getitem_workspace", "hb_cblosc_getitem_device",
     "hb_getitem_frames_batch_workspace", "hb_getitem_frames_batch_device", "hb_getitem_frames_batch",
     "hb_cblosc_decompress_frames_batch_workspace", "hb_cblosc_decompress_frames_batch_device", "hb_cblosc_decompress_frames_batch",
+    "hb_cblosc_compress_frames_batch_workspace", "hb_cblosc_compress_frames_batch_device", "hb_cblosc_compress_frames_batch",
     "hb_queue_create", "hb_queue_create_ex", "hb_queue_destroy", "hb_queue_compress", "hb_queue_decompress", "hb_queue_wait",
 ]
 
@@ -189,6 +190,9 @@ def lib():
             "hb_cblosc_decompress_frames_batch_workspace": (sz, [i32, vp, vp]),
             "hb_cblosc_decompress_frames_batch_device": (i32, [i32, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
             "hb_cblosc_decompress_frames_batch": (i32, [i32, vp, vp, vp, vp, vp, i32]),
+            "hb_cblosc_compress_frames_batch_workspace": (sz, [i32, vp, i32, i32]),
+            "hb_cblosc_compress_frames_batch_device": (i32, [i32, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
+            "hb_cblosc_compress_frames_batch": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -581,6 +585,24 @@ def CBloscCompress(data, shuffle=1, typesize=4):
     out = ctypes.create_string_buffer(cap)
     rc = _check(lib().hb_cblosc_compress(p, n, ctypes.cast(out, ctypes.c_void_p), cap, shuffle, typesize, device))
     return out.raw[:rc]
+
+
+def CBloscCompressBatch(datas, shuffle=1, typesize=4, dev=None):
+    """Many CBloscCompress calls through one set of launches (include/hipblosc.h hb_cblosc_compress_frames_batch): the i-th result is what
+    CBloscCompress(datas[i], shuffle, typesize) would have returned -- the frame, or the error (returned, not raised, as CompressBatch does)."""
+    n = len(datas)
+    if n == 0:
+        return []
+    L = lib()
+    keep = [_buf(d) for d in datas]
+    caps = [L.hb_cblosc_bound(k[1], typesize) for k in keep]
+    outs = [(ctypes.c_char * c)() for c in caps]
+    vp, sz, i64 = ctypes.c_void_p * n, ctypes.c_size_t * n, ctypes.c_int64 * n
+    srcs = vp(*[k[0].value for k in keep])
+    dsts = vp(*[ctypes.addressof(o) for o in outs])
+    rcs = i64()
+    _check(L.hb_cblosc_compress_frames_batch(n, srcs, sz(*[k[1] for k in keep]), dsts, sz(*caps), rcs, int(shuffle), int(typesize), device if dev is None else dev))
+    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(n)]
 
 
 # ---------------------------------------------------------------------------------------------

@@ -170,6 +170,25 @@ inline std::vector<Bytes> CBloscDecompressBatch(const std::vector<Bytes> &frames
     for (size_t k = 0; k < nf; k++) out[k].resize(rc[k] > 0 ? (size_t)rc[k] : 0);
     return out;
 }
+// many inputs to C-Blosc-1 frames through one set of launches (hb_cblosc_compress_frames_batch; shuffle 0 / 1 / 2 = none / byte / bit, one shuffle
+// and typesize for the whole batch): out[k] is the frame hb_cblosc_compress writes for datas[k], rc[k] its byte count or its HB_ERR_* code
+// (nothing is thrown per input)
+inline std::vector<Bytes> CBloscCompressBatch(const std::vector<Bytes> &datas, std::vector<int64_t> &rc, int shuffle = 1, int typeSize = 4, int device = 0) {
+    const size_t nf = datas.size();
+    std::vector<Bytes> out(nf);
+    rc.assign(nf, 0);
+    if (!nf) return out;
+    std::vector<const void *> src(nf); std::vector<void *> dst(nf); std::vector<size_t> ns(nf), cap(nf);
+    for (size_t k = 0; k < nf; k++) {
+        src[k] = datas[k].data(); ns[k] = datas[k].size();
+        cap[k] = hb_cblosc_bound(ns[k], typeSize);
+        out[k].resize(cap[k]);
+        dst[k] = out[k].data();
+    }
+    check(hb_cblosc_compress_frames_batch((int)nf, src.data(), ns.data(), dst.data(), cap.data(), rc.data(), shuffle, typeSize, device));
+    for (size_t k = 0; k < nf; k++) out[k].resize(rc[k] > 0 ? (size_t)rc[k] : 0);
+    return out;
+}
 inline Header GetInfo(const Bytes &data) { return ParseHeader(data); }                                            // blosc.go:306-308
 inline int GetDecompressedSize(const Bytes &data) { return (int)ParseHeader(data).NBytesOrig; }                   // blosc.go:311-317
 

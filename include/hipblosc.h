@@ -404,6 +404,42 @@ size_t  hb_cblosc_compress_workspace(size_t n, int shuffle, int typesize);
 int     hb_cblosc_compress_dev(const void *d_src, size_t n, void *d_frame, size_t cap, int shuffle, int typesize,
                                void *d_work, size_t work_bytes, hb_result *d_result, void *stream);
 int64_t hb_cblosc_compress(const void *src, size_t n, void *dst, size_t cap, int shuffle, int typesize, int device);
+/* ---- batched C-Blosc-1 encode: many inputs through ONE set of launches (upload, chunk map, filter, the matcher launch or launches, tile sums,
+ *      one scan workgroup per frame, pack, finish -- the same launches for 4 frames and for 4096).  One shuffle / typesize for the whole batch:
+ *      an array has one dtype and one filter.
+ *      Device form (rules of hb_cblosc_decompress_frames_batch_device: d_src / d_frame are HOST arrays of device pointers, asynchronous on
+ *      `stream`, no synchronisation, no caller pointer kept, d_work 256-byte aligned, d_results: nframes records in device or pinned memory;
+ *      sources may be read up to 15 bytes before and behind, inside their 16-byte blocks, exactly as the one-frame matcher does).  The outcome of
+ *      frame k is defined against hb_cblosc_compress_dev(d_src[k], n[k], d_frame[k], cap[k], shuffle, typesize, ...):
+ *        - what that call refuses per frame, in its order (HB_ERR_BAD_ARG for a NULL d_src[k] with n[k] != 0 or a NULL d_frame[k],
+ *          HB_ERR_DATA_TOO_LARGE, HB_ERR_SHORT_BUFFER for cap[k] < hb_cblosc_bound(n[k], typesize)) is d_results[k].status with bytes,
+ *          total_bytes and flags 0; nothing of such a frame is touched on the device and no other frame is disturbed.  All of it is decided
+ *          on the host, before the device is looked for;
+ *        - every other frame is byte for byte the frame that call writes for the same bytes at the same source address, with the same record.
+ *          That call takes the fused shuffle + match route for typesize 2 / 4 / 8 with the byte shuffle, at least one whole block and a
+ *          16-byte-aligned source; the batch decides PER FRAME by the same rule, so a batch may hold frames of both routes: one launch of
+ *          the fused matcher over the fused frames (every frame's first work item at a multiple of 8 x typesize), one of the plain matcher
+ *          over the rest, each only if such frames occur.  Frame k writes at most hb_cblosc_bound(n[k], typesize) bytes of d_frame[k] and
+ *          its own part of the workspace.
+ *      The call itself returns HB_ERR_BAD_ARG for nframes < 0, typesize outside 1..255 or shuffle outside 0..2 (then HB_OK for nframes == 0,
+ *      nothing is launched), NULL arrays, a NULL or misaligned d_work, a NULL d_results, or a batch with more than HB_CBLOSC_BATCH_MAX_WORK
+ *      blocks, chunks or filter workgroups (split it); HB_ERR_SHORT_BUFFER for work_bytes below the workspace query; then HB_ERR_NO_DEVICE.
+ *      Workspace: the query knows no pointers, so it charges every frame the dearer of its two routes -- a fused frame has the gap chunks in
+ *      front of it and a filtered copy of its last, shorter block only, any other frame of a batch with a filter the filtered copy of its
+ *      whole blocks: at most the sum of hb_cblosc_compress_workspace() over the frames + HB_CBLOSC_ENC_BATCH_FRAME_BYTES * nframes.  0 when the
+ *      call would return an error as a whole; 256 for nframes == 0.
+ *      Host form: inputs that follow each other exactly in host memory go up in ONE copy (while every input's offset in the span stays
+ *      16-byte aligned: each frame then takes the route hb_cblosc_compress takes), the others one copy each to 16-byte-aligned places; the
+ *      device form runs once; the records come down in one copy; many small frames are packed on the device and come down in one copy, large
+ *      ones one copy each.  Every input the batch did not carry or that did not end with status 0 is answered by hb_cblosc_compress, one call
+ *      each: rc[k] is always exactly what that call returns (the frame's bytes, or HB_ERR_*), and dst[k] holds exactly its bytes.  Returns
+ *      HB_OK unless the arguments as a whole are unusable. ---- */
+#define HB_CBLOSC_ENC_BATCH_FRAME_BYTES 270336    /* workspace per frame beyond its one-frame size: the records and up to 63 gap chunks */
+size_t  hb_cblosc_compress_frames_batch_workspace(int nframes, const size_t *n, int shuffle, int typesize);
+int     hb_cblosc_compress_frames_batch_device(int nframes, const void *const *d_src, const size_t *n, void *const *d_frame, const size_t *cap,
+                                               int shuffle, int typesize, void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
+int     hb_cblosc_compress_frames_batch(int nframes, const void *const *src, const size_t *n, void *const *dst, const size_t *cap, int64_t *rc,
+                                        int shuffle, int typesize, int device);
 
 #ifdef __cplusplus
 }
