@@ -20,6 +20,7 @@
 #include "hb_frame_plan.h"
 #include "hb_cblosc_batch.h"
 #include "hb_cblosc_enc_batch.h"
+#include "hb_cblosc_getitem_batch.h"
 #include <vector>
 #include <algorithm>
 #include <cstring>
@@ -651,6 +652,55 @@ int hb_cblosc_decompress_frames_batch(int nframes, const void *const *frame, con
     }
     if (hipStreamSynchronize(nullptr) != hipSuccess) return fail_all();
     for (int i = 0; i < m; i++) if (res[(size_t)i].status != HB_OK) single(P.idx[(size_t)i]);
+    return HB_OK;
+}
+
+// Many ranges of many C-Blosc-1 frames (include/hipblosc.h).  cbg_host_plan (hb_cblosc_getitem_batch.h) says which jobs the batch carries, which
+// frames go up and where each job's bytes lie in the packed device buffer: every frame a carried job reads goes up once, the device form runs
+// once, the records come down in one copy and the ranges in one copy.  Whatever did not end with status 0 on the device is answered by
+// hb_cblosc_getitem, so that rc[j] is its answer in every case.
+int hb_cblosc_getitem_frames_batch(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_getitem_job *jobs, void *const *dst, const size_t *cap,
+                                   int64_t *rc, int device) {
+    if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
+    if (njobs == 0) return HB_OK;
+    if (!frame || !n || !jobs || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
+    for (int j = 0; j < njobs; j++)
+        if (jobs[j].frame >= (uint32_t)nframes || jobs[j].reserved != 0u) return HB_ERR_BAD_ARG;
+    auto single = [&](int j) {
+        const hb_getitem_job &q = jobs[j];
+        rc[j] = hb_cblosc_getitem(frame[q.frame], n[q.frame], q.start, q.nitems, dst[j], cap[j], device);
+    };
+    auto all_single = [&]() { for (int j = 0; j < njobs; j++) single(j); return HB_OK; };
+    CbgHostPlan P;
+    cbg_host_plan(nframes, frame, n, njobs, jobs, dst, cap, P);
+    if (!P.any || hb_select_device(device) != HB_OK) return all_single();
+    const size_t wb = hb_cblosc_getitem_frames_batch_workspace(nframes, P.hd.data(), n, njobs, jobs);
+    if (!wb) return all_single();                                       // (a batch beyond the 32-bit limits: one call per job is still right)
+    Scratch sc(device);
+    uint8_t *d_in = sc.get(P.in_bytes + 256), *d_out = sc.get(P.out_bytes + 256), *d_work = sc.get(wb), *d_res = sc.get((size_t)njobs * sizeof(hb_result));
+    auto fail_all = [&]() { for (int j = 0; j < njobs; j++) rc[j] = HB_ERR_HIP; return HB_OK; };
+    if (!d_in || !d_out || !d_work || !d_res) return fail_all();
+    if (P.span_in && hipMemcpyAsync(d_in, frame[P.idx[0]], P.in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
+    // (a frame that is not uploaded keeps a NULL pointer: its jobs end with a status on the device and are answered one by one)
+    std::vector<const void *> pf((size_t)nframes, nullptr);
+    for (int k : P.idx) {
+        pf[(size_t)k] = d_in + P.ioff[(size_t)k];
+        if (!P.span_in && hipMemcpyAsync(d_in + P.ioff[(size_t)k], frame[k], n[k], hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
+    }
+    std::vector<void *> pd((size_t)njobs, nullptr);
+    for (int j = 0; j < njobs; j++) if (P.carried[(size_t)j]) pd[(size_t)j] = d_out + P.ooff[(size_t)j];
+    const int st = hb_cblosc_getitem_frames_batch_device(nframes, P.hd.data(), pf.data(), n, njobs, jobs, pd.data(), cap, d_work, wb, (hb_result *)d_res, nullptr);
+    if (st) { for (int j = 0; j < njobs; j++) rc[j] = st; return HB_OK; }
+    std::vector<hb_result> res((size_t)njobs);
+    if (hipMemcpy(res.data(), d_res, (size_t)njobs * sizeof(hb_result), hipMemcpyDeviceToHost) != hipSuccess) return fail_all();
+    std::vector<uint8_t> host(P.out_bytes);
+    if (P.out_bytes && hipMemcpy(host.data(), d_out, P.out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail_all();
+    for (int j = 0; j < njobs; j++) {
+        const hb_result &r = res[(size_t)j];
+        if (r.status != HB_OK) { single(j); continue; }
+        if (r.bytes) memcpy(dst[j], host.data() + P.ooff[(size_t)j], (size_t)r.bytes);
+        rc[j] = (int64_t)r.bytes;
+    }
     return HB_OK;
 }
 

@@ -22,11 +22,12 @@
 #include <cstring>
 #include "hb_cblosc_batch.h"       // the flags, cb_nsplit, CbStream / CbPlan, and the host side of the batch
 #include "hb_cblosc_enc_batch.h"   // the geometry of a written frame, and the host side of the batched encode
+#include "hb_cblosc_getitem_batch.h"   // the geometry of an item range, and the host side of the batched getitem
 
 // ---- the streams of blocks [b0, b0 + nb) (hb_cblosc_getitem_device: the blocks that cover a range; the others' bstarts entries and streams
 // are never read); stream offsets count from the first of these blocks ----
 __device__ __forceinline__ void cb_plan_block(const uint8_t *__restrict__ frame, uint32_t nbytes, uint32_t blocksize, uint32_t cbytes, uint32_t typesize, uint32_t flags,
-                                              CbPlan *plan, CbStream *streams, uint32_t b0, uint32_t idx) {
+                                              CbPlan *plan, CbStream *streams, uint32_t b0, uint32_t idx, bool own_records = false) {
     const uint32_t nblocks = (nbytes + blocksize - 1) / blocksize;
     const uint32_t b = b0 + idx;
     const uint32_t leftover = nbytes % blocksize;
@@ -36,7 +37,9 @@ __device__ __forceinline__ void cb_plan_block(const uint8_t *__restrict__ frame,
     const uint32_t nsplit = lastshort ? 1u : nsplit_frame;
     const uint32_t neblock = bsize / nsplit;
     CbStream *out = streams + (size_t)idx * nsplit_frame;
-    for (uint32_t s = 0; s < nsplit_frame; s++) { CbStream z; z.src = 0; z.csize = 0; z.dst = 0; z.usize = 0; out[s] = z; }
+    // (own_records: idx == 0 and the records are this block's alone -- k_cbg_plan: the last, shorter block has ONE record, not nsplit_frame)
+    const uint32_t nrec = own_records ? nsplit : nsplit_frame;
+    for (uint32_t s = 0; s < nrec; s++) { CbStream z; z.src = 0; z.csize = 0; z.dst = 0; z.usize = 0; out[s] = z; }
     uint32_t p = (uint32_t)frame[16 + 4 * b] | ((uint32_t)frame[17 + 4 * b] << 8) | ((uint32_t)frame[18 + 4 * b] << 16) | ((uint32_t)frame[19 + 4 * b] << 24);
     bool bad = neblock == 0u || (uint64_t)neblock * nsplit != bsize;                  // (blosc_c only splits what divides)
     for (uint32_t s = 0; s < nsplit && !bad; s++) {
@@ -429,6 +432,168 @@ __global__ __launch_bounds__(64) void k_cbb_finish(const CbbFrame *__restrict__ 
     hb_result *r = results + k;
     if (F.mode == CBB_REFUSED) { r->status = F.status; r->flags = 0; r->bytes = 0; r->total_bytes = 0; r->reserved = 0; return; }
     cb_result(plans + k, r, (uint64_t)F.nbytes);
+}
+
+// ---- batched getitem (hb_cblosc_getitem_frames_batch_device): many item ranges of many frames through ONE set of launches.  What is planned and
+// decoded is the DISTINCT (frame, block) pairs the jobs cover (hb_cblosc_getitem_batch.h: one CbgBlock each, with a CbPlan and a staged copy of
+// its own), whole and once; a gather per job then un-filters exactly the job's bytes out of the staged, still filtered blocks. ----
+// one thread per block record
+__global__ __launch_bounds__(64) void k_cbg_plan(const CbgFrame *__restrict__ frames, const CbgBlock *__restrict__ blocks, CbPlan *plans, uint32_t nblk, CbStream *streams) {
+    const uint32_t x = blockIdx.x * 64u + threadIdx.x;
+    if (x >= nblk) return;
+    const CbgBlock &K = blocks[x];
+    const CbgFrame &F = frames[K.frame];
+    cb_plan_block(F.frame, F.nbytes, F.blocksize, F.cbytes, F.typesize, F.flags, plans + x, streams + K.stream0, K.b, 0u, true);
+}
+// one wavefront per stream of the flat stream space, in the permuted order over all of it: as k_cbb_decode / k_cbb_decode_small, with the block
+// record as the owner -- its plan to read and to fail, its staged copy as the target (also without a filter: an LZ4 stream cannot be decoded
+// in part).  A stream goes to the small decoder exactly when hb_cblosc_getitem_device would send it there.
+__global__ __launch_bounds__(64) void k_cbg_decode(const CbgFrame *__restrict__ frames, const CbgBlock *__restrict__ blocks, CbPlan *plans, const uint32_t *__restrict__ str0,
+                                                    uint32_t nblk, const CbStream *__restrict__ streams, uint32_t nstreams, uint8_t *work, int small_launched, uint32_t P) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[RG_PWIN + 128];
+    __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
+    __shared__ __attribute__((aligned(16))) uint8_t s_d[SY_IMG + 64];
+    const int lane = threadIdx.x;
+    const uint32_t mgrp = (nstreams + 7u) / 8u;
+    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
+        const uint32_t i = cb_stream_of(it, mgrp, P);
+        if (i >= nstreams) continue;
+        const uint32_t x = RFL(hb_owner(str0, nblk, i));
+        CbPlan *plan = plans + x;
+        if (RFL(plan->fail)) continue;                                         // (one value for the whole wave: nobody is left behind at a wave_sync)
+        const CbgBlock &K = blocks[x];
+        const CbgFrame &F = frames[K.frame];
+        cb_decode_stream(F.frame, plan, cb_load_stream(streams, i), work + K.stage_off, small_launched && F.small, s_win, s_tq, s_d, lane);
+    }
+}
+__global__ __launch_bounds__(64) void k_cbg_decode_small(const CbgFrame *__restrict__ frames, const CbgBlock *__restrict__ blocks, CbPlan *plans, const uint32_t *__restrict__ str0,
+                                                          uint32_t nblk, const CbStream *__restrict__ streams, uint32_t nstreams, uint8_t *work, uint32_t P) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_in[CB_SMALL_IN + 64 + 128];
+    __shared__ __attribute__((aligned(16))) uint8_t s_out[CB_SMALL + 64];
+    __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
+    const int lane = threadIdx.x;
+    const uint32_t mgrp = (nstreams + 7u) / 8u;
+    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
+        const uint32_t i = cb_stream_of(it, mgrp, P);
+        if (i >= nstreams) continue;
+        const uint32_t x = RFL(hb_owner(str0, nblk, i));
+        const CbgBlock &K = blocks[x];
+        const CbgFrame &F = frames[K.frame];
+        if (!F.small) continue;
+        CbPlan *plan = plans + x;
+        if (RFL(plan->fail)) continue;
+        cb_decode_small_stream(F.frame, plan, cb_load_stream(streams, i), work + K.stage_off, s_in, s_out, s_tq, lane);
+    }
+}
+
+// ---- the clipped un-filter: byte p of the frame's decoded bytes out of the staged blocks of job J (block `b_lo` is its first record).  The
+// plain body: the edges of every range, and every shape the wide bodies below leave alone. ----
+template <int KIND>
+__device__ __forceinline__ uint8_t cbg_byte(const CbgFrame &F, const CbgJob &J, const CbgBlock *__restrict__ blocks, const uint8_t *__restrict__ work, uint32_t b_lo, uint32_t p) {
+    if (KIND == CBG_COPY && F.memcpyed) return F.frame[16u + (size_t)p];
+    const uint32_t b = p / F.blocksize, q = p - b * F.blocksize;
+    const CbgBlock &K = blocks[J.blk0 + (b - b_lo)];
+    const uint8_t *s = work + K.stage_off;
+    if (KIND == CBG_COPY) return s[q];
+    const uint32_t ts = F.typesize, nel = K.bsize / ts;
+    if (q >= nel * ts) return s[q];                                            // the bytes behind the last whole element
+    const uint32_t e = q / ts, j = q - e * ts;
+    if (KIND == CBG_UNSHUFFLE) return s[j * nel + e];
+    if (nel & 7u) return s[q];                                                 // not a multiple of 8 elements: the block was not filtered
+    const uint32_t ng = nel >> 3, g = e >> 3;
+    uint64_t x = 0;                                                            // byte k = row 8 j + k, elements 8 g .. 8 g + 7
+    for (uint32_t k = 0; k < 8u; k++) x |= (uint64_t)s[(size_t)(8u * j + k) * ng + g] << (8u * k);
+    return (uint8_t)(cb_transpose8(x) >> (8u * (e & 7u)));
+}
+// 16 bytes = 16 / TS whole elements starting with element e of a byte-shuffled block of nel elements
+template <uint32_t TS>
+__device__ __forceinline__ u32x4 cbg_unshuffle16(const uint8_t *__restrict__ s, uint32_t nel, uint32_t e) {
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+    for (uint32_t j = 0; j < TS; j++)
+#pragma unroll
+        for (uint32_t c = 0; c < 16u / TS; c++) {
+            const uint32_t i = c * TS + j;
+            w[i >> 2] |= (uint32_t)s[(size_t)j * nel + e + c] << (8u * (i & 3u));
+        }
+    u32x4 v; v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+    return v;
+}
+// the 8 * ts bytes of a whole group of 8 elements at byte q of a bit-shuffled block (false: not such a group -- the plain body has it)
+__device__ __forceinline__ bool cbg_bitun_group(uint8_t *__restrict__ d, const uint8_t *__restrict__ s, uint32_t bsize, uint32_t ts, uint32_t q) {
+    const uint32_t nel = bsize / ts, e = q / ts;
+    if ((nel & 7u) || e * ts != q || (e & 7u) || e + 8u > nel) return false;
+    const uint32_t ng = nel >> 3, g = e >> 3;
+    for (uint32_t j = 0; j < ts; j++) {
+        uint64_t x = 0;
+        for (uint32_t k = 0; k < 8u; k++) x |= (uint64_t)s[(size_t)(8u * j + k) * ng + g] << (8u * k);
+        x = cb_transpose8(x);
+        for (uint32_t k = 0; k < 8u; k++) d[k * ts + j] = (uint8_t)(x >> (8u * k));
+    }
+    return true;
+}
+// One launch per kind that occurs: gjob / gblk = the jobs of this kind and the prefix of their workgroup counts.  A thread has one unit of
+// cbg_unit_bytes() bytes, counted from the start of the FRAME (so that a unit does not straddle a block, a group or an item where the block
+// size allows it), clipped to the job's range: a whole unit of a fitting shape takes the wide body, everything else the plain one.  Nothing is
+// written outside [0, nitems * typesize) of the job's destination, and nothing at all when one of the job's blocks failed.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_cbg_gather(const CbgFrame *__restrict__ frames, const CbgJob *__restrict__ jobs, const CbgBlock *__restrict__ blocks,
+                                                     const CbPlan *__restrict__ plans, const uint32_t *__restrict__ gjob, const uint32_t *__restrict__ gblk, uint32_t nkind,
+                                                     const uint8_t *__restrict__ work) {
+    const uint32_t i = hb_owner(gblk, nkind, blockIdx.x);
+    const CbgJob &J = jobs[gjob[i]];
+    const CbgFrame &F = frames[J.frame];
+    int bad = 0;
+    for (uint32_t k = threadIdx.x; k < J.nb; k += 256u) bad |= plans[J.blk0 + k].fail != 0u;
+    if (__syncthreads_or(bad)) return;
+    const uint32_t ts = F.typesize, bs = F.blocksize, U = cbg_unit_bytes(KIND, ts);
+    const uint64_t at = ((uint64_t)J.unit0 + (uint64_t)(blockIdx.x - gblk[i]) * 256u + threadIdx.x) * U, end = J.off + J.bytes;
+    if (at >= end) return;
+    const uint32_t lo = (uint32_t)(at > J.off ? at : J.off), hi = (uint32_t)(at + U < end ? at + U : end);      // (end <= nbytes < 2^32)
+    uint8_t *d = J.dst + (lo - J.off);
+    const uint32_t b_lo = (KIND == CBG_COPY && F.memcpyed) ? 0u : (uint32_t)(J.off / bs);
+    if (hi - lo == U) {                                                        // a whole unit
+        if (KIND == CBG_COPY && F.memcpyed) { st16u(d, ld16u(F.frame + 16u + (size_t)lo)); return; }
+        const uint32_t b = lo / bs, q = lo - b * bs;
+        const CbgBlock &K = blocks[J.blk0 + (b - b_lo)];
+        const uint8_t *s = work + K.stage_off;
+        if (KIND == CBG_COPY) {
+            if (q + 16u <= K.bsize) { st16u(d, ld16u(s + q)); return; }
+        } else if (KIND == CBG_UNSHUFFLE) {
+            const uint32_t nel = K.bsize / ts, e = q / ts;
+            if (e * ts == q && q + 16u <= nel * ts) {
+                if (ts == 2u) { st16u(d, cbg_unshuffle16<2>(s, nel, e)); return; }
+                if (ts == 4u) { st16u(d, cbg_unshuffle16<4>(s, nel, e)); return; }
+                if (ts == 8u) { st16u(d, cbg_unshuffle16<8>(s, nel, e)); return; }
+                if (ts == 16u) { st16u(d, cbg_unshuffle16<16>(s, nel, e)); return; }
+            }
+        } else if (KIND == CBG_BITUN) {
+            if (q + U <= K.bsize && cbg_bitun_group(d, s, K.bsize, ts, q)) return;
+        } else {
+            // typesize 4, block size a multiple of 512: q is a multiple of 128.  A whole block takes cb_bitunshuffle4_item's arithmetic for item
+            // q / 128 (32 elements: 32 dword loads, 8 x 16-byte stores); the last, shorter block goes group by group
+            if (K.bsize == bs) { cb_bitunshuffle4_item(d, s + (q >> 5), 0, bs >> 5, 0u); return; }
+            if (q + 128u <= K.bsize) {
+                for (uint32_t g = 0; g < 4u; g++)
+                    if (!cbg_bitun_group(d + 32u * g, s, K.bsize, 4u, q + 32u * g))
+                        for (uint32_t k = 0; k < 32u; k++) d[32u * g + k] = cbg_byte<KIND>(F, J, blocks, work, b_lo, lo + 32u * g + k);
+                return;
+            }
+        }
+    }
+    for (uint32_t p = lo; p < hi; p++) d[p - lo] = cbg_byte<KIND>(F, J, blocks, work, b_lo, p);
+}
+
+// one thread per job: what the host decided, or k_cb_result's record from the OR of the fail words of the job's blocks
+__global__ __launch_bounds__(64) void k_cbg_finish(const CbgJob *__restrict__ jobs, const CbPlan *__restrict__ plans, hb_result *results, uint32_t njobs) {
+    const uint32_t j = blockIdx.x * 64u + threadIdx.x;
+    if (j >= njobs) return;
+    const CbgJob &J = jobs[j];
+    hb_result *r = results + j;
+    if (J.status) { r->status = J.status; r->flags = 0; r->bytes = 0; r->total_bytes = 0; r->reserved = 0; return; }
+    CbPlan p; p.fail = 0u;
+    for (uint32_t k = 0; k < J.nb; k++) p.fail |= plans[J.blk0 + k].fail;
+    cb_result(&p, r, J.bytes);
 }
 
 // =====================================================================================================================
@@ -889,43 +1054,7 @@ int hb_cblosc_decompress_frames_batch_device(int nframes, const hb_cblosc_header
 // Only blocks b_lo .. b_hi are planned, decoded and un-filtered -- whole blocks into a second staging area, then a copy of the range: the
 // per-block un-filter kernels (the tile kernels of hb_filters.hip among them) work on whole blocks, and a clipped variant of each would be
 // a second set of filters to keep right for at most two partly needed blocks per call.
-namespace {
-struct CbRange { uint32_t b_lo, nb, vbytes; uint64_t off, bytes; size_t streams, stage, total; };
-// the header refusals of hb_cblosc_decompress / hb_cblosc_decompress_dev, then the range; what is sized comes after the geometry checks
-int cb_getitem_prepare(const hb_cblosc_header *hdr, size_t n, int64_t start, int64_t nitems, CbRange &r) {
-    const uint32_t nbytes = hdr->nbytes, blocksize = hdr->blocksize, ts = hdr->typesize, flags = hdr->flags;
-    if (n < 16) return HB_ERR_INVALID_HEADER;
-    if (hdr->version != 2) return HB_ERR_INVALID_VERSION;
-    if (ts == 0u || (nbytes && blocksize == 0u)) return HB_ERR_INVALID_HEADER;
-    if (hdr->cbytes > n || hdr->cbytes < 16) return HB_ERR_INVALID_DATA;
-    uint64_t nblocks = 0;
-    if (flags & CB_FLAG_MEMCPY) {
-        if ((uint64_t)hdr->cbytes < 16ull + nbytes) return HB_ERR_INVALID_DATA;
-    } else {
-        if (hdr->codec_format != 1) return HB_ERR_INVALID_CODEC;
-        if (nbytes) {
-            nblocks = ((uint64_t)nbytes + blocksize - 1) / blocksize;
-            if (16ull + 4ull * nblocks > hdr->cbytes || blocksize < ts) return HB_ERR_INVALID_DATA;
-        }
-    }
-    const int64_t ne = (int64_t)(nbytes / ts);
-    if (start < 0 || nitems < 0 || start > ne || nitems > ne - start) return HB_ERR_BAD_ARG;
-    r.off = (uint64_t)start * ts; r.bytes = (uint64_t)nitems * ts;
-    r.b_lo = 0; r.nb = 0; r.vbytes = 0; r.streams = 0; r.stage = 0;
-    if (r.bytes && !(flags & CB_FLAG_MEMCPY)) {
-        r.b_lo = (uint32_t)(r.off / blocksize);
-        const uint32_t b_hi = (uint32_t)((r.off + r.bytes - 1) / blocksize);
-        r.nb = b_hi - r.b_lo + 1u;
-        const uint64_t end = (uint64_t)(b_hi + 1u) * blocksize;
-        r.vbytes = (uint32_t)((end < nbytes ? end : nbytes) - (uint64_t)r.b_lo * blocksize);
-        const size_t nsplit = (ts <= 16u && blocksize / ts >= 128u) ? ts : 1u;         // cb_nsplit() without the flag: the upper bound
-        r.streams = cb_align((size_t)r.nb * nsplit * sizeof(CbStream));
-        r.stage = cb_align((size_t)r.vbytes + 64);
-    }
-    r.total = 256 + r.streams + 2 * r.stage;
-    return HB_OK;
-}
-}  // namespace
+// (the geometry of a range -- CbRange, cb_getitem_prepare -- is hb_cblosc_getitem_batch.h's, shared with the batch below)
 
 size_t hb_cblosc_getitem_workspace(const hb_cblosc_header *hdr, int64_t start, int64_t nitems) {
     CbRange r;
@@ -963,6 +1092,93 @@ int hb_cblosc_getitem_device(const hb_cblosc_header *hdr, const void *d_frame, s
         }
     }
     hipLaunchKernelGGL(k_cb_result, dim3(1), dim3(1), 0, s, plan, d_result, r.bytes);
+    HB_HIP_TRY(hipGetLastError());
+    return HB_OK;
+}
+
+// ---- many ranges of many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_getitem_batch.h) ----
+size_t hb_cblosc_getitem_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n, int njobs, const hb_getitem_job *jobs) {
+    return cbg_workspace(nframes, hdrs, n, njobs, jobs);
+}
+
+int hb_cblosc_getitem_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_getitem_job *jobs,
+                                          void *const *d_dst, const size_t *cap, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
+    if (njobs == 0) return HB_OK;
+    if (!hdrs || !d_frame || !n || !jobs || !d_dst || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
+    CbgBatch B;
+    const int rc = cbg_prepare(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, true, B);
+    if (rc) return rc;
+    const CbgLayout &L = B.L;
+    // (the query knows no capacities and no pointers: where a job was refused for one of them it has counted blocks that this batch leaves out)
+    if (work_bytes < (B.ptr_refusals ? cbg_workspace(nframes, hdrs, n, njobs, jobs) : L.total)) return HB_ERR_SHORT_BUFFER;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t *w = (uint8_t *)d_work;
+    const size_t nf = (size_t)nframes, nj = (size_t)njobs, nb = (size_t)B.nblk;
+    // the records, the prefixes and the cleared plans go up in one copy (the buffer is read before the call returns, as with hb_batch.hip's)
+    std::vector<uint8_t> up(L.upload, 0);
+    memcpy(up.data() + L.frames, B.frames.data(), nf * sizeof(CbgFrame));
+    memcpy(up.data() + L.jobs, B.jobs.data(), nj * sizeof(CbgJob));
+    if (nb) {
+        memcpy(up.data() + L.blocks, B.blocks.data(), nb * sizeof(CbgBlock));
+        memcpy(up.data() + L.str0, B.str0.data(), nb * 4);
+    }
+    memcpy(up.data() + L.gjob, B.gjob.data(), nj * 4);
+    memcpy(up.data() + L.gblk, B.gblk.data(), nj * 4);
+    hb_prof_begin("cbg_upload", s);
+    HB_HIP_TRY(hipMemcpyAsync(w, up.data(), L.upload, hipMemcpyHostToDevice, s));
+    hb_prof_end(s);
+    const CbgFrame *d_frames = (const CbgFrame *)(w + L.frames);
+    const CbgJob *d_jobs = (const CbgJob *)(w + L.jobs);
+    const CbgBlock *d_blocks = (const CbgBlock *)(w + L.blocks);
+    CbPlan *d_plans = (CbPlan *)(w + L.plans);
+    const uint32_t *d_str0 = (const uint32_t *)(w + L.str0), *d_gjob = (const uint32_t *)(w + L.gjob), *d_gblk = (const uint32_t *)(w + L.gblk);
+    CbStream *d_streams = (CbStream *)(w + L.streams);
+    if (B.nstreams) {
+        const uint32_t nblk = (uint32_t)B.nblk, nstreams = (uint32_t)B.nstreams;
+        hb_prof_begin("k_cbg_plan", s);
+        hipLaunchKernelGGL(k_cbg_plan, dim3((nblk + 63u) / 64u), dim3(64), 0, s, d_frames, d_blocks, d_plans, nblk, d_streams);
+        hb_prof_end(s);
+        const uint32_t mgrp = (nstreams + 7u) / 8u;
+        uint32_t P = mgrp / 4u + 1u;                                    // coprime to the groups of 8 streams, about a quarter turn (cb_launch_blocks)
+        for (;; P++) { uint32_t x = P, y = mgrp; while (y) { const uint32_t t = x % y; x = y; y = t; } if (x == 1u) break; }
+        const unsigned grid = mgrp * 8u < 65536u ? mgrp * 8u : 65536u;
+        if (B.any_small) {
+            hb_prof_begin("k_cbg_decode_small", s);
+            hipLaunchKernelGGL(k_cbg_decode_small, dim3(grid), dim3(64), 0, s, d_frames, d_blocks, d_plans, d_str0, nblk, (const CbStream *)d_streams, nstreams, w, P);
+            hb_prof_end(s);
+        }
+        // (any block can have stored streams: the general decoder always runs; its passes per workgroup as in the batched decode)
+        unsigned gbig = grid;
+        if (!B.any_small && B.nsplit_all > 1u) {
+            unsigned p = B.nsplit_all;
+            while (p > 1u && mgrp * 8u / p < 2048u) p >>= 1;
+            gbig = (mgrp * 8u / p + 7u) / 8u * 8u;
+            if (gbig > 65536u) gbig = 65536u;
+        }
+        hb_prof_begin("k_cbg_decode", s);
+        hipLaunchKernelGGL(k_cbg_decode, dim3(gbig), dim3(64), 0, s, d_frames, d_blocks, d_plans, d_str0, nblk, (const CbStream *)d_streams, nstreams, w, (int)B.any_small, P);
+        hb_prof_end(s);
+    }
+    static const char *const gname[CBG_COUNT] = {"k_cbg_gather_copy", "k_cbg_gather_unshuffle", "k_cbg_gather_bitun", "k_cbg_gather_bitun4"};
+    for (int k = 0; k < CBG_COUNT; k++) {
+        const uint32_t k0 = B.kind0[k], nk = B.kind0[k + 1] - k0, blocks = B.kblocks[k];
+        if (!nk) continue;
+        hb_prof_begin(gname[k], s);
+#define CBG_LAUNCH(K) hipLaunchKernelGGL(k_cbg_gather<K>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_blocks, (const CbPlan *)d_plans, d_gjob + k0, d_gblk + k0, nk, (const uint8_t *)w)
+        switch (k) {
+        case CBG_COPY: CBG_LAUNCH(CBG_COPY); break;
+        case CBG_UNSHUFFLE: CBG_LAUNCH(CBG_UNSHUFFLE); break;
+        case CBG_BITUN: CBG_LAUNCH(CBG_BITUN); break;
+        default: CBG_LAUNCH(CBG_BITUN4); break;
+        }
+#undef CBG_LAUNCH
+        hb_prof_end(s);
+    }
+    hb_prof_begin("k_cbg_finish", s);
+    hipLaunchKernelGGL(k_cbg_finish, dim3((unsigned)((nj + 63) / 64)), dim3(64), 0, s, d_jobs, (const CbPlan *)d_plans, d_results, (uint32_t)njobs);
+    hb_prof_end(s);
     HB_HIP_TRY(hipGetLastError());
     return HB_OK;
 }

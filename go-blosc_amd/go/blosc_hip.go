@@ -861,3 +861,88 @@ func CBloscCompressBatchHIP(datas [][]byte, shuffle Shuffle, typeSize int) ([][]
 	}
 	return out, errs
 }
+
+// CBloscGetItemBatchHIP answers many blosc_getitem calls on C-Blosc-1 frames through ONE set of kernel launches
+// (hb_cblosc_getitem_frames_batch): a slice of a chunked array store takes one range out of each of hundreds of chunk frames, a fancy index
+// hundreds of small ranges out of the same few.  Every frame goes up once and every distinct block the jobs cover is decoded once, however
+// many jobs read it; out[j] / errs[j] are what hb_cblosc_getitem gives for items [Start, Start+NItems) of frames[Frame].  Without a device
+// every job gets the no-device error: there is no CPU path.  Go memory is borrowed for the call only (pinned slabs and C arrays, never Go
+// pointers in C memory).  Like the rest of this file: written against the C ABI, it has never met a compiler.
+func CBloscGetItemBatchHIP(frames [][]byte, jobs []GetItemJob) ([][]byte, []error) {
+	nj, nf := len(jobs), len(frames)
+	out := make([][]byte, nj)
+	errs := make([]error, nj)
+	if nj == 0 {
+		return out, errs
+	}
+	failAll := func(code C.int64_t) ([][]byte, []error) {
+		for j := range jobs {
+			errs[j] = hbError(code)
+		}
+		return out, errs
+	}
+	if !useHIP {
+		return failAll(C.int64_t(C.HB_ERR_NO_DEVICE))
+	}
+	for _, q := range jobs {
+		if q.Frame < 0 || q.Frame >= nf {
+			return failAll(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+	}
+	ptrBytes := C.size_t(unsafe.Sizeof(uintptr(0)))
+	srcs := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(nf) * ptrBytes))[:nf:nf]
+	dsts := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(nj) * ptrBytes))[:nj:nj]
+	defer C.free(unsafe.Pointer(&srcs[0]))
+	defer C.free(unsafe.Pointer(&dsts[0]))
+	lens := make([]C.size_t, nf)
+	caps := make([]C.size_t, nj)
+	rcs := make([]C.int64_t, nj)
+	jt := make([]C.hb_getitem_job, nj)
+	var inBytes, outBytes C.size_t
+	for k, f := range frames {
+		lens[k] = C.size_t(len(f))
+		inBytes += lens[k] // tightly packed: frames that follow each other exactly go up in ONE copy
+	}
+	for j, q := range jobs {
+		ts := int64(1)
+		if len(frames[q.Frame]) >= 16 && frames[q.Frame][3] != 0 {
+			ts = int64(frames[q.Frame][3])
+		}
+		if q.NItems > 0 && q.NItems <= (1<<32)/ts { // (a range no frame can hold is refused by the library: no room is needed for it)
+			caps[j] = C.size_t(q.NItems * ts)
+		}
+		outBytes += caps[j] + 1
+		jt[j].frame = C.uint32_t(q.Frame)
+		jt[j].start = C.int64_t(q.Start)
+		jt[j].nitems = C.int64_t(q.NItems)
+	}
+	slabIn, slabOut := C.hb_host_alloc(inBytes+64), C.hb_host_alloc(outBytes+64)
+	if slabIn == nil || slabOut == nil {
+		C.hb_host_free(slabIn)
+		C.hb_host_free(slabOut)
+		return failAll(C.int64_t(C.HB_ERR_HIP))
+	}
+	defer C.hb_host_free(slabIn)
+	defer C.hb_host_free(slabOut)
+	var io, oo C.size_t
+	for k, f := range frames {
+		srcs[k] = unsafe.Add(slabIn, uintptr(io))
+		copy(unsafe.Slice((*byte)(srcs[k]), len(f)), f)
+		io += lens[k]
+	}
+	for j := range jobs {
+		dsts[j] = unsafe.Add(slabOut, uintptr(oo))
+		oo += caps[j] + 1
+	}
+	if rc := C.hb_cblosc_getitem_frames_batch(C.int(nf), &srcs[0], &lens[0], C.int(nj), &jt[0], &dsts[0], &caps[0], &rcs[0], C.int(Device)); rc != C.HB_OK {
+		return failAll(C.int64_t(rc))
+	}
+	for j := range jobs {
+		if rcs[j] < 0 {
+			errs[j] = hbError(rcs[j])
+		} else {
+			out[j] = append([]byte(nil), unsafe.Slice((*byte)(dsts[j]), int(rcs[j]))...)
+		}
+	}
+	return out, errs
+}

@@ -103,6 +103,7 @@ EXPORTS = [
     "hb_getitem_frames_batch_workspace", "hb_getitem_frames_batch_device", "hb_getitem_frames_batch",
     "hb_cblosc_decompress_frames_batch_workspace", "hb_cblosc_decompress_frames_batch_device", "hb_cblosc_decompress_frames_batch",
     "hb_cblosc_compress_frames_batch_workspace", "hb_cblosc_compress_frames_batch_device", "hb_cblosc_compress_frames_batch",
+    "hb_cblosc_getitem_frames_batch_workspace", "hb_cblosc_getitem_frames_batch_device", "hb_cblosc_getitem_frames_batch",
     "hb_queue_create", "hb_queue_create_ex", "hb_queue_destroy", "hb_queue_compress", "hb_queue_decompress", "hb_queue_wait",
 ]
 
@@ -193,6 +194,9 @@ def lib():
             "hb_cblosc_compress_frames_batch_workspace": (sz, [i32, vp, i32, i32]),
             "hb_cblosc_compress_frames_batch_device": (i32, [i32, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
             "hb_cblosc_compress_frames_batch": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, i32]),
+            "hb_cblosc_getitem_frames_batch_workspace": (sz, [i32, vp, vp, i32, vp]),
+            "hb_cblosc_getitem_frames_batch_device": (i32, [i32, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp, vp]),
+            "hb_cblosc_getitem_frames_batch": (i32, [i32, vp, vp, i32, vp, vp, vp, vp, i32]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -576,6 +580,31 @@ def CBloscGetItem(frame, start, nitems):
     out = ctypes.create_string_buffer(max(cap, 1))
     rc = _check(lib().hb_cblosc_getitem(p, n, int(start), int(nitems), ctypes.cast(out, ctypes.c_void_p), cap, device))
     return out.raw[:rc]
+
+
+def CBloscGetItemBatch(frames, jobs, dev=None):
+    """Many CBloscGetItem calls through one set of launches (include/hipblosc.h hb_cblosc_getitem_frames_batch): `jobs` are (frame_index, start,
+    nitems) tuples over `frames`; every distinct block the jobs cover is decoded once.  The i-th result is what CBloscGetItem(frames[f], start,
+    nitems) would have returned for the i-th job -- the bytes, or the error it raises (returned, not raised, as GetItemBatch does)."""
+    jobs = list(jobs)
+    nj, nf = len(jobs), len(frames)
+    if nj == 0:
+        return []
+    keep = [_buf(f) for f in frames]
+    caps = []
+    for f, start, nitems in jobs:
+        ts = 1
+        if 0 <= f < nf and keep[f][1] >= 16:
+            ts = bytes(keep[f][2][3:4])[0] or 1
+        caps.append(max(int(nitems), 0) * ts)
+    outs = [(ctypes.c_char * max(c, 1))() for c in caps]
+    jt = (hb_getitem_job * nj)(*[hb_getitem_job(int(f), 0, int(s), int(k)) for f, s, k in jobs])
+    fr = (ctypes.c_void_p * max(nf, 1))(*[k[0].value for k in keep])
+    ns = (ctypes.c_size_t * max(nf, 1))(*[k[1] for k in keep])
+    dsts = (ctypes.c_void_p * nj)(*[ctypes.addressof(o) for o in outs])
+    rcs = (ctypes.c_int64 * nj)()
+    _check(lib().hb_cblosc_getitem_frames_batch(nf, fr, ns, nj, jt, dsts, (ctypes.c_size_t * nj)(*caps), rcs, device if dev is None else dev))
+    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(nj)]
 
 
 def CBloscCompress(data, shuffle=1, typesize=4):

@@ -170,6 +170,29 @@ inline std::vector<Bytes> CBloscDecompressBatch(const std::vector<Bytes> &frames
     for (size_t k = 0; k < nf; k++) out[k].resize(rc[k] > 0 ? (size_t)rc[k] : 0);
     return out;
 }
+// many blosc_getitem calls on C-Blosc-1 frames through one set of launches (hb_cblosc_getitem_frames_batch; every distinct block the jobs cover
+// is decoded once): out[j] is what hb_cblosc_getitem gives for items [start, start + nitems) of frames[frame], rc[j] the byte count or its
+// HB_ERR_* code (nothing is thrown per job)
+inline std::vector<Bytes> CBloscGetItemBatch(const std::vector<Bytes> &frames, const std::vector<GetItemJob> &jobs, std::vector<int64_t> &rc, int device = 0) {
+    const size_t nf = frames.size(), nj = jobs.size();
+    std::vector<Bytes> out(nj);
+    rc.assign(nj, 0);
+    if (!nj) return out;
+    std::vector<const void *> fr(nf); std::vector<size_t> ns(nf);
+    for (size_t k = 0; k < nf; k++) { fr[k] = frames[k].data(); ns[k] = frames[k].size(); }
+    std::vector<hb_getitem_job> jt(nj); std::vector<void *> dst(nj); std::vector<size_t> cap(nj);
+    for (size_t j = 0; j < nj; j++) {
+        jt[j] = hb_getitem_job{jobs[j].frame, 0u, jobs[j].start, jobs[j].nitems};
+        size_t ts = 1;
+        if (jobs[j].frame < nf && ns[jobs[j].frame] >= 16 && frames[jobs[j].frame][3]) ts = frames[jobs[j].frame][3];
+        cap[j] = jobs[j].nitems > 0 ? (size_t)jobs[j].nitems * ts : 0;
+        out[j].resize(cap[j] ? cap[j] : 1);
+        dst[j] = out[j].data();
+    }
+    check(hb_cblosc_getitem_frames_batch((int)nf, fr.data(), ns.data(), (int)nj, jt.data(), dst.data(), cap.data(), rc.data(), device));
+    for (size_t j = 0; j < nj; j++) out[j].resize(rc[j] > 0 ? (size_t)rc[j] : 0);
+    return out;
+}
 // many inputs to C-Blosc-1 frames through one set of launches (hb_cblosc_compress_frames_batch; shuffle 0 / 1 / 2 = none / byte / bit, one shuffle
 // and typesize for the whole batch): out[k] is the frame hb_cblosc_compress writes for datas[k], rc[k] its byte count or its HB_ERR_* code
 // (nothing is thrown per input)

@@ -395,6 +395,44 @@ int64_t hb_cblosc_getitem(const void *frame, size_t n, int64_t start, int64_t ni
 size_t  hb_cblosc_getitem_workspace(const hb_cblosc_header *hdr, int64_t start, int64_t nitems);
 int     hb_cblosc_getitem_device(const hb_cblosc_header *hdr, const void *d_frame, size_t n, int64_t start, int64_t nitems,
                                  void *d_dst, size_t cap, void *d_work, size_t work_bytes, hb_result *d_result, void *stream);
+/* ---- many ranges of many C-Blosc-1 frames through ONE set of launches: a slice or a fancy index of a chunked array store (one range out of
+ *      each of hundreds of chunk frames, or hundreds of small ranges out of a few).  Jobs are hb_getitem_job (`frame` indexes the frame arrays,
+ *      `reserved` is 0).  Every DISTINCT (frame, block) pair that the accepted jobs cover is planned and decoded once, however many jobs read
+ *      it; a gather per job then un-filters exactly its nitems * typesize bytes out of the decoded blocks.
+ *      Device form (rules of hb_getitem_frames_batch_device / hb_cblosc_decompress_frames_batch_device: d_frame / d_dst are HOST arrays of device
+ *      pointers, asynchronous on `stream`, does not synchronise, keeps no caller pointer, sources may be read up to 15 bytes past their end,
+ *      d_work 256-byte aligned, d_results njobs records in device or pinned memory; the suffix is _device for the reason given above
+ *      hb_getitem_frame_device).  The outcome of job j is defined against
+ *      hb_cblosc_getitem_device(&hdrs[f], d_frame[f], n[f], start, nitems, d_dst[j], cap[j], ...):
+ *        - what that call refuses as its return value is d_results[j].status with bytes, total_bytes and flags 0 -- its header, geometry and
+ *          range refusals in its order, then HB_ERR_SHORT_BUFFER for cap[j] < nitems * typesize, then HB_ERR_BAD_ARG for a NULL d_frame[f] or a
+ *          NULL d_dst[j] with bytes to write.  All decided on the host before hb_init(); a refused job touches nothing on the device;
+ *        - every other job gives the bytes and the record of that call: status 0, flags 1, bytes = total_bytes = nitems * typesize, or
+ *          HB_ERR_DECOMPRESSION_FAILED with bytes 0 when the plan or a stream of a block it covers fails.  The fail state is per BLOCK: a
+ *          damaged block spoils exactly the jobs whose range covers it.  Blocks that no job covers are never read;
+ *        - job j writes at most nitems * typesize bytes of d_dst[j] (unspecified inside them when it fails) and its part of the workspace.
+ *          Overlapping destinations are the caller's error.
+ *      The call as a whole: HB_ERR_BAD_ARG for nframes < 0 / njobs < 0, HB_OK for njobs == 0 (nothing launched), HB_ERR_BAD_ARG for NULL
+ *      arrays, a job with frame >= nframes or reserved != 0, a NULL or misaligned d_work, a NULL d_results, or more than
+ *      HB_CBLOSC_BATCH_MAX_WORK distinct blocks, streams or workgroups of any one gather kind (split it); HB_ERR_SHORT_BUFFER for work_bytes
+ *      below the workspace query; then HB_ERR_NO_DEVICE.
+ *      Workspace: the records, one stream array, one staged copy (block bytes + 64, 256-aligned) per distinct covered block of a frame that
+ *      is not memcpyed: at most the sum over the distinct covered blocks of hb_cblosc_getitem_workspace() for a one-block range
+ *      + HB_CBLOSC_GETITEM_BATCH_JOB_BYTES * (njobs + nframes); more jobs on blocks already covered add the per-job constant only.  0 when
+ *      the call as a whole would be refused, 256 for njobs == 0.
+ *      Host form (as hb_getitem_frames_batch): every frame an accepted job reads goes up once (frames exactly adjacent in host memory in one
+ *      copy), the device form runs once, the records come down in one copy and all ranges in one copy from a packed device buffer.  Every
+ *      job the batch did not carry or that did not end with status 0 is answered by hb_cblosc_getitem, one call each: rc[j] is always
+ *      exactly what that call returns for the job.  Returns HB_OK unless the arguments as a whole are unusable. ---- */
+#define HB_CBLOSC_GETITEM_BATCH_JOB_BYTES 512    /* workspace per job and per frame beyond the blocks */
+size_t  hb_cblosc_getitem_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n,
+                                                 int njobs, const hb_getitem_job *jobs);
+int     hb_cblosc_getitem_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n,
+                                              int njobs, const hb_getitem_job *jobs, void *const *d_dst, const size_t *cap,
+                                              void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
+int     hb_cblosc_getitem_frames_batch(int nframes, const void *const *frame, const size_t *n,
+                                       int njobs, const hb_getitem_job *jobs, void *const *dst, const size_t *cap,
+                                       int64_t *rc, int device);
 /* writing the format: a frame that blosc_decompress() of c-blosc 1.x (python-blosc, numcodecs ...) reads.  shuffle: 0 none, 1 byte
  * shuffle, 2 bit shuffle (BLOSC_NOSHUFFLE / BLOSC_SHUFFLE / BLOSC_BITSHUFFLE); LZ4 streams; block size 4096 x typesize (split) or
  * 4096 (not split), so that every stream is one chunk of this library's encoder; n below 2 GiB (c-blosc's limit).  Returns the
