@@ -3,6 +3,7 @@
 // No CPU fallback anywhere: without a HIP device every compute entry point fails loudly.
 #include "hb_common.h"
 #include "hb_frame_plan.h"
+#include "hb_cblosc_batch.h"          // cb_codec_refused: the one codec check of the C-Blosc-1 entry points
 
 #include <atomic>
 #include <mutex>
@@ -595,7 +596,7 @@ int64_t hb_cblosc_decompress(const void *frame, size_t n, void *dst, size_t cap,
     if (rc) return rc;
     if ((size_t)h.nbytes > cap) return HB_ERR_SHORT_BUFFER;
     if ((!dst && h.nbytes)) return HB_ERR_BAD_ARG;
-    if (!(h.flags & 0x02u) && h.codec_format != 1) return HB_ERR_INVALID_CODEC;
+    if (!(h.flags & CB_FLAG_MEMCPY) && cb_codec_refused(h, hb_cblosc_accepted())) return HB_ERR_INVALID_CODEC;
     if (!(h.flags & 0x02u) && h.nbytes) {
         // validate the geometry BEFORE sizing anything from it (a 16-byte forged header with blocksize 1 asked for
         // thousands of bytes of scratch per declared byte): the bstarts table must fit into the frame, a block holds >= 1 element

@@ -612,7 +612,7 @@ int hb_cblosc_decompress_frames_batch(int nframes, const void *const *frame, con
     if (!frame || !n || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
     auto single = [&](int k) { rc[k] = hb_cblosc_decompress(frame[k], n[k], dst[k], cap[k], device); };
     CbbHostPlan P;
-    cbb_host_plan(nframes, frame, n, dst, cap, P);
+    cbb_host_plan(nframes, frame, n, dst, cap, P, hb_cblosc_accepted());
     const int m = (int)P.idx.size();
     std::vector<uint8_t> carried((size_t)nframes, 0);
     for (int k : P.idx) carried[(size_t)k] = 1;
@@ -672,7 +672,7 @@ int hb_cblosc_getitem_frames_batch(int nframes, const void *const *frame, const 
     };
     auto all_single = [&]() { for (int j = 0; j < njobs; j++) single(j); return HB_OK; };
     CbgHostPlan P;
-    cbg_host_plan(nframes, frame, n, njobs, jobs, dst, cap, P);
+    cbg_host_plan(nframes, frame, n, njobs, jobs, dst, cap, P, hb_cblosc_accepted());
     if (!P.any || hb_select_device(device) != HB_OK) return all_single();
     const size_t wb = hb_cblosc_getitem_frames_batch_workspace(nframes, P.hd.data(), n, njobs, jobs);
     if (!wb) return all_single();                                       // (a batch beyond the 32-bit limits: one call per job is still right)

@@ -15,10 +15,12 @@
 //
 // Blocks and streams are independent, so there is no discovery problem here: k_cb_plan lists the streams (one lane per block
 // walks its cbytes fields), k_cb_decode puts one wavefront on every stream (the serial block decoder of hb_dec_common.h: streams
-// are 8-256 KiB, hundreds to thousands per frame), k_cb_unfilter undoes the per-block filter.  LZ4 / LZ4HC and memcpyed frames
-// only: the other codec formats are entropy coders or blosclz.
+// are 8-256 KiB, hundreds to thousands per frame), k_cb_unfilter undoes the per-block filter.  LZ4 / LZ4HC and memcpyed frames, and
+// -- once hb_cblosc_accept_codecs(0x3) has said so -- BloscLZ (the *_blz kernels: the same decoder behind bz_walk, hb_lz4_region.h);
+// the other codec formats are entropy coders.
 #include "hb_sym_decode.h"
 
+#include <atomic>
 #include <cstring>
 #include "hb_cblosc_batch.h"       // the flags, cb_nsplit, CbStream / CbPlan, and the host side of the batch
 #include "hb_cblosc_enc_batch.h"   // the geometry of a written frame, and the host side of the batched encode
@@ -46,7 +48,9 @@ __device__ __forceinline__ void cb_plan_block(const uint8_t *__restrict__ frame,
         if ((uint64_t)p + 4u > cbytes) { bad = true; break; }
         const uint32_t cb = (uint32_t)frame[p] | ((uint32_t)frame[p + 1] << 8) | ((uint32_t)frame[p + 2] << 16) | ((uint32_t)frame[p + 3] << 24);
         p += 4u;
-        if (cb == 0u || cb > 0x7FFFFFFFu || (uint64_t)p + cb > cbytes || cb > neblock + neblock / 255u + 16u) { bad = true; break; }
+        // (longer than LZ4's worst case: no LZ4 stream of this output.  BloscLZ has no such bound -- literal runs may be as short as one byte, two
+        // stream bytes per output byte, and the library decodes that: there the frame's own end is the only limit)
+        if (cb == 0u || cb > 0x7FFFFFFFu || (uint64_t)p + cb > cbytes || (!cb_is_blosclz(flags) && cb > neblock + neblock / 255u + 16u)) { bad = true; break; }
         CbStream st; st.src = p; st.csize = cb; st.dst = idx * blocksize + s * neblock; st.usize = neblock;
         out[s] = st;
         p += cb;
@@ -78,6 +82,7 @@ __device__ __forceinline__ CbStream cb_load_stream(const CbStream *__restrict__ 
 // The decoder is pass A of the symbolic decoder without the symbols (hb_sym_decode.h): 13 KiB of LDS per wavefront -- an image of the last
 // 4 KiB of output, older sources read back from HBM -- so that a dozen streams per CU are in flight.  (First version: the serial
 // block decoder with its 64 KiB history in LDS, one wavefront per CU: 21 GB/s on 256 MiB of float32.)
+template <int CODEC = RG_LZ4>
 __device__ __forceinline__ void cb_decode_stream(const uint8_t *__restrict__ frame, CbPlan *plan, const CbStream st, uint8_t *dst, int small_elsewhere,
                                                  uint8_t *s_win, uint2 *s_tq, uint8_t *s_d, int lane) {
     if (st.usize == 0u) return;
@@ -85,7 +90,7 @@ __device__ __forceinline__ void cb_decode_stream(const uint8_t *__restrict__ fra
     if (small_elsewhere && st.usize <= HB_CHUNK && st.csize <= CB_SMALL_IN) return;      // k_cb_decode_small has it
     uint32_t out = st.dst;
     bool parked;
-    const bool ok = sy_decode_unit<false>(frame + st.src, (uint64_t)st.csize, 0u, st.csize, st.dst, st.dst, out, dst, nullptr, s_win, s_tq, s_d, nullptr,
+    const bool ok = sy_decode_unit<false, RG_PWIN, false, CODEC>(frame + st.src, (uint64_t)st.csize, 0u, st.csize, st.dst, st.dst, out, dst, nullptr, s_win, s_tq, s_d, nullptr,
                                           lane, 1, 0u, 0u, nullptr, nullptr, nullptr, parked, st.dst + st.usize);
     if ((!ok || out != st.dst + st.usize) && lane == 0) atomicExch(&plan->fail, 1u);     // blosc_d: "nbytes != neblock -> -2"
     wave_sync();
@@ -103,6 +108,24 @@ __global__ __launch_bounds__(64) void k_cb_decode(const uint8_t *__restrict__ fr
         const uint32_t i = cb_stream_of(it, mgrp, P);
         if (i >= nstreams) continue;
         cb_decode_stream(frame, plan, cb_load_stream(streams, i), dst, small_elsewhere, s_win, s_tq, s_d, lane);
+    }
+}
+
+// The streams of a BloscLZ frame (codec format 0; accepted once hb_cblosc_accept_codecs has said so): the same decoder behind the BloscLZ
+// walker, the same LDS.  The host launches it INSTEAD of k_cb_decode / k_cb_decode_small -- a frame has one codec -- so the LZ4 kernels never
+// see such a stream, the small one included, which selects by size alone.  Stored streams are copied here.
+__global__ __launch_bounds__(64) void k_cb_decode_blz(const uint8_t *__restrict__ frame, CbPlan *plan, const CbStream *__restrict__ streams, uint32_t nstreams,
+                                                       uint8_t *dst, uint32_t P) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[RG_PWIN + 128];
+    __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
+    __shared__ __attribute__((aligned(16))) uint8_t s_d[SY_IMG + 64];
+    const int lane = threadIdx.x;
+    if (plan->fail) return;
+    const uint32_t mgrp = (nstreams + 7u) / 8u;
+    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
+        const uint32_t i = cb_stream_of(it, mgrp, P);
+        if (i >= nstreams) continue;
+        cb_decode_stream<RG_BLOSCLZ>(frame, plan, cb_load_stream(streams, i), dst, 0, s_win, s_tq, s_d, lane);
     }
 }
 
@@ -373,8 +396,29 @@ __global__ __launch_bounds__(64) void k_cbb_decode(const CbbFrame *__restrict__ 
         CbPlan *plan = plans + k;
         if (RFL(plan->fail)) continue;                                         // (one value for the whole wave: nobody is left behind at a wave_sync)
         const CbbFrame &F = frames[k];
+        if (cb_is_blosclz(F.flags)) continue;                                  // k_cbb_decode_blz has it (and F.small is 0: the small decoder passes it by)
         uint8_t *target = F.stage_off ? work + F.stage_off : F.dst;
         cb_decode_stream(F.frame, plan, cb_load_stream(streams, i), target, small_launched && F.small, s_win, s_tq, s_d, lane);
+    }
+}
+// the streams of the batch's BloscLZ frames (launched when there is one): the same walk over the flat stream space, the other codec's frames passed by
+__global__ __launch_bounds__(64) void k_cbb_decode_blz(const CbbFrame *__restrict__ frames, CbPlan *plans, const uint32_t *__restrict__ str0, uint32_t nframes,
+                                                        const CbStream *__restrict__ streams, uint32_t nstreams, uint8_t *work, uint32_t P) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[RG_PWIN + 128];
+    __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
+    __shared__ __attribute__((aligned(16))) uint8_t s_d[SY_IMG + 64];
+    const int lane = threadIdx.x;
+    const uint32_t mgrp = (nstreams + 7u) / 8u;
+    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
+        const uint32_t i = cb_stream_of(it, mgrp, P);
+        if (i >= nstreams) continue;
+        const uint32_t k = RFL(hb_owner(str0, nframes, i));
+        CbPlan *plan = plans + k;
+        if (RFL(plan->fail)) continue;
+        const CbbFrame &F = frames[k];
+        if (!cb_is_blosclz(F.flags)) continue;
+        uint8_t *target = F.stage_off ? work + F.stage_off : F.dst;
+        cb_decode_stream<RG_BLOSCLZ>(F.frame, plan, cb_load_stream(streams, i), target, 0, s_win, s_tq, s_d, lane);
     }
 }
 __global__ __launch_bounds__(64) void k_cbb_decode_small(const CbbFrame *__restrict__ frames, CbPlan *plans, const uint32_t *__restrict__ str0, uint32_t nframes,
@@ -463,7 +507,28 @@ __global__ __launch_bounds__(64) void k_cbg_decode(const CbgFrame *__restrict__ 
         if (RFL(plan->fail)) continue;                                         // (one value for the whole wave: nobody is left behind at a wave_sync)
         const CbgBlock &K = blocks[x];
         const CbgFrame &F = frames[K.frame];
+        if (cb_is_blosclz(F.flags)) continue;                                  // k_cbg_decode_blz has it (and F.small is 0: the small decoder passes it by)
         cb_decode_stream(F.frame, plan, cb_load_stream(streams, i), work + K.stage_off, small_launched && F.small, s_win, s_tq, s_d, lane);
+    }
+}
+// the streams of the covered blocks of BloscLZ frames (launched when there is one)
+__global__ __launch_bounds__(64) void k_cbg_decode_blz(const CbgFrame *__restrict__ frames, const CbgBlock *__restrict__ blocks, CbPlan *plans, const uint32_t *__restrict__ str0,
+                                                        uint32_t nblk, const CbStream *__restrict__ streams, uint32_t nstreams, uint8_t *work, uint32_t P) {
+    __shared__ __attribute__((aligned(16))) uint8_t s_win[RG_PWIN + 128];
+    __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
+    __shared__ __attribute__((aligned(16))) uint8_t s_d[SY_IMG + 64];
+    const int lane = threadIdx.x;
+    const uint32_t mgrp = (nstreams + 7u) / 8u;
+    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
+        const uint32_t i = cb_stream_of(it, mgrp, P);
+        if (i >= nstreams) continue;
+        const uint32_t x = RFL(hb_owner(str0, nblk, i));
+        CbPlan *plan = plans + x;
+        if (RFL(plan->fail)) continue;
+        const CbgBlock &K = blocks[x];
+        const CbgFrame &F = frames[K.frame];
+        if (!cb_is_blosclz(F.flags)) continue;
+        cb_decode_stream<RG_BLOSCLZ>(F.frame, plan, cb_load_stream(streams, i), work + K.stage_off, 0, s_win, s_tq, s_d, lane);
     }
 }
 __global__ __launch_bounds__(64) void k_cbg_decode_small(const CbgFrame *__restrict__ frames, const CbgBlock *__restrict__ blocks, CbPlan *plans, const uint32_t *__restrict__ str0,
@@ -874,7 +939,7 @@ static inline unsigned cb_grid(uint64_t items) { const uint64_t g = (items + 255
 // frame for b0 = 0; the last block of the frame may be shorter).  streams: nblocks * nsplit records, staged: nbytes + 64 bytes.
 static void cb_launch_blocks(const hb_cblosc_header *hdr, const uint8_t *d_frame, size_t n, uint32_t b0, uint32_t nblocks, uint32_t nbytes, uint8_t *out,
                              CbPlan *plan, CbStream *streams, uint8_t *staged, hipStream_t s) {
-    const uint32_t blocksize = hdr->blocksize, ts = hdr->typesize, flags = hdr->flags;
+    const uint32_t blocksize = hdr->blocksize, ts = hdr->typesize, flags = cb_record_flags(*hdr);      // (the codec as the frame was accepted: k_cb_plan's bound)
     const uint32_t nsplit = cb_nsplit(flags, ts, blocksize);
     // blosc_d: the byte shuffle counts for typesize > 1 only (and comes first), the bit shuffle for any typesize
     const bool unshuf = (flags & CB_FLAG_SHUFFLE) && ts > 1, unbit = !unshuf && (flags & CB_FLAG_BITSHUFFLE);
@@ -889,6 +954,17 @@ static void cb_launch_blocks(const hb_cblosc_header *hdr, const uint8_t *d_frame
     uint32_t P = mgrp / 4u + 1u;                                        // coprime to the groups of 8 streams, about a quarter turn
     for (;; P++) { uint32_t x = P, y = mgrp; while (y) { const uint32_t t = x % y; x = y; y = t; } if (x == 1u) break; }
     const unsigned grid = mgrp * 8u < 65536u ? mgrp * 8u : 65536u;
+    if (hdr->codec_format == CB_CODEC_BLOSCLZ) {                          // (accepted by the caller: hb_cblosc_accept_codecs)  One codec per frame: its decoder alone
+        unsigned gblz = grid;
+        if (nsplit > 1u) {                                              // (passes per workgroup as below)
+            unsigned p = nsplit;
+            while (p > 1u && mgrp * 8u / p < 2048u) p >>= 1;
+            gblz = (mgrp * 8u / p + 7u) / 8u * 8u;
+        }
+        hb_prof_begin("k_cb_decode_blz", s);
+        hipLaunchKernelGGL(k_cb_decode_blz, dim3(gblz), dim3(64), 0, s, d_frame, plan, streams, nstreams, target, P);
+        hb_prof_end(s);
+    } else {
     hb_prof_begin("k_cb_decode_small", s);
     if (small) hipLaunchKernelGGL(k_cb_decode_small, dim3(grid), dim3(64), 0, s, d_frame, plan, streams, nstreams, target, P);
     hb_prof_end(s);
@@ -904,6 +980,7 @@ static void cb_launch_blocks(const hb_cblosc_header *hdr, const uint8_t *d_frame
     }
     hipLaunchKernelGGL(k_cb_decode, dim3(gbig), dim3(64), 0, s, d_frame, plan, streams, nstreams, target, small ? 1 : 0, P);
     hb_prof_end(s);
+    }
     if (filtered) {
         hb_prof_begin("k_cb_unfilter", s);
         if (unshuf)
@@ -925,7 +1002,16 @@ static void cb_launch_blocks(const hb_cblosc_header *hdr, const uint8_t *d_frame
     }
 }
 
+// which codec formats the entry points below decode (hb_cblosc_batch.h: cb_codec_refused); every entry point reads it once
+static std::atomic<unsigned> g_cb_accept{CB_ACCEPT_DEFAULT};
+unsigned hb_cblosc_accepted() { return g_cb_accept.load(std::memory_order_relaxed); }
+
 extern "C" {
+
+int hb_cblosc_accept_codecs(unsigned mask) {
+    if (!cb_accept_valid(mask)) return HB_ERR_BAD_ARG;
+    return (int)g_cb_accept.exchange(mask, std::memory_order_relaxed);
+}
 
 // header fields of a C-Blosc-1 frame (host side); HB_OK or the error a malformed header gets
 int hb_cblosc_parse_header(const void *frame, size_t n, hb_cblosc_header *out) { return cb_parse_header(frame, n, out); }
@@ -938,6 +1024,7 @@ int hb_cblosc_decompress_dev(const hb_cblosc_header *hdr, const void *d_frame, s
     if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
     if (!hdr || !d_frame || (!d_dst && cap) || !d_work || ((uintptr_t)d_work & 255u) || !d_result) return HB_ERR_BAD_ARG;
     hipStream_t s = (hipStream_t)stream;
+    const unsigned accept = hb_cblosc_accepted();
     const uint32_t nbytes = hdr->nbytes, blocksize = hdr->blocksize, ts = hdr->typesize, flags = hdr->flags;
     // the record may come from a caller that ignored hb_cblosc_parse_header's return value, or built it itself: repeat its checks
     // before anything divides by a field
@@ -956,7 +1043,7 @@ int hb_cblosc_decompress_dev(const hb_cblosc_header *hdr, const void *d_frame, s
         hipLaunchKernelGGL(k_cb_result, dim3(1), dim3(1), 0, s, plan, d_result, (uint64_t)nbytes);
         return HB_OK;
     }
-    if (hdr->codec_format != 1) return HB_ERR_INVALID_CODEC;            // lz4 / lz4hc only
+    if (cb_codec_refused(*hdr, accept)) return HB_ERR_INVALID_CODEC;    // lz4 / lz4hc, and blosclz where the caller has asked for it
     const uint32_t nblocks = (uint32_t)(((uint64_t)nbytes + blocksize - 1) / blocksize);
     if (16ull + 4ull * nblocks > hdr->cbytes) return HB_ERR_INVALID_DATA;
     if (blocksize < ts) return HB_ERR_INVALID_DATA;                     // (c-blosc never writes it; a stream would hold less than one element)
@@ -972,7 +1059,7 @@ int hb_cblosc_decompress_dev(const hb_cblosc_header *hdr, const void *d_frame, s
 // ---- many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_batch.h) ----
 size_t hb_cblosc_decompress_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n) {
     CbbBatch B;
-    if (cbb_prepare(nframes, hdrs, nullptr, n, nullptr, nullptr, B)) return 0;
+    if (cbb_prepare(nframes, hdrs, nullptr, n, nullptr, nullptr, B, hb_cblosc_accepted())) return 0;
     return B.L.total ? B.L.total : 256;                                   // (never 0 for a batch that is accepted)
 }
 
@@ -982,7 +1069,7 @@ int hb_cblosc_decompress_frames_batch_device(int nframes, const hb_cblosc_header
     if (nframes == 0) return HB_OK;
     if (!hdrs || !d_frame || !n || !d_dst || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
     CbbBatch B;
-    const int rc = cbb_prepare(nframes, hdrs, d_frame, n, d_dst, cap, B);
+    const int rc = cbb_prepare(nframes, hdrs, d_frame, n, d_dst, cap, B, hb_cblosc_accepted());
     if (rc) return rc;
     const CbbLayout &L = B.L;
     if (work_bytes < L.total) return HB_ERR_SHORT_BUFFER;
@@ -1025,9 +1112,23 @@ int hb_cblosc_decompress_frames_batch_device(int nframes, const hb_cblosc_header
             gbig = (mgrp * 8u / p + 7u) / 8u * 8u;
             if (gbig > 65536u) gbig = 65536u;
         }
-        hb_prof_begin("k_cbb_decode", s);
-        hipLaunchKernelGGL(k_cbb_decode, dim3(gbig), dim3(64), 0, s, d_frames, d_plans, d_str0, (uint32_t)nframes, (const CbStream *)d_streams, nstreams, w, (int)B.any_small, P);
-        hb_prof_end(s);
+        if (B.any_lz4) {
+            hb_prof_begin("k_cbb_decode", s);
+            hipLaunchKernelGGL(k_cbb_decode, dim3(gbig), dim3(64), 0, s, d_frames, d_plans, d_str0, (uint32_t)nframes, (const CbStream *)d_streams, nstreams, w, (int)B.any_small, P);
+            hb_prof_end(s);
+        }
+        if (B.any_blz) {                                                // (the BloscLZ frames' streams, stored ones included; grid as gbig without the small decoder)
+            unsigned gblz = grid;
+            if (B.nsplit_all > 1u) {
+                unsigned p = B.nsplit_all;
+                while (p > 1u && mgrp * 8u / p < 2048u) p >>= 1;
+                gblz = (mgrp * 8u / p + 7u) / 8u * 8u;
+                if (gblz > 65536u) gblz = 65536u;
+            }
+            hb_prof_begin("k_cbb_decode_blz", s);
+            hipLaunchKernelGGL(k_cbb_decode_blz, dim3(gblz), dim3(64), 0, s, d_frames, d_plans, d_str0, (uint32_t)nframes, (const CbStream *)d_streams, nstreams, w, P);
+            hb_prof_end(s);
+        }
     }
     for (int k = 0; k < CBK_COUNT; k++) {
         const uint32_t k0 = B.kind0[k], nk = B.kind0[k + 1] - k0, blocks = B.kblocks[k];
@@ -1058,12 +1159,12 @@ int hb_cblosc_decompress_frames_batch_device(int nframes, const hb_cblosc_header
 
 size_t hb_cblosc_getitem_workspace(const hb_cblosc_header *hdr, int64_t start, int64_t nitems) {
     CbRange r;
-    if (!hdr || cb_getitem_prepare(hdr, (size_t)hdr->cbytes, start, nitems, r)) return 0;
+    if (!hdr || cb_getitem_prepare(hdr, (size_t)hdr->cbytes, start, nitems, r, hb_cblosc_accepted())) return 0;
     return r.total;
 }
 extern "C++" int hb_cblosc_getitem_prepare(const hb_cblosc_header *hdr, size_t n, int64_t start, int64_t nitems, uint64_t *bytes) {
     CbRange r;
-    const int rc = cb_getitem_prepare(hdr, n, start, nitems, r);
+    const int rc = cb_getitem_prepare(hdr, n, start, nitems, r, hb_cblosc_accepted());
     if (!rc) *bytes = r.bytes;
     return rc;
 }
@@ -1072,7 +1173,7 @@ int hb_cblosc_getitem_device(const hb_cblosc_header *hdr, const void *d_frame, s
                              void *d_work, size_t work_bytes, hb_result *d_result, void *stream) {
     if (!hdr) return HB_ERR_BAD_ARG;
     CbRange r;
-    const int rc = cb_getitem_prepare(hdr, n, start, nitems, r);
+    const int rc = cb_getitem_prepare(hdr, n, start, nitems, r, hb_cblosc_accepted());
     if (rc) return rc;
     if ((uint64_t)cap < r.bytes) return HB_ERR_SHORT_BUFFER;
     if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
@@ -1098,7 +1199,7 @@ int hb_cblosc_getitem_device(const hb_cblosc_header *hdr, const void *d_frame, s
 
 // ---- many ranges of many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_getitem_batch.h) ----
 size_t hb_cblosc_getitem_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n, int njobs, const hb_getitem_job *jobs) {
-    return cbg_workspace(nframes, hdrs, n, njobs, jobs);
+    return cbg_workspace(nframes, hdrs, n, njobs, jobs, hb_cblosc_accepted());
 }
 
 int hb_cblosc_getitem_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_getitem_job *jobs,
@@ -1107,11 +1208,12 @@ int hb_cblosc_getitem_frames_batch_device(int nframes, const hb_cblosc_header *h
     if (njobs == 0) return HB_OK;
     if (!hdrs || !d_frame || !n || !jobs || !d_dst || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
     CbgBatch B;
-    const int rc = cbg_prepare(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, true, B);
+    const unsigned accept = hb_cblosc_accepted();
+    const int rc = cbg_prepare(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, true, B, accept);
     if (rc) return rc;
     const CbgLayout &L = B.L;
     // (the query knows no capacities and no pointers: where a job was refused for one of them it has counted blocks that this batch leaves out)
-    if (work_bytes < (B.ptr_refusals ? cbg_workspace(nframes, hdrs, n, njobs, jobs) : L.total)) return HB_ERR_SHORT_BUFFER;
+    if (work_bytes < (B.ptr_refusals ? cbg_workspace(nframes, hdrs, n, njobs, jobs, accept) : L.total)) return HB_ERR_SHORT_BUFFER;
     if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
     uint8_t *w = (uint8_t *)d_work;
@@ -1157,9 +1259,23 @@ int hb_cblosc_getitem_frames_batch_device(int nframes, const hb_cblosc_header *h
             gbig = (mgrp * 8u / p + 7u) / 8u * 8u;
             if (gbig > 65536u) gbig = 65536u;
         }
-        hb_prof_begin("k_cbg_decode", s);
-        hipLaunchKernelGGL(k_cbg_decode, dim3(gbig), dim3(64), 0, s, d_frames, d_blocks, d_plans, d_str0, nblk, (const CbStream *)d_streams, nstreams, w, (int)B.any_small, P);
-        hb_prof_end(s);
+        if (B.any_lz4) {
+            hb_prof_begin("k_cbg_decode", s);
+            hipLaunchKernelGGL(k_cbg_decode, dim3(gbig), dim3(64), 0, s, d_frames, d_blocks, d_plans, d_str0, nblk, (const CbStream *)d_streams, nstreams, w, (int)B.any_small, P);
+            hb_prof_end(s);
+        }
+        if (B.any_blz) {                                                // (the covered blocks of BloscLZ frames, stored streams included)
+            unsigned gblz = grid;
+            if (B.nsplit_all > 1u) {
+                unsigned p = B.nsplit_all;
+                while (p > 1u && mgrp * 8u / p < 2048u) p >>= 1;
+                gblz = (mgrp * 8u / p + 7u) / 8u * 8u;
+                if (gblz > 65536u) gblz = 65536u;
+            }
+            hb_prof_begin("k_cbg_decode_blz", s);
+            hipLaunchKernelGGL(k_cbg_decode_blz, dim3(gblz), dim3(64), 0, s, d_frames, d_blocks, d_plans, d_str0, nblk, (const CbStream *)d_streams, nstreams, w, P);
+            hb_prof_end(s);
+        }
     }
     static const char *const gname[CBG_COUNT] = {"k_cbg_gather_copy", "k_cbg_gather_unshuffle", "k_cbg_gather_bitun", "k_cbg_gather_bitun4"};
     for (int k = 0; k < CBG_COUNT; k++) {

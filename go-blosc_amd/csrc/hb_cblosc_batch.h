@@ -29,6 +29,21 @@ CB_HD static inline uint32_t cb_nsplit(uint32_t flags, uint32_t typesize, uint32
 struct CbStream { uint32_t src, csize, dst, usize; };
 struct CbPlan { uint32_t fail, nblocks, nsplit, pad; };
 
+// ---- which codec formats the hb_cblosc_* entry points decode (include/hipblosc.h hb_cblosc_accept_codecs): bit k = codec format k.  The
+// word itself lives in hb_cblosc.hip; an entry point reads it ONCE (hb_cblosc_accepted) and hands the value to everything it asks below, so
+// that one call judges all its frames alike.  Every codec check of the C-Blosc-1 side is cb_codec_refused(). ----
+#define CB_CODEC_BLOSCLZ   0u
+#define CB_CODEC_LZ4       1u
+#define CB_ACCEPT_DEFAULT  0x2u      // LZ4 / LZ4HC
+#define CB_ACCEPT_BLOSCLZ  0x3u      // ... and BloscLZ
+static inline bool cb_accept_valid(unsigned mask) { return mask == CB_ACCEPT_DEFAULT || mask == CB_ACCEPT_BLOSCLZ; }
+// a frame with streams (not memcpyed): HB_OK, or HB_ERR_INVALID_CODEC for a codec format the mask does not name.  hb_cblosc_header.codec_format
+// decides, as it always has; the records that go to the device carry it in the flags' three high bits (cb_record_flags), where the header has
+// it too -- so a record built by hand with the two at odds is decoded as what it was accepted as.
+static inline int cb_codec_refused(const hb_cblosc_header &h, unsigned accept) { return (h.codec_format < 8u && ((accept >> h.codec_format) & 1u)) ? HB_OK : HB_ERR_INVALID_CODEC; }
+static inline uint32_t cb_record_flags(const hb_cblosc_header &h) { return (h.flags & 0x1Fu) | ((h.codec_format & 7u) << 5); }
+CB_HD static inline bool cb_is_blosclz(uint32_t flags) { return (flags >> 5) == CB_CODEC_BLOSCLZ; }
+
 static inline size_t cb_align(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // hb_cblosc_decompress_workspace: the plan, the stream records (cb_nsplit() without the flag: the upper bound), the staged copy
@@ -66,7 +81,7 @@ struct CbbFrame {
     uint32_t nbytes, blocksize, cbytes, typesize, flags, nsplit;
     uint32_t b0, nblocks;                // the blocks of this record: all of the frame's (b0 = 0) -- a record for "blocks [b0, b0 + nb)" fits as it is
     uint32_t stream0;                    // its first stream record (= str0[k])
-    uint32_t small;                      // every stream is at most one chunk: k_cbb_decode_small takes those that are not stored
+    uint32_t small;                      // an LZ4 frame whose every stream is at most one chunk: k_cbb_decode_small takes those that are not stored
     int32_t mode, kind, status;          // CBB_*; CBK_* or -1; mode CBB_REFUSED: `status` is what the host decided
     uint32_t ngrid, nfast;               // workgroups in the launch of its kind; CBK_BITUN4: the first nfast run the fast path, the rest the last, shorter block
     uint32_t pad;
@@ -76,7 +91,8 @@ static_assert(sizeof(CbbFrame) + sizeof(CbPlan) + 16 + 3 * 255 <= HB_CBLOSC_BATC
 
 // what hb_cblosc_decompress_dev returns for this header, in its order (the workspace apart); HB_OK: *mode says what there is to do.
 // have_ptrs == 0: the workspace query, which knows neither pointers nor capacities.
-static inline int cbb_refusal(const hb_cblosc_header &h, int have_ptrs, const void *d_frame, const void *d_dst, size_t n, size_t cap, int *mode) {
+static inline int cbb_refusal(const hb_cblosc_header &h, int have_ptrs, const void *d_frame, const void *d_dst, size_t n, size_t cap, int *mode,
+                              unsigned accept = CB_ACCEPT_DEFAULT) {
     const uint32_t nbytes = h.nbytes, blocksize = h.blocksize, ts = h.typesize;
     *mode = CBB_REFUSED;
     if (have_ptrs && (!d_frame || (!d_dst && cap))) return HB_ERR_BAD_ARG;
@@ -90,7 +106,7 @@ static inline int cbb_refusal(const hb_cblosc_header &h, int have_ptrs, const vo
         *mode = CBB_MEMCPY;
         return HB_OK;
     }
-    if (h.codec_format != 1) return HB_ERR_INVALID_CODEC;
+    if (cb_codec_refused(h, accept)) return HB_ERR_INVALID_CODEC;
     const uint64_t nblocks = ((uint64_t)nbytes + blocksize - 1) / blocksize;
     if (16ull + 4ull * nblocks > h.cbytes) return HB_ERR_INVALID_DATA;
     if (blocksize < ts) return HB_ERR_INVALID_DATA;
@@ -122,6 +138,7 @@ struct CbbBatch {
     uint64_t nblocks, nstreams;
     size_t stage;
     uint32_t any_small, nsplit_all;      // some frame's streams are at most one chunk; the nsplit that all frames with streams share, else 1
+    uint32_t any_lz4, any_blz;           // some frame with streams is LZ4 / BloscLZ: one decoder launch per codec that occurs
     CbbLayout L;
 };
 
@@ -132,9 +149,9 @@ static inline uint32_t cbb_grid(uint64_t items, uint32_t per_group, uint32_t mos
 
 // HB_OK, or what the call as a whole answers.  d_frame / d_dst / cap == NULL: the workspace query.
 static inline int cbb_prepare(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, void *const *d_dst, const size_t *cap,
-                              CbbBatch &B) {
+                              CbbBatch &B, unsigned accept = CB_ACCEPT_DEFAULT) {
     if (nframes < 0) return HB_ERR_BAD_ARG;
-    B.nblocks = 0; B.nstreams = 0; B.stage = 0; B.any_small = 0; B.nsplit_all = 0;
+    B.nblocks = 0; B.nstreams = 0; B.stage = 0; B.any_small = 0; B.nsplit_all = 0; B.any_lz4 = 0; B.any_blz = 0;
     for (int k = 0; k < CBK_COUNT; k++) B.kblocks[k] = 0;
     for (int k = 0; k <= CBK_COUNT; k++) B.kind0[k] = 0;
     B.L = cbb_layout(0, 0, 0);
@@ -154,12 +171,12 @@ static inline int cbb_prepare(int nframes, const hb_cblosc_header *hdrs, const v
         blk0[k] = (uint32_t)B.nblocks; str0[k] = (uint32_t)B.nstreams;
         F.kind = -1;
         int mode = CBB_REFUSED;
-        F.status = cbb_refusal(h, have, have ? d_frame[k] : nullptr, have ? d_dst[k] : nullptr, n[k], have ? cap[k] : 0, &mode);
+        F.status = cbb_refusal(h, have, have ? d_frame[k] : nullptr, have ? d_dst[k] : nullptr, n[k], have ? cap[k] : 0, &mode, accept);
         F.mode = mode;
         if (mode == CBB_REFUSED) continue;
         F.frame = have ? (const uint8_t *)d_frame[k] : nullptr; F.dst = have ? (uint8_t *)d_dst[k] : nullptr;
         F.n = n[k];
-        F.nbytes = h.nbytes; F.blocksize = h.blocksize; F.cbytes = h.cbytes; F.typesize = h.typesize; F.flags = h.flags;
+        F.nbytes = h.nbytes; F.blocksize = h.blocksize; F.cbytes = h.cbytes; F.typesize = h.typesize; F.flags = cb_record_flags(h);
         if (mode == CBB_EMPTY) continue;
         if (mode == CBB_MEMCPY) {
             F.kind = CBK_COPY;
@@ -169,7 +186,9 @@ static inline int cbb_prepare(int nframes, const hb_cblosc_header *hdrs, const v
             F.nsplit = cb_nsplit(h.flags, ts, bs);
             F.b0 = 0; F.nblocks = (uint32_t)(((uint64_t)h.nbytes + bs - 1) / bs);
             F.stream0 = (uint32_t)B.nstreams;
-            F.small = bs / F.nsplit <= HB_CHUNK ? 1u : 0u;
+            const bool blz = cb_is_blosclz(F.flags);
+            if (blz) B.any_blz = 1; else B.any_lz4 = 1;
+            F.small = !blz && bs / F.nsplit <= HB_CHUNK ? 1u : 0u;                // (the small decoder is LZ4's: it selects by this and by size alone)
             B.nblocks += F.nblocks;
             B.nstreams += (uint64_t)F.nblocks * F.nsplit;
             B.plans[k].nblocks = F.nblocks; B.plans[k].nsplit = F.nsplit;
@@ -223,7 +242,8 @@ struct CbbHostPlan {
     size_t in_bytes, out_bytes, span_bytes;
     bool span_in, span_out;
 };
-static inline void cbb_host_plan(int nframes, const void *const *frame, const size_t *n, void *const *dst, const size_t *cap, CbbHostPlan &P) {
+static inline void cbb_host_plan(int nframes, const void *const *frame, const size_t *n, void *const *dst, const size_t *cap, CbbHostPlan &P,
+                                 unsigned accept = CB_ACCEPT_DEFAULT) {
     P.idx.clear(); P.hd.clear(); P.ns.clear(); P.caps.clear(); P.ioff.clear(); P.ooff.clear();
     P.in_bytes = P.out_bytes = P.span_bytes = 0; P.span_in = P.span_out = false;
     for (int k = 0; k < nframes; k++) {
@@ -231,7 +251,7 @@ static inline void cbb_host_plan(int nframes, const void *const *frame, const si
         int mode = CBB_REFUSED;
         // (a NULL destination is hb_cblosc_decompress's to answer, unless the frame is empty: the device gets a buffer of its own either way)
         const bool ok = frame[k] && cb_parse_header(frame[k], n[k], &h) == HB_OK && (dst[k] || !h.nbytes) &&
-                        cbb_refusal(h, 1, frame[k], frame[k], n[k], cap[k], &mode) == HB_OK;
+                        cbb_refusal(h, 1, frame[k], frame[k], n[k], cap[k], &mode, accept) == HB_OK;
         if (ok) { P.idx.push_back(k); P.hd.push_back(h); }
     }
     const size_t m = P.idx.size();

@@ -11,7 +11,7 @@
 // ---- one range: items [start, start + nitems) of typesize bytes lie in blocks [b_lo, b_lo + nb) ----
 struct CbRange { uint32_t b_lo, nb, vbytes; uint64_t off, bytes; size_t streams, stage, total; };
 // the header refusals of hb_cblosc_decompress / hb_cblosc_decompress_dev, then the range; what is sized comes after the geometry checks
-static inline int cb_getitem_prepare(const hb_cblosc_header *hdr, size_t n, int64_t start, int64_t nitems, CbRange &r) {
+static inline int cb_getitem_prepare(const hb_cblosc_header *hdr, size_t n, int64_t start, int64_t nitems, CbRange &r, unsigned accept = CB_ACCEPT_DEFAULT) {
     const uint32_t nbytes = hdr->nbytes, blocksize = hdr->blocksize, ts = hdr->typesize, flags = hdr->flags;
     if (n < 16) return HB_ERR_INVALID_HEADER;
     if (hdr->version != 2) return HB_ERR_INVALID_VERSION;
@@ -21,7 +21,7 @@ static inline int cb_getitem_prepare(const hb_cblosc_header *hdr, size_t n, int6
     if (flags & CB_FLAG_MEMCPY) {
         if ((uint64_t)hdr->cbytes < 16ull + nbytes) return HB_ERR_INVALID_DATA;
     } else {
-        if (hdr->codec_format != 1) return HB_ERR_INVALID_CODEC;
+        if (cb_codec_refused(*hdr, accept)) return HB_ERR_INVALID_CODEC;
         if (nbytes) {
             nblocks = ((uint64_t)nbytes + blocksize - 1) / blocksize;
             if (16ull + 4ull * nblocks > hdr->cbytes || blocksize < ts) return HB_ERR_INVALID_DATA;
@@ -54,7 +54,7 @@ enum { CBG_COPY = 0, CBG_UNSHUFFLE, CBG_BITUN, CBG_BITUN4, CBG_COUNT };
 struct CbgFrame {
     const uint8_t *frame;                // d_frame[f]; NULL: no accepted job reads it
     uint32_t nbytes, blocksize, cbytes, typesize, flags, nsplit;
-    uint32_t small;                      // every stream is at most one chunk: k_cbg_decode_small takes those that are not stored
+    uint32_t small;                      // an LZ4 frame whose every stream is at most one chunk: k_cbg_decode_small takes those that are not stored
     uint32_t memcpyed;
 };
 struct CbgBlock {
@@ -84,8 +84,9 @@ CB_HD static inline uint32_t cbg_unit_bytes(int kind, uint32_t ts) { return kind
 
 // what hb_cblosc_getitem_device returns for the job, in its order without the device lookup; HB_OK: `r` is the range.
 // have_ptrs == 0: the workspace query, which knows neither pointers nor capacities.
-static inline int cbg_refusal(const hb_cblosc_header &h, size_t n, const hb_getitem_job &q, int have_ptrs, const void *d_frame, const void *d_dst, size_t cap, CbRange &r) {
-    const int rc = cb_getitem_prepare(&h, n, q.start, q.nitems, r);
+static inline int cbg_refusal(const hb_cblosc_header &h, size_t n, const hb_getitem_job &q, int have_ptrs, const void *d_frame, const void *d_dst, size_t cap, CbRange &r,
+                              unsigned accept = CB_ACCEPT_DEFAULT) {
+    const int rc = cb_getitem_prepare(&h, n, q.start, q.nitems, r, accept);
     if (rc) return rc;
     if (!have_ptrs) return HB_OK;
     if ((uint64_t)cap < r.bytes) return HB_ERR_SHORT_BUFFER;
@@ -125,6 +126,7 @@ struct CbgBatch {
     uint32_t kblocks[CBG_COUNT];         // workgroups of kind k
     uint64_t nblk, nstreams, stage;
     uint32_t any_small, nsplit_all;      // some covered frame's streams are at most one chunk; the nsplit that all covered frames share, else 1
+    uint32_t any_lz4, any_blz;           // some covered frame with streams is LZ4 / BloscLZ: one decoder launch per codec that occurs
     int ptr_refusals;                    // jobs refused for their capacity or a pointer: the workspace query counts their blocks, this batch does not
     CbgLayout L;
 };
@@ -137,8 +139,8 @@ static inline uint32_t cbg_bsize(const hb_cblosc_header &h, uint32_t b) {
 // HB_OK, or what the call as a whole answers.  d_frame / d_dst / cap == NULL: the workspace query.  fill == false: counts and layout only
 // (nothing whose size depends on the number of blocks is allocated).
 static inline int cbg_prepare_(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_getitem_job *jobs,
-                               void *const *d_dst, const size_t *cap, bool fill, CbgBatch &B) {
-    B.nblk = 0; B.nstreams = 0; B.stage = 0; B.any_small = 0; B.nsplit_all = 0; B.ptr_refusals = 0;
+                               void *const *d_dst, const size_t *cap, bool fill, CbgBatch &B, unsigned accept) {
+    B.nblk = 0; B.nstreams = 0; B.stage = 0; B.any_small = 0; B.nsplit_all = 0; B.ptr_refusals = 0; B.any_lz4 = 0; B.any_blz = 0;
     for (int k = 0; k < CBG_COUNT; k++) B.kblocks[k] = 0;
     for (int k = 0; k <= CBG_COUNT; k++) B.kind0[k] = 0;
     B.frames.clear(); B.jobs.clear(); B.runs.clear(); B.blocks.clear(); B.str0.clear(); B.gjob.clear(); B.gblk.clear();
@@ -161,7 +163,7 @@ static inline int cbg_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
         CbgJob &J = B.jobs[j];
         CbRange r;
         J.kind = -1; J.frame = q.frame;
-        J.status = cb_getitem_prepare(&h, n[q.frame], q.start, q.nitems, r);
+        J.status = cb_getitem_prepare(&h, n[q.frame], q.start, q.nitems, r, accept);
         if (J.status == HB_OK && have) {
             if ((uint64_t)cap[j] < r.bytes) J.status = HB_ERR_SHORT_BUFFER;
             else if (!d_frame[q.frame] || (!d_dst[j] && r.bytes)) J.status = HB_ERR_BAD_ARG;
@@ -171,10 +173,10 @@ static inline int cbg_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
         CbgFrame &F = B.frames[q.frame];
         if (!F.typesize) {                                                // the first accepted job of this frame
             F.frame = have ? (const uint8_t *)d_frame[q.frame] : nullptr;
-            F.nbytes = h.nbytes; F.blocksize = h.blocksize; F.cbytes = h.cbytes; F.typesize = h.typesize; F.flags = h.flags;
+            F.nbytes = h.nbytes; F.blocksize = h.blocksize; F.cbytes = h.cbytes; F.typesize = h.typesize; F.flags = cb_record_flags(h);
             F.memcpyed = (h.flags & CB_FLAG_MEMCPY) ? 1u : 0u;
             F.nsplit = F.memcpyed || !h.blocksize ? 1u : cb_nsplit(h.flags, h.typesize, h.blocksize);
-            F.small = !F.memcpyed && h.blocksize && h.blocksize / F.nsplit <= HB_CHUNK ? 1u : 0u;
+            F.small = !F.memcpyed && !cb_is_blosclz(F.flags) && h.blocksize && h.blocksize / F.nsplit <= HB_CHUNK ? 1u : 0u;      // (the small decoder is LZ4's)
         }
         J.dst = have ? (uint8_t *)d_dst[j] : nullptr;
         J.off = r.off; J.bytes = r.bytes; J.nb = r.nb;
@@ -213,6 +215,7 @@ static inline int cbg_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
         B.stage += full * cb_align((size_t)h.blocksize + 64) + (tail ? cb_align((size_t)(h.nbytes % h.blocksize) + 64) : 0u);
         if (B.nblk > HB_CBLOSC_BATCH_MAX_WORK || B.nstreams > HB_CBLOSC_BATCH_MAX_WORK) return HB_ERR_BAD_ARG;
         if (F.small) B.any_small = 1;
+        if (cb_is_blosclz(F.flags)) B.any_blz = 1; else B.any_lz4 = 1;
         B.nsplit_all = B.nsplit_all == 0 || B.nsplit_all == F.nsplit ? F.nsplit : 1u;
     }
     if (B.nsplit_all == 0) B.nsplit_all = 1;
@@ -261,15 +264,15 @@ static inline int cbg_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
 }
 // (a batch whose tables do not fit into host memory is one the caller has to split, like one beyond the 32-bit limits)
 static inline int cbg_prepare(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_getitem_job *jobs,
-                              void *const *d_dst, const size_t *cap, bool fill, CbgBatch &B) {
-    try { return cbg_prepare_(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, fill, B); }
+                              void *const *d_dst, const size_t *cap, bool fill, CbgBatch &B, unsigned accept = CB_ACCEPT_DEFAULT) {
+    try { return cbg_prepare_(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, fill, B, accept); }
     catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
 }
 
 // hb_cblosc_getitem_frames_batch_workspace: 0 when the call as a whole would be refused
-static inline size_t cbg_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n, int njobs, const hb_getitem_job *jobs) {
+static inline size_t cbg_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n, int njobs, const hb_getitem_job *jobs, unsigned accept = CB_ACCEPT_DEFAULT) {
     CbgBatch B;
-    if (cbg_prepare(nframes, hdrs, nullptr, n, njobs, jobs, nullptr, nullptr, false, B)) return 0;
+    if (cbg_prepare(nframes, hdrs, nullptr, n, njobs, jobs, nullptr, nullptr, false, B, accept)) return 0;
     return B.L.total ? B.L.total : 256;                                   // (never 0 for a batch that is accepted)
 }
 
@@ -286,7 +289,7 @@ struct CbgHostPlan {
     bool span_in, any;
 };
 static inline void cbg_host_plan(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_getitem_job *jobs, void *const *dst, const size_t *cap,
-                                 CbgHostPlan &P) {
+                                 CbgHostPlan &P, unsigned accept = CB_ACCEPT_DEFAULT) {
     const size_t nf = (size_t)nframes, nj = (size_t)njobs;
     P.hd.assign(nf, hb_cblosc_header{}); P.carried.assign(nj, 0); P.idx.clear(); P.ioff.assign(nf, 0); P.ooff.assign(nj, 0); P.nb.assign(nj, 0);
     P.in_bytes = P.out_bytes = 0; P.span_in = false; P.any = false;
@@ -298,7 +301,7 @@ static inline void cbg_host_plan(int nframes, const void *const *frame, const si
     for (size_t j = 0; j < nj; j++) {
         const hb_getitem_job &q = jobs[j];
         CbRange r;
-        if (!parsed[q.frame] || cb_getitem_prepare(&P.hd[q.frame], n[q.frame], q.start, q.nitems, r) != HB_OK) continue;
+        if (!parsed[q.frame] || cb_getitem_prepare(&P.hd[q.frame], n[q.frame], q.start, q.nitems, r, accept) != HB_OK) continue;
         if ((uint64_t)cap[j] < r.bytes || (!dst[j] && r.bytes)) continue;
         P.carried[j] = 1; P.nb[j] = (size_t)r.bytes; P.ooff[j] = P.out_bytes; P.out_bytes += (size_t)r.bytes;
         used[q.frame] = 1; P.any = true;

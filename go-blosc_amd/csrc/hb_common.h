@@ -184,6 +184,7 @@ unsigned hb_dbg_plane_mask();                            // hb_debug_plane_mask(
 
 // ---- internal launch API shared between translation units ----
 // hb_cblosc.hip: the header / geometry / range refusals of the C-Blosc-1 getitem entry points; *bytes = nitems * typesize
+unsigned hb_cblosc_accepted();        // the mask of hb_cblosc_accept_codecs (hb_cblosc.hip): read once per entry point
 int hb_cblosc_getitem_prepare(const hb_cblosc_header *hdr, size_t n, int64_t start, int64_t nitems, uint64_t *bytes);
 int hb_launch_filter(int op, uint8_t *d_dst, const uint8_t *d_src, size_t n, int typesize, hipStream_t s);
 // same, but every kernel returns immediately unless *gate != 0 (gate is read on the device)

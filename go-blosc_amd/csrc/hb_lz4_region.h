@@ -111,7 +111,7 @@ int hb_launch_lz4_region_index_batch(const RgJob *d_jobs, int njobs, uint32_t ma
 
 // ---- the same discovery for Snappy blocks (hb_snappy.hip: blocks that come without a unit index, i.e. written by any other encoder) ----
 // The kernels that parse are templated on the codec: elements instead of sequences.  CODEC of rg_parse_region / k_rg_settle_body / k_rg_fix_body.
-enum { RG_LZ4 = 0, RG_SNAPPY = 1 };
+enum { RG_LZ4 = 0, RG_SNAPPY = 1, RG_BLOSCLZ = 2 };       // (RG_BLOSCLZ: a decoder's walker only -- bz_walk below; nothing discovers BloscLZ chains)
 // one element, all values wave-uniform: `p[k]` = stream byte k of a buffer holding `avail` bytes from the element's tag.  false: the header runs off the buffer.
 struct SnElem { uint32_t kind, hdr; uint64_t lit; uint32_t mlen; uint64_t off; };
 __device__ __forceinline__ bool sn_parse_uniform(const uint8_t *p, uint64_t avail, SnElem &e) {
@@ -338,6 +338,157 @@ __device__ __forceinline__ bool sn_walk(const uint8_t *__restrict__ src, const u
     }
     return drain(true);
 }
+// ---- BloscLZ (the streams of C-Blosc-1 frames of codec format 0, hb_cblosc.hip; the format as blosclz 2.3 of c-blosc 1.21 reads it) ----
+// An element is a control byte c and what it announces.  c < 32: c + 1 literal bytes follow.  c >= 32 is a match: length (c >> 5) - 1, and when
+// that is 6 the bytes that follow are added to it up to and including the first that is not 255; then 3 more.  Its distance is ((c & 31) << 8) +
+// the next byte + 1 -- unless that byte is 255 and c & 31 is 31: then two more bytes, big-endian, + 8192.  So a distance takes 17 bits (73727 at
+// most), a length is open-ended, a literal run ends at 32 bytes.  The stream's first control byte counts with its three high bits cleared, and
+// a match must be followed by another element: a stream never ends in one.
+//
+// FILL, as sn_fill: 64 lanes parse 64 stream bytes "as if an element began at my byte" from the eight bytes at their position, the real chain
+// is walked on the scalar side.  Elements go to s_tq as {pos | lit << 13 | mlen << 19, distance}, positions window-relative.  Returns true when it
+// stopped at the end of the slice or at an element the lane-parallel path does not take: a length of more than two added bytes, an element that
+// does not end inside the slice -- literals behind `lim`, or a match with nothing behind it (the stream's end is decided one element at a time).
+// first: the slice begins at stream position 0.
+__device__ __forceinline__ bool bz_fill(const uint8_t *s_in, const uint32_t sh, const uint32_t lim, const bool first, uint32_t &si, uint32_t &nq,
+                                        uint2 *s_tq, const int lane) {
+    bool stop = false;
+    while (nq < 64u && !stop) {
+        if (si >= lim) { stop = true; break; }
+        const uint32_t base = si, p = base + (uint32_t)lane;
+        const uint64_t w = (uint64_t)dec_read4(s_in, sh + p) | ((uint64_t)dec_read4(s_in, sh + p + 4u) << 32);
+        uint32_t c = (uint32_t)w & 255u;
+        if (first && p == 0u) c &= 31u;
+        bool cplx = p >= lim;
+        uint32_t lit = 0, mlen = 0, dist = 0, nxt;
+        if (c < 32u) { lit = c + 1u; nxt = p + 1u + lit; if (nxt > lim) cplx = true; }
+        else {
+            uint32_t len = (c >> 5) - 1u, k = 1u;
+            const uint32_t ofs = (c & 31u) << 8;
+            if (len == 6u) {
+                const uint32_t e1 = (uint32_t)(w >> 8) & 255u;
+                len += e1; k = 2u;
+                if (e1 == 255u) { const uint32_t e2 = (uint32_t)(w >> 16) & 255u; len += e2; k = 3u; if (e2 == 255u) cplx = true; }
+            }
+            const uint32_t code = (uint32_t)(w >> (8u * k)) & 255u;
+            k++;
+            dist = ofs + code;
+            if (code == 255u && ofs == (31u << 8)) { dist = (((uint32_t)(w >> (8u * k)) & 255u) << 8) + ((uint32_t)(w >> (8u * k + 8u)) & 255u) + 8191u; k += 2u; }
+            dist += 1u; mlen = len + 3u; nxt = p + k;                  // (k <= 6: all of it lies in the eight bytes)
+            if (nxt >= lim) cplx = true;
+        }
+        const unsigned long long cmask = hb_ballot(cplx);
+        unsigned long long tmask = 0;
+        const uint32_t nrel = cplx ? 64u : nxt - base;
+        const uint32_t succ = nrel < 64u ? nrel : (uint32_t)lane;
+        const uint32_t cur = dec_walk(succ, nrel, base, cmask, tmask, stop);
+        const uint32_t rank = wave_rank(tmask);
+        if ((tmask >> lane) & 1ull) { uint2 e; e.x = p | (lit << 13) | (mlen << 19); e.y = dist; s_tq[nq + rank] = e; }
+        nq += (uint32_t)__builtin_popcountll(tmask);
+        si = cur;
+    }
+    return stop;
+}
+
+// The element chain [start, exitp) of a BloscLZ stream for a decoder, with sn_walk's contract and callbacks: an element is a token with literals
+// and no match (mlen == 0; `off` is 1 then) or with a match and no literals.  `off` is a full 32-bit value all the way: a distance does not fit
+// 16 bits.  What bz_fill does not take comes through `single`, parsed with every byte checked against the end of the stream; false when the
+// stream is not one the library decodes (a literal run or a match header that runs off the input, a match at the very end).
+template <uint32_t PWIN = RG_PWIN, class Batch, class Single>
+__device__ __forceinline__ bool bz_walk(const uint8_t *__restrict__ src, const uint64_t n_src, const uint32_t start, const uint32_t exitp,
+                                        uint8_t *s_win /* PWIN + 128 */, uint2 *s_tq /* DTQ */, const int lane, Batch &&batch, Single &&single) {
+    if (n_src > 0x7FFFFFFFull) return false;                             // (a stream's size field is an int32: positions are 32-bit here)
+    const uint32_t n = (uint32_t)n_src;
+    uint32_t si = start, wpos = 0, wlen = 0, wsh = 0, nq = 0;
+    auto refill = [&](uint32_t at) __attribute__((always_inline)) {
+        const uint8_t *g = src + at;
+        wsh = (uint32_t)((uintptr_t)g & 15u);
+        const uint32_t left = n - at;
+        wlen = left < PWIN - 16u ? left : PWIN - 16u;
+        const u32x4 *ga = (const u32x4 *)(g - wsh);
+        const uint32_t nv = (wsh + wlen + 15u) >> 4;
+        wave_sync();
+        for (uint32_t i = lane; i < nv; i += 64) ((u32x4 *)s_win)[i] = ga[i];
+        wpos = at;
+        wave_sync();
+    };
+    auto drain = [&](const bool all) __attribute__((always_inline)) -> bool {
+        while (nq >= 64u || (all && nq > 0u)) {
+            const uint32_t cntb = nq < 64u ? nq : 64u;
+            const uint2 e = s_tq[lane];                                    // {pos | lit << 13 | mlen << 19, distance}, window-relative (bz_fill)
+            const uint32_t tw = e.x & 0x1FFFu, lit = (e.x >> 13) & 63u, mlen = e.x >> 19;
+            const uint32_t off = mlen ? e.y : 1u;
+            const uint2 rest = dec_queue_rest(s_tq, lane);
+            if (!batch(cntb, wpos + tw, wpos + tw + 1u, lit, mlen, off, wsh + tw + 1u)) return false;
+            dec_queue_shift(s_tq, nq, cntb, rest, lane);
+        }
+        return true;
+    };
+    // stream byte q < n, wave-uniform: from the staged window where it holds it
+    auto sbyte = [&](uint32_t q) __attribute__((always_inline)) -> uint32_t {
+        return RFL((q >= wpos && q - wpos < wlen) ? (uint32_t)s_win[wsh + (q - wpos)] : (uint32_t)src[q]);
+    };
+    wave_sync();
+    while (si < exitp) {
+        if (si < wpos || si - wpos + PWIN / 4u > wlen) { if (si != wpos || wlen == 0) { if (!drain(true)) return false; refill(si); } }
+        uint32_t rel = si - wpos;
+        const uint32_t tolim = exitp - wpos;
+        const uint32_t lim = tolim < wlen ? tolim : wlen;
+        const bool stop = bz_fill(s_win, wsh, lim, wpos == 0u, rel, nq, s_tq, lane);
+        if (!drain(false)) return false;
+        const bool moved = (wpos + rel) != si;
+        si = wpos + rel;
+        if (moved && !stop) continue;
+        if (!drain(true)) return false;
+        if (si >= exitp) break;
+        if (moved && si - wpos + PWIN / 4u > wlen && wpos + wlen < n && wpos + wlen < exitp) continue;
+        // ---- one element the slow way: a length of any size, the end of the stream ----
+        uint32_t q = si;
+        uint32_t c = sbyte(q);
+        q++;
+        if (si == 0u) c &= 31u;
+        uint32_t lit = 0, len = 0, dist = 0;
+        if (c < 32u) {
+            lit = c + 1u;
+            if (lit > n - q) return false;
+        } else {
+            len = (c >> 5) - 1u;
+            const uint32_t ofs = (c & 31u) << 8;
+            if (len == 6u) {
+                // the added bytes, 64 per step: the first that is not 255 ends them (a byte behind the stream counts as such, and is found out below)
+                for (;;) {
+                    const uint32_t a = q + (uint32_t)lane;
+                    const uint32_t b = a < n ? (uint32_t)src[a] : 0u;
+                    const unsigned long long m = hb_ballot(b != 255u);
+                    if (!m) {                                              // 64 more of 255 (all inside the stream)
+                        if (len > 0x7FFFFFFFu - 255u * 64u) return false;  // (longer than any stream's output, and `len` never wraps)
+                        len += 255u * 64u; q += 64u;
+                        continue;
+                    }
+                    const int k = __builtin_ctzll(m);
+                    len += 255u * (uint32_t)k + (uint32_t)__builtin_amdgcn_readlane((int)b, k);
+                    q += (uint32_t)k + 1u;
+                    break;
+                }
+            }
+            if (q >= n || n - q < 2u) return false;                      // the distance byte and one more: a match is never the last thing
+            const uint32_t code = sbyte(q);
+            q++;
+            dist = ofs + code;
+            if (code == 255u && ofs == (31u << 8)) {
+                if (n - q < 2u) return false;
+                dist = (sbyte(q) << 8) + sbyte(q + 1u) + 8191u;
+                q += 2u;
+                if (q >= n) return false;
+            }
+            len += 3u;
+        }
+        if (!single(si, q, lit, len, dist + 1u, 0u)) return false;
+        si = q + lit;
+    }
+    return drain(true);
+}
+
 // the chain of a Snappy block (hb_lz4_region.hip): regions, parses, beliefs, verification -- RgPlan.ok / RgRegion.{entry, exit, opos} as for LZ4.
 // w: rg_layout(cap).total bytes; entry0: device pointer to the stream position of the first element (SnPlan.hdr)
 int hb_launch_snappy_region_chain(const uint8_t *src, size_t n, size_t cap, uint8_t *w, const uint32_t *entry0, hipStream_t s);

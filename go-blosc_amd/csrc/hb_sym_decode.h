@@ -498,6 +498,8 @@ __device__ __forceinline__ bool sy_decode_unit(const uint8_t *__restrict__ src, 
         }
         if constexpr (CODEC == RG_SNAPPY) {                            // elements instead of sequences (sn_walk, hb_lz4_region.h); nothing ever parks
             if (ok && !parked) ok = sn_walk<PWIN>(src, n_src, walk_from, exitp, s_win, s_tq, lane, batch, single);
+        } else if constexpr (CODEC == RG_BLOSCLZ) {                    // the elements of a BloscLZ stream (bz_walk): distances of up to 17 bits; nothing ever parks
+            if (ok && !parked) ok = bz_walk<PWIN>(src, n_src, walk_from, exitp, s_win, s_tq, lane, batch, single);
         } else if constexpr (!TOK) {
             if (ok && !parked) ok = rg_walk<PWIN>(src, n_src, walk_from, exitp, s_win, s_tq, lane, batch, single);
         } else {

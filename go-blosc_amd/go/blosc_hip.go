@@ -568,7 +568,20 @@ func CompressCBlosc(data []byte, shuffle Shuffle, typeSize int) ([]byte, error) 
 	return buf[:n], nil
 }
 
-// DecompressCBlosc reads a C-Blosc-1 frame with LZ4 / LZ4HC streams (or a memcpyed one); other codec formats: ErrInvalidCodec.
+// CBloscAcceptCodecs says which C-Blosc-1 codec formats DecompressCBlosc, CBloscDecompressBatchHIP and CBloscGetItemBatchHIP decode
+// (hb_cblosc_accept_codecs): bit k = codec format k.  0x2 (LZ4 / LZ4HC) is the default, 0x3 adds BloscLZ -- what blosc_compress() and
+// python-blosc write unless told otherwise; any other mask is refused and changes nothing.  Process-wide and safe to call from any
+// goroutine; returns the previous mask.  Opt-in because ErrInvalidCodec for a BloscLZ frame is an answer a caller may route on.
+func CBloscAcceptCodecs(mask uint) (uint, error) {
+	rc := C.hb_cblosc_accept_codecs(C.uint(mask))
+	if rc < 0 {
+		return 0, hbError(C.int64_t(rc))
+	}
+	return uint(rc), nil
+}
+
+// DecompressCBlosc reads a C-Blosc-1 frame with LZ4 / LZ4HC streams (or a memcpyed one), and BloscLZ streams once CBloscAcceptCodecs(0x3)
+// has been called; other codec formats: ErrInvalidCodec.
 func DecompressCBlosc(frame []byte) ([]byte, error) {
 	if !useHIP {
 		return nil, fmt.Errorf("%w: no HIP device", ErrDecompressionFailed)

@@ -104,6 +104,7 @@ EXPORTS = [
     "hb_cblosc_decompress_frames_batch_workspace", "hb_cblosc_decompress_frames_batch_device", "hb_cblosc_decompress_frames_batch",
     "hb_cblosc_compress_frames_batch_workspace", "hb_cblosc_compress_frames_batch_device", "hb_cblosc_compress_frames_batch",
     "hb_cblosc_getitem_frames_batch_workspace", "hb_cblosc_getitem_frames_batch_device", "hb_cblosc_getitem_frames_batch",
+    "hb_cblosc_accept_codecs",
     "hb_queue_create", "hb_queue_create_ex", "hb_queue_destroy", "hb_queue_compress", "hb_queue_decompress", "hb_queue_wait",
 ]
 
@@ -197,6 +198,7 @@ def lib():
             "hb_cblosc_getitem_frames_batch_workspace": (sz, [i32, vp, vp, i32, vp]),
             "hb_cblosc_getitem_frames_batch_device": (i32, [i32, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp, vp]),
             "hb_cblosc_getitem_frames_batch": (i32, [i32, vp, vp, i32, vp, vp, vp, vp, i32]),
+            "hb_cblosc_accept_codecs": (i32, [ctypes.c_uint]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -539,6 +541,12 @@ def CBloscParseHeader(frame):
     h = CBloscHeader()
     _check(lib().hb_cblosc_parse_header(p, n, ctypes.byref(h)))
     return h
+
+
+def CBloscAcceptCodecs(mask):
+    """Which C-Blosc-1 codec formats the CBlosc* calls decode (include/hipblosc.h hb_cblosc_accept_codecs): 0x2 = LZ4 / LZ4HC (the default),
+    0x3 adds BloscLZ.  Process-wide; returns the previous mask."""
+    return _check(lib().hb_cblosc_accept_codecs(int(mask)))
 
 
 def CBloscDecompress(frame):

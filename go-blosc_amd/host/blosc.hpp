@@ -151,6 +151,9 @@ inline std::vector<Bytes> GetItemBatch(const std::vector<Bytes> &frames, const s
     for (size_t j = 0; j < nj; j++) out[j].resize(rc[j] > 0 ? (size_t)rc[j] : 0);
     return out;
 }
+// which C-Blosc-1 codec formats the CBlosc* calls decode (hb_cblosc_accept_codecs): 0x2 = LZ4 / LZ4HC (the default), 0x3 adds BloscLZ; process-wide;
+// returns the previous mask, throws for any other mask
+inline unsigned CBloscAcceptCodecs(unsigned mask) { return (unsigned)check(hb_cblosc_accept_codecs(mask)); }
 // many C-Blosc-1 frames through one set of launches (hb_cblosc_decompress_frames_batch): out[k] is what hb_cblosc_decompress gives for frames[k],
 // rc[k] the byte count or its HB_ERR_* code (nothing is thrown per frame)
 inline std::vector<Bytes> CBloscDecompressBatch(const std::vector<Bytes> &frames, std::vector<int64_t> &rc, int device = 0) {
