@@ -21,6 +21,7 @@
 #include "hb_cblosc_batch.h"
 #include "hb_cblosc_enc_batch.h"
 #include "hb_cblosc_getitem_batch.h"
+#include "hb_cblosc_box_batch.h"
 #include <vector>
 #include <algorithm>
 #include <cstring>
@@ -702,6 +703,60 @@ int hb_cblosc_getitem_frames_batch(int nframes, const void *const *frame, const 
         rc[j] = (int64_t)r.bytes;
     }
     return HB_OK;
+}
+
+// Many boxes of many C-Blosc-1 frames (include/hipblosc.h).  cbx_host_plan (hb_cblosc_box_batch.h) answers what the host refuses and says which
+// jobs the batch carries, which frames go up and where each box lies, C-contiguous, in the packed device buffer: every frame a carried job
+// reads goes up once, the device form runs once over the carried jobs, the records come down in one copy and the packed boxes in one copy, and
+// the rows are placed at their strides here.  No job is answered row by row.
+static int cbx_host_call(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_cblosc_box_job *jobs, void *const *dst, const size_t *cap,
+                                  int64_t *rc, int device) {
+    if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
+    if (njobs == 0) return HB_OK;
+    if (!frame || !n || !jobs || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
+    for (int j = 0; j < njobs; j++)
+        if (jobs[j].frame >= (uint32_t)nframes) return HB_ERR_BAD_ARG;
+    CbxHostPlan P;
+    cbx_host_plan(nframes, frame, n, njobs, jobs, dst, cap, P, hb_cblosc_accepted());
+    for (int j = 0; j < njobs; j++) rc[j] = P.status[(size_t)j];
+    const int m = (int)P.carried.size();
+    if (m == 0) return HB_OK;
+    auto all = [&](int64_t st) { for (int j : P.carried) rc[j] = st; return HB_OK; };
+    const int sel = hb_select_device(device);
+    if (sel != HB_OK) return all(sel);
+    const size_t wb = hb_cblosc_getbox_frames_batch_workspace(nframes, P.hd.data(), n, m, P.pj.data());
+    if (!wb) return all(HB_ERR_BAD_ARG);                                // (a batch beyond the 32-bit limits: the caller has to split it)
+    Scratch sc(device);
+    uint8_t *d_in = sc.get(P.in_bytes + 256), *d_out = sc.get(P.out_bytes + 256), *d_work = sc.get(wb), *d_res = sc.get((size_t)m * sizeof(hb_result));
+    if (!d_in || !d_out || !d_work || !d_res) return all(HB_ERR_HIP);
+    if (P.span_in && hipMemcpyAsync(d_in, frame[P.idx[0]], P.in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return all(HB_ERR_HIP);
+    std::vector<const void *> pf((size_t)nframes, nullptr);
+    for (int k : P.idx) {
+        pf[(size_t)k] = d_in + P.ioff[(size_t)k];
+        if (!P.span_in && hipMemcpyAsync(d_in + P.ioff[(size_t)k], frame[k], n[k], hipMemcpyHostToDevice, nullptr) != hipSuccess) return all(HB_ERR_HIP);
+    }
+    std::vector<void *> pd((size_t)m);
+    for (int i = 0; i < m; i++) pd[(size_t)i] = d_out + P.ooff[(size_t)i];
+    const int st = hb_cblosc_getbox_frames_batch_device(nframes, P.hd.data(), pf.data(), n, m, P.pj.data(), pd.data(), P.caps.data(), d_work, wb, (hb_result *)d_res, nullptr);
+    if (st) return all(st);
+    std::vector<hb_result> res((size_t)m);
+    if (hipMemcpy(res.data(), d_res, (size_t)m * sizeof(hb_result), hipMemcpyDeviceToHost) != hipSuccess) return all(HB_ERR_HIP);
+    std::vector<uint8_t> host(P.out_bytes);
+    if (P.out_bytes && hipMemcpy(host.data(), d_out, P.out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return all(HB_ERR_HIP);
+    for (int i = 0; i < m; i++) {
+        const hb_result &r = res[(size_t)i];
+        const int j = P.carried[(size_t)i];
+        if (r.status != HB_OK) { rc[j] = r.status; continue; }          // (a failed job's destination keeps the caller's bytes)
+        if (r.bytes) cbx_place_rows(P.geom[(size_t)i], host.data() + P.ooff[(size_t)i], (uint8_t *)dst[j]);
+        rc[j] = (int64_t)r.bytes;
+    }
+    return HB_OK;
+}
+// (host tables that do not fit into memory: the batch is one the caller has to split, as for cbx_prepare -- no exception crosses the C ABI)
+int hb_cblosc_getbox_frames_batch(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_cblosc_box_job *jobs, void *const *dst, const size_t *cap,
+                                  int64_t *rc, int device) {
+    try { return cbx_host_call(nframes, frame, n, njobs, jobs, dst, cap, rc, device); }
+    catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
 }
 
 // Many inputs to C-Blosc-1 frames (include/hipblosc.h).  cbe_host_plan (hb_cblosc_enc_batch.h) says which inputs the batch carries and where they

@@ -25,6 +25,7 @@
 #include "hb_cblosc_batch.h"       // the flags, cb_nsplit, CbStream / CbPlan, and the host side of the batch
 #include "hb_cblosc_enc_batch.h"   // the geometry of a written frame, and the host side of the batched encode
 #include "hb_cblosc_getitem_batch.h"   // the geometry of an item range, and the host side of the batched getitem
+#include "hb_cblosc_box_batch.h"       // the geometry of a box, the host side of the batched box reads, the gather's index arithmetic
 
 // ---- the streams of blocks [b0, b0 + nb) (hb_cblosc_getitem_device: the blocks that cover a range; the others' bstarts entries and streams
 // are never read); stream offsets count from the first of these blocks ----
@@ -551,13 +552,18 @@ __global__ __launch_bounds__(64) void k_cbg_decode_small(const CbgFrame *__restr
     }
 }
 
-// ---- the clipped un-filter: byte p of the frame's decoded bytes out of the staged blocks of job J (block `b_lo` is its first record).  The
-// plain body: the edges of every range, and every shape the wide bodies below leave alone. ----
-template <int KIND>
-__device__ __forceinline__ uint8_t cbg_byte(const CbgFrame &F, const CbgJob &J, const CbgBlock *__restrict__ blocks, const uint8_t *__restrict__ work, uint32_t b_lo, uint32_t p) {
+// ---- the clipped un-filter: byte p of the frame's decoded bytes out of the staged blocks.  `look(b)` is the record of block number b: the
+// ranges' jobs have consecutive records (CbgSeqLookup), the boxes' a list of the blocks they touch (CbxLookup).  The plain body: the edges of
+// every range, and every shape the wide bodies below leave alone. ----
+struct CbgSeqLookup {
+    const CbgBlock *__restrict__ first; uint32_t b_lo;                        // the job's first record and its block number
+    __device__ __forceinline__ const CbgBlock &operator()(uint32_t b) const { return first[b - b_lo]; }
+};
+template <int KIND, class LOOK>
+__device__ __forceinline__ uint8_t cbg_byte(const CbgFrame &F, const LOOK &look, const uint8_t *__restrict__ work, uint32_t p) {
     if (KIND == CBG_COPY && F.memcpyed) return F.frame[16u + (size_t)p];
     const uint32_t b = p / F.blocksize, q = p - b * F.blocksize;
-    const CbgBlock &K = blocks[J.blk0 + (b - b_lo)];
+    const CbgBlock &K = look(b);
     const uint8_t *s = work + K.stage_off;
     if (KIND == CBG_COPY) return s[q];
     const uint32_t ts = F.typesize, nel = K.bsize / ts;
@@ -597,30 +603,16 @@ __device__ __forceinline__ bool cbg_bitun_group(uint8_t *__restrict__ d, const u
     }
     return true;
 }
-// One launch per kind that occurs: gjob / gblk = the jobs of this kind and the prefix of their workgroup counts.  A thread has one unit of
-// cbg_unit_bytes() bytes, counted from the start of the FRAME (so that a unit does not straddle a block, a group or an item where the block
-// size allows it), clipped to the job's range: a whole unit of a fitting shape takes the wide body, everything else the plain one.  Nothing is
-// written outside [0, nitems * typesize) of the job's destination, and nothing at all when one of the job's blocks failed.
-template <int KIND>
-__global__ __launch_bounds__(256) void k_cbg_gather(const CbgFrame *__restrict__ frames, const CbgJob *__restrict__ jobs, const CbgBlock *__restrict__ blocks,
-                                                     const CbPlan *__restrict__ plans, const uint32_t *__restrict__ gjob, const uint32_t *__restrict__ gblk, uint32_t nkind,
-                                                     const uint8_t *__restrict__ work) {
-    const uint32_t i = hb_owner(gblk, nkind, blockIdx.x);
-    const CbgJob &J = jobs[gjob[i]];
-    const CbgFrame &F = frames[J.frame];
-    int bad = 0;
-    for (uint32_t k = threadIdx.x; k < J.nb; k += 256u) bad |= plans[J.blk0 + k].fail != 0u;
-    if (__syncthreads_or(bad)) return;
+// One gather unit: bytes [lo, hi) of the frame's decoded bytes to d.  A unit is cbg_unit_bytes() bytes counted from the start of the FRAME (so
+// that it does not straddle a block, a group or an item where the block size allows it), clipped to the range or the row it belongs to: a
+// whole unit of a fitting shape takes the wide body, everything else the plain one.  Destinations have any alignment.
+template <int KIND, class LOOK>
+__device__ __forceinline__ void cbg_unit(const CbgFrame &F, const LOOK &look, const uint8_t *__restrict__ work, uint32_t lo, uint32_t hi, uint8_t *__restrict__ d) {
     const uint32_t ts = F.typesize, bs = F.blocksize, U = cbg_unit_bytes(KIND, ts);
-    const uint64_t at = ((uint64_t)J.unit0 + (uint64_t)(blockIdx.x - gblk[i]) * 256u + threadIdx.x) * U, end = J.off + J.bytes;
-    if (at >= end) return;
-    const uint32_t lo = (uint32_t)(at > J.off ? at : J.off), hi = (uint32_t)(at + U < end ? at + U : end);      // (end <= nbytes < 2^32)
-    uint8_t *d = J.dst + (lo - J.off);
-    const uint32_t b_lo = (KIND == CBG_COPY && F.memcpyed) ? 0u : (uint32_t)(J.off / bs);
     if (hi - lo == U) {                                                        // a whole unit
         if (KIND == CBG_COPY && F.memcpyed) { st16u(d, ld16u(F.frame + 16u + (size_t)lo)); return; }
         const uint32_t b = lo / bs, q = lo - b * bs;
-        const CbgBlock &K = blocks[J.blk0 + (b - b_lo)];
+        const CbgBlock &K = look(b);
         const uint8_t *s = work + K.stage_off;
         if (KIND == CBG_COPY) {
             if (q + 16u <= K.bsize) { st16u(d, ld16u(s + q)); return; }
@@ -641,12 +633,32 @@ __global__ __launch_bounds__(256) void k_cbg_gather(const CbgFrame *__restrict__
             if (q + 128u <= K.bsize) {
                 for (uint32_t g = 0; g < 4u; g++)
                     if (!cbg_bitun_group(d + 32u * g, s, K.bsize, 4u, q + 32u * g))
-                        for (uint32_t k = 0; k < 32u; k++) d[32u * g + k] = cbg_byte<KIND>(F, J, blocks, work, b_lo, lo + 32u * g + k);
+                        for (uint32_t k = 0; k < 32u; k++) d[32u * g + k] = cbg_byte<KIND>(F, look, work, lo + 32u * g + k);
                 return;
             }
         }
     }
-    for (uint32_t p = lo; p < hi; p++) d[p - lo] = cbg_byte<KIND>(F, J, blocks, work, b_lo, p);
+    for (uint32_t p = lo; p < hi; p++) d[p - lo] = cbg_byte<KIND>(F, look, work, p);
+}
+// One launch per kind that occurs: gjob / gblk = the jobs of this kind and the prefix of their workgroup counts.  A thread has one unit
+// (cbg_unit) clipped to the job's range.  Nothing is written outside [0, nitems * typesize) of the job's destination, and nothing at all when
+// one of the job's blocks failed.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_cbg_gather(const CbgFrame *__restrict__ frames, const CbgJob *__restrict__ jobs, const CbgBlock *__restrict__ blocks,
+                                                     const CbPlan *__restrict__ plans, const uint32_t *__restrict__ gjob, const uint32_t *__restrict__ gblk, uint32_t nkind,
+                                                     const uint8_t *__restrict__ work) {
+    const uint32_t i = hb_owner(gblk, nkind, blockIdx.x);
+    const CbgJob &J = jobs[gjob[i]];
+    const CbgFrame &F = frames[J.frame];
+    int bad = 0;
+    for (uint32_t k = threadIdx.x; k < J.nb; k += 256u) bad |= plans[J.blk0 + k].fail != 0u;
+    if (__syncthreads_or(bad)) return;
+    const uint32_t U = cbg_unit_bytes(KIND, F.typesize);
+    const uint64_t at = ((uint64_t)J.unit0 + (uint64_t)(blockIdx.x - gblk[i]) * 256u + threadIdx.x) * U, end = J.off + J.bytes;
+    if (at >= end) return;
+    const uint32_t lo = (uint32_t)(at > J.off ? at : J.off), hi = (uint32_t)(at + U < end ? at + U : end);      // (end <= nbytes < 2^32)
+    const CbgSeqLookup look{blocks + J.blk0, (KIND == CBG_COPY && F.memcpyed) ? 0u : (uint32_t)(J.off / F.blocksize)};
+    cbg_unit<KIND>(F, look, work, lo, hi, J.dst + (lo - J.off));
 }
 
 // one thread per job: what the host decided, or k_cb_result's record from the OR of the fail words of the job's blocks
@@ -658,6 +670,45 @@ __global__ __launch_bounds__(64) void k_cbg_finish(const CbgJob *__restrict__ jo
     if (J.status) { r->status = J.status; r->flags = 0; r->bytes = 0; r->total_bytes = 0; r->reserved = 0; return; }
     CbPlan p; p.fail = 0u;
     for (uint32_t k = 0; k < J.nb; k++) p.fail |= plans[J.blk0 + k].fail;
+    cb_result(&p, r, J.bytes);
+}
+
+// ---- batched box reads (hb_cblosc_getbox_frames_batch_device; the host side and the index arithmetic are hb_cblosc_box_batch.h).  The plan and
+// the decoders above run over the distinct block records as they are; the gather walks a job's rows by arithmetic. ----
+struct CbxLookup {
+    const CbgBlock *__restrict__ blocks; const CbxTouch *__restrict__ tl; uint32_t ntl, b_lo, dense;      // the job's touch list
+    __device__ __forceinline__ const CbgBlock &operator()(uint32_t b) const { return blocks[tl[cbx_find(tl, ntl, b_lo, dense, b)].rec]; }
+};
+// One launch per kind that occurs, over a workgroup prefix per job.  A job's thread space is rows x units per row (cbx_thread: whole rows to a
+// workgroup where rows are short, several workgroups to a row where they are long; the divisions are multiplications by reciprocals the host
+// put into the record).  Every workgroup first ORs the fail words of the blocks the job touches and writes nothing if one is set.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_cbx_gather(const CbgFrame *__restrict__ frames, const CbxJob *__restrict__ jobs, const CbgBlock *__restrict__ blocks,
+                                                     const CbPlan *__restrict__ plans, const CbxTouch *__restrict__ touch, const uint32_t *__restrict__ gjob,
+                                                     const uint32_t *__restrict__ gblk, uint32_t nkind, const uint8_t *__restrict__ work) {
+    const uint32_t i = hb_owner(gblk, nkind, blockIdx.x);
+    const CbxJob &J = jobs[gjob[i]];
+    const CbgFrame &F = frames[J.frame];
+    const CbxTouch *tl = touch + J.tl0;
+    int bad = 0;
+    for (uint32_t k = threadIdx.x; k < J.ntl; k += 256u) bad |= plans[tl[k].rec].fail != 0u;
+    if (__syncthreads_or(bad)) return;
+    uint32_t lo, hi;
+    uint64_t doff;
+    if (!cbx_thread(J, cbg_unit_bytes(KIND, F.typesize), blockIdx.x - gblk[i], threadIdx.x, lo, hi, doff)) return;
+    const CbxLookup look{blocks, tl, J.ntl, J.b_lo, J.dense};
+    cbg_unit<KIND>(F, look, work, lo, hi, J.dst + doff);
+}
+// one thread per job: what the host decided, or k_cb_result's record from the OR of the fail words of the blocks the job touches
+__global__ __launch_bounds__(64) void k_cbx_finish(const CbxJob *__restrict__ jobs, const CbPlan *__restrict__ plans, const CbxTouch *__restrict__ touch, hb_result *results,
+                                                    uint32_t njobs) {
+    const uint32_t j = blockIdx.x * 64u + threadIdx.x;
+    if (j >= njobs) return;
+    const CbxJob &J = jobs[j];
+    hb_result *r = results + j;
+    if (J.status) { r->status = J.status; r->flags = 0; r->bytes = 0; r->total_bytes = 0; r->reserved = 0; return; }
+    CbPlan p; p.fail = 0u;
+    for (uint32_t k = 0; k < J.ntl; k++) p.fail |= plans[touch[J.tl0 + k].rec].fail;
     cb_result(&p, r, J.bytes);
 }
 
@@ -1197,6 +1248,42 @@ int hb_cblosc_getitem_device(const hb_cblosc_header *hdr, const void *d_frame, s
     return HB_OK;
 }
 
+// The plan and the stream decoders over the block records of a batch (hb_cblosc_getitem_frames_batch_device and hb_cblosc_getbox_frames_batch_device
+// build the same records): k_cbg_plan, then one decoder launch per kind that occurs.
+static void cbg_launch_decoders(uint32_t nblk, uint32_t nstreams, uint32_t any_small, uint32_t nsplit_all, uint32_t any_lz4, uint32_t any_blz, const CbgFrame *d_frames,
+                                const CbgBlock *d_blocks, CbPlan *d_plans, const uint32_t *d_str0, CbStream *d_streams, uint8_t *w, hipStream_t s) {
+    hb_prof_begin("k_cbg_plan", s);
+    hipLaunchKernelGGL(k_cbg_plan, dim3((nblk + 63u) / 64u), dim3(64), 0, s, d_frames, d_blocks, d_plans, nblk, d_streams);
+    hb_prof_end(s);
+    const uint32_t mgrp = (nstreams + 7u) / 8u;
+    uint32_t P = mgrp / 4u + 1u;                                    // coprime to the groups of 8 streams, about a quarter turn (cb_launch_blocks)
+    for (;; P++) { uint32_t x = P, y = mgrp; while (y) { const uint32_t t = x % y; x = y; y = t; } if (x == 1u) break; }
+    const unsigned grid = mgrp * 8u < 65536u ? mgrp * 8u : 65536u;
+    unsigned gsplit = grid;                                         // several passes per workgroup where all frames split alike, as in the batched decode
+    if (nsplit_all > 1u) {
+        unsigned p = nsplit_all;
+        while (p > 1u && mgrp * 8u / p < 2048u) p >>= 1;
+        gsplit = (mgrp * 8u / p + 7u) / 8u * 8u;
+        if (gsplit > 65536u) gsplit = 65536u;
+    }
+    if (any_small) {
+        hb_prof_begin("k_cbg_decode_small", s);
+        hipLaunchKernelGGL(k_cbg_decode_small, dim3(grid), dim3(64), 0, s, d_frames, d_blocks, d_plans, d_str0, nblk, (const CbStream *)d_streams, nstreams, w, P);
+        hb_prof_end(s);
+    }
+    if (any_lz4) {                                                  // (any block can have stored streams: the general decoder runs next to the small one)
+        hb_prof_begin("k_cbg_decode", s);
+        hipLaunchKernelGGL(k_cbg_decode, dim3(any_small ? grid : gsplit), dim3(64), 0, s, d_frames, d_blocks, d_plans, d_str0, nblk, (const CbStream *)d_streams, nstreams, w,
+                           (int)any_small, P);
+        hb_prof_end(s);
+    }
+    if (any_blz) {                                                  // (the covered blocks of BloscLZ frames, stored streams included)
+        hb_prof_begin("k_cbg_decode_blz", s);
+        hipLaunchKernelGGL(k_cbg_decode_blz, dim3(gsplit), dim3(64), 0, s, d_frames, d_blocks, d_plans, d_str0, nblk, (const CbStream *)d_streams, nstreams, w, P);
+        hb_prof_end(s);
+    }
+}
+
 // ---- many ranges of many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_getitem_batch.h) ----
 size_t hb_cblosc_getitem_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n, int njobs, const hb_getitem_job *jobs) {
     return cbg_workspace(nframes, hdrs, n, njobs, jobs, hb_cblosc_accepted());
@@ -1237,46 +1324,8 @@ int hb_cblosc_getitem_frames_batch_device(int nframes, const hb_cblosc_header *h
     CbPlan *d_plans = (CbPlan *)(w + L.plans);
     const uint32_t *d_str0 = (const uint32_t *)(w + L.str0), *d_gjob = (const uint32_t *)(w + L.gjob), *d_gblk = (const uint32_t *)(w + L.gblk);
     CbStream *d_streams = (CbStream *)(w + L.streams);
-    if (B.nstreams) {
-        const uint32_t nblk = (uint32_t)B.nblk, nstreams = (uint32_t)B.nstreams;
-        hb_prof_begin("k_cbg_plan", s);
-        hipLaunchKernelGGL(k_cbg_plan, dim3((nblk + 63u) / 64u), dim3(64), 0, s, d_frames, d_blocks, d_plans, nblk, d_streams);
-        hb_prof_end(s);
-        const uint32_t mgrp = (nstreams + 7u) / 8u;
-        uint32_t P = mgrp / 4u + 1u;                                    // coprime to the groups of 8 streams, about a quarter turn (cb_launch_blocks)
-        for (;; P++) { uint32_t x = P, y = mgrp; while (y) { const uint32_t t = x % y; x = y; y = t; } if (x == 1u) break; }
-        const unsigned grid = mgrp * 8u < 65536u ? mgrp * 8u : 65536u;
-        if (B.any_small) {
-            hb_prof_begin("k_cbg_decode_small", s);
-            hipLaunchKernelGGL(k_cbg_decode_small, dim3(grid), dim3(64), 0, s, d_frames, d_blocks, d_plans, d_str0, nblk, (const CbStream *)d_streams, nstreams, w, P);
-            hb_prof_end(s);
-        }
-        // (any block can have stored streams: the general decoder always runs; its passes per workgroup as in the batched decode)
-        unsigned gbig = grid;
-        if (!B.any_small && B.nsplit_all > 1u) {
-            unsigned p = B.nsplit_all;
-            while (p > 1u && mgrp * 8u / p < 2048u) p >>= 1;
-            gbig = (mgrp * 8u / p + 7u) / 8u * 8u;
-            if (gbig > 65536u) gbig = 65536u;
-        }
-        if (B.any_lz4) {
-            hb_prof_begin("k_cbg_decode", s);
-            hipLaunchKernelGGL(k_cbg_decode, dim3(gbig), dim3(64), 0, s, d_frames, d_blocks, d_plans, d_str0, nblk, (const CbStream *)d_streams, nstreams, w, (int)B.any_small, P);
-            hb_prof_end(s);
-        }
-        if (B.any_blz) {                                                // (the covered blocks of BloscLZ frames, stored streams included)
-            unsigned gblz = grid;
-            if (B.nsplit_all > 1u) {
-                unsigned p = B.nsplit_all;
-                while (p > 1u && mgrp * 8u / p < 2048u) p >>= 1;
-                gblz = (mgrp * 8u / p + 7u) / 8u * 8u;
-                if (gblz > 65536u) gblz = 65536u;
-            }
-            hb_prof_begin("k_cbg_decode_blz", s);
-            hipLaunchKernelGGL(k_cbg_decode_blz, dim3(gblz), dim3(64), 0, s, d_frames, d_blocks, d_plans, d_str0, nblk, (const CbStream *)d_streams, nstreams, w, P);
-            hb_prof_end(s);
-        }
-    }
+    if (B.nstreams)
+        cbg_launch_decoders((uint32_t)B.nblk, (uint32_t)B.nstreams, B.any_small, B.nsplit_all, B.any_lz4, B.any_blz, d_frames, d_blocks, d_plans, d_str0, d_streams, w, s);
     static const char *const gname[CBG_COUNT] = {"k_cbg_gather_copy", "k_cbg_gather_unshuffle", "k_cbg_gather_bitun", "k_cbg_gather_bitun4"};
     for (int k = 0; k < CBG_COUNT; k++) {
         const uint32_t k0 = B.kind0[k], nk = B.kind0[k + 1] - k0, blocks = B.kblocks[k];
@@ -1294,6 +1343,72 @@ int hb_cblosc_getitem_frames_batch_device(int nframes, const hb_cblosc_header *h
     }
     hb_prof_begin("k_cbg_finish", s);
     hipLaunchKernelGGL(k_cbg_finish, dim3((unsigned)((nj + 63) / 64)), dim3(64), 0, s, d_jobs, (const CbPlan *)d_plans, d_results, (uint32_t)njobs);
+    hb_prof_end(s);
+    HB_HIP_TRY(hipGetLastError());
+    return HB_OK;
+}
+
+// ---- many boxes of many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_box_batch.h) ----
+size_t hb_cblosc_getbox_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n, int njobs, const hb_cblosc_box_job *jobs) {
+    return cbx_workspace(nframes, hdrs, n, njobs, jobs, hb_cblosc_accepted());
+}
+
+int hb_cblosc_getbox_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_cblosc_box_job *jobs,
+                                         void *const *d_dst, const size_t *cap, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
+    if (njobs == 0) return HB_OK;
+    if (!hdrs || !d_frame || !n || !jobs || !d_dst || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
+    CbxBatch B;
+    const unsigned accept = hb_cblosc_accepted();
+    const int rc = cbx_prepare(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, true, B, accept);
+    if (rc) return rc;
+    const CbxLayout &L = B.L;
+    // (the query knows no capacities and no pointers: where a job was refused for one of them it has counted blocks that this batch leaves out)
+    if (work_bytes < (B.ptr_refusals ? cbx_workspace(nframes, hdrs, n, njobs, jobs, accept) : L.total)) return HB_ERR_SHORT_BUFFER;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    uint8_t *w = (uint8_t *)d_work;
+    const size_t nf = (size_t)nframes, nj = (size_t)njobs, nb = (size_t)B.nblk;
+    // the records, the touch lists, the prefixes and the cleared plans go up in one copy (the buffer is read before the call returns)
+    std::vector<uint8_t> up(L.upload, 0);
+    memcpy(up.data() + L.frames, B.frames.data(), nf * sizeof(CbgFrame));
+    memcpy(up.data() + L.jobs, B.jobs.data(), nj * sizeof(CbxJob));
+    if (nb) {
+        memcpy(up.data() + L.blocks, B.blocks.data(), nb * sizeof(CbgBlock));
+        memcpy(up.data() + L.str0, B.str0.data(), nb * 4);
+        memcpy(up.data() + L.touch, B.touch.data(), B.touch.size() * sizeof(CbxTouch));
+    }
+    memcpy(up.data() + L.gjob, B.gjob.data(), nj * 4);
+    memcpy(up.data() + L.gblk, B.gblk.data(), nj * 4);
+    hb_prof_begin("cbx_upload", s);
+    HB_HIP_TRY(hipMemcpyAsync(w, up.data(), L.upload, hipMemcpyHostToDevice, s));
+    hb_prof_end(s);
+    const CbgFrame *d_frames = (const CbgFrame *)(w + L.frames);
+    const CbxJob *d_jobs = (const CbxJob *)(w + L.jobs);
+    const CbgBlock *d_blocks = (const CbgBlock *)(w + L.blocks);
+    CbPlan *d_plans = (CbPlan *)(w + L.plans);
+    const CbxTouch *d_touch = (const CbxTouch *)(w + L.touch);
+    const uint32_t *d_str0 = (const uint32_t *)(w + L.str0), *d_gjob = (const uint32_t *)(w + L.gjob), *d_gblk = (const uint32_t *)(w + L.gblk);
+    CbStream *d_streams = (CbStream *)(w + L.streams);
+    if (B.nstreams)
+        cbg_launch_decoders((uint32_t)B.nblk, (uint32_t)B.nstreams, B.any_small, B.nsplit_all, B.any_lz4, B.any_blz, d_frames, d_blocks, d_plans, d_str0, d_streams, w, s);
+    static const char *const gname[CBG_COUNT] = {"k_cbx_gather_copy", "k_cbx_gather_unshuffle", "k_cbx_gather_bitun", "k_cbx_gather_bitun4"};
+    for (int k = 0; k < CBG_COUNT; k++) {
+        const uint32_t k0 = B.kind0[k], nk = B.kind0[k + 1] - k0, blocks = B.kblocks[k];
+        if (!nk) continue;
+        hb_prof_begin(gname[k], s);
+#define CBX_LAUNCH(K) hipLaunchKernelGGL(k_cbx_gather<K>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_blocks, (const CbPlan *)d_plans, d_touch, d_gjob + k0, d_gblk + k0, nk, (const uint8_t *)w)
+        switch (k) {
+        case CBG_COPY: CBX_LAUNCH(CBG_COPY); break;
+        case CBG_UNSHUFFLE: CBX_LAUNCH(CBG_UNSHUFFLE); break;
+        case CBG_BITUN: CBX_LAUNCH(CBG_BITUN); break;
+        default: CBX_LAUNCH(CBG_BITUN4); break;
+        }
+#undef CBX_LAUNCH
+        hb_prof_end(s);
+    }
+    hb_prof_begin("k_cbx_finish", s);
+    hipLaunchKernelGGL(k_cbx_finish, dim3((unsigned)((nj + 63) / 64)), dim3(64), 0, s, d_jobs, (const CbPlan *)d_plans, d_touch, d_results, (uint32_t)njobs);
     hb_prof_end(s);
     HB_HIP_TRY(hipGetLastError());
     return HB_OK;

@@ -959,3 +959,110 @@ func CBloscGetItemBatchHIP(frames [][]byte, jobs []GetItemJob) ([][]byte, []erro
 	}
 	return out, errs
 }
+
+// BoxJob is one box of CBloscGetBoxBatchHIP: the items [Start[k], Start[k]+Shape[k]) along every dimension k of frames[Frame], a C-order chunk of
+// ChunkShape items (1 to 4 dimensions; the three slices have the same length).
+type BoxJob struct {
+	Frame                    int
+	ChunkShape, Start, Shape []int64
+}
+
+// CBloscGetBoxBatchHIP reads many N-d boxes of C-Blosc-1 chunk frames through ONE set of kernel launches (hb_cblosc_getbox_frames_batch):
+// `z[a:b, c:d]` of a chunked array store is one box per chunk it crosses.  Every frame goes up once, every distinct block that a row of a
+// box touches is decoded once, and blocks that lie between the rows are never read.  out[j] is the box in C order, errs[j] the job's error.
+// Without a device every job gets the no-device error: there is no CPU path.  Go memory is borrowed for the call only (pinned slabs and C
+// arrays, never Go pointers in C memory).  Like the rest of this file: written against the C ABI, it has never met a compiler.
+func CBloscGetBoxBatchHIP(frames [][]byte, jobs []BoxJob) ([][]byte, []error) {
+	nj, nf := len(jobs), len(frames)
+	out := make([][]byte, nj)
+	errs := make([]error, nj)
+	if nj == 0 {
+		return out, errs
+	}
+	failAll := func(code C.int64_t) ([][]byte, []error) {
+		for j := range jobs {
+			errs[j] = hbError(code)
+		}
+		return out, errs
+	}
+	if !useHIP {
+		return failAll(C.int64_t(C.HB_ERR_NO_DEVICE))
+	}
+	for _, q := range jobs {
+		nd := len(q.ChunkShape)
+		if q.Frame < 0 || q.Frame >= nf || nd < 1 || nd > int(C.HB_CBLOSC_BOX_MAX_NDIM) || len(q.Start) != nd || len(q.Shape) != nd {
+			return failAll(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+	}
+	ptrBytes := C.size_t(unsafe.Sizeof(uintptr(0)))
+	srcs := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(nf) * ptrBytes))[:nf:nf]
+	dsts := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(nj) * ptrBytes))[:nj:nj]
+	defer C.free(unsafe.Pointer(&srcs[0]))
+	defer C.free(unsafe.Pointer(&dsts[0]))
+	lens := make([]C.size_t, nf)
+	caps := make([]C.size_t, nj)
+	rcs := make([]C.int64_t, nj)
+	jt := make([]C.hb_cblosc_box_job, nj)
+	var inBytes, outBytes C.size_t
+	for k, f := range frames {
+		lens[k] = C.size_t(len(f))
+		inBytes += lens[k] // tightly packed: frames that follow each other exactly go up in ONE copy
+	}
+	for j, q := range jobs {
+		ts := int64(1)
+		if len(frames[q.Frame]) >= 16 && frames[q.Frame][3] != 0 {
+			ts = int64(frames[q.Frame][3])
+		}
+		jt[j].frame = C.uint32_t(q.Frame)
+		jt[j].ndim = C.uint32_t(len(q.ChunkShape))
+		bytes := ts // packed: the strides of the box itself
+		for k := len(q.ChunkShape) - 1; k >= 0; k-- {
+			jt[j].chunk_shape[k] = C.int64_t(q.ChunkShape[k])
+			jt[j].start[k] = C.int64_t(q.Start[k])
+			jt[j].shape[k] = C.int64_t(q.Shape[k])
+			jt[j].dst_stride[k] = C.int64_t(bytes)
+			m := q.Shape[k]
+			if m < 0 {
+				m = 1 // (refused by the library)
+			}
+			if m > 0 && bytes > (1<<32)/m { // (a box no frame can hold is refused by the library: no room is needed for it)
+				bytes = 1 << 32
+			} else {
+				bytes *= m
+			}
+		}
+		if bytes < 1<<32 {
+			caps[j] = C.size_t(bytes)
+		}
+		outBytes += caps[j] + 1
+	}
+	slabIn, slabOut := C.hb_host_alloc(inBytes+64), C.hb_host_alloc(outBytes+64)
+	if slabIn == nil || slabOut == nil {
+		C.hb_host_free(slabIn)
+		C.hb_host_free(slabOut)
+		return failAll(C.int64_t(C.HB_ERR_HIP))
+	}
+	defer C.hb_host_free(slabIn)
+	defer C.hb_host_free(slabOut)
+	var io, oo C.size_t
+	for k, f := range frames {
+		srcs[k] = unsafe.Add(slabIn, uintptr(io))
+		copy(unsafe.Slice((*byte)(srcs[k]), len(f)), f)
+		io += lens[k]
+	}
+	for j := range jobs {
+		dsts[j] = unsafe.Add(slabOut, uintptr(oo))
+		oo += caps[j] + 1
+	}
+	if rc := C.hb_cblosc_getbox_frames_batch(C.int(nf), &srcs[0], &lens[0], C.int(nj), &jt[0], &dsts[0], &caps[0], &rcs[0], C.int(Device)); rc != C.HB_OK {
+		return failAll(C.int64_t(rc))
+	}
+	for j := range jobs {
+		if rcs[j] < 0 {
+			errs[j] = hbError(rcs[j])
+		} else {
+			out[j] = append([]byte(nil), unsafe.Slice((*byte)(dsts[j]), int(rcs[j]))...)
+		}
+	}
+	return out, errs
+}

@@ -104,6 +104,7 @@ EXPORTS = [
     "hb_cblosc_decompress_frames_batch_workspace", "hb_cblosc_decompress_frames_batch_device", "hb_cblosc_decompress_frames_batch",
     "hb_cblosc_compress_frames_batch_workspace", "hb_cblosc_compress_frames_batch_device", "hb_cblosc_compress_frames_batch",
     "hb_cblosc_getitem_frames_batch_workspace", "hb_cblosc_getitem_frames_batch_device", "hb_cblosc_getitem_frames_batch",
+    "hb_cblosc_getbox_frames_batch_workspace", "hb_cblosc_getbox_frames_batch_device", "hb_cblosc_getbox_frames_batch",
     "hb_cblosc_accept_codecs",
     "hb_queue_create", "hb_queue_create_ex", "hb_queue_destroy", "hb_queue_compress", "hb_queue_decompress", "hb_queue_wait",
 ]
@@ -122,6 +123,21 @@ class hb_result(ctypes.Structure):
 
 class hb_getitem_job(ctypes.Structure):
     _fields_ = [("frame", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("start", ctypes.c_int64), ("nitems", ctypes.c_int64)]
+
+
+class hb_cblosc_box_job(ctypes.Structure):
+    """include/hipblosc.h hb_cblosc_box_job: an N-d box of a C-order chunk and the byte strides of its destination"""
+    _fields_ = [("frame", ctypes.c_uint32), ("ndim", ctypes.c_uint32), ("chunk_shape", ctypes.c_int64 * 4), ("start", ctypes.c_int64 * 4),
+                ("shape", ctypes.c_int64 * 4), ("dst_stride", ctypes.c_int64 * 4)]
+
+
+def box_job(frame, chunk_shape, start, shape, dst_stride):
+    """hb_cblosc_box_job from sequences of ndim entries each (the entries behind them stay 0)"""
+    nd = len(chunk_shape)
+    if not (len(start) == len(shape) == len(dst_stride) == nd) or nd > 4:
+        raise ValueError("chunk_shape, start, shape and dst_stride need the same number of entries, at most 4")
+    a = ctypes.c_int64 * 4
+    return hb_cblosc_box_job(int(frame), nd, a(*[int(v) for v in chunk_shape]), a(*[int(v) for v in start]), a(*[int(v) for v in shape]), a(*[int(v) for v in dst_stride]))
 
 
 _lib = None
@@ -198,6 +214,9 @@ def lib():
             "hb_cblosc_getitem_frames_batch_workspace": (sz, [i32, vp, vp, i32, vp]),
             "hb_cblosc_getitem_frames_batch_device": (i32, [i32, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp, vp]),
             "hb_cblosc_getitem_frames_batch": (i32, [i32, vp, vp, i32, vp, vp, vp, vp, i32]),
+            "hb_cblosc_getbox_frames_batch_workspace": (sz, [i32, vp, vp, i32, vp]),
+            "hb_cblosc_getbox_frames_batch_device": (i32, [i32, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp, vp]),
+            "hb_cblosc_getbox_frames_batch": (i32, [i32, vp, vp, i32, vp, vp, vp, vp, i32]),
             "hb_cblosc_accept_codecs": (i32, [ctypes.c_uint]),
         }
         for name, (res, args) in sig.items():
@@ -613,6 +632,103 @@ def CBloscGetItemBatch(frames, jobs, dev=None):
     rcs = (ctypes.c_int64 * nj)()
     _check(lib().hb_cblosc_getitem_frames_batch(nf, fr, ns, nj, jt, dsts, (ctypes.c_size_t * nj)(*caps), rcs, device if dev is None else dev))
     return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(nj)]
+
+
+def _typesize_of(keep, nf, f):
+    return (bytes(keep[f][2][3:4])[0] or 1) if 0 <= f < nf and keep[f][1] >= 16 else 1
+
+
+def CBloscGetBoxBatch(frames, jobs, dev=None):
+    """Many N-d boxes of many chunk frames through one set of launches (include/hipblosc.h hb_cblosc_getbox_frames_batch): `jobs` are
+    (frame_index, chunk_shape, start, shape) tuples over `frames`, the chunk in C order, at most 4 dimensions; every distinct block that a row
+    of a box touches is decoded once.  The i-th result is the box's bytes in C order -- what numpy slicing of the chunk gives -- or the job's
+    error (returned, not raised, as CBloscGetItemBatch does)."""
+    jobs = list(jobs)
+    nj, nf = len(jobs), len(frames)
+    if nj == 0:
+        return []
+    keep = [_buf(f) for f in frames]
+    jt, caps = (hb_cblosc_box_job * nj)(), []
+    for j, (f, chunk_shape, start, shape) in enumerate(jobs):
+        ts = _typesize_of(keep, nf, f)
+        strides, nbytes = [], ts
+        for m in reversed([max(int(v), 0) for v in shape]):
+            strides.insert(0, nbytes)
+            nbytes *= m
+        jt[j] = box_job(f, chunk_shape, start, shape, strides)
+        caps.append(nbytes)
+    outs = [(ctypes.c_char * max(c, 1))() for c in caps]
+    fr = (ctypes.c_void_p * max(nf, 1))(*[k[0].value for k in keep])
+    ns = (ctypes.c_size_t * max(nf, 1))(*[k[1] for k in keep])
+    dsts = (ctypes.c_void_p * nj)(*[ctypes.addressof(o) for o in outs])
+    rcs = (ctypes.c_int64 * nj)()
+    _check(lib().hb_cblosc_getbox_frames_batch(nf, fr, ns, nj, jt, dsts, (ctypes.c_size_t * nj)(*caps), rcs, device if dev is None else dev))
+    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(nj)]
+
+
+def region_jobs(grid_shape, chunk_shape, region, typesize):
+    """The box jobs of a region read of a chunked array: one (hb_cblosc_box_job, byte offset into the output) per chunk that `region` -- a
+    (lo, hi) pair per dimension, in items of the whole array -- crosses, every job with the strides of the C-order output array; and the
+    output's shape.  Chunk (c_0, c_1 ...) is frame number c in C order of the grid; chunks at the array's edge are stored whole."""
+    nd = len(chunk_shape)
+    if not (len(grid_shape) == len(region) == nd) or not 1 <= nd <= 4:
+        raise ValueError("grid_shape, chunk_shape and region need the same number of entries, 1 to 4")
+    out_shape = [hi - lo for lo, hi in region]
+    if any(lo < 0 or hi < lo or hi > g * c for (lo, hi), g, c in zip(region, grid_shape, chunk_shape)):
+        raise ValueError("the region lies outside the array")
+    strides, acc = [], int(typesize)
+    for m in reversed(out_shape):
+        strides.insert(0, acc)
+        acc *= m
+    jobs = []
+    if all(out_shape):
+        spans = [range(lo // c, (hi - 1) // c + 1) for (lo, hi), c in zip(region, chunk_shape)]
+        idx = [r.start for r in spans]
+        while True:
+            f, start, shape, off = 0, [], [], 0
+            for k in range(nd):
+                f = f * grid_shape[k] + idx[k]
+                a, b = max(region[k][0], idx[k] * chunk_shape[k]), min(region[k][1], (idx[k] + 1) * chunk_shape[k])
+                start.append(a - idx[k] * chunk_shape[k])
+                shape.append(b - a)
+                off += (a - region[k][0]) * strides[k]
+            jobs.append((box_job(f, chunk_shape, start, shape, strides), off))
+            k = nd - 1
+            while k >= 0:
+                idx[k] += 1
+                if idx[k] < spans[k].stop:
+                    break
+                idx[k] = spans[k].start
+                k -= 1
+            if k < 0:
+                break
+    return jobs, out_shape
+
+
+def CBloscReadRegion(frames, grid_shape, chunk_shape, region, typesize, dev=None):
+    """`z[lo_0:hi_0, lo_1:hi_1 ...]` of a chunked array whose chunks are the C-Blosc-1 frames `frames`, in C order of the chunk grid
+    `grid_shape`, every chunk `chunk_shape` items of `typesize` bytes: one box job per chunk the region crosses (region_jobs), all of them
+    through one hb_cblosc_getbox_frames_batch call into one output array.  Returns the region's bytes in C order; raises the first job's error."""
+    pairs, out_shape = region_jobs(grid_shape, chunk_shape, region, typesize)
+    total = int(typesize)
+    for m in out_shape:
+        total *= m
+    nj, nf = len(pairs), len(frames)
+    if nj == 0:
+        return b""
+    out = (ctypes.c_char * total)()
+    base = ctypes.addressof(out)
+    keep = [_buf(f) for f in frames]
+    jt = (hb_cblosc_box_job * nj)(*[p[0] for p in pairs])
+    fr = (ctypes.c_void_p * max(nf, 1))(*[k[0].value for k in keep])
+    ns = (ctypes.c_size_t * max(nf, 1))(*[k[1] for k in keep])
+    dsts = (ctypes.c_void_p * nj)(*[base + off for _, off in pairs])
+    caps = (ctypes.c_size_t * nj)(*[total - off for _, off in pairs])
+    rcs = (ctypes.c_int64 * nj)()
+    _check(lib().hb_cblosc_getbox_frames_batch(nf, fr, ns, nj, jt, dsts, caps, rcs, device if dev is None else dev))
+    for rc in rcs:
+        _check(int(rc))
+    return bytes(out)
 
 
 def CBloscCompress(data, shuffle=1, typesize=4):

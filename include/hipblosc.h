@@ -350,8 +350,8 @@ int     hb_cblosc_parse_header(const void *frame, size_t n, hb_cblosc_header *ou
 /* which C-Blosc-1 codec formats the hb_cblosc_* entry points accept: bit k = codec format k.  Default 0x2 (LZ4 / LZ4HC).
  * Accepted masks: 0x2 and 0x3 (adds BloscLZ); anything else HB_ERR_BAD_ARG and no change.  Returns the previous mask.
  * Process-wide and thread-safe: an atomic word that every entry point (hb_cblosc_decompress*, hb_cblosc_decompress_frames_batch*,
- * hb_cblosc_getitem*, hb_cblosc_getitem_frames_batch*, device and host forms and their workspace queries) reads once per call.  With
- * bit 0 set a BloscLZ frame gets exactly the refusals, in the same order, that an LZ4 frame with the same header gets; wherever the
+ * hb_cblosc_getitem*, hb_cblosc_getitem_frames_batch*, hb_cblosc_getbox_frames_batch*, device and host forms and their workspace queries) reads once
+ * per call.  With bit 0 set a BloscLZ frame gets exactly the refusals, in the same order, that an LZ4 frame with the same header gets; wherever the
  * comments below say "codec format != 1" read "a codec format the mask does not name".  Opt-in, because HB_ERR_INVALID_CODEC for
  * BloscLZ is an answer callers may route on (to a CPU decoder).  Writing is not touched: hb_cblosc_compress* writes LZ4. */
 int     hb_cblosc_accept_codecs(unsigned mask);
@@ -443,6 +443,60 @@ int     hb_cblosc_getitem_frames_batch_device(int nframes, const hb_cblosc_heade
 int     hb_cblosc_getitem_frames_batch(int nframes, const void *const *frame, const size_t *n,
                                        int njobs, const hb_getitem_job *jobs, void *const *dst, const size_t *cap,
                                        int64_t *rc, int device);
+/* ---- many N-d boxes of many C-Blosc-1 frames through ONE set of launches: `z[a:b, c:d]` of a chunked array store is, per chunk it crosses, a
+ *      box of a C-order chunk, and the boxes of all chunks land in one output array whose strides are not the chunk's.  A job IS a box: the
+ *      gather walks its rows (the runs along the last dimension) by arithmetic, not by a record per row, and the destination is strided.  A box
+ *      that is a whole chunk with the output array's strides decodes a chunk grid straight into its array.
+ *      Item (i_0 .. i_{ndim-1}) of the box is the chunk's item at linear index sum_k (start[k] + i_k) * prod_{m>k} chunk_shape[m]; it is written
+ *      to d_dst[j] + sum_k i_k * dst_stride[k] (64-bit offsets: the output array may exceed 4 GiB).
+ *      Device form (rules of hb_cblosc_getitem_frames_batch_device, the _device suffix included).  The outcome of job j is defined against one
+ *      hb_cblosc_getitem_device call per box row, with start = the row's linear index, nitems = shape[ndim-1] and the row's destination:
+ *        - refused per job, decided on the host before hb_init(), d_results[j].status with bytes, total_bytes and flags 0, in this order: the
+ *          header, codec and geometry refusals of that call in its order (hb_cblosc_accept_codecs is honoured); HB_ERR_BAD_ARG for ndim outside
+ *          1 .. HB_CBLOSC_BOX_MAX_NDIM, a negative entry, a box outside the chunk, prod chunk_shape * typesize != nbytes (checked without
+ *          overflow), a negative dst_stride or dst_stride[ndim-1] != typesize; HB_ERR_SHORT_BUFFER for cap[j] < sum_k (shape[k] - 1) *
+ *          dst_stride[k] + typesize; HB_ERR_BAD_ARG for a NULL d_frame[f] or a NULL d_dst[j] with bytes to write.  A refused job keeps its
+ *          place and touches nothing;
+ *        - a box with some shape[k] == 0: status 0, bytes 0, nothing planned or written;
+ *        - every other job: status 0, flags 1, bytes = total_bytes = prod shape * typesize -- or HB_ERR_DECOMPRESSION_FAILED with bytes 0 when
+ *          the plan or a stream of a block THAT ONE OF ITS ROWS TOUCHES fails; a failed job writes nothing.  The fail state is per block: a
+ *          damaged block spoils exactly the jobs one of whose rows touches it.  A block that no row of any accepted job touches is never
+ *          planned, decoded or read, also when it lies between two touched blocks of one job (a thin box of a 3-D chunk skips whole blocks);
+ *          every distinct (frame, block) pair is planned and decoded once, however many jobs and rows read it;
+ *        - nothing is written outside the box's items: the gaps between rows keep the caller's bytes.  Overlapping destinations are the
+ *          caller's error.
+ *      The call as a whole: as hb_cblosc_getitem_frames_batch_device (HB_ERR_BAD_ARG for negative counts, HB_OK and nothing launched for
+ *      njobs == 0, HB_ERR_BAD_ARG for NULL arrays, frame >= nframes, a NULL or misaligned d_work, a NULL d_results, or more than
+ *      HB_CBLOSC_BATCH_MAX_WORK distinct blocks, streams, (job, touched block) pairs or workgroups of one gather kind; then HB_ERR_SHORT_BUFFER
+ *      for work_bytes below the workspace query; then HB_ERR_NO_DEVICE).
+ *      Workspace: the records, one stream array, one staged copy per distinct covered block, and a list of the blocks each job touches; it does
+ *      NOT grow with the number of rows.  At most the sum over the distinct covered blocks of hb_cblosc_getitem_workspace() for a one-block
+ *      range + HB_CBLOSC_BOX_BATCH_JOB_BYTES * (njobs + nframes) + HB_CBLOSC_BOX_BATCH_TOUCH_BYTES * (the number of (job, touched block)
+ *      pairs).  0 when the call as a whole would be refused, 256 for njobs == 0.
+ *      Host form: every frame an accepted job reads goes up once (frames exactly adjacent in host memory in one copy), the device form runs
+ *      once and gathers into a packed device buffer with the boxes C-contiguous, the records and the packed boxes come down in one copy
+ *      each, and the host places the rows at their strides.  rc[j] is the box's byte count or the job's status (what the host refuses, it
+ *      refuses as above, a frame that does not parse with hb_cblosc_parse_header's answer; without a device every accepted job answers
+ *      HB_ERR_NO_DEVICE).  There is no per-row fallback: a row's own hb_cblosc_getitem answers HB_ERR_DECOMPRESSION_FAILED exactly where
+ *      the job does.  A failed job's destination keeps the caller's bytes.  Returns HB_OK unless the arguments as a whole are unusable. ---- */
+#define HB_CBLOSC_BOX_MAX_NDIM 4
+#define HB_CBLOSC_BOX_BATCH_JOB_BYTES   512      /* workspace per job and per frame beyond the blocks */
+#define HB_CBLOSC_BOX_BATCH_TOUCH_BYTES 8        /* workspace per (job, touched block) pair */
+typedef struct hb_cblosc_box_job {
+    uint32_t frame;            /* index into the frame arrays */
+    uint32_t ndim;             /* 1 .. HB_CBLOSC_BOX_MAX_NDIM */
+    int64_t  chunk_shape[4];   /* items, C order (last dimension contiguous); product * typesize == the header's nbytes */
+    int64_t  start[4], shape[4];   /* the box in items: 0 <= start[k], 0 <= shape[k], start[k] + shape[k] <= chunk_shape[k] */
+    int64_t  dst_stride[4];    /* BYTES between neighbours along dimension k in the destination; >= 0; dst_stride[ndim-1] == typesize */
+} hb_cblosc_box_job;           /* entries at k >= ndim are 0 */
+size_t  hb_cblosc_getbox_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n,
+                                                int njobs, const hb_cblosc_box_job *jobs);
+int     hb_cblosc_getbox_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n,
+                                             int njobs, const hb_cblosc_box_job *jobs, void *const *d_dst, const size_t *cap,
+                                             void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
+int     hb_cblosc_getbox_frames_batch(int nframes, const void *const *frame, const size_t *n,
+                                      int njobs, const hb_cblosc_box_job *jobs, void *const *dst, const size_t *cap,
+                                      int64_t *rc, int device);
 /* writing the format: a frame that blosc_decompress() of c-blosc 1.x (python-blosc, numcodecs ...) reads.  shuffle: 0 none, 1 byte
  * shuffle, 2 bit shuffle (BLOSC_NOSHUFFLE / BLOSC_SHUFFLE / BLOSC_BITSHUFFLE); LZ4 streams; block size 4096 x typesize (split) or
  * 4096 (not split), so that every stream is one chunk of this library's encoder; n below 2 GiB (c-blosc's limit).  Returns the
