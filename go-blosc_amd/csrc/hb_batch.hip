@@ -22,6 +22,7 @@
 #include "hb_cblosc_enc_batch.h"
 #include "hb_cblosc_getitem_batch.h"
 #include "hb_cblosc_box_batch.h"
+#include "hb_cblosc_enc_box_batch.h"
 #include <vector>
 #include <algorithm>
 #include <cstring>
@@ -759,6 +760,59 @@ int hb_cblosc_getbox_frames_batch(int nframes, const void *const *frame, const s
     catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
 }
 
+// The records and the frames of a batched C-Blosc-1 encode come down (both host forms end here): the records in one copy; many small frames are
+// packed on the device and come down in ONE copy, large ones one copy each, as in hb_compress_frames_batch.  idx[i]: the caller's input that
+// carried frame i; pf[i]: its frame on the device.  `single` answers an input whose frame did not end with status 0.
+extern "C++" {
+template <class SINGLE>
+static int cbe_host_download(const std::vector<int> &idx, const std::vector<void *> &pf, const uint8_t *d_res, void *const *dst, const size_t *cap, int64_t *rc, Scratch &sc,
+                             SINGLE single) {
+    const int m = (int)idx.size();
+    auto fail_all = [&]() { for (int k : idx) rc[k] = HB_ERR_HIP; return HB_OK; };
+    std::vector<hb_result> res((size_t)m);
+    if (hipMemcpy(res.data(), d_res, (size_t)m * sizeof(hb_result), hipMemcpyDeviceToHost) != hipSuccess) return fail_all();
+    // download as in hb_compress_frames_batch: many small frames are packed on the device and come down in ONE copy, large ones one copy each
+    size_t total_out = 0;
+    std::vector<size_t> outs((size_t)m, 0), poff((size_t)m, 0);
+    std::vector<uint8_t> again((size_t)m, 0);
+    for (int i = 0; i < m; i++) {
+        const int k = idx[(size_t)i];
+        const hb_result &r = res[(size_t)i];
+        if (r.status) { again[(size_t)i] = 1; rc[k] = r.status; continue; }
+        if (r.bytes > cap[k]) { rc[k] = HB_ERR_SHORT_BUFFER; continue; }  // (what hb_cblosc_compress answers when the frame does not fit)
+        outs[(size_t)i] = (size_t)r.bytes; poff[(size_t)i] = total_out; total_out += (size_t)r.bytes; rc[k] = (int64_t)r.bytes;
+    }
+    const bool packed = m >= 16 && total_out / (size_t)m < ((size_t)256 << 10);
+    if (packed && total_out) {
+        std::vector<PackJob> jobs((size_t)m);
+        size_t mx = 0;
+        for (int i = 0; i < m; i++) { jobs[(size_t)i] = PackJob{(const uint8_t *)pf[(size_t)i], (uint64_t)poff[(size_t)i], (uint64_t)outs[(size_t)i]}; mx = std::max(mx, outs[(size_t)i]); }
+        uint8_t *d_pack = sc.get(total_out + 256), *d_jobs = sc.get((size_t)m * sizeof(PackJob));
+        std::vector<uint8_t> host(total_out);
+        bool good = d_pack && d_jobs && hipMemcpyAsync(d_jobs, jobs.data(), (size_t)m * sizeof(PackJob), hipMemcpyHostToDevice, nullptr) == hipSuccess;
+        for (int j0 = 0; good && j0 < m; j0 += 65535) {
+            const unsigned ny = (unsigned)std::min(65535, m - j0), gx = (unsigned)std::min<size_t>(16, (mx + 65535) / 65536);
+            hipLaunchKernelGGL(k_bt_pack, dim3(gx ? gx : 1, ny), dim3(256), 0, nullptr, (const PackJob *)d_jobs + j0, d_pack);
+        }
+        good = good && hipMemcpy(host.data(), d_pack, total_out, hipMemcpyDeviceToHost) == hipSuccess;
+        for (int i = 0; i < m; i++) {
+            const int k = idx[(size_t)i];
+            if (rc[k] < 0) continue;
+            if (good) memcpy(dst[k], host.data() + poff[(size_t)i], outs[(size_t)i]); else rc[k] = HB_ERR_HIP;
+        }
+    } else {
+        for (int i = 0; i < m; i++) {
+            const int k = idx[(size_t)i];
+            if (rc[k] < 0) continue;
+            if (hipMemcpyAsync(dst[k], pf[(size_t)i], outs[(size_t)i], hipMemcpyDeviceToHost, nullptr) != hipSuccess) rc[k] = HB_ERR_HIP;
+        }
+        if (hipStreamSynchronize(nullptr) != hipSuccess) return fail_all();
+    }
+    for (int i = 0; i < m; i++) if (again[(size_t)i]) single(idx[(size_t)i]);
+    return HB_OK;
+}
+}  // extern "C++"
+
 // Many inputs to C-Blosc-1 frames (include/hipblosc.h).  cbe_host_plan (hb_cblosc_enc_batch.h) says which inputs the batch carries and where they
 // and their frames lie on the device; whatever it does not carry, and whatever did not end with status 0 on the device, is answered by
 // hb_cblosc_compress, so that rc[k] is its answer in every case.
@@ -792,47 +846,63 @@ int hb_cblosc_compress_frames_batch(int nframes, const void *const *src, const s
     }
     const int st = hb_cblosc_compress_frames_batch_device(m, ps.data(), P.ns.data(), pf.data(), P.caps.data(), shuffle, typesize, d_work, wb, (hb_result *)d_res, nullptr);
     if (st) { for (int k : P.idx) rc[k] = st; return HB_OK; }
-    std::vector<hb_result> res((size_t)m);
-    if (hipMemcpy(res.data(), d_res, (size_t)m * sizeof(hb_result), hipMemcpyDeviceToHost) != hipSuccess) return fail_all();
-    // download as in hb_compress_frames_batch: many small frames are packed on the device and come down in ONE copy, large ones one copy each
-    size_t total_out = 0;
-    std::vector<size_t> outs((size_t)m, 0), poff((size_t)m, 0);
-    std::vector<uint8_t> again((size_t)m, 0);
+    return cbe_host_download(P.idx, pf, d_res, dst, cap, rc, sc, single);
+}
+
+// Many source boxes to C-Blosc-1 frames (include/hipblosc.h).  cbxe_host_plan (hb_cblosc_enc_box_batch.h) answers what has no assembled chunk
+// and says which jobs the batch carries: their boxes are packed C-contiguously here, items only, and go up in one copy; the device form runs
+// once with the packed strides and writes the fill itself.  Whatever the batch does not carry, and whatever did not end with status 0 on the
+// device, is answered by hb_cblosc_compress for the chunk assembled on the host.
+static int cbxe_host_call(int nframes, const hb_cblosc_src_box *boxes, const void *const *src, void *const *dst, const size_t *cap, int64_t *rc, const void *fill,
+                          int shuffle, int typesize, int device) {
+    if (nframes < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
+    if (nframes == 0) return HB_OK;
+    if (!boxes || !src || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
+    CbxeHostPlan P;
+    cbxe_host_plan(nframes, boxes, src, dst, typesize, P);
+    uint8_t table[CBXE_FILL_BYTES];
+    cbxe_fill_table(fill, typesize, table);
+    auto single = [&](int k) {
+        const CbxeGeom &g = P.geom[(size_t)k];
+        if (!src[k] && g.src_bytes) { rc[k] = hb_cblosc_compress(nullptr, (size_t)g.nbytes, dst[k], cap[k], shuffle, typesize, device); return; }      // (no chunk to assemble: its refusal)
+        std::vector<uint8_t> chunk((size_t)g.nbytes);
+        if (g.nbytes) cbxe_assemble(g, (const uint8_t *)src[k], table, chunk.data());
+        rc[k] = hb_cblosc_compress(chunk.data(), chunk.size(), dst[k], cap[k], shuffle, typesize, device);
+    };
+    const int m = (int)P.carried.size();
+    std::vector<uint8_t> carried((size_t)nframes, 0);
+    for (int k : P.carried) carried[(size_t)k] = 1;
+    for (int k = 0; k < nframes; k++) {
+        if (P.status[(size_t)k]) rc[k] = P.status[(size_t)k];
+        else if (!carried[(size_t)k]) single(k);
+    }
+    if (m == 0) return HB_OK;
+    auto rest_single = [&]() { for (int k : P.carried) single(k); return HB_OK; };
+    if (hb_select_device(device) != HB_OK) return rest_single();
+    const size_t wb = hb_cblosc_compress_boxes_batch_workspace(m, P.pb.data(), shuffle, typesize);
+    if (!wb) return rest_single();                                       // (a batch beyond the 32-bit limits: one call per chunk is still right)
+    auto fail_all = [&]() { for (int k : P.carried) rc[k] = HB_ERR_HIP; return HB_OK; };
+    Scratch sc(device);
+    uint8_t *d_in = sc.get(P.in_bytes + 256), *d_out = sc.get(P.out_bytes + 256), *d_work = sc.get(wb), *d_res = sc.get((size_t)m * sizeof(hb_result));
+    if (!d_in || !d_out || !d_work || !d_res) return fail_all();
+    d_in += (16u - ((uintptr_t)d_in & 15u)) & 15u;                       // (the plan's offsets are multiples of 16: so are the addresses)
+    std::vector<uint8_t> packed(P.in_bytes, 0);
+    std::vector<const void *> ps((size_t)m); std::vector<void *> pf((size_t)m);
     for (int i = 0; i < m; i++) {
-        const int k = P.idx[(size_t)i];
-        const hb_result &r = res[(size_t)i];
-        if (r.status) { again[(size_t)i] = 1; rc[k] = r.status; continue; }
-        if (r.bytes > cap[k]) { rc[k] = HB_ERR_SHORT_BUFFER; continue; }  // (what hb_cblosc_compress answers when the frame does not fit)
-        outs[(size_t)i] = (size_t)r.bytes; poff[(size_t)i] = total_out; total_out += (size_t)r.bytes; rc[k] = (int64_t)r.bytes;
+        const int k = P.carried[(size_t)i];
+        cbxe_pack_box(P.geom[(size_t)k], (const uint8_t *)src[k], packed.data() + P.ioff[(size_t)i]);
+        ps[(size_t)i] = d_in + P.ioff[(size_t)i]; pf[(size_t)i] = d_out + P.ooff[(size_t)i];
     }
-    const bool packed = m >= 16 && total_out / (size_t)m < ((size_t)256 << 10);
-    if (packed && total_out) {
-        std::vector<PackJob> jobs((size_t)m);
-        size_t mx = 0;
-        for (int i = 0; i < m; i++) { jobs[(size_t)i] = PackJob{(const uint8_t *)pf[(size_t)i], (uint64_t)poff[(size_t)i], (uint64_t)outs[(size_t)i]}; mx = std::max(mx, outs[(size_t)i]); }
-        uint8_t *d_pack = sc.get(total_out + 256), *d_jobs = sc.get((size_t)m * sizeof(PackJob));
-        std::vector<uint8_t> host(total_out);
-        bool good = d_pack && d_jobs && hipMemcpyAsync(d_jobs, jobs.data(), (size_t)m * sizeof(PackJob), hipMemcpyHostToDevice, nullptr) == hipSuccess;
-        for (int j0 = 0; good && j0 < m; j0 += 65535) {
-            const unsigned ny = (unsigned)std::min(65535, m - j0), gx = (unsigned)std::min<size_t>(16, (mx + 65535) / 65536);
-            hipLaunchKernelGGL(k_bt_pack, dim3(gx ? gx : 1, ny), dim3(256), 0, nullptr, (const PackJob *)d_jobs + j0, d_pack);
-        }
-        good = good && hipMemcpy(host.data(), d_pack, total_out, hipMemcpyDeviceToHost) == hipSuccess;
-        for (int i = 0; i < m; i++) {
-            const int k = P.idx[(size_t)i];
-            if (rc[k] < 0) continue;
-            if (good) memcpy(dst[k], host.data() + poff[(size_t)i], outs[(size_t)i]); else rc[k] = HB_ERR_HIP;
-        }
-    } else {
-        for (int i = 0; i < m; i++) {
-            const int k = P.idx[(size_t)i];
-            if (rc[k] < 0) continue;
-            if (hipMemcpyAsync(dst[k], pf[(size_t)i], outs[(size_t)i], hipMemcpyDeviceToHost, nullptr) != hipSuccess) rc[k] = HB_ERR_HIP;
-        }
-        if (hipStreamSynchronize(nullptr) != hipSuccess) return fail_all();
-    }
-    for (int i = 0; i < m; i++) if (again[(size_t)i]) single(P.idx[(size_t)i]);
-    return HB_OK;
+    if (P.in_bytes && hipMemcpyAsync(d_in, packed.data(), P.in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
+    const int st = hb_cblosc_compress_boxes_batch_device(m, P.pb.data(), ps.data(), pf.data(), P.caps.data(), fill, shuffle, typesize, d_work, wb, (hb_result *)d_res, nullptr);
+    if (st) { (void)hipStreamSynchronize(nullptr); return rest_single(); }     // (`packed` is pageable: the copy has to be over before it goes)
+    return cbe_host_download(P.carried, pf, d_res, dst, cap, rc, sc, single);
+}
+// (host tables that do not fit into memory: the batch is one the caller has to split -- no exception crosses the C ABI)
+int hb_cblosc_compress_boxes_batch(int nframes, const hb_cblosc_src_box *boxes, const void *const *src, void *const *dst, const size_t *cap, int64_t *rc, const void *fill,
+                                   int shuffle, int typesize, int device) {
+    try { return cbxe_host_call(nframes, boxes, src, dst, cap, rc, fill, shuffle, typesize, device); }
+    catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
 }
 
 }  // extern "C"

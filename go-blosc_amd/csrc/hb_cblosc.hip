@@ -26,6 +26,7 @@
 #include "hb_cblosc_enc_batch.h"   // the geometry of a written frame, and the host side of the batched encode
 #include "hb_cblosc_getitem_batch.h"   // the geometry of an item range, and the host side of the batched getitem
 #include "hb_cblosc_box_batch.h"       // the geometry of a box, the host side of the batched box reads, the gather's index arithmetic
+#include "hb_cblosc_enc_box_batch.h"   // the geometry of a source box, the host side of the batched box writes, the gather's index arithmetic
 
 // ---- the streams of blocks [b0, b0 + nb) (hb_cblosc_getitem_device: the blocks that cover a range; the others' bstarts entries and streams
 // are never read); stream offsets count from the first of these blocks ----
@@ -959,6 +960,24 @@ __global__ __launch_bounds__(64) void k_cbeb_finish(const CbeFrame *__restrict__
     cbe_finish(plans + k, last, F.nbytes, F.blocksize, F.typesize, F.flags, F.nfull, 16u + 4u * F.nblocks, F.dst, F.cap, r, lane);
 }
 
+// ---- batched box writes (hb_cblosc_compress_boxes_batch_device; the host side and the index arithmetic are hb_cblosc_enc_box_batch.h): the
+// chunks that are not read where they lie are assembled in the workspace, then the batch above runs over them. ----
+struct CbxeDeviceIO {
+    __device__ __forceinline__ void copy16(uint8_t *d, const uint8_t *s) { *(u32x4 *)d = ld16u_nt(s); }      // (the source is read once; the staged chunk is read next)
+    __device__ __forceinline__ void fill16(uint8_t *d, const uint8_t *s) { *(u32x4 *)d = ld16u(s); }
+    __device__ __forceinline__ void put(uint8_t *d, uint8_t v) { *d = v; }
+    __device__ __forceinline__ uint8_t get(const uint8_t *s) { return *s; }
+};
+// One launch over the workgroup prefix of the staged jobs.  A thread owns one 16-byte unit of its job's staged chunk (cbxe_thread): one
+// unaligned 16-byte load and one aligned store inside the box, one aligned store of the rotated fill pattern outside, byte by byte where the
+// unit crosses the box's edge or a chunk row.  The source is read only at the box's items.
+__global__ __launch_bounds__(256) void k_cbxe_gather(const CbxeJob *__restrict__ jobs, const uint32_t *__restrict__ gblk, uint32_t njobs, const uint8_t *__restrict__ table,
+                                                      uint32_t ts, uint64_t rcp_ts) {
+    const uint32_t i = hb_owner(gblk, njobs, blockIdx.x);
+    CbxeDeviceIO io;
+    cbxe_thread(jobs[i], table, ts, rcp_ts, blockIdx.x - gblk[i], threadIdx.x, io);
+}
+
 void hb_launch_match_selfcontained(const uint8_t *src, size_t n, void *desc, uint8_t *records, uint32_t nchunks, int accel, hipStream_t s);   // hb_lz4_enc.hip
 bool hb_launch_match_fused_selfcontained(const uint8_t *src, int typesize, void *desc, uint8_t *records, uint32_t nblk, int accel, hipStream_t s);
 void hb_launch_match_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, void *desc, uint8_t *records, uint32_t total_chunks, int accel, hipStream_t s);
@@ -1481,26 +1500,10 @@ int hb_cblosc_compress_dev(const void *d_src, size_t n, void *d_frame, size_t ca
     HB_HIP_TRY(hipGetLastError());
     return HB_OK;
 }
-// ---- many inputs, one set of launches (include/hipblosc.h; the host side is hb_cblosc_enc_batch.h) ----
-size_t hb_cblosc_compress_frames_batch_workspace(int nframes, const size_t *n, int shuffle, int typesize) {
-    CbeBatch B;
-    if (cbe_prepare(nframes, nullptr, n, nullptr, nullptr, shuffle, typesize, nullptr, B)) return 0;
-    return B.query;
-}
-
-int hb_cblosc_compress_frames_batch_device(int nframes, const void *const *d_src, const size_t *n, void *const *d_frame, const size_t *cap, int shuffle, int typesize,
-                                           void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
-    if (nframes < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
-    if (nframes == 0) return HB_OK;
-    if (!d_src || !n || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
-    uint8_t *w = (uint8_t *)d_work;
-    CbeBatch B;
-    const int rc = cbe_prepare(nframes, d_src, n, d_frame, cap, shuffle, typesize, w, B);
-    if (rc) return rc;
+// everything of a batched encode behind cbe_prepare: upload, map, filter, matchers, tiles, scan, pack, finish over the workspace `w` that B was
+// laid out for.  hb_cblosc_compress_frames_batch_device and hb_cblosc_compress_boxes_batch_device both end here.
+static int cbe_launch_batch(int nframes, const CbeBatch &B, int shuffle, int typesize, uint8_t *w, hb_result *d_results, hipStream_t s) {
     const CbeLayout &L = B.L;
-    if (work_bytes < B.query || B.query < L.total) return HB_ERR_SHORT_BUFFER;      // (the layout never exceeds the query: hb_cblosc_enc_batch.h)
-    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
-    hipStream_t s = (hipStream_t)stream;
     const size_t nf = (size_t)nframes;
     // the frame records, the matcher's records, the prefixes and the cleared plans go up in one copy (the buffer is read before the call returns)
     std::vector<uint8_t> up(L.upload, 0);
@@ -1559,5 +1562,65 @@ int hb_cblosc_compress_frames_batch_device(int nframes, const void *const *d_src
     hb_prof_end(s);
     HB_HIP_TRY(hipGetLastError());
     return HB_OK;
+}
+// ---- many inputs, one set of launches (include/hipblosc.h; the host side is hb_cblosc_enc_batch.h) ----
+size_t hb_cblosc_compress_frames_batch_workspace(int nframes, const size_t *n, int shuffle, int typesize) {
+    CbeBatch B;
+    if (cbe_prepare(nframes, nullptr, n, nullptr, nullptr, shuffle, typesize, nullptr, B)) return 0;
+    return B.query;
+}
+
+int hb_cblosc_compress_frames_batch_device(int nframes, const void *const *d_src, const size_t *n, void *const *d_frame, const size_t *cap, int shuffle, int typesize,
+                                           void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    if (nframes < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
+    if (nframes == 0) return HB_OK;
+    if (!d_src || !n || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
+    uint8_t *w = (uint8_t *)d_work;
+    CbeBatch B;
+    const int rc = cbe_prepare(nframes, d_src, n, d_frame, cap, shuffle, typesize, w, B);
+    if (rc) return rc;
+    const CbeLayout &L = B.L;
+    if (work_bytes < B.query || B.query < L.total) return HB_ERR_SHORT_BUFFER;      // (the layout never exceeds the query: hb_cblosc_enc_batch.h)
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    return cbe_launch_batch(nframes, B, shuffle, typesize, w, d_results, (hipStream_t)stream);
+}
+
+// ---- many source boxes, one set of launches (include/hipblosc.h; the host side is hb_cblosc_enc_box_batch.h) ----
+size_t hb_cblosc_compress_boxes_batch_workspace(int nframes, const hb_cblosc_src_box *boxes, int shuffle, int typesize) {
+    return cbxe_workspace(nframes, boxes, shuffle, typesize);
+}
+
+int hb_cblosc_compress_boxes_batch_device(int nframes, const hb_cblosc_src_box *boxes, const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill,
+                                          int shuffle, int typesize, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    if (nframes < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
+    if (nframes == 0) return HB_OK;
+    if (!boxes || !d_src || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
+    uint8_t *w = (uint8_t *)d_work;
+    CbxeBatch B;
+    const int rc = cbxe_prepare(nframes, boxes, d_src, d_frame, cap, fill, shuffle, typesize, w, B);
+    if (rc) return rc;
+    const CbxeLayout &L = B.L;
+    // (the query knows no pointers: it stages every frame, so this layout never exceeds it -- as the encoder's own never exceeds its query)
+    const size_t query = cbxe_workspace(nframes, boxes, shuffle, typesize);
+    if (!query) return HB_ERR_BAD_ARG;                                    // (the limits are taken as the query takes them: over all frames as if every one were staged)
+    if (work_bytes < query || query < L.total || B.E.query < B.E.L.total) return HB_ERR_SHORT_BUFFER;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nj = B.jobs.size();
+    // the job records, their workgroup prefix and the fill table go up in one copy (the buffer is read before the call returns)
+    std::vector<uint8_t> up(L.upload, 0);
+    if (nj) memcpy(up.data() + L.jobs, B.jobs.data(), nj * sizeof(CbxeJob));
+    memcpy(up.data() + L.gblk, B.gblk.data(), (nj + 1) * 4);
+    memcpy(up.data() + L.fill, B.table, CBXE_FILL_BYTES);
+    hb_prof_begin("cbxe_upload", s);
+    HB_HIP_TRY(hipMemcpyAsync(w, up.data(), L.upload, hipMemcpyHostToDevice, s));
+    hb_prof_end(s);
+    if (nj) {
+        hb_prof_begin("k_cbxe_gather", s);
+        hipLaunchKernelGGL(k_cbxe_gather, dim3((unsigned)B.groups), dim3(256), 0, s, (const CbxeJob *)(w + L.jobs), (const uint32_t *)(w + L.gblk), (uint32_t)nj,
+                           (const uint8_t *)(w + L.fill), (uint32_t)typesize, cbx_recip((uint32_t)typesize));
+        hb_prof_end(s);
+    }
+    return cbe_launch_batch(nframes, B.E, shuffle, typesize, w + L.enc, d_results, s);
 }
 }  // extern "C"

@@ -1066,3 +1066,161 @@ func CBloscGetBoxBatchHIP(frames [][]byte, jobs []BoxJob) ([][]byte, []error) {
 	}
 	return out, errs
 }
+
+// SrcBox is one chunk of CBloscCompressBoxBatchHIP: the part [0, Shape[k]) along every dimension k of a C-order chunk of ChunkShape items comes
+// from Src, whose first byte is the box's first item and whose neighbours along dimension k lie SrcStride[k] BYTES apart (1 to 4 dimensions;
+// the three slices have the same length; the last stride is the typeSize).  Every other item of the chunk is the fill value.  A nil Src is a
+// chunk that is all fill.
+type SrcBox struct {
+	Src                          []byte
+	ChunkShape, Shape, SrcStride []int64
+}
+
+// CBloscCompressBoxBatchHIP writes the chunk frames of `z[...] = arr` through ONE set of kernel launches (hb_cblosc_compress_boxes_batch): a
+// chunk of an N-d array is a strided box of it, at the array's edge a partial box padded with `fill` (typeSize bytes; nil: zeros).  The
+// items of every box, and nothing of the gaps between its rows, are packed C-contiguously into one pinned slab (so an array write moves the
+// array once, not every chunk's span of it); the library gets the packed strides, pads on the device, and encodes as
+// CBloscCompressBatchHIP encodes contiguous inputs.  out[k], errs[k] are what CompressCBlosc gives for the assembled chunk.  Without a
+// device every job gets the no-device error: there is no CPU path.  Go memory is borrowed for the call only (one pinned slab each way and C
+// arrays, never Go pointers in C memory).  Like the rest of this file: written against the C ABI, it has never met a compiler.
+func CBloscCompressBoxBatchHIP(boxes []SrcBox, fill []byte, shuffle Shuffle, typeSize int) ([][]byte, []error) {
+	n := len(boxes)
+	out := make([][]byte, n)
+	errs := make([]error, n)
+	if n == 0 {
+		return out, errs
+	}
+	failAll := func(code C.int64_t) ([][]byte, []error) {
+		for k := range boxes {
+			errs[k] = hbError(code)
+		}
+		return out, errs
+	}
+	if !useHIP {
+		return failAll(C.int64_t(C.HB_ERR_NO_DEVICE))
+	}
+	if typeSize < 1 || typeSize > 255 || (fill != nil && len(fill) != typeSize) {
+		return failAll(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	for _, q := range boxes {
+		nd := len(q.ChunkShape)
+		if nd < 1 || nd > int(C.HB_CBLOSC_BOX_MAX_NDIM) || len(q.Shape) != nd || len(q.SrcStride) != nd {
+			return failAll(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+	}
+	ptrBytes := C.size_t(unsafe.Sizeof(uintptr(0)))
+	srcs := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(n) * ptrBytes))[:n:n]
+	dsts := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(n) * ptrBytes))[:n:n]
+	defer C.free(unsafe.Pointer(&srcs[0]))
+	defer C.free(unsafe.Pointer(&dsts[0]))
+	caps := make([]C.size_t, n)
+	rcs := make([]C.int64_t, n)
+	bt := make([]C.hb_cblosc_src_box, n)
+	items := make([]int64, n) // bytes of the box's items; 0: none to pack (no item, no source, or a box the library refuses)
+	var inBytes, outBytes C.size_t
+	for k, q := range boxes {
+		bt[k].ndim = C.uint32_t(len(q.ChunkShape))
+		bytes := int64(typeSize)  // of the chunk
+		packed := int64(typeSize) // of the box's items: also the packed stride of dimension d
+		span := int64(typeSize)   // of the source, first item to last
+		valid := q.SrcStride[len(q.SrcStride)-1] == int64(typeSize)
+		for d := len(q.ChunkShape) - 1; d >= 0; d-- {
+			bt[k].chunk_shape[d] = C.int64_t(q.ChunkShape[d])
+			bt[k].shape[d] = C.int64_t(q.Shape[d])
+			bt[k].src_stride[d] = C.int64_t(q.SrcStride[d]) // (a refused box keeps its strides: the library answers for it)
+			m := q.ChunkShape[d]
+			if m < 0 {
+				m = 0 // (refused by the library)
+			}
+			if m > 0 && bytes > (1<<31)/m { // (a chunk beyond 2 GiB is refused by the library: no room is needed for it)
+				bytes = 1 << 31
+			} else {
+				bytes *= m
+			}
+			if q.Shape[d] < 0 || q.Shape[d] > q.ChunkShape[d] || q.SrcStride[d] < 0 {
+				valid = false
+			}
+			if valid {
+				packed *= q.Shape[d]
+				if q.Shape[d] > 0 {
+					span += (q.Shape[d] - 1) * q.SrcStride[d]
+				}
+			}
+		}
+		if valid && bytes < 1<<31 && packed > 0 && q.Src != nil {
+			if span > int64(len(q.Src)) {
+				return failAll(C.int64_t(C.HB_ERR_BAD_ARG)) // a box that reaches beyond its source never gets to the library
+			}
+			items[k] = packed
+			stride := int64(typeSize)
+			for d := len(q.Shape) - 1; d >= 0; d-- {
+				bt[k].src_stride[d] = C.int64_t(stride)
+				stride *= q.Shape[d]
+			}
+		}
+		caps[k] = 16
+		if bytes < 1<<31 {
+			caps[k] = C.hb_cblosc_bound(C.size_t(bytes), C.int(typeSize))
+		}
+		inBytes += (C.size_t(items[k]) + 15) &^ 15
+		outBytes += caps[k]
+	}
+	slabIn, slabOut := C.hb_host_alloc(inBytes+64), C.hb_host_alloc(outBytes+64)
+	if slabIn == nil || slabOut == nil {
+		C.hb_host_free(slabIn)
+		C.hb_host_free(slabOut)
+		return failAll(C.int64_t(C.HB_ERR_HIP))
+	}
+	defer C.hb_host_free(slabIn)
+	defer C.hb_host_free(slabOut)
+	var io, oo C.size_t
+	for k, q := range boxes {
+		srcs[k] = nil
+		if items[k] > 0 {
+			srcs[k] = unsafe.Add(slabIn, uintptr(io))
+			dst := unsafe.Slice((*byte)(srcs[k]), int(items[k]))
+			// the box's rows, outer indices in C order (missing leading dimensions: one index, stride 0)
+			var sh, st [4]int64
+			nd := len(q.Shape)
+			for d := 0; d < 4; d++ {
+				sh[d], st[d] = 1, 0
+			}
+			for d := 0; d < nd; d++ {
+				sh[4-nd+d], st[4-nd+d] = q.Shape[d], q.SrcStride[d]
+			}
+			row := int(sh[3]) * typeSize
+			at := 0
+			for i0 := int64(0); i0 < sh[0]; i0++ {
+				for i1 := int64(0); i1 < sh[1]; i1++ {
+					for i2 := int64(0); i2 < sh[2]; i2++ {
+						from := int(i0*st[0] + i1*st[1] + i2*st[2])
+						copy(dst[at:at+row], q.Src[from:from+row])
+						at += row
+					}
+				}
+			}
+		} else if q.Src != nil {
+			srcs[k] = slabIn // (no item is read; a refused box is refused whatever its source)
+		}
+		dsts[k] = unsafe.Add(slabOut, uintptr(oo))
+		io += (C.size_t(items[k]) + 15) &^ 15
+		oo += caps[k]
+	}
+	var fillPtr unsafe.Pointer
+	if fill != nil {
+		fillPtr = C.malloc(C.size_t(typeSize))
+		defer C.free(fillPtr)
+		copy(unsafe.Slice((*byte)(fillPtr), typeSize), fill)
+	}
+	if rc := C.hb_cblosc_compress_boxes_batch(C.int(n), &bt[0], &srcs[0], &dsts[0], &caps[0], &rcs[0], fillPtr, C.int(shuffle), C.int(typeSize), C.int(Device)); rc != C.HB_OK {
+		return failAll(C.int64_t(rc))
+	}
+	for k := range boxes {
+		if rcs[k] < 0 {
+			errs[k] = hbError(rcs[k])
+		} else {
+			out[k] = append([]byte(nil), unsafe.Slice((*byte)(dsts[k]), int(rcs[k]))...)
+		}
+	}
+	return out, errs
+}

@@ -105,6 +105,7 @@ EXPORTS = [
     "hb_cblosc_compress_frames_batch_workspace", "hb_cblosc_compress_frames_batch_device", "hb_cblosc_compress_frames_batch",
     "hb_cblosc_getitem_frames_batch_workspace", "hb_cblosc_getitem_frames_batch_device", "hb_cblosc_getitem_frames_batch",
     "hb_cblosc_getbox_frames_batch_workspace", "hb_cblosc_getbox_frames_batch_device", "hb_cblosc_getbox_frames_batch",
+    "hb_cblosc_compress_boxes_batch_workspace", "hb_cblosc_compress_boxes_batch_device", "hb_cblosc_compress_boxes_batch",
     "hb_cblosc_accept_codecs",
     "hb_queue_create", "hb_queue_create_ex", "hb_queue_destroy", "hb_queue_compress", "hb_queue_decompress", "hb_queue_wait",
 ]
@@ -138,6 +139,21 @@ def box_job(frame, chunk_shape, start, shape, dst_stride):
         raise ValueError("chunk_shape, start, shape and dst_stride need the same number of entries, at most 4")
     a = ctypes.c_int64 * 4
     return hb_cblosc_box_job(int(frame), nd, a(*[int(v) for v in chunk_shape]), a(*[int(v) for v in start]), a(*[int(v) for v in shape]), a(*[int(v) for v in dst_stride]))
+
+
+class hb_cblosc_src_box(ctypes.Structure):
+    """include/hipblosc.h hb_cblosc_src_box: the part of a C-order chunk that comes from a strided source, anchored at the chunk's origin"""
+    _fields_ = [("ndim", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("chunk_shape", ctypes.c_int64 * 4), ("shape", ctypes.c_int64 * 4),
+                ("src_stride", ctypes.c_int64 * 4)]
+
+
+def src_box(chunk_shape, shape, src_stride):
+    """hb_cblosc_src_box from sequences of ndim entries each (the entries behind them stay 0)"""
+    nd = len(chunk_shape)
+    if not (len(shape) == len(src_stride) == nd) or nd > 4:
+        raise ValueError("chunk_shape, shape and src_stride need the same number of entries, at most 4")
+    a = ctypes.c_int64 * 4
+    return hb_cblosc_src_box(nd, 0, a(*[int(v) for v in chunk_shape]), a(*[int(v) for v in shape]), a(*[int(v) for v in src_stride]))
 
 
 _lib = None
@@ -217,6 +233,9 @@ def lib():
             "hb_cblosc_getbox_frames_batch_workspace": (sz, [i32, vp, vp, i32, vp]),
             "hb_cblosc_getbox_frames_batch_device": (i32, [i32, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp, vp]),
             "hb_cblosc_getbox_frames_batch": (i32, [i32, vp, vp, i32, vp, vp, vp, vp, i32]),
+            "hb_cblosc_compress_boxes_batch_workspace": (sz, [i32, vp, i32, i32]),
+            "hb_cblosc_compress_boxes_batch_device": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
+            "hb_cblosc_compress_boxes_batch": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32]),
             "hb_cblosc_accept_codecs": (i32, [ctypes.c_uint]),
         }
         for name, (res, args) in sig.items():
@@ -756,6 +775,108 @@ def CBloscCompressBatch(datas, shuffle=1, typesize=4, dev=None):
     rcs = i64()
     _check(L.hb_cblosc_compress_frames_batch(n, srcs, sz(*[k[1] for k in keep]), dsts, sz(*caps), rcs, int(shuffle), int(typesize), device if dev is None else dev))
     return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(n)]
+
+
+def _chunk_bytes(box, typesize):
+    """the bytes of the chunk a source box stands for, or None where the library refuses the box before it sizes anything"""
+    n = int(typesize)
+    if not 1 <= box.ndim <= 4:
+        return None
+    for k in range(box.ndim):
+        if box.chunk_shape[k] < 0:
+            return None
+        n *= box.chunk_shape[k]
+    return n if n < (1 << 31) else None
+
+
+def CBloscCompressBoxBatch(srcs, boxes, fill=None, shuffle=1, typesize=4, dev=None):
+    """Many strided N-d source boxes to chunk frames through one set of launches (include/hipblosc.h hb_cblosc_compress_boxes_batch): boxes[i]
+    (src_box) says which part of chunk i comes from srcs[i] -- a bytes-like object whose first byte is the box's first item, an address, or
+    None for a chunk that is all fill -- and with which byte strides; every other item is `fill` (typesize bytes; None: zeros).  The i-th
+    result is the frame CBloscCompress gives for the assembled chunk, or the job's error (returned, not raised, as CBloscCompressBatch does)."""
+    boxes = list(boxes)
+    n = len(boxes)
+    if len(srcs) != n:
+        raise ValueError("one source per box")
+    if fill is not None and len(fill) != typesize:
+        raise ValueError("fill needs typesize bytes")
+    if n == 0:
+        return []
+    L = lib()
+    keep, ptrs = [], []
+    for s, b in zip(srcs, boxes):
+        if s is None or isinstance(s, int):
+            ptrs.append(s)
+            continue
+        p, k, kp = _buf(s)
+        keep.append(kp)
+        span, nd = int(typesize), min(b.ndim, 4)
+        if all(b.shape[d] > 0 for d in range(nd)):
+            span += sum((b.shape[d] - 1) * b.src_stride[d] for d in range(nd))
+            if all(b.src_stride[d] >= 0 for d in range(nd)) and span > k:
+                raise ValueError("a box reaches beyond its source")
+        ptrs.append(p.value)
+    sizes = [_chunk_bytes(b, typesize) for b in boxes]
+    caps = [L.hb_cblosc_bound(c, typesize) if c is not None else 16 for c in sizes]
+    outs = [(ctypes.c_char * c)() for c in caps]
+    vp, sz, i64 = ctypes.c_void_p * n, ctypes.c_size_t * n, ctypes.c_int64 * n
+    bt = (hb_cblosc_src_box * n)(*boxes)
+    dsts = vp(*[ctypes.addressof(o) for o in outs])
+    rcs = i64()
+    fb = None if fill is None else ctypes.create_string_buffer(bytes(fill), typesize)
+    _check(L.hb_cblosc_compress_boxes_batch(n, bt, vp(*ptrs), dsts, sz(*caps), rcs, fb, int(shuffle), int(typesize), device if dev is None else dev))
+    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(n)]
+
+
+def array_jobs(array_shape, chunk_shape, typesize):
+    """The source boxes of writing a whole C-order array as chunks: one (hb_cblosc_src_box, byte offset into the array) per chunk of the grid
+    ceil(array_shape / chunk_shape), in C order of the grid, every box with the array's strides; a chunk at the array's edge carries the part
+    the array has.  The counterpart of region_jobs."""
+    nd = len(chunk_shape)
+    if len(array_shape) != nd or not 1 <= nd <= 4:
+        raise ValueError("array_shape and chunk_shape need the same number of entries, 1 to 4")
+    if any(c < 1 for c in chunk_shape) or any(a < 0 for a in array_shape):
+        raise ValueError("chunk_shape needs positive entries, array_shape none below 0")
+    strides, acc = [], int(typesize)
+    for m in reversed(array_shape):
+        strides.insert(0, acc)
+        acc *= m
+    grid = [-(-a // c) for a, c in zip(array_shape, chunk_shape)]
+    jobs = []
+    if all(grid):
+        idx = [0] * nd
+        while True:
+            shape = [min(c, a - i * c) for a, c, i in zip(array_shape, chunk_shape, idx)]
+            jobs.append((src_box(chunk_shape, shape, strides), sum(i * c * s for i, c, s in zip(idx, chunk_shape, strides))))
+            k = nd - 1
+            while k >= 0:
+                idx[k] += 1
+                if idx[k] < grid[k]:
+                    break
+                idx[k] = 0
+                k -= 1
+            if k < 0:
+                break
+    return jobs
+
+
+def CBloscWriteRegion(array_bytes, array_shape, chunk_shape, typesize, shuffle=1, fill=None, dev=None):
+    """`z[...] = arr` of a chunked array: the C-order array `array_bytes` of `array_shape` items of `typesize` bytes as C-Blosc-1 frames of
+    `chunk_shape` items each, in C order of the chunk grid -- one source box per chunk (array_jobs), all of them through one
+    hb_cblosc_compress_boxes_batch call; edge chunks are padded with `fill`.  Returns the list of frames (what CBloscReadRegion takes); raises
+    the first job's error."""
+    p, n, keep = _buf(array_bytes)
+    total = int(typesize)
+    for m in array_shape:
+        total *= m
+    if n != total:
+        raise ValueError("array_bytes does not hold array_shape items")
+    pairs = array_jobs(array_shape, chunk_shape, typesize)
+    res = CBloscCompressBoxBatch([p.value + off for _, off in pairs], [b for b, _ in pairs], fill, shuffle, typesize, dev)
+    for r in res:
+        if isinstance(r, Exception):
+            raise r
+    return res
 
 
 # ---------------------------------------------------------------------------------------------

@@ -252,6 +252,40 @@ inline std::vector<Bytes> CBloscCompressBatch(const std::vector<Bytes> &datas, s
     for (size_t k = 0; k < nf; k++) out[k].resize(rc[k] > 0 ? (size_t)rc[k] : 0);
     return out;
 }
+// many strided N-d source boxes to C-Blosc-1 chunk frames through one set of launches (hb_cblosc_compress_boxes_batch): box k is the part
+// [0, shape) of a chunk of chunk_shape items (1 to 4 dimensions, the same number of entries in all three) that is read from src with the byte
+// strides src_stride; every other item of the chunk is `fill` (typeSize bytes; nullptr: zeros).  out[k] is the frame hb_cblosc_compress writes
+// for the assembled chunk, rc[k] its byte count or the job's HB_ERR_* code (nothing is thrown per job)
+struct SrcBox { const void *src; std::vector<int64_t> chunk_shape, shape, src_stride; };
+inline std::vector<Bytes> CBloscCompressBoxBatch(const std::vector<SrcBox> &boxes, std::vector<int64_t> &rc, const void *fill = nullptr, int shuffle = 1, int typeSize = 4,
+                                                 int device = 0) {
+    const size_t nf = boxes.size();
+    std::vector<Bytes> out(nf);
+    rc.assign(nf, 0);
+    if (!nf) return out;
+    std::vector<hb_cblosc_src_box> bt(nf); std::vector<const void *> src(nf); std::vector<void *> dst(nf); std::vector<size_t> cap(nf);
+    for (size_t k = 0; k < nf; k++) {
+        const SrcBox &q = boxes[k];
+        const size_t nd = q.chunk_shape.size();
+        if (nd < 1 || nd > HB_CBLOSC_BOX_MAX_NDIM || q.shape.size() != nd || q.src_stride.size() != nd) check(HB_ERR_BAD_ARG);
+        hb_cblosc_src_box &t = bt[k];
+        t = hb_cblosc_src_box{};
+        t.ndim = (uint32_t)nd;
+        uint64_t bytes = typeSize > 0 ? (uint64_t)typeSize : 1u;
+        for (size_t d = nd; d-- > 0;) {
+            t.chunk_shape[d] = q.chunk_shape[d]; t.shape[d] = q.shape[d]; t.src_stride[d] = q.src_stride[d];
+            const uint64_t m = q.chunk_shape[d] > 0 ? (uint64_t)q.chunk_shape[d] : 0u;
+            bytes = m && bytes > (1ull << 31) / m ? (1ull << 31) : bytes * m;         // (a chunk beyond 2 GiB is refused by the library: no room is needed for it)
+        }
+        src[k] = q.src;
+        cap[k] = bytes < (1ull << 31) ? hb_cblosc_bound((size_t)bytes, typeSize) : 16;
+        out[k].resize(cap[k]);
+        dst[k] = out[k].data();
+    }
+    check(hb_cblosc_compress_boxes_batch((int)nf, bt.data(), src.data(), dst.data(), cap.data(), rc.data(), fill, shuffle, typeSize, device));
+    for (size_t k = 0; k < nf; k++) out[k].resize(rc[k] > 0 ? (size_t)rc[k] : 0);
+    return out;
+}
 inline Header GetInfo(const Bytes &data) { return ParseHeader(data); }                                            // blosc.go:306-308
 inline int GetDecompressedSize(const Bytes &data) { return (int)ParseHeader(data).NBytesOrig; }                   // blosc.go:311-317
 

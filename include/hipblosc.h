@@ -542,6 +542,55 @@ int     hb_cblosc_compress_frames_batch_device(int nframes, const void *const *d
                                                int shuffle, int typesize, void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
 int     hb_cblosc_compress_frames_batch(int nframes, const void *const *src, const size_t *n, void *const *dst, const size_t *cap, int64_t *rc,
                                         int shuffle, int typesize, int device);
+/* ---- batched C-Blosc-1 box writes: the chunk frames of `z[...] = arr` through ONE set of launches.  A chunk of an N-d array is not contiguous:
+ *      it is a strided box of the array, and at the array's edge a partial box that the store pads to the full chunk shape with the fill value.
+ *      A job is such a box: a gather assembles the chunks on the device (one launch over all of them), then the batched encode above runs over
+ *      the assembled chunks.  These are whole-frame writes: a frame stays immutable.
+ *      Item (i_0 .. i_{ndim-1}) of the chunk is read from d_src[k] + sum_m i_m * src_stride[m] if every i_m < shape[m]; otherwise it is the
+ *      fill value.  Source offsets are 64-bit (the source array may exceed 4 GiB); a stride of 0 (broadcast) is allowed; sources of different
+ *      frames may overlap, they are only read.  `fill` is a HOST pointer to typesize bytes, one fill value per batch (as there is one shuffle
+ *      and one typesize); NULL means zeros; it is read before the call returns.
+ *      Device form (rules of hb_cblosc_compress_frames_batch_device).  With C the assembled chunk, frame k is byte for byte, and with the same
+ *      hb_result, what hb_cblosc_compress_dev writes for C placed at a 16-byte-aligned address: typesize 2 / 4 / 8 with the byte shuffle and at
+ *      least one whole block always takes the fused shuffle + match route.  A chunk of 0 bytes gives the frame of n == 0.  Refused per frame,
+ *      decided on the host before the device is looked for, d_results[k].status with bytes, total_bytes and flags 0, no other frame disturbed,
+ *      in this order:
+ *        1. HB_ERR_BAD_ARG: ndim outside 1 .. HB_CBLOSC_BOX_MAX_NDIM, reserved != 0, a negative entry, shape[k] > chunk_shape[k], a negative
+ *           src_stride, or src_stride[ndim-1] != typesize;
+ *        2. HB_ERR_DATA_TOO_LARGE: the chunk's byte count overflows or is beyond what hb_cblosc_compress_dev takes (checked without overflow);
+ *        3. for n = the chunk's bytes, that call's order: HB_ERR_BAD_ARG for a NULL d_frame[k], or a NULL d_src[k] while the box has at least
+ *           one source item (an all-fill chunk needs no source); then HB_ERR_SHORT_BUFFER for cap[k] < hb_cblosc_bound(n, typesize).
+ *      Direct jobs: where shape == chunk_shape in every dimension, the source strides are the chunk's own C-order strides and d_src[k] is
+ *      16-byte aligned, the encoder reads d_src[k] itself -- no staged copy, no gather work; such a source is read up to 15 bytes before and
+ *      behind, inside its 16-byte blocks, as the compress batch documents.  For every other job the source is read ONLY at the box's items,
+ *      never in the gaps and never past the last item.
+ *      The call as a whole: exactly as hb_cblosc_compress_frames_batch_device (HB_ERR_BAD_ARG for nframes < 0, typesize outside 1..255 or
+ *      shuffle outside 0..2; then HB_OK for nframes == 0, nothing launched; HB_ERR_BAD_ARG for NULL arrays, a NULL or misaligned d_work, a NULL
+ *      d_results, or more than HB_CBLOSC_BATCH_MAX_WORK blocks, chunks, filter workgroups or gather workgroups (counted as the workspace
+ *      query counts them, which knows no pointers: over all frames as if every one were staged); HB_ERR_SHORT_BUFFER for
+ *      work_bytes below the workspace query; then HB_ERR_NO_DEVICE).  Asynchronous on `stream`, no synchronisation, no caller pointer kept.
+ *      Workspace: the query knows no pointers.  At most hb_cblosc_compress_frames_batch_workspace() for the chunk sizes + a staged copy per
+ *      frame (chunk bytes + 64, 256-aligned) + HB_CBLOSC_ENC_BOX_FRAME_BYTES * nframes.  0 when the call as a whole would be refused, 256 for
+ *      nframes == 0.
+ *      Host form: the host packs each carried box C-contiguously (box items only, no fill), all packed boxes go up in one copy, the device
+ *      form runs once with the packed strides (fill is written on the device), records and frames come down as in
+ *      hb_cblosc_compress_frames_batch.  Every job the batch did not carry or that did not end with status 0 is answered by assembling the
+ *      chunk on the host and calling hb_cblosc_compress: rc[k] is exactly what that call returns for the assembled chunk.  The refusals 1. and
+ *      2. have no assembled chunk: they are rc[k] directly.  Returns HB_OK unless the arguments as a whole are unusable. ---- */
+#define HB_CBLOSC_ENC_BOX_FRAME_BYTES 2048        /* workspace per frame beyond the compress batch's and the staged copy: the job record, the fill table */
+typedef struct hb_cblosc_src_box {
+    uint32_t ndim;             /* 1 .. HB_CBLOSC_BOX_MAX_NDIM */
+    uint32_t reserved;         /* 0 */
+    int64_t  chunk_shape[4];   /* items of the frame to write, C order; nbytes = product * typesize */
+    int64_t  shape[4];         /* the part that comes from the source, anchored at the chunk's origin: 0 <= shape[k] <= chunk_shape[k]; every other item is the fill value */
+    int64_t  src_stride[4];    /* BYTES between neighbours along dimension k in the source; >= 0; src_stride[ndim-1] == typesize */
+} hb_cblosc_src_box;           /* entries at k >= ndim are 0 */
+size_t  hb_cblosc_compress_boxes_batch_workspace(int nframes, const hb_cblosc_src_box *boxes, int shuffle, int typesize);
+int     hb_cblosc_compress_boxes_batch_device(int nframes, const hb_cblosc_src_box *boxes, const void *const *d_src,
+                                              void *const *d_frame, const size_t *cap, const void *fill, int shuffle, int typesize,
+                                              void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
+int     hb_cblosc_compress_boxes_batch(int nframes, const hb_cblosc_src_box *boxes, const void *const *src,
+                                       void *const *dst, const size_t *cap, int64_t *rc, const void *fill, int shuffle, int typesize, int device);
 
 #ifdef __cplusplus
 }
