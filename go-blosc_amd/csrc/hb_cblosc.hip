@@ -27,6 +27,7 @@
 #include "hb_cblosc_getitem_batch.h"   // the geometry of an item range, and the host side of the batched getitem
 #include "hb_cblosc_box_batch.h"       // the geometry of a box, the host side of the batched box reads, the gather's index arithmetic
 #include "hb_cblosc_enc_box_batch.h"   // the geometry of a source box, the host side of the batched box writes, the gather's index arithmetic
+#include "hb_cblosc_upd_box_batch.h"   // the geometry of an update box, the host side of the batched box updates, the overlay's index arithmetic
 
 // ---- the streams of blocks [b0, b0 + nb) (hb_cblosc_getitem_device: the blocks that cover a range; the others' bstarts entries and streams
 // are never read); stream offsets count from the first of these blocks ----
@@ -978,6 +979,31 @@ __global__ __launch_bounds__(256) void k_cbxe_gather(const CbxeJob *__restrict__
     cbxe_thread(jobs[i], table, ts, rcp_ts, blockIdx.x - gblk[i], threadIdx.x, io);
 }
 
+// ---- batched box updates (hb_cblosc_update_boxes_batch_device; the host side and the index arithmetic are hb_cblosc_upd_box_batch.h): the
+// staged chunk holds the base already (the gather's fill, or the batch decoder's bytes); the overlay puts the box's items over it. ----
+struct CbxuDeviceIO {
+    __device__ __forceinline__ void copy16(uint8_t *d, const uint8_t *s) { *(u32x4 *)d = ld16u_nt(s); }      // (the source is read once; the staged chunk is read next)
+    __device__ __forceinline__ void put(uint8_t *d, uint8_t v) { *d = v; }
+    __device__ __forceinline__ uint8_t get(const uint8_t *s) { return *s; }
+};
+// One launch over the workgroup prefix of the overlay jobs.  A thread owns one 16-byte-aligned slice of the staged chunk intersected with one
+// box row (cbxu_thread): one unaligned non-temporal 16-byte load and one aligned 16-byte store where the slice is whole, byte by byte where
+// the row's ends clip it.  Work is proportional to the box; no byte outside the box is stored, no source byte outside its items is read.
+__global__ __launch_bounds__(256) void k_cbxu_overlay(const CbxuJob *__restrict__ jobs, const uint32_t *__restrict__ oblk, uint32_t njobs) {
+    const uint32_t i = hb_owner(oblk, njobs, blockIdx.x);
+    CbxuDeviceIO io;
+    cbxu_thread(jobs[i], blockIdx.x - oblk[i], threadIdx.x, io);
+}
+// one lane per old-frame job: a base that did not decode spoils its own frame's record, whatever the encoder made of the staged bytes
+__global__ __launch_bounds__(64) void k_cbxu_finish(const uint32_t *__restrict__ fin, const hb_result *__restrict__ dres, hb_result *results, uint32_t ndec) {
+    const uint32_t i = blockIdx.x * 64u + threadIdx.x;
+    if (i >= ndec) return;
+    const int32_t st = dres[i].status;
+    if (st == 0) return;
+    hb_result *r = results + fin[i];
+    r->status = st; r->flags = 0; r->bytes = 0; r->total_bytes = 0; r->reserved = 0;
+}
+
 void hb_launch_match_selfcontained(const uint8_t *src, size_t n, void *desc, uint8_t *records, uint32_t nchunks, int accel, hipStream_t s);   // hb_lz4_enc.hip
 bool hb_launch_match_fused_selfcontained(const uint8_t *src, int typesize, void *desc, uint8_t *records, uint32_t nblk, int accel, hipStream_t s);
 void hb_launch_match_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, void *desc, uint8_t *records, uint32_t total_chunks, int accel, hipStream_t s);
@@ -1126,26 +1152,10 @@ int hb_cblosc_decompress_dev(const hb_cblosc_header *hdr, const void *d_frame, s
     return HB_OK;
 }
 
-// ---- many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_batch.h) ----
-size_t hb_cblosc_decompress_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n) {
-    CbbBatch B;
-    if (cbb_prepare(nframes, hdrs, nullptr, n, nullptr, nullptr, B, hb_cblosc_accepted())) return 0;
-    return B.L.total ? B.L.total : 256;                                   // (never 0 for a batch that is accepted)
-}
-
-int hb_cblosc_decompress_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, void *const *d_dst,
-                                             const size_t *cap, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
-    if (nframes < 0) return HB_ERR_BAD_ARG;
-    if (nframes == 0) return HB_OK;
-    if (!hdrs || !d_frame || !n || !d_dst || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
-    CbbBatch B;
-    const int rc = cbb_prepare(nframes, hdrs, d_frame, n, d_dst, cap, B, hb_cblosc_accepted());
-    if (rc) return rc;
+// everything of a batched decode behind cbb_prepare: upload, plan, the decoders, the un-filters, finish over the workspace `w` that B was laid
+// out for.  hb_cblosc_decompress_frames_batch_device and hb_cblosc_update_boxes_batch_device both end here.
+static int cbb_launch_batch(int nframes, const CbbBatch &B, uint8_t *w, hb_result *d_results, hipStream_t s) {
     const CbbLayout &L = B.L;
-    if (work_bytes < L.total) return HB_ERR_SHORT_BUFFER;
-    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
-    hipStream_t s = (hipStream_t)stream;
-    uint8_t *w = (uint8_t *)d_work;
     const size_t nf = (size_t)nframes;
     // the frame records, the prefixes and the cleared plans go up in one copy (the buffer is read before the call returns, as with hb_batch.hip's)
     std::vector<uint8_t> up(L.upload, 0);
@@ -1219,6 +1229,26 @@ int hb_cblosc_decompress_frames_batch_device(int nframes, const hb_cblosc_header
     hb_prof_end(s);
     HB_HIP_TRY(hipGetLastError());
     return HB_OK;
+}
+// ---- many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_batch.h) ----
+size_t hb_cblosc_decompress_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n) {
+    CbbBatch B;
+    if (cbb_prepare(nframes, hdrs, nullptr, n, nullptr, nullptr, B, hb_cblosc_accepted())) return 0;
+    return B.L.total ? B.L.total : 256;                                   // (never 0 for a batch that is accepted)
+}
+
+int hb_cblosc_decompress_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, void *const *d_dst,
+                                             const size_t *cap, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    if (nframes < 0) return HB_ERR_BAD_ARG;
+    if (nframes == 0) return HB_OK;
+    if (!hdrs || !d_frame || !n || !d_dst || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
+    CbbBatch B;
+    const int rc = cbb_prepare(nframes, hdrs, d_frame, n, d_dst, cap, B, hb_cblosc_accepted());
+    if (rc) return rc;
+    const CbbLayout &L = B.L;
+    if (work_bytes < L.total) return HB_ERR_SHORT_BUFFER;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    return cbb_launch_batch(nframes, B, (uint8_t *)d_work, d_results, (hipStream_t)stream);
 }
 
 // ---- blosc_getitem: items [start, start + nitems) of typesize bytes from the blocks that hold them ----
@@ -1622,5 +1652,72 @@ int hb_cblosc_compress_boxes_batch_device(int nframes, const hb_cblosc_src_box *
         hb_prof_end(s);
     }
     return cbe_launch_batch(nframes, B.E, shuffle, typesize, w + L.enc, d_results, s);
+}
+
+// ---- many update boxes, one set of launches (include/hipblosc.h; the host side is hb_cblosc_upd_box_batch.h) ----
+size_t hb_cblosc_update_boxes_batch_workspace(int njobs, const hb_cblosc_upd_box *boxes, const hb_cblosc_header *old_hdrs, const size_t *old_n, int shuffle, int typesize) {
+    return cbxu_workspace(njobs, boxes, old_hdrs, old_n, shuffle, typesize, hb_cblosc_accepted());
+}
+
+int hb_cblosc_update_boxes_batch_device(int njobs, const hb_cblosc_upd_box *boxes, const hb_cblosc_header *old_hdrs, const void *const *d_old, const size_t *old_n,
+                                        const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill, int shuffle, int typesize,
+                                        void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
+    if (njobs == 0) return HB_OK;
+    if (!boxes || !old_hdrs || !d_old || !old_n || !d_src || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
+    uint8_t *w = (uint8_t *)d_work;
+    const unsigned accept = hb_cblosc_accepted();                         // (read once: the query below judges the frames as the call does)
+    CbxuBatch B;
+    const int rc = cbxu_prepare(njobs, boxes, old_hdrs, d_old, old_n, d_src, d_frame, cap, fill, shuffle, typesize, w, accept, B);
+    if (rc) return rc;
+    const CbxuLayout &L = B.L;
+    const CbxeLayout &XL = B.X.L;
+    // (the query knows no pointers: it stages every job and decodes every old frame it cannot refuse, so this layout never exceeds it)
+    const size_t query = cbxu_workspace(njobs, boxes, old_hdrs, old_n, shuffle, typesize, accept);
+    if (!query) return HB_ERR_BAD_ARG;                                    // (the limits are taken as the query takes them)
+    if (work_bytes < query || query < L.total || B.X.E.query < B.X.E.L.total) return HB_ERR_SHORT_BUFFER;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t no = B.jobs.size(), ng = B.X.jobs.size(), nd = B.fin.size();
+    // the overlay's records, prefix and finish list, and behind them the gather's records, prefix and fill table, go up in one copy (the
+    // buffer is read before the call returns)
+    std::vector<uint8_t> up(L.box + XL.upload, 0);
+    if (no) memcpy(up.data() + L.jobs, B.jobs.data(), no * sizeof(CbxuJob));
+    if (no) memcpy(up.data() + L.oblk, B.oblk.data(), (no + 1) * 4);
+    if (nd) memcpy(up.data() + L.fin, B.fin.data(), nd * 4);
+    if (ng) memcpy(up.data() + L.box + XL.jobs, B.X.jobs.data(), ng * sizeof(CbxeJob));
+    memcpy(up.data() + L.box + XL.gblk, B.X.gblk.data(), (ng + 1) * 4);
+    memcpy(up.data() + L.box + XL.fill, B.X.table, CBXE_FILL_BYTES);
+    hb_prof_begin("cbxu_upload", s);
+    HB_HIP_TRY(hipMemcpyAsync(w, up.data(), up.size(), hipMemcpyHostToDevice, s));
+    hb_prof_end(s);
+    uint8_t *wx = w + L.box;
+    hb_result *d_dres = (hb_result *)(w + L.dres);
+    if (ng) {                                                             // the fill bases, and the whole boxes that are not read where they lie
+        hb_prof_begin("k_cbxe_gather", s);
+        hipLaunchKernelGGL(k_cbxe_gather, dim3((unsigned)B.ggroups), dim3(256), 0, s, (const CbxeJob *)(wx + XL.jobs), (const uint32_t *)(wx + XL.gblk), (uint32_t)ng,
+                           (const uint8_t *)(wx + XL.fill), (uint32_t)typesize, cbx_recip((uint32_t)typesize));
+        hb_prof_end(s);
+    }
+    if (nd) {                                                             // the old-frame bases, straight into their staged slots
+        const int st = cbb_launch_batch((int)nd, B.D, w + L.dec, d_dres, s);
+        if (st) return st;
+    }
+    if (no) {
+        hb_prof_begin("k_cbxu_overlay", s);
+        hipLaunchKernelGGL(k_cbxu_overlay, dim3((unsigned)B.ogroups), dim3(256), 0, s, (const CbxuJob *)(w + L.jobs), (const uint32_t *)(w + L.oblk), (uint32_t)no);
+        hb_prof_end(s);
+    }
+    // (the encoder reads the staged bytes of a base that failed to decode: they lie inside the workspace and may be anything, and the encoder
+    // takes any bytes; k_cbxu_finish then overrides that frame's record)
+    const int st = cbe_launch_batch(njobs, B.X.E, shuffle, typesize, wx + XL.enc, d_results, s);
+    if (st) return st;
+    if (nd) {
+        hb_prof_begin("k_cbxu_finish", s);
+        hipLaunchKernelGGL(k_cbxu_finish, dim3((unsigned)((nd + 63) / 64)), dim3(64), 0, s, (const uint32_t *)(w + L.fin), (const hb_result *)d_dres, d_results, (uint32_t)nd);
+        hb_prof_end(s);
+        HB_HIP_TRY(hipGetLastError());
+    }
+    return HB_OK;
 }
 }  // extern "C"

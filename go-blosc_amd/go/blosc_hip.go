@@ -1224,3 +1224,261 @@ func CBloscCompressBoxBatchHIP(boxes []SrcBox, fill []byte, shuffle Shuffle, typ
 	}
 	return out, errs
 }
+
+// UpdBox is one chunk of CBloscUpdateBoxBatchHIP: the box [Start[k], Start[k]+Shape[k]) along every dimension k of a C-order chunk of
+// ChunkShape items is replaced by the items of Src, whose first byte is the box's first item and whose neighbours along dimension k lie
+// SrcStride[k] BYTES apart (1 to 4 dimensions; the four slices have the same length; the last stride is the typeSize).  Every other item is
+// the old frame's, Old -- or the fill value where Old is nil: a chunk the store does not have yet.  A box that covers its whole chunk never
+// looks at Old.
+type UpdBox struct {
+	Old, Src                            []byte
+	ChunkShape, Start, Shape, SrcStride []int64
+}
+
+// CBloscUpdateBoxBatchHIP writes the NEW chunk frames of `z[a:b, c:d] = arr` through ONE set of kernel launches (hb_cblosc_update_boxes_batch):
+// per touched chunk the old frame is decoded on the device, the box's items are put over it, and the chunk is encoded again; frames stay
+// immutable, the caller swaps the new ones in.  The items of every box are packed C-contiguously into one pinned slab, the old frames that
+// are read go behind them; the library gets the packed strides.  out[k], errs[k] are what CompressCBlosc gives for the updated chunk, or
+// the decode's error for an old frame that does not decode.  `fill`: typeSize bytes; nil: zeros.  Without a device every job gets the
+// no-device error: there is no CPU path.  Go memory is borrowed for the call only (one pinned slab each way and C arrays, never Go pointers
+// in C memory).  Like the rest of this file: written against the C ABI, it has never met a compiler.
+func CBloscUpdateBoxBatchHIP(boxes []UpdBox, fill []byte, shuffle Shuffle, typeSize int) ([][]byte, []error) {
+	n := len(boxes)
+	out := make([][]byte, n)
+	errs := make([]error, n)
+	if n == 0 {
+		return out, errs
+	}
+	failAll := func(code C.int64_t) ([][]byte, []error) {
+		for k := range boxes {
+			errs[k] = hbError(code)
+		}
+		return out, errs
+	}
+	if !useHIP {
+		return failAll(C.int64_t(C.HB_ERR_NO_DEVICE))
+	}
+	if typeSize < 1 || typeSize > 255 || (fill != nil && len(fill) != typeSize) {
+		return failAll(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	for _, q := range boxes {
+		nd := len(q.ChunkShape)
+		if nd < 1 || nd > int(C.HB_CBLOSC_BOX_MAX_NDIM) || len(q.Start) != nd || len(q.Shape) != nd || len(q.SrcStride) != nd {
+			return failAll(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+	}
+	ptrBytes := C.size_t(unsafe.Sizeof(uintptr(0)))
+	srcs := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(n) * ptrBytes))[:n:n]
+	olds := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(n) * ptrBytes))[:n:n]
+	dsts := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(n) * ptrBytes))[:n:n]
+	defer C.free(unsafe.Pointer(&srcs[0]))
+	defer C.free(unsafe.Pointer(&olds[0]))
+	defer C.free(unsafe.Pointer(&dsts[0]))
+	caps := make([]C.size_t, n)
+	oldN := make([]C.size_t, n)
+	rcs := make([]C.int64_t, n)
+	bt := make([]C.hb_cblosc_upd_box, n)
+	items := make([]int64, n) // bytes of the box's items; 0: none to pack (no item, no source, or a box the library refuses)
+	whole := make([]bool, n)  // the box covers its chunk: the old frame is not looked at
+	var inBytes, outBytes C.size_t
+	for k, q := range boxes {
+		bt[k].ndim = C.uint32_t(len(q.ChunkShape))
+		bytes := int64(typeSize)  // of the chunk
+		packed := int64(typeSize) // of the box's items: also the packed stride of dimension d
+		span := int64(typeSize)   // of the source, first item to last
+		valid := q.SrcStride[len(q.SrcStride)-1] == int64(typeSize)
+		whole[k] = true
+		for d := len(q.ChunkShape) - 1; d >= 0; d-- {
+			bt[k].chunk_shape[d] = C.int64_t(q.ChunkShape[d])
+			bt[k].start[d] = C.int64_t(q.Start[d])
+			bt[k].shape[d] = C.int64_t(q.Shape[d])
+			bt[k].src_stride[d] = C.int64_t(q.SrcStride[d]) // (a refused box keeps its strides: the library answers for it)
+			m := q.ChunkShape[d]
+			if m < 0 {
+				m = 0 // (refused by the library)
+			}
+			if m > 0 && bytes > (1<<31)/m { // (a chunk beyond 2 GiB is refused by the library: no room is needed for it)
+				bytes = 1 << 31
+			} else {
+				bytes *= m
+			}
+			if q.Start[d] != 0 || q.Shape[d] != q.ChunkShape[d] {
+				whole[k] = false
+			}
+			if q.Start[d] < 0 || q.Shape[d] < 0 || q.Start[d] > q.ChunkShape[d] || q.Shape[d] > q.ChunkShape[d]-q.Start[d] || q.SrcStride[d] < 0 {
+				valid = false
+			}
+			if valid {
+				packed *= q.Shape[d]
+				if q.Shape[d] > 0 {
+					span += (q.Shape[d] - 1) * q.SrcStride[d]
+				}
+			}
+		}
+		if valid && bytes < 1<<31 && packed > 0 && q.Src != nil {
+			if span > int64(len(q.Src)) {
+				return failAll(C.int64_t(C.HB_ERR_BAD_ARG)) // a box that reaches beyond its source never gets to the library
+			}
+			items[k] = packed
+			stride := int64(typeSize)
+			for d := len(q.Shape) - 1; d >= 0; d-- {
+				bt[k].src_stride[d] = C.int64_t(stride)
+				stride *= q.Shape[d]
+			}
+		}
+		caps[k] = 16
+		if bytes < 1<<31 {
+			caps[k] = C.hb_cblosc_bound(C.size_t(bytes), C.int(typeSize))
+		}
+		inBytes += (C.size_t(items[k]) + 15) &^ 15
+		if q.Old != nil && !whole[k] {
+			oldN[k] = C.size_t(len(q.Old))
+			inBytes += (oldN[k] + 15) &^ 15
+		}
+		outBytes += caps[k]
+	}
+	slabIn, slabOut := C.hb_host_alloc(inBytes+64), C.hb_host_alloc(outBytes+64)
+	if slabIn == nil || slabOut == nil {
+		C.hb_host_free(slabIn)
+		C.hb_host_free(slabOut)
+		return failAll(C.int64_t(C.HB_ERR_HIP))
+	}
+	defer C.hb_host_free(slabIn)
+	defer C.hb_host_free(slabOut)
+	var io, oo C.size_t
+	for k, q := range boxes {
+		srcs[k] = nil
+		if items[k] > 0 {
+			srcs[k] = unsafe.Add(slabIn, uintptr(io))
+			dst := unsafe.Slice((*byte)(srcs[k]), int(items[k]))
+			// the box's rows, outer indices in C order (missing leading dimensions: one index, stride 0)
+			var sh, st [4]int64
+			nd := len(q.Shape)
+			for d := 0; d < 4; d++ {
+				sh[d], st[d] = 1, 0
+			}
+			for d := 0; d < nd; d++ {
+				sh[4-nd+d], st[4-nd+d] = q.Shape[d], q.SrcStride[d]
+			}
+			row := int(sh[3]) * typeSize
+			at := 0
+			for i0 := int64(0); i0 < sh[0]; i0++ {
+				for i1 := int64(0); i1 < sh[1]; i1++ {
+					for i2 := int64(0); i2 < sh[2]; i2++ {
+						from := int(i0*st[0] + i1*st[1] + i2*st[2])
+						copy(dst[at:at+row], q.Src[from:from+row])
+						at += row
+					}
+				}
+			}
+		} else if q.Src != nil {
+			srcs[k] = slabIn // (no item is read; a refused box is refused whatever its source)
+		}
+		io += (C.size_t(items[k]) + 15) &^ 15
+		olds[k] = nil
+		if q.Old != nil && !whole[k] {
+			olds[k] = unsafe.Add(slabIn, uintptr(io))
+			copy(unsafe.Slice((*byte)(olds[k]), len(q.Old)), q.Old)
+			io += (oldN[k] + 15) &^ 15
+		}
+		dsts[k] = unsafe.Add(slabOut, uintptr(oo))
+		oo += caps[k]
+	}
+	var fillPtr unsafe.Pointer
+	if fill != nil {
+		fillPtr = C.malloc(C.size_t(typeSize))
+		defer C.free(fillPtr)
+		copy(unsafe.Slice((*byte)(fillPtr), typeSize), fill)
+	}
+	if rc := C.hb_cblosc_update_boxes_batch(C.int(n), &bt[0], &olds[0], &oldN[0], &srcs[0], &dsts[0], &caps[0], &rcs[0], fillPtr, C.int(shuffle), C.int(typeSize), C.int(Device)); rc != C.HB_OK {
+		return failAll(C.int64_t(rc))
+	}
+	for k := range boxes {
+		if rcs[k] < 0 {
+			errs[k] = hbError(rcs[k])
+		} else {
+			out[k] = append([]byte(nil), unsafe.Slice((*byte)(dsts[k]), int(rcs[k]))...)
+		}
+	}
+	return out, errs
+}
+
+// CBloscUpdateRegion is `z[lo_0:hi_0, lo_1:hi_1 ...] = data` of a chunked array whose chunks are the C-Blosc-1 frames `frames`, in C order of
+// the chunk grid ceil(arrayShape / chunkShape); a nil frame is a chunk the store does not have, its base is `fill`.  `region` holds a
+// (lo, hi) pair per dimension in items of the whole array, `data` the region's items in C order.  One update box per touched chunk, all of
+// them through one CBloscUpdateBoxBatchHIP call.  It returns the new frames of the touched chunks keyed by their grid index and leaves
+// `frames` as it is; the first job's error ends it.
+func CBloscUpdateRegion(frames [][]byte, arrayShape, chunkShape []int64, region [][2]int64, data []byte, typeSize int, shuffle Shuffle, fill []byte) (map[int][]byte, error) {
+	nd := len(chunkShape)
+	if nd < 1 || nd > int(C.HB_CBLOSC_BOX_MAX_NDIM) || len(arrayShape) != nd || len(region) != nd || typeSize < 1 {
+		return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	grid := make([]int64, nd)
+	strides := make([]int64, nd)
+	lo := make([]int64, nd) // the first and one past the last chunk the region touches, per dimension
+	hi := make([]int64, nd)
+	total := int64(typeSize)
+	nchunks := int64(1)
+	for d := nd - 1; d >= 0; d-- {
+		if chunkShape[d] < 1 || arrayShape[d] < 0 || region[d][0] < 0 || region[d][1] < region[d][0] || region[d][1] > arrayShape[d] {
+			return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+		grid[d] = (arrayShape[d] + chunkShape[d] - 1) / chunkShape[d]
+		nchunks *= grid[d]
+		strides[d] = total
+		total *= region[d][1] - region[d][0]
+	}
+	if int64(len(data)) != total || int64(len(frames)) != nchunks {
+		return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	res := map[int][]byte{}
+	if total == 0 {
+		return res, nil
+	}
+	for d := 0; d < nd; d++ {
+		lo[d] = region[d][0] / chunkShape[d]
+		hi[d] = (region[d][1]-1)/chunkShape[d] + 1
+	}
+	idx := append([]int64(nil), lo...)
+	var boxes []UpdBox
+	var where []int
+	for {
+		f, off := int64(0), int64(0)
+		start := make([]int64, nd)
+		shape := make([]int64, nd)
+		for d := 0; d < nd; d++ {
+			f = f*grid[d] + idx[d]
+			a, b := region[d][0], region[d][1]
+			if c := idx[d] * chunkShape[d]; c > a {
+				a = c
+			}
+			if c := (idx[d] + 1) * chunkShape[d]; c < b {
+				b = c
+			}
+			start[d] = a - idx[d]*chunkShape[d]
+			shape[d] = b - a
+			off += (a - region[d][0]) * strides[d]
+		}
+		boxes = append(boxes, UpdBox{Old: frames[f], Src: data[off:], ChunkShape: chunkShape, Start: start, Shape: shape, SrcStride: strides})
+		where = append(where, int(f))
+		d := nd - 1
+		for ; d >= 0; d-- {
+			idx[d]++
+			if idx[d] < hi[d] {
+				break
+			}
+			idx[d] = lo[d]
+		}
+		if d < 0 {
+			break
+		}
+	}
+	out, errs := CBloscUpdateBoxBatchHIP(boxes, fill, shuffle, typeSize)
+	for k := range boxes {
+		if errs[k] != nil {
+			return nil, errs[k]
+		}
+		res[where[k]] = out[k]
+	}
+	return res, nil
+}

@@ -106,6 +106,7 @@ EXPORTS = [
     "hb_cblosc_getitem_frames_batch_workspace", "hb_cblosc_getitem_frames_batch_device", "hb_cblosc_getitem_frames_batch",
     "hb_cblosc_getbox_frames_batch_workspace", "hb_cblosc_getbox_frames_batch_device", "hb_cblosc_getbox_frames_batch",
     "hb_cblosc_compress_boxes_batch_workspace", "hb_cblosc_compress_boxes_batch_device", "hb_cblosc_compress_boxes_batch",
+    "hb_cblosc_update_boxes_batch_workspace", "hb_cblosc_update_boxes_batch_device", "hb_cblosc_update_boxes_batch",
     "hb_cblosc_accept_codecs",
     "hb_queue_create", "hb_queue_create_ex", "hb_queue_destroy", "hb_queue_compress", "hb_queue_decompress", "hb_queue_wait",
 ]
@@ -154,6 +155,21 @@ def src_box(chunk_shape, shape, src_stride):
         raise ValueError("chunk_shape, shape and src_stride need the same number of entries, at most 4")
     a = ctypes.c_int64 * 4
     return hb_cblosc_src_box(nd, 0, a(*[int(v) for v in chunk_shape]), a(*[int(v) for v in shape]), a(*[int(v) for v in src_stride]))
+
+
+class hb_cblosc_upd_box(ctypes.Structure):
+    """include/hipblosc.h hb_cblosc_upd_box: the box of a C-order chunk that a strided source replaces, anywhere inside the chunk"""
+    _fields_ = [("ndim", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("chunk_shape", ctypes.c_int64 * 4), ("start", ctypes.c_int64 * 4),
+                ("shape", ctypes.c_int64 * 4), ("src_stride", ctypes.c_int64 * 4)]
+
+
+def upd_box(chunk_shape, start, shape, strides):
+    """hb_cblosc_upd_box from sequences of ndim entries each (the entries behind them stay 0)"""
+    nd = len(chunk_shape)
+    if not (len(start) == len(shape) == len(strides) == nd) or nd > 4:
+        raise ValueError("chunk_shape, start, shape and strides need the same number of entries, at most 4")
+    a = ctypes.c_int64 * 4
+    return hb_cblosc_upd_box(nd, 0, a(*[int(v) for v in chunk_shape]), a(*[int(v) for v in start]), a(*[int(v) for v in shape]), a(*[int(v) for v in strides]))
 
 
 _lib = None
@@ -236,6 +252,9 @@ def lib():
             "hb_cblosc_compress_boxes_batch_workspace": (sz, [i32, vp, i32, i32]),
             "hb_cblosc_compress_boxes_batch_device": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
             "hb_cblosc_compress_boxes_batch": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32]),
+            "hb_cblosc_update_boxes_batch_workspace": (sz, [i32, vp, vp, vp, i32, i32]),
+            "hb_cblosc_update_boxes_batch_device": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
+            "hb_cblosc_update_boxes_batch": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32]),
             "hb_cblosc_accept_codecs": (i32, [ctypes.c_uint]),
         }
         for name, (res, args) in sig.items():
@@ -877,6 +896,119 @@ def CBloscWriteRegion(array_bytes, array_shape, chunk_shape, typesize, shuffle=1
         if isinstance(r, Exception):
             raise r
     return res
+
+
+def CBloscUpdateBoxBatch(olds, srcs, boxes, fill=None, shuffle=1, typesize=4, dev=None):
+    """Many box updates of chunk frames through one set of launches (include/hipblosc.h hb_cblosc_update_boxes_batch): boxes[i] (upd_box) says
+    which box of chunk i is replaced by the items at srcs[i] -- a bytes-like object whose first byte is the box's first item, an address, or
+    None for a box without items -- and with which byte strides; every other item of the new chunk is the old frame's olds[i], or `fill`
+    (typesize bytes; None: zeros) where olds[i] is None: the store has no such chunk yet.  A box that covers its whole chunk never looks at
+    olds[i].  The i-th result is the NEW frame -- what CBloscCompress gives for the updated chunk -- or the job's error (returned, not raised,
+    as CBloscCompressBoxBatch does).  The old frames are not changed."""
+    boxes = list(boxes)
+    n = len(boxes)
+    if len(srcs) != n or len(olds) != n:
+        raise ValueError("one old frame (or None) and one source per box")
+    if fill is not None and len(fill) != typesize:
+        raise ValueError("fill needs typesize bytes")
+    if n == 0:
+        return []
+    L = lib()
+    keep, ptrs, optr, olen = [], [], [], []
+    for s, b in zip(srcs, boxes):
+        if s is None or isinstance(s, int):
+            ptrs.append(s)
+            continue
+        p, k, kp = _buf(s)
+        keep.append(kp)
+        span, nd = int(typesize), min(b.ndim, 4)
+        if all(b.shape[d] > 0 for d in range(nd)):
+            span += sum((b.shape[d] - 1) * b.src_stride[d] for d in range(nd))
+            if all(b.src_stride[d] >= 0 for d in range(nd)) and span > k:
+                raise ValueError("a box reaches beyond its source")
+        ptrs.append(p.value)
+    for o in olds:
+        if o is None:
+            optr.append(None)
+            olen.append(0)
+            continue
+        p, k, kp = _buf(o)
+        keep.append(kp)
+        optr.append(p.value)
+        olen.append(k)
+    sizes = [_chunk_bytes(b, typesize) for b in boxes]
+    caps = [L.hb_cblosc_bound(c, typesize) if c is not None else 16 for c in sizes]
+    outs = [(ctypes.c_char * c)() for c in caps]
+    vp, sz, i64 = ctypes.c_void_p * n, ctypes.c_size_t * n, ctypes.c_int64 * n
+    bt = (hb_cblosc_upd_box * n)(*boxes)
+    dsts = vp(*[ctypes.addressof(o) for o in outs])
+    rcs = i64()
+    fb = None if fill is None else ctypes.create_string_buffer(bytes(fill), typesize)
+    _check(L.hb_cblosc_update_boxes_batch(n, bt, vp(*optr), sz(*olen), vp(*ptrs), dsts, sz(*caps), rcs, fb, int(shuffle), int(typesize), device if dev is None else dev))
+    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(n)]
+
+
+def update_jobs(array_shape, chunk_shape, region, typesize):
+    """The update boxes of `z[lo_0:hi_0, lo_1:hi_1 ...] = data` on a chunked array: one (grid index, hb_cblosc_upd_box, byte offset) per chunk
+    that `region` -- a (lo, hi) pair per dimension, in items of the whole array -- touches.  The grid is ceil(array_shape / chunk_shape) and
+    the grid index counts its chunks in C order; the box has the strides of a C-order array of the region's shape, and the offset is that of
+    the box's first item in such an array.  A chunk at the array's edge keeps the full chunk shape, as in array_jobs.  The counterpart of
+    region_jobs for writing."""
+    nd = len(chunk_shape)
+    if not (len(array_shape) == len(region) == nd) or not 1 <= nd <= 4:
+        raise ValueError("array_shape, chunk_shape and region need the same number of entries, 1 to 4")
+    if any(c < 1 for c in chunk_shape) or any(a < 0 for a in array_shape):
+        raise ValueError("chunk_shape needs positive entries, array_shape none below 0")
+    if any(lo < 0 or hi < lo or hi > a for (lo, hi), a in zip(region, array_shape)):
+        raise ValueError("the region lies outside the array")
+    grid = [-(-a // c) for a, c in zip(array_shape, chunk_shape)]
+    out_shape = [hi - lo for lo, hi in region]
+    strides, acc = [], int(typesize)
+    for m in reversed(out_shape):
+        strides.insert(0, acc)
+        acc *= m
+    jobs = []
+    if all(out_shape):
+        spans = [range(lo // c, (hi - 1) // c + 1) for (lo, hi), c in zip(region, chunk_shape)]
+        idx = [r.start for r in spans]
+        while True:
+            f, start, shape, off = 0, [], [], 0
+            for k in range(nd):
+                f = f * grid[k] + idx[k]
+                a, b = max(region[k][0], idx[k] * chunk_shape[k]), min(region[k][1], (idx[k] + 1) * chunk_shape[k])
+                start.append(a - idx[k] * chunk_shape[k])
+                shape.append(b - a)
+                off += (a - region[k][0]) * strides[k]
+            jobs.append((f, upd_box(chunk_shape, start, shape, strides), off))
+            k = nd - 1
+            while k >= 0:
+                idx[k] += 1
+                if idx[k] < spans[k].stop:
+                    break
+                idx[k] = spans[k].start
+                k -= 1
+            if k < 0:
+                break
+    return jobs
+
+
+def CBloscUpdateRegion(frames, array_shape, chunk_shape, region, data, typesize, shuffle=1, fill=None, dev=None):
+    """`z[lo_0:hi_0, lo_1:hi_1 ...] = data` of a chunked array whose chunks are the C-Blosc-1 frames `frames`, in C order of the chunk grid
+    ceil(array_shape / chunk_shape) (None: a chunk the store does not have, its base is `fill`): `data` is the region's bytes in C order.  One
+    update box per touched chunk (update_jobs), all of them through one hb_cblosc_update_boxes_batch call.  Returns {grid index: new frame} for
+    the touched chunks and leaves `frames` as it is -- a frame is immutable, the caller swaps the new ones in; raises the first job's error."""
+    p, n, keep = _buf(data)
+    total = int(typesize)
+    for lo, hi in region:
+        total *= hi - lo
+    jobs = update_jobs(array_shape, chunk_shape, region, typesize)
+    if n != total:
+        raise ValueError("data does not hold the region's items")
+    res = CBloscUpdateBoxBatch([frames[f] for f, _, _ in jobs], [p.value + off for _, _, off in jobs], [b for _, b, _ in jobs], fill, shuffle, typesize, dev)
+    for r in res:
+        if isinstance(r, Exception):
+            raise r
+    return {f: r for (f, _, _), r in zip(jobs, res)}
 
 
 # ---------------------------------------------------------------------------------------------

@@ -286,6 +286,42 @@ inline std::vector<Bytes> CBloscCompressBoxBatch(const std::vector<SrcBox> &boxe
     for (size_t k = 0; k < nf; k++) out[k].resize(rc[k] > 0 ? (size_t)rc[k] : 0);
     return out;
 }
+// many box updates of C-Blosc-1 chunk frames through one set of launches (hb_cblosc_update_boxes_batch): job k replaces the box [start, start +
+// shape) of a chunk of chunk_shape items (1 to 4 dimensions, the same number of entries in all four) by the items read from src with the byte
+// strides src_stride; every other item is the old frame's (`old`, n bytes), or `fill` (typeSize bytes; nullptr: zeros) where old == nullptr
+// and old_n == 0: a chunk the store does not have yet.  A box that covers its whole chunk never looks at `old`.  out[k] is the NEW frame --
+// what hb_cblosc_compress writes for the updated chunk; the old frame is not changed -- rc[k] its byte count or the job's HB_ERR_* code
+// (nothing is thrown per job)
+struct UpdBox { const void *old; size_t old_n; const void *src; std::vector<int64_t> chunk_shape, start, shape, src_stride; };
+inline std::vector<Bytes> CBloscUpdateBoxBatch(const std::vector<UpdBox> &boxes, std::vector<int64_t> &rc, const void *fill = nullptr, int shuffle = 1, int typeSize = 4,
+                                               int device = 0) {
+    const size_t nj = boxes.size();
+    std::vector<Bytes> out(nj);
+    rc.assign(nj, 0);
+    if (!nj) return out;
+    std::vector<hb_cblosc_upd_box> bt(nj); std::vector<const void *> old(nj), src(nj); std::vector<void *> dst(nj); std::vector<size_t> on(nj), cap(nj);
+    for (size_t k = 0; k < nj; k++) {
+        const UpdBox &q = boxes[k];
+        const size_t nd = q.chunk_shape.size();
+        if (nd < 1 || nd > HB_CBLOSC_BOX_MAX_NDIM || q.start.size() != nd || q.shape.size() != nd || q.src_stride.size() != nd) check(HB_ERR_BAD_ARG);
+        hb_cblosc_upd_box &t = bt[k];
+        t = hb_cblosc_upd_box{};
+        t.ndim = (uint32_t)nd;
+        uint64_t bytes = typeSize > 0 ? (uint64_t)typeSize : 1u;
+        for (size_t d = nd; d-- > 0;) {
+            t.chunk_shape[d] = q.chunk_shape[d]; t.start[d] = q.start[d]; t.shape[d] = q.shape[d]; t.src_stride[d] = q.src_stride[d];
+            const uint64_t m = q.chunk_shape[d] > 0 ? (uint64_t)q.chunk_shape[d] : 0u;
+            bytes = m && bytes > (1ull << 31) / m ? (1ull << 31) : bytes * m;         // (a chunk beyond 2 GiB is refused by the library: no room is needed for it)
+        }
+        old[k] = q.old; on[k] = q.old_n; src[k] = q.src;
+        cap[k] = bytes < (1ull << 31) ? hb_cblosc_bound((size_t)bytes, typeSize) : 16;
+        out[k].resize(cap[k]);
+        dst[k] = out[k].data();
+    }
+    check(hb_cblosc_update_boxes_batch((int)nj, bt.data(), old.data(), on.data(), src.data(), dst.data(), cap.data(), rc.data(), fill, shuffle, typeSize, device));
+    for (size_t k = 0; k < nj; k++) out[k].resize(rc[k] > 0 ? (size_t)rc[k] : 0);
+    return out;
+}
 inline Header GetInfo(const Bytes &data) { return ParseHeader(data); }                                            // blosc.go:306-308
 inline int GetDecompressedSize(const Bytes &data) { return (int)ParseHeader(data).NBytesOrig; }                   // blosc.go:311-317
 

@@ -591,6 +591,65 @@ int     hb_cblosc_compress_boxes_batch_device(int nframes, const hb_cblosc_src_b
                                               void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
 int     hb_cblosc_compress_boxes_batch(int nframes, const hb_cblosc_src_box *boxes, const void *const *src,
                                        void *const *dst, const size_t *cap, int64_t *rc, const void *fill, int shuffle, int typesize, int device);
+/* ---- batched C-Blosc-1 box updates: `z[a:b, c:d] = arr` where the region cuts through chunks, through ONE set of launches.  Frames stay
+ *      immutable: an update writes a NEW frame per touched chunk (old frame + strided source box -> new frame) and the caller swaps it in.
+ *      One job is one chunk: one old frame, one source box, one new frame.  With C' the chunk after the update, item (i_0 .. i_{ndim-1}) of C'
+ *      is read from d_src[k] + sum_m (i_m - start[m]) * src_stride[m] where every start[m] <= i_m < start[m] + shape[m] (64-bit offsets, a
+ *      stride of 0 allowed, read ONLY at the box's items); every other item is the BASE, one of three, decided on the host:
+ *        - no base: the box covers the whole chunk (start 0 and shape == chunk_shape in every dimension).  The old frame is not parsed,
+ *          uploaded or read; old_hdrs[k], d_old[k], old_n[k] may be anything.  The job is exactly the box-write job of the same shape and
+ *          strides, its direct route included;
+ *        - fill: d_old[k] == NULL && old_n[k] == 0, the store has no such chunk yet.  The base is the fill value (`fill`: a HOST pointer to
+ *          typesize bytes, one per batch, NULL means zeros, read before the call returns); old_hdrs[k] is ignored;
+ *        - old frame: the base is what hb_cblosc_decompress_frames_batch_device decodes from (old_hdrs[k], d_old[k], old_n[k]): a frame of
+ *          any writer and block size, LZ4 or (when accepted: hb_cblosc_accept_codecs is honoured) BloscLZ, memcpyed, shuffled, bit-shuffled
+ *          or neither.  A box with some shape[k] == 0 over an old frame is legal: it re-encodes the old chunk with this batch's shuffle.
+ *      Device form (rules of hb_cblosc_compress_boxes_batch_device).  Frame k is byte for byte, and with the same hb_result, what
+ *      hb_cblosc_compress_dev writes for C' placed at a 16-byte-aligned address (typesize 2 / 4 / 8 with the byte shuffle and at least one
+ *      whole block takes the fused route).  A chunk of 0 bytes gives the frame of n == 0.  Refused per job, decided on the host before the
+ *      device is looked for, d_results[k].status with bytes, total_bytes and flags 0, no other job disturbed, in this order:
+ *        1. HB_ERR_BAD_ARG: ndim outside 1 .. HB_CBLOSC_BOX_MAX_NDIM, reserved != 0, a negative entry, a box outside the chunk, a negative
+ *           src_stride, or src_stride[ndim-1] != typesize;
+ *        2. HB_ERR_DATA_TOO_LARGE: the chunk's byte count overflows or is beyond what hb_cblosc_compress_dev takes (as for box writes);
+ *        3. for an old-frame base: HB_ERR_BAD_ARG for old_hdrs[k].typesize != typesize or old_hdrs[k].nbytes != the chunk's bytes; then the
+ *           per-frame refusals of hb_cblosc_decompress_frames_batch_device for that frame with a destination of exactly the chunk's bytes,
+ *           in that function's order (the codec refusal and a NULL d_old[k] with old_n[k] != 0 among them);
+ *        4. hb_cblosc_compress_dev's for the chunk's bytes: HB_ERR_BAD_ARG for a NULL d_frame[k], or a NULL d_src[k] while the box has at
+ *           least one item; then HB_ERR_SHORT_BUFFER for cap[k] < hb_cblosc_bound(chunk bytes, typesize).
+ *      Device-time failure: if the plan or a stream of the old frame fails, d_results[k] is {HB_ERR_DECOMPRESSION_FAILED, flags 0, bytes 0,
+ *      total_bytes 0}; the first hb_cblosc_bound bytes of d_frame[k] are then unspecified, nothing beyond them is touched, no other job is
+ *      disturbed.  THE CALLER HAS TO LOOK AT d_results[k] BEFORE IT SWAPS d_frame[k] IN: a frame is only valid where its record's status is 0.
+ *      The call as a whole: exactly as hb_cblosc_compress_boxes_batch_device (HB_ERR_BAD_ARG for njobs < 0, typesize outside 1..255 or shuffle
+ *      outside 0..2; then HB_OK for njobs == 0, nothing launched; HB_ERR_BAD_ARG for NULL arrays, a NULL or misaligned d_work, a NULL
+ *      d_results, or more than HB_CBLOSC_BATCH_MAX_WORK of any kind the encoder or the decoder counts or of overlay workgroups, counted as
+ *      the workspace query counts them; HB_ERR_SHORT_BUFFER for work_bytes below the query; then HB_ERR_NO_DEVICE).  Asynchronous on `stream`,
+ *      no synchronisation, no caller pointer kept.
+ *      Workspace: the query knows no pointers, but it knows old_hdrs and old_n: a job with old_n[k] == 0 is charged as a fill base, every job
+ *      is staged.  At most hb_cblosc_compress_boxes_batch_workspace() for the chunk sizes + hb_cblosc_decompress_frames_batch_workspace() over
+ *      the old frames that are decoded + one hb_result per decoded frame + HB_CBLOSC_UPD_BOX_JOB_BYTES * njobs.  0 when the call as a whole
+ *      would be refused, 256 for njobs == 0.
+ *      Host form: the old frames of the carried old-frame jobs go up (frames exactly adjacent in host memory in one copy), the packed boxes
+ *      (items only) go up in one copy, the device form runs once, records and frames come down as in hb_cblosc_compress_frames_batch.  A job
+ *      the batch did not carry or that did not end with status 0 is answered on the host: hb_cblosc_decompress of the old frame into the
+ *      chunk (or the fill), the naive overlay loops, hb_cblosc_compress; rc[k] is exactly what that sequence returns: the frame's bytes, the
+ *      decode's error (a frame that does not parse: hb_cblosc_parse_header's answer; then HB_ERR_BAD_ARG for a header whose typesize or
+ *      nbytes is not the chunk's) or the compress call's.  The refusals 1. and 2. are rc[k] directly.  Returns HB_OK unless the arguments as
+ *      a whole are unusable. ---- */
+#define HB_CBLOSC_UPD_BOX_JOB_BYTES 2048          /* workspace per job beyond the parts named above: the overlay record, prefix and finish words, alignment */
+typedef struct hb_cblosc_upd_box {
+    uint32_t ndim;             /* 1 .. HB_CBLOSC_BOX_MAX_NDIM */
+    uint32_t reserved;         /* 0 */
+    int64_t  chunk_shape[4];   /* items of the chunk, C order */
+    int64_t  start[4], shape[4];   /* the box inside the chunk: 0 <= start[k], 0 <= shape[k], start[k] + shape[k] <= chunk_shape[k] */
+    int64_t  src_stride[4];    /* BYTES between neighbours in the source; >= 0; src_stride[ndim-1] == typesize */
+} hb_cblosc_upd_box;           /* entries at k >= ndim are 0 */
+size_t  hb_cblosc_update_boxes_batch_workspace(int njobs, const hb_cblosc_upd_box *boxes, const hb_cblosc_header *old_hdrs, const size_t *old_n,
+                                               int shuffle, int typesize);
+int     hb_cblosc_update_boxes_batch_device(int njobs, const hb_cblosc_upd_box *boxes, const hb_cblosc_header *old_hdrs, const void *const *d_old,
+                                            const size_t *old_n, const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill,
+                                            int shuffle, int typesize, void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
+int     hb_cblosc_update_boxes_batch(int njobs, const hb_cblosc_upd_box *boxes, const void *const *old, const size_t *old_n, const void *const *src,
+                                     void *const *dst, const size_t *cap, int64_t *rc, const void *fill, int shuffle, int typesize, int device);
 
 #ifdef __cplusplus
 }
