@@ -22,6 +22,7 @@
 #include "hb_cblosc_enc_batch.h"
 #include "hb_cblosc_getitem_batch.h"
 #include "hb_cblosc_box_batch.h"
+#include "hb_cblosc_slice_batch.h"
 #include "hb_cblosc_enc_box_batch.h"
 #include "hb_cblosc_upd_box_batch.h"
 #include <vector>
@@ -710,23 +711,26 @@ int hb_cblosc_getitem_frames_batch(int nframes, const void *const *frame, const 
 // Many boxes of many C-Blosc-1 frames (include/hipblosc.h).  cbx_host_plan (hb_cblosc_box_batch.h) answers what the host refuses and says which
 // jobs the batch carries, which frames go up and where each box lies, C-contiguous, in the packed device buffer: every frame a carried job
 // reads goes up once, the device form runs once over the carried jobs, the records come down in one copy and the packed boxes in one copy, and
-// the rows are placed at their strides here.  No job is answered row by row.
-static int cbx_host_call(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_cblosc_box_job *jobs, void *const *dst, const size_t *cap,
-                                  int64_t *rc, int device) {
+// the rows are placed at their strides here.  No job is answered row by row.  The stepped selections of hb_cblosc_getslice_frames_batch go the
+// same way with their own plan, query and device form (`plan`, `query`, `run`).
+extern "C++" {
+template <class JOB, class PLAN, class QUERY, class RUN>
+static int cbx_host_call(int nframes, const void *const *frame, const size_t *n, int njobs, const JOB *jobs, void *const *dst, const size_t *cap,
+                         int64_t *rc, int device, PLAN plan, QUERY query, RUN run) {
     if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
     if (njobs == 0) return HB_OK;
     if (!frame || !n || !jobs || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
     for (int j = 0; j < njobs; j++)
         if (jobs[j].frame >= (uint32_t)nframes) return HB_ERR_BAD_ARG;
-    CbxHostPlan P;
-    cbx_host_plan(nframes, frame, n, njobs, jobs, dst, cap, P, hb_cblosc_accepted());
+    CbxHostPlanOf<JOB> P;
+    plan(nframes, frame, n, njobs, jobs, dst, cap, P, hb_cblosc_accepted());
     for (int j = 0; j < njobs; j++) rc[j] = P.status[(size_t)j];
     const int m = (int)P.carried.size();
     if (m == 0) return HB_OK;
     auto all = [&](int64_t st) { for (int j : P.carried) rc[j] = st; return HB_OK; };
     const int sel = hb_select_device(device);
     if (sel != HB_OK) return all(sel);
-    const size_t wb = hb_cblosc_getbox_frames_batch_workspace(nframes, P.hd.data(), n, m, P.pj.data());
+    const size_t wb = query(nframes, P.hd.data(), n, m, P.pj.data());
     if (!wb) return all(HB_ERR_BAD_ARG);                                // (a batch beyond the 32-bit limits: the caller has to split it)
     Scratch sc(device);
     uint8_t *d_in = sc.get(P.in_bytes + 256), *d_out = sc.get(P.out_bytes + 256), *d_work = sc.get(wb), *d_res = sc.get((size_t)m * sizeof(hb_result));
@@ -739,7 +743,7 @@ static int cbx_host_call(int nframes, const void *const *frame, const size_t *n,
     }
     std::vector<void *> pd((size_t)m);
     for (int i = 0; i < m; i++) pd[(size_t)i] = d_out + P.ooff[(size_t)i];
-    const int st = hb_cblosc_getbox_frames_batch_device(nframes, P.hd.data(), pf.data(), n, m, P.pj.data(), pd.data(), P.caps.data(), d_work, wb, (hb_result *)d_res, nullptr);
+    const int st = run(nframes, P.hd.data(), pf.data(), n, m, P.pj.data(), pd.data(), P.caps.data(), d_work, wb, (hb_result *)d_res, nullptr);
     if (st) return all(st);
     std::vector<hb_result> res((size_t)m);
     if (hipMemcpy(res.data(), d_res, (size_t)m * sizeof(hb_result), hipMemcpyDeviceToHost) != hipSuccess) return all(HB_ERR_HIP);
@@ -754,10 +758,16 @@ static int cbx_host_call(int nframes, const void *const *frame, const size_t *n,
     }
     return HB_OK;
 }
+}  // extern "C++"
 // (host tables that do not fit into memory: the batch is one the caller has to split, as for cbx_prepare -- no exception crosses the C ABI)
 int hb_cblosc_getbox_frames_batch(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_cblosc_box_job *jobs, void *const *dst, const size_t *cap,
                                   int64_t *rc, int device) {
-    try { return cbx_host_call(nframes, frame, n, njobs, jobs, dst, cap, rc, device); }
+    try { return cbx_host_call(nframes, frame, n, njobs, jobs, dst, cap, rc, device, cbx_host_plan, hb_cblosc_getbox_frames_batch_workspace, hb_cblosc_getbox_frames_batch_device); }
+    catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
+}
+int hb_cblosc_getslice_frames_batch(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_cblosc_slice_job *jobs, void *const *dst, const size_t *cap,
+                                    int64_t *rc, int device) {
+    try { return cbx_host_call(nframes, frame, n, njobs, jobs, dst, cap, rc, device, cbs_host_plan, hb_cblosc_getslice_frames_batch_workspace, hb_cblosc_getslice_frames_batch_device); }
     catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
 }
 

@@ -26,6 +26,7 @@
 #include "hb_cblosc_enc_batch.h"   // the geometry of a written frame, and the host side of the batched encode
 #include "hb_cblosc_getitem_batch.h"   // the geometry of an item range, and the host side of the batched getitem
 #include "hb_cblosc_box_batch.h"       // the geometry of a box, the host side of the batched box reads, the gather's index arithmetic
+#include "hb_cblosc_slice_batch.h"     // the geometry of a stepped selection, the host side of the batched slice reads, the stepped gather's index arithmetic
 #include "hb_cblosc_enc_box_batch.h"   // the geometry of a source box, the host side of the batched box writes, the gather's index arithmetic
 #include "hb_cblosc_upd_box_batch.h"   // the geometry of an update box, the host side of the batched box updates, the overlay's index arithmetic
 
@@ -700,6 +701,76 @@ __global__ __launch_bounds__(256) void k_cbx_gather(const CbgFrame *__restrict__
     if (!cbx_thread(J, cbg_unit_bytes(KIND, F.typesize), blockIdx.x - gblk[i], threadIdx.x, lo, hi, doff)) return;
     const CbxLookup look{blocks, tl, J.ntl, J.b_lo, J.dense};
     cbg_unit<KIND>(F, look, work, lo, hi, J.dst + doff);
+}
+// ---- batched slice reads (hb_cblosc_getslice_frames_batch_device; hb_cblosc_slice_batch.h): the jobs whose rows are stepped.  Everything but
+// the gather is the box batch's. ----
+// 16 bytes = 16 / TS items, `istr` bytes apart, the first at byte p of the frame's decoded bytes.  An item that lies whole inside the whole
+// elements of its block is read where it is staged (a byte-shuffled block plane by plane); one that straddles two blocks or lies behind a
+// block's last whole element goes byte by byte through cbg_byte.  Neighbouring items usually share a block: its record is looked up once.
+template <int KIND, uint32_t TS, class LOOK>
+__device__ __forceinline__ u32x4 cbs_items16(const CbgFrame &F, const LOOK &look, const uint8_t *__restrict__ work, uint32_t p, uint32_t istr) {
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    const uint32_t bs = F.blocksize;
+    const bool direct = KIND == CBG_COPY && F.memcpyed;
+    uint32_t cur = ~0u, bsize = 0u, nel = 0u;
+    const uint8_t *s = nullptr;
+#pragma unroll
+    for (uint32_t c = 0; c < 16u / TS; c++) {
+        const uint32_t pc = p + c * istr;
+        uint32_t q = 0u, e = 0u;
+        bool whole = direct;
+        if (!direct) {
+            const uint32_t b = pc / bs;
+            q = pc - b * bs;
+            if (b != cur) { const CbgBlock &K = look(b); s = work + K.stage_off; bsize = K.bsize; nel = bsize / TS; cur = b; }
+            if (KIND == CBG_COPY) whole = q + TS <= bsize;
+            else { e = q / TS; whole = e * TS == q && e < nel; }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < TS; j++) {
+            const uint32_t i = c * TS + j;
+            const uint8_t v = direct ? F.frame[16u + (size_t)pc + j] : !whole ? cbg_byte<KIND>(F, look, work, pc + j) : KIND == CBG_COPY ? s[q + j] : s[(size_t)j * nel + e];
+            w[i >> 2] |= (uint32_t)v << (8u * (i & 3u));
+        }
+    }
+    u32x4 v; v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+    return v;
+}
+// One unit of a stepped row: `cnt` items, istr bytes apart from byte p of the frame's decoded bytes on, to d, packed.  16 bytes of whole items
+// of a copied or byte-shuffled frame are assembled in registers and stored at once (d has any alignment); the plain body has the row tails,
+// the other typesizes and both bit-shuffle kinds.
+template <int KIND, class LOOK>
+__device__ __forceinline__ void cbs_unit(const CbgFrame &F, const LOOK &look, const uint8_t *__restrict__ work, uint32_t p, uint32_t istr, uint32_t cnt, uint8_t *__restrict__ d) {
+    const uint32_t ts = F.typesize;
+    if ((KIND == CBG_COPY || KIND == CBG_UNSHUFFLE) && cnt * ts == 16u) {
+        if (ts == 1u && KIND == CBG_COPY) { st16u(d, cbs_items16<KIND, 1>(F, look, work, p, istr)); return; }      // (one byte is never shuffled)
+        if (ts == 2u) { st16u(d, cbs_items16<KIND, 2>(F, look, work, p, istr)); return; }
+        if (ts == 4u) { st16u(d, cbs_items16<KIND, 4>(F, look, work, p, istr)); return; }
+        if (ts == 8u) { st16u(d, cbs_items16<KIND, 8>(F, look, work, p, istr)); return; }
+        if (ts == 16u) { st16u(d, cbs_items16<KIND, 16>(F, look, work, p, istr)); return; }
+    }
+    for (uint32_t c = 0; c < cnt; c++)
+        for (uint32_t j = 0; j < ts; j++) d[c * ts + j] = cbg_byte<KIND>(F, look, work, p + c * istr + j);
+}
+// One launch per kind that occurs among the jobs with stepped rows; gjob / gblk / rows are those jobs in launch order.  A job's thread space
+// is rows x units per row, a unit being 16 bytes of the row's destination (cbs_thread).  The fail check comes before any store, as above.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_cbs_gather(const CbgFrame *__restrict__ frames, const CbxJob *__restrict__ jobs, const CbsRow *__restrict__ rows,
+                                                     const CbgBlock *__restrict__ blocks, const CbPlan *__restrict__ plans, const CbxTouch *__restrict__ touch,
+                                                     const uint32_t *__restrict__ gjob, const uint32_t *__restrict__ gblk, uint32_t nkind, const uint8_t *__restrict__ work) {
+    const uint32_t i = hb_owner(gblk, nkind, blockIdx.x);
+    const CbxJob &J = jobs[gjob[i]];
+    const CbsRow R = rows[i];
+    const CbgFrame &F = frames[J.frame];
+    const CbxTouch *tl = touch + J.tl0;
+    int bad = 0;
+    for (uint32_t k = threadIdx.x; k < J.ntl; k += 256u) bad |= plans[tl[k].rec].fail != 0u;
+    if (__syncthreads_or(bad)) return;
+    uint32_t it0, cnt, roff;
+    uint64_t doff;
+    if (!cbs_thread(J, R, F.typesize, blockIdx.x - gblk[i], threadIdx.x, it0, cnt, roff, doff)) return;
+    const CbxLookup look{blocks, tl, J.ntl, J.b_lo, J.dense};
+    cbs_unit<KIND>(F, look, work, roff + it0 * R.istr, R.istr, cnt, J.dst + doff);
 }
 // one thread per job: what the host decided, or k_cb_result's record from the OR of the fail words of the blocks the job touches
 __global__ __launch_bounds__(64) void k_cbx_finish(const CbxJob *__restrict__ jobs, const CbPlan *__restrict__ plans, const CbxTouch *__restrict__ touch, hb_result *results,
@@ -1397,24 +1468,10 @@ int hb_cblosc_getitem_frames_batch_device(int nframes, const hb_cblosc_header *h
     return HB_OK;
 }
 
-// ---- many boxes of many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_box_batch.h) ----
-size_t hb_cblosc_getbox_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n, int njobs, const hb_cblosc_box_job *jobs) {
-    return cbx_workspace(nframes, hdrs, n, njobs, jobs, hb_cblosc_accepted());
-}
-
-int hb_cblosc_getbox_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_cblosc_box_job *jobs,
-                                         void *const *d_dst, const size_t *cap, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
-    if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
-    if (njobs == 0) return HB_OK;
-    if (!hdrs || !d_frame || !n || !jobs || !d_dst || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
-    CbxBatch B;
-    const unsigned accept = hb_cblosc_accepted();
-    const int rc = cbx_prepare(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, true, B, accept);
-    if (rc) return rc;
+// A prepared batch of boxes or of stepped selections (CbxBatch) on the device: one upload, the plan and the decoders over the distinct blocks,
+// the gathers -- k_cbx_gather per kind among the jobs with plain rows, k_cbs_gather per kind among those with stepped rows -- and the records.
+static int cbx_launch(const CbxBatch &B, int nframes, int njobs, void *d_work, hb_result *d_results, void *stream) {
     const CbxLayout &L = B.L;
-    // (the query knows no capacities and no pointers: where a job was refused for one of them it has counted blocks that this batch leaves out)
-    if (work_bytes < (B.ptr_refusals ? cbx_workspace(nframes, hdrs, n, njobs, jobs, accept) : L.total)) return HB_ERR_SHORT_BUFFER;
-    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
     uint8_t *w = (uint8_t *)d_work;
     const size_t nf = (size_t)nframes, nj = (size_t)njobs, nb = (size_t)B.nblk;
@@ -1429,6 +1486,11 @@ int hb_cblosc_getbox_frames_batch_device(int nframes, const hb_cblosc_header *hd
     }
     memcpy(up.data() + L.gjob, B.gjob.data(), nj * 4);
     memcpy(up.data() + L.gblk, B.gblk.data(), nj * 4);
+    if (const size_t ns = B.srow.size()) {
+        memcpy(up.data() + L.srow, B.srow.data(), ns * sizeof(CbsRow));
+        memcpy(up.data() + L.sgjob, B.sgjob.data(), ns * 4);
+        memcpy(up.data() + L.sgblk, B.sgblk.data(), ns * 4);
+    }
     hb_prof_begin("cbx_upload", s);
     HB_HIP_TRY(hipMemcpyAsync(w, up.data(), L.upload, hipMemcpyHostToDevice, s));
     hb_prof_end(s);
@@ -1456,11 +1518,67 @@ int hb_cblosc_getbox_frames_batch_device(int nframes, const hb_cblosc_header *hd
 #undef CBX_LAUNCH
         hb_prof_end(s);
     }
+    const CbsRow *d_srow = (const CbsRow *)(w + L.srow);
+    const uint32_t *d_sgjob = (const uint32_t *)(w + L.sgjob), *d_sgblk = (const uint32_t *)(w + L.sgblk);
+    static const char *const sname[CBG_COUNT] = {"k_cbs_gather_copy", "k_cbs_gather_unshuffle", "k_cbs_gather_bitun", "k_cbs_gather_bitun4"};
+    for (int k = 0; k < CBG_COUNT; k++) {
+        const uint32_t k0 = B.skind0[k], nk = B.skind0[k + 1] - k0, blocks = B.skblocks[k];
+        if (!nk) continue;
+        hb_prof_begin(sname[k], s);
+#define CBS_LAUNCH(K) hipLaunchKernelGGL(k_cbs_gather<K>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_srow + k0, d_blocks, (const CbPlan *)d_plans, d_touch, d_sgjob + k0, d_sgblk + k0, nk, (const uint8_t *)w)
+        switch (k) {
+        case CBG_COPY: CBS_LAUNCH(CBG_COPY); break;
+        case CBG_UNSHUFFLE: CBS_LAUNCH(CBG_UNSHUFFLE); break;
+        case CBG_BITUN: CBS_LAUNCH(CBG_BITUN); break;
+        default: CBS_LAUNCH(CBG_BITUN4); break;
+        }
+#undef CBS_LAUNCH
+        hb_prof_end(s);
+    }
     hb_prof_begin("k_cbx_finish", s);
     hipLaunchKernelGGL(k_cbx_finish, dim3((unsigned)((nj + 63) / 64)), dim3(64), 0, s, d_jobs, (const CbPlan *)d_plans, d_touch, d_results, (uint32_t)njobs);
     hb_prof_end(s);
     HB_HIP_TRY(hipGetLastError());
     return HB_OK;
+}
+
+// ---- many boxes of many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_box_batch.h) ----
+size_t hb_cblosc_getbox_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n, int njobs, const hb_cblosc_box_job *jobs) {
+    return cbx_workspace(nframes, hdrs, n, njobs, jobs, hb_cblosc_accepted());
+}
+
+int hb_cblosc_getbox_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_cblosc_box_job *jobs,
+                                         void *const *d_dst, const size_t *cap, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
+    if (njobs == 0) return HB_OK;
+    if (!hdrs || !d_frame || !n || !jobs || !d_dst || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
+    CbxBatch B;
+    const unsigned accept = hb_cblosc_accepted();
+    const int rc = cbx_prepare(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, true, B, accept);
+    if (rc) return rc;
+    // (the query knows no capacities and no pointers: where a job was refused for one of them it has counted blocks that this batch leaves out)
+    if (work_bytes < (B.ptr_refusals ? cbx_workspace(nframes, hdrs, n, njobs, jobs, accept) : B.L.total)) return HB_ERR_SHORT_BUFFER;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    return cbx_launch(B, nframes, njobs, d_work, d_results, stream);
+}
+
+// ---- many stepped selections of many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_slice_batch.h) ----
+size_t hb_cblosc_getslice_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n, int njobs, const hb_cblosc_slice_job *jobs) {
+    return cbs_workspace(nframes, hdrs, n, njobs, jobs, hb_cblosc_accepted());
+}
+
+int hb_cblosc_getslice_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_cblosc_slice_job *jobs,
+                                           void *const *d_dst, const size_t *cap, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
+    if (njobs == 0) return HB_OK;
+    if (!hdrs || !d_frame || !n || !jobs || !d_dst || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
+    CbxBatch B;
+    const unsigned accept = hb_cblosc_accepted();
+    const int rc = cbs_prepare(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, true, B, accept);
+    if (rc) return rc;
+    if (work_bytes < (B.ptr_refusals ? cbs_workspace(nframes, hdrs, n, njobs, jobs, accept) : B.L.total)) return HB_ERR_SHORT_BUFFER;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    return cbx_launch(B, nframes, njobs, d_work, d_results, stream);
 }
 
 size_t hb_cblosc_bound(size_t n, int typesize) {

@@ -38,7 +38,11 @@ struct CbxJob {
     uint32_t dense;                      // the list has no holes: block b is entry b - b_lo
     int32_t kind, status;                // CBG_* or -1 (nothing to gather); status != 0: what the host decided, nothing else is valid
 };
-static_assert(sizeof(CbxTouch) == 8 && sizeof(CbxJob) == 152, "the records are uploaded as they are");
+// A stepped row (hb_cblosc_slice_batch.h): `nit` items of the typesize, `istr` bytes apart in the frame's decoded bytes.  Such a job keeps its
+// CbxJob -- rowbytes and upr / rpw / wpr / rcp16 / rcp_wpr then speak of the row's DESTINATION bytes (cbs_thread), rcp_unit is unused -- and has
+// one of these beside it, in the order of its kind's launch list.  A box has none.
+struct CbsRow { uint32_t nit, istr; };
+static_assert(sizeof(CbxTouch) == 8 && sizeof(CbxJob) == 152 && sizeof(CbsRow) == 8, "the records are uploaded as they are");
 static_assert(sizeof(CbxTouch) == HB_CBLOSC_BOX_BATCH_TOUCH_BYTES, "the per-pair constant of include/hipblosc.h");
 // per job: its record and two prefix words; per frame: its record; once: the padding of the sections (at most 6 x 16 + 2 x 255 bytes, and
 // every batch has a job and a frame).  Per distinct block the records are those of hb_cblosc_getitem_batch.h.
@@ -48,6 +52,7 @@ static_assert(sizeof(CbxJob) + 8 <= HB_CBLOSC_BOX_BATCH_JOB_BYTES && sizeof(CbgF
 // ---- one box ----
 struct CbxGeom {
     uint32_t ts, shp[3], cstr[3], off0, rowbytes, nrows;
+    uint32_t nit, istr;                  // the row in the frame: nit items, istr bytes apart (a box: istr == ts, the row is one run of rowbytes)
     uint64_t dstr[3], bytes, need;       // need: the bytes of the destination the box spans; 0 for an empty box
 };
 // The refusals of job q in the order of include/hipblosc.h; HB_OK: `g` is the box (bytes == 0: an empty one, nothing else of g is valid).
@@ -91,6 +96,7 @@ static inline int cbx_refusal(const hb_cblosc_header &h, size_t n, const hb_cblo
         }
         for (int o = 2 - (nd - 1); o >= 0; o--) { g.shp[o] = 1u; g.cstr[o] = 0u; g.dstr[o] = 0u; }
         g.off0 = (uint32_t)off; g.rowbytes = (uint32_t)((uint64_t)q.shape[nd - 1] * ts);
+        g.nit = (uint32_t)q.shape[nd - 1]; g.istr = ts;
         g.nrows = g.shp[0] * g.shp[1] * g.shp[2];
     }
     if (have_ptrs && (!d_frame || (!d_dst && g.bytes))) return HB_ERR_BAD_ARG;
@@ -101,16 +107,23 @@ static inline int cbx_refusal(const hb_cblosc_header &h, size_t n, const hb_cblo
 // sub-box from outer dimension k on, first byte to last; where the gap between two neighbours along k, cstr[k] - ext[k + 1], is smaller than
 // a block, no block fits into a gap, and the same then holds for every dimension further in (the gaps only grow outwards: cstr[k] -
 // ext[k + 1] >= cstr[k + 1] - ext[k + 2]), so the envelope of that sub-box is exact and costs O(1).  Otherwise the outer indices are walked.
+// A stepped row (istr != ts) is one level more: its extent is (nit - 1) istr + ts, the gap between two of its items istr - ts.  Where that gap
+// is below the block size the row's envelope is exact; otherwise the items are walked, and every item then starts in a new block, so the walk
+// is O(touched blocks).  (With steps the gaps no longer grow outwards; env[k] asks for every level below it, so nothing relies on that.)
 template <class EMIT>
 static inline void cbx_cover(const CbxGeom &g, uint32_t bs, EMIT emit) {
     uint64_t ext[4];
     bool env[4];
-    ext[3] = g.rowbytes; env[3] = true;
+    ext[3] = (uint64_t)(g.nit - 1u) * g.istr + g.ts; env[3] = g.nit == 1u || g.istr - g.ts < bs;       // (a box: rowbytes, true)
     for (int k = 2; k >= 0; k--) {
         ext[k] = (uint64_t)(g.shp[k] - 1u) * g.cstr[k] + ext[k + 1];
         env[k] = env[k + 1] && (g.shp[k] == 1u || (uint64_t)g.cstr[k] - ext[k + 1] < bs);
     }
     auto run = [&](uint64_t at, uint64_t len) { emit((uint32_t)(at / bs), (uint32_t)((at + len - 1) / bs)); };
+    auto row = [&](uint64_t at) {
+        if (env[3]) { run(at, ext[3]); return; }
+        for (uint32_t i = 0; i < g.nit; i++) run(at + (uint64_t)i * g.istr, g.ts);
+    };
     if (env[0]) { run(g.off0, ext[0]); return; }
     for (uint32_t i0 = 0; i0 < g.shp[0]; i0++) {
         const uint64_t a0 = (uint64_t)g.off0 + (uint64_t)i0 * g.cstr[0];
@@ -118,7 +131,7 @@ static inline void cbx_cover(const CbxGeom &g, uint32_t bs, EMIT emit) {
         for (uint32_t i1 = 0; i1 < g.shp[1]; i1++) {
             const uint64_t a1 = a0 + (uint64_t)i1 * g.cstr[1];
             if (env[2]) { run(a1, ext[2]); continue; }
-            for (uint32_t i2 = 0; i2 < g.shp[2]; i2++) run(a1 + (uint64_t)i2 * g.cstr[2], g.rowbytes);
+            for (uint32_t i2 = 0; i2 < g.shp[2]; i2++) row(a1 + (uint64_t)i2 * g.cstr[2]);
         }
     }
 }
@@ -163,8 +176,8 @@ CB_HD static inline uint32_t cbx_find(const CbxTouch *tl, uint32_t ntl, uint32_t
 }
 
 // everything up to `upload` goes up in ONE copy
-struct CbxLayout { size_t frames, jobs, blocks, plans, str0, touch, gjob, gblk, upload, streams, stage, total; };
-static inline CbxLayout cbx_layout(size_t nframes, size_t njobs, uint64_t nblk, uint64_t ntouch, uint64_t nstreams, uint64_t stage_bytes) {
+struct CbxLayout { size_t frames, jobs, blocks, plans, str0, touch, gjob, gblk, srow, sgjob, sgblk, upload, streams, stage, total; };
+static inline CbxLayout cbx_layout(size_t nframes, size_t njobs, uint64_t nblk, uint64_t ntouch, uint64_t nstreams, uint64_t stage_bytes, size_t nstep = 0) {
     CbxLayout L{};
     size_t o = 0;
     auto take = [&](size_t b, size_t al) { size_t at = o; o += (b + al - 1) / al * al; return at; };
@@ -176,6 +189,9 @@ static inline CbxLayout cbx_layout(size_t nframes, size_t njobs, uint64_t nblk, 
     L.touch = take((size_t)ntouch * sizeof(CbxTouch), 16);
     L.gjob = take(njobs * 4, 16);
     L.gblk = take(njobs * 4, 16);
+    L.srow = take(nstep * sizeof(CbsRow), 16);                            // (the jobs with stepped rows: nothing for a batch of boxes)
+    L.sgjob = take(nstep * 4, 16);
+    L.sgblk = take(nstep * 4, 16);
     o = cb_align(o);
     L.upload = o;
     L.streams = take((size_t)nstreams * sizeof(CbStream), 256);
@@ -194,18 +210,31 @@ struct CbxBatch {
     std::vector<uint32_t> str0, gjob, gblk;
     uint32_t kind0[CBG_COUNT + 1];       // jobs of kind k: gjob[kind0[k], kind0[k + 1])
     uint32_t kblocks[CBG_COUNT];         // workgroups of kind k
+    std::vector<CbsRow> jrow, srow;      // stepped rows: per job (nit == 0: a job with plain rows), and in launch order beside sgjob / sgblk
+    std::vector<uint32_t> sgjob, sgblk;
+    uint32_t skind0[CBG_COUNT + 1], skblocks[CBG_COUNT];      // as kind0 / kblocks, over the jobs with stepped rows
     uint64_t nblk, nstreams, stage, ntouch;
     uint32_t any_small, nsplit_all, any_lz4, any_blz;
     int ptr_refusals;                    // jobs refused for their capacity or a pointer: the workspace query counts their blocks, this batch does not
     CbxLayout L;
 };
 
+// the units of a stepped row: a thread owns 16 bytes of the row's destination, counted from the row's start -- 16 / ts whole items where the
+// typesize divides 16, else one item
+CB_HD static inline uint32_t cbs_items_per_unit(uint32_t ts) { return 16u % ts ? 1u : 16u / ts; }
+
 // HB_OK, or what the call as a whole answers.  d_frame / d_dst / cap == NULL: the workspace query.  fill == false: counts and layout only.
-static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_cblosc_box_job *jobs,
-                               void *const *d_dst, const size_t *cap, bool fill, CbxBatch &B, unsigned accept) {
+// JOB is hb_cblosc_box_job with cbx_refusal, or hb_cblosc_slice_job with cbs_refusal (hb_cblosc_slice_batch.h): `refuse` has cbx_refusal's
+// arguments and makes the CbxGeom, and everything from there on is the same.
+template <class JOB, class REFUSE>
+static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const JOB *jobs,
+                               void *const *d_dst, const size_t *cap, bool fill, CbxBatch &B, unsigned accept, REFUSE refuse) {
     B.nblk = 0; B.nstreams = 0; B.stage = 0; B.ntouch = 0; B.any_small = 0; B.nsplit_all = 0; B.ptr_refusals = 0; B.any_lz4 = 0; B.any_blz = 0;
     for (int k = 0; k < CBG_COUNT; k++) B.kblocks[k] = 0;
     for (int k = 0; k <= CBG_COUNT; k++) B.kind0[k] = 0;
+    for (int k = 0; k < CBG_COUNT; k++) B.skblocks[k] = 0;
+    for (int k = 0; k <= CBG_COUNT; k++) B.skind0[k] = 0;
+    B.jrow.clear(); B.srow.clear(); B.sgjob.clear(); B.sgblk.clear();
     B.frames.clear(); B.jobs.clear(); B.jruns.clear(); B.runs.clear(); B.blocks.clear(); B.touch.clear(); B.str0.clear(); B.gjob.clear(); B.gblk.clear();
     B.L = cbx_layout(0, 0, 0, 0, 0, 0);
     if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
@@ -218,17 +247,19 @@ static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
     const size_t nf = (size_t)nframes, nj = (size_t)njobs;
     B.frames.assign(nf, CbgFrame{});
     B.jobs.assign(nj, CbxJob{});
-    uint64_t kb[CBG_COUNT] = {0};
-    uint32_t kn[CBG_COUNT] = {0};
+    B.jrow.assign(nj, CbsRow{0u, 0u});
+    uint64_t kb[CBG_COUNT] = {0}, skb[CBG_COUNT] = {0};
+    uint32_t kn[CBG_COUNT] = {0}, skn[CBG_COUNT] = {0};
+    size_t nstep = 0;
     for (size_t j = 0; j < nj; j++) {
-        const hb_cblosc_box_job &q = jobs[j];
+        const JOB &q = jobs[j];
         const hb_cblosc_header &h = hdrs[q.frame];
         CbxJob &J = B.jobs[j];
         CbxGeom g;
         J.kind = -1; J.frame = q.frame;
-        J.status = cbx_refusal(h, n[q.frame], q, 0, nullptr, nullptr, 0, g, accept);
+        J.status = refuse(h, n[q.frame], q, 0, nullptr, nullptr, 0, g, accept);
         if (J.status == HB_OK && have) {
-            J.status = cbx_refusal(h, n[q.frame], q, 1, d_frame[q.frame], d_dst[j], cap[j], g, accept);
+            J.status = refuse(h, n[q.frame], q, 1, d_frame[q.frame], d_dst[j], cap[j], g, accept);
             if (J.status) B.ptr_refusals++;
         }
         if (J.status) continue;
@@ -250,13 +281,20 @@ static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
         for (int k = 0; k < 3; k++) { J.dstr[k] = g.dstr[k]; J.cstr[k] = g.cstr[k]; J.shp[k] = g.shp[k]; }
         J.rcp[0] = cbx_recip(g.shp[1]); J.rcp[1] = cbx_recip(g.shp[2]); J.rcp_unit = cbx_recip(U);
         J.off0 = g.off0; J.rowbytes = g.rowbytes; J.nrows = g.nrows;
-        J.upr = cbx_units_per_row(g.rowbytes, U, cbx_row_misalign(g, U));
+        const bool stepped = g.istr != ts;
+        if (stepped) {                                                    // (units of the row's destination: no misalignment term)
+            const uint32_t ipu = cbs_items_per_unit(ts);
+            B.jrow[j] = CbsRow{g.nit, g.istr};
+            J.rcp_unit = 0; J.upr = (g.nit + ipu - 1u) / ipu;
+            nstep++;
+        } else
+            J.upr = cbx_units_per_row(g.rowbytes, U, cbx_row_misalign(g, U));
         if (J.upr <= 256u) { J.rpw = 256u / J.upr; J.wpr = 1u; J.rcp16 = 65535u / J.upr + 1u; }
         else { J.rpw = 1u; J.wpr = (J.upr + 255u) / 256u; J.rcp16 = 0u; }
         J.rcp_wpr = cbx_recip(J.wpr);
-        kb[J.kind] += cbx_groups(J);
-        kn[J.kind]++;
-        if (kb[J.kind] > HB_CBLOSC_BATCH_MAX_WORK) return HB_ERR_BAD_ARG;
+        (stepped ? skb : kb)[J.kind] += cbx_groups(J);
+        (stepped ? skn : kn)[J.kind]++;
+        if (kb[J.kind] > HB_CBLOSC_BATCH_MAX_WORK || skb[J.kind] > HB_CBLOSC_BATCH_MAX_WORK) return HB_ERR_BAD_ARG;
         if (F.memcpyed) continue;
         // the blocks its rows touch: runs in increasing order, merged as they come
         const size_t first = B.jruns.size();
@@ -297,10 +335,11 @@ static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
         B.nsplit_all = B.nsplit_all == 0 || B.nsplit_all == F.nsplit ? F.nsplit : 1u;
     }
     if (B.nsplit_all == 0) B.nsplit_all = 1;
-    B.L = cbx_layout(nf, nj, B.nblk, B.ntouch, B.nstreams, B.stage);
-    uint32_t at = 0;
+    B.L = cbx_layout(nf, nj, B.nblk, B.ntouch, B.nstreams, B.stage, nstep);
+    uint32_t at = 0, sat = 0;
     for (int k = 0; k < CBG_COUNT; k++) { B.kind0[k] = at; at += kn[k]; B.kblocks[k] = (uint32_t)kb[k]; }
-    B.kind0[CBG_COUNT] = at;
+    for (int k = 0; k < CBG_COUNT; k++) { B.skind0[k] = sat; sat += skn[k]; B.skblocks[k] = (uint32_t)skb[k]; }
+    B.kind0[CBG_COUNT] = at; B.skind0[CBG_COUNT] = sat;
     if (!fill) return HB_OK;
     // ---- the tables ----
     B.blocks.resize((size_t)B.nblk);
@@ -329,11 +368,18 @@ static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
         for (uint64_t b = jr.lo; b <= jr.hi; b++) B.touch[t++] = CbxTouch{(uint32_t)b, r.blk0 + ((uint32_t)b - r.lo)};
     }
     B.gjob.assign(nj, 0u); B.gblk.assign(nj, 0u);
-    uint32_t fill_at[CBG_COUNT], blk_at[CBG_COUNT] = {0};
-    for (int k = 0; k < CBG_COUNT; k++) fill_at[k] = B.kind0[k];
+    B.srow.assign(nstep, CbsRow{0u, 0u}); B.sgjob.assign(nstep, 0u); B.sgblk.assign(nstep, 0u);
+    uint32_t fill_at[CBG_COUNT], blk_at[CBG_COUNT] = {0}, sfill_at[CBG_COUNT], sblk_at[CBG_COUNT] = {0};
+    for (int k = 0; k < CBG_COUNT; k++) { fill_at[k] = B.kind0[k]; sfill_at[k] = B.skind0[k]; }
     for (size_t j = 0; j < nj; j++) {
         const CbxJob &J = B.jobs[j];
         if (J.status || J.kind < 0) continue;
+        if (B.jrow[j].nit) {
+            const uint32_t at = sfill_at[J.kind]++;
+            B.sgjob[at] = (uint32_t)j; B.sgblk[at] = sblk_at[J.kind]; B.srow[at] = B.jrow[j];
+            sblk_at[J.kind] += (uint32_t)cbx_groups(J);
+            continue;
+        }
         B.gjob[fill_at[J.kind]] = (uint32_t)j; B.gblk[fill_at[J.kind]] = blk_at[J.kind];
         fill_at[J.kind]++; blk_at[J.kind] += (uint32_t)cbx_groups(J);
     }
@@ -341,7 +387,7 @@ static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
 }
 static inline int cbx_prepare(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_cblosc_box_job *jobs,
                               void *const *d_dst, const size_t *cap, bool fill, CbxBatch &B, unsigned accept = CB_ACCEPT_DEFAULT) {
-    try { return cbx_prepare_(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, fill, B, accept); }
+    try { return cbx_prepare_(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, fill, B, accept, cbx_refusal); }
     catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
 }
 
@@ -355,11 +401,12 @@ static inline size_t cbx_workspace(int nframes, const hb_cblosc_header *hdrs, co
 // ---- the host form: what each job is answered with before the device is asked, which jobs the batch carries (with their boxes C-contiguous
 // in one packed device buffer: job i's bytes follow those of the carried jobs before it), which frames go up and where.  Frames that follow
 // each other exactly in host memory go up in one copy. ----
-struct CbxHostPlan {
+template <class JOB>
+struct CbxHostPlanOf {
     std::vector<hb_cblosc_header> hd;    // per frame; a frame that does not parse keeps a zeroed record
     std::vector<int64_t> status;         // per job: its refusal, or 0
     std::vector<int> carried;            // the jobs the batch carries, in order
-    std::vector<hb_cblosc_box_job> pj;   // per carried job: the job with the strides of its packed box
+    std::vector<JOB> pj;                 // per carried job: the job with the strides of its packed box
     std::vector<CbxGeom> geom;           // per carried job
     std::vector<size_t> ooff, caps;      // per carried job
     std::vector<int> idx;                // the frames that a carried job reads, in order
@@ -367,8 +414,12 @@ struct CbxHostPlan {
     size_t in_bytes, out_bytes;
     bool span_in;
 };
-static inline void cbx_host_plan(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_cblosc_box_job *jobs, void *const *dst, const size_t *cap,
-                                 CbxHostPlan &P, unsigned accept = CB_ACCEPT_DEFAULT) {
+typedef CbxHostPlanOf<hb_cblosc_box_job> CbxHostPlan;
+static inline const int64_t *cbx_extent(const hb_cblosc_box_job &q) { return q.shape; }      // the items per dimension that a job writes
+// (`refuse`: cbx_refusal, or cbs_refusal of hb_cblosc_slice_batch.h, as for cbx_prepare_)
+template <class JOB, class REFUSE>
+static inline void cbx_host_plan_(int nframes, const void *const *frame, const size_t *n, int njobs, const JOB *jobs, void *const *dst, const size_t *cap,
+                                  CbxHostPlanOf<JOB> &P, unsigned accept, REFUSE refuse) {
     const size_t nf = (size_t)nframes, nj = (size_t)njobs;
     P.hd.assign(nf, hb_cblosc_header{}); P.status.assign(nj, 0); P.carried.clear(); P.pj.clear(); P.geom.clear(); P.ooff.clear(); P.caps.clear(); P.idx.clear(); P.ioff.assign(nf, 0);
     P.in_bytes = P.out_bytes = 0; P.span_in = false;
@@ -379,13 +430,13 @@ static inline void cbx_host_plan(int nframes, const void *const *frame, const si
         if (parsed[k]) P.hd[k] = hb_cblosc_header{};
     }
     for (size_t j = 0; j < nj; j++) {
-        const hb_cblosc_box_job &q = jobs[j];
+        const JOB &q = jobs[j];
         CbxGeom g;
-        P.status[j] = parsed[q.frame] ? parsed[q.frame] : cbx_refusal(P.hd[q.frame], n[q.frame], q, 1, frame[q.frame], dst[j], cap[j], g, accept);
+        P.status[j] = parsed[q.frame] ? parsed[q.frame] : refuse(P.hd[q.frame], n[q.frame], q, 1, frame[q.frame], dst[j], cap[j], g, accept);
         if (P.status[j]) continue;
-        hb_cblosc_box_job p = q;
+        JOB p = q;
         int64_t stride = g.ts;
-        for (int k = (int)q.ndim - 1; k >= 0; k--) { p.dst_stride[k] = stride; stride *= q.shape[k] > 0 ? q.shape[k] : 1; }
+        for (int k = (int)q.ndim - 1; k >= 0; k--) { p.dst_stride[k] = stride; stride *= cbx_extent(q)[k] > 0 ? cbx_extent(q)[k] : 1; }
         P.carried.push_back((int)j); P.pj.push_back(p); P.geom.push_back(g); P.ooff.push_back(P.out_bytes); P.caps.push_back((size_t)g.bytes);
         P.out_bytes += (size_t)g.bytes;
         used[q.frame] = 1;
@@ -395,6 +446,10 @@ static inline void cbx_host_plan(int nframes, const void *const *frame, const si
     for (size_t i = 0; P.span_in && i + 1 < P.idx.size(); i++)
         P.span_in = (const uint8_t *)frame[P.idx[i]] + n[P.idx[i]] == (const uint8_t *)frame[P.idx[i + 1]];
     for (int k : P.idx) { P.ioff[(size_t)k] = P.in_bytes; P.in_bytes += P.span_in ? n[k] : cb_align(n[k] + 64); }
+}
+static inline void cbx_host_plan(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_cblosc_box_job *jobs, void *const *dst, const size_t *cap,
+                                 CbxHostPlan &P, unsigned accept = CB_ACCEPT_DEFAULT) {
+    cbx_host_plan_(nframes, frame, n, njobs, jobs, dst, cap, P, accept, cbx_refusal);
 }
 // the rows of a packed box (C-contiguous, `g.bytes` bytes) to their places in the caller's array
 static inline void cbx_place_rows(const CbxGeom &g, const uint8_t *packed, uint8_t *dst) {

@@ -105,6 +105,7 @@ EXPORTS = [
     "hb_cblosc_compress_frames_batch_workspace", "hb_cblosc_compress_frames_batch_device", "hb_cblosc_compress_frames_batch",
     "hb_cblosc_getitem_frames_batch_workspace", "hb_cblosc_getitem_frames_batch_device", "hb_cblosc_getitem_frames_batch",
     "hb_cblosc_getbox_frames_batch_workspace", "hb_cblosc_getbox_frames_batch_device", "hb_cblosc_getbox_frames_batch",
+    "hb_cblosc_getslice_frames_batch_workspace", "hb_cblosc_getslice_frames_batch_device", "hb_cblosc_getslice_frames_batch",
     "hb_cblosc_compress_boxes_batch_workspace", "hb_cblosc_compress_boxes_batch_device", "hb_cblosc_compress_boxes_batch",
     "hb_cblosc_update_boxes_batch_workspace", "hb_cblosc_update_boxes_batch_device", "hb_cblosc_update_boxes_batch",
     "hb_cblosc_accept_codecs",
@@ -140,6 +141,21 @@ def box_job(frame, chunk_shape, start, shape, dst_stride):
         raise ValueError("chunk_shape, start, shape and dst_stride need the same number of entries, at most 4")
     a = ctypes.c_int64 * 4
     return hb_cblosc_box_job(int(frame), nd, a(*[int(v) for v in chunk_shape]), a(*[int(v) for v in start]), a(*[int(v) for v in shape]), a(*[int(v) for v in dst_stride]))
+
+
+class hb_cblosc_slice_job(ctypes.Structure):
+    """include/hipblosc.h hb_cblosc_slice_job: a stepped N-d selection of a C-order chunk and the byte strides of its destination"""
+    _fields_ = [("frame", ctypes.c_uint32), ("ndim", ctypes.c_uint32), ("chunk_shape", ctypes.c_int64 * 4), ("start", ctypes.c_int64 * 4),
+                ("count", ctypes.c_int64 * 4), ("step", ctypes.c_int64 * 4), ("dst_stride", ctypes.c_int64 * 4)]
+
+
+def slice_job(frame, chunk_shape, start, count, step, dst_stride):
+    """hb_cblosc_slice_job from sequences of ndim entries each (the entries behind them stay 0)"""
+    nd = len(chunk_shape)
+    if not (len(start) == len(count) == len(step) == len(dst_stride) == nd) or nd > 4:
+        raise ValueError("chunk_shape, start, count, step and dst_stride need the same number of entries, at most 4")
+    a = ctypes.c_int64 * 4
+    return hb_cblosc_slice_job(int(frame), nd, *[a(*[int(v) for v in seq]) for seq in (chunk_shape, start, count, step, dst_stride)])
 
 
 class hb_cblosc_src_box(ctypes.Structure):
@@ -249,6 +265,9 @@ def lib():
             "hb_cblosc_getbox_frames_batch_workspace": (sz, [i32, vp, vp, i32, vp]),
             "hb_cblosc_getbox_frames_batch_device": (i32, [i32, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp, vp]),
             "hb_cblosc_getbox_frames_batch": (i32, [i32, vp, vp, i32, vp, vp, vp, vp, i32]),
+            "hb_cblosc_getslice_frames_batch_workspace": (sz, [i32, vp, vp, i32, vp]),
+            "hb_cblosc_getslice_frames_batch_device": (i32, [i32, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp, vp]),
+            "hb_cblosc_getslice_frames_batch": (i32, [i32, vp, vp, i32, vp, vp, vp, vp, i32]),
             "hb_cblosc_compress_boxes_batch_workspace": (sz, [i32, vp, i32, i32]),
             "hb_cblosc_compress_boxes_batch_device": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
             "hb_cblosc_compress_boxes_batch": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32]),
@@ -766,6 +785,133 @@ def CBloscReadRegion(frames, grid_shape, chunk_shape, region, typesize, dev=None
     _check(lib().hb_cblosc_getbox_frames_batch(nf, fr, ns, nj, jt, dsts, caps, rcs, device if dev is None else dev))
     for rc in rcs:
         _check(int(rc))
+    return bytes(out)
+
+
+def CBloscGetSliceBatch(frames, jobs, dev=None):
+    """Many stepped N-d selections of many chunk frames through one set of launches (include/hipblosc.h hb_cblosc_getslice_frames_batch):
+    `jobs` are (frame_index, chunk_shape, start, count, step) tuples over `frames`, the chunk in C order, at most 4 dimensions; only the blocks
+    that hold a selected item are decoded, each once.  The i-th result is the selection's bytes in C order -- what
+    `chunk[s0:s0 + c0 * t0:t0, ...]` gives in numpy -- or the job's error (returned, not raised, as CBloscGetBoxBatch does)."""
+    jobs = list(jobs)
+    nj, nf = len(jobs), len(frames)
+    if nj == 0:
+        return []
+    keep = [_buf(f) for f in frames]
+    jt, caps = (hb_cblosc_slice_job * nj)(), []
+    for j, (f, chunk_shape, start, count, step) in enumerate(jobs):
+        ts = _typesize_of(keep, nf, f)
+        strides, nbytes = [], ts
+        for m in reversed([max(int(v), 0) for v in count]):
+            strides.insert(0, nbytes)
+            nbytes *= m
+        jt[j] = slice_job(f, chunk_shape, start, count, step, strides)
+        caps.append(nbytes)
+    outs = [(ctypes.c_char * max(c, 1))() for c in caps]
+    fr = (ctypes.c_void_p * max(nf, 1))(*[k[0].value for k in keep])
+    ns = (ctypes.c_size_t * max(nf, 1))(*[k[1] for k in keep])
+    dsts = (ctypes.c_void_p * nj)(*[ctypes.addressof(o) for o in outs])
+    rcs = (ctypes.c_int64 * nj)()
+    _check(lib().hb_cblosc_getslice_frames_batch(nf, fr, ns, nj, jt, dsts, (ctypes.c_size_t * nj)(*caps), rcs, device if dev is None else dev))
+    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(nj)]
+
+
+def slice_jobs(grid_shape, chunk_shape, slices, typesize):
+    """The slice jobs of a stepped read of a chunked array: one (hb_cblosc_slice_job, byte offset into the output) per chunk that holds an
+    item of `slices` -- a (lo, hi, step) triple per dimension, in items of the whole array, as `z[lo:hi:step]` -- every job with the strides
+    of the C-order output array; and the output's shape.  Chunk (c_0, c_1 ...) is frame number c in C order of the grid; a chunk that a step
+    jumps over gets no job."""
+    nd = len(chunk_shape)
+    if not (len(grid_shape) == len(slices) == nd) or not 1 <= nd <= 4:
+        raise ValueError("grid_shape, chunk_shape and slices need the same number of entries, 1 to 4")
+    if any(lo < 0 or hi < lo or hi > g * c or st < 1 for (lo, hi, st), g, c in zip(slices, grid_shape, chunk_shape)):
+        raise ValueError("the slices lie outside the array, or a step is below 1")
+    out_shape = [(hi - lo + st - 1) // st for lo, hi, st in slices]
+    strides, acc = [], int(typesize)
+    for m in reversed(out_shape):
+        strides.insert(0, acc)
+        acc *= m
+    # per dimension: (chunk index, first output index, start inside the chunk, count) of every chunk that holds a selected index
+    per = []
+    for (lo, hi, st), c, m in zip(slices, chunk_shape, out_shape):
+        parts, i = [], 0
+        while i < m:
+            ch = (lo + i * st) // c
+            cnt = min(m - i, ((ch + 1) * c - 1 - (lo + i * st)) // st + 1)
+            parts.append((ch, i, lo + i * st - ch * c, cnt))
+            i += cnt
+        per.append(parts)
+    jobs = []
+    if all(out_shape):
+        steps = [st for _, _, st in slices]
+        idx = [0] * nd
+        while True:
+            f, off = 0, 0
+            for k in range(nd):
+                f = f * grid_shape[k] + per[k][idx[k]][0]
+                off += per[k][idx[k]][1] * strides[k]
+            jobs.append((slice_job(f, chunk_shape, [per[k][idx[k]][2] for k in range(nd)], [per[k][idx[k]][3] for k in range(nd)], steps, strides), off))
+            k = nd - 1
+            while k >= 0:
+                idx[k] += 1
+                if idx[k] < len(per[k]):
+                    break
+                idx[k] = 0
+                k -= 1
+            if k < 0:
+                break
+    return jobs, out_shape
+
+
+def CBloscReadSlices(frames, grid_shape, chunk_shape, slices, typesize, fill=None, dev=None):
+    """`z[lo_0:hi_0:step_0, lo_1:hi_1:step_1 ...]` of a chunked array whose chunks are the C-Blosc-1 frames `frames`, in C order of the chunk
+    grid `grid_shape`, every chunk `chunk_shape` items of `typesize` bytes: one slice job per chunk that holds a selected item (slice_jobs),
+    all of them through one hb_cblosc_getslice_frames_batch call into one output array.  An entry of `frames` may be None -- the store has no
+    such chunk: its part of the output is `fill` (`typesize` bytes), written here, and with fill=None that raises.  Returns the selection's
+    bytes in C order; raises the first job's error."""
+    pairs, out_shape = slice_jobs(grid_shape, chunk_shape, slices, typesize)
+    ts, total = int(typesize), int(typesize)
+    for m in out_shape:
+        total *= m
+    absent = [p for p in pairs if frames[p[0].frame] is None]
+    if absent:
+        if fill is None:
+            raise ValueError("a selected chunk is absent and there is no fill value")
+        if len(bytes(fill)) != ts:
+            raise ValueError("fill needs typesize bytes")
+    if not pairs:
+        return b""
+    out = (ctypes.c_char * total)()
+    base = ctypes.addressof(out)
+    for job, off in absent:                                               # the rows of an absent chunk's part of the output
+        nd = job.ndim
+        row = bytes(fill) * job.count[nd - 1]
+        outer = [0] * (nd - 1)
+        while True:
+            at = off + sum(i * job.dst_stride[k] for k, i in enumerate(outer))
+            ctypes.memmove(base + at, row, len(row))
+            k = nd - 2
+            while k >= 0:
+                outer[k] += 1
+                if outer[k] < job.count[k]:
+                    break
+                outer[k] = 0
+                k -= 1
+            if k < 0:
+                break
+    pairs = [p for p in pairs if frames[p[0].frame] is not None]
+    nj, nf = len(pairs), len(frames)
+    if nj:
+        keep = [_buf(f if f is not None else b"") for f in frames]
+        jt = (hb_cblosc_slice_job * nj)(*[p[0] for p in pairs])
+        fr = (ctypes.c_void_p * max(nf, 1))(*[k[0].value for k in keep])
+        ns = (ctypes.c_size_t * max(nf, 1))(*[k[1] for k in keep])
+        dsts = (ctypes.c_void_p * nj)(*[base + off for _, off in pairs])
+        caps = (ctypes.c_size_t * nj)(*[total - off for _, off in pairs])
+        rcs = (ctypes.c_int64 * nj)()
+        _check(lib().hb_cblosc_getslice_frames_batch(nf, fr, ns, nj, jt, dsts, caps, rcs, device if dev is None else dev))
+        for rc in rcs:
+            _check(int(rc))
     return bytes(out)
 
 

@@ -233,6 +233,43 @@ inline std::vector<Bytes> CBloscGetBoxBatch(const std::vector<Bytes> &frames, co
     for (size_t j = 0; j < nj; j++) out[j].resize(rc[j] > 0 ? (size_t)rc[j] : 0);
     return out;
 }
+// many stepped N-d selections of C-order chunk frames through one set of launches (hb_cblosc_getslice_frames_batch; only the blocks that hold a
+// selected item are decoded, each once): job j = the items start[k] + i * step[k], 0 <= i < count[k], of frames[frame], a chunk of chunk_shape
+// items (1 to 4 dimensions, the same number of entries in all four).  out[j] is the selection in C order, rc[j] its byte count or the job's
+// HB_ERR_* code (nothing is thrown per job)
+struct SliceJob { uint32_t frame; std::vector<int64_t> chunk_shape, start, count, step; };
+inline std::vector<Bytes> CBloscGetSliceBatch(const std::vector<Bytes> &frames, const std::vector<SliceJob> &jobs, std::vector<int64_t> &rc, int device = 0) {
+    const size_t nf = frames.size(), nj = jobs.size();
+    std::vector<Bytes> out(nj);
+    rc.assign(nj, 0);
+    if (!nj) return out;
+    std::vector<const void *> fr(nf); std::vector<size_t> ns(nf);
+    for (size_t k = 0; k < nf; k++) { fr[k] = frames[k].data(); ns[k] = frames[k].size(); }
+    std::vector<hb_cblosc_slice_job> jt(nj); std::vector<void *> dst(nj); std::vector<size_t> cap(nj);
+    for (size_t j = 0; j < nj; j++) {
+        const SliceJob &q = jobs[j];
+        const size_t nd = q.chunk_shape.size();
+        if (nd < 1 || nd > HB_CBLOSC_BOX_MAX_NDIM || q.start.size() != nd || q.count.size() != nd || q.step.size() != nd) check(HB_ERR_BAD_ARG);
+        size_t ts = 1;
+        if (q.frame < nf && ns[q.frame] >= 16 && frames[q.frame][3]) ts = frames[q.frame][3];
+        hb_cblosc_slice_job &t = jt[j];
+        t = hb_cblosc_slice_job{};
+        t.frame = q.frame; t.ndim = (uint32_t)nd;
+        uint64_t bytes = ts;                                              // packed: the strides of the selection itself
+        for (size_t k = nd; k-- > 0;) {
+            t.chunk_shape[k] = q.chunk_shape[k]; t.start[k] = q.start[k]; t.count[k] = q.count[k]; t.step[k] = q.step[k];
+            t.dst_stride[k] = (int64_t)bytes;
+            const uint64_t m = q.count[k] > 0 ? (uint64_t)q.count[k] : (q.count[k] == 0 ? 0u : 1u);
+            bytes = m && bytes > (1ull << 32) / m ? (1ull << 32) : bytes * m;         // (a selection no frame can hold is refused by the library: no room is needed for it)
+        }
+        cap[j] = bytes <= 0xFFFFFFFFull ? (size_t)bytes : 0;
+        out[j].resize(cap[j] ? cap[j] : 1);
+        dst[j] = out[j].data();
+    }
+    check(hb_cblosc_getslice_frames_batch((int)nf, fr.data(), ns.data(), (int)nj, jt.data(), dst.data(), cap.data(), rc.data(), device));
+    for (size_t j = 0; j < nj; j++) out[j].resize(rc[j] > 0 ? (size_t)rc[j] : 0);
+    return out;
+}
 // many inputs to C-Blosc-1 frames through one set of launches (hb_cblosc_compress_frames_batch; shuffle 0 / 1 / 2 = none / byte / bit, one shuffle
 // and typesize for the whole batch): out[k] is the frame hb_cblosc_compress writes for datas[k], rc[k] its byte count or its HB_ERR_* code
 // (nothing is thrown per input)

@@ -350,7 +350,7 @@ int     hb_cblosc_parse_header(const void *frame, size_t n, hb_cblosc_header *ou
 /* which C-Blosc-1 codec formats the hb_cblosc_* entry points accept: bit k = codec format k.  Default 0x2 (LZ4 / LZ4HC).
  * Accepted masks: 0x2 and 0x3 (adds BloscLZ); anything else HB_ERR_BAD_ARG and no change.  Returns the previous mask.
  * Process-wide and thread-safe: an atomic word that every entry point (hb_cblosc_decompress*, hb_cblosc_decompress_frames_batch*,
- * hb_cblosc_getitem*, hb_cblosc_getitem_frames_batch*, hb_cblosc_getbox_frames_batch*, device and host forms and their workspace queries) reads once
+ * hb_cblosc_getitem*, hb_cblosc_getitem_frames_batch*, hb_cblosc_getbox_frames_batch*, hb_cblosc_getslice_frames_batch*, device and host forms and their workspace queries) reads once
  * per call.  With bit 0 set a BloscLZ frame gets exactly the refusals, in the same order, that an LZ4 frame with the same header gets; wherever the
  * comments below say "codec format != 1" read "a codec format the mask does not name".  Opt-in, because HB_ERR_INVALID_CODEC for
  * BloscLZ is an answer callers may route on (to a CPU decoder).  Writing is not touched: hb_cblosc_compress* writes LZ4. */
@@ -497,6 +497,51 @@ int     hb_cblosc_getbox_frames_batch_device(int nframes, const hb_cblosc_header
 int     hb_cblosc_getbox_frames_batch(int nframes, const void *const *frame, const size_t *n,
                                       int njobs, const hb_cblosc_box_job *jobs, void *const *dst, const size_t *cap,
                                       int64_t *rc, int device);
+/* ---- many stepped N-d selections of many C-Blosc-1 frames through ONE set of launches: `z[::2, 3::8]` of a chunked array store is, per chunk
+ *      that holds a selected item, a box job with one more field per dimension, the step.  Everything of hb_cblosc_getbox_frames_batch* holds
+ *      with `count` for `shape`, except what follows.
+ *      Item (i_0 .. i_{ndim-1}) of the selection, 0 <= i_k < count[k], is the chunk's item at linear index sum_k (start[k] + i_k * step[k]) *
+ *      prod_{m>k} chunk_shape[m]; it is written to d_dst[j] + sum_k i_k * dst_stride[k].
+ *      Device form:
+ *        - refused per job, decided on the host before hb_init(), in the order of the box batch: the header, codec and geometry refusals
+ *          (hb_cblosc_accept_codecs is honoured); HB_ERR_BAD_ARG for what the box batch refuses of the box (start, count), and for step[k] < 1
+ *          for some k < ndim or count[k] > 0 && start[k] + (count[k] - 1) * step[k] >= chunk_shape[k] (checked without overflow);
+ *          HB_ERR_SHORT_BUFFER for cap[j] < sum_k (count[k] - 1) * dst_stride[k] + typesize; HB_ERR_BAD_ARG for a NULL d_frame[f] or a NULL
+ *          d_dst[j] with bytes to write.  A refused job keeps its place and touches nothing;
+ *        - a job with some count[k] == 0: status 0, bytes 0, nothing planned or written;
+ *        - a dimension with count[k] == 1 is taken with step 1: nothing depends on a step that nobody takes;
+ *        - every other job: status 0, flags 1, bytes = total_bytes = prod count * typesize -- or HB_ERR_DECOMPRESSION_FAILED with bytes 0 when
+ *          the plan or a stream of a block that it touches fails; a failed job writes nothing.  A block is touched iff it holds a byte of a
+ *          selected item: an untouched block is never planned, decoded or read, also when it lies between two selected items of ONE ROW; every
+ *          distinct (frame, block) pair is planned and decoded once.  The fail state is per block;
+ *        - nothing is written outside the selected items' destination bytes.
+ *      A job whose steps are all 1 answers exactly what hb_cblosc_getbox_frames_batch* answers for the box (start, count): the record, the
+ *      bytes written, the bytes left alone and the workspace query.
+ *      The call as a whole: as the box batch, in its order, HB_CBLOSC_BATCH_MAX_WORK included (the workgroups of the stepped gathers are counted
+ *      per kind like those of the plain ones).
+ *      Workspace: as the box batch, plus 16 bytes per job whose last dimension is stepped; it grows neither with rows nor with items.  At most
+ *      the sum over the distinct touched blocks of hb_cblosc_getitem_workspace() for a one-block range + HB_CBLOSC_SLICE_BATCH_JOB_BYTES *
+ *      (njobs + nframes) + HB_CBLOSC_BOX_BATCH_TOUCH_BYTES * (the number of (job, touched block) pairs).  0 when the call as a whole would be
+ *      refused, 256 for njobs == 0.
+ *      Host form: as the box batch's -- the frames go up once, the device form runs once into a packed buffer with the selections
+ *      C-contiguous, one copy down, and the host places the rows.  There is no per-item fallback.  Index lists per dimension are not
+ *      covered. ---- */
+#define HB_CBLOSC_SLICE_BATCH_JOB_BYTES 512      /* workspace per job and per frame beyond the blocks */
+typedef struct hb_cblosc_slice_job {
+    uint32_t frame;            /* index into the frame arrays */
+    uint32_t ndim;             /* 1 .. HB_CBLOSC_BOX_MAX_NDIM */
+    int64_t  chunk_shape[4];   /* items, C order (last dimension contiguous); product * typesize == the header's nbytes */
+    int64_t  start[4], count[4], step[4];   /* items start[k] + i * step[k], 0 <= i < count[k]; step[k] >= 1; the last one inside the chunk */
+    int64_t  dst_stride[4];    /* BYTES between neighbours along dimension k in the destination; >= 0; dst_stride[ndim-1] == typesize */
+} hb_cblosc_slice_job;         /* entries at k >= ndim are 0 */
+size_t  hb_cblosc_getslice_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n,
+                                                  int njobs, const hb_cblosc_slice_job *jobs);
+int     hb_cblosc_getslice_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n,
+                                               int njobs, const hb_cblosc_slice_job *jobs, void *const *d_dst, const size_t *cap,
+                                               void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
+int     hb_cblosc_getslice_frames_batch(int nframes, const void *const *frame, const size_t *n,
+                                        int njobs, const hb_cblosc_slice_job *jobs, void *const *dst, const size_t *cap,
+                                        int64_t *rc, int device);
 /* writing the format: a frame that blosc_decompress() of c-blosc 1.x (python-blosc, numcodecs ...) reads.  shuffle: 0 none, 1 byte
  * shuffle, 2 bit shuffle (BLOSC_NOSHUFFLE / BLOSC_SHUFFLE / BLOSC_BITSHUFFLE); LZ4 streams; block size 4096 x typesize (split) or
  * 4096 (not split), so that every stream is one chunk of this library's encoder; n below 2 GiB (c-blosc's limit).  Returns the
