@@ -2,7 +2,10 @@
 offsets) instead of coming from an encoder, so that shapes no encoder of ours emits get decoded too -- offsets up to 65535,
 overlapping matches with every small period, matches that reach exactly to the first byte of the block, sequences without
 literals, length extensions of one to thousands of bytes, runs of MiB.  The block only has to obey the FORMAT
-(token, lengths, offset <= bytes produced so far); the expected output is what the oracle's decoder makes of it."""
+(token, lengths, offset <= bytes produced so far); the expected output is what the oracle's decoder makes of it.
+
+build_stream() / expand() are the same for blocks made by hand: the sequences are given one by one, and what they decode to follows from
+the builder's own arithmetic, without any decoder (tests/cblosc_lz4_cases.py builds the LZ4 streams of C-Blosc-1 frames with them)."""
 import numpy as np
 
 
@@ -14,9 +17,45 @@ def _ext(n):
     return out
 
 
-def random_block(rng, target_out, regime_len=1 << 20, align=1):
+def build_stream(sequences, final):
+    """sequences: [(literal bytes, offset, match length)], match length >= 4, 1 <= offset <= 65535 (NOT checked against the bytes produced so
+    far: an invalid block is built like a valid one); final: the literals of the last, literal-only sequence.  Returns the LZ4 block."""
+    s = bytearray()
+    for lit, off, ml in sequences:
+        lit = bytes(lit)
+        assert ml >= 4 and 0 <= off <= 65535, (off, ml)
+        s.append((min(len(lit), 15) << 4) | min(ml - 4, 15))
+        if len(lit) >= 15: s += _ext(len(lit) - 15)
+        s += lit
+        s += bytes((off & 255, off >> 8))
+        if ml - 4 >= 15: s += _ext(ml - 4 - 15)
+    final = bytes(final)
+    s.append(min(len(final), 15) << 4)
+    if len(final) >= 15: s += _ext(len(final) - 15)
+    s += final
+    return bytes(s)
+
+
+def expand(sequences, final):
+    """What build_stream(sequences, final) decodes to: a match copies from `off` bytes back, and one longer than `off` repeats those bytes
+    (every offset must lie inside what has been produced)."""
+    out = bytearray()
+    for lit, off, ml in sequences:
+        out += lit
+        assert 1 <= off <= len(out), (off, len(out))
+        if off >= ml:
+            out += out[len(out) - off:len(out) - off + ml]
+        else:
+            pat = bytes(out[len(out) - off:])
+            out += (pat * (ml // off + 1))[:ml]
+    out += final
+    return bytes(out)
+
+
+def random_block(rng, target_out, regime_len=1 << 20, align=1, min_final=0):
     """Returns (block bytes, decoded length).  `target_out`: decoded bytes wanted at least (the last sequence is literal-only and
-    brings the decoded length to a multiple of `align`)."""
+    brings the decoded length to a multiple of `align`).  min_final: the fewest literals of that last sequence (liblz4 refuses blocks that
+    end in fewer than 5, or whose last match ends inside the last 12 bytes); applied after the draw, so 0 changes nothing."""
     s = bytearray()
     produced = 0
     regimes = ("dense", "runs", "literal", "far", "mixed", "periodic", "huge")
@@ -54,6 +93,8 @@ def random_block(rng, target_out, regime_len=1 << 20, align=1):
             produced += lit + ml
     lit = int(rng.integers(0, 30))                                  # the final, literal-only sequence
     lit += (-(produced + lit)) % align
+    if lit < min_final:
+        lit += -(-(min_final - lit) // align) * align
     s.append(min(lit, 15) << 4)
     if lit >= 15: s += _ext(lit - 15)
     s += rng.integers(0, 256, lit, dtype=np.uint8).tobytes()
