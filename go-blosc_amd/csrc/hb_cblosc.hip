@@ -14,14 +14,19 @@
 //   only when the block holds a multiple of 8 elements, else the block is stored unfiltered (shuffle.c blosc_internal_bitshuffle).
 //
 // Blocks and streams are independent, so there is no discovery problem here: k_cb_plan lists the streams (one lane per block
-// walks its cbytes fields), k_cb_decode puts one wavefront on every stream (the serial block decoder of hb_dec_common.h: streams
-// are 8-256 KiB, hundreds to thousands per frame), k_cb_unfilter undoes the per-block filter.  LZ4 / LZ4HC and memcpyed frames, and
-// -- once hb_cblosc_accept_codecs(0x3) has said so -- BloscLZ (the *_blz kernels: the same decoder behind bz_walk, hb_lz4_region.h);
-// the other codec formats are entropy coders.
+// walks its cbytes fields), k_cb_streams puts one wavefront on every stream (streams are 8-256 KiB, hundreds to thousands per
+// frame), k_cb_unfilter undoes the per-block filter.  LZ4 / LZ4HC and memcpyed frames, and -- once hb_cblosc_accept_codecs(0x3)
+// has said so -- BloscLZ (the same decoder behind bz_walk, hb_lz4_region.h); the other codec formats are entropy coders.
+// ONE stream-decode kernel serves every path: k_cb_streams<SPACE, WHICH>, a loop over the permuted stream order with the LZ4, the
+// BloscLZ or the small (LDS-resident) decoder as its body.  A SPACE says who owns stream i -- the one frame of the call (CbOneSpace),
+// a frame of a batch (CbbSpace), a block record of a getitem / box / slice / update batch (CbgSpace) -- and cb_launch_streams launches
+// what the owners need, small, then LZ4, then BloscLZ, with cb_decode_schedule's grids (hb_cblosc_batch.h), under the profile stage
+// names k_cb_decode[_small|_blz], k_cbb_decode[...] and k_cbg_decode[...] of the three families.
 #include "hb_sym_decode.h"
 
 #include <atomic>
 #include <cstring>
+#include <type_traits>
 #include "hb_cblosc_batch.h"       // the flags, cb_nsplit, CbStream / CbPlan, and the host side of the batch
 #include "hb_cblosc_enc_batch.h"   // the geometry of a written frame, and the host side of the batched encode
 #include "hb_cblosc_getitem_batch.h"   // the geometry of an item range, and the host side of the batched getitem
@@ -68,16 +73,10 @@ __global__ void k_cb_plan(const uint8_t *__restrict__ frame, uint64_t n, uint32_
     cb_plan_block(frame, nbytes, blocksize, cbytes, typesize, flags, plan, streams, b0, idx);
 }
 
-#define CB_SMALL_IN 3072u        // longest stream k_cb_decode_small stages (see there)
+#define CB_SMALL_IN 3072u        // longest stream the small decoder stages (cb_decode_small_stream)
 // ---- one wavefront per stream ----
-// (the bodies are device functions: the one-frame kernels pass their own frame, plan and target, the batch kernels k_cbb_* those of the frame
-// that owns the stream.  Everything they are given is wave-uniform, and so is every way out of them.)
-// stream i of the permuted order: stream i is byte plane i % typesize of its block, workgroup it runs on XCD it % 8, and the planes differ
-// several times in cost -- in stream order two XCDs would get all the streams of the token-dense plane (measured: 3.1 ms against 1.5).
-// Workgroup (step k = it / 8, XCD x = it % 8) takes stream 8 * (k * P mod m) + (x + k) % 8; grid a multiple of 8.
-__device__ __forceinline__ uint32_t cb_stream_of(uint32_t it, uint32_t mgrp, uint32_t P) {
-    return (uint32_t)(((uint64_t)(it >> 3) * P) % mgrp) * 8u + ((it + (it >> 3) + it / gridDim.x) & 7u);
-}
+// (the bodies are device functions: the kernel template k_cb_streams below passes the frame, plan and target of whoever owns the stream.
+// Everything they are given is wave-uniform, and so is every way out of them.)
 __device__ __forceinline__ CbStream cb_load_stream(const CbStream *__restrict__ streams, uint32_t i) {
     CbStream st = streams[i];                                                  // wave-uniform, but it comes out of a vector load: to scalar registers
     st.src = RFL(st.src); st.csize = RFL(st.csize); st.dst = RFL(st.dst); st.usize = RFL(st.usize);
@@ -91,7 +90,7 @@ __device__ __forceinline__ void cb_decode_stream(const uint8_t *__restrict__ fra
                                                  uint8_t *s_win, uint2 *s_tq, uint8_t *s_d, int lane) {
     if (st.usize == 0u) return;
     if (st.csize == st.usize) { wave_copy_g2g(dst + st.dst, frame + st.src, st.usize, lane); return; }      // stored
-    if (small_elsewhere && st.usize <= HB_CHUNK && st.csize <= CB_SMALL_IN) return;      // k_cb_decode_small has it
+    if (small_elsewhere && st.usize <= HB_CHUNK && st.csize <= CB_SMALL_IN) return;      // the small decoder has it
     uint32_t out = st.dst;
     bool parked;
     const bool ok = sy_decode_unit<false, RG_PWIN, false, CODEC>(frame + st.src, (uint64_t)st.csize, 0u, st.csize, st.dst, st.dst, out, dst, nullptr, s_win, s_tq, s_d, nullptr,
@@ -99,47 +98,13 @@ __device__ __forceinline__ void cb_decode_stream(const uint8_t *__restrict__ fra
     if ((!ok || out != st.dst + st.usize) && lane == 0) atomicExch(&plan->fail, 1u);     // blosc_d: "nbytes != neblock -> -2"
     wave_sync();
 }
-__global__ __launch_bounds__(64) void k_cb_decode(const uint8_t *__restrict__ frame, CbPlan *plan, const CbStream *__restrict__ streams, uint32_t nstreams,
-                                                   uint8_t *dst, int small_elsewhere, uint32_t P) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_win[RG_PWIN + 128];
-    __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
-    __shared__ __attribute__((aligned(16))) uint8_t s_d[SY_IMG + 64];
-    const int lane = threadIdx.x;
-    if (plan->fail) return;
-    // one stream per workgroup up to 65536 streams, so that a finished cheap stream makes room for the next one
-    const uint32_t mgrp = (nstreams + 7u) / 8u;
-    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
-        const uint32_t i = cb_stream_of(it, mgrp, P);
-        if (i >= nstreams) continue;
-        cb_decode_stream(frame, plan, cb_load_stream(streams, i), dst, small_elsewhere, s_win, s_tq, s_d, lane);
-    }
-}
-
-// The streams of a BloscLZ frame (codec format 0; accepted once hb_cblosc_accept_codecs has said so): the same decoder behind the BloscLZ
-// walker, the same LDS.  The host launches it INSTEAD of k_cb_decode / k_cb_decode_small -- a frame has one codec -- so the LZ4 kernels never
-// see such a stream, the small one included, which selects by size alone.  Stored streams are copied here.
-__global__ __launch_bounds__(64) void k_cb_decode_blz(const uint8_t *__restrict__ frame, CbPlan *plan, const CbStream *__restrict__ streams, uint32_t nstreams,
-                                                       uint8_t *dst, uint32_t P) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_win[RG_PWIN + 128];
-    __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
-    __shared__ __attribute__((aligned(16))) uint8_t s_d[SY_IMG + 64];
-    const int lane = threadIdx.x;
-    if (plan->fail) return;
-    const uint32_t mgrp = (nstreams + 7u) / 8u;
-    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
-        const uint32_t i = cb_stream_of(it, mgrp, P);
-        if (i >= nstreams) continue;
-        cb_decode_stream<RG_BLOSCLZ>(frame, plan, cb_load_stream(streams, i), dst, 0, s_win, s_tq, s_d, lane);
-    }
-}
-
 // Streams of at most one chunk (what hb_cblosc_compress writes: every stream is a 4 KiB chunk of the matcher): stream and output both
 // fit into LDS, so the chunk decoder's machinery applies as it is -- window-parallel token parser, one token per lane, copies inside
-// the LDS image in dependency rounds (hb_dec_common.h) -- at 17 wavefronts per CU.  k_cb_decode leaves these streams alone.
+// the LDS image in dependency rounds (hb_dec_common.h) -- at 17 wavefronts per CU.  The LZ4 decoder leaves these streams alone.
 #define CB_SMALL HB_CHUNK
 __device__ __forceinline__ void cb_decode_small_stream(const uint8_t *__restrict__ frame, CbPlan *plan, const CbStream st, uint8_t *__restrict__ dst,
                                                        uint8_t *s_in, uint8_t *s_out, uint2 *s_tq, int lane) {
-    if (st.usize == 0u || st.usize > CB_SMALL || st.csize == st.usize || st.csize > CB_SMALL_IN) return;      // (stored streams: k_cb_decode copies them)
+    if (st.usize == 0u || st.usize > CB_SMALL || st.csize == st.usize || st.csize > CB_SMALL_IN) return;      // (stored streams: the LZ4 decoder copies them)
     const uint8_t *g = frame + st.src;
     const uint32_t sh = (uint32_t)((uintptr_t)g & 15u), slen = st.csize;           // slen < usize <= 4096
     wave_sync();
@@ -184,19 +149,101 @@ __device__ __forceinline__ void cb_decode_small_stream(const uint8_t *__restrict
     const uint32_t t0 = st.usize & ~15u;
     if (t0 + (uint32_t)lane < st.usize) o[t0 + lane] = s_out[t0 + lane];
 }
-__global__ __launch_bounds__(64) void k_cb_decode_small(const uint8_t *__restrict__ frame, CbPlan *plan, const CbStream *__restrict__ streams, uint32_t nstreams,
-                                                         uint8_t *__restrict__ dst, uint32_t P) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_in[CB_SMALL_IN + 64 + 128];
-    __shared__ __attribute__((aligned(16))) uint8_t s_out[CB_SMALL + 64];
+// ---- who owns stream i: a space gives the unified loop below the wave-uniform context of a stream -- the compressed frame, the plan to read
+// and to fail, where the decoded bytes go, whether the owner's codec is BloscLZ, whether its streams are at most one chunk ("small": an LZ4
+// owner only).  The owner index and the fail word come out of vector loads and go through RFL: the bodies above contain wave_sync. ----
+struct CbCtx { const uint8_t *frame; CbPlan *plan; uint8_t *target; bool blz, small; };
+// What the batches' spaces look up -- frame and block records, stream prefixes -- went up before the launch and nobody writes it while a kernel
+// runs.  It is read through the constant address space, so that these wave-uniform reads are scalar loads: a `const T *__restrict__` kernel
+// argument gets that by itself, a pointer inside an argument struct carries no such promise (as vector loads they cost k_cbb_decode 6 %:
+// profiles/cblosc_decode_unify_ab.json, first_build_ms).
+#define CB_RO(T) const __attribute__((address_space(4))) T
+template <class T>
+__device__ __forceinline__ CB_RO(T) *cb_ro(const T *p) { return (CB_RO(T) *)(uintptr_t)p; }
+// one frame (hb_cblosc_decompress_dev, hb_cblosc_getitem_device): what the host decided, for every stream
+struct CbOneSpace {
+    const uint8_t *frame; CbPlan *plan; uint8_t *target; int blz, small;
+    static constexpr bool one_plan = true;                                 // one owner: the kernel tests its fail word once, on entry (per stream: +2.7 % on k_cb_decode, second_build_ms of the same file)
+    __device__ __forceinline__ CbCtx operator()(uint32_t) const { return CbCtx{frame, plan, target, blz != 0, small != 0}; }
+};
+// a batch of whole frames: the frame that owns the stream -- its staged copy, or its destination when there is no filter to undo
+struct CbbSpace {
+    const CbbFrame *frames; CbPlan *plans; const uint32_t *str0; uint32_t nframes; uint8_t *work;
+    static constexpr bool one_plan = false;
+    __device__ __forceinline__ CbCtx operator()(uint32_t i) const {
+        const uint32_t k = RFL(hb_owner(cb_ro(str0), nframes, i));
+        CB_RO(CbbFrame) &F = cb_ro(frames)[k];
+        return CbCtx{F.frame, plans + k, F.stage_off ? work + F.stage_off : F.dst, cb_is_blosclz(F.flags), F.small != 0u};
+    }
+};
+// a batch of block records (the getitem, box, slice and update batches): the record's own plan, its staged copy as the target (also without a
+// filter: a stream cannot be decoded in part)
+struct CbgSpace {
+    const CbgFrame *frames; const CbgBlock *blocks; CbPlan *plans; const uint32_t *str0; uint32_t nblk; uint8_t *work;
+    static constexpr bool one_plan = false;
+    __device__ __forceinline__ CbCtx operator()(uint32_t i) const {
+        const uint32_t x = RFL(hb_owner(cb_ro(str0), nblk, i));
+        CB_RO(CbgBlock) &K = cb_ro(blocks)[x];
+        CB_RO(CbgFrame) &F = cb_ro(frames)[K.frame];
+        return CbCtx{F.frame, plans + x, work + K.stage_off, cb_is_blosclz(F.flags), F.small != 0u};
+    }
+};
+// The one stream-decode kernel: one wavefront per stream of the space, in the permuted order (cb_stream_of) over all of it; the host's grids
+// are cb_decode_schedule's.  WHICH is the decoder: LZ4 (stored streams of LZ4 owners are copied here; with the small decoder launched, the
+// short streams of small owners are left to it), BloscLZ (the same decoder behind bz_walk, hb_lz4_region.h, stored streams included: an owner
+// has one codec, so each of the two passes the other's owners by), or the small decoder (small owners only: it selects by that and by size).
+// In a batch a stream is skipped once its owner's plan has failed -- one value for the whole wave: nobody is left behind at a wave_sync.
+enum { CBW_LZ4 = 0, CBW_BLZ, CBW_SMALL };
+template <class SPACE, int WHICH>
+__global__ __launch_bounds__(64) void k_cb_streams(SPACE sp, const CbStream *__restrict__ streams, uint32_t nstreams, int small_launched, uint32_t P) {
     __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
     const int lane = threadIdx.x;
-    if (plan->fail) return;
-    const uint32_t mgrp = (nstreams + 7u) / 8u;                                // (stream order as in k_dec_indexed, hb_lz4_dec.hip: cb_stream_of)
+    const uint32_t mgrp = (nstreams + 7u) / 8u;
+    if constexpr (SPACE::one_plan) { if (sp(0u).plan->fail) return; }
     for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
-        const uint32_t i = cb_stream_of(it, mgrp, P);
+        const uint32_t i = cb_stream_of(it, mgrp, P, gridDim.x);
         if (i >= nstreams) continue;
-        cb_decode_small_stream(frame, plan, cb_load_stream(streams, i), dst, s_in, s_out, s_tq, lane);
+        const CbCtx c = sp(i);
+        if constexpr (!SPACE::one_plan) { if (RFL(c.plan->fail)) continue; }
+        if constexpr (WHICH == CBW_SMALL) {
+            __shared__ __attribute__((aligned(16))) uint8_t s_in[CB_SMALL_IN + 64 + 128];
+            __shared__ __attribute__((aligned(16))) uint8_t s_out[CB_SMALL + 64];
+            if (!c.small) continue;
+            cb_decode_small_stream(c.frame, c.plan, cb_load_stream(streams, i), c.target, s_in, s_out, s_tq, lane);
+        } else {
+            __shared__ __attribute__((aligned(16))) uint8_t s_win[RG_PWIN + 128];
+            __shared__ __attribute__((aligned(16))) uint8_t s_d[SY_IMG + 64];
+            if (c.blz != (WHICH == CBW_BLZ)) continue;
+            cb_decode_stream<WHICH == CBW_BLZ ? RG_BLOSCLZ : RG_LZ4>(c.frame, c.plan, cb_load_stream(streams, i), c.target, WHICH == CBW_LZ4 && small_launched && c.small,
+                                                                     s_win, s_tq, s_d, lane);
+        }
     }
+}
+
+// a run-time kind (CBK_* / CBG_*: 0 .. 3) as a compile-time one: f(std::integral_constant<int, K>{}); anything else is the last kind
+static_assert(CBK_COUNT == 4 && CBK_COPY == 3 && CBG_COUNT == 4 && CBG_BITUN4 == 3, "cb_with_kind's default is the last kind of either set");
+template <class F>
+static inline void cb_with_kind(int k, F &&f) {
+    switch (k) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    default: f(std::integral_constant<int, 3>{}); break;
+    }
+}
+// The decoder launches of a space: the small decoder, LZ4, BloscLZ, each when an owner needs it, under the stage names of the family.
+template <class SPACE>
+static void cb_launch_streams(const SPACE &sp, const CbStream *streams, uint32_t nstreams, uint32_t any_small, uint32_t any_lz4, uint32_t any_blz, uint32_t nsplit_all,
+                              const char *name_small, const char *name_lz4, const char *name_blz, hipStream_t s) {
+    const CbSchedule S = cb_decode_schedule(nstreams, nsplit_all, any_small);
+    auto launch = [&](auto which, uint32_t grid, const char *name) {
+        hb_prof_begin(name, s);
+        hipLaunchKernelGGL((k_cb_streams<SPACE, decltype(which)::value>), dim3(grid), dim3(64), 0, s, sp, streams, nstreams, (int)any_small, S.P);
+        hb_prof_end(s);
+    };
+    if (any_small) launch(std::integral_constant<int, CBW_SMALL>{}, S.grid_small, name_small);
+    if (any_lz4) launch(std::integral_constant<int, CBW_LZ4>{}, S.grid_lz4, name_lz4);      // (any owner can have stored streams: it runs next to the small one)
+    if (any_blz) launch(std::integral_constant<int, CBW_BLZ>{}, S.grid_blz, name_blz);
 }
 
 // ---- the per-block filters, undone ----
@@ -369,6 +416,8 @@ __device__ __forceinline__ void cb_result(const CbPlan *plan, hb_result *result,
     else { result->status = HB_OK; result->bytes = nbytes; }
 }
 __global__ void k_cb_result(const CbPlan *plan, hb_result *result, uint64_t nbytes) { cb_result(plan, result, nbytes); }
+// a job or a frame the host refused: its status, nothing decoded
+__device__ __forceinline__ void cb_refused_result(hb_result *r, int status) { r->status = status; r->flags = 0; r->bytes = 0; r->total_bytes = 0; r->reserved = 0; }
 __global__ void k_cb_init(CbPlan *plan) { plan->fail = 0; }
 
 // ---- batches (hb_cblosc_decompress_frames_batch_device): many frames through ONE set of launches.  Blocks and streams are as independent
@@ -381,68 +430,6 @@ __global__ __launch_bounds__(64) void k_cbb_plan(const CbbFrame *__restrict__ fr
     const uint32_t k = hb_owner(blk0, nframes, x);
     const CbbFrame &F = frames[k];
     cb_plan_block(F.frame, F.nbytes, F.blocksize, F.cbytes, F.typesize, F.flags, plans + k, streams + F.stream0, F.b0, x - blk0[k]);
-}
-
-// one wavefront per stream of the flat stream space, in the permuted order over all of it.  The stream's frame gives the plan to read and to
-// fail, the source and the target (its staged copy, or its destination when there is no filter to undo).  A stream goes to the small decoder
-// exactly when hb_cblosc_decompress_dev would send it there: its frame's streams are at most one chunk, and it is short enough and not stored.
-__global__ __launch_bounds__(64) void k_cbb_decode(const CbbFrame *__restrict__ frames, CbPlan *plans, const uint32_t *__restrict__ str0, uint32_t nframes,
-                                                    const CbStream *__restrict__ streams, uint32_t nstreams, uint8_t *work, int small_launched, uint32_t P) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_win[RG_PWIN + 128];
-    __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
-    __shared__ __attribute__((aligned(16))) uint8_t s_d[SY_IMG + 64];
-    const int lane = threadIdx.x;
-    const uint32_t mgrp = (nstreams + 7u) / 8u;
-    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
-        const uint32_t i = cb_stream_of(it, mgrp, P);
-        if (i >= nstreams) continue;
-        const uint32_t k = RFL(hb_owner(str0, nframes, i));
-        CbPlan *plan = plans + k;
-        if (RFL(plan->fail)) continue;                                         // (one value for the whole wave: nobody is left behind at a wave_sync)
-        const CbbFrame &F = frames[k];
-        if (cb_is_blosclz(F.flags)) continue;                                  // k_cbb_decode_blz has it (and F.small is 0: the small decoder passes it by)
-        uint8_t *target = F.stage_off ? work + F.stage_off : F.dst;
-        cb_decode_stream(F.frame, plan, cb_load_stream(streams, i), target, small_launched && F.small, s_win, s_tq, s_d, lane);
-    }
-}
-// the streams of the batch's BloscLZ frames (launched when there is one): the same walk over the flat stream space, the other codec's frames passed by
-__global__ __launch_bounds__(64) void k_cbb_decode_blz(const CbbFrame *__restrict__ frames, CbPlan *plans, const uint32_t *__restrict__ str0, uint32_t nframes,
-                                                        const CbStream *__restrict__ streams, uint32_t nstreams, uint8_t *work, uint32_t P) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_win[RG_PWIN + 128];
-    __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
-    __shared__ __attribute__((aligned(16))) uint8_t s_d[SY_IMG + 64];
-    const int lane = threadIdx.x;
-    const uint32_t mgrp = (nstreams + 7u) / 8u;
-    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
-        const uint32_t i = cb_stream_of(it, mgrp, P);
-        if (i >= nstreams) continue;
-        const uint32_t k = RFL(hb_owner(str0, nframes, i));
-        CbPlan *plan = plans + k;
-        if (RFL(plan->fail)) continue;
-        const CbbFrame &F = frames[k];
-        if (!cb_is_blosclz(F.flags)) continue;
-        uint8_t *target = F.stage_off ? work + F.stage_off : F.dst;
-        cb_decode_stream<RG_BLOSCLZ>(F.frame, plan, cb_load_stream(streams, i), target, 0, s_win, s_tq, s_d, lane);
-    }
-}
-__global__ __launch_bounds__(64) void k_cbb_decode_small(const CbbFrame *__restrict__ frames, CbPlan *plans, const uint32_t *__restrict__ str0, uint32_t nframes,
-                                                          const CbStream *__restrict__ streams, uint32_t nstreams, uint8_t *work, uint32_t P) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_in[CB_SMALL_IN + 64 + 128];
-    __shared__ __attribute__((aligned(16))) uint8_t s_out[CB_SMALL + 64];
-    __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
-    const int lane = threadIdx.x;
-    const uint32_t mgrp = (nstreams + 7u) / 8u;
-    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
-        const uint32_t i = cb_stream_of(it, mgrp, P);
-        if (i >= nstreams) continue;
-        const uint32_t k = RFL(hb_owner(str0, nframes, i));
-        const CbbFrame &F = frames[k];
-        if (!F.small) continue;
-        CbPlan *plan = plans + k;
-        if (RFL(plan->fail)) continue;
-        uint8_t *target = F.stage_off ? work + F.stage_off : F.dst;
-        cb_decode_small_stream(F.frame, plan, cb_load_stream(streams, i), target, s_in, s_out, s_tq, lane);
-    }
 }
 
 // one launch per kind that occurs: ufrm / ublk = the frames of this kind and the prefix of their workgroup counts (every frame has at least one).
@@ -478,7 +465,7 @@ __global__ __launch_bounds__(64) void k_cbb_finish(const CbbFrame *__restrict__ 
     if (k >= nframes) return;
     const CbbFrame &F = frames[k];
     hb_result *r = results + k;
-    if (F.mode == CBB_REFUSED) { r->status = F.status; r->flags = 0; r->bytes = 0; r->total_bytes = 0; r->reserved = 0; return; }
+    if (F.mode == CBB_REFUSED) { cb_refused_result(r, F.status); return; }
     cb_result(plans + k, r, (uint64_t)F.nbytes);
 }
 
@@ -493,68 +480,6 @@ __global__ __launch_bounds__(64) void k_cbg_plan(const CbgFrame *__restrict__ fr
     const CbgFrame &F = frames[K.frame];
     cb_plan_block(F.frame, F.nbytes, F.blocksize, F.cbytes, F.typesize, F.flags, plans + x, streams + K.stream0, K.b, 0u, true);
 }
-// one wavefront per stream of the flat stream space, in the permuted order over all of it: as k_cbb_decode / k_cbb_decode_small, with the block
-// record as the owner -- its plan to read and to fail, its staged copy as the target (also without a filter: an LZ4 stream cannot be decoded
-// in part).  A stream goes to the small decoder exactly when hb_cblosc_getitem_device would send it there.
-__global__ __launch_bounds__(64) void k_cbg_decode(const CbgFrame *__restrict__ frames, const CbgBlock *__restrict__ blocks, CbPlan *plans, const uint32_t *__restrict__ str0,
-                                                    uint32_t nblk, const CbStream *__restrict__ streams, uint32_t nstreams, uint8_t *work, int small_launched, uint32_t P) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_win[RG_PWIN + 128];
-    __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
-    __shared__ __attribute__((aligned(16))) uint8_t s_d[SY_IMG + 64];
-    const int lane = threadIdx.x;
-    const uint32_t mgrp = (nstreams + 7u) / 8u;
-    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
-        const uint32_t i = cb_stream_of(it, mgrp, P);
-        if (i >= nstreams) continue;
-        const uint32_t x = RFL(hb_owner(str0, nblk, i));
-        CbPlan *plan = plans + x;
-        if (RFL(plan->fail)) continue;                                         // (one value for the whole wave: nobody is left behind at a wave_sync)
-        const CbgBlock &K = blocks[x];
-        const CbgFrame &F = frames[K.frame];
-        if (cb_is_blosclz(F.flags)) continue;                                  // k_cbg_decode_blz has it (and F.small is 0: the small decoder passes it by)
-        cb_decode_stream(F.frame, plan, cb_load_stream(streams, i), work + K.stage_off, small_launched && F.small, s_win, s_tq, s_d, lane);
-    }
-}
-// the streams of the covered blocks of BloscLZ frames (launched when there is one)
-__global__ __launch_bounds__(64) void k_cbg_decode_blz(const CbgFrame *__restrict__ frames, const CbgBlock *__restrict__ blocks, CbPlan *plans, const uint32_t *__restrict__ str0,
-                                                        uint32_t nblk, const CbStream *__restrict__ streams, uint32_t nstreams, uint8_t *work, uint32_t P) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_win[RG_PWIN + 128];
-    __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
-    __shared__ __attribute__((aligned(16))) uint8_t s_d[SY_IMG + 64];
-    const int lane = threadIdx.x;
-    const uint32_t mgrp = (nstreams + 7u) / 8u;
-    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
-        const uint32_t i = cb_stream_of(it, mgrp, P);
-        if (i >= nstreams) continue;
-        const uint32_t x = RFL(hb_owner(str0, nblk, i));
-        CbPlan *plan = plans + x;
-        if (RFL(plan->fail)) continue;
-        const CbgBlock &K = blocks[x];
-        const CbgFrame &F = frames[K.frame];
-        if (!cb_is_blosclz(F.flags)) continue;
-        cb_decode_stream<RG_BLOSCLZ>(F.frame, plan, cb_load_stream(streams, i), work + K.stage_off, 0, s_win, s_tq, s_d, lane);
-    }
-}
-__global__ __launch_bounds__(64) void k_cbg_decode_small(const CbgFrame *__restrict__ frames, const CbgBlock *__restrict__ blocks, CbPlan *plans, const uint32_t *__restrict__ str0,
-                                                          uint32_t nblk, const CbStream *__restrict__ streams, uint32_t nstreams, uint8_t *work, uint32_t P) {
-    __shared__ __attribute__((aligned(16))) uint8_t s_in[CB_SMALL_IN + 64 + 128];
-    __shared__ __attribute__((aligned(16))) uint8_t s_out[CB_SMALL + 64];
-    __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
-    const int lane = threadIdx.x;
-    const uint32_t mgrp = (nstreams + 7u) / 8u;
-    for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
-        const uint32_t i = cb_stream_of(it, mgrp, P);
-        if (i >= nstreams) continue;
-        const uint32_t x = RFL(hb_owner(str0, nblk, i));
-        const CbgBlock &K = blocks[x];
-        const CbgFrame &F = frames[K.frame];
-        if (!F.small) continue;
-        CbPlan *plan = plans + x;
-        if (RFL(plan->fail)) continue;
-        cb_decode_small_stream(F.frame, plan, cb_load_stream(streams, i), work + K.stage_off, s_in, s_out, s_tq, lane);
-    }
-}
-
 // ---- the clipped un-filter: byte p of the frame's decoded bytes out of the staged blocks.  `look(b)` is the record of block number b: the
 // ranges' jobs have consecutive records (CbgSeqLookup), the boxes' a list of the blocks they touch (CbxLookup).  The plain body: the edges of
 // every range, and every shape the wide bodies below leave alone. ----
@@ -670,7 +595,7 @@ __global__ __launch_bounds__(64) void k_cbg_finish(const CbgJob *__restrict__ jo
     if (j >= njobs) return;
     const CbgJob &J = jobs[j];
     hb_result *r = results + j;
-    if (J.status) { r->status = J.status; r->flags = 0; r->bytes = 0; r->total_bytes = 0; r->reserved = 0; return; }
+    if (J.status) { cb_refused_result(r, J.status); return; }
     CbPlan p; p.fail = 0u;
     for (uint32_t k = 0; k < J.nb; k++) p.fail |= plans[J.blk0 + k].fail;
     cb_result(&p, r, J.bytes);
@@ -779,7 +704,7 @@ __global__ __launch_bounds__(64) void k_cbx_finish(const CbxJob *__restrict__ jo
     if (j >= njobs) return;
     const CbxJob &J = jobs[j];
     hb_result *r = results + j;
-    if (J.status) { r->status = J.status; r->flags = 0; r->bytes = 0; r->total_bytes = 0; r->reserved = 0; return; }
+    if (J.status) { cb_refused_result(r, J.status); return; }
     CbPlan p; p.fail = 0u;
     for (uint32_t k = 0; k < J.ntl; k++) p.fail |= plans[touch[J.tl0 + k].rec].fail;
     cb_result(&p, r, J.bytes);
@@ -1115,39 +1040,11 @@ static void cb_launch_blocks(const hb_cblosc_header *hdr, const uint8_t *d_frame
     const uint32_t nstreams = nblocks * nsplit;
     hb_prof_begin("k_cb_plan", s);
     hipLaunchKernelGGL(k_cb_plan, dim3((nblocks + 63) / 64), dim3(64), 0, s, d_frame, (uint64_t)n, hdr->nbytes, blocksize, hdr->cbytes, ts, flags, plan, streams, b0, nblocks);
-    const bool small = blocksize / nsplit <= HB_CHUNK;                   // streams of at most one chunk: the LDS-resident decoder takes them
     hb_prof_end(s);
-    const uint32_t mgrp = (nstreams + 7u) / 8u;
-    uint32_t P = mgrp / 4u + 1u;                                        // coprime to the groups of 8 streams, about a quarter turn
-    for (;; P++) { uint32_t x = P, y = mgrp; while (y) { const uint32_t t = x % y; x = y; y = t; } if (x == 1u) break; }
-    const unsigned grid = mgrp * 8u < 65536u ? mgrp * 8u : 65536u;
-    if (hdr->codec_format == CB_CODEC_BLOSCLZ) {                          // (accepted by the caller: hb_cblosc_accept_codecs)  One codec per frame: its decoder alone
-        unsigned gblz = grid;
-        if (nsplit > 1u) {                                              // (passes per workgroup as below)
-            unsigned p = nsplit;
-            while (p > 1u && mgrp * 8u / p < 2048u) p >>= 1;
-            gblz = (mgrp * 8u / p + 7u) / 8u * 8u;
-        }
-        hb_prof_begin("k_cb_decode_blz", s);
-        hipLaunchKernelGGL(k_cb_decode_blz, dim3(gblz), dim3(64), 0, s, d_frame, plan, streams, nstreams, target, P);
-        hb_prof_end(s);
-    } else {
-    hb_prof_begin("k_cb_decode_small", s);
-    if (small) hipLaunchKernelGGL(k_cb_decode_small, dim3(grid), dim3(64), 0, s, d_frame, plan, streams, nstreams, target, P);
-    hb_prof_end(s);
-    hb_prof_begin("k_cb_decode", s);
-    // (long streams: as many passes per workgroup as a block has streams, fewer while that leaves under 2048 workgroups -- with the
-    // rotation by the pass number a workgroup decodes one stream of each plane, and all workgroups live about equally long; see
-    // k_cb_decode_small)
-    unsigned gbig = grid;
-    if (!small && nsplit > 1u) {
-        unsigned p = nsplit;
-        while (p > 1u && mgrp * 8u / p < 2048u) p >>= 1;
-        gbig = (mgrp * 8u / p + 7u) / 8u * 8u;
-    }
-    hipLaunchKernelGGL(k_cb_decode, dim3(gbig), dim3(64), 0, s, d_frame, plan, streams, nstreams, target, small ? 1 : 0, P);
-    hb_prof_end(s);
-    }
+    const bool blz = hdr->codec_format == CB_CODEC_BLOSCLZ;              // (accepted by the caller: hb_cblosc_accept_codecs)  One codec per frame: its decoder alone
+    const bool small = !blz && blocksize / nsplit <= HB_CHUNK;           // streams of at most one chunk: the LDS-resident decoder takes them
+    if (!blz && !small) { hb_prof_begin("k_cb_decode_small", s); hb_prof_end(s); }      // (every LZ4 frame reports the same stages, this one empty here: the rate tools' tables key on them)
+    cb_launch_streams(CbOneSpace{d_frame, plan, target, blz, small}, streams, nstreams, small, !blz, blz, nsplit, "k_cb_decode_small", "k_cb_decode", "k_cb_decode_blz", s);
     if (filtered) {
         hb_prof_begin("k_cb_unfilter", s);
         if (unshuf)
@@ -1245,54 +1142,15 @@ static int cbb_launch_batch(int nframes, const CbbBatch &B, uint8_t *w, hb_resul
         hb_prof_begin("k_cbb_plan", s);
         hipLaunchKernelGGL(k_cbb_plan, dim3((nblocks + 63u) / 64u), dim3(64), 0, s, d_frames, d_plans, d_blk0, (uint32_t)nframes, nblocks, d_streams);
         hb_prof_end(s);
-        const uint32_t mgrp = (nstreams + 7u) / 8u;
-        uint32_t P = mgrp / 4u + 1u;                                    // coprime to the groups of 8 streams, about a quarter turn (cb_launch_blocks)
-        for (;; P++) { uint32_t x = P, y = mgrp; while (y) { const uint32_t t = x % y; x = y; y = t; } if (x == 1u) break; }
-        const unsigned grid = mgrp * 8u < 65536u ? mgrp * 8u : 65536u;
-        if (B.any_small) {
-            hb_prof_begin("k_cbb_decode_small", s);
-            hipLaunchKernelGGL(k_cbb_decode_small, dim3(grid), dim3(64), 0, s, d_frames, d_plans, d_str0, (uint32_t)nframes, (const CbStream *)d_streams, nstreams, w, P);
-            hb_prof_end(s);
-        }
-        // (any frame with streams can have stored ones: the general decoder always runs.  Its passes per workgroup as in cb_launch_blocks, when
-        // no frame has short streams and all split alike)
-        unsigned gbig = grid;
-        if (!B.any_small && B.nsplit_all > 1u) {
-            unsigned p = B.nsplit_all;
-            while (p > 1u && mgrp * 8u / p < 2048u) p >>= 1;
-            gbig = (mgrp * 8u / p + 7u) / 8u * 8u;
-            if (gbig > 65536u) gbig = 65536u;
-        }
-        if (B.any_lz4) {
-            hb_prof_begin("k_cbb_decode", s);
-            hipLaunchKernelGGL(k_cbb_decode, dim3(gbig), dim3(64), 0, s, d_frames, d_plans, d_str0, (uint32_t)nframes, (const CbStream *)d_streams, nstreams, w, (int)B.any_small, P);
-            hb_prof_end(s);
-        }
-        if (B.any_blz) {                                                // (the BloscLZ frames' streams, stored ones included; grid as gbig without the small decoder)
-            unsigned gblz = grid;
-            if (B.nsplit_all > 1u) {
-                unsigned p = B.nsplit_all;
-                while (p > 1u && mgrp * 8u / p < 2048u) p >>= 1;
-                gblz = (mgrp * 8u / p + 7u) / 8u * 8u;
-                if (gblz > 65536u) gblz = 65536u;
-            }
-            hb_prof_begin("k_cbb_decode_blz", s);
-            hipLaunchKernelGGL(k_cbb_decode_blz, dim3(gblz), dim3(64), 0, s, d_frames, d_plans, d_str0, (uint32_t)nframes, (const CbStream *)d_streams, nstreams, w, P);
-            hb_prof_end(s);
-        }
+        cb_launch_streams(CbbSpace{d_frames, d_plans, d_str0, (uint32_t)nframes, w}, d_streams, nstreams, B.any_small, B.any_lz4, B.any_blz, B.nsplit_all,
+                          "k_cbb_decode_small", "k_cbb_decode", "k_cbb_decode_blz", s);
     }
     for (int k = 0; k < CBK_COUNT; k++) {
         const uint32_t k0 = B.kind0[k], nk = B.kind0[k + 1] - k0, blocks = B.kblocks[k];
         if (!nk) continue;
         hb_prof_begin(k == CBK_COPY ? "k_cbb_copy" : "k_cbb_unfilter", s);
-#define CBB_LAUNCH(K) hipLaunchKernelGGL(k_cbb_unfilter<K>, dim3(blocks), dim3(256), 0, s, d_frames, d_ufrm + k0, d_ublk + k0, nk, w)
-        switch (k) {
-        case CBK_UNSHUFFLE: CBB_LAUNCH(CBK_UNSHUFFLE); break;
-        case CBK_BITUN: CBB_LAUNCH(CBK_BITUN); break;
-        case CBK_BITUN4: CBB_LAUNCH(CBK_BITUN4); break;
-        default: CBB_LAUNCH(CBK_COPY); break;
-        }
-#undef CBB_LAUNCH
+        // (any other kind: CBK_COPY, the last)
+        cb_with_kind(k, [&](auto K) { hipLaunchKernelGGL(k_cbb_unfilter<K.value>, dim3(blocks), dim3(256), 0, s, d_frames, d_ufrm + k0, d_ublk + k0, nk, w); });
         hb_prof_end(s);
     }
     hb_prof_begin("k_cbb_finish", s);
@@ -1369,39 +1227,14 @@ int hb_cblosc_getitem_device(const hb_cblosc_header *hdr, const void *d_frame, s
 }
 
 // The plan and the stream decoders over the block records of a batch (hb_cblosc_getitem_frames_batch_device and hb_cblosc_getbox_frames_batch_device
-// build the same records): k_cbg_plan, then one decoder launch per kind that occurs.
+// build the same records): k_cbg_plan, then one decoder launch per kind that occurs (stages k_cbg_decode_small / k_cbg_decode / k_cbg_decode_blz).
 static void cbg_launch_decoders(uint32_t nblk, uint32_t nstreams, uint32_t any_small, uint32_t nsplit_all, uint32_t any_lz4, uint32_t any_blz, const CbgFrame *d_frames,
                                 const CbgBlock *d_blocks, CbPlan *d_plans, const uint32_t *d_str0, CbStream *d_streams, uint8_t *w, hipStream_t s) {
     hb_prof_begin("k_cbg_plan", s);
     hipLaunchKernelGGL(k_cbg_plan, dim3((nblk + 63u) / 64u), dim3(64), 0, s, d_frames, d_blocks, d_plans, nblk, d_streams);
     hb_prof_end(s);
-    const uint32_t mgrp = (nstreams + 7u) / 8u;
-    uint32_t P = mgrp / 4u + 1u;                                    // coprime to the groups of 8 streams, about a quarter turn (cb_launch_blocks)
-    for (;; P++) { uint32_t x = P, y = mgrp; while (y) { const uint32_t t = x % y; x = y; y = t; } if (x == 1u) break; }
-    const unsigned grid = mgrp * 8u < 65536u ? mgrp * 8u : 65536u;
-    unsigned gsplit = grid;                                         // several passes per workgroup where all frames split alike, as in the batched decode
-    if (nsplit_all > 1u) {
-        unsigned p = nsplit_all;
-        while (p > 1u && mgrp * 8u / p < 2048u) p >>= 1;
-        gsplit = (mgrp * 8u / p + 7u) / 8u * 8u;
-        if (gsplit > 65536u) gsplit = 65536u;
-    }
-    if (any_small) {
-        hb_prof_begin("k_cbg_decode_small", s);
-        hipLaunchKernelGGL(k_cbg_decode_small, dim3(grid), dim3(64), 0, s, d_frames, d_blocks, d_plans, d_str0, nblk, (const CbStream *)d_streams, nstreams, w, P);
-        hb_prof_end(s);
-    }
-    if (any_lz4) {                                                  // (any block can have stored streams: the general decoder runs next to the small one)
-        hb_prof_begin("k_cbg_decode", s);
-        hipLaunchKernelGGL(k_cbg_decode, dim3(any_small ? grid : gsplit), dim3(64), 0, s, d_frames, d_blocks, d_plans, d_str0, nblk, (const CbStream *)d_streams, nstreams, w,
-                           (int)any_small, P);
-        hb_prof_end(s);
-    }
-    if (any_blz) {                                                  // (the covered blocks of BloscLZ frames, stored streams included)
-        hb_prof_begin("k_cbg_decode_blz", s);
-        hipLaunchKernelGGL(k_cbg_decode_blz, dim3(gsplit), dim3(64), 0, s, d_frames, d_blocks, d_plans, d_str0, nblk, (const CbStream *)d_streams, nstreams, w, P);
-        hb_prof_end(s);
-    }
+    cb_launch_streams(CbgSpace{d_frames, d_blocks, d_plans, d_str0, nblk, w}, d_streams, nstreams, any_small, any_lz4, any_blz, nsplit_all,
+                      "k_cbg_decode_small", "k_cbg_decode", "k_cbg_decode_blz", s);
 }
 
 // ---- many ranges of many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_getitem_batch.h) ----
@@ -1451,14 +1284,9 @@ int hb_cblosc_getitem_frames_batch_device(int nframes, const hb_cblosc_header *h
         const uint32_t k0 = B.kind0[k], nk = B.kind0[k + 1] - k0, blocks = B.kblocks[k];
         if (!nk) continue;
         hb_prof_begin(gname[k], s);
-#define CBG_LAUNCH(K) hipLaunchKernelGGL(k_cbg_gather<K>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_blocks, (const CbPlan *)d_plans, d_gjob + k0, d_gblk + k0, nk, (const uint8_t *)w)
-        switch (k) {
-        case CBG_COPY: CBG_LAUNCH(CBG_COPY); break;
-        case CBG_UNSHUFFLE: CBG_LAUNCH(CBG_UNSHUFFLE); break;
-        case CBG_BITUN: CBG_LAUNCH(CBG_BITUN); break;
-        default: CBG_LAUNCH(CBG_BITUN4); break;
-        }
-#undef CBG_LAUNCH
+        cb_with_kind(k, [&](auto K) {                                    // (any other kind: CBG_BITUN4, the last)
+            hipLaunchKernelGGL(k_cbg_gather<K.value>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_blocks, (const CbPlan *)d_plans, d_gjob + k0, d_gblk + k0, nk, (const uint8_t *)w);
+        });
         hb_prof_end(s);
     }
     hb_prof_begin("k_cbg_finish", s);
@@ -1508,14 +1336,10 @@ static int cbx_launch(const CbxBatch &B, int nframes, int njobs, void *d_work, h
         const uint32_t k0 = B.kind0[k], nk = B.kind0[k + 1] - k0, blocks = B.kblocks[k];
         if (!nk) continue;
         hb_prof_begin(gname[k], s);
-#define CBX_LAUNCH(K) hipLaunchKernelGGL(k_cbx_gather<K>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_blocks, (const CbPlan *)d_plans, d_touch, d_gjob + k0, d_gblk + k0, nk, (const uint8_t *)w)
-        switch (k) {
-        case CBG_COPY: CBX_LAUNCH(CBG_COPY); break;
-        case CBG_UNSHUFFLE: CBX_LAUNCH(CBG_UNSHUFFLE); break;
-        case CBG_BITUN: CBX_LAUNCH(CBG_BITUN); break;
-        default: CBX_LAUNCH(CBG_BITUN4); break;
-        }
-#undef CBX_LAUNCH
+        cb_with_kind(k, [&](auto K) {                                    // (any other kind: CBG_BITUN4, the last)
+            hipLaunchKernelGGL(k_cbx_gather<K.value>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_blocks, (const CbPlan *)d_plans, d_touch, d_gjob + k0, d_gblk + k0, nk,
+                               (const uint8_t *)w);
+        });
         hb_prof_end(s);
     }
     const CbsRow *d_srow = (const CbsRow *)(w + L.srow);
@@ -1525,14 +1349,10 @@ static int cbx_launch(const CbxBatch &B, int nframes, int njobs, void *d_work, h
         const uint32_t k0 = B.skind0[k], nk = B.skind0[k + 1] - k0, blocks = B.skblocks[k];
         if (!nk) continue;
         hb_prof_begin(sname[k], s);
-#define CBS_LAUNCH(K) hipLaunchKernelGGL(k_cbs_gather<K>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_srow + k0, d_blocks, (const CbPlan *)d_plans, d_touch, d_sgjob + k0, d_sgblk + k0, nk, (const uint8_t *)w)
-        switch (k) {
-        case CBG_COPY: CBS_LAUNCH(CBG_COPY); break;
-        case CBG_UNSHUFFLE: CBS_LAUNCH(CBG_UNSHUFFLE); break;
-        case CBG_BITUN: CBS_LAUNCH(CBG_BITUN); break;
-        default: CBS_LAUNCH(CBG_BITUN4); break;
-        }
-#undef CBS_LAUNCH
+        cb_with_kind(k, [&](auto K) {                                    // (any other kind: CBG_BITUN4, the last)
+            hipLaunchKernelGGL(k_cbs_gather<K.value>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_srow + k0, d_blocks, (const CbPlan *)d_plans, d_touch, d_sgjob + k0,
+                               d_sgblk + k0, nk, (const uint8_t *)w);
+        });
         hb_prof_end(s);
     }
     hb_prof_begin("k_cbx_finish", s);

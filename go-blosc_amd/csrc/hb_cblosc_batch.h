@@ -29,6 +29,34 @@ CB_HD static inline uint32_t cb_nsplit(uint32_t flags, uint32_t typesize, uint32
 struct CbStream { uint32_t src, csize, dst, usize; };
 struct CbPlan { uint32_t fail, nblocks, nsplit, pad; };
 
+// ---- the launch schedule of the stream decoders (hb_cblosc.hip k_cb_streams: one wavefront per stream, one frame's or a whole batch's) ----
+// Stream i of the permuted order: stream i is byte plane i % typesize of its block, workgroup it runs on XCD it % 8, and the planes differ
+// several times in cost -- in stream order two XCDs would get all the streams of the token-dense plane (measured: 3.1 ms against 1.5).
+// Workgroup it of a launch of `grid` (step k = it / 8, XCD x = it % 8, pass it / grid) takes stream 8 * (k * P mod mgrp) + (x + k + pass) % 8:
+// with P coprime to the mgrp groups of 8 streams and grid a multiple of 8, every index of [0, 8 * mgrp) exactly once.
+CB_HD static inline uint32_t cb_stream_of(uint32_t it, uint32_t mgrp, uint32_t P, uint32_t grid) {
+    return (uint32_t)(((uint64_t)(it >> 3) * P) % mgrp) * 8u + ((it + (it >> 3) + it / grid) & 7u);
+}
+// P and the grids of the three decoder launches.  The small decoder gets one stream per workgroup up to 65536 streams, so that a finished cheap
+// stream makes room for the next one.  Long streams: as many passes per workgroup as a block has streams (nsplit_all: the nsplit every owner
+// shares, else 1), fewer while that leaves under 2048 workgroups -- with the rotation by the pass number a workgroup decodes one stream of
+// each plane, and all workgroups live about equally long.  Where the small decoder runs too, the LZ4 launch keeps its shape.
+struct CbSchedule { uint32_t P, grid_small, grid_lz4, grid_blz; };
+static inline CbSchedule cb_decode_schedule(uint32_t nstreams, uint32_t nsplit_all, uint32_t any_small) {
+    const uint32_t mgrp = (nstreams + 7u) / 8u;
+    uint32_t P = mgrp / 4u + 1u;                                            // coprime to the groups of 8 streams, about a quarter turn
+    for (;; P++) { uint32_t x = P, y = mgrp; while (y) { const uint32_t t = x % y; x = y; y = t; } if (x == 1u) break; }
+    const uint32_t grid = mgrp * 8u < 65536u ? mgrp * 8u : 65536u;
+    uint32_t gsplit = grid;
+    if (nsplit_all > 1u) {
+        uint32_t p = nsplit_all;
+        while (p > 1u && mgrp * 8u / p < 2048u) p >>= 1;
+        gsplit = (mgrp * 8u / p + 7u) / 8u * 8u;
+        if (gsplit > 65536u) gsplit = 65536u;
+    }
+    return CbSchedule{P, grid, any_small ? grid : gsplit, gsplit};
+}
+
 // ---- which codec formats the hb_cblosc_* entry points decode (include/hipblosc.h hb_cblosc_accept_codecs): bit k = codec format k.  The
 // word itself lives in hb_cblosc.hip; an entry point reads it ONCE (hb_cblosc_accepted) and hands the value to everything it asks below, so
 // that one call judges all its frames alike.  Every codec check of the C-Blosc-1 side is cb_codec_refused(). ----
@@ -81,7 +109,7 @@ struct CbbFrame {
     uint32_t nbytes, blocksize, cbytes, typesize, flags, nsplit;
     uint32_t b0, nblocks;                // the blocks of this record: all of the frame's (b0 = 0) -- a record for "blocks [b0, b0 + nb)" fits as it is
     uint32_t stream0;                    // its first stream record (= str0[k])
-    uint32_t small;                      // an LZ4 frame whose every stream is at most one chunk: k_cbb_decode_small takes those that are not stored
+    uint32_t small;                      // an LZ4 frame whose every stream is at most one chunk: the small decoder (stage k_cbb_decode_small) takes those that are not stored
     int32_t mode, kind, status;          // CBB_*; CBK_* or -1; mode CBB_REFUSED: `status` is what the host decided
     uint32_t ngrid, nfast;               // workgroups in the launch of its kind; CBK_BITUN4: the first nfast run the fast path, the rest the last, shorter block
     uint32_t pad;

@@ -54,7 +54,7 @@ enum { CBG_COPY = 0, CBG_UNSHUFFLE, CBG_BITUN, CBG_BITUN4, CBG_COUNT };
 struct CbgFrame {
     const uint8_t *frame;                // d_frame[f]; NULL: no accepted job reads it
     uint32_t nbytes, blocksize, cbytes, typesize, flags, nsplit;
-    uint32_t small;                      // an LZ4 frame whose every stream is at most one chunk: k_cbg_decode_small takes those that are not stored
+    uint32_t small;                      // an LZ4 frame whose every stream is at most one chunk: the small decoder (stage k_cbg_decode_small) takes those that are not stored
     uint32_t memcpyed;
 };
 struct CbgBlock {

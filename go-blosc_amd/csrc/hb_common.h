@@ -150,7 +150,8 @@ __device__ __forceinline__ void bitshuffle4_window(const u32x4 a, const u32x4 b,
 
 // the owner of x in a prefix array (pre[0] == 0, non-decreasing): the LAST i < n with pre[i] <= x.  Where neighbours are equal (owners without
 // work) that is the one behind them, whose count is not 0.  Wave-uniform where x is (a block index, a stream of a one-wave workgroup).
-__device__ __forceinline__ uint32_t hb_owner(const uint32_t *__restrict__ pre, uint32_t n, uint32_t x) {
+template <class PRE>                                                     // (a pointer to uint32_t in any address space)
+__device__ __forceinline__ uint32_t hb_owner(PRE pre, uint32_t n, uint32_t x) {
     uint32_t lo = 0, hi = n;                                              // pre[lo] <= x; hi == n or pre[hi] > x
     while (hi - lo > 1u) {
         const uint32_t mid = lo + (hi - lo) / 2u;

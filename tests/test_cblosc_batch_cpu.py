@@ -1,7 +1,8 @@
 """CPU tests of the batched C-Blosc-1 decode (include/hipblosc.h hb_cblosc_decompress_frames_batch*): everything the host decides -- the
 refusals of the call as a whole, the workspace size, the frames the header refuses -- needs no device.  The frames are built by hand: a
 header, the bstarts table, then { int32 size, bytes } per stored stream.  The host code of the entry points (csrc/hb_cblosc_batch.h) also
-runs under ASan + UBSan in a stand-alone driver (tests/tools/cblosc_batch_asan_check.cpp)."""
+runs under ASan + UBSan in a stand-alone driver (tests/tools/cblosc_batch_asan_check.cpp), and so does the launch schedule of the stream
+decoders (cb_decode_schedule, cb_stream_of: tests/tools/cblosc_schedule_check.cpp)."""
 import ctypes
 import os
 import struct
@@ -183,3 +184,88 @@ def test_host_code_under_sanitizers(tmp_path):
     out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     assert out.returncode == 0, out.stdout + out.stderr
     assert "ok under ASan" in out.stdout
+
+
+def _step(mgrp):
+    """The decoders' step through the groups of 8 streams: the first number from mgrp / 4 + 1 on that is coprime to mgrp."""
+    import math
+    P = mgrp // 4 + 1
+    while math.gcd(P, mgrp) != 1:
+        P += 1
+    return P
+
+
+def _passes_grid(mgrp, nsplit, cap):
+    p = nsplit
+    while p > 1 and mgrp * 8 // p < 2048:
+        p >>= 1
+    g = (mgrp * 8 // p + 7) // 8 * 8
+    return min(g, 65536) if cap else g
+
+
+def _one_frame_formula(nstreams, nsplit, small):
+    """What the one-frame launcher computed before cb_decode_schedule: (P, small, LZ4, BloscLZ); the passes' grid without the 65536 cap."""
+    mgrp = (nstreams + 7) // 8
+    grid = min(mgrp * 8, 65536)
+    gblz = _passes_grid(mgrp, nsplit, False) if nsplit > 1 else grid
+    gbig = _passes_grid(mgrp, nsplit, False) if not small and nsplit > 1 else grid
+    return _step(mgrp), grid, gbig, gblz
+
+
+def _frames_batch_formula(nstreams, nsplit_all, any_small):
+    """What the whole-frame batch computed: the general decoder's grid and the BloscLZ decoder's, each written out with the cap."""
+    mgrp = (nstreams + 7) // 8
+    grid = min(mgrp * 8, 65536)
+    gbig = _passes_grid(mgrp, nsplit_all, True) if not any_small and nsplit_all > 1 else grid
+    gblz = _passes_grid(mgrp, nsplit_all, True) if nsplit_all > 1 else grid
+    return _step(mgrp), grid, gbig, gblz
+
+
+def _records_batch_formula(nstreams, nsplit_all, any_small):
+    """What the block-record batches computed: one split grid, used by the LZ4 decoder when the small one does not run, and by BloscLZ."""
+    mgrp = (nstreams + 7) // 8
+    grid = min(mgrp * 8, 65536)
+    gsplit = _passes_grid(mgrp, nsplit_all, True) if nsplit_all > 1 else grid
+    return _step(mgrp), grid, (grid if any_small else gsplit), gsplit
+
+
+def test_decode_schedule_and_stream_order_under_sanitizers(tmp_path):
+    """csrc/hb_cblosc_batch.h cb_decode_schedule and cb_stream_of in a stand-alone program under ASan + UBSan (CPU build only).  The order
+    visits every index of [0, 8 * mgrp) exactly once at the full grid, at grid 8 and at the passes' grid; the schedule equals the three
+    formulas it replaced, and above 65536 blocks differs from the one-frame formula by the cap alone."""
+    exe = str(tmp_path / "cblosc_schedule_check")
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-I" + os.path.join(ROOT, "include"), "-o", exe, os.path.join(ROOT, "tests", "tools", "cblosc_schedule_check.cpp")])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert "90 orders ok under ASan + UBSan" in out.stdout           # 10 stream counts x 3 nsplit x 3 grids
+
+    edges = {1, 2, 3, 7, 8, 9, 63, 64, 65, 127, 128, 129, 255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 2047, 2048, 2049, 4095, 4096, 4097, 8191, 8192, 8193,
+             16383, 16384, 16385, 32767, 32768, 32769, 65535, 65536}
+    below = sorted(set(range(1, 2200)) | set(range(2200, 65536, 61)) | edges)
+    above = [65537, 65544, 70000, 100000, 131071, 131072, 131073, 200001, 262143, 262144]
+    cases = []
+    for nsplit in (1, 2, 4, 8, 16):
+        for nblocks in below + above:
+            for nstreams in (nblocks * nsplit, (nblocks - 1) * nsplit + 1):       # every block split; a last, shorter block with its one stream
+                for any_small in (0, 1):
+                    cases.append((nblocks, nstreams, nsplit, any_small))
+    path = tmp_path / "cases.txt"
+    path.write_text("".join(f"{c[1]} {c[2]} {c[3]}\n" for c in cases))
+    out = subprocess.run([exe, str(path)], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    rows = [tuple(int(v) for v in line.split()) for line in out.stdout.splitlines()]
+    assert len(rows) == len(cases)
+    capped = 0
+    for (nblocks, nstreams, nsplit, any_small), row in zip(cases, rows):
+        assert row[:3] == (nstreams, nsplit, any_small)
+        got = row[3:]
+        assert all(g % 8 == 0 and 8 <= g <= 65536 for g in got[1:]), (nblocks, row)
+        assert got == _frames_batch_formula(nstreams, nsplit, any_small) == _records_batch_formula(nstreams, nsplit, any_small), (nblocks, row)
+        one = _one_frame_formula(nstreams, nsplit, any_small)
+        if nblocks <= 65536:
+            assert got == one, (nblocks, row, one)
+        else:
+            assert got == (one[0], one[1], min(one[2], 65536), min(one[3], 65536)), (nblocks, row, one)
+            capped += got != one
+    assert capped > 0                                                 # (the cap is the one launch shape that changed: the cases reach it)

@@ -207,7 +207,8 @@ def test_a_large_frame(hb, O, cb):
 
 
 def test_more_streams_than_workgroups_and_a_ragged_tail(hb, O):
-    # the stream order of the decoders (hb_cblosc.hip k_cb_decode_small / k_cb_decode: 8 * (k P mod m) + (x + k + pass) mod 8) has to
+    # the stream order of the decoders (hb_cblosc.hip k_cb_streams, profile stages k_cb_decode_small / k_cb_decode; cb_stream_of,
+    # hb_cblosc_batch.h: 8 * (k P mod m) + (x + k + pass) mod 8) has to
     # visit every stream exactly once also when there are several passes per workgroup and the stream count is no multiple of 8:
     # 300 MiB + 4 KiB + 13 bytes of float32 written here = 19201 blocks = 76804 streams (one of them the short, unsplit last block)
     n = (300 << 20) + 4096 + 13

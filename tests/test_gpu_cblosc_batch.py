@@ -325,6 +325,42 @@ def test_one_launch_set_for_any_number_of_frames(hb, inputs):
     assert lists[0] == ["cbb_upload", "k_cbb_plan", "k_cbb_decode_small", "k_cbb_decode", "k_cbb_unfilter", "k_cbb_finish"]
 
 
+def _lz4_grid(nstreams, nsplit_all, any_small):
+    """cb_decode_schedule's rule (csrc/hb_cblosc_batch.h) for the LZ4 decoder's launch -> (its grid, 8 * mgrp)"""
+    mgrp = (nstreams + 7) // 8
+    grid = min(8 * mgrp, 65536)
+    if any_small or nsplit_all <= 1:
+        return grid, 8 * mgrp
+    p = nsplit_all
+    while p > 1 and 8 * mgrp // p < 2048:
+        p >>= 1
+    return min((8 * mgrp // p + 7) // 8 * 8, 65536), 8 * mgrp
+
+
+def test_several_passes_per_workgroup(hb):
+    """Four frames of stored streams, typesize 4, split, no filter, block size 16640: 257 blocks each, one frame with a 13-byte last block.  The
+    streams are 4160 bytes -- over one chunk, so no frame is "small" -- and there are enough of them that every workgroup of the stream
+    decoder (k_cb_streams) makes two passes of the shared loop, in the whole-frame batch (4112 stream records) and in the block-record batch
+    (4109: the short block has one, so the count is no multiple of 8).  Both must return the bytes exactly."""
+    bs, ts = 16640, 4
+    rng = np.random.default_rng(2056)
+    datas = [rng.integers(0, 256, n, dtype=np.uint8).tobytes() for n in (257 * bs, 257 * bs, 256 * bs + 13, 257 * bs)]
+    frames = [stored_frame(x, typesize=ts, blocksize=bs, flags=0x20) for x in datas]
+    assert all(_nstreams(hb, f) == 257 * ts for f in frames) and bs // ts > 4096
+    for nstreams in (4 * 257 * ts, 4 * 257 * ts - (ts - 1)):
+        grid, space = _lz4_grid(nstreams, ts, 0)
+        assert grid < space and (space + grid - 1) // grid == 2, (nstreams, grid, space)      # (else this test has stopped covering the case)
+    assert (4 * 257 * ts - (ts - 1)) % 8 != 0
+    res = hb.CBloscDecompressBatch(frames)
+    assert [type(r) for r in res] == [bytes] * 4
+    assert all(r == x for r, x in zip(res, datas))
+    jobs = [(k, 0, len(x) // ts) for k, x in enumerate(datas)] + [(2, 255 * (bs // ts) - 1, bs // ts + 4)]      # every block of every frame; the short one's tail again
+    res = hb.CBloscGetItemBatch(frames, jobs)
+    assert [type(r) for r in res] == [bytes] * len(jobs)
+    for (k, start, nitems), r in zip(jobs, res):
+        assert r == datas[k][start * ts:(start + nitems) * ts], (k, start, nitems)
+
+
 def test_host_form(hb, inputs, own):
     L = hb.lib()
     good = [own[k] for k in (0, 4, 7, 10, 13, 22, 24)]

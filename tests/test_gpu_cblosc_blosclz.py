@@ -1,5 +1,5 @@
-"""GPU tests of BloscLZ streams in C-Blosc-1 frames (include/hipblosc.h hb_cblosc_accept_codecs; kernels k_cb_decode_blz, k_cbb_decode_blz,
-k_cbg_decode_blz behind bz_walk, csrc/hb_lz4_region.h), through all four entry points: CBloscDecompress, CBloscDecompressBatch, CBloscGetItem,
+"""GPU tests of BloscLZ streams in C-Blosc-1 frames (include/hipblosc.h hb_cblosc_accept_codecs; the BloscLZ instantiations
+of the kernel template k_cb_streams -- profile stages k_cb_decode_blz, k_cbb_decode_blz, k_cbg_decode_blz -- behind bz_walk, csrc/hb_lz4_region.h), through all four entry points: CBloscDecompress, CBloscDecompressBatch, CBloscGetItem,
 CBloscGetItemBatch.
 
 Writers: c-blosc 1.21 itself with cname "blosclz" (ctypes, as tests/test_gpu_cblosc.py does; those parts skip where the library is missing)
