@@ -23,6 +23,7 @@
 #include "hb_cblosc_getitem_batch.h"
 #include "hb_cblosc_box_batch.h"
 #include "hb_cblosc_slice_batch.h"
+#include "hb_cblosc_index_batch.h"
 #include "hb_cblosc_enc_box_batch.h"
 #include "hb_cblosc_upd_box_batch.h"
 #include <vector>
@@ -769,6 +770,20 @@ int hb_cblosc_getslice_frames_batch(int nframes, const void *const *frame, const
                                     int64_t *rc, int device) {
     try { return cbx_host_call(nframes, frame, n, njobs, jobs, dst, cap, rc, device, cbs_host_plan, hb_cblosc_getslice_frames_batch_workspace, hb_cblosc_getslice_frames_batch_device); }
     catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
+}
+int hb_cblosc_getindex_frames_batch(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_cblosc_index_job *jobs, const int64_t *index, int64_t nindex,
+                                    void *const *dst, const size_t *cap, int64_t *rc, int device) {
+    try {
+        if (nframes >= 0 && cbi_call_refused(njobs, jobs, index, nindex)) return HB_ERR_BAD_ARG;
+        return cbx_host_call(
+            nframes, frame, n, njobs, jobs, dst, cap, rc, device,
+            [&](int nf, const void *const *f, const size_t *nn, int nj, const hb_cblosc_index_job *q, void *const *d, const size_t *c, CbiHostPlan &P, unsigned accept) {
+                cbi_host_plan(nf, f, nn, nj, q, index, nindex, d, c, P, accept);
+            },
+            [&](int nf, const hb_cblosc_header *h, const size_t *nn, int nj, const hb_cblosc_index_job *q) { return hb_cblosc_getindex_frames_batch_workspace(nf, h, nn, nj, q, index, nindex); },
+            [&](int nf, const hb_cblosc_header *h, const void *const *f, const size_t *nn, int nj, const hb_cblosc_index_job *q, void *const *d, const size_t *c, void *wk, size_t wb,
+                hb_result *res, void *st) { return hb_cblosc_getindex_frames_batch_device(nf, h, f, nn, nj, q, index, nindex, d, c, wk, wb, res, st); });
+    } catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
 }
 
 // The records and the frames of a batched C-Blosc-1 encode come down (both host forms end here): the records in one copy; many small frames are

@@ -32,6 +32,7 @@
 #include "hb_cblosc_getitem_batch.h"   // the geometry of an item range, and the host side of the batched getitem
 #include "hb_cblosc_box_batch.h"       // the geometry of a box, the host side of the batched box reads, the gather's index arithmetic
 #include "hb_cblosc_slice_batch.h"     // the geometry of a stepped selection, the host side of the batched slice reads, the stepped gather's index arithmetic
+#include "hb_cblosc_index_batch.h"     // the geometry of an orthogonal selection, the host side of the batched index-list reads, the index arithmetic of its two gathers
 #include "hb_cblosc_enc_box_batch.h"   // the geometry of a source box, the host side of the batched box writes, the gather's index arithmetic
 #include "hb_cblosc_upd_box_batch.h"   // the geometry of an update box, the host side of the batched box updates, the overlay's index arithmetic
 
@@ -697,6 +698,103 @@ __global__ __launch_bounds__(256) void k_cbs_gather(const CbgFrame *__restrict__
     const CbxLookup look{blocks, tl, J.ntl, J.b_lo, J.dense};
     cbs_unit<KIND>(F, look, work, roff + it0 * R.istr, R.istr, cnt, J.dst + doff);
 }
+// ---- batched index-list reads (hb_cblosc_getindex_frames_batch_device; hb_cblosc_index_batch.h): the jobs in which a dimension takes its
+// indices from a list.  Everything but the two gathers is the box batch's.  `tab` is the batch's table section: byte offsets, index * (chunk
+// stride), in the caller's order. ----
+// The rows gather: the row is a plain run, an outer dimension has a list.  A thread has one frame-aligned unit of a row (cbi_thread_rows) and
+// the wide bodies of cbg_unit; only the row's offset comes from tables.  The fail check comes before any store, as above.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_cbi_gather_rows(const CbgFrame *__restrict__ frames, const CbxJob *__restrict__ jobs, const CbiRow *__restrict__ rows,
+                                                          const CbgBlock *__restrict__ blocks, const CbPlan *__restrict__ plans, const CbxTouch *__restrict__ touch,
+                                                          const uint32_t *__restrict__ tab, const uint32_t *__restrict__ gjob, const uint32_t *__restrict__ gblk,
+                                                          uint32_t nkind, const uint8_t *__restrict__ work) {
+    const uint32_t i = hb_owner(gblk, nkind, blockIdx.x);
+    const CbxJob &J = jobs[gjob[i]];
+    const CbiRow R = rows[i];
+    const CbgFrame &F = frames[J.frame];
+    const CbxTouch *tl = touch + J.tl0;
+    int bad = 0;
+    for (uint32_t k = threadIdx.x; k < J.ntl; k += 256u) bad |= plans[tl[k].rec].fail != 0u;
+    if (__syncthreads_or(bad)) return;
+    uint32_t lo, hi;
+    uint64_t doff;
+    if (!cbi_thread_rows(J, R, tab, cbg_unit_bytes(KIND, F.typesize), blockIdx.x - gblk[i], threadIdx.x, lo, hi, doff)) return;
+    const CbxLookup look{blocks, tl, J.ntl, J.b_lo, J.dense};
+    cbg_unit<KIND>(F, look, work, lo, hi, J.dst + doff);
+}
+// 16 bytes = 16 / TS items of a row from item `it` on, the row at byte roff of the frame's decoded bytes: item i lies cbi_item(rt, istr, i) bytes
+// into it.  As cbs_items16: an item that lies whole inside the whole elements of its block is read where it is staged, any other goes byte by
+// byte through cbg_byte, and a block's record is looked up once while neighbours share it.
+template <int KIND, uint32_t TS, class LOOK>
+__device__ __forceinline__ u32x4 cbi_items16(const CbgFrame &F, const LOOK &look, const uint8_t *__restrict__ work, uint32_t roff, const uint32_t *__restrict__ rt,
+                                             uint32_t istr, uint32_t it) {
+    uint32_t w[4] = {0u, 0u, 0u, 0u};
+    const uint32_t bs = F.blocksize;
+    const bool direct = KIND == CBG_COPY && F.memcpyed;
+    uint32_t cur = ~0u, bsize = 0u, nel = 0u;
+    const uint8_t *s = nullptr;
+#pragma unroll
+    for (uint32_t c = 0; c < 16u / TS; c++) {
+        const uint32_t pc = roff + cbi_item(rt, istr, it + c);
+        uint32_t q = 0u, e = 0u;
+        bool whole = direct;
+        if (!direct) {
+            const uint32_t b = pc / bs;
+            q = pc - b * bs;
+            if (b != cur) { const CbgBlock &K = look(b); s = work + K.stage_off; bsize = K.bsize; nel = bsize / TS; cur = b; }
+            if (KIND == CBG_COPY) whole = q + TS <= bsize;
+            else { e = q / TS; whole = e * TS == q && e < nel; }
+        }
+#pragma unroll
+        for (uint32_t j = 0; j < TS; j++) {
+            const uint32_t i = c * TS + j;
+            const uint8_t v = direct ? F.frame[16u + (size_t)pc + j] : !whole ? cbg_byte<KIND>(F, look, work, pc + j) : KIND == CBG_COPY ? s[q + j] : s[(size_t)j * nel + e];
+            w[i >> 2] |= (uint32_t)v << (8u * (i & 3u));
+        }
+    }
+    u32x4 v; v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
+    return v;
+}
+// One unit of such a row: items [it, it + cnt) to d, packed.  16 bytes of whole items of a copied or byte-shuffled frame are assembled in
+// registers and stored at once (d has any alignment); the plain body has the row tails, the other typesizes and both bit-shuffle kinds.
+template <int KIND, class LOOK>
+__device__ __forceinline__ void cbi_unit(const CbgFrame &F, const LOOK &look, const uint8_t *__restrict__ work, uint32_t roff, const uint32_t *__restrict__ rt, uint32_t istr,
+                                         uint32_t it, uint32_t cnt, uint8_t *__restrict__ d) {
+    const uint32_t ts = F.typesize;
+    if ((KIND == CBG_COPY || KIND == CBG_UNSHUFFLE) && cnt * ts == 16u) {
+        if (ts == 1u && KIND == CBG_COPY) { st16u(d, cbi_items16<KIND, 1>(F, look, work, roff, rt, istr, it)); return; }      // (one byte is never shuffled)
+        if (ts == 2u) { st16u(d, cbi_items16<KIND, 2>(F, look, work, roff, rt, istr, it)); return; }
+        if (ts == 4u) { st16u(d, cbi_items16<KIND, 4>(F, look, work, roff, rt, istr, it)); return; }
+        if (ts == 8u) { st16u(d, cbi_items16<KIND, 8>(F, look, work, roff, rt, istr, it)); return; }
+        if (ts == 16u) { st16u(d, cbi_items16<KIND, 16>(F, look, work, roff, rt, istr, it)); return; }
+    }
+    for (uint32_t c = 0; c < cnt; c++) {
+        const uint32_t pc = roff + cbi_item(rt, istr, it + c);
+        for (uint32_t j = 0; j < ts; j++) d[c * ts + j] = cbg_byte<KIND>(F, look, work, pc + j);
+    }
+}
+// The items gather: the row has a list, or it is stepped while an outer dimension has one.  A thread has 16 bytes of the row's destination
+// (cbi_thread_items) and reads each item's offset from the row's table, or by the row's step.
+template <int KIND>
+__global__ __launch_bounds__(256) void k_cbi_gather_items(const CbgFrame *__restrict__ frames, const CbxJob *__restrict__ jobs, const CbiRow *__restrict__ rows,
+                                                           const CbgBlock *__restrict__ blocks, const CbPlan *__restrict__ plans, const CbxTouch *__restrict__ touch,
+                                                           const uint32_t *__restrict__ tab, const uint32_t *__restrict__ gjob, const uint32_t *__restrict__ gblk,
+                                                           uint32_t nkind, const uint8_t *__restrict__ work) {
+    const uint32_t i = hb_owner(gblk, nkind, blockIdx.x);
+    const CbxJob &J = jobs[gjob[i]];
+    const CbiRow R = rows[i];
+    const CbgFrame &F = frames[J.frame];
+    const CbxTouch *tl = touch + J.tl0;
+    int bad = 0;
+    for (uint32_t k = threadIdx.x; k < J.ntl; k += 256u) bad |= plans[tl[k].rec].fail != 0u;
+    if (__syncthreads_or(bad)) return;
+    uint32_t it0, cnt, roff;
+    uint64_t doff;
+    if (!cbi_thread_items(J, R, tab, F.typesize, blockIdx.x - gblk[i], threadIdx.x, it0, cnt, roff, doff)) return;
+    const CbxLookup look{blocks, tl, J.ntl, J.b_lo, J.dense};
+    const uint32_t *__restrict__ rt = R.tab[3] != CBI_NONE ? tab + R.tab[3] : nullptr;
+    cbi_unit<KIND>(F, look, work, roff, rt, R.istr, it0, cnt, J.dst + doff);
+}
 // one thread per job: what the host decided, or k_cb_result's record from the OR of the fail words of the blocks the job touches
 __global__ __launch_bounds__(64) void k_cbx_finish(const CbxJob *__restrict__ jobs, const CbPlan *__restrict__ plans, const CbxTouch *__restrict__ touch, hb_result *results,
                                                     uint32_t njobs) {
@@ -1296,8 +1394,9 @@ int hb_cblosc_getitem_frames_batch_device(int nframes, const hb_cblosc_header *h
     return HB_OK;
 }
 
-// A prepared batch of boxes or of stepped selections (CbxBatch) on the device: one upload, the plan and the decoders over the distinct blocks,
-// the gathers -- k_cbx_gather per kind among the jobs with plain rows, k_cbs_gather per kind among those with stepped rows -- and the records.
+// A prepared batch of boxes, of stepped selections or of index-list selections (CbxBatch) on the device: one upload, the plan and the decoders
+// over the distinct blocks, the gathers -- k_cbx_gather per kind among the jobs with plain rows, k_cbs_gather per kind among those with stepped
+// rows, then k_cbi_gather_rows and k_cbi_gather_items per kind among those with an index list -- and the records.
 static int cbx_launch(const CbxBatch &B, int nframes, int njobs, void *d_work, hb_result *d_results, void *stream) {
     const CbxLayout &L = B.L;
     hipStream_t s = (hipStream_t)stream;
@@ -1318,6 +1417,12 @@ static int cbx_launch(const CbxBatch &B, int nframes, int njobs, void *d_work, h
         memcpy(up.data() + L.srow, B.srow.data(), ns * sizeof(CbsRow));
         memcpy(up.data() + L.sgjob, B.sgjob.data(), ns * 4);
         memcpy(up.data() + L.sgblk, B.sgblk.data(), ns * 4);
+    }
+    if (const size_t ni = B.irow.size()) {
+        memcpy(up.data() + L.irow, B.irow.data(), ni * sizeof(CbiRow));
+        memcpy(up.data() + L.igjob, B.igjob.data(), ni * 4);
+        memcpy(up.data() + L.igblk, B.igblk.data(), ni * 4);
+        memcpy(up.data() + L.itab, B.itab.data(), B.itab.size() * 4);
     }
     hb_prof_begin("cbx_upload", s);
     HB_HIP_TRY(hipMemcpyAsync(w, up.data(), L.upload, hipMemcpyHostToDevice, s));
@@ -1352,6 +1457,24 @@ static int cbx_launch(const CbxBatch &B, int nframes, int njobs, void *d_work, h
         cb_with_kind(k, [&](auto K) {                                    // (any other kind: CBG_BITUN4, the last)
             hipLaunchKernelGGL(k_cbs_gather<K.value>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_srow + k0, d_blocks, (const CbPlan *)d_plans, d_touch, d_sgjob + k0,
                                d_sgblk + k0, nk, (const uint8_t *)w);
+        });
+        hb_prof_end(s);
+    }
+    const CbiRow *d_irow = (const CbiRow *)(w + L.irow);
+    const uint32_t *d_igjob = (const uint32_t *)(w + L.igjob), *d_igblk = (const uint32_t *)(w + L.igblk), *d_itab = (const uint32_t *)(w + L.itab);
+    static const char *const iname[2 * CBG_COUNT] = {"k_cbi_gather_rows_copy",  "k_cbi_gather_rows_unshuffle",  "k_cbi_gather_rows_bitun",  "k_cbi_gather_rows_bitun4",
+                                                     "k_cbi_gather_items_copy", "k_cbi_gather_items_unshuffle", "k_cbi_gather_items_bitun", "k_cbi_gather_items_bitun4"};
+    for (int l = 0; l < 2 * CBG_COUNT; l++) {
+        const uint32_t k0 = B.ikind0[l], nk = B.ikind0[l + 1] - k0, blocks = B.ikblocks[l];
+        if (!nk) continue;
+        hb_prof_begin(iname[l], s);
+        cb_with_kind(l % CBG_COUNT, [&](auto K) {                        // (any other kind: CBG_BITUN4, the last)
+            if (l < CBG_COUNT)
+                hipLaunchKernelGGL(k_cbi_gather_rows<K.value>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_irow + k0, d_blocks, (const CbPlan *)d_plans, d_touch, d_itab,
+                                   d_igjob + k0, d_igblk + k0, nk, (const uint8_t *)w);
+            else
+                hipLaunchKernelGGL(k_cbi_gather_items<K.value>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_irow + k0, d_blocks, (const CbPlan *)d_plans, d_touch, d_itab,
+                                   d_igjob + k0, d_igblk + k0, nk, (const uint8_t *)w);
         });
         hb_prof_end(s);
     }
@@ -1397,6 +1520,27 @@ int hb_cblosc_getslice_frames_batch_device(int nframes, const hb_cblosc_header *
     const int rc = cbs_prepare(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, true, B, accept);
     if (rc) return rc;
     if (work_bytes < (B.ptr_refusals ? cbs_workspace(nframes, hdrs, n, njobs, jobs, accept) : B.L.total)) return HB_ERR_SHORT_BUFFER;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    return cbx_launch(B, nframes, njobs, d_work, d_results, stream);
+}
+
+// ---- many orthogonal selections of many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_index_batch.h) ----
+size_t hb_cblosc_getindex_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n, int njobs, const hb_cblosc_index_job *jobs, const int64_t *index,
+                                                 int64_t nindex) {
+    return cbi_workspace(nframes, hdrs, n, njobs, jobs, index, nindex, hb_cblosc_accepted());
+}
+
+int hb_cblosc_getindex_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_cblosc_index_job *jobs,
+                                           const int64_t *index, int64_t nindex, void *const *d_dst, const size_t *cap, void *d_work, size_t work_bytes, hb_result *d_results,
+                                           void *stream) {
+    if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
+    if (njobs == 0) return HB_OK;
+    if (!hdrs || !d_frame || !n || !jobs || !d_dst || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
+    CbxBatch B;
+    const unsigned accept = hb_cblosc_accepted();
+    const int rc = cbi_prepare(nframes, hdrs, d_frame, n, njobs, jobs, index, nindex, d_dst, cap, true, B, accept);
+    if (rc) return rc;
+    if (work_bytes < (B.ptr_refusals ? cbi_workspace(nframes, hdrs, n, njobs, jobs, index, nindex, accept) : B.L.total)) return HB_ERR_SHORT_BUFFER;
     if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
     return cbx_launch(B, nframes, njobs, d_work, d_results, stream);
 }

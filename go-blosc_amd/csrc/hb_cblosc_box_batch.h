@@ -42,7 +42,13 @@ struct CbxJob {
 // CbxJob -- rowbytes and upr / rpw / wpr / rcp16 / rcp_wpr then speak of the row's DESTINATION bytes (cbs_thread), rcp_unit is unused -- and has
 // one of these beside it, in the order of its kind's launch list.  A box has none.
 struct CbsRow { uint32_t nit, istr; };
-static_assert(sizeof(CbxTouch) == 8 && sizeof(CbxJob) == 152 && sizeof(CbsRow) == 8, "the records are uploaded as they are");
+// A job with an index list (hb_cblosc_index_batch.h) keeps its CbxJob too and has one of these beside it, in the order of its gather's launch
+// list.  tab[k]: where the table of outer dimension k (0 .. 2) or of the row (3) starts in the batch's table section, in entries -- a table holds
+// the BYTE offsets index * (chunk stride) of the dimension's indices in the caller's order -- or CBI_NONE: the dimension goes by arithmetic
+// (cstr[k], or for the row nit items istr bytes apart, as in CbsRow).
+#define CBI_NONE 0xFFFFFFFFu
+struct CbiRow { uint32_t tab[4]; uint32_t nit, istr; };
+static_assert(sizeof(CbxTouch) == 8 && sizeof(CbxJob) == 152 && sizeof(CbsRow) == 8 && sizeof(CbiRow) == 24, "the records are uploaded as they are");
 static_assert(sizeof(CbxTouch) == HB_CBLOSC_BOX_BATCH_TOUCH_BYTES, "the per-pair constant of include/hipblosc.h");
 // per job: its record and two prefix words; per frame: its record; once: the padding of the sections (at most 6 x 16 + 2 x 255 bytes, and
 // every batch has a job and a frame).  Per distinct block the records are those of hb_cblosc_getitem_batch.h.
@@ -176,8 +182,9 @@ CB_HD static inline uint32_t cbx_find(const CbxTouch *tl, uint32_t ntl, uint32_t
 }
 
 // everything up to `upload` goes up in ONE copy
-struct CbxLayout { size_t frames, jobs, blocks, plans, str0, touch, gjob, gblk, srow, sgjob, sgblk, upload, streams, stage, total; };
-static inline CbxLayout cbx_layout(size_t nframes, size_t njobs, uint64_t nblk, uint64_t ntouch, uint64_t nstreams, uint64_t stage_bytes, size_t nstep = 0) {
+struct CbxLayout { size_t frames, jobs, blocks, plans, str0, touch, gjob, gblk, srow, sgjob, sgblk, irow, igjob, igblk, itab, upload, streams, stage, total; };
+static inline CbxLayout cbx_layout(size_t nframes, size_t njobs, uint64_t nblk, uint64_t ntouch, uint64_t nstreams, uint64_t stage_bytes, size_t nstep = 0,
+                                   size_t nidx = 0, uint64_t ntab = 0) {
     CbxLayout L{};
     size_t o = 0;
     auto take = [&](size_t b, size_t al) { size_t at = o; o += (b + al - 1) / al * al; return at; };
@@ -192,6 +199,10 @@ static inline CbxLayout cbx_layout(size_t nframes, size_t njobs, uint64_t nblk, 
     L.srow = take(nstep * sizeof(CbsRow), 16);                            // (the jobs with stepped rows: nothing for a batch of boxes)
     L.sgjob = take(nstep * 4, 16);
     L.sgblk = take(nstep * 4, 16);
+    L.irow = take(nidx * sizeof(CbiRow), 16);                             // (the jobs with index lists and their tables: nothing for boxes and slices)
+    L.igjob = take(nidx * 4, 16);
+    L.igblk = take(nidx * 4, 16);
+    L.itab = take((size_t)ntab * 4, 16);
     o = cb_align(o);
     L.upload = o;
     L.streams = take((size_t)nstreams * sizeof(CbStream), 256);
@@ -213,6 +224,12 @@ struct CbxBatch {
     std::vector<CbsRow> jrow, srow;      // stepped rows: per job (nit == 0: a job with plain rows), and in launch order beside sgjob / sgblk
     std::vector<uint32_t> sgjob, sgblk;
     uint32_t skind0[CBG_COUNT + 1], skblocks[CBG_COUNT];      // as kind0 / kblocks, over the jobs with stepped rows
+    // jobs with index lists (hb_cblosc_index_batch.h): per job its record and its gather (0: none, 1: rows, 2: items); in launch order beside
+    // igjob / igblk, the rows gather's kinds first (launch list CBG_COUNT * (gather - 1) + kind); and the tables
+    std::vector<CbiRow> jirow, irow;
+    std::vector<uint8_t> jigather;
+    std::vector<uint32_t> igjob, igblk, itab;
+    uint32_t ikind0[2 * CBG_COUNT + 1], ikblocks[2 * CBG_COUNT];
     uint64_t nblk, nstreams, stage, ntouch;
     uint32_t any_small, nsplit_all, any_lz4, any_blz;
     int ptr_refusals;                    // jobs refused for their capacity or a pointer: the workspace query counts their blocks, this batch does not
@@ -223,18 +240,32 @@ struct CbxBatch {
 // typesize divides 16, else one item
 CB_HD static inline uint32_t cbs_items_per_unit(uint32_t ts) { return 16u % ts ? 1u : 16u / ts; }
 
+// What cbx_prepare_ asks about index lists.  Boxes and slices have none: this is their answer, and every branch on it folds away.
+// hb_cblosc_index_batch.h has the one that speaks of the job `refuse` accepted last.
+struct CbxNoLists {
+    bool listed() const { return false; }
+    bool fits() const { return true; }
+    // the job's tables go behind `tab`, its record into R, what its rows need into J.upr; true: the items gather, false: the rows gather
+    bool shape(const CbxGeom &, uint32_t, uint32_t, CbxJob &, CbiRow &, std::vector<uint32_t> &) { return false; }
+    template <class EMIT> void cover(const CbxGeom &, uint32_t, EMIT) {}
+};
+
 // HB_OK, or what the call as a whole answers.  d_frame / d_dst / cap == NULL: the workspace query.  fill == false: counts and layout only.
-// JOB is hb_cblosc_box_job with cbx_refusal, or hb_cblosc_slice_job with cbs_refusal (hb_cblosc_slice_batch.h): `refuse` has cbx_refusal's
-// arguments and makes the CbxGeom, and everything from there on is the same.
-template <class JOB, class REFUSE>
+// JOB is hb_cblosc_box_job with cbx_refusal, or hb_cblosc_slice_job with cbs_refusal (hb_cblosc_slice_batch.h), or hb_cblosc_index_job with
+// cbi_refusal and its lists (hb_cblosc_index_batch.h): `refuse` has cbx_refusal's arguments and makes the CbxGeom, and everything from there on
+// is the same but for the jobs `lists` speaks for.
+template <class JOB, class REFUSE, class LISTS>
 static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const JOB *jobs,
-                               void *const *d_dst, const size_t *cap, bool fill, CbxBatch &B, unsigned accept, REFUSE refuse) {
+                               void *const *d_dst, const size_t *cap, bool fill, CbxBatch &B, unsigned accept, REFUSE refuse, LISTS &lists) {
     B.nblk = 0; B.nstreams = 0; B.stage = 0; B.ntouch = 0; B.any_small = 0; B.nsplit_all = 0; B.ptr_refusals = 0; B.any_lz4 = 0; B.any_blz = 0;
     for (int k = 0; k < CBG_COUNT; k++) B.kblocks[k] = 0;
     for (int k = 0; k <= CBG_COUNT; k++) B.kind0[k] = 0;
     for (int k = 0; k < CBG_COUNT; k++) B.skblocks[k] = 0;
     for (int k = 0; k <= CBG_COUNT; k++) B.skind0[k] = 0;
     B.jrow.clear(); B.srow.clear(); B.sgjob.clear(); B.sgblk.clear();
+    for (int k = 0; k < 2 * CBG_COUNT; k++) B.ikblocks[k] = 0;
+    for (int k = 0; k <= 2 * CBG_COUNT; k++) B.ikind0[k] = 0;
+    B.jirow.clear(); B.irow.clear(); B.jigather.clear(); B.igjob.clear(); B.igblk.clear(); B.itab.clear();
     B.frames.clear(); B.jobs.clear(); B.jruns.clear(); B.runs.clear(); B.blocks.clear(); B.touch.clear(); B.str0.clear(); B.gjob.clear(); B.gblk.clear();
     B.L = cbx_layout(0, 0, 0, 0, 0, 0);
     if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
@@ -248,9 +279,9 @@ static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
     B.frames.assign(nf, CbgFrame{});
     B.jobs.assign(nj, CbxJob{});
     B.jrow.assign(nj, CbsRow{0u, 0u});
-    uint64_t kb[CBG_COUNT] = {0}, skb[CBG_COUNT] = {0};
-    uint32_t kn[CBG_COUNT] = {0}, skn[CBG_COUNT] = {0};
-    size_t nstep = 0;
+    uint64_t kb[CBG_COUNT] = {0}, skb[CBG_COUNT] = {0}, ikb[2 * CBG_COUNT] = {0};
+    uint32_t kn[CBG_COUNT] = {0}, skn[CBG_COUNT] = {0}, ikn[2 * CBG_COUNT] = {0};
+    size_t nstep = 0, nidx = 0;
     for (size_t j = 0; j < nj; j++) {
         const JOB &q = jobs[j];
         const hb_cblosc_header &h = hdrs[q.frame];
@@ -263,6 +294,7 @@ static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
             if (J.status) B.ptr_refusals++;
         }
         if (J.status) continue;
+        if (!lists.fits()) return HB_ERR_BAD_ARG;                         // (lists beyond the 32-bit limits: the caller has to split the job)
         CbgFrame &F = B.frames[q.frame];
         if (!F.typesize) {                                                // the first accepted job of this frame
             F.frame = have ? (const uint8_t *)d_frame[q.frame] : nullptr;
@@ -281,8 +313,13 @@ static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
         for (int k = 0; k < 3; k++) { J.dstr[k] = g.dstr[k]; J.cstr[k] = g.cstr[k]; J.shp[k] = g.shp[k]; }
         J.rcp[0] = cbx_recip(g.shp[1]); J.rcp[1] = cbx_recip(g.shp[2]); J.rcp_unit = cbx_recip(U);
         J.off0 = g.off0; J.rowbytes = g.rowbytes; J.nrows = g.nrows;
-        const bool stepped = g.istr != ts;
-        if (stepped) {                                                    // (units of the row's destination: no misalignment term)
+        const bool stepped = g.istr != ts, listed = lists.listed();
+        if (listed) {                                                     // (its own launch lists: the other gathers never see it)
+            if (B.jirow.empty()) { B.jirow.assign(nj, CbiRow{{CBI_NONE, CBI_NONE, CBI_NONE, CBI_NONE}, 0u, 0u}); B.jigather.assign(nj, 0); }
+            B.jigather[j] = lists.shape(g, ts, U, J, B.jirow[j], B.itab) ? 2 : 1;
+            if (B.itab.size() > HB_CBLOSC_BATCH_MAX_WORK) return HB_ERR_BAD_ARG;
+            nidx++;
+        } else if (stepped) {                                             // (units of the row's destination: no misalignment term)
             const uint32_t ipu = cbs_items_per_unit(ts);
             B.jrow[j] = CbsRow{g.nit, g.istr};
             J.rcp_unit = 0; J.upr = (g.nit + ipu - 1u) / ipu;
@@ -292,16 +329,23 @@ static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
         if (J.upr <= 256u) { J.rpw = 256u / J.upr; J.wpr = 1u; J.rcp16 = 65535u / J.upr + 1u; }
         else { J.rpw = 1u; J.wpr = (J.upr + 255u) / 256u; J.rcp16 = 0u; }
         J.rcp_wpr = cbx_recip(J.wpr);
-        (stepped ? skb : kb)[J.kind] += cbx_groups(J);
-        (stepped ? skn : kn)[J.kind]++;
+        if (listed) {
+            const int l = CBG_COUNT * (B.jigather[j] - 1) + J.kind;
+            ikb[l] += cbx_groups(J); ikn[l]++;
+            if (ikb[l] > HB_CBLOSC_BATCH_MAX_WORK) return HB_ERR_BAD_ARG;
+        } else {
+            (stepped ? skb : kb)[J.kind] += cbx_groups(J);
+            (stepped ? skn : kn)[J.kind]++;
+        }
         if (kb[J.kind] > HB_CBLOSC_BATCH_MAX_WORK || skb[J.kind] > HB_CBLOSC_BATCH_MAX_WORK) return HB_ERR_BAD_ARG;
         if (F.memcpyed) continue;
         // the blocks its rows touch: runs in increasing order, merged as they come
         const size_t first = B.jruns.size();
-        cbx_cover(g, bs, [&](uint32_t lo, uint32_t hi) {
+        auto emit = [&](uint32_t lo, uint32_t hi) {
             if (B.jruns.size() > first && (uint64_t)lo <= (uint64_t)B.jruns.back().hi + 1u) { if (hi > B.jruns.back().hi) B.jruns.back().hi = hi; }
             else B.jruns.push_back(CbgRun{q.frame, lo, hi, (uint32_t)j});
-        });
+        };
+        if (listed) lists.cover(g, bs, emit); else cbx_cover(g, bs, emit);
         J.tl0 = (uint32_t)B.ntouch;                                       // (ntouch stays below 2^31: checked below, job by job)
         for (size_t i = first; i < B.jruns.size(); i++) B.ntouch += (uint64_t)B.jruns[i].hi - B.jruns[i].lo + 1u;
         if (B.ntouch > HB_CBLOSC_BATCH_MAX_WORK) return HB_ERR_BAD_ARG;
@@ -335,8 +379,10 @@ static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
         B.nsplit_all = B.nsplit_all == 0 || B.nsplit_all == F.nsplit ? F.nsplit : 1u;
     }
     if (B.nsplit_all == 0) B.nsplit_all = 1;
-    B.L = cbx_layout(nf, nj, B.nblk, B.ntouch, B.nstreams, B.stage, nstep);
-    uint32_t at = 0, sat = 0;
+    B.L = cbx_layout(nf, nj, B.nblk, B.ntouch, B.nstreams, B.stage, nstep, nidx, B.itab.size());
+    uint32_t at = 0, sat = 0, iat = 0;
+    for (int k = 0; k < 2 * CBG_COUNT; k++) { B.ikind0[k] = iat; iat += ikn[k]; B.ikblocks[k] = (uint32_t)ikb[k]; }
+    B.ikind0[2 * CBG_COUNT] = iat;
     for (int k = 0; k < CBG_COUNT; k++) { B.kind0[k] = at; at += kn[k]; B.kblocks[k] = (uint32_t)kb[k]; }
     for (int k = 0; k < CBG_COUNT; k++) { B.skind0[k] = sat; sat += skn[k]; B.skblocks[k] = (uint32_t)skb[k]; }
     B.kind0[CBG_COUNT] = at; B.skind0[CBG_COUNT] = sat;
@@ -369,11 +415,20 @@ static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
     }
     B.gjob.assign(nj, 0u); B.gblk.assign(nj, 0u);
     B.srow.assign(nstep, CbsRow{0u, 0u}); B.sgjob.assign(nstep, 0u); B.sgblk.assign(nstep, 0u);
-    uint32_t fill_at[CBG_COUNT], blk_at[CBG_COUNT] = {0}, sfill_at[CBG_COUNT], sblk_at[CBG_COUNT] = {0};
+    B.irow.assign(nidx, CbiRow{}); B.igjob.assign(nidx, 0u); B.igblk.assign(nidx, 0u);
+    uint32_t fill_at[CBG_COUNT], blk_at[CBG_COUNT] = {0}, sfill_at[CBG_COUNT], sblk_at[CBG_COUNT] = {0}, ifill_at[2 * CBG_COUNT], iblk_at[2 * CBG_COUNT] = {0};
     for (int k = 0; k < CBG_COUNT; k++) { fill_at[k] = B.kind0[k]; sfill_at[k] = B.skind0[k]; }
+    for (int k = 0; k < 2 * CBG_COUNT; k++) ifill_at[k] = B.ikind0[k];
     for (size_t j = 0; j < nj; j++) {
         const CbxJob &J = B.jobs[j];
         if (J.status || J.kind < 0) continue;
+        if (nidx && B.jigather[j]) {
+            const int l = CBG_COUNT * (B.jigather[j] - 1) + J.kind;
+            const uint32_t at = ifill_at[l]++;
+            B.igjob[at] = (uint32_t)j; B.igblk[at] = iblk_at[l]; B.irow[at] = B.jirow[j];
+            iblk_at[l] += (uint32_t)cbx_groups(J);
+            continue;
+        }
         if (B.jrow[j].nit) {
             const uint32_t at = sfill_at[J.kind]++;
             B.sgjob[at] = (uint32_t)j; B.sgblk[at] = sblk_at[J.kind]; B.srow[at] = B.jrow[j];
@@ -384,6 +439,12 @@ static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
         fill_at[J.kind]++; blk_at[J.kind] += (uint32_t)cbx_groups(J);
     }
     return HB_OK;
+}
+template <class JOB, class REFUSE>
+static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const JOB *jobs,
+                               void *const *d_dst, const size_t *cap, bool fill, CbxBatch &B, unsigned accept, REFUSE refuse) {
+    CbxNoLists none;
+    return cbx_prepare_(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, fill, B, accept, refuse, none);
 }
 static inline int cbx_prepare(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_cblosc_box_job *jobs,
                               void *const *d_dst, const size_t *cap, bool fill, CbxBatch &B, unsigned accept = CB_ACCEPT_DEFAULT) {

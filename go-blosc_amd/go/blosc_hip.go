@@ -1180,7 +1180,7 @@ func CBloscGetSliceBatchHIP(frames [][]byte, jobs []SliceJob) ([][]byte, []error
 // order of the chunk grid gridShape, every chunk chunkShape items of typeSize bytes: one SliceJob per chunk that holds a selected item -- a
 // chunk that a step jumps over gets none -- all of them through one CBloscGetSliceBatchHIP call, placed into the C-order output here.  slices[k]
 // is {lo, hi, step} in items of the whole array.  A nil entry of frames is a chunk the store does not have: its part of the output is fill
-// (typeSize bytes), and a nil fill is then an error.  Index lists per dimension are not covered.
+// (typeSize bytes), and a nil fill is then an error.  Index lists per dimension: CBloscReadOIndex.
 func CBloscReadSlices(frames [][]byte, gridShape, chunkShape []int64, slices [][3]int64, typeSize int, fill []byte) ([]byte, error) {
 	nd := len(chunkShape)
 	if nd < 1 || nd > int(C.HB_CBLOSC_BOX_MAX_NDIM) || len(gridShape) != nd || len(slices) != nd || typeSize < 1 {
@@ -1262,6 +1262,286 @@ func CBloscReadSlices(frames [][]byte, gridShape, chunkShape []int64, slices [][
 	if len(present) > 0 {
 		var errs []error
 		got, errs = CBloscGetSliceBatchHIP(frames, present)
+		for _, err := range errs {
+			if err != nil {
+				return nil, err
+			}
+		}
+	}
+	at := 0
+	for j, q := range jobs { // the rows of every job to their places in the output
+		var packed []byte
+		if !absent[j] {
+			packed = got[at]
+			at++
+		}
+		rowBytes := int(q.Count[nd-1]) * typeSize
+		outer := make([]int64, nd)
+		for r := 0; ; r++ {
+			dst := offs[j]
+			for k := 0; k < nd-1; k++ {
+				dst += outer[k] * strides[k]
+			}
+			if absent[j] {
+				for i := 0; i < rowBytes; i += typeSize {
+					copy(out[int(dst)+i:], fill)
+				}
+			} else {
+				copy(out[dst:], packed[r*rowBytes:(r+1)*rowBytes])
+			}
+			k := nd - 2
+			for ; k >= 0; k-- {
+				if outer[k]++; outer[k] < q.Count[k] {
+					break
+				}
+				outer[k] = 0
+			}
+			if k < 0 {
+				break
+			}
+		}
+	}
+	return out, nil
+}
+
+// IndexJob is one orthogonal selection of CBloscGetIndexBatchHIP over frames[Frame], a C-order chunk of ChunkShape items (1 to 4 dimensions;
+// the five slices have the same length): along dimension k the chunk-local indices Lists[k], in that order, repeats allowed, where Lists[k]
+// is not nil -- else the items Start[k] + i*Step[k], 0 <= i < Count[k].  A non-nil empty list selects nothing.
+type IndexJob struct {
+	Frame                          int
+	ChunkShape, Start, Count, Step []int64
+	Lists                          [][]int64
+}
+
+// CBloscGetIndexBatchHIP reads many orthogonal N-d selections of C-Blosc-1 chunk frames through ONE set of kernel launches
+// (hb_cblosc_getindex_frames_batch): `z.oindex[[3, 17, 400], :]` of a chunked array store is one job per chunk that holds a selected item.
+// Every frame goes up once, every distinct block that holds a selected item is decoded once, and blocks that lie between two list entries of a
+// row or between two selected rows are never read.  out[j] is the selection in C order, errs[j] the job's error.
+// Without a device every job gets the no-device error: there is no CPU path.  Go memory is borrowed for the call only (pinned slabs and C
+// arrays, never Go pointers in C memory).  Like the rest of this file: written against the C ABI, it has never met a compiler.
+func CBloscGetIndexBatchHIP(frames [][]byte, jobs []IndexJob) ([][]byte, []error) {
+	nj, nf := len(jobs), len(frames)
+	out := make([][]byte, nj)
+	errs := make([]error, nj)
+	if nj == 0 {
+		return out, errs
+	}
+	failAll := func(code C.int64_t) ([][]byte, []error) {
+		for j := range jobs {
+			errs[j] = hbError(code)
+		}
+		return out, errs
+	}
+	if !useHIP {
+		return failAll(C.int64_t(C.HB_ERR_NO_DEVICE))
+	}
+	for _, q := range jobs {
+		nd := len(q.ChunkShape)
+		if q.Frame < 0 || q.Frame >= nf || nd < 1 || nd > int(C.HB_CBLOSC_BOX_MAX_NDIM) || len(q.Start) != nd || len(q.Count) != nd || len(q.Step) != nd || len(q.Lists) != nd {
+			return failAll(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+	}
+	ptrBytes := C.size_t(unsafe.Sizeof(uintptr(0)))
+	srcs := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(nf) * ptrBytes))[:nf:nf]
+	dsts := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(nj) * ptrBytes))[:nj:nj]
+	defer C.free(unsafe.Pointer(&srcs[0]))
+	defer C.free(unsafe.Pointer(&dsts[0]))
+	lens := make([]C.size_t, nf)
+	caps := make([]C.size_t, nj)
+	rcs := make([]C.int64_t, nj)
+	jt := make([]C.hb_cblosc_index_job, nj)
+	index := []C.int64_t{0} // (never empty: the array has to be there for an empty list as well)
+	var inBytes, outBytes C.size_t
+	for k, f := range frames {
+		lens[k] = C.size_t(len(f))
+		inBytes += lens[k] // tightly packed: frames that follow each other exactly go up in ONE copy
+	}
+	for j, q := range jobs {
+		ts := int64(1)
+		if len(frames[q.Frame]) >= 16 && frames[q.Frame][3] != 0 {
+			ts = int64(frames[q.Frame][3])
+		}
+		jt[j].frame = C.uint32_t(q.Frame)
+		jt[j].ndim = C.uint32_t(len(q.ChunkShape))
+		bytes := ts // packed: the strides of the selection itself
+		for k := len(q.ChunkShape) - 1; k >= 0; k-- {
+			m := q.Count[k]
+			jt[j].list[k] = -1
+			if q.Lists[k] != nil {
+				m = int64(len(q.Lists[k]))
+				jt[j].list[k] = C.int64_t(len(index))
+				for _, v := range q.Lists[k] {
+					index = append(index, C.int64_t(v))
+				}
+			}
+			jt[j].chunk_shape[k] = C.int64_t(q.ChunkShape[k])
+			jt[j].start[k] = C.int64_t(q.Start[k])
+			jt[j].count[k] = C.int64_t(m)
+			jt[j].step[k] = C.int64_t(q.Step[k])
+			jt[j].dst_stride[k] = C.int64_t(bytes)
+			if m < 0 {
+				m = 1 // (refused by the library)
+			}
+			if m > 0 && bytes > (1<<32)/m { // (a selection beyond 4 GiB is one to split: no room is made for it)
+				bytes = 1 << 32
+			} else {
+				bytes *= m
+			}
+		}
+		if bytes < 1<<32 {
+			caps[j] = C.size_t(bytes)
+		}
+		outBytes += caps[j] + 1
+	}
+	slabIn, slabOut := C.hb_host_alloc(inBytes+64), C.hb_host_alloc(outBytes+64)
+	if slabIn == nil || slabOut == nil {
+		C.hb_host_free(slabIn)
+		C.hb_host_free(slabOut)
+		return failAll(C.int64_t(C.HB_ERR_HIP))
+	}
+	defer C.hb_host_free(slabIn)
+	defer C.hb_host_free(slabOut)
+	var io, oo C.size_t
+	for k, f := range frames {
+		srcs[k] = unsafe.Add(slabIn, uintptr(io))
+		copy(unsafe.Slice((*byte)(srcs[k]), len(f)), f)
+		io += lens[k]
+	}
+	for j := range jobs {
+		dsts[j] = unsafe.Add(slabOut, uintptr(oo))
+		oo += caps[j] + 1
+	}
+	if rc := C.hb_cblosc_getindex_frames_batch(C.int(nf), &srcs[0], &lens[0], C.int(nj), &jt[0], &index[0], C.int64_t(len(index)), &dsts[0], &caps[0], &rcs[0], C.int(Device)); rc != C.HB_OK {
+		return failAll(C.int64_t(rc))
+	}
+	for j := range jobs {
+		if rcs[j] < 0 {
+			errs[j] = hbError(rcs[j])
+		} else {
+			out[j] = append([]byte(nil), unsafe.Slice((*byte)(dsts[j]), int(rcs[j]))...)
+		}
+	}
+	return out, errs
+}
+
+// OSel is the selection of CBloscReadOIndex along one dimension, in items of the whole array: the indices List, in any order, repeats
+// allowed, where List is not nil -- else Lo:Hi:Step.
+type OSel struct {
+	Lo, Hi, Step int64
+	List         []int64
+}
+
+// CBloscReadOIndex answers `z.oindex[sel_0, sel_1 ...]` of a chunked array whose chunks are the C-Blosc-1 frames `frames`, in C order of the
+// chunk grid gridShape, every chunk chunkShape items of typeSize bytes.  A list is cut into maximal runs of consecutive OUTPUT positions that
+// fall into one chunk, and a job is one combination of such runs (a sorted list: one IndexJob per chunk that holds a selected item); all of
+// them go through one CBloscGetIndexBatchHIP call and are placed into the C-order output here.  Negative or out-of-range indices are an
+// error: they are not wrapped.  A nil entry of frames is a chunk the store does not have: its part of the output is fill (typeSize bytes), and
+// a nil fill is then an error.
+func CBloscReadOIndex(frames [][]byte, gridShape, chunkShape []int64, sel []OSel, typeSize int, fill []byte) ([]byte, error) {
+	nd := len(chunkShape)
+	if nd < 1 || nd > int(C.HB_CBLOSC_BOX_MAX_NDIM) || len(gridShape) != nd || len(sel) != nd || typeSize < 1 {
+		return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	// per dimension: a chunk that holds selected indices, the first output index, how many -- and where they start in it, or their chunk-local list
+	type part struct {
+		chunk, first, start, count int64
+		list                       []int64
+	}
+	parts := make([][]part, nd)
+	outShape := make([]int64, nd)
+	strides := make([]int64, nd)
+	steps := make([]int64, nd)
+	total := int64(typeSize)
+	for k := 0; k < nd; k++ {
+		steps[k] = 1
+		if sel[k].List != nil {
+			l := sel[k].List
+			outShape[k] = int64(len(l))
+			for i := 0; i < len(l); {
+				if l[i] < 0 || l[i] >= gridShape[k]*chunkShape[k] {
+					return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+				}
+				ch := l[i] / chunkShape[k]
+				e := i + 1
+				for e < len(l) && l[e] >= 0 && l[e]/chunkShape[k] == ch {
+					e++
+				}
+				local := make([]int64, e-i)
+				for x := i; x < e; x++ {
+					local[x-i] = l[x] - ch*chunkShape[k]
+				}
+				parts[k] = append(parts[k], part{ch, int64(i), 0, int64(e - i), local})
+				i = e
+			}
+			continue
+		}
+		lo, hi, st := sel[k].Lo, sel[k].Hi, sel[k].Step
+		if lo < 0 || hi < lo || hi > gridShape[k]*chunkShape[k] || st < 1 {
+			return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+		steps[k] = st
+		outShape[k] = (hi - lo + st - 1) / st
+		for i := int64(0); i < outShape[k]; {
+			at := lo + i*st
+			ch := at / chunkShape[k]
+			cnt := ((ch+1)*chunkShape[k]-1-at)/st + 1
+			if cnt > outShape[k]-i {
+				cnt = outShape[k] - i
+			}
+			parts[k] = append(parts[k], part{ch, i, at - ch*chunkShape[k], cnt, nil})
+			i += cnt
+		}
+	}
+	for k := nd - 1; k >= 0; k-- {
+		strides[k] = total
+		total *= outShape[k]
+	}
+	out := make([]byte, total)
+	if total == 0 {
+		return out, nil
+	}
+	var jobs []IndexJob
+	var offs []int64
+	var absent []bool
+	idx := make([]int, nd)
+	for {
+		q := IndexJob{ChunkShape: chunkShape, Start: make([]int64, nd), Count: make([]int64, nd), Step: steps, Lists: make([][]int64, nd)}
+		f, off := int64(0), int64(0)
+		for k := 0; k < nd; k++ {
+			p := parts[k][idx[k]]
+			f = f*gridShape[k] + p.chunk
+			off += p.first * strides[k]
+			q.Start[k], q.Count[k], q.Lists[k] = p.start, p.count, p.list
+		}
+		if f >= int64(len(frames)) {
+			return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+		q.Frame = int(f)
+		if frames[f] == nil && len(fill) != typeSize {
+			return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG)) // an absent chunk and no fill value
+		}
+		jobs, offs, absent = append(jobs, q), append(offs, off), append(absent, frames[f] == nil)
+		k := nd - 1
+		for ; k >= 0; k-- {
+			if idx[k]++; idx[k] < len(parts[k]) {
+				break
+			}
+			idx[k] = 0
+		}
+		if k < 0 {
+			break
+		}
+	}
+	var present []IndexJob
+	for j, q := range jobs {
+		if !absent[j] {
+			present = append(present, q)
+		}
+	}
+	var got [][]byte
+	if len(present) > 0 {
+		var errs []error
+		got, errs = CBloscGetIndexBatchHIP(frames, present)
 		for _, err := range errs {
 			if err != nil {
 				return nil, err

@@ -106,6 +106,7 @@ EXPORTS = [
     "hb_cblosc_getitem_frames_batch_workspace", "hb_cblosc_getitem_frames_batch_device", "hb_cblosc_getitem_frames_batch",
     "hb_cblosc_getbox_frames_batch_workspace", "hb_cblosc_getbox_frames_batch_device", "hb_cblosc_getbox_frames_batch",
     "hb_cblosc_getslice_frames_batch_workspace", "hb_cblosc_getslice_frames_batch_device", "hb_cblosc_getslice_frames_batch",
+    "hb_cblosc_getindex_frames_batch_workspace", "hb_cblosc_getindex_frames_batch_device", "hb_cblosc_getindex_frames_batch",
     "hb_cblosc_compress_boxes_batch_workspace", "hb_cblosc_compress_boxes_batch_device", "hb_cblosc_compress_boxes_batch",
     "hb_cblosc_update_boxes_batch_workspace", "hb_cblosc_update_boxes_batch_device", "hb_cblosc_update_boxes_batch",
     "hb_cblosc_accept_codecs",
@@ -156,6 +157,23 @@ def slice_job(frame, chunk_shape, start, count, step, dst_stride):
         raise ValueError("chunk_shape, start, count, step and dst_stride need the same number of entries, at most 4")
     a = ctypes.c_int64 * 4
     return hb_cblosc_slice_job(int(frame), nd, *[a(*[int(v) for v in seq]) for seq in (chunk_shape, start, count, step, dst_stride)])
+
+
+class hb_cblosc_index_job(ctypes.Structure):
+    """include/hipblosc.h hb_cblosc_index_job: an orthogonal N-d selection of a C-order chunk -- per dimension a stepped slice or a list of
+    indices in the call's index array -- and the byte strides of its destination"""
+    _fields_ = [("frame", ctypes.c_uint32), ("ndim", ctypes.c_uint32), ("chunk_shape", ctypes.c_int64 * 4), ("start", ctypes.c_int64 * 4),
+                ("count", ctypes.c_int64 * 4), ("step", ctypes.c_int64 * 4), ("list", ctypes.c_int64 * 4), ("dst_stride", ctypes.c_int64 * 4)]
+
+
+def index_job(frame, chunk_shape, start, count, step, lists, dst_stride):
+    """hb_cblosc_index_job from sequences of ndim entries each (the entries behind them stay 0); lists[k] is -1 for a slice dimension, else
+    where the dimension's count[k] indices start in the call's index array"""
+    nd = len(chunk_shape)
+    if not (len(start) == len(count) == len(step) == len(lists) == len(dst_stride) == nd) or nd > 4:
+        raise ValueError("chunk_shape, start, count, step, lists and dst_stride need the same number of entries, at most 4")
+    a = ctypes.c_int64 * 4
+    return hb_cblosc_index_job(int(frame), nd, *[a(*[int(v) for v in seq]) for seq in (chunk_shape, start, count, step, lists, dst_stride)])
 
 
 class hb_cblosc_src_box(ctypes.Structure):
@@ -268,6 +286,9 @@ def lib():
             "hb_cblosc_getslice_frames_batch_workspace": (sz, [i32, vp, vp, i32, vp]),
             "hb_cblosc_getslice_frames_batch_device": (i32, [i32, vp, vp, vp, i32, vp, vp, vp, vp, sz, vp, vp]),
             "hb_cblosc_getslice_frames_batch": (i32, [i32, vp, vp, i32, vp, vp, vp, vp, i32]),
+            "hb_cblosc_getindex_frames_batch_workspace": (sz, [i32, vp, vp, i32, vp, vp, ctypes.c_int64]),
+            "hb_cblosc_getindex_frames_batch_device": (i32, [i32, vp, vp, vp, i32, vp, vp, ctypes.c_int64, vp, vp, vp, sz, vp, vp]),
+            "hb_cblosc_getindex_frames_batch": (i32, [i32, vp, vp, i32, vp, vp, ctypes.c_int64, vp, vp, vp, i32]),
             "hb_cblosc_compress_boxes_batch_workspace": (sz, [i32, vp, i32, i32]),
             "hb_cblosc_compress_boxes_batch_device": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
             "hb_cblosc_compress_boxes_batch": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32]),
@@ -910,6 +931,168 @@ def CBloscReadSlices(frames, grid_shape, chunk_shape, slices, typesize, fill=Non
         caps = (ctypes.c_size_t * nj)(*[total - off for _, off in pairs])
         rcs = (ctypes.c_int64 * nj)()
         _check(lib().hb_cblosc_getslice_frames_batch(nf, fr, ns, nj, jt, dsts, caps, rcs, device if dev is None else dev))
+        for rc in rcs:
+            _check(int(rc))
+    return bytes(out)
+
+
+def _is_triple(sel):
+    """a (start, count, step) / (lo, hi, step) triple -- a tuple of three ints; any other sequence is a list of indices"""
+    return isinstance(sel, tuple) and len(sel) == 3
+
+
+def CBloscGetIndexBatch(frames, jobs, dev=None):
+    """Many orthogonal N-d selections of many chunk frames through one set of launches (include/hipblosc.h hb_cblosc_getindex_frames_batch):
+    `jobs` are (frame_index, chunk_shape, sel) tuples over `frames`, the chunk in C order, at most 4 dimensions; sel[k] is a (start, count,
+    step) tuple or a sequence of chunk-local indices in any order, repeats allowed (a list, a range, an array).  Only the blocks that hold a
+    selected item are decoded, each once.  The i-th result is the selection's bytes in C order -- what `chunk[np.ix_(...)]` gives in numpy --
+    or the job's error (returned, not raised, as CBloscGetSliceBatch does)."""
+    jobs = list(jobs)
+    nj, nf = len(jobs), len(frames)
+    if nj == 0:
+        return []
+    keep = [_buf(f) for f in frames]
+    jt, caps, index = (hb_cblosc_index_job * nj)(), [], []
+    for j, (f, chunk_shape, sel) in enumerate(jobs):
+        ts = _typesize_of(keep, nf, f)
+        start, count, step, lists = [], [], [], []
+        for s in sel:
+            if _is_triple(s):
+                start.append(s[0]); count.append(s[1]); step.append(s[2]); lists.append(-1)
+            else:
+                s = [int(v) for v in s]
+                start.append(0); count.append(len(s)); step.append(1); lists.append(len(index))
+                index.extend(s)
+        strides, nbytes = [], ts
+        for m in reversed([max(int(v), 0) for v in count]):
+            strides.insert(0, nbytes)
+            nbytes *= m
+        jt[j] = index_job(f, chunk_shape, start, count, step, lists, strides)
+        caps.append(nbytes)
+    outs = [(ctypes.c_char * max(c, 1))() for c in caps]
+    fr = (ctypes.c_void_p * max(nf, 1))(*[k[0].value for k in keep])
+    ns = (ctypes.c_size_t * max(nf, 1))(*[k[1] for k in keep])
+    dsts = (ctypes.c_void_p * nj)(*[ctypes.addressof(o) for o in outs])
+    rcs = (ctypes.c_int64 * nj)()
+    ix = (ctypes.c_int64 * max(len(index), 1))(*index)
+    _check(lib().hb_cblosc_getindex_frames_batch(nf, fr, ns, nj, jt, ix, len(index), dsts, (ctypes.c_size_t * nj)(*caps), rcs, device if dev is None else dev))
+    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(nj)]
+
+
+def index_jobs(grid_shape, chunk_shape, selection, typesize):
+    """The index jobs of `z.oindex[...]` over a chunked array: (jobs, index, out_shape) with `jobs` a list of (hb_cblosc_index_job, byte offset
+    into the output), `index` the index array all of them share, and the output's shape.  selection[k] is a (lo, hi, step) tuple in items of
+    the whole array, as `lo:hi:step`, or a sequence of array-level indices in any order, repeats allowed.  A list is cut into maximal runs of
+    consecutive OUTPUT positions that fall into one chunk, and a job is one combination of such runs: a sorted list gives one job per chunk
+    that holds a selected item.  Chunk (c_0, c_1 ...) is frame number c in C order of the grid.  Negative or out-of-range indices raise
+    ValueError."""
+    nd = len(chunk_shape)
+    if not (len(grid_shape) == len(selection) == nd) or not 1 <= nd <= 4:
+        raise ValueError("grid_shape, chunk_shape and selection need the same number of entries, 1 to 4")
+    # per dimension: (chunk index, first output index, start inside the chunk or where its indices start in `index`, count) per part
+    per, out_shape, steps, index = [], [], [], []
+    for sel, g, c in zip(selection, grid_shape, chunk_shape):
+        parts = []
+        if _is_triple(sel):
+            lo, hi, st = (int(v) for v in sel)
+            if lo < 0 or hi < lo or hi > g * c or st < 1:
+                raise ValueError("a slice lies outside the array, or its step is below 1")
+            m, i = (hi - lo + st - 1) // st, 0
+            while i < m:
+                ch = (lo + i * st) // c
+                cnt = min(m - i, ((ch + 1) * c - 1 - (lo + i * st)) // st + 1)
+                parts.append((ch, i, lo + i * st - ch * c, cnt, False))
+                i += cnt
+            steps.append(st)
+        else:
+            sel = [int(v) for v in sel]
+            if any(v < 0 or v >= g * c for v in sel):
+                raise ValueError("an index lies outside the array (negative indices are not wrapped)")
+            m, i = len(sel), 0
+            while i < m:
+                ch, k = sel[i] // c, i + 1
+                while k < m and sel[k] // c == ch:
+                    k += 1
+                parts.append((ch, i, len(index), k - i, True))
+                index.extend(v - ch * c for v in sel[i:k])
+                i = k
+            steps.append(1)
+        per.append(parts)
+        out_shape.append(m)
+    strides, acc = [], int(typesize)
+    for m in reversed(out_shape):
+        strides.insert(0, acc)
+        acc *= m
+    jobs = []
+    if all(out_shape):
+        idx = [0] * nd
+        while True:
+            f, off = 0, 0
+            for k in range(nd):
+                f = f * grid_shape[k] + per[k][idx[k]][0]
+                off += per[k][idx[k]][1] * strides[k]
+            parts = [per[k][idx[k]] for k in range(nd)]
+            jobs.append((index_job(f, chunk_shape, [0 if p[4] else p[2] for p in parts], [p[3] for p in parts], steps, [p[2] if p[4] else -1 for p in parts], strides), off))
+            k = nd - 1
+            while k >= 0:
+                idx[k] += 1
+                if idx[k] < len(per[k]):
+                    break
+                idx[k] = 0
+                k -= 1
+            if k < 0:
+                break
+    return jobs, index, out_shape
+
+
+def CBloscReadOIndex(frames, grid_shape, chunk_shape, selection, typesize, fill=None, dev=None):
+    """`z.oindex[sel_0, sel_1 ...]` of a chunked array whose chunks are the C-Blosc-1 frames `frames`, in C order of the chunk grid
+    `grid_shape`, every chunk `chunk_shape` items of `typesize` bytes; selection[k] is a (lo, hi, step) tuple or a sequence of array-level
+    indices in any order (index_jobs).  All jobs go through one hb_cblosc_getindex_frames_batch call into one output array.  An entry of
+    `frames` may be None -- the store has no such chunk: its part of the output is `fill` (`typesize` bytes), written here, and with
+    fill=None that raises.  Returns the selection's bytes in C order; raises the first job's error."""
+    pairs, index, out_shape = index_jobs(grid_shape, chunk_shape, selection, typesize)
+    ts, total = int(typesize), int(typesize)
+    for m in out_shape:
+        total *= m
+    absent = [p for p in pairs if frames[p[0].frame] is None]
+    if absent:
+        if fill is None:
+            raise ValueError("a selected chunk is absent and there is no fill value")
+        if len(bytes(fill)) != ts:
+            raise ValueError("fill needs typesize bytes")
+    if not pairs:
+        return b""
+    out = (ctypes.c_char * total)()
+    base = ctypes.addressof(out)
+    for job, off in absent:                                               # the rows of an absent chunk's part of the output
+        nd = job.ndim
+        row = bytes(fill) * job.count[nd - 1]
+        outer = [0] * (nd - 1)
+        while True:
+            at = off + sum(i * job.dst_stride[k] for k, i in enumerate(outer))
+            ctypes.memmove(base + at, row, len(row))
+            k = nd - 2
+            while k >= 0:
+                outer[k] += 1
+                if outer[k] < job.count[k]:
+                    break
+                outer[k] = 0
+                k -= 1
+            if k < 0:
+                break
+    pairs = [p for p in pairs if frames[p[0].frame] is not None]
+    nj, nf = len(pairs), len(frames)
+    if nj:
+        keep = [_buf(f if f is not None else b"") for f in frames]
+        jt = (hb_cblosc_index_job * nj)(*[p[0] for p in pairs])
+        fr = (ctypes.c_void_p * max(nf, 1))(*[k[0].value for k in keep])
+        ns = (ctypes.c_size_t * max(nf, 1))(*[k[1] for k in keep])
+        dsts = (ctypes.c_void_p * nj)(*[base + off for _, off in pairs])
+        caps = (ctypes.c_size_t * nj)(*[total - off for _, off in pairs])
+        rcs = (ctypes.c_int64 * nj)()
+        ix = (ctypes.c_int64 * max(len(index), 1))(*index)
+        _check(lib().hb_cblosc_getindex_frames_batch(nf, fr, ns, nj, jt, ix, len(index), dsts, caps, rcs, device if dev is None else dev))
         for rc in rcs:
             _check(int(rc))
     return bytes(out)

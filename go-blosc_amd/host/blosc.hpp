@@ -270,6 +270,50 @@ inline std::vector<Bytes> CBloscGetSliceBatch(const std::vector<Bytes> &frames, 
     for (size_t j = 0; j < nj; j++) out[j].resize(rc[j] > 0 ? (size_t)rc[j] : 0);
     return out;
 }
+// many orthogonal N-d selections of C-order chunk frames through one set of launches (hb_cblosc_getindex_frames_batch; only the blocks that hold
+// a selected item are decoded, each once): along dimension k job j takes the chunk-local indices lists[k], in that order, repeats allowed,
+// where lists[k] is there and not empty -- else the items start[k] + i * step[k], 0 <= i < count[k] (for an EMPTY selection along k: count[k]
+// == 0).  1 to 4 dimensions, the same number of entries in all five.  out[j] is the selection in C order, what chunk[np.ix_(...)] gives in
+// numpy; rc[j] its byte count or the job's HB_ERR_* code (nothing is thrown per job)
+struct IndexJob { uint32_t frame; std::vector<int64_t> chunk_shape, start, count, step; std::vector<std::vector<int64_t>> lists; };
+inline std::vector<Bytes> CBloscGetIndexBatch(const std::vector<Bytes> &frames, const std::vector<IndexJob> &jobs, std::vector<int64_t> &rc, int device = 0) {
+    const size_t nf = frames.size(), nj = jobs.size();
+    std::vector<Bytes> out(nj);
+    rc.assign(nj, 0);
+    if (!nj) return out;
+    std::vector<const void *> fr(nf); std::vector<size_t> ns(nf);
+    for (size_t k = 0; k < nf; k++) { fr[k] = frames[k].data(); ns[k] = frames[k].size(); }
+    std::vector<hb_cblosc_index_job> jt(nj); std::vector<void *> dst(nj); std::vector<size_t> cap(nj);
+    std::vector<int64_t> index;
+    for (size_t j = 0; j < nj; j++) {
+        const IndexJob &q = jobs[j];
+        const size_t nd = q.chunk_shape.size();
+        if (nd < 1 || nd > HB_CBLOSC_BOX_MAX_NDIM || q.start.size() != nd || q.count.size() != nd || q.step.size() != nd || q.lists.size() != nd) check(HB_ERR_BAD_ARG);
+        size_t ts = 1;
+        if (q.frame < nf && ns[q.frame] >= 16 && frames[q.frame][3]) ts = frames[q.frame][3];
+        hb_cblosc_index_job &t = jt[j];
+        t = hb_cblosc_index_job{};
+        t.frame = q.frame; t.ndim = (uint32_t)nd;
+        uint64_t bytes = ts;                                              // packed: the strides of the selection itself
+        for (size_t k = nd; k-- > 0;) {
+            const bool listed = !q.lists[k].empty();
+            t.chunk_shape[k] = q.chunk_shape[k]; t.start[k] = q.start[k]; t.step[k] = q.step[k];
+            t.count[k] = listed ? (int64_t)q.lists[k].size() : q.count[k];
+            t.list[k] = listed ? (int64_t)index.size() : -1;
+            index.insert(index.end(), q.lists[k].begin(), q.lists[k].end());
+            t.dst_stride[k] = (int64_t)bytes;
+            const uint64_t m = t.count[k] > 0 ? (uint64_t)t.count[k] : (t.count[k] == 0 ? 0u : 1u);
+            bytes = m && bytes > (1ull << 32) / m ? (1ull << 32) : bytes * m;         // (a selection beyond 4 GiB is one to split: no room is made for it)
+        }
+        cap[j] = bytes <= 0xFFFFFFFFull ? (size_t)bytes : 0;
+        out[j].resize(cap[j] ? cap[j] : 1);
+        dst[j] = out[j].data();
+    }
+    index.push_back(0);                                                   // (never NULL)
+    check(hb_cblosc_getindex_frames_batch((int)nf, fr.data(), ns.data(), (int)nj, jt.data(), index.data(), (int64_t)index.size() - 1, dst.data(), cap.data(), rc.data(), device));
+    for (size_t j = 0; j < nj; j++) out[j].resize(rc[j] > 0 ? (size_t)rc[j] : 0);
+    return out;
+}
 // many inputs to C-Blosc-1 frames through one set of launches (hb_cblosc_compress_frames_batch; shuffle 0 / 1 / 2 = none / byte / bit, one shuffle
 // and typesize for the whole batch): out[k] is the frame hb_cblosc_compress writes for datas[k], rc[k] its byte count or its HB_ERR_* code
 // (nothing is thrown per input)

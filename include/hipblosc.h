@@ -524,8 +524,8 @@ int     hb_cblosc_getbox_frames_batch(int nframes, const void *const *frame, con
  *      (njobs + nframes) + HB_CBLOSC_BOX_BATCH_TOUCH_BYTES * (the number of (job, touched block) pairs).  0 when the call as a whole would be
  *      refused, 256 for njobs == 0.
  *      Host form: as the box batch's -- the frames go up once, the device form runs once into a packed buffer with the selections
- *      C-contiguous, one copy down, and the host places the rows.  There is no per-item fallback.  Index lists per dimension are not
- *      covered. ---- */
+ *      C-contiguous, one copy down, and the host places the rows.  There is no per-item fallback.  Index lists per dimension are
+ *      hb_cblosc_getindex_frames_batch*, below. ---- */
 #define HB_CBLOSC_SLICE_BATCH_JOB_BYTES 512      /* workspace per job and per frame beyond the blocks */
 typedef struct hb_cblosc_slice_job {
     uint32_t frame;            /* index into the frame arrays */
@@ -542,6 +542,53 @@ int     hb_cblosc_getslice_frames_batch_device(int nframes, const hb_cblosc_head
 int     hb_cblosc_getslice_frames_batch(int nframes, const void *const *frame, const size_t *n,
                                         int njobs, const hb_cblosc_slice_job *jobs, void *const *dst, const size_t *cap,
                                         int64_t *rc, int device);
+/* ---- many orthogonal N-d selections of many C-Blosc-1 frames through ONE set of launches: `z.oindex[[3, 17, 400], :]`, `z.oindex[rows, :, cols]`
+ *      or a boolean mask along an axis after nonzero() is, per chunk that holds a selected item, a slice job in which a dimension may take its
+ *      indices from a list instead of start / step.  Everything of hb_cblosc_getslice_frames_batch* holds, except what follows.
+ *      `index` is a HOST array of nindex entries in all three forms, like `jobs`; the lists of all jobs live in it and jobs may share a list.
+ *      Item (i_0 .. i_{ndim-1}) of the selection, 0 <= i_k < count[k], is the chunk's item at coordinate c_k = list[k] >= 0 ?
+ *      index[list[k] + i_k] : start[k] + i_k * step[k]; it is written to d_dst[j] + sum_k i_k * dst_stride[k].  A list may be in any order (a
+ *      descending one is the reversed read no slice expresses), may repeat an index and may be longer than its dimension.
+ *      Device form:
+ *        - refused per job, on the host before hb_init(), in the slice batch's order; in its HB_ERR_BAD_ARG group (after the header, codec and
+ *          geometry refusals, before the capacity and the pointers) also: list[k] < -1, list[k] + count[k] > nindex (checked without overflow),
+ *          an index < 0 or >= chunk_shape[k] (negative indices are not wrapped).  A slice dimension keeps the slice batch's rules, "count[k]
+ *          == 1 is taken with step 1" included; start[k] and step[k] of a list dimension are not looked at;
+ *        - a job with some count[k] == 0: status 0, bytes 0, nothing planned or written; of its other lists only the bounds in `index` are
+ *          checked;
+ *        - a block is touched iff it holds a byte of a selected item, whatever the order and the repeats: an untouched block is never planned,
+ *          decoded or read, also between two list entries of one row or between two selected rows; every distinct (frame, block) pair is
+ *          decoded once per call and stands once in a job's touch list.  The fail state is per block, a failed job writes nothing, and nothing
+ *          is written outside the selected items' destination bytes.
+ *      A job whose list[k] are all -1 answers exactly what hb_cblosc_getslice_frames_batch* answers for the same fields: the record, the bytes
+ *      written, the bytes left alone and the workspace query.
+ *      The call as a whole: as the slice batch, in its order; its HB_ERR_BAD_ARG group also has nindex < 0, index == NULL while some job has a
+ *      list dimension, and more than HB_CBLOSC_BATCH_MAX_WORK table entries or rows of one job.
+ *      Workspace: the slice batch's bound with HB_CBLOSC_INDEX_BATCH_JOB_BYTES as the per-job constant, plus HB_CBLOSC_INDEX_BATCH_ENTRY_BYTES
+ *      times the sum of count[k] over the list dimensions of the accepted jobs: it grows with the lists' lengths (their sum), never with rows
+ *      or selected items (their product).  0 when the call as a whole would be refused, 256 for njobs == 0.
+ *      Host form: as the box batch's -- the frames go up once, the device form runs once into a packed buffer with the selections
+ *      C-contiguous, one copy down, and the host places the rows.  There is no per-item fallback; without a device every accepted job
+ *      answers HB_ERR_NO_DEVICE. ---- */
+#define HB_CBLOSC_INDEX_BATCH_JOB_BYTES   512    /* workspace per job and per frame beyond the blocks */
+#define HB_CBLOSC_INDEX_BATCH_ENTRY_BYTES 4      /* workspace per list entry of an accepted job */
+typedef struct hb_cblosc_index_job {
+    uint32_t frame;            /* index into the frame arrays */
+    uint32_t ndim;             /* 1 .. HB_CBLOSC_BOX_MAX_NDIM */
+    int64_t  chunk_shape[4];   /* items, C order (last dimension contiguous); product * typesize == the header's nbytes */
+    int64_t  start[4], count[4], step[4];   /* dimension k with list[k] < 0: the slice start[k] + i * step[k], as in hb_cblosc_slice_job */
+    int64_t  list[4];          /* -1: a slice dimension.  >= 0: dimension k takes the count[k] chunk-local indices
+                                  index[list[k] .. list[k] + count[k]) of the call's index array, in that order; start[k], step[k] not looked at */
+    int64_t  dst_stride[4];    /* BYTES between neighbours along dimension k in the destination; >= 0; dst_stride[ndim-1] == typesize */
+} hb_cblosc_index_job;         /* entries at k >= ndim are 0 and not looked at */
+size_t  hb_cblosc_getindex_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n,
+                                                  int njobs, const hb_cblosc_index_job *jobs, const int64_t *index, int64_t nindex);
+int     hb_cblosc_getindex_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n,
+                                               int njobs, const hb_cblosc_index_job *jobs, const int64_t *index, int64_t nindex,
+                                               void *const *d_dst, const size_t *cap, void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
+int     hb_cblosc_getindex_frames_batch(int nframes, const void *const *frame, const size_t *n,
+                                        int njobs, const hb_cblosc_index_job *jobs, const int64_t *index, int64_t nindex,
+                                        void *const *dst, const size_t *cap, int64_t *rc, int device);
 /* writing the format: a frame that blosc_decompress() of c-blosc 1.x (python-blosc, numcodecs ...) reads.  shuffle: 0 none, 1 byte
  * shuffle, 2 bit shuffle (BLOSC_NOSHUFFLE / BLOSC_SHUFFLE / BLOSC_BITSHUFFLE); LZ4 streams; block size 4096 x typesize (split) or
  * 4096 (not split), so that every stream is one chunk of this library's encoder; n below 2 GiB (c-blosc's limit).  Returns the
