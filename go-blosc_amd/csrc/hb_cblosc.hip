@@ -247,6 +247,27 @@ static void cb_launch_streams(const SPACE &sp, const CbStream *streams, uint32_t
     if (any_blz) launch(std::integral_constant<int, CBW_BLZ>{}, S.grid_blz, name_blz);
 }
 
+// ---- what the launch code of the read batches shares (the getitem batch and cbx_launch below) ----
+// a section of the one upload: the vector to its layout offset, unless it is empty; and a section of the workspace as the records it holds
+template <class T>
+static inline void cb_put(std::vector<uint8_t> &up, size_t at, const std::vector<T> &v) {
+    if (!v.empty()) memcpy(up.data() + at, v.data(), v.size() * sizeof(T));
+}
+template <class T>
+static inline T *cb_at(uint8_t *w, size_t at) { return (T *)(w + at); }
+// One launch per kind that occurs among a gather's jobs: kind0 = where each kind's jobs start in the launch list (CBG_COUNT + 1 entries),
+// kblocks / names = the kind's workgroup count and profile stage.  launch(K, k0, nk, blocks) gets the kind as a compile-time constant.
+template <class LAUNCH>
+static void cb_launch_kinds(const uint32_t *kind0, const uint32_t *kblocks, const char *const *names, hipStream_t s, LAUNCH &&launch) {
+    for (int k = 0; k < CBG_COUNT; k++) {
+        const uint32_t k0 = kind0[k], nk = kind0[k + 1] - k0, blocks = kblocks[k];
+        if (!nk) continue;
+        hb_prof_begin(names[k], s);
+        cb_with_kind(k, [&](auto K) { launch(K, k0, nk, blocks); });      // (any other kind: CBG_BITUN4, the last)
+        hb_prof_end(s);
+    }
+}
+
 // ---- the per-block filters, undone ----
 // (bodies with their workgroup index `bx` and grid size `gx`: the one-frame kernels pass blockIdx.x / gridDim.x, k_cbb_unfilter the workgroup's
 // place among those of its frame)
@@ -590,16 +611,21 @@ __global__ __launch_bounds__(256) void k_cbg_gather(const CbgFrame *__restrict__
     cbg_unit<KIND>(F, look, work, lo, hi, J.dst + (lo - J.off));
 }
 
-// one thread per job: what the host decided, or k_cb_result's record from the OR of the fail words of the job's blocks
-__global__ __launch_bounds__(64) void k_cbg_finish(const CbgJob *__restrict__ jobs, const CbPlan *__restrict__ plans, hb_result *results, uint32_t njobs) {
+// One thread per job: what the host decided, or k_cb_result's record from the OR of the fail words of the job's `nrec` block records, the k-th
+// of which is plan rec(J, k).  The body of k_cbg_finish (consecutive records) and k_cbx_finish (the touch list).
+template <class JOB, class REC>
+__device__ __forceinline__ void cb_finish_jobs(const JOB *__restrict__ jobs, const CbPlan *__restrict__ plans, hb_result *results, uint32_t njobs, uint32_t JOB::*nrec, REC rec) {
     const uint32_t j = blockIdx.x * 64u + threadIdx.x;
     if (j >= njobs) return;
-    const CbgJob &J = jobs[j];
+    const JOB &J = jobs[j];
     hb_result *r = results + j;
     if (J.status) { cb_refused_result(r, J.status); return; }
     CbPlan p; p.fail = 0u;
-    for (uint32_t k = 0; k < J.nb; k++) p.fail |= plans[J.blk0 + k].fail;
+    for (uint32_t k = 0; k < J.*nrec; k++) p.fail |= plans[rec(J, k)].fail;
     cb_result(&p, r, J.bytes);
+}
+__global__ __launch_bounds__(64) void k_cbg_finish(const CbgJob *__restrict__ jobs, const CbPlan *__restrict__ plans, hb_result *results, uint32_t njobs) {
+    cb_finish_jobs(jobs, plans, results, njobs, &CbgJob::nb, [](const CbgJob &J, uint32_t k) { return J.blk0 + k; });
 }
 
 // ---- batched box reads (hb_cblosc_getbox_frames_batch_device; the host side and the index arithmetic are hb_cblosc_box_batch.h).  The plan and
@@ -608,33 +634,54 @@ struct CbxLookup {
     const CbgBlock *__restrict__ blocks; const CbxTouch *__restrict__ tl; uint32_t ntl, b_lo, dense;      // the job's touch list
     __device__ __forceinline__ const CbgBlock &operator()(uint32_t b) const { return blocks[tl[cbx_find(tl, ntl, b_lo, dense, b)].rec]; }
 };
+// How the four N-d gather kernels below open: gjob / gblk = the jobs of the launch and the prefix of their workgroup counts.  The workgroup finds
+// its job (number i of the launch: its row record, where the launch has them, is rows[i]) and its place wl among the job's workgroups, ORs the fail
+// words of the blocks the job touches and is not `live` -- the whole workgroup, before any store -- if one is set.  The records are the kernels'
+// own `const __restrict__` arguments handed through: inlined, they are read with scalar loads as before (CB_RO above says what else costs).
+struct CbxWg {
+    bool live; const CbxJob &J; const CbgFrame &F; uint32_t i, wl; CbxLookup look;
+};
+__device__ __forceinline__ CbxWg cbx_enter(const CbgFrame *__restrict__ frames, const CbxJob *__restrict__ jobs, const CbgBlock *__restrict__ blocks, const CbPlan *__restrict__ plans,
+                                           const CbxTouch *__restrict__ touch, const uint32_t *__restrict__ gjob, const uint32_t *__restrict__ gblk, uint32_t nkind) {
+    const uint32_t i = hb_owner(gblk, nkind, blockIdx.x);
+    const CbxJob &J = jobs[gjob[i]];
+    const CbxTouch *tl = touch + J.tl0;
+    int bad = 0;
+    for (uint32_t k = threadIdx.x; k < J.ntl; k += 256u) bad |= plans[tl[k].rec].fail != 0u;
+    const bool live = !__syncthreads_or(bad);
+    return CbxWg{live, J, frames[J.frame], i, blockIdx.x - gblk[i], CbxLookup{blocks, tl, J.ntl, J.b_lo, J.dense}};
+}
 // One launch per kind that occurs, over a workgroup prefix per job.  A job's thread space is rows x units per row (cbx_thread: whole rows to a
 // workgroup where rows are short, several workgroups to a row where they are long; the divisions are multiplications by reciprocals the host
-// put into the record).  Every workgroup first ORs the fail words of the blocks the job touches and writes nothing if one is set.
+// put into the record).
 template <int KIND>
 __global__ __launch_bounds__(256) void k_cbx_gather(const CbgFrame *__restrict__ frames, const CbxJob *__restrict__ jobs, const CbgBlock *__restrict__ blocks,
                                                      const CbPlan *__restrict__ plans, const CbxTouch *__restrict__ touch, const uint32_t *__restrict__ gjob,
                                                      const uint32_t *__restrict__ gblk, uint32_t nkind, const uint8_t *__restrict__ work) {
-    const uint32_t i = hb_owner(gblk, nkind, blockIdx.x);
-    const CbxJob &J = jobs[gjob[i]];
-    const CbgFrame &F = frames[J.frame];
-    const CbxTouch *tl = touch + J.tl0;
-    int bad = 0;
-    for (uint32_t k = threadIdx.x; k < J.ntl; k += 256u) bad |= plans[tl[k].rec].fail != 0u;
-    if (__syncthreads_or(bad)) return;
+    const CbxWg W = cbx_enter(frames, jobs, blocks, plans, touch, gjob, gblk, nkind);
+    if (!W.live) return;
     uint32_t lo, hi;
     uint64_t doff;
-    if (!cbx_thread(J, cbg_unit_bytes(KIND, F.typesize), blockIdx.x - gblk[i], threadIdx.x, lo, hi, doff)) return;
-    const CbxLookup look{blocks, tl, J.ntl, J.b_lo, J.dense};
-    cbg_unit<KIND>(F, look, work, lo, hi, J.dst + doff);
+    if (!cbx_thread(W.J, cbg_unit_bytes(KIND, W.F.typesize), W.wl, threadIdx.x, lo, hi, doff)) return;
+    cbg_unit<KIND>(W.F, W.look, work, lo, hi, W.J.dst + doff);
 }
-// ---- batched slice reads (hb_cblosc_getslice_frames_batch_device; hb_cblosc_slice_batch.h): the jobs whose rows are stepped.  Everything but
-// the gather is the box batch's. ----
-// 16 bytes = 16 / TS items, `istr` bytes apart, the first at byte p of the frame's decoded bytes.  An item that lies whole inside the whole
-// elements of its block is read where it is staged (a byte-shuffled block plane by plane); one that straddles two blocks or lies behind a
-// block's last whole element goes byte by byte through cbg_byte.  Neighbouring items usually share a block: its record is looked up once.
-template <int KIND, uint32_t TS, class LOOK>
-__device__ __forceinline__ u32x4 cbs_items16(const CbgFrame &F, const LOOK &look, const uint8_t *__restrict__ work, uint32_t p, uint32_t istr) {
+// ---- rows of items: the stepped rows of the slice batch (hb_cblosc_getslice_frames_batch_device; hb_cblosc_slice_batch.h) and the listed or
+// stepped rows of the index batch below.  A unit is 16 bytes of the row's destination: items that lie at(0), at(1) ... bytes behind byte p of
+// the frame's decoded bytes, `at` being one of two by-value policies.  Which one is the kernel's choice at compile time: the stepped gather
+// has no table to test for. ----
+struct CbsStepped {                                                            // a stepped row from its first item of the unit on: i * istr
+    uint32_t istr;
+    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return i * istr; }
+};
+struct CbiListed {                                                             // a row of the index batch from its start on, the unit's first item being `it`: cbi_item
+    const uint32_t *__restrict__ rt; uint32_t istr, it;
+    __device__ __forceinline__ uint32_t operator()(uint32_t i) const { return cbi_item(rt, istr, it + i); }
+};
+// 16 bytes = 16 / TS items.  An item that lies whole inside the whole elements of its block is read where it is staged (a byte-shuffled block
+// plane by plane); one that straddles two blocks or lies behind a block's last whole element goes byte by byte through cbg_byte.  Neighbouring
+// items usually share a block: its record is looked up once.
+template <int KIND, uint32_t TS, class LOOK, class AT>
+__device__ __forceinline__ u32x4 cbr_items16(const CbgFrame &F, const LOOK &look, const uint8_t *__restrict__ work, uint32_t p, const AT at) {
     uint32_t w[4] = {0u, 0u, 0u, 0u};
     const uint32_t bs = F.blocksize;
     const bool direct = KIND == CBG_COPY && F.memcpyed;
@@ -642,7 +689,7 @@ __device__ __forceinline__ u32x4 cbs_items16(const CbgFrame &F, const LOOK &look
     const uint8_t *s = nullptr;
 #pragma unroll
     for (uint32_t c = 0; c < 16u / TS; c++) {
-        const uint32_t pc = p + c * istr;
+        const uint32_t pc = p + at(c);
         uint32_t q = 0u, e = 0u;
         bool whole = direct;
         if (!direct) {
@@ -662,116 +709,59 @@ __device__ __forceinline__ u32x4 cbs_items16(const CbgFrame &F, const LOOK &look
     u32x4 v; v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
     return v;
 }
-// One unit of a stepped row: `cnt` items, istr bytes apart from byte p of the frame's decoded bytes on, to d, packed.  16 bytes of whole items
-// of a copied or byte-shuffled frame are assembled in registers and stored at once (d has any alignment); the plain body has the row tails,
-// the other typesizes and both bit-shuffle kinds.
-template <int KIND, class LOOK>
-__device__ __forceinline__ void cbs_unit(const CbgFrame &F, const LOOK &look, const uint8_t *__restrict__ work, uint32_t p, uint32_t istr, uint32_t cnt, uint8_t *__restrict__ d) {
+// One unit of a row: `cnt` items to d, packed.  16 bytes of whole items of a copied or byte-shuffled frame are assembled in registers and stored
+// at once (d has any alignment); the plain body has the row tails, the other typesizes and both bit-shuffle kinds -- through cbg_byte, which
+// reads a bit-shuffled block the same way for CBG_BITUN and CBG_BITUN4.
+template <int KIND, class LOOK, class AT>
+__device__ __forceinline__ void cbr_unit(const CbgFrame &F, const LOOK &look, const uint8_t *__restrict__ work, uint32_t p, const AT at, uint32_t cnt, uint8_t *__restrict__ d) {
     const uint32_t ts = F.typesize;
     if ((KIND == CBG_COPY || KIND == CBG_UNSHUFFLE) && cnt * ts == 16u) {
-        if (ts == 1u && KIND == CBG_COPY) { st16u(d, cbs_items16<KIND, 1>(F, look, work, p, istr)); return; }      // (one byte is never shuffled)
-        if (ts == 2u) { st16u(d, cbs_items16<KIND, 2>(F, look, work, p, istr)); return; }
-        if (ts == 4u) { st16u(d, cbs_items16<KIND, 4>(F, look, work, p, istr)); return; }
-        if (ts == 8u) { st16u(d, cbs_items16<KIND, 8>(F, look, work, p, istr)); return; }
-        if (ts == 16u) { st16u(d, cbs_items16<KIND, 16>(F, look, work, p, istr)); return; }
+        if (ts == 1u && KIND == CBG_COPY) { st16u(d, cbr_items16<KIND, 1>(F, look, work, p, at)); return; }      // (one byte is never shuffled)
+        if (ts == 2u) { st16u(d, cbr_items16<KIND, 2>(F, look, work, p, at)); return; }
+        if (ts == 4u) { st16u(d, cbr_items16<KIND, 4>(F, look, work, p, at)); return; }
+        if (ts == 8u) { st16u(d, cbr_items16<KIND, 8>(F, look, work, p, at)); return; }
+        if (ts == 16u) { st16u(d, cbr_items16<KIND, 16>(F, look, work, p, at)); return; }
     }
-    for (uint32_t c = 0; c < cnt; c++)
-        for (uint32_t j = 0; j < ts; j++) d[c * ts + j] = cbg_byte<KIND>(F, look, work, p + c * istr + j);
+    for (uint32_t c = 0; c < cnt; c++) {
+        const uint32_t pc = p + at(c);
+        for (uint32_t j = 0; j < ts; j++) d[c * ts + j] = cbg_byte<KIND>(F, look, work, pc + j);
+    }
 }
-// One launch per kind that occurs among the jobs with stepped rows; gjob / gblk / rows are those jobs in launch order.  A job's thread space
-// is rows x units per row, a unit being 16 bytes of the row's destination (cbs_thread).  The fail check comes before any store, as above.
+// The kind an items gather is launched with.  KIND reaches cbr_unit alone -- cbs_thread and cbi_thread_items do not see it -- and there the two
+// bit-shuffle kinds have the plain body only, in which cbg_byte tests nothing but KIND == CBG_COPY and KIND == CBG_UNSHUFFLE: the CBG_BITUN4
+// instantiation would be the CBG_BITUN one once more (it was: the same instructions, 35 VGPRs each).  So jobs of kind CBG_BITUN4 run the CBG_BITUN
+// instantiation, under their own stage name; the host sorts the jobs into four kinds as for every other gather.
+static constexpr int cbr_items_kind(int kind) { return kind == CBG_BITUN4 ? CBG_BITUN : kind; }
+// The slice batch's gather: one launch per kind that occurs among the jobs with stepped rows; gjob / gblk / rows are those jobs in launch
+// order.  A job's thread space is rows x units per row (cbs_thread).  Everything but this gather is the box batch's.
 template <int KIND>
 __global__ __launch_bounds__(256) void k_cbs_gather(const CbgFrame *__restrict__ frames, const CbxJob *__restrict__ jobs, const CbsRow *__restrict__ rows,
                                                      const CbgBlock *__restrict__ blocks, const CbPlan *__restrict__ plans, const CbxTouch *__restrict__ touch,
                                                      const uint32_t *__restrict__ gjob, const uint32_t *__restrict__ gblk, uint32_t nkind, const uint8_t *__restrict__ work) {
-    const uint32_t i = hb_owner(gblk, nkind, blockIdx.x);
-    const CbxJob &J = jobs[gjob[i]];
-    const CbsRow R = rows[i];
-    const CbgFrame &F = frames[J.frame];
-    const CbxTouch *tl = touch + J.tl0;
-    int bad = 0;
-    for (uint32_t k = threadIdx.x; k < J.ntl; k += 256u) bad |= plans[tl[k].rec].fail != 0u;
-    if (__syncthreads_or(bad)) return;
+    const CbxWg W = cbx_enter(frames, jobs, blocks, plans, touch, gjob, gblk, nkind);
+    if (!W.live) return;
+    const CbsRow R = rows[W.i];
     uint32_t it0, cnt, roff;
     uint64_t doff;
-    if (!cbs_thread(J, R, F.typesize, blockIdx.x - gblk[i], threadIdx.x, it0, cnt, roff, doff)) return;
-    const CbxLookup look{blocks, tl, J.ntl, J.b_lo, J.dense};
-    cbs_unit<KIND>(F, look, work, roff + it0 * R.istr, R.istr, cnt, J.dst + doff);
+    if (!cbs_thread(W.J, R, W.F.typesize, W.wl, threadIdx.x, it0, cnt, roff, doff)) return;
+    cbr_unit<KIND>(W.F, W.look, work, roff + it0 * R.istr, CbsStepped{R.istr}, cnt, W.J.dst + doff);
 }
 // ---- batched index-list reads (hb_cblosc_getindex_frames_batch_device; hb_cblosc_index_batch.h): the jobs in which a dimension takes its
 // indices from a list.  Everything but the two gathers is the box batch's.  `tab` is the batch's table section: byte offsets, index * (chunk
 // stride), in the caller's order. ----
 // The rows gather: the row is a plain run, an outer dimension has a list.  A thread has one frame-aligned unit of a row (cbi_thread_rows) and
-// the wide bodies of cbg_unit; only the row's offset comes from tables.  The fail check comes before any store, as above.
+// the wide bodies of cbg_unit; only the row's offset comes from tables.
 template <int KIND>
 __global__ __launch_bounds__(256) void k_cbi_gather_rows(const CbgFrame *__restrict__ frames, const CbxJob *__restrict__ jobs, const CbiRow *__restrict__ rows,
                                                           const CbgBlock *__restrict__ blocks, const CbPlan *__restrict__ plans, const CbxTouch *__restrict__ touch,
                                                           const uint32_t *__restrict__ tab, const uint32_t *__restrict__ gjob, const uint32_t *__restrict__ gblk,
                                                           uint32_t nkind, const uint8_t *__restrict__ work) {
-    const uint32_t i = hb_owner(gblk, nkind, blockIdx.x);
-    const CbxJob &J = jobs[gjob[i]];
-    const CbiRow R = rows[i];
-    const CbgFrame &F = frames[J.frame];
-    const CbxTouch *tl = touch + J.tl0;
-    int bad = 0;
-    for (uint32_t k = threadIdx.x; k < J.ntl; k += 256u) bad |= plans[tl[k].rec].fail != 0u;
-    if (__syncthreads_or(bad)) return;
+    const CbxWg W = cbx_enter(frames, jobs, blocks, plans, touch, gjob, gblk, nkind);
+    if (!W.live) return;
     uint32_t lo, hi;
     uint64_t doff;
-    if (!cbi_thread_rows(J, R, tab, cbg_unit_bytes(KIND, F.typesize), blockIdx.x - gblk[i], threadIdx.x, lo, hi, doff)) return;
-    const CbxLookup look{blocks, tl, J.ntl, J.b_lo, J.dense};
-    cbg_unit<KIND>(F, look, work, lo, hi, J.dst + doff);
-}
-// 16 bytes = 16 / TS items of a row from item `it` on, the row at byte roff of the frame's decoded bytes: item i lies cbi_item(rt, istr, i) bytes
-// into it.  As cbs_items16: an item that lies whole inside the whole elements of its block is read where it is staged, any other goes byte by
-// byte through cbg_byte, and a block's record is looked up once while neighbours share it.
-template <int KIND, uint32_t TS, class LOOK>
-__device__ __forceinline__ u32x4 cbi_items16(const CbgFrame &F, const LOOK &look, const uint8_t *__restrict__ work, uint32_t roff, const uint32_t *__restrict__ rt,
-                                             uint32_t istr, uint32_t it) {
-    uint32_t w[4] = {0u, 0u, 0u, 0u};
-    const uint32_t bs = F.blocksize;
-    const bool direct = KIND == CBG_COPY && F.memcpyed;
-    uint32_t cur = ~0u, bsize = 0u, nel = 0u;
-    const uint8_t *s = nullptr;
-#pragma unroll
-    for (uint32_t c = 0; c < 16u / TS; c++) {
-        const uint32_t pc = roff + cbi_item(rt, istr, it + c);
-        uint32_t q = 0u, e = 0u;
-        bool whole = direct;
-        if (!direct) {
-            const uint32_t b = pc / bs;
-            q = pc - b * bs;
-            if (b != cur) { const CbgBlock &K = look(b); s = work + K.stage_off; bsize = K.bsize; nel = bsize / TS; cur = b; }
-            if (KIND == CBG_COPY) whole = q + TS <= bsize;
-            else { e = q / TS; whole = e * TS == q && e < nel; }
-        }
-#pragma unroll
-        for (uint32_t j = 0; j < TS; j++) {
-            const uint32_t i = c * TS + j;
-            const uint8_t v = direct ? F.frame[16u + (size_t)pc + j] : !whole ? cbg_byte<KIND>(F, look, work, pc + j) : KIND == CBG_COPY ? s[q + j] : s[(size_t)j * nel + e];
-            w[i >> 2] |= (uint32_t)v << (8u * (i & 3u));
-        }
-    }
-    u32x4 v; v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3];
-    return v;
-}
-// One unit of such a row: items [it, it + cnt) to d, packed.  16 bytes of whole items of a copied or byte-shuffled frame are assembled in
-// registers and stored at once (d has any alignment); the plain body has the row tails, the other typesizes and both bit-shuffle kinds.
-template <int KIND, class LOOK>
-__device__ __forceinline__ void cbi_unit(const CbgFrame &F, const LOOK &look, const uint8_t *__restrict__ work, uint32_t roff, const uint32_t *__restrict__ rt, uint32_t istr,
-                                         uint32_t it, uint32_t cnt, uint8_t *__restrict__ d) {
-    const uint32_t ts = F.typesize;
-    if ((KIND == CBG_COPY || KIND == CBG_UNSHUFFLE) && cnt * ts == 16u) {
-        if (ts == 1u && KIND == CBG_COPY) { st16u(d, cbi_items16<KIND, 1>(F, look, work, roff, rt, istr, it)); return; }      // (one byte is never shuffled)
-        if (ts == 2u) { st16u(d, cbi_items16<KIND, 2>(F, look, work, roff, rt, istr, it)); return; }
-        if (ts == 4u) { st16u(d, cbi_items16<KIND, 4>(F, look, work, roff, rt, istr, it)); return; }
-        if (ts == 8u) { st16u(d, cbi_items16<KIND, 8>(F, look, work, roff, rt, istr, it)); return; }
-        if (ts == 16u) { st16u(d, cbi_items16<KIND, 16>(F, look, work, roff, rt, istr, it)); return; }
-    }
-    for (uint32_t c = 0; c < cnt; c++) {
-        const uint32_t pc = roff + cbi_item(rt, istr, it + c);
-        for (uint32_t j = 0; j < ts; j++) d[c * ts + j] = cbg_byte<KIND>(F, look, work, pc + j);
-    }
+    if (!cbi_thread_rows(W.J, rows[W.i], tab, cbg_unit_bytes(KIND, W.F.typesize), W.wl, threadIdx.x, lo, hi, doff)) return;
+    cbg_unit<KIND>(W.F, W.look, work, lo, hi, W.J.dst + doff);
 }
 // The items gather: the row has a list, or it is stepped while an outer dimension has one.  A thread has 16 bytes of the row's destination
 // (cbi_thread_items) and reads each item's offset from the row's table, or by the row's step.
@@ -780,32 +770,17 @@ __global__ __launch_bounds__(256) void k_cbi_gather_items(const CbgFrame *__rest
                                                            const CbgBlock *__restrict__ blocks, const CbPlan *__restrict__ plans, const CbxTouch *__restrict__ touch,
                                                            const uint32_t *__restrict__ tab, const uint32_t *__restrict__ gjob, const uint32_t *__restrict__ gblk,
                                                            uint32_t nkind, const uint8_t *__restrict__ work) {
-    const uint32_t i = hb_owner(gblk, nkind, blockIdx.x);
-    const CbxJob &J = jobs[gjob[i]];
-    const CbiRow R = rows[i];
-    const CbgFrame &F = frames[J.frame];
-    const CbxTouch *tl = touch + J.tl0;
-    int bad = 0;
-    for (uint32_t k = threadIdx.x; k < J.ntl; k += 256u) bad |= plans[tl[k].rec].fail != 0u;
-    if (__syncthreads_or(bad)) return;
+    const CbxWg W = cbx_enter(frames, jobs, blocks, plans, touch, gjob, gblk, nkind);
+    if (!W.live) return;
+    const CbiRow R = rows[W.i];
     uint32_t it0, cnt, roff;
     uint64_t doff;
-    if (!cbi_thread_items(J, R, tab, F.typesize, blockIdx.x - gblk[i], threadIdx.x, it0, cnt, roff, doff)) return;
-    const CbxLookup look{blocks, tl, J.ntl, J.b_lo, J.dense};
-    const uint32_t *__restrict__ rt = R.tab[3] != CBI_NONE ? tab + R.tab[3] : nullptr;
-    cbi_unit<KIND>(F, look, work, roff, rt, R.istr, it0, cnt, J.dst + doff);
+    if (!cbi_thread_items(W.J, R, tab, W.F.typesize, W.wl, threadIdx.x, it0, cnt, roff, doff)) return;
+    cbr_unit<KIND>(W.F, W.look, work, roff, CbiListed{R.tab[3] != CBI_NONE ? tab + R.tab[3] : nullptr, R.istr, it0}, cnt, W.J.dst + doff);
 }
-// one thread per job: what the host decided, or k_cb_result's record from the OR of the fail words of the blocks the job touches
 __global__ __launch_bounds__(64) void k_cbx_finish(const CbxJob *__restrict__ jobs, const CbPlan *__restrict__ plans, const CbxTouch *__restrict__ touch, hb_result *results,
                                                     uint32_t njobs) {
-    const uint32_t j = blockIdx.x * 64u + threadIdx.x;
-    if (j >= njobs) return;
-    const CbxJob &J = jobs[j];
-    hb_result *r = results + j;
-    if (J.status) { cb_refused_result(r, J.status); return; }
-    CbPlan p; p.fail = 0u;
-    for (uint32_t k = 0; k < J.ntl; k++) p.fail |= plans[touch[J.tl0 + k].rec].fail;
-    cb_result(&p, r, J.bytes);
+    cb_finish_jobs(jobs, plans, results, njobs, &CbxJob::ntl, [touch](const CbxJob &J, uint32_t k) { return touch[J.tl0 + k].rec; });
 }
 
 // =====================================================================================================================
@@ -1355,40 +1330,27 @@ int hb_cblosc_getitem_frames_batch_device(int nframes, const hb_cblosc_header *h
     if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
     uint8_t *w = (uint8_t *)d_work;
-    const size_t nf = (size_t)nframes, nj = (size_t)njobs, nb = (size_t)B.nblk;
     // the records, the prefixes and the cleared plans go up in one copy (the buffer is read before the call returns, as with hb_batch.hip's)
     std::vector<uint8_t> up(L.upload, 0);
-    memcpy(up.data() + L.frames, B.frames.data(), nf * sizeof(CbgFrame));
-    memcpy(up.data() + L.jobs, B.jobs.data(), nj * sizeof(CbgJob));
-    if (nb) {
-        memcpy(up.data() + L.blocks, B.blocks.data(), nb * sizeof(CbgBlock));
-        memcpy(up.data() + L.str0, B.str0.data(), nb * 4);
-    }
-    memcpy(up.data() + L.gjob, B.gjob.data(), nj * 4);
-    memcpy(up.data() + L.gblk, B.gblk.data(), nj * 4);
+    cb_put(up, L.frames, B.frames); cb_put(up, L.jobs, B.jobs); cb_put(up, L.blocks, B.blocks); cb_put(up, L.str0, B.str0);
+    cb_put(up, L.gjob, B.gjob); cb_put(up, L.gblk, B.gblk);
     hb_prof_begin("cbg_upload", s);
     HB_HIP_TRY(hipMemcpyAsync(w, up.data(), L.upload, hipMemcpyHostToDevice, s));
     hb_prof_end(s);
-    const CbgFrame *d_frames = (const CbgFrame *)(w + L.frames);
-    const CbgJob *d_jobs = (const CbgJob *)(w + L.jobs);
-    const CbgBlock *d_blocks = (const CbgBlock *)(w + L.blocks);
-    CbPlan *d_plans = (CbPlan *)(w + L.plans);
-    const uint32_t *d_str0 = (const uint32_t *)(w + L.str0), *d_gjob = (const uint32_t *)(w + L.gjob), *d_gblk = (const uint32_t *)(w + L.gblk);
-    CbStream *d_streams = (CbStream *)(w + L.streams);
+    const CbgFrame *d_frames = cb_at<const CbgFrame>(w, L.frames);
+    const CbgJob *d_jobs = cb_at<const CbgJob>(w, L.jobs);
+    const CbgBlock *d_blocks = cb_at<const CbgBlock>(w, L.blocks);
+    CbPlan *d_plans = cb_at<CbPlan>(w, L.plans);
+    const uint32_t *d_gjob = cb_at<const uint32_t>(w, L.gjob), *d_gblk = cb_at<const uint32_t>(w, L.gblk);
     if (B.nstreams)
-        cbg_launch_decoders((uint32_t)B.nblk, (uint32_t)B.nstreams, B.any_small, B.nsplit_all, B.any_lz4, B.any_blz, d_frames, d_blocks, d_plans, d_str0, d_streams, w, s);
+        cbg_launch_decoders((uint32_t)B.nblk, (uint32_t)B.nstreams, B.any_small, B.nsplit_all, B.any_lz4, B.any_blz, d_frames, d_blocks, d_plans, cb_at<const uint32_t>(w, L.str0),
+                            cb_at<CbStream>(w, L.streams), w, s);
     static const char *const gname[CBG_COUNT] = {"k_cbg_gather_copy", "k_cbg_gather_unshuffle", "k_cbg_gather_bitun", "k_cbg_gather_bitun4"};
-    for (int k = 0; k < CBG_COUNT; k++) {
-        const uint32_t k0 = B.kind0[k], nk = B.kind0[k + 1] - k0, blocks = B.kblocks[k];
-        if (!nk) continue;
-        hb_prof_begin(gname[k], s);
-        cb_with_kind(k, [&](auto K) {                                    // (any other kind: CBG_BITUN4, the last)
-            hipLaunchKernelGGL(k_cbg_gather<K.value>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_blocks, (const CbPlan *)d_plans, d_gjob + k0, d_gblk + k0, nk, (const uint8_t *)w);
-        });
-        hb_prof_end(s);
-    }
+    cb_launch_kinds(B.kind0, B.kblocks, gname, s, [&](auto K, uint32_t k0, uint32_t nk, uint32_t blocks) {
+        hipLaunchKernelGGL(k_cbg_gather<K.value>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_blocks, (const CbPlan *)d_plans, d_gjob + k0, d_gblk + k0, nk, (const uint8_t *)w);
+    });
     hb_prof_begin("k_cbg_finish", s);
-    hipLaunchKernelGGL(k_cbg_finish, dim3((unsigned)((nj + 63) / 64)), dim3(64), 0, s, d_jobs, (const CbPlan *)d_plans, d_results, (uint32_t)njobs);
+    hipLaunchKernelGGL(k_cbg_finish, dim3(((unsigned)njobs + 63u) / 64u), dim3(64), 0, s, d_jobs, (const CbPlan *)d_plans, d_results, (uint32_t)njobs);
     hb_prof_end(s);
     HB_HIP_TRY(hipGetLastError());
     return HB_OK;
@@ -1397,92 +1359,77 @@ int hb_cblosc_getitem_frames_batch_device(int nframes, const hb_cblosc_header *h
 // A prepared batch of boxes, of stepped selections or of index-list selections (CbxBatch) on the device: one upload, the plan and the decoders
 // over the distinct blocks, the gathers -- k_cbx_gather per kind among the jobs with plain rows, k_cbs_gather per kind among those with stepped
 // rows, then k_cbi_gather_rows and k_cbi_gather_items per kind among those with an index list -- and the records.
-static int cbx_launch(const CbxBatch &B, int nframes, int njobs, void *d_work, hb_result *d_results, void *stream) {
+static int cbx_launch(const CbxBatch &B, int njobs, void *d_work, hb_result *d_results, void *stream) {
     const CbxLayout &L = B.L;
     hipStream_t s = (hipStream_t)stream;
     uint8_t *w = (uint8_t *)d_work;
-    const size_t nf = (size_t)nframes, nj = (size_t)njobs, nb = (size_t)B.nblk;
     // the records, the touch lists, the prefixes and the cleared plans go up in one copy (the buffer is read before the call returns)
     std::vector<uint8_t> up(L.upload, 0);
-    memcpy(up.data() + L.frames, B.frames.data(), nf * sizeof(CbgFrame));
-    memcpy(up.data() + L.jobs, B.jobs.data(), nj * sizeof(CbxJob));
-    if (nb) {
-        memcpy(up.data() + L.blocks, B.blocks.data(), nb * sizeof(CbgBlock));
-        memcpy(up.data() + L.str0, B.str0.data(), nb * 4);
-        memcpy(up.data() + L.touch, B.touch.data(), B.touch.size() * sizeof(CbxTouch));
-    }
-    memcpy(up.data() + L.gjob, B.gjob.data(), nj * 4);
-    memcpy(up.data() + L.gblk, B.gblk.data(), nj * 4);
-    if (const size_t ns = B.srow.size()) {
-        memcpy(up.data() + L.srow, B.srow.data(), ns * sizeof(CbsRow));
-        memcpy(up.data() + L.sgjob, B.sgjob.data(), ns * 4);
-        memcpy(up.data() + L.sgblk, B.sgblk.data(), ns * 4);
-    }
-    if (const size_t ni = B.irow.size()) {
-        memcpy(up.data() + L.irow, B.irow.data(), ni * sizeof(CbiRow));
-        memcpy(up.data() + L.igjob, B.igjob.data(), ni * 4);
-        memcpy(up.data() + L.igblk, B.igblk.data(), ni * 4);
-        memcpy(up.data() + L.itab, B.itab.data(), B.itab.size() * 4);
-    }
+    cb_put(up, L.frames, B.frames); cb_put(up, L.jobs, B.jobs); cb_put(up, L.blocks, B.blocks); cb_put(up, L.str0, B.str0); cb_put(up, L.touch, B.touch);
+    cb_put(up, L.gjob, B.gjob); cb_put(up, L.gblk, B.gblk);
+    cb_put(up, L.srow, B.srow); cb_put(up, L.sgjob, B.sgjob); cb_put(up, L.sgblk, B.sgblk);
+    cb_put(up, L.irow, B.irow); cb_put(up, L.igjob, B.igjob); cb_put(up, L.igblk, B.igblk); cb_put(up, L.itab, B.itab);
     hb_prof_begin("cbx_upload", s);
     HB_HIP_TRY(hipMemcpyAsync(w, up.data(), L.upload, hipMemcpyHostToDevice, s));
     hb_prof_end(s);
-    const CbgFrame *d_frames = (const CbgFrame *)(w + L.frames);
-    const CbxJob *d_jobs = (const CbxJob *)(w + L.jobs);
-    const CbgBlock *d_blocks = (const CbgBlock *)(w + L.blocks);
-    CbPlan *d_plans = (CbPlan *)(w + L.plans);
-    const CbxTouch *d_touch = (const CbxTouch *)(w + L.touch);
-    const uint32_t *d_str0 = (const uint32_t *)(w + L.str0), *d_gjob = (const uint32_t *)(w + L.gjob), *d_gblk = (const uint32_t *)(w + L.gblk);
-    CbStream *d_streams = (CbStream *)(w + L.streams);
+    const CbgFrame *d_frames = cb_at<const CbgFrame>(w, L.frames);
+    const CbxJob *d_jobs = cb_at<const CbxJob>(w, L.jobs);
+    const CbgBlock *d_blocks = cb_at<const CbgBlock>(w, L.blocks);
+    CbPlan *d_plans = cb_at<CbPlan>(w, L.plans);
+    const CbxTouch *d_touch = cb_at<const CbxTouch>(w, L.touch);
     if (B.nstreams)
-        cbg_launch_decoders((uint32_t)B.nblk, (uint32_t)B.nstreams, B.any_small, B.nsplit_all, B.any_lz4, B.any_blz, d_frames, d_blocks, d_plans, d_str0, d_streams, w, s);
+        cbg_launch_decoders((uint32_t)B.nblk, (uint32_t)B.nstreams, B.any_small, B.nsplit_all, B.any_lz4, B.any_blz, d_frames, d_blocks, d_plans, cb_at<const uint32_t>(w, L.str0),
+                            cb_at<CbStream>(w, L.streams), w, s);
+    const uint32_t *d_gjob = cb_at<const uint32_t>(w, L.gjob), *d_gblk = cb_at<const uint32_t>(w, L.gblk);
     static const char *const gname[CBG_COUNT] = {"k_cbx_gather_copy", "k_cbx_gather_unshuffle", "k_cbx_gather_bitun", "k_cbx_gather_bitun4"};
-    for (int k = 0; k < CBG_COUNT; k++) {
-        const uint32_t k0 = B.kind0[k], nk = B.kind0[k + 1] - k0, blocks = B.kblocks[k];
-        if (!nk) continue;
-        hb_prof_begin(gname[k], s);
-        cb_with_kind(k, [&](auto K) {                                    // (any other kind: CBG_BITUN4, the last)
-            hipLaunchKernelGGL(k_cbx_gather<K.value>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_blocks, (const CbPlan *)d_plans, d_touch, d_gjob + k0, d_gblk + k0, nk,
-                               (const uint8_t *)w);
-        });
-        hb_prof_end(s);
-    }
-    const CbsRow *d_srow = (const CbsRow *)(w + L.srow);
-    const uint32_t *d_sgjob = (const uint32_t *)(w + L.sgjob), *d_sgblk = (const uint32_t *)(w + L.sgblk);
+    cb_launch_kinds(B.kind0, B.kblocks, gname, s, [&](auto K, uint32_t k0, uint32_t nk, uint32_t blocks) {
+        hipLaunchKernelGGL(k_cbx_gather<K.value>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_blocks, (const CbPlan *)d_plans, d_touch, d_gjob + k0, d_gblk + k0, nk,
+                           (const uint8_t *)w);
+    });
+    const CbsRow *d_srow = cb_at<const CbsRow>(w, L.srow);
+    const uint32_t *d_sgjob = cb_at<const uint32_t>(w, L.sgjob), *d_sgblk = cb_at<const uint32_t>(w, L.sgblk);
     static const char *const sname[CBG_COUNT] = {"k_cbs_gather_copy", "k_cbs_gather_unshuffle", "k_cbs_gather_bitun", "k_cbs_gather_bitun4"};
-    for (int k = 0; k < CBG_COUNT; k++) {
-        const uint32_t k0 = B.skind0[k], nk = B.skind0[k + 1] - k0, blocks = B.skblocks[k];
-        if (!nk) continue;
-        hb_prof_begin(sname[k], s);
-        cb_with_kind(k, [&](auto K) {                                    // (any other kind: CBG_BITUN4, the last)
-            hipLaunchKernelGGL(k_cbs_gather<K.value>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_srow + k0, d_blocks, (const CbPlan *)d_plans, d_touch, d_sgjob + k0,
-                               d_sgblk + k0, nk, (const uint8_t *)w);
-        });
-        hb_prof_end(s);
-    }
-    const CbiRow *d_irow = (const CbiRow *)(w + L.irow);
-    const uint32_t *d_igjob = (const uint32_t *)(w + L.igjob), *d_igblk = (const uint32_t *)(w + L.igblk), *d_itab = (const uint32_t *)(w + L.itab);
+    cb_launch_kinds(B.skind0, B.skblocks, sname, s, [&](auto K, uint32_t k0, uint32_t nk, uint32_t blocks) {
+        hipLaunchKernelGGL(k_cbs_gather<cbr_items_kind(K.value)>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_srow + k0, d_blocks, (const CbPlan *)d_plans, d_touch,
+                           d_sgjob + k0, d_sgblk + k0, nk, (const uint8_t *)w);
+    });
+    // (the index jobs' launch list: the rows gather's kinds, then the items gather's)
+    const CbiRow *d_irow = cb_at<const CbiRow>(w, L.irow);
+    const uint32_t *d_igjob = cb_at<const uint32_t>(w, L.igjob), *d_igblk = cb_at<const uint32_t>(w, L.igblk), *d_itab = cb_at<const uint32_t>(w, L.itab);
     static const char *const iname[2 * CBG_COUNT] = {"k_cbi_gather_rows_copy",  "k_cbi_gather_rows_unshuffle",  "k_cbi_gather_rows_bitun",  "k_cbi_gather_rows_bitun4",
                                                      "k_cbi_gather_items_copy", "k_cbi_gather_items_unshuffle", "k_cbi_gather_items_bitun", "k_cbi_gather_items_bitun4"};
-    for (int l = 0; l < 2 * CBG_COUNT; l++) {
-        const uint32_t k0 = B.ikind0[l], nk = B.ikind0[l + 1] - k0, blocks = B.ikblocks[l];
-        if (!nk) continue;
-        hb_prof_begin(iname[l], s);
-        cb_with_kind(l % CBG_COUNT, [&](auto K) {                        // (any other kind: CBG_BITUN4, the last)
-            if (l < CBG_COUNT)
-                hipLaunchKernelGGL(k_cbi_gather_rows<K.value>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_irow + k0, d_blocks, (const CbPlan *)d_plans, d_touch, d_itab,
-                                   d_igjob + k0, d_igblk + k0, nk, (const uint8_t *)w);
-            else
-                hipLaunchKernelGGL(k_cbi_gather_items<K.value>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_irow + k0, d_blocks, (const CbPlan *)d_plans, d_touch, d_itab,
-                                   d_igjob + k0, d_igblk + k0, nk, (const uint8_t *)w);
-        });
-        hb_prof_end(s);
-    }
+    cb_launch_kinds(B.ikind0, B.ikblocks, iname, s, [&](auto K, uint32_t k0, uint32_t nk, uint32_t blocks) {
+        hipLaunchKernelGGL(k_cbi_gather_rows<K.value>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_irow + k0, d_blocks, (const CbPlan *)d_plans, d_touch, d_itab, d_igjob + k0,
+                           d_igblk + k0, nk, (const uint8_t *)w);
+    });
+    cb_launch_kinds(B.ikind0 + CBG_COUNT, B.ikblocks + CBG_COUNT, iname + CBG_COUNT, s, [&](auto K, uint32_t k0, uint32_t nk, uint32_t blocks) {
+        hipLaunchKernelGGL(k_cbi_gather_items<cbr_items_kind(K.value)>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_irow + k0, d_blocks, (const CbPlan *)d_plans, d_touch, d_itab,
+                           d_igjob + k0, d_igblk + k0, nk, (const uint8_t *)w);
+    });
     hb_prof_begin("k_cbx_finish", s);
-    hipLaunchKernelGGL(k_cbx_finish, dim3((unsigned)((nj + 63) / 64)), dim3(64), 0, s, d_jobs, (const CbPlan *)d_plans, d_touch, d_results, (uint32_t)njobs);
+    hipLaunchKernelGGL(k_cbx_finish, dim3(((unsigned)njobs + 63u) / 64u), dim3(64), 0, s, d_jobs, (const CbPlan *)d_plans, d_touch, d_results, (uint32_t)njobs);
     hb_prof_end(s);
     HB_HIP_TRY(hipGetLastError());
     return HB_OK;
+}
+// The three N-d `_device` calls: bad argument, then what `prepare` says, then short buffer, then no device; and the launches.  `prepare` fills
+// the batch, `workspace` is the call's own size query.
+extern "C++" {
+template <class PREPARE, class WORKSPACE>
+static int cbx_device_call(int nframes, int njobs, bool have_all, void *d_work, size_t work_bytes, hb_result *d_results, void *stream, PREPARE prepare,
+                           WORKSPACE workspace) {
+    if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
+    if (njobs == 0) return HB_OK;
+    if (!have_all || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
+    CbxBatch B;
+    const unsigned accept = hb_cblosc_accepted();
+    const int rc = prepare(B, accept);
+    if (rc) return rc;
+    // (the query knows no capacities and no pointers: where a job was refused for one of them it has counted blocks that this batch leaves out)
+    if (work_bytes < (B.ptr_refusals ? workspace(accept) : B.L.total)) return HB_ERR_SHORT_BUFFER;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    return cbx_launch(B, njobs, d_work, d_results, stream);
+}
 }
 
 // ---- many boxes of many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_box_batch.h) ----
@@ -1492,17 +1439,10 @@ size_t hb_cblosc_getbox_frames_batch_workspace(int nframes, const hb_cblosc_head
 
 int hb_cblosc_getbox_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_cblosc_box_job *jobs,
                                          void *const *d_dst, const size_t *cap, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
-    if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
-    if (njobs == 0) return HB_OK;
-    if (!hdrs || !d_frame || !n || !jobs || !d_dst || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
-    CbxBatch B;
-    const unsigned accept = hb_cblosc_accepted();
-    const int rc = cbx_prepare(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, true, B, accept);
-    if (rc) return rc;
-    // (the query knows no capacities and no pointers: where a job was refused for one of them it has counted blocks that this batch leaves out)
-    if (work_bytes < (B.ptr_refusals ? cbx_workspace(nframes, hdrs, n, njobs, jobs, accept) : B.L.total)) return HB_ERR_SHORT_BUFFER;
-    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
-    return cbx_launch(B, nframes, njobs, d_work, d_results, stream);
+    return cbx_device_call(
+        nframes, njobs, hdrs && d_frame && n && jobs && d_dst && cap, d_work, work_bytes, d_results, stream,
+        [&](CbxBatch &B, unsigned accept) { return cbx_prepare(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, true, B, accept); },
+        [&](unsigned accept) { return cbx_workspace(nframes, hdrs, n, njobs, jobs, accept); });
 }
 
 // ---- many stepped selections of many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_slice_batch.h) ----
@@ -1512,16 +1452,10 @@ size_t hb_cblosc_getslice_frames_batch_workspace(int nframes, const hb_cblosc_he
 
 int hb_cblosc_getslice_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_cblosc_slice_job *jobs,
                                            void *const *d_dst, const size_t *cap, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
-    if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
-    if (njobs == 0) return HB_OK;
-    if (!hdrs || !d_frame || !n || !jobs || !d_dst || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
-    CbxBatch B;
-    const unsigned accept = hb_cblosc_accepted();
-    const int rc = cbs_prepare(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, true, B, accept);
-    if (rc) return rc;
-    if (work_bytes < (B.ptr_refusals ? cbs_workspace(nframes, hdrs, n, njobs, jobs, accept) : B.L.total)) return HB_ERR_SHORT_BUFFER;
-    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
-    return cbx_launch(B, nframes, njobs, d_work, d_results, stream);
+    return cbx_device_call(
+        nframes, njobs, hdrs && d_frame && n && jobs && d_dst && cap, d_work, work_bytes, d_results, stream,
+        [&](CbxBatch &B, unsigned accept) { return cbs_prepare(nframes, hdrs, d_frame, n, njobs, jobs, d_dst, cap, true, B, accept); },
+        [&](unsigned accept) { return cbs_workspace(nframes, hdrs, n, njobs, jobs, accept); });
 }
 
 // ---- many orthogonal selections of many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_index_batch.h) ----
@@ -1533,16 +1467,10 @@ size_t hb_cblosc_getindex_frames_batch_workspace(int nframes, const hb_cblosc_he
 int hb_cblosc_getindex_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_cblosc_index_job *jobs,
                                            const int64_t *index, int64_t nindex, void *const *d_dst, const size_t *cap, void *d_work, size_t work_bytes, hb_result *d_results,
                                            void *stream) {
-    if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
-    if (njobs == 0) return HB_OK;
-    if (!hdrs || !d_frame || !n || !jobs || !d_dst || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
-    CbxBatch B;
-    const unsigned accept = hb_cblosc_accepted();
-    const int rc = cbi_prepare(nframes, hdrs, d_frame, n, njobs, jobs, index, nindex, d_dst, cap, true, B, accept);
-    if (rc) return rc;
-    if (work_bytes < (B.ptr_refusals ? cbi_workspace(nframes, hdrs, n, njobs, jobs, index, nindex, accept) : B.L.total)) return HB_ERR_SHORT_BUFFER;
-    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
-    return cbx_launch(B, nframes, njobs, d_work, d_results, stream);
+    return cbx_device_call(
+        nframes, njobs, hdrs && d_frame && n && jobs && d_dst && cap, d_work, work_bytes, d_results, stream,
+        [&](CbxBatch &B, unsigned accept) { return cbi_prepare(nframes, hdrs, d_frame, n, njobs, jobs, index, nindex, d_dst, cap, true, B, accept); },
+        [&](unsigned accept) { return cbi_workspace(nframes, hdrs, n, njobs, jobs, index, nindex, accept); });
 }
 
 size_t hb_cblosc_bound(size_t n, int typesize) {

@@ -8,6 +8,7 @@ the MI355X through libhipblosc.so; there is no CPU fallback — importing works 
 ctypes only: no torch types cross the boundary (device pointers are plain integers).
 """
 import ctypes
+import itertools
 import os
 from dataclasses import dataclass
 
@@ -328,6 +329,62 @@ def _buf(b):
     return ctypes.cast(arr, ctypes.c_void_p), len(mv), arr
 
 
+# ---- what the batch wrappers share ----
+def _frame_arrays(frames, absent_ok=False):
+    """(pointers, sizes, keepalives) of the frames of a batch, the arrays with one slot at least; absent_ok: None, a chunk the store does not
+    have, goes as an empty frame (no job may read it)"""
+    keep = [_buf(b"" if f is None and absent_ok else f) for f in frames]
+    nf = max(len(keep), 1)
+    return (ctypes.c_void_p * nf)(*[k[0].value for k in keep]), (ctypes.c_size_t * nf)(*[k[1] for k in keep]), keep
+
+
+def _typesize_of(keep, nf, f):
+    """byte 3 of frame f's header (both formats keep the typesize there; 0 counts as 1), or 1 where there is no such frame or header"""
+    return (bytes(keep[f][2][3:4])[0] or 1) if 0 <= f < nf and keep[f][1] >= 16 else 1
+
+
+def _c_strides(counts, itemsize):
+    """the C-order byte strides of an array of `counts` items of `itemsize` bytes (a count below 0 is 0), and the array's bytes"""
+    strides, nbytes = [], int(itemsize)
+    for m in reversed([max(int(v), 0) for v in counts]):
+        strides.insert(0, nbytes)
+        nbytes *= m
+    return strides, nbytes
+
+
+def _out_buffers(caps):
+    """a buffer of caps[i] bytes (one at least) per job; the arrays of their addresses and of the capacities, and one for the jobs' codes"""
+    n = len(caps)
+    outs = [(ctypes.c_char * max(c, 1))() for c in caps]
+    return outs, (ctypes.c_void_p * n)(*[ctypes.addressof(o) for o in outs]), (ctypes.c_size_t * n)(*caps), (ctypes.c_int64 * n)()
+
+
+def _results(outs, rcs):
+    """per job its bytes, or its error as an object (returned, not raised)"""
+    return [bytes(o[:rc]) if rc >= 0 else _BY_CODE.get(int(rc), HipBloscError)(f"code {rc}") for o, rc in zip(outs, rcs)]
+
+
+def _odometer(spans):
+    """every index vector of an N-d grid in C order (the last dimension fastest); spans[k] is a range, or a count for range(count).  One empty
+    vector for no dimensions, none where a dimension is empty."""
+    return itertools.product(*[v if hasattr(v, "__iter__") else range(v) for v in spans])
+
+
+def _read_into(call, frames, pairs, out, dev, index=None, absent_ok=False):
+    """The jobs `pairs` -- (job record, byte offset into `out`) -- through the one batch call `call`, each writing at its offset with the rest of
+    `out` as its capacity; `index`: the index array of an index batch.  Raises the first job's error."""
+    nj, base, total = len(pairs), ctypes.addressof(out), len(out)
+    fr, ns, keep = _frame_arrays(frames, absent_ok)
+    jt = (type(pairs[0][0]) * nj)(*[p[0] for p in pairs])
+    dsts = (ctypes.c_void_p * nj)(*[base + off for _, off in pairs])
+    caps = (ctypes.c_size_t * nj)(*[total - off for _, off in pairs])
+    rcs = (ctypes.c_int64 * nj)()
+    lists = () if index is None else ((ctypes.c_int64 * max(len(index), 1))(*index), len(index))
+    _check(call(len(frames), fr, ns, nj, jt, *lists, dsts, caps, rcs, device if dev is None else dev))
+    for rc in rcs:
+        _check(int(rc))
+
+
 # ---------------------------------------------------------------------------------------------
 # Header / Options, blosc.go:154-245
 # ---------------------------------------------------------------------------------------------
@@ -446,21 +503,11 @@ def GetItemBatch(frames, jobs, typeSize=0, dev=None):
     nj, nf = len(jobs), len(frames)
     if nj == 0:
         return []
-    keep = [_buf(f) for f in frames]
-    caps = []
-    for f, start, nitems in jobs:
-        ts = typeSize if typeSize > 0 else 1
-        if typeSize <= 0 and 0 <= f < nf and keep[f][1] >= HeaderSize:
-            ts = bytes(keep[f][2][3:4])[0] or 1
-        caps.append(max(int(nitems), 0) * ts)
-    outs = [(ctypes.c_char * max(c, 1))() for c in caps]
+    fr, ns, keep = _frame_arrays(frames)
+    outs, dsts, caps, rcs = _out_buffers([max(int(k), 0) * (typeSize if typeSize > 0 else _typesize_of(keep, nf, f)) for f, _, k in jobs])
     jt = (hb_getitem_job * nj)(*[hb_getitem_job(int(f), 0, int(s), int(k)) for f, s, k in jobs])
-    fr = (ctypes.c_void_p * max(nf, 1))(*[k[0].value for k in keep])
-    ns = (ctypes.c_size_t * max(nf, 1))(*[k[1] for k in keep])
-    dsts = (ctypes.c_void_p * nj)(*[ctypes.addressof(o) for o in outs])
-    rcs = (ctypes.c_int64 * nj)()
-    _check(lib().hb_getitem_frames_batch(nf, fr, ns, nj, jt, dsts, (ctypes.c_size_t * nj)(*caps), rcs, None, int(typeSize), device if dev is None else dev))
-    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(nj)]
+    _check(lib().hb_getitem_frames_batch(nf, fr, ns, nj, jt, dsts, caps, rcs, None, int(typeSize), device if dev is None else dev))
+    return _results(outs, rcs)
 
 
 def GetInfo(data):                                                  # blosc.go:306-308
@@ -662,18 +709,14 @@ def CBloscDecompressBatch(frames, dev=None):
     if n == 0:
         return []
     L = lib()
-    keep = [_buf(f) for f in frames]
-    caps = []
+    srcs, ns, keep = _frame_arrays(frames)
+    sizes = []
     for p, k, _ in keep:
         h = CBloscHeader()
-        caps.append(h.nbytes if L.hb_cblosc_parse_header(p, k, ctypes.byref(h)) == 0 else 0)
-    outs = [(ctypes.c_char * max(c, 1))() for c in caps]
-    vp, sz, i64 = ctypes.c_void_p * n, ctypes.c_size_t * n, ctypes.c_int64 * n
-    srcs = vp(*[k[0].value for k in keep])
-    dsts = vp(*[ctypes.addressof(o) for o in outs])
-    rcs = i64()
-    _check(L.hb_cblosc_decompress_frames_batch(n, srcs, sz(*[k[1] for k in keep]), dsts, sz(*caps), rcs, device if dev is None else dev))
-    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(n)]
+        sizes.append(h.nbytes if L.hb_cblosc_parse_header(p, k, ctypes.byref(h)) == 0 else 0)
+    outs, dsts, caps, rcs = _out_buffers(sizes)
+    _check(L.hb_cblosc_decompress_frames_batch(n, srcs, ns, dsts, caps, rcs, device if dev is None else dev))
+    return _results(outs, rcs)
 
 
 def CBloscGetItem(frame, start, nitems):
@@ -695,25 +738,11 @@ def CBloscGetItemBatch(frames, jobs, dev=None):
     nj, nf = len(jobs), len(frames)
     if nj == 0:
         return []
-    keep = [_buf(f) for f in frames]
-    caps = []
-    for f, start, nitems in jobs:
-        ts = 1
-        if 0 <= f < nf and keep[f][1] >= 16:
-            ts = bytes(keep[f][2][3:4])[0] or 1
-        caps.append(max(int(nitems), 0) * ts)
-    outs = [(ctypes.c_char * max(c, 1))() for c in caps]
+    fr, ns, keep = _frame_arrays(frames)
+    outs, dsts, caps, rcs = _out_buffers([max(int(k), 0) * _typesize_of(keep, nf, f) for f, _, k in jobs])
     jt = (hb_getitem_job * nj)(*[hb_getitem_job(int(f), 0, int(s), int(k)) for f, s, k in jobs])
-    fr = (ctypes.c_void_p * max(nf, 1))(*[k[0].value for k in keep])
-    ns = (ctypes.c_size_t * max(nf, 1))(*[k[1] for k in keep])
-    dsts = (ctypes.c_void_p * nj)(*[ctypes.addressof(o) for o in outs])
-    rcs = (ctypes.c_int64 * nj)()
-    _check(lib().hb_cblosc_getitem_frames_batch(nf, fr, ns, nj, jt, dsts, (ctypes.c_size_t * nj)(*caps), rcs, device if dev is None else dev))
-    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(nj)]
-
-
-def _typesize_of(keep, nf, f):
-    return (bytes(keep[f][2][3:4])[0] or 1) if 0 <= f < nf and keep[f][1] >= 16 else 1
+    _check(lib().hb_cblosc_getitem_frames_batch(nf, fr, ns, nj, jt, dsts, caps, rcs, device if dev is None else dev))
+    return _results(outs, rcs)
 
 
 def CBloscGetBoxBatch(frames, jobs, dev=None):
@@ -725,23 +754,31 @@ def CBloscGetBoxBatch(frames, jobs, dev=None):
     nj, nf = len(jobs), len(frames)
     if nj == 0:
         return []
-    keep = [_buf(f) for f in frames]
-    jt, caps = (hb_cblosc_box_job * nj)(), []
+    fr, ns, keep = _frame_arrays(frames)
+    jt, sizes = (hb_cblosc_box_job * nj)(), []
     for j, (f, chunk_shape, start, shape) in enumerate(jobs):
-        ts = _typesize_of(keep, nf, f)
-        strides, nbytes = [], ts
-        for m in reversed([max(int(v), 0) for v in shape]):
-            strides.insert(0, nbytes)
-            nbytes *= m
+        strides, nbytes = _c_strides(shape, _typesize_of(keep, nf, f))
         jt[j] = box_job(f, chunk_shape, start, shape, strides)
-        caps.append(nbytes)
-    outs = [(ctypes.c_char * max(c, 1))() for c in caps]
-    fr = (ctypes.c_void_p * max(nf, 1))(*[k[0].value for k in keep])
-    ns = (ctypes.c_size_t * max(nf, 1))(*[k[1] for k in keep])
-    dsts = (ctypes.c_void_p * nj)(*[ctypes.addressof(o) for o in outs])
-    rcs = (ctypes.c_int64 * nj)()
-    _check(lib().hb_cblosc_getbox_frames_batch(nf, fr, ns, nj, jt, dsts, (ctypes.c_size_t * nj)(*caps), rcs, device if dev is None else dev))
-    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(nj)]
+        sizes.append(nbytes)
+    outs, dsts, caps, rcs = _out_buffers(sizes)
+    _check(lib().hb_cblosc_getbox_frames_batch(nf, fr, ns, nj, jt, dsts, caps, rcs, device if dev is None else dev))
+    return _results(outs, rcs)
+
+
+def _region_chunks(grid_shape, chunk_shape, region, strides):
+    """(grid index in C order, start inside the chunk, shape, byte offset into a C-order array of the region's shape with `strides`) of the
+    part of `region` -- a (lo, hi) pair per dimension -- in every chunk it crosses; nothing for an empty region"""
+    if not all(hi > lo for lo, hi in region):
+        return
+    for idx in _odometer([range(lo // c, (hi - 1) // c + 1) for (lo, hi), c in zip(region, chunk_shape)]):
+        f, start, shape, off = 0, [], [], 0
+        for k, i in enumerate(idx):
+            f = f * grid_shape[k] + i
+            a, b = max(region[k][0], i * chunk_shape[k]), min(region[k][1], (i + 1) * chunk_shape[k])
+            start.append(a - i * chunk_shape[k])
+            shape.append(b - a)
+            off += (a - region[k][0]) * strides[k]
+        yield f, start, shape, off
 
 
 def region_jobs(grid_shape, chunk_shape, region, typesize):
@@ -754,33 +791,8 @@ def region_jobs(grid_shape, chunk_shape, region, typesize):
     out_shape = [hi - lo for lo, hi in region]
     if any(lo < 0 or hi < lo or hi > g * c for (lo, hi), g, c in zip(region, grid_shape, chunk_shape)):
         raise ValueError("the region lies outside the array")
-    strides, acc = [], int(typesize)
-    for m in reversed(out_shape):
-        strides.insert(0, acc)
-        acc *= m
-    jobs = []
-    if all(out_shape):
-        spans = [range(lo // c, (hi - 1) // c + 1) for (lo, hi), c in zip(region, chunk_shape)]
-        idx = [r.start for r in spans]
-        while True:
-            f, start, shape, off = 0, [], [], 0
-            for k in range(nd):
-                f = f * grid_shape[k] + idx[k]
-                a, b = max(region[k][0], idx[k] * chunk_shape[k]), min(region[k][1], (idx[k] + 1) * chunk_shape[k])
-                start.append(a - idx[k] * chunk_shape[k])
-                shape.append(b - a)
-                off += (a - region[k][0]) * strides[k]
-            jobs.append((box_job(f, chunk_shape, start, shape, strides), off))
-            k = nd - 1
-            while k >= 0:
-                idx[k] += 1
-                if idx[k] < spans[k].stop:
-                    break
-                idx[k] = spans[k].start
-                k -= 1
-            if k < 0:
-                break
-    return jobs, out_shape
+    strides, _ = _c_strides(out_shape, typesize)
+    return [(box_job(f, chunk_shape, start, shape, strides), off) for f, start, shape, off in _region_chunks(grid_shape, chunk_shape, region, strides)], out_shape
 
 
 def CBloscReadRegion(frames, grid_shape, chunk_shape, region, typesize, dev=None):
@@ -788,24 +800,10 @@ def CBloscReadRegion(frames, grid_shape, chunk_shape, region, typesize, dev=None
     `grid_shape`, every chunk `chunk_shape` items of `typesize` bytes: one box job per chunk the region crosses (region_jobs), all of them
     through one hb_cblosc_getbox_frames_batch call into one output array.  Returns the region's bytes in C order; raises the first job's error."""
     pairs, out_shape = region_jobs(grid_shape, chunk_shape, region, typesize)
-    total = int(typesize)
-    for m in out_shape:
-        total *= m
-    nj, nf = len(pairs), len(frames)
-    if nj == 0:
+    if not pairs:
         return b""
-    out = (ctypes.c_char * total)()
-    base = ctypes.addressof(out)
-    keep = [_buf(f) for f in frames]
-    jt = (hb_cblosc_box_job * nj)(*[p[0] for p in pairs])
-    fr = (ctypes.c_void_p * max(nf, 1))(*[k[0].value for k in keep])
-    ns = (ctypes.c_size_t * max(nf, 1))(*[k[1] for k in keep])
-    dsts = (ctypes.c_void_p * nj)(*[base + off for _, off in pairs])
-    caps = (ctypes.c_size_t * nj)(*[total - off for _, off in pairs])
-    rcs = (ctypes.c_int64 * nj)()
-    _check(lib().hb_cblosc_getbox_frames_batch(nf, fr, ns, nj, jt, dsts, caps, rcs, device if dev is None else dev))
-    for rc in rcs:
-        _check(int(rc))
+    out = (ctypes.c_char * _c_strides(out_shape, typesize)[1])()
+    _read_into(lib().hb_cblosc_getbox_frames_batch, frames, pairs, out, dev)
     return bytes(out)
 
 
@@ -818,23 +816,36 @@ def CBloscGetSliceBatch(frames, jobs, dev=None):
     nj, nf = len(jobs), len(frames)
     if nj == 0:
         return []
-    keep = [_buf(f) for f in frames]
-    jt, caps = (hb_cblosc_slice_job * nj)(), []
+    fr, ns, keep = _frame_arrays(frames)
+    jt, sizes = (hb_cblosc_slice_job * nj)(), []
     for j, (f, chunk_shape, start, count, step) in enumerate(jobs):
-        ts = _typesize_of(keep, nf, f)
-        strides, nbytes = [], ts
-        for m in reversed([max(int(v), 0) for v in count]):
-            strides.insert(0, nbytes)
-            nbytes *= m
+        strides, nbytes = _c_strides(count, _typesize_of(keep, nf, f))
         jt[j] = slice_job(f, chunk_shape, start, count, step, strides)
-        caps.append(nbytes)
-    outs = [(ctypes.c_char * max(c, 1))() for c in caps]
-    fr = (ctypes.c_void_p * max(nf, 1))(*[k[0].value for k in keep])
-    ns = (ctypes.c_size_t * max(nf, 1))(*[k[1] for k in keep])
-    dsts = (ctypes.c_void_p * nj)(*[ctypes.addressof(o) for o in outs])
-    rcs = (ctypes.c_int64 * nj)()
-    _check(lib().hb_cblosc_getslice_frames_batch(nf, fr, ns, nj, jt, dsts, (ctypes.c_size_t * nj)(*caps), rcs, device if dev is None else dev))
-    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(nj)]
+        sizes.append(nbytes)
+    outs, dsts, caps, rcs = _out_buffers(sizes)
+    _check(lib().hb_cblosc_getslice_frames_batch(nf, fr, ns, nj, jt, dsts, caps, rcs, device if dev is None else dev))
+    return _results(outs, rcs)
+
+
+def _step_parts(lo, st, m, c):
+    """the m indices lo, lo + st ... of a dimension with chunks of c items, cut at the chunks' edges: (chunk index, first output index, start
+    inside the chunk, count) of every chunk that holds one"""
+    parts, i = [], 0
+    while i < m:
+        ch = (lo + i * st) // c
+        cnt = min(m - i, ((ch + 1) * c - 1 - (lo + i * st)) // st + 1)
+        parts.append((ch, i, lo + i * st - ch * c, cnt))
+        i += cnt
+    return parts
+
+
+def _parts_place(parts, grid_shape, strides):
+    """a job that is one such part per dimension: its chunk's grid index in C order, and the byte offset of its first item in the output"""
+    f, off = 0, 0
+    for p, g, s in zip(parts, grid_shape, strides):
+        f = f * g + p[0]
+        off += p[1] * s
+    return f, off
 
 
 def slice_jobs(grid_shape, chunk_shape, slices, typesize):
@@ -848,40 +859,38 @@ def slice_jobs(grid_shape, chunk_shape, slices, typesize):
     if any(lo < 0 or hi < lo or hi > g * c or st < 1 for (lo, hi, st), g, c in zip(slices, grid_shape, chunk_shape)):
         raise ValueError("the slices lie outside the array, or a step is below 1")
     out_shape = [(hi - lo + st - 1) // st for lo, hi, st in slices]
-    strides, acc = [], int(typesize)
-    for m in reversed(out_shape):
-        strides.insert(0, acc)
-        acc *= m
-    # per dimension: (chunk index, first output index, start inside the chunk, count) of every chunk that holds a selected index
-    per = []
-    for (lo, hi, st), c, m in zip(slices, chunk_shape, out_shape):
-        parts, i = [], 0
-        while i < m:
-            ch = (lo + i * st) // c
-            cnt = min(m - i, ((ch + 1) * c - 1 - (lo + i * st)) // st + 1)
-            parts.append((ch, i, lo + i * st - ch * c, cnt))
-            i += cnt
-        per.append(parts)
+    strides, _ = _c_strides(out_shape, typesize)
+    steps = [st for _, _, st in slices]
     jobs = []
-    if all(out_shape):
-        steps = [st for _, _, st in slices]
-        idx = [0] * nd
-        while True:
-            f, off = 0, 0
-            for k in range(nd):
-                f = f * grid_shape[k] + per[k][idx[k]][0]
-                off += per[k][idx[k]][1] * strides[k]
-            jobs.append((slice_job(f, chunk_shape, [per[k][idx[k]][2] for k in range(nd)], [per[k][idx[k]][3] for k in range(nd)], steps, strides), off))
-            k = nd - 1
-            while k >= 0:
-                idx[k] += 1
-                if idx[k] < len(per[k]):
-                    break
-                idx[k] = 0
-                k -= 1
-            if k < 0:
-                break
+    for parts in _odometer([_step_parts(lo, st, m, c) for (lo, _, st), c, m in zip(slices, chunk_shape, out_shape)]):
+        f, off = _parts_place(parts, grid_shape, strides)
+        jobs.append((slice_job(f, chunk_shape, [p[2] for p in parts], [p[3] for p in parts], steps, strides), off))
     return jobs, out_shape
+
+
+def _read_or_fill(call, frames, pairs, out_shape, typesize, fill, dev, index=None):
+    """What CBloscReadSlices and CBloscReadOIndex do with their jobs `pairs`: the part of a chunk that is None in `frames` is `fill`, written
+    here row by row, the other jobs go through the one batch call (_read_into).  Returns the output's bytes."""
+    ts = int(typesize)
+    absent = [p for p in pairs if frames[p[0].frame] is None]
+    if absent:
+        if fill is None:
+            raise ValueError("a selected chunk is absent and there is no fill value")
+        if len(bytes(fill)) != ts:
+            raise ValueError("fill needs typesize bytes")
+    if not pairs:
+        return b""
+    out = (ctypes.c_char * _c_strides(out_shape, ts)[1])()
+    base = ctypes.addressof(out)
+    for job, off in absent:
+        nd = job.ndim
+        row = bytes(fill) * job.count[nd - 1]
+        for outer in _odometer(job.count[: nd - 1]):
+            ctypes.memmove(base + off + sum(i * job.dst_stride[k] for k, i in enumerate(outer)), row, len(row))
+    pairs = [p for p in pairs if frames[p[0].frame] is not None]
+    if pairs:
+        _read_into(call, frames, pairs, out, dev, index, absent_ok=True)
+    return bytes(out)
 
 
 def CBloscReadSlices(frames, grid_shape, chunk_shape, slices, typesize, fill=None, dev=None):
@@ -891,49 +900,7 @@ def CBloscReadSlices(frames, grid_shape, chunk_shape, slices, typesize, fill=Non
     such chunk: its part of the output is `fill` (`typesize` bytes), written here, and with fill=None that raises.  Returns the selection's
     bytes in C order; raises the first job's error."""
     pairs, out_shape = slice_jobs(grid_shape, chunk_shape, slices, typesize)
-    ts, total = int(typesize), int(typesize)
-    for m in out_shape:
-        total *= m
-    absent = [p for p in pairs if frames[p[0].frame] is None]
-    if absent:
-        if fill is None:
-            raise ValueError("a selected chunk is absent and there is no fill value")
-        if len(bytes(fill)) != ts:
-            raise ValueError("fill needs typesize bytes")
-    if not pairs:
-        return b""
-    out = (ctypes.c_char * total)()
-    base = ctypes.addressof(out)
-    for job, off in absent:                                               # the rows of an absent chunk's part of the output
-        nd = job.ndim
-        row = bytes(fill) * job.count[nd - 1]
-        outer = [0] * (nd - 1)
-        while True:
-            at = off + sum(i * job.dst_stride[k] for k, i in enumerate(outer))
-            ctypes.memmove(base + at, row, len(row))
-            k = nd - 2
-            while k >= 0:
-                outer[k] += 1
-                if outer[k] < job.count[k]:
-                    break
-                outer[k] = 0
-                k -= 1
-            if k < 0:
-                break
-    pairs = [p for p in pairs if frames[p[0].frame] is not None]
-    nj, nf = len(pairs), len(frames)
-    if nj:
-        keep = [_buf(f if f is not None else b"") for f in frames]
-        jt = (hb_cblosc_slice_job * nj)(*[p[0] for p in pairs])
-        fr = (ctypes.c_void_p * max(nf, 1))(*[k[0].value for k in keep])
-        ns = (ctypes.c_size_t * max(nf, 1))(*[k[1] for k in keep])
-        dsts = (ctypes.c_void_p * nj)(*[base + off for _, off in pairs])
-        caps = (ctypes.c_size_t * nj)(*[total - off for _, off in pairs])
-        rcs = (ctypes.c_int64 * nj)()
-        _check(lib().hb_cblosc_getslice_frames_batch(nf, fr, ns, nj, jt, dsts, caps, rcs, device if dev is None else dev))
-        for rc in rcs:
-            _check(int(rc))
-    return bytes(out)
+    return _read_or_fill(lib().hb_cblosc_getslice_frames_batch, frames, pairs, out_shape, typesize, fill, dev)
 
 
 def _is_triple(sel):
@@ -951,10 +918,9 @@ def CBloscGetIndexBatch(frames, jobs, dev=None):
     nj, nf = len(jobs), len(frames)
     if nj == 0:
         return []
-    keep = [_buf(f) for f in frames]
-    jt, caps, index = (hb_cblosc_index_job * nj)(), [], []
+    fr, ns, keep = _frame_arrays(frames)
+    jt, sizes, index = (hb_cblosc_index_job * nj)(), [], []
     for j, (f, chunk_shape, sel) in enumerate(jobs):
-        ts = _typesize_of(keep, nf, f)
         start, count, step, lists = [], [], [], []
         for s in sel:
             if _is_triple(s):
@@ -963,20 +929,13 @@ def CBloscGetIndexBatch(frames, jobs, dev=None):
                 s = [int(v) for v in s]
                 start.append(0); count.append(len(s)); step.append(1); lists.append(len(index))
                 index.extend(s)
-        strides, nbytes = [], ts
-        for m in reversed([max(int(v), 0) for v in count]):
-            strides.insert(0, nbytes)
-            nbytes *= m
+        strides, nbytes = _c_strides(count, _typesize_of(keep, nf, f))
         jt[j] = index_job(f, chunk_shape, start, count, step, lists, strides)
-        caps.append(nbytes)
-    outs = [(ctypes.c_char * max(c, 1))() for c in caps]
-    fr = (ctypes.c_void_p * max(nf, 1))(*[k[0].value for k in keep])
-    ns = (ctypes.c_size_t * max(nf, 1))(*[k[1] for k in keep])
-    dsts = (ctypes.c_void_p * nj)(*[ctypes.addressof(o) for o in outs])
-    rcs = (ctypes.c_int64 * nj)()
+        sizes.append(nbytes)
+    outs, dsts, caps, rcs = _out_buffers(sizes)
     ix = (ctypes.c_int64 * max(len(index), 1))(*index)
-    _check(lib().hb_cblosc_getindex_frames_batch(nf, fr, ns, nj, jt, ix, len(index), dsts, (ctypes.c_size_t * nj)(*caps), rcs, device if dev is None else dev))
-    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(nj)]
+    _check(lib().hb_cblosc_getindex_frames_batch(nf, fr, ns, nj, jt, ix, len(index), dsts, caps, rcs, device if dev is None else dev))
+    return _results(outs, rcs)
 
 
 def index_jobs(grid_shape, chunk_shape, selection, typesize):
@@ -997,12 +956,8 @@ def index_jobs(grid_shape, chunk_shape, selection, typesize):
             lo, hi, st = (int(v) for v in sel)
             if lo < 0 or hi < lo or hi > g * c or st < 1:
                 raise ValueError("a slice lies outside the array, or its step is below 1")
-            m, i = (hi - lo + st - 1) // st, 0
-            while i < m:
-                ch = (lo + i * st) // c
-                cnt = min(m - i, ((ch + 1) * c - 1 - (lo + i * st)) // st + 1)
-                parts.append((ch, i, lo + i * st - ch * c, cnt, False))
-                i += cnt
+            m = (hi - lo + st - 1) // st
+            parts = [p + (False,) for p in _step_parts(lo, st, m, c)]
             steps.append(st)
         else:
             sel = [int(v) for v in sel]
@@ -1019,29 +974,11 @@ def index_jobs(grid_shape, chunk_shape, selection, typesize):
             steps.append(1)
         per.append(parts)
         out_shape.append(m)
-    strides, acc = [], int(typesize)
-    for m in reversed(out_shape):
-        strides.insert(0, acc)
-        acc *= m
+    strides, _ = _c_strides(out_shape, typesize)
     jobs = []
-    if all(out_shape):
-        idx = [0] * nd
-        while True:
-            f, off = 0, 0
-            for k in range(nd):
-                f = f * grid_shape[k] + per[k][idx[k]][0]
-                off += per[k][idx[k]][1] * strides[k]
-            parts = [per[k][idx[k]] for k in range(nd)]
-            jobs.append((index_job(f, chunk_shape, [0 if p[4] else p[2] for p in parts], [p[3] for p in parts], steps, [p[2] if p[4] else -1 for p in parts], strides), off))
-            k = nd - 1
-            while k >= 0:
-                idx[k] += 1
-                if idx[k] < len(per[k]):
-                    break
-                idx[k] = 0
-                k -= 1
-            if k < 0:
-                break
+    for parts in _odometer(per):
+        f, off = _parts_place(parts, grid_shape, strides)
+        jobs.append((index_job(f, chunk_shape, [0 if p[4] else p[2] for p in parts], [p[3] for p in parts], steps, [p[2] if p[4] else -1 for p in parts], strides), off))
     return jobs, index, out_shape
 
 
@@ -1052,50 +989,7 @@ def CBloscReadOIndex(frames, grid_shape, chunk_shape, selection, typesize, fill=
     `frames` may be None -- the store has no such chunk: its part of the output is `fill` (`typesize` bytes), written here, and with
     fill=None that raises.  Returns the selection's bytes in C order; raises the first job's error."""
     pairs, index, out_shape = index_jobs(grid_shape, chunk_shape, selection, typesize)
-    ts, total = int(typesize), int(typesize)
-    for m in out_shape:
-        total *= m
-    absent = [p for p in pairs if frames[p[0].frame] is None]
-    if absent:
-        if fill is None:
-            raise ValueError("a selected chunk is absent and there is no fill value")
-        if len(bytes(fill)) != ts:
-            raise ValueError("fill needs typesize bytes")
-    if not pairs:
-        return b""
-    out = (ctypes.c_char * total)()
-    base = ctypes.addressof(out)
-    for job, off in absent:                                               # the rows of an absent chunk's part of the output
-        nd = job.ndim
-        row = bytes(fill) * job.count[nd - 1]
-        outer = [0] * (nd - 1)
-        while True:
-            at = off + sum(i * job.dst_stride[k] for k, i in enumerate(outer))
-            ctypes.memmove(base + at, row, len(row))
-            k = nd - 2
-            while k >= 0:
-                outer[k] += 1
-                if outer[k] < job.count[k]:
-                    break
-                outer[k] = 0
-                k -= 1
-            if k < 0:
-                break
-    pairs = [p for p in pairs if frames[p[0].frame] is not None]
-    nj, nf = len(pairs), len(frames)
-    if nj:
-        keep = [_buf(f if f is not None else b"") for f in frames]
-        jt = (hb_cblosc_index_job * nj)(*[p[0] for p in pairs])
-        fr = (ctypes.c_void_p * max(nf, 1))(*[k[0].value for k in keep])
-        ns = (ctypes.c_size_t * max(nf, 1))(*[k[1] for k in keep])
-        dsts = (ctypes.c_void_p * nj)(*[base + off for _, off in pairs])
-        caps = (ctypes.c_size_t * nj)(*[total - off for _, off in pairs])
-        rcs = (ctypes.c_int64 * nj)()
-        ix = (ctypes.c_int64 * max(len(index), 1))(*index)
-        _check(lib().hb_cblosc_getindex_frames_batch(nf, fr, ns, nj, jt, ix, len(index), dsts, caps, rcs, device if dev is None else dev))
-        for rc in rcs:
-            _check(int(rc))
-    return bytes(out)
+    return _read_or_fill(lib().hb_cblosc_getindex_frames_batch, frames, pairs, out_shape, typesize, fill, dev, index)
 
 
 def CBloscCompress(data, shuffle=1, typesize=4):
@@ -1114,15 +1008,10 @@ def CBloscCompressBatch(datas, shuffle=1, typesize=4, dev=None):
     if n == 0:
         return []
     L = lib()
-    keep = [_buf(d) for d in datas]
-    caps = [L.hb_cblosc_bound(k[1], typesize) for k in keep]
-    outs = [(ctypes.c_char * c)() for c in caps]
-    vp, sz, i64 = ctypes.c_void_p * n, ctypes.c_size_t * n, ctypes.c_int64 * n
-    srcs = vp(*[k[0].value for k in keep])
-    dsts = vp(*[ctypes.addressof(o) for o in outs])
-    rcs = i64()
-    _check(L.hb_cblosc_compress_frames_batch(n, srcs, sz(*[k[1] for k in keep]), dsts, sz(*caps), rcs, int(shuffle), int(typesize), device if dev is None else dev))
-    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(n)]
+    srcs, ns, keep = _frame_arrays(datas)
+    outs, dsts, caps, rcs = _out_buffers([L.hb_cblosc_bound(k[1], typesize) for k in keep])
+    _check(L.hb_cblosc_compress_frames_batch(n, srcs, ns, dsts, caps, rcs, int(shuffle), int(typesize), device if dev is None else dev))
+    return _results(outs, rcs)
 
 
 def _chunk_bytes(box, typesize):
@@ -1135,6 +1024,31 @@ def _chunk_bytes(box, typesize):
             return None
         n *= box.chunk_shape[k]
     return n if n < (1 << 31) else None
+
+
+def _box_sources(srcs, boxes, typesize, keep):
+    """the pointer array of the sources of a box batch -- srcs[i] is a bytes-like object (checked: boxes[i] must not reach beyond it; its
+    keepalive is appended to `keep`), an address or None"""
+    ptrs = []
+    for s, b in zip(srcs, boxes):
+        if s is None or isinstance(s, int):
+            ptrs.append(s)
+            continue
+        p, k, kp = _buf(s)
+        keep.append(kp)
+        span, nd = int(typesize), min(b.ndim, 4)
+        if all(b.shape[d] > 0 for d in range(nd)):
+            span += sum((b.shape[d] - 1) * b.src_stride[d] for d in range(nd))
+            if all(b.src_stride[d] >= 0 for d in range(nd)) and span > k:
+                raise ValueError("a box reaches beyond its source")
+        ptrs.append(p.value)
+    return (ctypes.c_void_p * len(ptrs))(*ptrs)
+
+
+def _frame_caps(boxes, typesize):
+    """per box the bound of its chunk's frame; a header's bytes where the library refuses the box before it sizes anything"""
+    sizes = [_chunk_bytes(b, typesize) for b in boxes]
+    return [lib().hb_cblosc_bound(c, typesize) if c is not None else 16 for c in sizes]
 
 
 def CBloscCompressBoxBatch(srcs, boxes, fill=None, shuffle=1, typesize=4, dev=None):
@@ -1150,30 +1064,13 @@ def CBloscCompressBoxBatch(srcs, boxes, fill=None, shuffle=1, typesize=4, dev=No
         raise ValueError("fill needs typesize bytes")
     if n == 0:
         return []
-    L = lib()
-    keep, ptrs = [], []
-    for s, b in zip(srcs, boxes):
-        if s is None or isinstance(s, int):
-            ptrs.append(s)
-            continue
-        p, k, kp = _buf(s)
-        keep.append(kp)
-        span, nd = int(typesize), min(b.ndim, 4)
-        if all(b.shape[d] > 0 for d in range(nd)):
-            span += sum((b.shape[d] - 1) * b.src_stride[d] for d in range(nd))
-            if all(b.src_stride[d] >= 0 for d in range(nd)) and span > k:
-                raise ValueError("a box reaches beyond its source")
-        ptrs.append(p.value)
-    sizes = [_chunk_bytes(b, typesize) for b in boxes]
-    caps = [L.hb_cblosc_bound(c, typesize) if c is not None else 16 for c in sizes]
-    outs = [(ctypes.c_char * c)() for c in caps]
-    vp, sz, i64 = ctypes.c_void_p * n, ctypes.c_size_t * n, ctypes.c_int64 * n
+    keep = []
+    ptrs = _box_sources(srcs, boxes, typesize, keep)
+    outs, dsts, caps, rcs = _out_buffers(_frame_caps(boxes, typesize))
     bt = (hb_cblosc_src_box * n)(*boxes)
-    dsts = vp(*[ctypes.addressof(o) for o in outs])
-    rcs = i64()
     fb = None if fill is None else ctypes.create_string_buffer(bytes(fill), typesize)
-    _check(L.hb_cblosc_compress_boxes_batch(n, bt, vp(*ptrs), dsts, sz(*caps), rcs, fb, int(shuffle), int(typesize), device if dev is None else dev))
-    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(n)]
+    _check(lib().hb_cblosc_compress_boxes_batch(n, bt, ptrs, dsts, caps, rcs, fb, int(shuffle), int(typesize), device if dev is None else dev))
+    return _results(outs, rcs)
 
 
 def array_jobs(array_shape, chunk_shape, typesize):
@@ -1185,26 +1082,11 @@ def array_jobs(array_shape, chunk_shape, typesize):
         raise ValueError("array_shape and chunk_shape need the same number of entries, 1 to 4")
     if any(c < 1 for c in chunk_shape) or any(a < 0 for a in array_shape):
         raise ValueError("chunk_shape needs positive entries, array_shape none below 0")
-    strides, acc = [], int(typesize)
-    for m in reversed(array_shape):
-        strides.insert(0, acc)
-        acc *= m
-    grid = [-(-a // c) for a, c in zip(array_shape, chunk_shape)]
+    strides, _ = _c_strides(array_shape, typesize)
     jobs = []
-    if all(grid):
-        idx = [0] * nd
-        while True:
-            shape = [min(c, a - i * c) for a, c, i in zip(array_shape, chunk_shape, idx)]
-            jobs.append((src_box(chunk_shape, shape, strides), sum(i * c * s for i, c, s in zip(idx, chunk_shape, strides))))
-            k = nd - 1
-            while k >= 0:
-                idx[k] += 1
-                if idx[k] < grid[k]:
-                    break
-                idx[k] = 0
-                k -= 1
-            if k < 0:
-                break
+    for idx in _odometer([-(-a // c) for a, c in zip(array_shape, chunk_shape)]):
+        shape = [min(c, a - i * c) for a, c, i in zip(array_shape, chunk_shape, idx)]
+        jobs.append((src_box(chunk_shape, shape, strides), sum(i * c * s for i, c, s in zip(idx, chunk_shape, strides))))
     return jobs
 
 
@@ -1242,20 +1124,8 @@ def CBloscUpdateBoxBatch(olds, srcs, boxes, fill=None, shuffle=1, typesize=4, de
         raise ValueError("fill needs typesize bytes")
     if n == 0:
         return []
-    L = lib()
-    keep, ptrs, optr, olen = [], [], [], []
-    for s, b in zip(srcs, boxes):
-        if s is None or isinstance(s, int):
-            ptrs.append(s)
-            continue
-        p, k, kp = _buf(s)
-        keep.append(kp)
-        span, nd = int(typesize), min(b.ndim, 4)
-        if all(b.shape[d] > 0 for d in range(nd)):
-            span += sum((b.shape[d] - 1) * b.src_stride[d] for d in range(nd))
-            if all(b.src_stride[d] >= 0 for d in range(nd)) and span > k:
-                raise ValueError("a box reaches beyond its source")
-        ptrs.append(p.value)
+    keep, optr, olen = [], [], []
+    ptrs = _box_sources(srcs, boxes, typesize, keep)
     for o in olds:
         if o is None:
             optr.append(None)
@@ -1265,16 +1135,12 @@ def CBloscUpdateBoxBatch(olds, srcs, boxes, fill=None, shuffle=1, typesize=4, de
         keep.append(kp)
         optr.append(p.value)
         olen.append(k)
-    sizes = [_chunk_bytes(b, typesize) for b in boxes]
-    caps = [L.hb_cblosc_bound(c, typesize) if c is not None else 16 for c in sizes]
-    outs = [(ctypes.c_char * c)() for c in caps]
-    vp, sz, i64 = ctypes.c_void_p * n, ctypes.c_size_t * n, ctypes.c_int64 * n
+    outs, dsts, caps, rcs = _out_buffers(_frame_caps(boxes, typesize))
     bt = (hb_cblosc_upd_box * n)(*boxes)
-    dsts = vp(*[ctypes.addressof(o) for o in outs])
-    rcs = i64()
     fb = None if fill is None else ctypes.create_string_buffer(bytes(fill), typesize)
-    _check(L.hb_cblosc_update_boxes_batch(n, bt, vp(*optr), sz(*olen), vp(*ptrs), dsts, sz(*caps), rcs, fb, int(shuffle), int(typesize), device if dev is None else dev))
-    return [bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}") for i in range(n)]
+    _check(lib().hb_cblosc_update_boxes_batch(n, bt, (ctypes.c_void_p * n)(*optr), (ctypes.c_size_t * n)(*olen), ptrs, dsts, caps, rcs, fb, int(shuffle), int(typesize),
+                                              device if dev is None else dev))
+    return _results(outs, rcs)
 
 
 def update_jobs(array_shape, chunk_shape, region, typesize):
@@ -1291,34 +1157,8 @@ def update_jobs(array_shape, chunk_shape, region, typesize):
     if any(lo < 0 or hi < lo or hi > a for (lo, hi), a in zip(region, array_shape)):
         raise ValueError("the region lies outside the array")
     grid = [-(-a // c) for a, c in zip(array_shape, chunk_shape)]
-    out_shape = [hi - lo for lo, hi in region]
-    strides, acc = [], int(typesize)
-    for m in reversed(out_shape):
-        strides.insert(0, acc)
-        acc *= m
-    jobs = []
-    if all(out_shape):
-        spans = [range(lo // c, (hi - 1) // c + 1) for (lo, hi), c in zip(region, chunk_shape)]
-        idx = [r.start for r in spans]
-        while True:
-            f, start, shape, off = 0, [], [], 0
-            for k in range(nd):
-                f = f * grid[k] + idx[k]
-                a, b = max(region[k][0], idx[k] * chunk_shape[k]), min(region[k][1], (idx[k] + 1) * chunk_shape[k])
-                start.append(a - idx[k] * chunk_shape[k])
-                shape.append(b - a)
-                off += (a - region[k][0]) * strides[k]
-            jobs.append((f, upd_box(chunk_shape, start, shape, strides), off))
-            k = nd - 1
-            while k >= 0:
-                idx[k] += 1
-                if idx[k] < spans[k].stop:
-                    break
-                idx[k] = spans[k].start
-                k -= 1
-            if k < 0:
-                break
-    return jobs
+    strides, _ = _c_strides([hi - lo for lo, hi in region], typesize)
+    return [(f, upd_box(chunk_shape, start, shape, strides), off) for f, start, shape, off in _region_chunks(grid, chunk_shape, region, strides)]
 
 
 def CBloscUpdateRegion(frames, array_shape, chunk_shape, region, data, typesize, shuffle=1, fill=None, dev=None):
@@ -1349,19 +1189,10 @@ def CompressBatch(datas, codec=LZ4, level=5, shuffle=Shuffle1, typesize=4, opts=
     if n == 0:
         return []
     L = lib()
-    keep = [_buf(d) for d in datas]
-    caps = [L.hb_frame_bound(k[1]) for k in keep]
-    outs = [(ctypes.c_char * c)() for c in caps]
-    vp, sz, i64 = ctypes.c_void_p * n, ctypes.c_size_t * n, ctypes.c_int64 * n
-    srcs = vp(*[k[0].value for k in keep])
-    dsts = vp(*[ctypes.addressof(o) for o in outs])
-    rcs = i64()
-    _check(L.hb_compress_frames_batch(n, srcs, sz(*[k[1] for k in keep]), dsts, sz(*caps), rcs, int(codec), int(level), int(shuffle), int(typesize),
-                                      int(opts), device if dev is None else dev))
-    res = []
-    for i in range(n):
-        res.append(bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}"))
-    return res
+    srcs, ns, keep = _frame_arrays(datas)
+    outs, dsts, caps, rcs = _out_buffers([L.hb_frame_bound(k[1]) for k in keep])
+    _check(L.hb_compress_frames_batch(n, srcs, ns, dsts, caps, rcs, int(codec), int(level), int(shuffle), int(typesize), int(opts), device if dev is None else dev))
+    return _results(outs, rcs)
 
 
 def DecompressBatch(frames, typesize=0, dev=None):
@@ -1369,20 +1200,13 @@ def DecompressBatch(frames, typesize=0, dev=None):
     if n == 0:
         return []
     L = lib()
-    keep = [_buf(f) for f in frames]
-    caps = []
+    srcs, ns, keep = _frame_arrays(frames)
+    sizes = []
     for f in frames:
         try:
-            caps.append(max(ParseHeader(bytes(f[:16])).NBytesOrig, 1))
+            sizes.append(max(ParseHeader(bytes(f[:16])).NBytesOrig, 1))
         except BloscError:
-            caps.append(1)
-    outs = [(ctypes.c_char * c)() for c in caps]
-    vp, sz, i64 = ctypes.c_void_p * n, ctypes.c_size_t * n, ctypes.c_int64 * n
-    srcs = vp(*[k[0].value for k in keep])
-    dsts = vp(*[ctypes.addressof(o) for o in outs])
-    rcs = i64()
-    _check(L.hb_decompress_frames_batch(n, srcs, sz(*[k[1] for k in keep]), dsts, sz(*caps), rcs, int(typesize), device if dev is None else dev))
-    res = []
-    for i in range(n):
-        res.append(bytes(outs[i][: rcs[i]]) if rcs[i] >= 0 else _BY_CODE.get(int(rcs[i]), HipBloscError)(f"code {rcs[i]}"))
-    return res
+            sizes.append(1)
+    outs, dsts, caps, rcs = _out_buffers(sizes)
+    _check(L.hb_decompress_frames_batch(n, srcs, ns, dsts, caps, rcs, int(typesize), device if dev is None else dev))
+    return _results(outs, rcs)

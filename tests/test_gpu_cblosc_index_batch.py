@@ -406,6 +406,43 @@ def test_a_blosclz_frame_needs_the_codec_mask(hb):
     assert isinstance(hb.CBloscGetIndexBatch([f], [job])[0], hb.ErrInvalidCodec)
 
 
+def test_both_bit_shuffle_kinds_through_the_two_items_gathers(hb):
+    """The gathers that take a row item by item -- k_cbs_gather for a stepped row, k_cbi_gather_items for a listed one -- have one body for both
+    bit-shuffle kinds, so jobs of kind CBG_BITUN4 (typesize 4, a block size that is a multiple of 512) run the kernel of kind CBG_BITUN, under
+    their own stage names.  The sweeps above pick their typesize-4 bit-shuffled selections at random: none of them is sure to put a stepped and a
+    listed row over whole blocks AND over a last block that was left unfiltered.  Here: 1227 items in blocks of 512 -- two whole blocks and 203
+    items, no multiple of 8 -- once with typesize 4 (CBG_BITUN4) and once with typesize 8 (CBG_BITUN); a row of step 3 that crosses both block
+    boundaries and ends in the short block, and an unsorted list with repeats that holds the first and the last item of every block."""
+    compress = _cblosc()
+    n, per = 1227, 512
+    frames, arrays = [], []
+    for ts in (4, 8):
+        a = _array(np.random.default_rng(40 + ts), (n,), ts, 0)
+        f = _never_split(lambda: compress(a.tobytes(), 5, 2, ts, b"lz4", per * ts))
+        assert f[2] & 0x04 and not f[2] & 0x03 and _geom(f) == (ts, n * ts, per * ts, 3) and (per * ts) % 512 == 0 and (n - 2 * per) % 8
+        frames.append(f)
+        arrays.append(a)
+    stepped = [(1, 409, 3)]                                               # items 1, 4 ... 1225: 511 -> 514, 1024 -> 1027, the last in the short block
+    assert {i // per for i in _coords(stepped)[0]} == {0, 1, 2} and _coords(stepped)[0][-1] == n - 2
+    listed = [[n - 1, 0, per - 1, per, 2 * per - 1, 2 * per, per - 1, 7, n - 1, 600, 2 * per + 1, 3, per]]
+    assert {0, per - 1, per, 2 * per - 1, 2 * per, n - 1} <= set(listed[0]) and listed[0] != sorted(listed[0]) and len(set(listed[0])) < len(listed[0])
+    jobs = [(k, (n,), sel, _strides(_counts(sel), ts, (0,))) for k, ts in enumerate((4, 8)) for sel in (stepped, listed)]
+    wants = [_want(arrays[k], sel) for k, cs, sel, st in jobs]
+    L = hb.lib()
+    with DevIndex(hb, frames, jobs, seed=23) as B:
+        try:
+            L.hb_profile_enable(1)
+            got, rec = B.run()
+            stages = _stages(L)
+        finally:
+            L.hb_profile_enable(0)
+        for j, (k, cs, sel, st) in enumerate(jobs):
+            assert _rec(rec[j]) == (0, 1, wants[j].size, wants[j].size), (j, _rec(rec[j]))
+            assert np.array_equal(got[j], _expected_buffer(wants[j], st, B.cap[j])), (j, jobs[j])
+    assert {"k_cbs_gather_bitun4", "k_cbi_gather_items_bitun4", "k_cbs_gather_bitun", "k_cbi_gather_items_bitun"} <= set(stages), stages
+    assert hb.CBloscGetIndexBatch(frames, [j[:3] for j in jobs]) == [w.tobytes() for w in wants]
+
+
 def test_device_contract_refused_jobs_between_good_ones_and_no_jobs(hb, slabs, chunks):
     f, a = slabs
     other, oa, ocs = chunks[4]
