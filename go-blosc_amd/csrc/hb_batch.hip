@@ -24,6 +24,7 @@
 #include "hb_cblosc_box_batch.h"
 #include "hb_cblosc_slice_batch.h"
 #include "hb_cblosc_index_batch.h"
+#include "hb_cblosc_point_batch.h"
 #include "hb_cblosc_enc_box_batch.h"
 #include "hb_cblosc_upd_box_batch.h"
 #include <vector>
@@ -715,9 +716,13 @@ int hb_cblosc_getitem_frames_batch(int nframes, const void *const *frame, const 
 // the rows are placed at their strides here.  No job is answered row by row.  The stepped selections of hb_cblosc_getslice_frames_batch go the
 // same way with their own plan, query and device form (`plan`, `query`, `run`).
 extern "C++" {
-template <class JOB, class PLAN, class QUERY, class RUN>
+struct CbxPlaceRows {                    // carried job i of the plan: its packed box to the caller's strides
+    template <class PLAN_>
+    void operator()(const PLAN_ &P, size_t i, const uint8_t *packed, uint8_t *dst) const { cbx_place_rows(P.geom[i], packed, dst); }
+};
+template <class JOB, class PLAN, class QUERY, class RUN, class PLACE = CbxPlaceRows>
 static int cbx_host_call(int nframes, const void *const *frame, const size_t *n, int njobs, const JOB *jobs, void *const *dst, const size_t *cap,
-                         int64_t *rc, int device, PLAN plan, QUERY query, RUN run) {
+                         int64_t *rc, int device, PLAN plan, QUERY query, RUN run, PLACE place = PLACE{}) {
     if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
     if (njobs == 0) return HB_OK;
     if (!frame || !n || !jobs || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
@@ -754,7 +759,7 @@ static int cbx_host_call(int nframes, const void *const *frame, const size_t *n,
         const hb_result &r = res[(size_t)i];
         const int j = P.carried[(size_t)i];
         if (r.status != HB_OK) { rc[j] = r.status; continue; }          // (a failed job's destination keeps the caller's bytes)
-        if (r.bytes) cbx_place_rows(P.geom[(size_t)i], host.data() + P.ooff[(size_t)i], (uint8_t *)dst[j]);
+        if (r.bytes) place(P, (size_t)i, host.data() + P.ooff[(size_t)i], (uint8_t *)dst[j]);
         rc[j] = (int64_t)r.bytes;
     }
     return HB_OK;
@@ -783,6 +788,29 @@ int hb_cblosc_getindex_frames_batch(int nframes, const void *const *frame, const
             [&](int nf, const hb_cblosc_header *h, const size_t *nn, int nj, const hb_cblosc_index_job *q) { return hb_cblosc_getindex_frames_batch_workspace(nf, h, nn, nj, q, index, nindex); },
             [&](int nf, const hb_cblosc_header *h, const void *const *f, const size_t *nn, int nj, const hb_cblosc_index_job *q, void *const *d, const size_t *c, void *wk, size_t wb,
                 hb_result *res, void *st) { return hb_cblosc_getindex_frames_batch_device(nf, h, f, nn, nj, q, index, nindex, d, c, wk, wb, res, st); });
+    } catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
+}
+// The jobs of points go the same way: cbp_host_plan packs the carried jobs' points (out = the point's place in its job), the device form runs
+// over those, and the host places every item where the caller's point says.
+int hb_cblosc_getpoints_frames_batch(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_cblosc_point_job *jobs, const hb_cblosc_point *points,
+                                     int64_t npoints, void *const *dst, const size_t *cap, int64_t *rc, int device) {
+    try {
+        if (nframes >= 0 && cbp_call_refused(njobs, jobs, points, npoints)) return HB_ERR_BAD_ARG;
+        std::vector<hb_cblosc_point> packed;
+        return cbx_host_call(
+            nframes, frame, n, njobs, jobs, dst, cap, rc, device,
+            [&](int nf, const void *const *f, const size_t *nn, int nj, const hb_cblosc_point_job *q, void *const *d, const size_t *c, CbpHostPlan &P, unsigned accept) {
+                cbp_host_plan(nf, f, nn, nj, q, points, npoints, d, c, P, packed, accept);
+            },
+            [&](int nf, const hb_cblosc_header *h, const size_t *nn, int nj, const hb_cblosc_point_job *q) {
+                return hb_cblosc_getpoints_frames_batch_workspace(nf, h, nn, nj, q, packed.data(), (int64_t)packed.size());
+            },
+            [&](int nf, const hb_cblosc_header *h, const void *const *f, const size_t *nn, int nj, const hb_cblosc_point_job *q, void *const *d, const size_t *c, void *wk, size_t wb,
+                hb_result *res, void *st) { return hb_cblosc_getpoints_frames_batch_device(nf, h, f, nn, nj, q, packed.data(), (int64_t)packed.size(), d, c, wk, wb, res, st); },
+            [&](const CbpHostPlan &P, size_t i, const uint8_t *from, uint8_t *to) {
+                const hb_cblosc_point_job &q = jobs[P.carried[i]];
+                cbp_place(q, points, P.hd[q.frame].typesize, from, to);
+            });
     } catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
 }
 

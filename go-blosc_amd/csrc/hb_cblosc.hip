@@ -33,6 +33,7 @@
 #include "hb_cblosc_box_batch.h"       // the geometry of a box, the host side of the batched box reads, the gather's index arithmetic
 #include "hb_cblosc_slice_batch.h"     // the geometry of a stepped selection, the host side of the batched slice reads, the stepped gather's index arithmetic
 #include "hb_cblosc_index_batch.h"     // the geometry of an orthogonal selection, the host side of the batched index-list reads, the index arithmetic of its two gathers
+#include "hb_cblosc_point_batch.h"     // the host side of the batched point reads, the point table, the point gather's thread mapping
 #include "hb_cblosc_enc_box_batch.h"   // the geometry of a source box, the host side of the batched box writes, the gather's index arithmetic
 #include "hb_cblosc_upd_box_batch.h"   // the geometry of an update box, the host side of the batched box updates, the overlay's index arithmetic
 
@@ -778,6 +779,65 @@ __global__ __launch_bounds__(256) void k_cbi_gather_items(const CbgFrame *__rest
     if (!cbi_thread_items(W.J, R, tab, W.F.typesize, W.wl, threadIdx.x, it0, cnt, roff, doff)) return;
     cbr_unit<KIND>(W.F, W.look, work, roff, CbiListed{R.tab[3] != CBI_NONE ? tab + R.tab[3] : nullptr, R.istr, it0}, cnt, W.J.dst + doff);
 }
+// ---- batched point reads (hb_cblosc_getpoints_frames_batch_device; hb_cblosc_point_batch.h): a job is a run of the batch's point table, one
+// entry per item -- where it starts in the frame's decoded bytes, where it goes in the job's destination.  Everything but this gather is the box
+// batch's. ----
+// One item of TS bytes at byte p of the frame's decoded bytes, in registers: an item that lies whole inside the whole elements of its block is
+// read where it is staged (a byte-shuffled block plane by plane, TS byte loads at j * nel + e) after ONE lookup of its block; one that straddles
+// two blocks or lies behind a block's last whole element goes byte by byte through cbg_byte, which looks up the block of every byte.
+template <int KIND, uint32_t TS, class LOOK>
+__device__ __forceinline__ void cbp_item_wide(const CbgFrame &F, const LOOK &look, const uint8_t *__restrict__ work, uint32_t p, uint32_t (&w)[4]) {
+    w[0] = w[1] = w[2] = w[3] = 0u;
+    const bool direct = KIND == CBG_COPY && F.memcpyed;
+    const uint8_t *s = nullptr;
+    uint32_t q = 0u, e = 0u, nel = 0u;
+    bool whole = direct;
+    if (!direct) {
+        const uint32_t bs = F.blocksize, b = p / bs;
+        q = p - b * bs;
+        const CbgBlock &K = look(b);
+        s = work + K.stage_off;
+        nel = K.bsize / TS;
+        if (KIND == CBG_COPY) whole = q + TS <= K.bsize;
+        else { e = q / TS; whole = e * TS == q && e < nel; }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < TS; j++) {
+        const uint8_t v = direct ? F.frame[16u + (size_t)p + j] : !whole ? cbg_byte<KIND>(F, look, work, p + j) : KIND == CBG_COPY ? s[q + j] : s[(size_t)j * nel + e];
+        w[j >> 2] |= (uint32_t)v << (8u * (j & 3u));
+    }
+}
+// One point: the item at byte p to d, which has any alignment.  Typesizes 1, 2, 4, 8 and 16 of a copied or byte-shuffled frame are written with
+// ONE store of the item's size; every other typesize and both bit-shuffle kinds go byte by byte through cbg_byte.
+template <int KIND, class LOOK>
+__device__ __forceinline__ void cbp_item(const CbgFrame &F, const LOOK &look, const uint8_t *__restrict__ work, uint32_t p, uint8_t *__restrict__ d) {
+    const uint32_t ts = F.typesize;
+    if (KIND == CBG_COPY || KIND == CBG_UNSHUFFLE) {
+        uint32_t w[4];
+        if (ts == 1u && KIND == CBG_COPY) { cbp_item_wide<KIND, 1>(F, look, work, p, w); d[0] = (uint8_t)w[0]; return; }      // (one byte is never shuffled)
+        if (ts == 2u) { cbp_item_wide<KIND, 2>(F, look, work, p, w); ((hb_u16u *)d)->v = (uint16_t)w[0]; return; }
+        if (ts == 4u) { cbp_item_wide<KIND, 4>(F, look, work, p, w); st4u(d, w[0]); return; }
+        if (ts == 8u) { cbp_item_wide<KIND, 8>(F, look, work, p, w); st8u(d, (uint64_t)w[0] | ((uint64_t)w[1] << 32)); return; }
+        if (ts == 16u) { cbp_item_wide<KIND, 16>(F, look, work, p, w); u32x4 v; v.x = w[0]; v.y = w[1]; v.z = w[2]; v.w = w[3]; st16u(d, v); return; }
+    }
+    for (uint32_t j = 0; j < ts; j++) d[j] = cbg_byte<KIND>(F, look, work, p + j);
+}
+// The point gather: one launch per kind that occurs among the jobs of points; gjob / gblk / rows are those jobs in launch order.  A thread has
+// one point of its job (cbp_thread), 256 points to a workgroup.  KIND reaches cbp_item alone, where the two bit-shuffle kinds have the plain
+// body only: jobs of kind CBG_BITUN4 run the CBG_BITUN instantiation under their own stage name (cbr_items_kind).
+template <int KIND>
+__global__ __launch_bounds__(256) void k_cbp_gather(const CbgFrame *__restrict__ frames, const CbxJob *__restrict__ jobs, const CbpRow *__restrict__ rows,
+                                                     const CbgBlock *__restrict__ blocks, const CbPlan *__restrict__ plans, const CbxTouch *__restrict__ touch,
+                                                     const CbpPoint *__restrict__ pts, const uint32_t *__restrict__ gjob, const uint32_t *__restrict__ gblk, uint32_t nkind,
+                                                     const uint8_t *__restrict__ work) {
+    const CbxWg W = cbx_enter(frames, jobs, blocks, plans, touch, gjob, gblk, nkind);
+    if (!W.live) return;
+    const CbpRow R = rows[W.i];
+    uint32_t p;
+    if (!cbp_thread(R, W.wl, threadIdx.x, p)) return;
+    const CbpPoint P = pts[R.pt0 + p];
+    cbp_item<KIND>(W.F, W.look, work, P.off, W.J.dst + P.out);
+}
 __global__ __launch_bounds__(64) void k_cbx_finish(const CbxJob *__restrict__ jobs, const CbPlan *__restrict__ plans, const CbxTouch *__restrict__ touch, hb_result *results,
                                                     uint32_t njobs) {
     cb_finish_jobs(jobs, plans, results, njobs, &CbxJob::ntl, [touch](const CbxJob &J, uint32_t k) { return touch[J.tl0 + k].rec; });
@@ -1356,9 +1416,10 @@ int hb_cblosc_getitem_frames_batch_device(int nframes, const hb_cblosc_header *h
     return HB_OK;
 }
 
-// A prepared batch of boxes, of stepped selections or of index-list selections (CbxBatch) on the device: one upload, the plan and the decoders
-// over the distinct blocks, the gathers -- k_cbx_gather per kind among the jobs with plain rows, k_cbs_gather per kind among those with stepped
-// rows, then k_cbi_gather_rows and k_cbi_gather_items per kind among those with an index list -- and the records.
+// A prepared batch of boxes, of stepped selections, of index-list selections or of points (CbxBatch) on the device: one upload, the plan and the
+// decoders over the distinct blocks, the gathers -- k_cbx_gather per kind among the jobs with plain rows, k_cbs_gather per kind among those with
+// stepped rows, k_cbi_gather_rows and k_cbi_gather_items per kind among those with an index list, k_cbp_gather per kind among the jobs of
+// points -- and the records.
 static int cbx_launch(const CbxBatch &B, int njobs, void *d_work, hb_result *d_results, void *stream) {
     const CbxLayout &L = B.L;
     hipStream_t s = (hipStream_t)stream;
@@ -1369,6 +1430,7 @@ static int cbx_launch(const CbxBatch &B, int njobs, void *d_work, hb_result *d_r
     cb_put(up, L.gjob, B.gjob); cb_put(up, L.gblk, B.gblk);
     cb_put(up, L.srow, B.srow); cb_put(up, L.sgjob, B.sgjob); cb_put(up, L.sgblk, B.sgblk);
     cb_put(up, L.irow, B.irow); cb_put(up, L.igjob, B.igjob); cb_put(up, L.igblk, B.igblk); cb_put(up, L.itab, B.itab);
+    cb_put(up, L.prow, B.prow); cb_put(up, L.pgjob, B.pgjob); cb_put(up, L.pgblk, B.pgblk); cb_put(up, L.ptab, B.ptab);
     hb_prof_begin("cbx_upload", s);
     HB_HIP_TRY(hipMemcpyAsync(w, up.data(), L.upload, hipMemcpyHostToDevice, s));
     hb_prof_end(s);
@@ -1405,6 +1467,14 @@ static int cbx_launch(const CbxBatch &B, int njobs, void *d_work, hb_result *d_r
     cb_launch_kinds(B.ikind0 + CBG_COUNT, B.ikblocks + CBG_COUNT, iname + CBG_COUNT, s, [&](auto K, uint32_t k0, uint32_t nk, uint32_t blocks) {
         hipLaunchKernelGGL(k_cbi_gather_items<cbr_items_kind(K.value)>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_irow + k0, d_blocks, (const CbPlan *)d_plans, d_touch, d_itab,
                            d_igjob + k0, d_igblk + k0, nk, (const uint8_t *)w);
+    });
+    const CbpRow *d_prow = cb_at<const CbpRow>(w, L.prow);
+    const CbpPoint *d_ptab = cb_at<const CbpPoint>(w, L.ptab);
+    const uint32_t *d_pgjob = cb_at<const uint32_t>(w, L.pgjob), *d_pgblk = cb_at<const uint32_t>(w, L.pgblk);
+    static const char *const pname[CBG_COUNT] = {"k_cbp_gather_copy", "k_cbp_gather_unshuffle", "k_cbp_gather_bitun", "k_cbp_gather_bitun4"};
+    cb_launch_kinds(B.pkind0, B.pkblocks, pname, s, [&](auto K, uint32_t k0, uint32_t nk, uint32_t blocks) {
+        hipLaunchKernelGGL(k_cbp_gather<cbr_items_kind(K.value)>, dim3(blocks), dim3(256), 0, s, d_frames, d_jobs, d_prow + k0, d_blocks, (const CbPlan *)d_plans, d_touch, d_ptab,
+                           d_pgjob + k0, d_pgblk + k0, nk, (const uint8_t *)w);
     });
     hb_prof_begin("k_cbx_finish", s);
     hipLaunchKernelGGL(k_cbx_finish, dim3(((unsigned)njobs + 63u) / 64u), dim3(64), 0, s, d_jobs, (const CbPlan *)d_plans, d_touch, d_results, (uint32_t)njobs);
@@ -1471,6 +1541,21 @@ int hb_cblosc_getindex_frames_batch_device(int nframes, const hb_cblosc_header *
         nframes, njobs, hdrs && d_frame && n && jobs && d_dst && cap, d_work, work_bytes, d_results, stream,
         [&](CbxBatch &B, unsigned accept) { return cbi_prepare(nframes, hdrs, d_frame, n, njobs, jobs, index, nindex, d_dst, cap, true, B, accept); },
         [&](unsigned accept) { return cbi_workspace(nframes, hdrs, n, njobs, jobs, index, nindex, accept); });
+}
+
+// ---- many coordinate selections of many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_point_batch.h) ----
+size_t hb_cblosc_getpoints_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n, int njobs, const hb_cblosc_point_job *jobs, const hb_cblosc_point *points,
+                                                  int64_t npoints) {
+    return cbp_workspace(nframes, hdrs, n, njobs, jobs, points, npoints, hb_cblosc_accepted());
+}
+
+int hb_cblosc_getpoints_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_cblosc_point_job *jobs,
+                                            const hb_cblosc_point *points, int64_t npoints, void *const *d_dst, const size_t *cap, void *d_work, size_t work_bytes,
+                                            hb_result *d_results, void *stream) {
+    return cbx_device_call(
+        nframes, njobs, hdrs && d_frame && n && jobs && d_dst && cap, d_work, work_bytes, d_results, stream,
+        [&](CbxBatch &B, unsigned accept) { return cbp_prepare(nframes, hdrs, d_frame, n, njobs, jobs, points, npoints, d_dst, cap, true, B, accept); },
+        [&](unsigned accept) { return cbp_workspace(nframes, hdrs, n, njobs, jobs, points, npoints, accept); });
 }
 
 size_t hb_cblosc_bound(size_t n, int typesize) {

@@ -48,7 +48,14 @@ struct CbsRow { uint32_t nit, istr; };
 // (cstr[k], or for the row nit items istr bytes apart, as in CbsRow).
 #define CBI_NONE 0xFFFFFFFFu
 struct CbiRow { uint32_t tab[4]; uint32_t nit, istr; };
-static_assert(sizeof(CbxTouch) == 8 && sizeof(CbxJob) == 152 && sizeof(CbsRow) == 8 && sizeof(CbiRow) == 24, "the records are uploaded as they are");
+// A job of points (hb_cblosc_point_batch.h) keeps its CbxJob as well -- dst, bytes, frame, the touch list, kind and status; the fields that
+// describe rows stay 0 -- and has one of these beside it, in the order of its kind's launch list: its npt entries of the batch's point table
+// start at pt0.  A table entry is one point, in the caller's order: where the item starts in the frame's decoded bytes (nbytes < 2^32) and
+// where it goes in the job's destination, in bytes.
+struct CbpRow { uint32_t pt0, npt; };
+struct CbpPoint { uint32_t off, pad; uint64_t out; };
+static_assert(sizeof(CbxTouch) == 8 && sizeof(CbxJob) == 152 && sizeof(CbsRow) == 8 && sizeof(CbiRow) == 24 && sizeof(CbpRow) == 8 && sizeof(CbpPoint) == 16,
+              "the records are uploaded as they are");
 static_assert(sizeof(CbxTouch) == HB_CBLOSC_BOX_BATCH_TOUCH_BYTES, "the per-pair constant of include/hipblosc.h");
 // per job: its record and two prefix words; per frame: its record; once: the padding of the sections (at most 6 x 16 + 2 x 255 bytes, and
 // every batch has a job and a frame).  Per distinct block the records are those of hb_cblosc_getitem_batch.h.
@@ -182,9 +189,9 @@ CB_HD static inline uint32_t cbx_find(const CbxTouch *tl, uint32_t ntl, uint32_t
 }
 
 // everything up to `upload` goes up in ONE copy
-struct CbxLayout { size_t frames, jobs, blocks, plans, str0, touch, gjob, gblk, srow, sgjob, sgblk, irow, igjob, igblk, itab, upload, streams, stage, total; };
+struct CbxLayout { size_t frames, jobs, blocks, plans, str0, touch, gjob, gblk, srow, sgjob, sgblk, irow, igjob, igblk, itab, prow, pgjob, pgblk, ptab, upload, streams, stage, total; };
 static inline CbxLayout cbx_layout(size_t nframes, size_t njobs, uint64_t nblk, uint64_t ntouch, uint64_t nstreams, uint64_t stage_bytes, size_t nstep = 0,
-                                   size_t nidx = 0, uint64_t ntab = 0) {
+                                   size_t nidx = 0, uint64_t ntab = 0, size_t npj = 0, uint64_t npts = 0) {
     CbxLayout L{};
     size_t o = 0;
     auto take = [&](size_t b, size_t al) { size_t at = o; o += (b + al - 1) / al * al; return at; };
@@ -203,6 +210,10 @@ static inline CbxLayout cbx_layout(size_t nframes, size_t njobs, uint64_t nblk, 
     L.igjob = take(nidx * 4, 16);
     L.igblk = take(nidx * 4, 16);
     L.itab = take((size_t)ntab * 4, 16);
+    L.prow = take(npj * sizeof(CbpRow), 16);                              // (the jobs of points and their table: nothing for the N-d selections)
+    L.pgjob = take(npj * 4, 16);
+    L.pgblk = take(npj * 4, 16);
+    L.ptab = take((size_t)npts * sizeof(CbpPoint), 16);
     o = cb_align(o);
     L.upload = o;
     L.streams = take((size_t)nstreams * sizeof(CbStream), 256);
@@ -230,6 +241,11 @@ struct CbxBatch {
     std::vector<uint8_t> jigather;
     std::vector<uint32_t> igjob, igblk, itab;
     uint32_t ikind0[2 * CBG_COUNT + 1], ikblocks[2 * CBG_COUNT];
+    // jobs of points (hb_cblosc_point_batch.h): their rows in launch order beside pgjob / pgblk, and the point table
+    std::vector<CbpRow> prow;
+    std::vector<CbpPoint> ptab;
+    std::vector<uint32_t> pgjob, pgblk;
+    uint32_t pkind0[CBG_COUNT + 1], pkblocks[CBG_COUNT];
     uint64_t nblk, nstreams, stage, ntouch;
     uint32_t any_small, nsplit_all, any_lz4, any_blz;
     int ptr_refusals;                    // jobs refused for their capacity or a pointer: the workspace query counts their blocks, this batch does not
@@ -239,6 +255,95 @@ struct CbxBatch {
 // the units of a stepped row: a thread owns 16 bytes of the row's destination, counted from the row's start -- 16 / ts whole items where the
 // typesize divides 16, else one item
 CB_HD static inline uint32_t cbs_items_per_unit(uint32_t ts) { return 16u % ts ? 1u : 16u / ts; }
+
+// ---- what cbx_prepare_ below and cbp_prepare_ (hb_cblosc_point_batch.h) share: the empty batch, a frame's record, a job's gather kind, the
+// table of distinct blocks out of the jobs' runs, and the block records and touch lists ----
+static inline void cbx_reset(CbxBatch &B) {
+    B.nblk = 0; B.nstreams = 0; B.stage = 0; B.ntouch = 0; B.any_small = 0; B.nsplit_all = 0; B.ptr_refusals = 0; B.any_lz4 = 0; B.any_blz = 0;
+    for (int k = 0; k < CBG_COUNT; k++) B.kblocks[k] = 0;
+    for (int k = 0; k <= CBG_COUNT; k++) B.kind0[k] = 0;
+    for (int k = 0; k < CBG_COUNT; k++) B.skblocks[k] = 0;
+    for (int k = 0; k <= CBG_COUNT; k++) B.skind0[k] = 0;
+    B.jrow.clear(); B.srow.clear(); B.sgjob.clear(); B.sgblk.clear();
+    for (int k = 0; k < 2 * CBG_COUNT; k++) B.ikblocks[k] = 0;
+    for (int k = 0; k <= 2 * CBG_COUNT; k++) B.ikind0[k] = 0;
+    B.jirow.clear(); B.irow.clear(); B.jigather.clear(); B.igjob.clear(); B.igblk.clear(); B.itab.clear();
+    B.frames.clear(); B.jobs.clear(); B.jruns.clear(); B.runs.clear(); B.blocks.clear(); B.touch.clear(); B.str0.clear(); B.gjob.clear(); B.gblk.clear();
+    for (int k = 0; k < CBG_COUNT; k++) B.pkblocks[k] = 0;
+    for (int k = 0; k <= CBG_COUNT; k++) B.pkind0[k] = 0;
+    B.prow.clear(); B.ptab.clear(); B.pgjob.clear(); B.pgblk.clear();
+    B.L = cbx_layout(0, 0, 0, 0, 0, 0);
+}
+static inline void cbx_frame_record(CbgFrame &F, const hb_cblosc_header &h, const uint8_t *d_frame) {
+    F.frame = d_frame;
+    F.nbytes = h.nbytes; F.blocksize = h.blocksize; F.cbytes = h.cbytes; F.typesize = h.typesize; F.flags = cb_record_flags(h);
+    F.memcpyed = (h.flags & CB_FLAG_MEMCPY) ? 1u : 0u;
+    F.nsplit = F.memcpyed || !h.blocksize ? 1u : cb_nsplit(h.flags, h.typesize, h.blocksize);
+    F.small = !F.memcpyed && !cb_is_blosclz(F.flags) && h.blocksize && h.blocksize / F.nsplit <= HB_CHUNK ? 1u : 0u;
+}
+static inline int cbx_kind(const hb_cblosc_header &h, const CbgFrame &F) {
+    const uint32_t ts = h.typesize, bs = h.blocksize;
+    const bool unshuf = (h.flags & CB_FLAG_SHUFFLE) && ts > 1, unbit = !unshuf && (h.flags & CB_FLAG_BITSHUFFLE);
+    return F.memcpyed ? CBG_COPY : unshuf ? CBG_UNSHUFFLE : !unbit ? CBG_COPY : (ts == 4u && bs % 512u == 0u) ? CBG_BITUN4 : CBG_BITUN;
+}
+// B.runs and the counts from B.jruns; HB_ERR_BAD_ARG: beyond the 32-bit limits
+static inline int cbx_distinct_blocks(CbxBatch &B, const hb_cblosc_header *hdrs) {
+    // the distinct blocks: sort the jobs' runs by (frame, first block), merge what overlaps or touches
+    B.runs = B.jruns;
+    std::sort(B.runs.begin(), B.runs.end(), [](const CbgRun &a, const CbgRun &b) { return a.frame != b.frame ? a.frame < b.frame : a.lo != b.lo ? a.lo < b.lo : a.hi < b.hi; });
+    size_t m = 0;
+    for (size_t i = 0; i < B.runs.size(); i++) {
+        const CbgRun &r = B.runs[i];
+        if (m && B.runs[m - 1].frame == r.frame && (uint64_t)r.lo <= (uint64_t)B.runs[m - 1].hi + 1u) { if (r.hi > B.runs[m - 1].hi) B.runs[m - 1].hi = r.hi; }
+        else B.runs[m++] = r;
+    }
+    B.runs.resize(m);
+    for (CbgRun &r : B.runs) {
+        const hb_cblosc_header &h = hdrs[r.frame];
+        const CbgFrame &F = B.frames[r.frame];
+        const uint32_t last = (uint32_t)(((uint64_t)h.nbytes + h.blocksize - 1) / h.blocksize) - 1u;
+        const bool tail = r.hi == last && h.nbytes % h.blocksize != 0u;       // the run ends with the frame's last, shorter block: one stream
+        const uint64_t cnt = (uint64_t)r.hi - r.lo + 1u, full = cnt - (tail ? 1u : 0u);
+        r.blk0 = (uint32_t)B.nblk;
+        B.nblk += cnt;
+        B.nstreams += full * F.nsplit + (tail ? 1u : 0u);
+        B.stage += full * cb_align((size_t)h.blocksize + 64) + (tail ? cb_align((size_t)(h.nbytes % h.blocksize) + 64) : 0u);
+        if (B.nblk > HB_CBLOSC_BATCH_MAX_WORK || B.nstreams > HB_CBLOSC_BATCH_MAX_WORK) return HB_ERR_BAD_ARG;
+        if (F.small) B.any_small = 1;
+        if (cb_is_blosclz(F.flags)) B.any_blz = 1; else B.any_lz4 = 1;
+        B.nsplit_all = B.nsplit_all == 0 || B.nsplit_all == F.nsplit ? F.nsplit : 1u;
+    }
+    if (B.nsplit_all == 0) B.nsplit_all = 1;
+    return HB_OK;
+}
+// the block records behind the layout's stage offset, and every job's touch list (B.jruns are in job order, as B.jobs[].tl0 counts them)
+static inline void cbx_block_tables(CbxBatch &B, const hb_cblosc_header *hdrs) {
+    B.blocks.resize((size_t)B.nblk);
+    B.str0.resize((size_t)B.nblk);
+    uint32_t stream = 0;
+    uint64_t stage = B.L.stage;
+    size_t x = 0;
+    for (const CbgRun &r : B.runs) {
+        const hb_cblosc_header &h = hdrs[r.frame];
+        const CbgFrame &F = B.frames[r.frame];
+        for (uint64_t b = r.lo; b <= r.hi; b++, x++) {
+            CbgBlock &K = B.blocks[x];
+            K.frame = r.frame; K.b = (uint32_t)b; K.bsize = cbg_bsize(h, (uint32_t)b); K.pad = 0;
+            K.nstreams = K.bsize == h.blocksize ? F.nsplit : 1u;
+            K.stream0 = stream; B.str0[x] = stream; stream += K.nstreams;
+            K.stage_off = stage; stage += cb_align((size_t)K.bsize + 64);
+        }
+    }
+    // the touch lists: a job's run lies inside the merged run that is the last of its frame to start at or before it
+    B.touch.resize((size_t)B.ntouch);
+    size_t t = 0;
+    for (const CbgRun &jr : B.jruns) {
+        const CbgRun key{jr.frame, jr.lo, 0u, 0u};
+        auto it = std::upper_bound(B.runs.begin(), B.runs.end(), key, [](const CbgRun &a, const CbgRun &b) { return a.frame != b.frame ? a.frame < b.frame : a.lo < b.lo; });
+        const CbgRun &r = *(it - 1);
+        for (uint64_t b = jr.lo; b <= jr.hi; b++) B.touch[t++] = CbxTouch{(uint32_t)b, r.blk0 + ((uint32_t)b - r.lo)};
+    }
+}
 
 // What cbx_prepare_ asks about index lists.  Boxes and slices have none: this is their answer, and every branch on it folds away.
 // hb_cblosc_index_batch.h has the one that speaks of the job `refuse` accepted last.
@@ -257,17 +362,7 @@ struct CbxNoLists {
 template <class JOB, class REFUSE, class LISTS>
 static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const JOB *jobs,
                                void *const *d_dst, const size_t *cap, bool fill, CbxBatch &B, unsigned accept, REFUSE refuse, LISTS &lists) {
-    B.nblk = 0; B.nstreams = 0; B.stage = 0; B.ntouch = 0; B.any_small = 0; B.nsplit_all = 0; B.ptr_refusals = 0; B.any_lz4 = 0; B.any_blz = 0;
-    for (int k = 0; k < CBG_COUNT; k++) B.kblocks[k] = 0;
-    for (int k = 0; k <= CBG_COUNT; k++) B.kind0[k] = 0;
-    for (int k = 0; k < CBG_COUNT; k++) B.skblocks[k] = 0;
-    for (int k = 0; k <= CBG_COUNT; k++) B.skind0[k] = 0;
-    B.jrow.clear(); B.srow.clear(); B.sgjob.clear(); B.sgblk.clear();
-    for (int k = 0; k < 2 * CBG_COUNT; k++) B.ikblocks[k] = 0;
-    for (int k = 0; k <= 2 * CBG_COUNT; k++) B.ikind0[k] = 0;
-    B.jirow.clear(); B.irow.clear(); B.jigather.clear(); B.igjob.clear(); B.igblk.clear(); B.itab.clear();
-    B.frames.clear(); B.jobs.clear(); B.jruns.clear(); B.runs.clear(); B.blocks.clear(); B.touch.clear(); B.str0.clear(); B.gjob.clear(); B.gblk.clear();
-    B.L = cbx_layout(0, 0, 0, 0, 0, 0);
+    cbx_reset(B);
     if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
     if (njobs == 0) return HB_OK;
     if (!hdrs || !n || !jobs) return HB_ERR_BAD_ARG;
@@ -296,19 +391,12 @@ static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
         if (J.status) continue;
         if (!lists.fits()) return HB_ERR_BAD_ARG;                         // (lists beyond the 32-bit limits: the caller has to split the job)
         CbgFrame &F = B.frames[q.frame];
-        if (!F.typesize) {                                                // the first accepted job of this frame
-            F.frame = have ? (const uint8_t *)d_frame[q.frame] : nullptr;
-            F.nbytes = h.nbytes; F.blocksize = h.blocksize; F.cbytes = h.cbytes; F.typesize = h.typesize; F.flags = cb_record_flags(h);
-            F.memcpyed = (h.flags & CB_FLAG_MEMCPY) ? 1u : 0u;
-            F.nsplit = F.memcpyed || !h.blocksize ? 1u : cb_nsplit(h.flags, h.typesize, h.blocksize);
-            F.small = !F.memcpyed && !cb_is_blosclz(F.flags) && h.blocksize && h.blocksize / F.nsplit <= HB_CHUNK ? 1u : 0u;
-        }
+        if (!F.typesize) cbx_frame_record(F, h, have ? (const uint8_t *)d_frame[q.frame] : nullptr);      // the first accepted job of this frame
         J.dst = have ? (uint8_t *)d_dst[j] : nullptr;
         J.bytes = g.bytes;
         if (!g.bytes) continue;                                           // an empty box: nothing is planned or written
         const uint32_t ts = h.typesize, bs = h.blocksize;
-        const bool unshuf = (h.flags & CB_FLAG_SHUFFLE) && ts > 1, unbit = !unshuf && (h.flags & CB_FLAG_BITSHUFFLE);
-        J.kind = F.memcpyed ? CBG_COPY : unshuf ? CBG_UNSHUFFLE : !unbit ? CBG_COPY : (ts == 4u && bs % 512u == 0u) ? CBG_BITUN4 : CBG_BITUN;
+        J.kind = cbx_kind(h, F);
         const uint32_t U = cbg_unit_bytes(J.kind, ts);
         for (int k = 0; k < 3; k++) { J.dstr[k] = g.dstr[k]; J.cstr[k] = g.cstr[k]; J.shp[k] = g.shp[k]; }
         J.rcp[0] = cbx_recip(g.shp[1]); J.rcp[1] = cbx_recip(g.shp[2]); J.rcp_unit = cbx_recip(U);
@@ -353,32 +441,7 @@ static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
         J.b_lo = B.jruns[first].lo;
         J.dense = B.jruns.size() == first + 1 ? 1u : 0u;
     }
-    // the distinct blocks: sort the jobs' runs by (frame, first block), merge what overlaps or touches
-    B.runs = B.jruns;
-    std::sort(B.runs.begin(), B.runs.end(), [](const CbgRun &a, const CbgRun &b) { return a.frame != b.frame ? a.frame < b.frame : a.lo != b.lo ? a.lo < b.lo : a.hi < b.hi; });
-    size_t m = 0;
-    for (size_t i = 0; i < B.runs.size(); i++) {
-        const CbgRun &r = B.runs[i];
-        if (m && B.runs[m - 1].frame == r.frame && (uint64_t)r.lo <= (uint64_t)B.runs[m - 1].hi + 1u) { if (r.hi > B.runs[m - 1].hi) B.runs[m - 1].hi = r.hi; }
-        else B.runs[m++] = r;
-    }
-    B.runs.resize(m);
-    for (CbgRun &r : B.runs) {
-        const hb_cblosc_header &h = hdrs[r.frame];
-        const CbgFrame &F = B.frames[r.frame];
-        const uint32_t last = (uint32_t)(((uint64_t)h.nbytes + h.blocksize - 1) / h.blocksize) - 1u;
-        const bool tail = r.hi == last && h.nbytes % h.blocksize != 0u;       // the run ends with the frame's last, shorter block: one stream
-        const uint64_t cnt = (uint64_t)r.hi - r.lo + 1u, full = cnt - (tail ? 1u : 0u);
-        r.blk0 = (uint32_t)B.nblk;
-        B.nblk += cnt;
-        B.nstreams += full * F.nsplit + (tail ? 1u : 0u);
-        B.stage += full * cb_align((size_t)h.blocksize + 64) + (tail ? cb_align((size_t)(h.nbytes % h.blocksize) + 64) : 0u);
-        if (B.nblk > HB_CBLOSC_BATCH_MAX_WORK || B.nstreams > HB_CBLOSC_BATCH_MAX_WORK) return HB_ERR_BAD_ARG;
-        if (F.small) B.any_small = 1;
-        if (cb_is_blosclz(F.flags)) B.any_blz = 1; else B.any_lz4 = 1;
-        B.nsplit_all = B.nsplit_all == 0 || B.nsplit_all == F.nsplit ? F.nsplit : 1u;
-    }
-    if (B.nsplit_all == 0) B.nsplit_all = 1;
+    if (const int rc = cbx_distinct_blocks(B, hdrs)) return rc;
     B.L = cbx_layout(nf, nj, B.nblk, B.ntouch, B.nstreams, B.stage, nstep, nidx, B.itab.size());
     uint32_t at = 0, sat = 0, iat = 0;
     for (int k = 0; k < 2 * CBG_COUNT; k++) { B.ikind0[k] = iat; iat += ikn[k]; B.ikblocks[k] = (uint32_t)ikb[k]; }
@@ -388,31 +451,7 @@ static inline int cbx_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
     B.kind0[CBG_COUNT] = at; B.skind0[CBG_COUNT] = sat;
     if (!fill) return HB_OK;
     // ---- the tables ----
-    B.blocks.resize((size_t)B.nblk);
-    B.str0.resize((size_t)B.nblk);
-    uint32_t stream = 0;
-    uint64_t stage = B.L.stage;
-    size_t x = 0;
-    for (const CbgRun &r : B.runs) {
-        const hb_cblosc_header &h = hdrs[r.frame];
-        const CbgFrame &F = B.frames[r.frame];
-        for (uint64_t b = r.lo; b <= r.hi; b++, x++) {
-            CbgBlock &K = B.blocks[x];
-            K.frame = r.frame; K.b = (uint32_t)b; K.bsize = cbg_bsize(h, (uint32_t)b); K.pad = 0;
-            K.nstreams = K.bsize == h.blocksize ? F.nsplit : 1u;
-            K.stream0 = stream; B.str0[x] = stream; stream += K.nstreams;
-            K.stage_off = stage; stage += cb_align((size_t)K.bsize + 64);
-        }
-    }
-    // the touch lists: a job's run lies inside the merged run that is the last of its frame to start at or before it
-    B.touch.resize((size_t)B.ntouch);
-    size_t t = 0;
-    for (const CbgRun &jr : B.jruns) {
-        const CbgRun key{jr.frame, jr.lo, 0u, 0u};
-        auto it = std::upper_bound(B.runs.begin(), B.runs.end(), key, [](const CbgRun &a, const CbgRun &b) { return a.frame != b.frame ? a.frame < b.frame : a.lo < b.lo; });
-        const CbgRun &r = *(it - 1);
-        for (uint64_t b = jr.lo; b <= jr.hi; b++) B.touch[t++] = CbxTouch{(uint32_t)b, r.blk0 + ((uint32_t)b - r.lo)};
-    }
+    cbx_block_tables(B, hdrs);
     B.gjob.assign(nj, 0u); B.gblk.assign(nj, 0u);
     B.srow.assign(nstep, CbsRow{0u, 0u}); B.sgjob.assign(nstep, 0u); B.sgblk.assign(nstep, 0u);
     B.irow.assign(nidx, CbiRow{}); B.igjob.assign(nidx, 0u); B.igblk.assign(nidx, 0u);
@@ -468,7 +507,7 @@ struct CbxHostPlanOf {
     std::vector<int64_t> status;         // per job: its refusal, or 0
     std::vector<int> carried;            // the jobs the batch carries, in order
     std::vector<JOB> pj;                 // per carried job: the job with the strides of its packed box
-    std::vector<CbxGeom> geom;           // per carried job
+    std::vector<CbxGeom> geom;           // per carried job (none for jobs of points: hb_cblosc_point_batch.h)
     std::vector<size_t> ooff, caps;      // per carried job
     std::vector<int> idx;                // the frames that a carried job reads, in order
     std::vector<size_t> ioff;            // per frame
@@ -476,14 +515,27 @@ struct CbxHostPlanOf {
     bool span_in;
 };
 typedef CbxHostPlanOf<hb_cblosc_box_job> CbxHostPlan;
+template <class JOB>
+static inline void cbx_host_plan_reset(CbxHostPlanOf<JOB> &P, size_t nf, size_t nj) {
+    P.hd.assign(nf, hb_cblosc_header{}); P.status.assign(nj, 0); P.carried.clear(); P.pj.clear(); P.geom.clear(); P.ooff.clear(); P.caps.clear(); P.idx.clear(); P.ioff.assign(nf, 0);
+    P.in_bytes = P.out_bytes = 0; P.span_in = false;
+}
+// the frames that go up (used[k]: a carried job reads frame k) and where
+template <class JOB>
+static inline void cbx_host_plan_frames(CbxHostPlanOf<JOB> &P, int nframes, const void *const *frame, const size_t *n, const std::vector<uint8_t> &used) {
+    for (int k = 0; k < nframes; k++) if (used[(size_t)k]) P.idx.push_back(k);
+    P.span_in = P.idx.size() > 1;
+    for (size_t i = 0; P.span_in && i + 1 < P.idx.size(); i++)
+        P.span_in = (const uint8_t *)frame[P.idx[i]] + n[P.idx[i]] == (const uint8_t *)frame[P.idx[i + 1]];
+    for (int k : P.idx) { P.ioff[(size_t)k] = P.in_bytes; P.in_bytes += P.span_in ? n[k] : cb_align(n[k] + 64); }
+}
 static inline const int64_t *cbx_extent(const hb_cblosc_box_job &q) { return q.shape; }      // the items per dimension that a job writes
 // (`refuse`: cbx_refusal, or cbs_refusal of hb_cblosc_slice_batch.h, as for cbx_prepare_)
 template <class JOB, class REFUSE>
 static inline void cbx_host_plan_(int nframes, const void *const *frame, const size_t *n, int njobs, const JOB *jobs, void *const *dst, const size_t *cap,
                                   CbxHostPlanOf<JOB> &P, unsigned accept, REFUSE refuse) {
     const size_t nf = (size_t)nframes, nj = (size_t)njobs;
-    P.hd.assign(nf, hb_cblosc_header{}); P.status.assign(nj, 0); P.carried.clear(); P.pj.clear(); P.geom.clear(); P.ooff.clear(); P.caps.clear(); P.idx.clear(); P.ioff.assign(nf, 0);
-    P.in_bytes = P.out_bytes = 0; P.span_in = false;
+    cbx_host_plan_reset(P, nf, nj);
     std::vector<int> parsed(nf, 0);
     std::vector<uint8_t> used(nf, 0);
     for (size_t k = 0; k < nf; k++) {
@@ -502,11 +554,7 @@ static inline void cbx_host_plan_(int nframes, const void *const *frame, const s
         P.out_bytes += (size_t)g.bytes;
         used[q.frame] = 1;
     }
-    for (int k = 0; k < nframes; k++) if (used[(size_t)k]) P.idx.push_back(k);
-    P.span_in = P.idx.size() > 1;
-    for (size_t i = 0; P.span_in && i + 1 < P.idx.size(); i++)
-        P.span_in = (const uint8_t *)frame[P.idx[i]] + n[P.idx[i]] == (const uint8_t *)frame[P.idx[i + 1]];
-    for (int k : P.idx) { P.ioff[(size_t)k] = P.in_bytes; P.in_bytes += P.span_in ? n[k] : cb_align(n[k] + 64); }
+    cbx_host_plan_frames(P, nframes, frame, n, used);
 }
 static inline void cbx_host_plan(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_cblosc_box_job *jobs, void *const *dst, const size_t *cap,
                                  CbxHostPlan &P, unsigned accept = CB_ACCEPT_DEFAULT) {

@@ -1584,6 +1584,173 @@ func CBloscReadOIndex(frames [][]byte, gridShape, chunkShape []int64, sel []OSel
 	return out, nil
 }
 
+// PointJob is one coordinate selection of CBloscGetPointBatchHIP over frames[Frame]: the chunk-local LINEAR item indices Items, in any order,
+// repeats allowed; item i goes to position Outs[i] of the job's result (the two slices have the same length).
+type PointJob struct {
+	Frame       int
+	Items, Outs []int64
+}
+
+// CBloscGetPointBatchHIP reads many coordinate selections of C-Blosc-1 chunk frames through ONE set of kernel launches
+// (hb_cblosc_getpoints_frames_batch): `z.vindex[rows, cols]`, `z[mask]` or any scattered lookup of single items is one job per chunk that
+// holds a point.  Every frame goes up once, every distinct block that holds a byte of a selected item is decoded once, no other block is read.
+// out[j] is max(Outs)+1 items long -- the selected items at their positions, zeros elsewhere -- and errs[j] the job's error.
+// Without a device every job gets the no-device error: there is no CPU path.  Go memory is borrowed for the call only (pinned slabs and C
+// arrays, never Go pointers in C memory).  Like the rest of this file: written against the C ABI, it has never met a compiler.
+func CBloscGetPointBatchHIP(frames [][]byte, jobs []PointJob) ([][]byte, []error) {
+	nj, nf := len(jobs), len(frames)
+	out := make([][]byte, nj)
+	errs := make([]error, nj)
+	if nj == 0 {
+		return out, errs
+	}
+	failAll := func(code C.int64_t) ([][]byte, []error) {
+		for j := range jobs {
+			errs[j] = hbError(code)
+		}
+		return out, errs
+	}
+	if !useHIP {
+		return failAll(C.int64_t(C.HB_ERR_NO_DEVICE))
+	}
+	for _, q := range jobs {
+		if q.Frame < 0 || q.Frame >= nf || len(q.Items) != len(q.Outs) {
+			return failAll(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+	}
+	ptrBytes := C.size_t(unsafe.Sizeof(uintptr(0)))
+	srcs := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(nf) * ptrBytes))[:nf:nf]
+	dsts := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(nj) * ptrBytes))[:nj:nj]
+	defer C.free(unsafe.Pointer(&srcs[0]))
+	defer C.free(unsafe.Pointer(&dsts[0]))
+	lens := make([]C.size_t, nf)
+	caps := make([]C.size_t, nj)
+	rcs := make([]C.int64_t, nj)
+	jt := make([]C.hb_cblosc_point_job, nj)
+	points := []C.hb_cblosc_point{{}} // (never empty: the array has to be there for a job without points as well)
+	var inBytes, outBytes C.size_t
+	for k, f := range frames {
+		lens[k] = C.size_t(len(f))
+		inBytes += lens[k] // tightly packed: frames that follow each other exactly go up in ONE copy
+	}
+	for j, q := range jobs {
+		ts := int64(1)
+		if len(frames[q.Frame]) >= 16 && frames[q.Frame][3] != 0 {
+			ts = int64(frames[q.Frame][3])
+		}
+		jt[j].frame = C.uint32_t(q.Frame)
+		jt[j].first = C.int64_t(len(points))
+		jt[j].count = C.int64_t(len(q.Items))
+		top := int64(-1)
+		for i, v := range q.Items {
+			points = append(points, C.hb_cblosc_point{item: C.int64_t(v), out: C.int64_t(q.Outs[i])})
+			if q.Outs[i] > top {
+				top = q.Outs[i]
+			}
+		}
+		if top+1 < (1<<32)/ts { // (a span beyond 4 GiB is one to split: no room is made for it)
+			caps[j] = C.size_t((top + 1) * ts)
+		}
+		outBytes += caps[j] + 1
+	}
+	slabIn, slabOut := C.hb_host_alloc(inBytes+64), C.hb_host_alloc(outBytes+64)
+	if slabIn == nil || slabOut == nil {
+		C.hb_host_free(slabIn)
+		C.hb_host_free(slabOut)
+		return failAll(C.int64_t(C.HB_ERR_HIP))
+	}
+	defer C.hb_host_free(slabIn)
+	defer C.hb_host_free(slabOut)
+	var io, oo C.size_t
+	for k, f := range frames {
+		srcs[k] = unsafe.Add(slabIn, uintptr(io))
+		copy(unsafe.Slice((*byte)(srcs[k]), len(f)), f)
+		io += lens[k]
+	}
+	for j := range jobs {
+		dsts[j] = unsafe.Add(slabOut, uintptr(oo))
+		clear(unsafe.Slice((*byte)(dsts[j]), int(caps[j]))) // (the positions no point goes to)
+		oo += caps[j] + 1
+	}
+	if rc := C.hb_cblosc_getpoints_frames_batch(C.int(nf), &srcs[0], &lens[0], C.int(nj), &jt[0], &points[0], C.int64_t(len(points)), &dsts[0], &caps[0], &rcs[0], C.int(Device)); rc != C.HB_OK {
+		return failAll(C.int64_t(rc))
+	}
+	for j := range jobs {
+		if rcs[j] < 0 {
+			errs[j] = hbError(rcs[j])
+		} else {
+			out[j] = append([]byte(nil), unsafe.Slice((*byte)(dsts[j]), int(caps[j]))...)
+		}
+	}
+	return out, errs
+}
+
+// CBloscReadVIndex reads `z.vindex[coords[0], coords[1] ...]` of a chunked array whose chunks are the C-Blosc-1 frames `frames`, in C order of
+// the chunk grid gridShape, every chunk chunkShape items of typeSize bytes: coords holds one slice of array-level coordinates per dimension,
+// all of the same length, and point i is (coords[0][i], coords[1][i] ...).  The points are grouped per chunk -- one PointJob per chunk that
+// holds a point, its Items the ravelled chunk-local coordinates, its Outs the points' positions in coords -- and all jobs go through one
+// CBloscGetPointBatchHIP call.  A nil frame is a chunk the store does not have: its points are `fill` (typeSize bytes; nil: an error).
+// Returns len(coords[0]) * typeSize bytes, point i at i * typeSize.  A boolean mask is this call over the coordinates of its set entries.
+func CBloscReadVIndex(frames [][]byte, gridShape, chunkShape []int64, coords [][]int64, typeSize int, fill []byte) ([]byte, error) {
+	nd := len(chunkShape)
+	if nd < 1 || nd > int(C.HB_CBLOSC_BOX_MAX_NDIM) || len(gridShape) != nd || len(coords) != nd || typeSize < 1 {
+		return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	np := len(coords[0])
+	for k := 1; k < nd; k++ {
+		if len(coords[k]) != np {
+			return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+	}
+	out := make([]byte, np*typeSize)
+	slot := map[int64]int{} // frame number -> its job
+	var jobs []PointJob
+	for i := 0; i < np; i++ {
+		f, item := int64(0), int64(0)
+		for k := 0; k < nd; k++ {
+			c := coords[k][i]
+			if c < 0 || c >= gridShape[k]*chunkShape[k] { // (negative coordinates are not wrapped)
+				return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+			}
+			f = f*gridShape[k] + c/chunkShape[k]
+			item = item*chunkShape[k] + c%chunkShape[k]
+		}
+		if f >= int64(len(frames)) {
+			return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+		if frames[f] == nil {
+			if len(fill) != typeSize {
+				return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG)) // an absent chunk and no fill value
+			}
+			copy(out[i*typeSize:], fill)
+			continue
+		}
+		j, ok := slot[f]
+		if !ok {
+			j = len(jobs)
+			slot[f] = j
+			jobs = append(jobs, PointJob{Frame: int(f)})
+		}
+		jobs[j].Items = append(jobs[j].Items, item)
+		jobs[j].Outs = append(jobs[j].Outs, int64(i))
+	}
+	if len(jobs) == 0 {
+		return out, nil
+	}
+	got, errs := CBloscGetPointBatchHIP(frames, jobs)
+	for _, err := range errs {
+		if err != nil {
+			return nil, err
+		}
+	}
+	for j, q := range jobs { // a job's result spans the output up to its last point: its own items to their places
+		for _, o := range q.Outs {
+			copy(out[int(o)*typeSize:(int(o)+1)*typeSize], got[j][int(o)*typeSize:])
+		}
+	}
+	return out, nil
+}
+
 // SrcBox is one chunk of CBloscCompressBoxBatchHIP: the part [0, Shape[k]) along every dimension k of a C-order chunk of ChunkShape items comes
 // from Src, whose first byte is the box's first item and whose neighbours along dimension k lie SrcStride[k] BYTES apart (1 to 4 dimensions;
 // the three slices have the same length; the last stride is the typeSize).  Every other item of the chunk is the fill value.  A nil Src is a

@@ -108,6 +108,7 @@ EXPORTS = [
     "hb_cblosc_getbox_frames_batch_workspace", "hb_cblosc_getbox_frames_batch_device", "hb_cblosc_getbox_frames_batch",
     "hb_cblosc_getslice_frames_batch_workspace", "hb_cblosc_getslice_frames_batch_device", "hb_cblosc_getslice_frames_batch",
     "hb_cblosc_getindex_frames_batch_workspace", "hb_cblosc_getindex_frames_batch_device", "hb_cblosc_getindex_frames_batch",
+    "hb_cblosc_getpoints_frames_batch_workspace", "hb_cblosc_getpoints_frames_batch_device", "hb_cblosc_getpoints_frames_batch",
     "hb_cblosc_compress_boxes_batch_workspace", "hb_cblosc_compress_boxes_batch_device", "hb_cblosc_compress_boxes_batch",
     "hb_cblosc_update_boxes_batch_workspace", "hb_cblosc_update_boxes_batch_device", "hb_cblosc_update_boxes_batch",
     "hb_cblosc_accept_codecs",
@@ -175,6 +176,21 @@ def index_job(frame, chunk_shape, start, count, step, lists, dst_stride):
         raise ValueError("chunk_shape, start, count, step, lists and dst_stride need the same number of entries, at most 4")
     a = ctypes.c_int64 * 4
     return hb_cblosc_index_job(int(frame), nd, *[a(*[int(v) for v in seq]) for seq in (chunk_shape, start, count, step, lists, dst_stride)])
+
+
+class hb_cblosc_point(ctypes.Structure):
+    """include/hipblosc.h hb_cblosc_point: a chunk-local linear item index and where the item goes in the job's destination, in items"""
+    _fields_ = [("item", ctypes.c_int64), ("out", ctypes.c_int64)]
+
+
+class hb_cblosc_point_job(ctypes.Structure):
+    """include/hipblosc.h hb_cblosc_point_job: a coordinate selection of a chunk -- a range of the call's point array"""
+    _fields_ = [("frame", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("first", ctypes.c_int64), ("count", ctypes.c_int64)]
+
+
+def point_job(frame, first, count):
+    """hb_cblosc_point_job: the job of frame `frame` that owns points[first : first + count] of the call's point array"""
+    return hb_cblosc_point_job(int(frame), 0, int(first), int(count))
 
 
 class hb_cblosc_src_box(ctypes.Structure):
@@ -290,6 +306,9 @@ def lib():
             "hb_cblosc_getindex_frames_batch_workspace": (sz, [i32, vp, vp, i32, vp, vp, ctypes.c_int64]),
             "hb_cblosc_getindex_frames_batch_device": (i32, [i32, vp, vp, vp, i32, vp, vp, ctypes.c_int64, vp, vp, vp, sz, vp, vp]),
             "hb_cblosc_getindex_frames_batch": (i32, [i32, vp, vp, i32, vp, vp, ctypes.c_int64, vp, vp, vp, i32]),
+            "hb_cblosc_getpoints_frames_batch_workspace": (sz, [i32, vp, vp, i32, vp, vp, ctypes.c_int64]),
+            "hb_cblosc_getpoints_frames_batch_device": (i32, [i32, vp, vp, vp, i32, vp, vp, ctypes.c_int64, vp, vp, vp, sz, vp, vp]),
+            "hb_cblosc_getpoints_frames_batch": (i32, [i32, vp, vp, i32, vp, vp, ctypes.c_int64, vp, vp, vp, i32]),
             "hb_cblosc_compress_boxes_batch_workspace": (sz, [i32, vp, i32, i32]),
             "hb_cblosc_compress_boxes_batch_device": (i32, [i32, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
             "hb_cblosc_compress_boxes_batch": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, i32, i32]),
@@ -370,16 +389,17 @@ def _odometer(spans):
     return itertools.product(*[v if hasattr(v, "__iter__") else range(v) for v in spans])
 
 
-def _read_into(call, frames, pairs, out, dev, index=None, absent_ok=False):
+def _read_into(call, frames, pairs, out, dev, index=None, absent_ok=False, points=None):
     """The jobs `pairs` -- (job record, byte offset into `out`) -- through the one batch call `call`, each writing at its offset with the rest of
-    `out` as its capacity; `index`: the index array of an index batch.  Raises the first job's error."""
+    `out` as its capacity; `index`: the index array of an index batch; `points`: the point array of a point batch.  Raises the first job's
+    error."""
     nj, base, total = len(pairs), ctypes.addressof(out), len(out)
     fr, ns, keep = _frame_arrays(frames, absent_ok)
     jt = (type(pairs[0][0]) * nj)(*[p[0] for p in pairs])
     dsts = (ctypes.c_void_p * nj)(*[base + off for _, off in pairs])
     caps = (ctypes.c_size_t * nj)(*[total - off for _, off in pairs])
     rcs = (ctypes.c_int64 * nj)()
-    lists = () if index is None else ((ctypes.c_int64 * max(len(index), 1))(*index), len(index))
+    lists = _point_array(points) if points is not None else () if index is None else ((ctypes.c_int64 * max(len(index), 1))(*index), len(index))
     _check(call(len(frames), fr, ns, nj, jt, *lists, dsts, caps, rcs, device if dev is None else dev))
     for rc in rcs:
         _check(int(rc))
@@ -990,6 +1010,101 @@ def CBloscReadOIndex(frames, grid_shape, chunk_shape, selection, typesize, fill=
     fill=None that raises.  Returns the selection's bytes in C order; raises the first job's error."""
     pairs, index, out_shape = index_jobs(grid_shape, chunk_shape, selection, typesize)
     return _read_or_fill(lib().hb_cblosc_getindex_frames_batch, frames, pairs, out_shape, typesize, fill, dev, index)
+
+
+def _point_array(points):
+    """the call's point array from (item, out) pairs -- one slot at least -- and its length"""
+    buf = (hb_cblosc_point * max(len(points), 1))()
+    for i, (item, out) in enumerate(points):
+        buf[i].item, buf[i].out = int(item), int(out)
+    return buf, len(points)
+
+
+def CBloscGetPointBatch(frames, jobs, dev=None):
+    """Many coordinate selections of many chunk frames through one set of launches (include/hipblosc.h hb_cblosc_getpoints_frames_batch):
+    `jobs` are (frame_index, items, outs) tuples over `frames` -- `items` the chunk-local linear item indices in any order, repeats allowed,
+    `outs` where each goes in the job's result, in items.  Only the blocks that hold a selected item are decoded, each once.  The i-th result
+    is max(outs) + 1 items long, with `chunk.ravel()[items]` at the positions `outs` and zeros elsewhere, or the job's error (returned, not
+    raised, as CBloscGetIndexBatch does)."""
+    jobs = list(jobs)
+    nj, nf = len(jobs), len(frames)
+    if nj == 0:
+        return []
+    fr, ns, keep = _frame_arrays(frames)
+    jt, sizes, points = (hb_cblosc_point_job * nj)(), [], []
+    for j, (f, items, outs) in enumerate(jobs):
+        items, outs = [int(v) for v in items], [int(v) for v in outs]
+        if len(items) != len(outs):
+            raise ValueError("items and outs need the same number of entries")
+        jt[j] = point_job(f, len(points), len(items))
+        points.extend(zip(items, outs))
+        sizes.append(max(max(outs, default=-1) + 1, 0) * _typesize_of(keep, nf, f))
+    outbufs, dsts, caps, rcs = _out_buffers(sizes)
+    pa, npt = _point_array(points)
+    _check(lib().hb_cblosc_getpoints_frames_batch(nf, fr, ns, nj, jt, pa, npt, dsts, caps, rcs, device if dev is None else dev))
+    return [bytes(o[:size]) if rc >= 0 else _BY_CODE.get(int(rc), HipBloscError)(f"code {rc}") for o, rc, size in zip(outbufs, rcs, sizes)]
+
+
+def point_jobs(grid_shape, chunk_shape, coords, typesize):
+    """The point jobs of `z.vindex[coords]` over a chunked array: (jobs, points) with `jobs` a list of (hb_cblosc_point_job, byte offset into
+    the output) -- one job per chunk that holds a point, in C order of the grid; every job writes into the whole output, so every offset is
+    0 -- and `points` the (item, out) pairs all of them share.  coords is a tuple of ndim equal-length integer sequences in items of the whole
+    array; point i is (coords[0][i], coords[1][i] ...), its `item` the ravelled chunk-local coordinate, its `out` i.  Chunk (c_0, c_1 ...)
+    is frame number c in C order of the grid.  Negative or out-of-range coordinates raise ValueError."""
+    nd = len(chunk_shape)
+    if not (len(grid_shape) == len(coords) == nd) or not 1 <= nd <= 4:
+        raise ValueError("grid_shape, chunk_shape and coords need the same number of entries, 1 to 4")
+    coords = [[int(v) for v in c] for c in coords]
+    if any(len(c) != len(coords[0]) for c in coords):
+        raise ValueError("the coordinate sequences need the same length")
+    if any(v < 0 or v >= g * m for c, g, m in zip(coords, grid_shape, chunk_shape) for v in c):
+        raise ValueError("a coordinate lies outside the array (negative indices are not wrapped)")
+    gstr, cstr = _c_strides(grid_shape, 1)[0], _c_strides(chunk_shape, 1)[0]      # in chunks of the grid, in items of the chunk
+    per = {}
+    for i, pt in enumerate(zip(*coords)):
+        f = sum(v // m * s for v, m, s in zip(pt, chunk_shape, gstr))
+        per.setdefault(f, []).append((sum(v % m * s for v, m, s in zip(pt, chunk_shape, cstr)), i))
+    jobs, points = [], []
+    for f in sorted(per):
+        jobs.append((point_job(f, len(points), len(per[f])), 0))
+        points.extend(per[f])
+    return jobs, points
+
+
+def CBloscReadVIndex(frames, grid_shape, chunk_shape, coords, typesize, fill=None, dev=None):
+    """`z.vindex[coords_0, coords_1 ...]` of a chunked array whose chunks are the C-Blosc-1 frames `frames`, in C order of the chunk grid
+    `grid_shape`, every chunk `chunk_shape` items of `typesize` bytes: one point job per chunk that holds a point (point_jobs), all of them
+    through one hb_cblosc_getpoints_frames_batch call into one output array.  An entry of `frames` may be None -- the store has no such chunk:
+    its points are `fill` (`typesize` bytes), written here, and with fill=None that raises.  Returns len(coords[0]) * typesize bytes, point
+    i at i * typesize; raises the first job's error."""
+    pairs, points = point_jobs(grid_shape, chunk_shape, coords, typesize)
+    ts = int(typesize)
+    absent = [p for p in pairs if frames[p[0].frame] is None]
+    if absent:
+        if fill is None:
+            raise ValueError("a selected chunk is absent and there is no fill value")
+        if len(bytes(fill)) != ts:
+            raise ValueError("fill needs typesize bytes")
+    if not pairs:
+        return b""
+    out = (ctypes.c_char * (len(points) * ts))()
+    for job, _ in absent:
+        for _, o in points[job.first: job.first + job.count]:
+            ctypes.memmove(ctypes.addressof(out) + o * ts, bytes(fill), ts)
+    pairs = [p for p in pairs if frames[p[0].frame] is not None]
+    if pairs:
+        _read_into(lib().hb_cblosc_getpoints_frames_batch, frames, pairs, out, dev, absent_ok=True, points=points)
+    return bytes(out)
+
+
+def CBloscReadMask(frames, grid_shape, chunk_shape, mask, typesize, fill=None, dev=None):
+    """`z[mask]` for a boolean numpy array `mask` of the whole array's shape: CBloscReadVIndex of np.nonzero(mask) -- the selected items in C
+    order"""
+    import numpy as np                     # (the one mirror that takes an array: a mask has no other form)
+    mask = np.asarray(mask, dtype=bool)
+    if mask.shape != tuple(g * c for g, c in zip(grid_shape, chunk_shape)):
+        raise ValueError("the mask needs the array's shape")
+    return CBloscReadVIndex(frames, grid_shape, chunk_shape, [c.tolist() for c in np.nonzero(mask)], typesize, fill, dev)
 
 
 def CBloscCompress(data, shuffle=1, typesize=4):

@@ -314,6 +314,38 @@ inline std::vector<Bytes> CBloscGetIndexBatch(const std::vector<Bytes> &frames, 
     for (size_t j = 0; j < nj; j++) out[j].resize(rc[j] > 0 ? (size_t)rc[j] : 0);
     return out;
 }
+// many coordinate selections of chunk frames through one set of launches (hb_cblosc_getpoints_frames_batch; only the blocks that hold a selected
+// item are decoded, each once): job j takes the chunk-local LINEAR item indices items[i] of frames[frame], in any order, repeats allowed, and
+// puts item i at position outs[i] of its result.  out[j] is max(outs) + 1 items long -- chunk.ravel()[items] at the positions outs, zeros
+// elsewhere -- and rc[j] is the bytes of the selected items, items.size() * typesize, or the job's HB_ERR_* code (nothing is thrown per job)
+struct PointJob { uint32_t frame; std::vector<int64_t> items, outs; };
+inline std::vector<Bytes> CBloscGetPointBatch(const std::vector<Bytes> &frames, const std::vector<PointJob> &jobs, std::vector<int64_t> &rc, int device = 0) {
+    const size_t nf = frames.size(), nj = jobs.size();
+    std::vector<Bytes> out(nj);
+    rc.assign(nj, 0);
+    if (!nj) return out;
+    std::vector<const void *> fr(nf); std::vector<size_t> ns(nf);
+    for (size_t k = 0; k < nf; k++) { fr[k] = frames[k].data(); ns[k] = frames[k].size(); }
+    std::vector<hb_cblosc_point_job> jt(nj); std::vector<void *> dst(nj); std::vector<size_t> cap(nj);
+    std::vector<hb_cblosc_point> points;
+    for (size_t j = 0; j < nj; j++) {
+        const PointJob &q = jobs[j];
+        if (q.items.size() != q.outs.size()) check(HB_ERR_BAD_ARG);
+        size_t ts = 1;
+        if (q.frame < nf && ns[q.frame] >= 16 && frames[q.frame][3]) ts = frames[q.frame][3];
+        jt[j] = hb_cblosc_point_job{q.frame, 0, (int64_t)points.size(), (int64_t)q.items.size()};
+        int64_t top = -1;
+        for (size_t i = 0; i < q.items.size(); i++) { points.push_back(hb_cblosc_point{q.items[i], q.outs[i]}); if (q.outs[i] > top) top = q.outs[i]; }
+        const uint64_t bytes = (uint64_t)(top + 1) * ts;
+        cap[j] = bytes <= 0xFFFFFFFFull ? (size_t)bytes : 0;              // (a span beyond 4 GiB is one to split: no room is made for it)
+        out[j].assign(cap[j] ? cap[j] : 1, 0);
+        dst[j] = out[j].data();
+    }
+    points.push_back(hb_cblosc_point{0, 0});                              // (never NULL)
+    check(hb_cblosc_getpoints_frames_batch((int)nf, fr.data(), ns.data(), (int)nj, jt.data(), points.data(), (int64_t)points.size() - 1, dst.data(), cap.data(), rc.data(), device));
+    for (size_t j = 0; j < nj; j++) out[j].resize(rc[j] > 0 ? cap[j] : 0);
+    return out;
+}
 // many inputs to C-Blosc-1 frames through one set of launches (hb_cblosc_compress_frames_batch; shuffle 0 / 1 / 2 = none / byte / bit, one shuffle
 // and typesize for the whole batch): out[k] is the frame hb_cblosc_compress writes for datas[k], rc[k] its byte count or its HB_ERR_* code
 // (nothing is thrown per input)

@@ -589,6 +589,58 @@ int     hb_cblosc_getindex_frames_batch_device(int nframes, const hb_cblosc_head
 int     hb_cblosc_getindex_frames_batch(int nframes, const void *const *frame, const size_t *n,
                                         int njobs, const hb_cblosc_index_job *jobs, const int64_t *index, int64_t nindex,
                                         void *const *dst, const size_t *cap, int64_t *rc, int device);
+/* ---- many coordinate selections of many C-Blosc-1 frames through ONE set of launches: `z.vindex[[r0, r1 ...], [c0, c1 ...]]`, `z[boolean_mask]`
+ *      (vindex of nonzero(mask)) and every scattered lookup of single items is, per chunk that holds a point, ONE job that owns a range of the
+ *      call's point array.  `points` is a HOST array of npoints entries in all three forms, like `jobs`; job j owns points[first .. first +
+ *      count), and jobs may share or overlap ranges.  `item` is the chunk-local LINEAR item index of the header's typesize, what
+ *      hb_cblosc_getitem calls `start` (the C layer does not know the chunk's shape: the mirrors ravel N-d coordinates); point p is written
+ *      to d_dst[j] + out * typesize.  Points come in any order and an item may appear more than once with different `out`; two points of one
+ *      call with the same destination bytes are the caller's error.
+ *      The outcome of a point is defined against hb_cblosc_getitem_device(&hdrs[f], d_frame[f], n[f], item, 1, d_dst[j] + out * typesize,
+ *      typesize, ...); the job is accepted or refused as a whole.
+ *      Device form:
+ *        - refused per job, on the host before hb_init(), d_results[j].status carrying the answer with bytes, total_bytes and flags 0, in this
+ *          order: the header, codec and geometry refusals of that call in its order (hb_cblosc_accept_codecs is honoured); HB_ERR_BAD_ARG for
+ *          first < 0, count < 0, first + count > npoints (checked without overflow), an item that hb_cblosc_getitem refuses for nitems == 1
+ *          (negative items are not wrapped), out < 0, (out + 1) * typesize overflowing 64 bits; HB_ERR_SHORT_BUFFER for cap[j] < (max out + 1) *
+ *          typesize; HB_ERR_BAD_ARG for a NULL d_frame[f], or a NULL d_dst[j] with bytes to write.  A refused job keeps its place and touches
+ *          nothing;
+ *        - count == 0: status 0, bytes 0, nothing planned or written.  Every other job: status 0, flags 1, bytes = total_bytes = count *
+ *          typesize -- or, if the plan or a stream of a block the job TOUCHES fails, HB_ERR_DECOMPRESSION_FAILED, bytes 0, nothing written;
+ *        - a block is touched iff it holds a byte of a selected item (an item straddles two blocks where the block size is no multiple of the
+ *          typesize: it touches both), whatever the order and the repeats: every distinct (frame, block) pair is planned and decoded once per
+ *          call and stands once in a job's touch list, an untouched block is never planned, decoded or read.  The fail state is per block.
+ *          Memcpyed frames are a copy: no block record exists for them.  Nothing is written outside the selected items' destination bytes.
+ *      The call as a whole: as the getitem batch, in its order (reserved != 0 and frame >= nframes: HB_ERR_BAD_ARG); its HB_ERR_BAD_ARG group
+ *      also has npoints < 0, points == NULL while some job has count > 0, and more than HB_CBLOSC_BATCH_MAX_WORK points of the accepted jobs
+ *      together or workgroups of one gather kind.
+ *      Workspace: at most the sum over the distinct touched blocks of hb_cblosc_getitem_workspace() for a one-block range +
+ *      HB_CBLOSC_POINT_BATCH_JOB_BYTES * (njobs + nframes) + HB_CBLOSC_BOX_BATCH_TOUCH_BYTES * (the number of (job, touched block) pairs) +
+ *      HB_CBLOSC_POINT_BATCH_POINT_BYTES * (the points of the accepted jobs): more points on blocks already touched add the per-point
+ *      constant only.  0 when the call as a whole would be refused, 256 for njobs == 0.
+ *      Host form: as the box batch's -- the frames go up once, the device form runs once into a packed buffer in which job j's point p lies
+ *      at p * typesize of its part, the records and the packed buffer come down in one copy each, and the host places point p at dst[j] +
+ *      out * typesize.  rc[j] is count * typesize or the job's status.  There is no per-point fallback; without a device every accepted job
+ *      answers HB_ERR_NO_DEVICE; a failed job's destination keeps the caller's bytes. ---- */
+#define HB_CBLOSC_POINT_BATCH_JOB_BYTES   512    /* workspace per job and per frame beyond the blocks */
+#define HB_CBLOSC_POINT_BATCH_POINT_BYTES 16     /* workspace per point of an accepted job */
+typedef struct hb_cblosc_point {
+    int64_t  item;             /* chunk-local linear item index, 0 <= item < nbytes / typesize */
+    int64_t  out;              /* the point goes to d_dst[j] + out * typesize; >= 0 */
+} hb_cblosc_point;
+typedef struct hb_cblosc_point_job {
+    uint32_t frame;            /* index into the frame arrays */
+    uint32_t reserved;         /* 0 */
+    int64_t  first, count;     /* its points: points[first .. first + count) of the call's point array */
+} hb_cblosc_point_job;
+size_t  hb_cblosc_getpoints_frames_batch_workspace(int nframes, const hb_cblosc_header *hdrs, const size_t *n,
+                                                   int njobs, const hb_cblosc_point_job *jobs, const hb_cblosc_point *points, int64_t npoints);
+int     hb_cblosc_getpoints_frames_batch_device(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n,
+                                                int njobs, const hb_cblosc_point_job *jobs, const hb_cblosc_point *points, int64_t npoints,
+                                                void *const *d_dst, const size_t *cap, void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
+int     hb_cblosc_getpoints_frames_batch(int nframes, const void *const *frame, const size_t *n,
+                                         int njobs, const hb_cblosc_point_job *jobs, const hb_cblosc_point *points, int64_t npoints,
+                                         void *const *dst, const size_t *cap, int64_t *rc, int device);
 /* writing the format: a frame that blosc_decompress() of c-blosc 1.x (python-blosc, numcodecs ...) reads.  shuffle: 0 none, 1 byte
  * shuffle, 2 bit shuffle (BLOSC_NOSHUFFLE / BLOSC_SHUFFLE / BLOSC_BITSHUFFLE); LZ4 streams; block size 4096 x typesize (split) or
  * 4096 (not split), so that every stream is one chunk of this library's encoder; n below 2 GiB (c-blosc's limit).  Returns the
