@@ -63,6 +63,9 @@ struct DecCtx {
 #ifndef DEC_PREFETCH
 #define DEC_PREFETCH 0                   // 1: a unit fetches ahead for the unit its wave takes next (DecPre); built, off until it is measured
 #endif
+#ifndef DEC_STAGE_DEPTH
+#define DEC_STAGE_DEPTH 4                // 16-byte vectors a lane has under way when a unit fills LDS from the stream (stage(), the literal-run unit); 1: load, wait, write, one at a time
+#endif
 #define DEC_NO_UNIT 0xFFFFFFFFu
 // What a unit fetched ahead for the unit its wave takes next (k_dec_indexed: `it + gridDim.x`), so that a unit does not begin with three
 // memory round trips in a row behind the acknowledgements of the 64 byte stores before it (entries, first window, first parse):
@@ -230,10 +233,32 @@ __device__ __forceinline__ void dec_unit(const DecCtx &c, const uint32_t u, uint
         if (last) fine = fine && left == 0 && (DEC_LD_BYTE(src + tokpos) & 15u) == 0u; else fine = fine && rem1 == left && tok1 == tokpos;
         if (!fine) { if (lane == 0) atomicExch(&plan->fail, 1u); return; }
         if (ush) {                                          // wide loads (any alignment) into the image, then the strided stores
+#if DEC_STAGE_DEPTH > 1
+            // all loads of a group first, then its LDS writes: one memory round trip per group instead of one per vector
+            // (lv is zeroed in front of the predicated load -- an else that wrote it would make every load wait for the one before).
+            // The instance with the modes at run time sits at its register limit: groups of two there, or it spills.
+            constexpr int LD = (USH < 0 && DEC_STAGE_DEPTH > 2) ? 2 : DEC_STAGE_DEPTH;
+            for (uint32_t i0 = lane * 16u; i0 < outlen; i0 += 1024u * LD) {
+                u32x4 lv[LD];
+#pragma unroll
+                for (int k = 0; k < LD; k++) {
+                    const uint32_t i = i0 + 1024u * k;
+                    lv[k] = u32x4{0u, 0u, 0u, 0u};
+                    if (i + 16u <= outlen) lv[k] = ld16u(g + i);
+                }
+#pragma unroll
+                for (int k = 0; k < LD; k++) {
+                    const uint32_t i = i0 + 1024u * k;
+                    if (i + 16u <= outlen) *(u32x4 *)(s_out + i) = lv[k];
+                    else for (uint32_t r = i; r < outlen; r++) s_out[r] = g[r];
+                }
+            }
+#else
             for (uint32_t i = lane * 16u; i < outlen; i += 1024u) {
                 if (i + 16u <= outlen) *(u32x4 *)(s_out + i) = ld16u(g + i);
                 else for (uint32_t r = i; r < outlen; r++) s_out[r] = g[r];
             }
+#endif
             wave_sync();
             pf_issue();
             dec_flush_ush<USH>(udst, s_out, outlen, lane, (uint32_t)ush, pf_commit);
@@ -266,15 +291,41 @@ __device__ __forceinline__ void dec_unit(const DecCtx &c, const uint32_t u, uint
         const uint32_t cnt = avail < DEC_IN_WIN ? avail : DEC_IN_WIN;
         const u32x4 *ga = (const u32x4 *)(g - sh + a16);
         const uint32_t nv = (cnt + 15u) >> 4;
+#if DEC_STAGE_DEPTH > 1
+        if (!there) {                                       // nv <= 64 * SV: every vector of the window is under way before the first LDS write
+            constexpr int SV = (int)(((DEC_IN_WIN + 15u) / 16u + 63u) / 64u);
+            static_assert(SV <= 4, "stage(): four vectors per lane");
+            // (named values, not an array: as one wide register tuple, the first load is waited for when the second is put in)
+            const u32x4 *gl = ga + lane; u32x4 *sl = (u32x4 *)s_in + lane;
+            const uint32_t ul = (uint32_t)lane;
+            u32x4 a0, a1, a2, a3;
+            if (SV > 0 && ul < nv) a0 = gl[0];
+            if (SV > 1 && ul + 64u < nv) a1 = gl[64];
+            if (SV > 2 && ul + 128u < nv) a2 = gl[128];
+            if (SV > 3 && ul + 192u < nv) a3 = gl[192];
+            if (SV > 0 && ul < nv) sl[0] = a0;
+            if (SV > 1 && ul + 64u < nv) sl[64] = a1;
+            if (SV > 2 && ul + 128u < nv) sl[128] = a2;
+            if (SV > 3 && ul + 192u < nv) sl[192] = a3;
+        }
+#else
         if (!there) for (uint32_t i = lane; i < nv; i += 64) ((u32x4 *)s_in)[i] = ga[i];
+#endif
         wlo = a16 > sh ? a16 - sh : 0u;
         staged = a16 + cnt - sh;
         shw = (int)sh - (int)a16;
         wave_sync();
     };
+#if DEC_STAGE_DEPTH > 1 && !DEC_PREFETCH
+    uint32_t tokv = 0;                                      // the token byte of the run the unit begins in: under way with the window's vectors
+    if (rem != HB_IDX_AT_TOKEN) tokv = (uint32_t)src[tokpos];
+    stage(0u, staged0);
+    uint32_t tok = RFL(tokv);
+#else
     stage(0u, staged0);
     uint32_t tok = 0;
     if (rem != HB_IDX_AT_TOKEN) tok = DEC_LD_BYTE(src + tokpos);
+#endif
 #define INB(i) s_in[(uint32_t)((int)(i) + shw)]              /* stream byte at slice position i (inside the window) */
     uint32_t si = 0, di = 0;
     bool at_token = false;       // state when the unit stops

@@ -1,6 +1,7 @@
 // hb_lz4.h — internal interface of the device LZ4 block codec (hb_lz4_enc.hip / hb_lz4_dec.hip).
 #pragma once
 #include "hb_common.h"
+#include <type_traits>
 
 #include "hb_format.h"
 
@@ -80,6 +81,68 @@ __device__ __forceinline__ void wave_copy_g2g(uint8_t *dst, const uint8_t *src, 
     for (uint32_t i = lane; i < body; i += 64) st16u(dst + head + i * 16u, ld16u(src + head + i * 16u));
     const uint32_t done = head + body * 16u;
     if (done + lane < len) dst[done + lane] = src[done + lane];
+}
+
+// The same copy with up to D body vectors per lane in flight, for copies that wait on HBM rather than on issue (k_stitch): the head byte,
+// the first D body vectors and the tail byte are all loaded before the first store, so a range of up to D KiB costs one memory round
+// trip, not one per vector and one each for head and tail; longer ranges go on in groups of D.  Every byte is loaded once and stored
+// once at the addresses wave_copy_g2g touches for the same arguments.  GLOBAL: dst and src are known to be device memory, which keeps
+// the accesses global_* when the pointers came out of a structure (flat_* also counts against lgkmcnt).
+// k_stitch has it behind -DSTITCH_DEPTH=D and does not use it: there it measured slower than wave_copy_g2g at every D.
+template <int D, bool GLOBAL>
+struct WaveCopyDeep {
+    typedef typename std::conditional<GLOBAL, __attribute__((address_space(1))) uint8_t, uint8_t>::type byte_t;
+    typedef typename std::conditional<GLOBAL, __attribute__((address_space(1))) hb_u128u, hb_u128u>::type vec_t;
+    byte_t *dst; const byte_t *src;                         // past the head
+    uint32_t head, body, tail;                              // bytes, vectors, bytes
+    u32x4 v[D]; uint32_t hb, tb;
+    __device__ __forceinline__ void group_load(uint32_t base, int lane) {
+#pragma unroll
+        for (int k = 0; k < D; k++) {                       // zeroed first: an else that wrote v[k] would make each load wait for the one before
+            const uint32_t i = base + 64u * k + (uint32_t)lane;
+            v[k] = u32x4{0u, 0u, 0u, 0u};
+            if (i < body) v[k] = ((const vec_t *)(src + i * 16u))->v;
+        }
+    }
+    // Every lane's loads of the group have to be back before the first store, in straight-line code: the loads and the stores are
+    // skipped by exec branches, behind which the compiler no longer knows how many are outstanding and waits for vmcnt(0) in front
+    // of every single store -- which, on gfx9, also sits out the store before it.  One use of all the values here, and none there.
+    __device__ __forceinline__ void group_arrive() {
+#pragma unroll
+        for (int k = 0; k < D; k++) asm volatile("" : "+v"(v[k]));
+    }
+    __device__ __forceinline__ void group_store(uint32_t base, int lane) {
+#pragma unroll
+        for (int k = 0; k < D; k++) {
+            const uint32_t i = base + 64u * k + (uint32_t)lane;
+            if (i < body) ((vec_t *)(dst + i * 16u))->v = v[k];
+        }
+    }
+    __device__ __forceinline__ void load(uint8_t *d, const uint8_t *s, uint32_t len, int lane) {
+        head = (uint32_t)((16u - ((uintptr_t)d & 15u)) & 15u);
+        if (head > len) head = len;
+        body = (len - head) >> 4;
+        tail = len - head - body * 16u;
+        dst = (byte_t *)(d + head); src = (const byte_t *)(s + head);
+        hb = 0; tb = 0;
+        if ((uint32_t)lane < head) hb = src[(int)lane - (int)head];
+        group_load(0u, lane);
+        if ((uint32_t)lane < tail) tb = src[body * 16u + lane];
+    }
+    __device__ __forceinline__ void store(int lane) {
+        asm volatile("" : "+v"(hb), "+v"(tb));
+        group_arrive();
+        if ((uint32_t)lane < head) dst[(int)lane - (int)head] = (uint8_t)hb;
+        group_store(0u, lane);
+        if ((uint32_t)lane < tail) dst[body * 16u + lane] = (uint8_t)tb;
+        for (uint32_t base = 64u * D; base < body; base += 64u * D) { group_load(base, lane); group_arrive(); group_store(base, lane); }
+    }
+};
+template <int D, bool GLOBAL>
+__device__ __forceinline__ void wave_copy_g2g_deep(uint8_t *dst, const uint8_t *src, uint32_t len, int lane) {
+    WaveCopyDeep<D, GLOBAL> c;
+    c.load(dst, src, len, lane);
+    c.store(lane);
 }
 
 // the same with streaming accesses (no reuse on either side: k_stitch reads a record once and writes the frame once)

@@ -1138,8 +1138,17 @@ __global__ __launch_bounds__(256) void k_scan(const Agg *__restrict__ tile_agg, 
 #ifndef STITCH_NT
 #define STITCH_NT 0     // (measured: nontemporal copies in k_stitch 0.249 -> 0.265 ms)
 #endif
+#ifndef STITCH_DEPTH
+#define STITCH_DEPTH 0  // D > 0: D body vectors per lane under way in the record and literal copies (wave_copy_g2g_deep).  Measured with D = 2, 4, 5
+                        // and never faster than one vector at a time: 0.249 -> 0.255-0.271 ms per GiB, so it is compiled out
+#endif
+#ifndef STITCH_GLOBAL
+#define STITCH_GLOBAL 1 // with STITCH_DEPTH: the copies address device memory as such (global_*), also where the batch branch took the pointers from BatchFrame
+#endif
 #if STITCH_NT
 #define STITCH_COPY wave_copy_g2g_nt
+#elif STITCH_DEPTH
+#define STITCH_COPY wave_copy_g2g_deep<STITCH_DEPTH, STITCH_GLOBAL != 0>
 #else
 #define STITCH_COPY wave_copy_g2g
 #endif
@@ -1153,7 +1162,12 @@ __global__ __launch_bounds__(STITCH_THREADS) void k_stitch(
     __shared__ Agg s[256];
     __shared__ uint32_t s_nf[256];
     __shared__ ChunkDesc s_desc[256];
-    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int t = threadIdx.x, lane = t & 63;
+#if STITCH_DEPTH
+    const int wave = __builtin_amdgcn_readfirstlane(t >> 6);          // uniform, and known to be: record and frame addresses are scalar base + lane offset
+#else
+    const int wave = t >> 6;
+#endif
     constexpr int NW = STITCH_THREADS / 64;
     uint32_t tile = blockIdx.x;                                       // tile inside its frame
     if (bf) {                                                         // batch: everything frame-local from here on
@@ -1358,7 +1372,7 @@ __global__ __launch_bounds__(STITCH_THREADS) void k_sn_pack(const ChunkDesc *__r
         const uint32_t incl = (uint32_t)__builtin_amdgcn_readfirstlane((int)s[c]);
         const uint32_t len = (uint32_t)__builtin_amdgcn_readfirstlane((int)desc[ck].enc_len);
         const uint64_t O = tbase + incl - len;
-        wave_copy_g2g(out + O, records + (size_t)ck * HB_RSTRIDE, len, lane);
+        STITCH_COPY(out + O, records + (size_t)ck * HB_RSTRIDE, len, lane);
         if (index && lane == 0) {
             uint32_t *e = (uint32_t *)(index + HB_SNX_HDR_BYTES);
             e[ck] = (uint32_t)O;
