@@ -35,6 +35,7 @@
 #include "hb_cblosc_index_batch.h"     // the geometry of an orthogonal selection, the host side of the batched index-list reads, the index arithmetic of its two gathers
 #include "hb_cblosc_point_batch.h"     // the host side of the batched point reads, the point table, the point gather's thread mapping
 #include "hb_cblosc_enc_box_batch.h"   // the geometry of a source box, the host side of the batched box writes, the gather's index arithmetic
+#include "hb_cblosc_upd_index_batch.h" // the selection updates: refusal, tables, records, and the two scatters' index arithmetic
 #include "hb_cblosc_upd_box_batch.h"   // the geometry of an update box, the host side of the batched box updates, the overlay's index arithmetic
 
 // ---- the streams of blocks [b0, b0 + nb) (hb_cblosc_getitem_device: the blocks that cover a range; the others' bstarts entries and streams
@@ -1133,6 +1134,54 @@ __global__ __launch_bounds__(64) void k_cbxu_finish(const uint32_t *__restrict__
     r->status = st; r->flags = 0; r->bytes = 0; r->total_bytes = 0; r->reserved = 0;
 }
 
+// ---- batched selection updates (hb_cblosc_update_index_batch_device; the host side and the index arithmetic are hb_cblosc_upd_index_batch.h): the
+// box updates' launch set with two scatters in the overlay's place, the inverse of the index gathers.  The staged chunk holds the base already.
+// An index occurs once in a list (the host refuses a repeat), so every chunk byte is stored by at most one thread of at most one of the two
+// launches: the new frame does not depend on the order the threads run in. ----
+template <class T> struct __attribute__((packed, aligned(1))) hb_unaligned { T v; };
+struct CbiuDeviceIO {
+    typedef u32x4 V16;
+    __device__ __forceinline__ void copy16(uint8_t *d, const uint8_t *s) { *(u32x4 *)d = ld16u_nt(s); }      // (the source is read once; the staged chunk is read next)
+    __device__ __forceinline__ void put(uint8_t *d, uint8_t v) { *d = v; }
+    __device__ __forceinline__ uint8_t get(const uint8_t *s) { return *s; }
+    __device__ __forceinline__ V16 load16(const uint8_t *s) { return ld16u_nt(s); }
+    // item c of v (c is a constant once the caller's loop is unrolled), TS bytes, to a destination aligned to TS
+    template <uint32_t TS>
+    __device__ __forceinline__ void item(uint8_t *d, const V16 &v, uint32_t c) {
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        if constexpr (TS == 1u) *d = (uint8_t)(w[c >> 2] >> (8u * (c & 3u)));
+        else if constexpr (TS == 2u) *(uint16_t *)d = (uint16_t)(w[c >> 1] >> (16u * (c & 1u)));
+        else if constexpr (TS == 4u) *(uint32_t *)d = w[c];
+        else if constexpr (TS == 8u) *(uint64_t *)d = (uint64_t)w[2u * c] | ((uint64_t)w[2u * c + 1u] << 32);
+        else *(u32x4 *)d = v;
+    }
+    template <uint32_t TS>
+    __device__ __forceinline__ void copy_item(uint8_t *d, const uint8_t *s) {
+        if constexpr (TS == 1u) *d = *s;
+        else if constexpr (TS == 2u) *(uint16_t *)d = ((const hb_unaligned<uint16_t> *)s)->v;
+        else if constexpr (TS == 4u) *(uint32_t *)d = ((const hb_unaligned<uint32_t> *)s)->v;
+        else if constexpr (TS == 8u) *(uint64_t *)d = ((const hb_unaligned<uint64_t> *)s)->v;
+        else *(u32x4 *)d = ld16u(s);
+    }
+};
+// The rows scatter: the row is a plain run.  One launch over the workgroup prefix of its jobs.  A thread owns one 16-byte-aligned slice of the
+// staged chunk intersected with one selected row (cbiu_thread_rows): one unaligned non-temporal 16-byte load and one aligned 16-byte store
+// where the slice is whole, byte by byte where the row's ends clip it; only the row's chunk offset and source offset come from tables or steps.
+__global__ __launch_bounds__(256) void k_cbiu_scatter_rows(const CbiuJob *__restrict__ jobs, const uint32_t *__restrict__ blk, uint32_t njobs, const CbiuPair *__restrict__ tab) {
+    const uint32_t i = hb_owner(blk, njobs, blockIdx.x);
+    CbiuDeviceIO io;
+    cbiu_thread_rows(jobs[i], tab, blockIdx.x - blk[i], threadIdx.x, io);
+}
+// The items scatter: the row is stepped or listed.  A thread owns cbs_items_per_unit(ts) consecutive selection items of a row
+// (cbiu_thread_items): without a src_list that is 16 contiguous source bytes, loaded once; each item is stored whole by one instruction for
+// typesize 1, 2, 4, 8 or 16, byte by byte for the others.  With a src_list the source is read per item.
+__global__ __launch_bounds__(256) void k_cbiu_scatter_items(const CbiuJob *__restrict__ jobs, const uint32_t *__restrict__ blk, uint32_t njobs, const CbiuPair *__restrict__ tab,
+                                                             uint32_t ts) {
+    const uint32_t i = hb_owner(blk, njobs, blockIdx.x);
+    CbiuDeviceIO io;
+    cbiu_thread_items(jobs[i], tab, ts, blockIdx.x - blk[i], threadIdx.x, io);
+}
+
 void hb_launch_match_selfcontained(const uint8_t *src, size_t n, void *desc, uint8_t *records, uint32_t nchunks, int accel, hipStream_t s);   // hb_lz4_enc.hip
 bool hb_launch_match_fused_selfcontained(const uint8_t *src, int typesize, void *desc, uint8_t *records, uint32_t nblk, int accel, hipStream_t s);
 void hb_launch_match_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, void *desc, uint8_t *records, uint32_t total_chunks, int accel, hipStream_t s);
@@ -1806,6 +1855,84 @@ int hb_cblosc_update_boxes_batch_device(int njobs, const hb_cblosc_upd_box *boxe
     // (the encoder reads the staged bytes of a base that failed to decode: they lie inside the workspace and may be anything, and the encoder
     // takes any bytes; k_cbxu_finish then overrides that frame's record)
     const int st = cbe_launch_batch(njobs, B.X.E, shuffle, typesize, wx + XL.enc, d_results, s);
+    if (st) return st;
+    if (nd) {
+        hb_prof_begin("k_cbxu_finish", s);
+        hipLaunchKernelGGL(k_cbxu_finish, dim3((unsigned)((nd + 63) / 64)), dim3(64), 0, s, (const uint32_t *)(w + L.fin), (const hb_result *)d_dres, d_results, (uint32_t)nd);
+        hb_prof_end(s);
+        HB_HIP_TRY(hipGetLastError());
+    }
+    return HB_OK;
+}
+
+// ---- many selection updates, one set of launches (include/hipblosc.h; the host side is hb_cblosc_upd_index_batch.h) ----
+size_t hb_cblosc_update_index_batch_workspace(int njobs, const hb_cblosc_upd_index *jobs, const int64_t *index, int64_t nindex, const hb_cblosc_header *old_hdrs,
+                                              const size_t *old_n, int shuffle, int typesize) {
+    return cbiu_workspace(njobs, jobs, index, nindex, old_hdrs, old_n, shuffle, typesize, hb_cblosc_accepted());
+}
+
+int hb_cblosc_update_index_batch_device(int njobs, const hb_cblosc_upd_index *jobs, const int64_t *index, int64_t nindex, const hb_cblosc_header *old_hdrs,
+                                        const void *const *d_old, const size_t *old_n, const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill,
+                                        int shuffle, int typesize, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
+    if (njobs == 0) return HB_OK;
+    if (!jobs || !old_hdrs || !d_old || !old_n || !d_src || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
+    uint8_t *w = (uint8_t *)d_work;
+    const unsigned accept = hb_cblosc_accepted();                         // (read once: the query below judges the frames as the call does)
+    CbiuBatch B;
+    const int rc = cbiu_prepare(njobs, jobs, index, nindex, old_hdrs, d_old, old_n, d_src, d_frame, cap, fill, shuffle, typesize, w, accept, B);
+    if (rc) return rc;
+    const CbxuLayout &L = B.U.L;
+    const CbxeLayout &XL = B.U.X.L;
+    const CbiuLayout &SL = B.S;
+    // (the query knows no pointers: it stages every job, decodes every old frame it cannot refuse and counts every scatter record and table
+    // entry, so this layout never exceeds it)
+    const size_t query = cbiu_workspace(njobs, jobs, index, nindex, old_hdrs, old_n, shuffle, typesize, accept);
+    if (!query) return HB_ERR_BAD_ARG;                                    // (the limits are taken as the query takes them)
+    if (work_bytes < query || query < L.total || B.U.X.E.query < B.U.X.E.L.total) return HB_ERR_SHORT_BUFFER;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t nr = B.rjobs.size(), ni = B.ijobs.size(), nt = B.tab.size(), ng = B.U.X.jobs.size(), nd = B.U.fin.size();
+    // the scatters' records, prefixes and tables, the finish list, and behind them the gather's records, prefix and fill table, go up in one
+    // copy (the buffer is read before the call returns)
+    std::vector<uint8_t> up(L.box + XL.upload, 0);
+    uint8_t *us = up.data() + L.sel;
+    if (nr) { memcpy(us + SL.rjobs, B.rjobs.data(), nr * sizeof(CbiuJob)); memcpy(us + SL.rblk, B.rblk.data(), (nr + 1) * 4); }
+    if (ni) { memcpy(us + SL.ijobs, B.ijobs.data(), ni * sizeof(CbiuJob)); memcpy(us + SL.iblk, B.iblk.data(), (ni + 1) * 4); }
+    if (nt) memcpy(us + SL.tab, B.tab.data(), nt * sizeof(CbiuPair));
+    if (nd) memcpy(up.data() + L.fin, B.U.fin.data(), nd * 4);
+    if (ng) memcpy(up.data() + L.box + XL.jobs, B.U.X.jobs.data(), ng * sizeof(CbxeJob));
+    memcpy(up.data() + L.box + XL.gblk, B.U.X.gblk.data(), (ng + 1) * 4);
+    memcpy(up.data() + L.box + XL.fill, B.U.X.table, CBXE_FILL_BYTES);
+    hb_prof_begin("cbiu_upload", s);
+    HB_HIP_TRY(hipMemcpyAsync(w, up.data(), up.size(), hipMemcpyHostToDevice, s));
+    hb_prof_end(s);
+    uint8_t *wx = w + L.box, *ws = w + L.sel;
+    hb_result *d_dres = (hb_result *)(w + L.dres);
+    if (ng) {                                                             // the fill bases, and the whole chunks that are not read where they lie
+        hb_prof_begin("k_cbxe_gather", s);
+        hipLaunchKernelGGL(k_cbxe_gather, dim3((unsigned)B.U.ggroups), dim3(256), 0, s, (const CbxeJob *)(wx + XL.jobs), (const uint32_t *)(wx + XL.gblk), (uint32_t)ng,
+                           (const uint8_t *)(wx + XL.fill), (uint32_t)typesize, cbx_recip((uint32_t)typesize));
+        hb_prof_end(s);
+    }
+    if (nd) {                                                             // the old-frame bases, straight into their staged slots
+        const int st = cbb_launch_batch((int)nd, B.U.D, w + L.dec, d_dres, s);
+        if (st) return st;
+    }
+    if (nr) {
+        hb_prof_begin("k_cbiu_scatter_rows", s);
+        hipLaunchKernelGGL(k_cbiu_scatter_rows, dim3((unsigned)B.rgroups), dim3(256), 0, s, (const CbiuJob *)(ws + SL.rjobs), (const uint32_t *)(ws + SL.rblk), (uint32_t)nr,
+                           (const CbiuPair *)(ws + SL.tab));
+        hb_prof_end(s);
+    }
+    if (ni) {
+        hb_prof_begin("k_cbiu_scatter_items", s);
+        hipLaunchKernelGGL(k_cbiu_scatter_items, dim3((unsigned)B.igroups), dim3(256), 0, s, (const CbiuJob *)(ws + SL.ijobs), (const uint32_t *)(ws + SL.iblk), (uint32_t)ni,
+                           (const CbiuPair *)(ws + SL.tab), (uint32_t)typesize);
+        hb_prof_end(s);
+    }
+    // (a base that failed to decode: as in the box updates, the encoder takes any bytes and k_cbxu_finish overrides that frame's record)
+    const int st = cbe_launch_batch(njobs, B.U.X.E, shuffle, typesize, wx + XL.enc, d_results, s);
     if (st) return st;
     if (nd) {
         hb_prof_begin("k_cbxu_finish", s);

@@ -223,7 +223,9 @@ static inline void cbi_host_plan(int nframes, const void *const *frame, const si
 // ---- the index arithmetic of the two gathers.  Rows map to workgroups as in cbx_thread / cbs_thread, and the row decomposition (i0, i1, i2)
 // in mixed radix stays as it is; an outer dimension contributes tab[R.tab[k] + i_k] where it has a table, else i_k * cstr[k].  false: a surplus
 // thread.  u: the thread's unit of its row; roff: the row's offset in the frame's decoded bytes; drow: the row's offset in the destination. ----
-CB_HD static inline bool cbi_row(const CbxJob &J, const CbiRow &R, const uint32_t *tab, uint32_t wl, uint32_t t, uint32_t &u, uint32_t &roff, uint64_t &drow) {
+// (the decomposition by itself -- the thread's row as (i0, i1, i2) and its unit u of that row -- is also what the scatters of
+// hb_cblosc_upd_index_batch.h take, whose tables are of another kind)
+CB_HD static inline bool cbi_row_index(const CbxJob &J, uint32_t wl, uint32_t t, uint32_t &u, uint32_t &i0, uint32_t &i1, uint32_t &i2) {
     const uint32_t wrow = cbx_div(wl, J.rcp_wpr), wsub = wl - wrow * J.wpr;
     const uint32_t lr = (t * J.rcp16) >> 16;
     u = wsub * 256u + t - lr * J.upr;
@@ -231,8 +233,15 @@ CB_HD static inline bool cbi_row(const CbxJob &J, const CbiRow &R, const uint32_
     const uint64_t row64 = (uint64_t)wrow * J.rpw + lr;
     if (row64 >= J.nrows) return false;
     const uint32_t row = (uint32_t)row64;
-    const uint32_t r1 = cbx_div(row, J.rcp[1]), i2 = row - r1 * J.shp[2];
-    const uint32_t i0 = cbx_div(r1, J.rcp[0]), i1 = r1 - i0 * J.shp[1];
+    const uint32_t r1 = cbx_div(row, J.rcp[1]);
+    i2 = row - r1 * J.shp[2];
+    i0 = cbx_div(r1, J.rcp[0]);
+    i1 = r1 - i0 * J.shp[1];
+    return true;
+}
+CB_HD static inline bool cbi_row(const CbxJob &J, const CbiRow &R, const uint32_t *tab, uint32_t wl, uint32_t t, uint32_t &u, uint32_t &roff, uint64_t &drow) {
+    uint32_t i0, i1, i2;
+    if (!cbi_row_index(J, wl, t, u, i0, i1, i2)) return false;
     roff = J.off0 + (R.tab[0] != CBI_NONE ? tab[R.tab[0] + i0] : i0 * J.cstr[0]) + (R.tab[1] != CBI_NONE ? tab[R.tab[1] + i1] : i1 * J.cstr[1]) +
            (R.tab[2] != CBI_NONE ? tab[R.tab[2] + i2] : i2 * J.cstr[2]);
     drow = (uint64_t)i0 * J.dstr[0] + (uint64_t)i1 * J.dstr[1] + (uint64_t)i2 * J.dstr[2];

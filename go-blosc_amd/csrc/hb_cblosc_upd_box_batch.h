@@ -122,14 +122,16 @@ static inline void cbxu_overlay_host(const CbxuGeom &g, const uint8_t *src, uint
 // ---- the batch.  The workspace: [overlay records | their workgroup prefix | the finish list] and, right behind them, the box writes' own
 // upload area go up in ONE copy; the box writes' part (records, staged chunks, the encoder's workspace: CbxeLayout relative to `box`), the
 // decoder's workspace, the decoder's records. ----
-struct CbxuLayout { size_t jobs, oblk, fin, box, dec, dres, total; };
-static inline CbxuLayout cbxu_layout(size_t noverlay, size_t ndec, size_t box_bytes, size_t dec_bytes) {
+// (`sel`: what another overlay stage uploads in place of the overlay records -- the scatters of hb_cblosc_upd_index_batch.h; nothing for boxes)
+struct CbxuLayout { size_t jobs, oblk, fin, sel, box, dec, dres, total; };
+static inline CbxuLayout cbxu_layout(size_t noverlay, size_t ndec, size_t box_bytes, size_t dec_bytes, size_t sel_bytes = 0) {
     CbxuLayout L{};
     size_t o = 0;
     auto take = [&](size_t b) { size_t at = o; o += cb_align(b); return at; };
     L.jobs = take(noverlay * sizeof(CbxuJob));
     L.oblk = take((noverlay + 1) * 4);
     L.fin = take(ndec * 4);
+    L.sel = take(sel_bytes);
     L.box = take(box_bytes);
     L.dec = take(dec_bytes);
     L.dres = take(ndec * sizeof(hb_result));
@@ -158,9 +160,37 @@ struct CbxuBatch {
     size_t query;                        // hb_cblosc_update_boxes_batch_workspace
 };
 
+// What the overlay stage is.  cbxu_prepare_ below decides bases, staging, the gather's, the decoder's and the encoder's batches for every
+// kind of update; the stage says what a job is (its refusal, its stand-in source box) and keeps the records of whatever puts the source's
+// items over the staged base.  This one is the box updates' own: CbxuJob records and their workgroup prefix, in B.jobs / B.oblk.
+struct CbxuBoxStage {
+    const hb_cblosc_upd_box *boxes;
+    CbxuBatch &B;
+    size_t noverlay;
+    bool has_jobs() const { return boxes != nullptr; }
+    void begin(size_t) { noverlay = 0; }
+    int refusal(size_t k, int typesize, CbxuGeom &g) { return cbxu_refusal(boxes[k], typesize, g); }
+    hb_cblosc_src_box src_box(size_t k) const { return cbxu_src_box(boxes[k]); }
+    bool count(size_t, const CbxuGeom &g) {                               // a job with a base and items; false: beyond the 32-bit limits
+        noverlay++;
+        B.ogroups += cbxu_groups(g);
+        return B.ogroups <= HB_CBLOSC_BATCH_MAX_WORK;
+    }
+    size_t records() const { return noverlay; }                           // CbxuJob records of the layout
+    size_t sel_bytes() const { return 0; }
+    void reserve() { B.jobs.reserve(noverlay); B.oblk.assign(1, 0u); }
+    void job(size_t, const CbxuGeom &g, const uint8_t *src, uint8_t *slot) {
+        CbxuJob J;
+        cbxu_job(g, src, slot, J);
+        B.jobs.push_back(J);
+        B.oblk.push_back(B.oblk.back() + cbxu_groups(g));
+    }
+};
+
 // HB_OK, or what the call as a whole answers.  d_old / d_src / d_frame / cap == NULL: the workspace query, which knows no pointers: it stages
 // every job and charges a job with old_n == 0 as a fill base.  `work`: d_work, for the staged addresses.
-static inline int cbxu_prepare_(int njobs, const hb_cblosc_upd_box *boxes, const hb_cblosc_header *old_hdrs, const void *const *d_old, const size_t *old_n,
+template <class STAGE>
+static inline int cbxu_prepare_(int njobs, STAGE &S, const hb_cblosc_header *old_hdrs, const void *const *d_old, const size_t *old_n,
                                 const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill, int shuffle, int typesize, uint8_t *work,
                                 unsigned accept, CbxuBatch &B) {
     B.geom.clear(); B.status.clear(); B.base.clear(); B.sb.clear(); B.ssrc.clear(); B.jobs.clear(); B.oblk.clear(); B.fin.clear();
@@ -170,16 +200,16 @@ static inline int cbxu_prepare_(int njobs, const hb_cblosc_upd_box *boxes, const
     if (njobs < 0) return HB_ERR_BAD_ARG;
     if (typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
     if (njobs == 0) { B.query = 256; return HB_OK; }
-    if (!boxes || !old_hdrs || !old_n) return HB_ERR_BAD_ARG;
+    if (!S.has_jobs() || !old_hdrs || !old_n) return HB_ERR_BAD_ARG;
     const int have = d_old != nullptr;
     if (have && (!d_src || !d_frame || !cap)) return HB_ERR_BAD_ARG;
     const size_t nj = (size_t)njobs;
     B.geom.resize(nj); B.status.assign(nj, 0); B.base.assign(nj, CBXU_NOBASE); B.sb.assign(nj, hb_cblosc_src_box{}); B.ssrc.assign(nj, nullptr);
-    size_t noverlay = 0;
+    S.begin(nj);
     std::vector<uint8_t> dec(nj, 0);
     for (size_t k = 0; k < nj; k++) {
         CbxuGeom &g = B.geom[k];
-        int st = cbxu_refusal(boxes[k], typesize, g);
+        int st = S.refusal(k, typesize, g);
         const int base = g.nobase ? CBXU_NOBASE : (old_n[k] == 0 && (!have || !d_old[k])) ? CBXU_FILL : CBXU_OLD;
         B.base[k] = (uint8_t)base;
         if (!st && base == CBXU_OLD) {
@@ -194,19 +224,15 @@ static inline int cbxu_prepare_(int njobs, const hb_cblosc_upd_box *boxes, const
         }
         B.status[k] = st;
         if (st) continue;                                                 // (sb[k] stays a box of 0 dimensions: the box writes refuse it and give it nothing)
-        B.sb[k] = cbxu_src_box(boxes[k]);
+        B.sb[k] = S.src_box(k);
         if (base == CBXU_NOBASE) { B.ssrc[k] = have ? d_src[k] : nullptr; continue; }
         for (int d = 0; d < 4; d++) B.sb[k].shape[d] = 0;                 // an all-fill chunk: staged, no source
         if (!g.e.nbytes) continue;
         if (base == CBXU_OLD) { dec[k] = 1; B.fin.push_back((uint32_t)k); }
-        if (g.e.src_bytes) {
-            noverlay++;
-            B.ogroups += cbxu_groups(g);
-            if (B.ogroups > HB_CBLOSC_BATCH_MAX_WORK) return HB_ERR_BAD_ARG;
-        }
+        if (g.e.src_bytes && !S.count(k, g)) return HB_ERR_BAD_ARG;
     }
     const size_t ndec = B.fin.size();
-    const CbxuLayout L0 = cbxu_layout(noverlay, ndec, 0, 0);
+    const CbxuLayout L0 = cbxu_layout(S.records(), ndec, 0, 0, S.sel_bytes());
     uint8_t *wbox = work ? work + L0.box : nullptr;
     int rc = cbxe_prepare_(njobs, B.sb.data(), have ? B.ssrc.data() : nullptr, d_frame, cap, fill, shuffle, typesize, wbox, B.X);
     if (rc) return rc;
@@ -226,7 +252,7 @@ static inline int cbxu_prepare_(int njobs, const hb_cblosc_upd_box *boxes, const
         }
         B.X.jobs.swap(keep); B.X.gblk.swap(gblk);
         B.ggroups = B.X.gblk.back();
-        B.jobs.reserve(noverlay); B.oblk.assign(1, 0u);
+        S.reserve();
         for (size_t k = 0; k < nj; k++) {
             const CbxuGeom &g = B.geom[k];
             if (B.status[k] || B.base[k] == CBXU_NOBASE || !g.e.nbytes) continue;
@@ -234,12 +260,7 @@ static inline int cbxu_prepare_(int njobs, const hb_cblosc_upd_box *boxes, const
             if (dec[k]) {
                 B.dh.push_back(old_hdrs[k]); B.dfrm.push_back(d_old[k]); B.dn.push_back(old_n[k]); B.dcap.push_back((size_t)g.e.nbytes); B.ddst.push_back(slot);
             }
-            if (g.e.src_bytes) {
-                CbxuJob J;
-                cbxu_job(g, (const uint8_t *)d_src[k], slot, J);
-                B.jobs.push_back(J);
-                B.oblk.push_back(B.oblk.back() + cbxu_groups(g));
-            }
+            if (g.e.src_bytes) S.job(k, g, (const uint8_t *)d_src[k], slot);
         }
     } else {
         for (size_t k = 0; k < nj; k++) if (dec[k]) { B.dh.push_back(old_hdrs[k]); B.dn.push_back(old_n[k]); }
@@ -250,14 +271,17 @@ static inline int cbxu_prepare_(int njobs, const hb_cblosc_upd_box *boxes, const
         if (rc) return rc;
         dec_bytes = B.D.L.total ? B.D.L.total : 256;
     }
-    B.L = cbxu_layout(noverlay, ndec, have ? B.X.L.total : B.X.query, dec_bytes);
+    B.L = cbxu_layout(S.records(), ndec, have ? B.X.L.total : B.X.query, dec_bytes, S.sel_bytes());
     B.query = B.L.total;
     return HB_OK;
 }
 static inline int cbxu_prepare(int njobs, const hb_cblosc_upd_box *boxes, const hb_cblosc_header *old_hdrs, const void *const *d_old, const size_t *old_n,
                                const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill, int shuffle, int typesize, uint8_t *work,
                                unsigned accept, CbxuBatch &B) {
-    try { return cbxu_prepare_(njobs, boxes, old_hdrs, d_old, old_n, d_src, d_frame, cap, fill, shuffle, typesize, work, accept, B); }
+    try {
+        CbxuBoxStage S{boxes, B, 0};
+        return cbxu_prepare_(njobs, S, old_hdrs, d_old, old_n, d_src, d_frame, cap, fill, shuffle, typesize, work, accept, B);
+    }
     catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
 }
 // hb_cblosc_update_boxes_batch_workspace: 0 when the call as a whole would be refused
@@ -273,26 +297,30 @@ static inline size_t cbxu_workspace(int njobs, const hb_cblosc_upd_box *boxes, c
 // the device buffers: old frames that follow each other exactly in host memory mirror their span (one copy), every other one lies at a
 // 16-byte-aligned offset with 64 bytes of slack; packed boxes and frames as in CbxeHostPlan.  An old frame that is not read (no base) is not
 // dereferenced.
-struct CbxuHostPlan {
+template <class JOB>
+struct CbxuHostPlanOf {
     std::vector<CbxuGeom> geom;          // per job
     std::vector<int64_t> status;         // per job: HB_ERR_BAD_ARG / HB_ERR_DATA_TOO_LARGE of cbxu_refusal, or 0
     std::vector<uint8_t> base;           // per job: CBXU_*
     std::vector<int> carried;            // the jobs the batch carries, in order
-    std::vector<hb_cblosc_upd_box> pb;   // per carried job: the box with the strides of its packed items
+    std::vector<JOB> pb;                 // per carried job: the job with the strides of its packed items
     std::vector<hb_cblosc_header> hd;    // per carried job: the old frame's header (an old-frame base only)
     std::vector<size_t> ioff, ooff, caps, foff;      // foff: the old frame in the device image (an old-frame base only)
     size_t in_bytes, out_bytes, old_bytes;
     bool span_old;
 };
-static inline void cbxu_host_plan(int njobs, const hb_cblosc_upd_box *boxes, const void *const *old, const size_t *old_n, const void *const *src, void *const *dst,
-                                  int typesize, unsigned accept, CbxuHostPlan &P) {
+typedef CbxuHostPlanOf<hb_cblosc_upd_box> CbxuHostPlan;
+// refuse(k, g): the per-job refusals that need no pointer; packed(k): job k as the device form gets it, over its packed items
+template <class JOB, class REFUSE, class PACKED>
+static inline void cbxu_host_plan_(int njobs, const void *const *old, const size_t *old_n, const void *const *src, void *const *dst, int typesize, unsigned accept,
+                                   CbxuHostPlanOf<JOB> &P, REFUSE refuse, PACKED packed) {
     const size_t nj = (size_t)njobs;
     P.geom.resize(nj); P.status.assign(nj, 0); P.base.assign(nj, CBXU_NOBASE);
     P.carried.clear(); P.pb.clear(); P.hd.clear(); P.ioff.clear(); P.ooff.clear(); P.caps.clear(); P.foff.clear();
     P.in_bytes = P.out_bytes = P.old_bytes = 0; P.span_old = false;
     for (size_t k = 0; k < nj; k++) {
         CbxuGeom &g = P.geom[k];
-        P.status[k] = cbxu_refusal(boxes[k], typesize, g);
+        P.status[k] = refuse(k, g);
         P.base[k] = (uint8_t)(g.nobase ? CBXU_NOBASE : (!old[k] && old_n[k] == 0) ? CBXU_FILL : CBXU_OLD);
         if (P.status[k] || !dst[k] || (!src[k] && g.e.src_bytes)) continue;     // (refused here, or the host sequence's to refuse)
         hb_cblosc_header h{};
@@ -302,10 +330,7 @@ static inline void cbxu_host_plan(int njobs, const hb_cblosc_upd_box *boxes, con
                 cbb_refusal(h, 1, old[k], old[k], old_n[k], (size_t)g.e.nbytes, &mode, accept) != HB_OK)
                 continue;
         }
-        hb_cblosc_upd_box p = boxes[k];
-        int64_t stride = typesize;
-        for (int d = (int)p.ndim - 1; d >= 0; d--) { p.src_stride[d] = stride; stride *= p.shape[d] > 0 ? p.shape[d] : 1; }
-        P.carried.push_back((int)k); P.pb.push_back(p); P.hd.push_back(h);
+        P.carried.push_back((int)k); P.pb.push_back(packed(k)); P.hd.push_back(h);
         P.ioff.push_back(P.in_bytes); P.ooff.push_back(P.out_bytes);
         P.caps.push_back(cbe_bound((size_t)g.e.nbytes, typesize) + 64);
         P.in_bytes += ((size_t)g.e.src_bytes + 64 + 15) & ~(size_t)15;
@@ -332,4 +357,14 @@ static inline void cbxu_host_plan(int njobs, const hb_cblosc_upd_box *boxes, con
         P.old_bytes += P.span_old ? old_n[k] : (old_n[k] + 64 + 15) & ~(size_t)15;
     }
     if (P.span_old) P.old_bytes += 64;
+}
+static inline void cbxu_host_plan(int njobs, const hb_cblosc_upd_box *boxes, const void *const *old, const size_t *old_n, const void *const *src, void *const *dst,
+                                  int typesize, unsigned accept, CbxuHostPlan &P) {
+    cbxu_host_plan_(njobs, old, old_n, src, dst, typesize, accept, P, [&](size_t k, CbxuGeom &g) { return cbxu_refusal(boxes[k], typesize, g); },
+                    [&](size_t k) {
+                        hb_cblosc_upd_box p = boxes[k];
+                        int64_t stride = typesize;
+                        for (int d = (int)p.ndim - 1; d >= 0; d--) { p.src_stride[d] = stride; stride *= p.shape[d] > 0 ? p.shape[d] : 1; }
+                        return p;
+                    });
 }

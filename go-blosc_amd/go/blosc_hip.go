@@ -2166,3 +2166,273 @@ func CBloscUpdateRegion(frames [][]byte, arrayShape, chunkShape []int64, region 
 	}
 	return res, nil
 }
+
+// UpdIndex is one chunk of CBloscUpdateIndexBatchHIP: an orthogonal selection of a C-order chunk of ChunkShape items is replaced by items of
+// Src.  Dimension k is the slice Start[k] + i*Step[k], i < Count[k], or -- where List[k] is not empty -- the chunk-local indices List[k] in
+// that order, none of them twice (Start, Count, Step of that dimension are then not looked at).  Selection item i of dimension k is read at
+// source coordinate i, or at SrcList[k][i] where SrcList[k] is not empty (as long as List[k]); neighbours along dimension k of the source lie
+// SrcStride[k] BYTES apart (1 to 4 dimensions; the last stride is the typeSize).  List and SrcList are nil or have one entry per dimension.
+// Every other item is the old frame's, Old -- or the fill value where Old is nil.
+type UpdIndex struct {
+	Old, Src                                   []byte
+	ChunkShape, Start, Count, Step, SrcStride []int64
+	List, SrcList                              [][]int64
+}
+
+// CBloscUpdateIndexBatchHIP writes the NEW chunk frames of `z[::2, 3::8] = v` and `z.oindex[rows, cols] = v` through ONE set of kernel
+// launches (hb_cblosc_update_index_batch): per touched chunk the old frame is decoded on the device, the selected items are scattered over it,
+// and the chunk is encoded again; frames stay immutable, the caller swaps the new ones in.  The sources (up to the last byte a selection
+// reads) and the old frames go into one pinned slab, the new frames come back in another; the lists of all jobs share one index array.
+// out[k], errs[k] are what CompressCBlosc gives for the updated chunk, or the job's error.  `fill`: typeSize bytes; nil: zeros.  Without a
+// device every job gets the no-device error: there is no CPU path.  Go memory is borrowed for the call only.  Like the rest of this file:
+// written against the C ABI, it has never met a compiler -- this image has no Go toolchain.
+func CBloscUpdateIndexBatchHIP(jobs []UpdIndex, fill []byte, shuffle Shuffle, typeSize int) ([][]byte, []error) {
+	n := len(jobs)
+	out := make([][]byte, n)
+	errs := make([]error, n)
+	if n == 0 {
+		return out, errs
+	}
+	failAll := func(code C.int64_t) ([][]byte, []error) {
+		for k := range jobs {
+			errs[k] = hbError(code)
+		}
+		return out, errs
+	}
+	if !useHIP {
+		return failAll(C.int64_t(C.HB_ERR_NO_DEVICE))
+	}
+	if typeSize < 1 || typeSize > 255 || (fill != nil && len(fill) != typeSize) {
+		return failAll(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	jt := make([]C.hb_cblosc_upd_index, n)
+	caps := make([]C.size_t, n)
+	oldN := make([]C.size_t, n)
+	rcs := make([]C.int64_t, n)
+	span := make([]int64, n) // the bytes of Src that go up: first byte to the last byte of the last item a valid selection reads
+	var index []C.int64_t
+	var inBytes, outBytes C.size_t
+	for k, q := range jobs {
+		nd := len(q.ChunkShape)
+		if nd < 1 || nd > int(C.HB_CBLOSC_BOX_MAX_NDIM) || len(q.Start) != nd || len(q.Count) != nd || len(q.Step) != nd || len(q.SrcStride) != nd ||
+			(q.List != nil && len(q.List) != nd) || (q.SrcList != nil && len(q.SrcList) != nd) {
+			return failAll(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+		jt[k].ndim = C.uint32_t(nd)
+		bytes := int64(typeSize)
+		need := int64(typeSize)
+		items := true
+		for d := nd - 1; d >= 0; d-- {
+			jt[k].chunk_shape[d] = C.int64_t(q.ChunkShape[d])
+			jt[k].start[d], jt[k].count[d], jt[k].step[d] = C.int64_t(q.Start[d]), C.int64_t(q.Count[d]), C.int64_t(q.Step[d])
+			jt[k].src_stride[d] = C.int64_t(q.SrcStride[d])
+			jt[k].list[d], jt[k].src_list[d] = -1, -1
+			last := q.Count[d] - 1 // the largest source coordinate of the dimension
+			if q.List != nil && len(q.List[d]) > 0 {
+				jt[k].list[d], jt[k].start[d], jt[k].step[d] = C.int64_t(len(index)), 0, 1
+				jt[k].count[d] = C.int64_t(len(q.List[d]))
+				for _, v := range q.List[d] {
+					index = append(index, C.int64_t(v))
+				}
+				last = int64(len(q.List[d])) - 1
+				if q.SrcList != nil && len(q.SrcList[d]) > 0 {
+					if len(q.SrcList[d]) != len(q.List[d]) {
+						return failAll(C.int64_t(C.HB_ERR_BAD_ARG))
+					}
+					jt[k].src_list[d] = C.int64_t(len(index))
+					last = 0
+					for _, v := range q.SrcList[d] {
+						index = append(index, C.int64_t(v))
+						if v > last {
+							last = v
+						}
+					}
+				}
+			} else if q.SrcList != nil && len(q.SrcList[d]) > 0 {
+				return failAll(C.int64_t(C.HB_ERR_BAD_ARG))
+			}
+			if last < 0 || q.SrcStride[d] < 0 {
+				items = false // (an empty count, or a job the library refuses)
+			} else {
+				need += last * q.SrcStride[d]
+			}
+			m := q.ChunkShape[d]
+			if m < 0 {
+				m = 0 // (refused by the library)
+			}
+			if m > 0 && bytes > (1<<31)/m { // (a chunk beyond 2 GiB is refused by the library: no room is needed for it)
+				bytes = 1 << 31
+			} else {
+				bytes *= m
+			}
+		}
+		if items && q.Src != nil {
+			if need > int64(len(q.Src)) {
+				return failAll(C.int64_t(C.HB_ERR_BAD_ARG)) // a selection that reaches beyond its source never gets to the library
+			}
+			span[k] = need
+		}
+		caps[k] = 16
+		if bytes < 1<<31 {
+			caps[k] = C.hb_cblosc_bound(C.size_t(bytes), C.int(typeSize))
+		}
+		inBytes += (C.size_t(span[k]) + 15) &^ 15
+		if q.Old != nil {
+			oldN[k] = C.size_t(len(q.Old))
+			inBytes += (oldN[k] + 15) &^ 15
+		}
+		outBytes += caps[k]
+	}
+	index = append(index, 0) // (one slot at least)
+	ptrBytes := C.size_t(unsafe.Sizeof(uintptr(0)))
+	srcs := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(n) * ptrBytes))[:n:n]
+	olds := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(n) * ptrBytes))[:n:n]
+	dsts := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(n) * ptrBytes))[:n:n]
+	defer C.free(unsafe.Pointer(&srcs[0]))
+	defer C.free(unsafe.Pointer(&olds[0]))
+	defer C.free(unsafe.Pointer(&dsts[0]))
+	slabIn, slabOut := C.hb_host_alloc(inBytes+64), C.hb_host_alloc(outBytes+64)
+	if slabIn == nil || slabOut == nil {
+		C.hb_host_free(slabIn)
+		C.hb_host_free(slabOut)
+		return failAll(C.int64_t(C.HB_ERR_HIP))
+	}
+	defer C.hb_host_free(slabIn)
+	defer C.hb_host_free(slabOut)
+	var io, oo C.size_t
+	for k, q := range jobs {
+		srcs[k] = nil
+		if span[k] > 0 {
+			srcs[k] = unsafe.Add(slabIn, uintptr(io))
+			copy(unsafe.Slice((*byte)(srcs[k]), int(span[k])), q.Src[:span[k]])
+		} else if q.Src != nil {
+			srcs[k] = slabIn // (no item is read; a refused job is refused whatever its source)
+		}
+		io += (C.size_t(span[k]) + 15) &^ 15
+		olds[k] = nil
+		if q.Old != nil {
+			olds[k] = unsafe.Add(slabIn, uintptr(io))
+			copy(unsafe.Slice((*byte)(olds[k]), len(q.Old)), q.Old)
+			io += (oldN[k] + 15) &^ 15
+		}
+		dsts[k] = unsafe.Add(slabOut, uintptr(oo))
+		oo += caps[k]
+	}
+	var fillPtr unsafe.Pointer
+	if fill != nil {
+		fillPtr = C.malloc(C.size_t(typeSize))
+		defer C.free(fillPtr)
+		copy(unsafe.Slice((*byte)(fillPtr), typeSize), fill)
+	}
+	if rc := C.hb_cblosc_update_index_batch(C.int(n), &jt[0], &index[0], C.int64_t(len(index)-1), &olds[0], &oldN[0], &srcs[0], &dsts[0], &caps[0], &rcs[0], fillPtr, C.int(shuffle), C.int(typeSize), C.int(Device)); rc != C.HB_OK {
+		return failAll(C.int64_t(rc))
+	}
+	for k := range jobs {
+		if rcs[k] < 0 {
+			errs[k] = hbError(rcs[k])
+		} else {
+			out[k] = append([]byte(nil), unsafe.Slice((*byte)(dsts[k]), int(rcs[k]))...)
+		}
+	}
+	return out, errs
+}
+
+// CBloscUpdateOIndex is `z.oindex[sel_0, sel_1 ...] = data` of a chunked array whose chunks are the C-Blosc-1 frames `frames`, in C order of
+// the chunk grid ceil(arrayShape / chunkShape); a nil frame is a chunk the store does not have, its base is `fill`.  selection[k] holds the
+// array-level indices of dimension k in any order (a stepped slice is the list lo, lo+step ...); `data` holds one item per combination of
+// entries, in C order.  An index that is repeated in a list keeps its LAST occurrence, as numpy assignment does in practice; the earlier ones
+// appear in no job.  Per dimension the entries of a chunk are grouped with their positions in the list as the job's SrcList, so there is
+// exactly ONE job per touched chunk, all of them through one CBloscUpdateIndexBatchHIP call.  It returns the new frames of the touched chunks
+// keyed by their grid index and leaves `frames` as it is; the first job's error ends it.
+func CBloscUpdateOIndex(frames [][]byte, arrayShape, chunkShape []int64, selection [][]int64, data []byte, typeSize int, shuffle Shuffle, fill []byte) (map[int][]byte, error) {
+	nd := len(chunkShape)
+	if nd < 1 || nd > int(C.HB_CBLOSC_BOX_MAX_NDIM) || len(arrayShape) != nd || len(selection) != nd || typeSize < 1 {
+		return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	type part struct {
+		chunk      int64
+		list, from []int64
+	}
+	grid := make([]int64, nd)
+	strides := make([]int64, nd)
+	parts := make([][]part, nd)
+	total := int64(typeSize)
+	nchunks := int64(1)
+	for d := nd - 1; d >= 0; d-- {
+		if chunkShape[d] < 1 || arrayShape[d] < 0 {
+			return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+		grid[d] = (arrayShape[d] + chunkShape[d] - 1) / chunkShape[d]
+		nchunks *= grid[d]
+		strides[d] = total
+		total *= int64(len(selection[d]))
+		last := map[int64]int64{} // a repeated index: its last position
+		for i, v := range selection[d] {
+			if v < 0 || v >= arrayShape[d] {
+				return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG)) // (negative indices are not wrapped)
+			}
+			last[v] = int64(i)
+		}
+		at := map[int64]int{}
+		for i, v := range selection[d] { // in the order of the positions that count
+			if last[v] != int64(i) {
+				continue
+			}
+			ch := v / chunkShape[d]
+			p, ok := at[ch]
+			if !ok {
+				p = len(parts[d])
+				at[ch] = p
+				parts[d] = append(parts[d], part{chunk: ch})
+			}
+			parts[d][p].list = append(parts[d][p].list, v-ch*chunkShape[d])
+			parts[d][p].from = append(parts[d][p].from, int64(i))
+		}
+	}
+	if int64(len(data)) != total || int64(len(frames)) != nchunks {
+		return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	res := map[int][]byte{}
+	if total == 0 {
+		return res, nil
+	}
+	idx := make([]int, nd)
+	zeros := make([]int64, nd)
+	ones := make([]int64, nd)
+	for d := range ones {
+		ones[d] = 1
+	}
+	var jobs []UpdIndex
+	var where []int
+	for {
+		f := int64(0)
+		list := make([][]int64, nd)
+		from := make([][]int64, nd)
+		for d := 0; d < nd; d++ {
+			p := parts[d][idx[d]]
+			f = f*grid[d] + p.chunk
+			list[d], from[d] = p.list, p.from
+		}
+		jobs = append(jobs, UpdIndex{Old: frames[f], Src: data, ChunkShape: chunkShape, Start: zeros, Count: zeros, Step: ones, SrcStride: strides, List: list, SrcList: from})
+		where = append(where, int(f))
+		d := nd - 1
+		for ; d >= 0; d-- {
+			idx[d]++
+			if idx[d] < len(parts[d]) {
+				break
+			}
+			idx[d] = 0
+		}
+		if d < 0 {
+			break
+		}
+	}
+	out, errs := CBloscUpdateIndexBatchHIP(jobs, fill, shuffle, typeSize)
+	for k := range jobs {
+		if errs[k] != nil {
+			return nil, errs[k]
+		}
+		res[where[k]] = out[k]
+	}
+	return res, nil
+}

@@ -111,6 +111,7 @@ EXPORTS = [
     "hb_cblosc_getpoints_frames_batch_workspace", "hb_cblosc_getpoints_frames_batch_device", "hb_cblosc_getpoints_frames_batch",
     "hb_cblosc_compress_boxes_batch_workspace", "hb_cblosc_compress_boxes_batch_device", "hb_cblosc_compress_boxes_batch",
     "hb_cblosc_update_boxes_batch_workspace", "hb_cblosc_update_boxes_batch_device", "hb_cblosc_update_boxes_batch",
+    "hb_cblosc_update_index_batch_workspace", "hb_cblosc_update_index_batch_device", "hb_cblosc_update_index_batch",
     "hb_cblosc_accept_codecs",
     "hb_queue_create", "hb_queue_create_ex", "hb_queue_destroy", "hb_queue_compress", "hb_queue_decompress", "hb_queue_wait",
 ]
@@ -223,6 +224,25 @@ def upd_box(chunk_shape, start, shape, strides):
     return hb_cblosc_upd_box(nd, 0, a(*[int(v) for v in chunk_shape]), a(*[int(v) for v in start]), a(*[int(v) for v in shape]), a(*[int(v) for v in strides]))
 
 
+class hb_cblosc_upd_index(ctypes.Structure):
+    """include/hipblosc.h hb_cblosc_upd_index: the orthogonal selection of a C-order chunk that a strided source replaces -- per dimension a
+    stepped slice or a list of indices in the call's index array, with an optional list of source coordinates beside it"""
+    _fields_ = [("ndim", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("chunk_shape", ctypes.c_int64 * 4), ("start", ctypes.c_int64 * 4),
+                ("count", ctypes.c_int64 * 4), ("step", ctypes.c_int64 * 4), ("list", ctypes.c_int64 * 4), ("src_list", ctypes.c_int64 * 4),
+                ("src_stride", ctypes.c_int64 * 4)]
+
+
+def upd_index(chunk_shape, start, count, step, lists, src_lists, strides):
+    """hb_cblosc_upd_index from sequences of ndim entries each (the entries behind them stay 0); lists[k] is -1 for a slice dimension, else
+    where the dimension's count[k] chunk-local indices start in the call's index array; src_lists[k] is -1 (selection item i comes from
+    source coordinate i), else where its count[k] source coordinates start"""
+    nd = len(chunk_shape)
+    if not (len(start) == len(count) == len(step) == len(lists) == len(src_lists) == len(strides) == nd) or nd > 4:
+        raise ValueError("chunk_shape, start, count, step, lists, src_lists and strides need the same number of entries, at most 4")
+    a = ctypes.c_int64 * 4
+    return hb_cblosc_upd_index(nd, 0, *[a(*[int(v) for v in seq]) for seq in (chunk_shape, start, count, step, lists, src_lists, strides)])
+
+
 _lib = None
 
 
@@ -315,6 +335,9 @@ def lib():
             "hb_cblosc_update_boxes_batch_workspace": (sz, [i32, vp, vp, vp, i32, i32]),
             "hb_cblosc_update_boxes_batch_device": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
             "hb_cblosc_update_boxes_batch": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32]),
+            "hb_cblosc_update_index_batch_workspace": (sz, [i32, vp, vp, i64, vp, vp, i32, i32]),
+            "hb_cblosc_update_index_batch_device": (i32, [i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
+            "hb_cblosc_update_index_batch": (i32, [i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32]),
             "hb_cblosc_accept_codecs": (i32, [ctypes.c_uint]),
         }
         for name, (res, args) in sig.items():
@@ -1293,6 +1316,166 @@ def CBloscUpdateRegion(frames, array_shape, chunk_shape, region, data, typesize,
         if isinstance(r, Exception):
             raise r
     return {f: r for (f, _, _), r in zip(jobs, res)}
+
+
+def _is_pair(sel):
+    """an (indices, source coordinates) pair: a tuple of two sequences"""
+    return isinstance(sel, tuple) and len(sel) == 2 and all(hasattr(v, "__len__") for v in sel)
+
+
+def CBloscUpdateIndexBatch(olds, srcs, jobs, fill=None, shuffle=1, typesize=4, dev=None, index=None):
+    """Many selection updates of chunk frames through one set of launches (include/hipblosc.h hb_cblosc_update_index_batch): jobs[i] is a
+    (chunk_shape, sel, strides) tuple -- sel[k] a (start, count, step) tuple, a sequence of chunk-local indices in any order (none of them
+    twice), or an (indices, source coordinates) pair of two such sequences -- and the selected items of chunk i are replaced by the items at
+    srcs[i] (a bytes-like object, an address, or None for a selection without items) with the byte strides `strides`: selection item i of a
+    dimension comes from source coordinate i, or from the coordinate the pair names.  With `index` given, jobs[i] are hb_cblosc_upd_index
+    records (upd_index) over that index array instead, as update_index_jobs makes them.  Every other item of the new chunk is the old
+    frame's olds[i], or `fill` (typesize bytes; None: zeros) where olds[i] is None.  The i-th result is the NEW frame -- what CBloscCompress
+    gives for the updated chunk -- or the job's error (returned, not raised, as CBloscUpdateBoxBatch does).  The old frames are not changed."""
+    jobs = list(jobs)
+    n = len(jobs)
+    if len(srcs) != n or len(olds) != n:
+        raise ValueError("one old frame (or None) and one source per job")
+    if fill is not None and len(fill) != typesize:
+        raise ValueError("fill needs typesize bytes")
+    if n == 0:
+        return []
+    if index is None:
+        index, recs = [], []
+        for chunk_shape, sel, strides in jobs:
+            start, count, step, lists, slists = [], [], [], [], []
+            for sl in sel:
+                if _is_triple(sl):
+                    start.append(sl[0]); count.append(sl[1]); step.append(sl[2]); lists.append(-1); slists.append(-1)
+                    continue
+                idx, sc = sl if _is_pair(sl) else (sl, None)
+                idx = [int(v) for v in idx]
+                start.append(0); count.append(len(idx)); step.append(1); lists.append(len(index))
+                index.extend(idx)
+                if sc is None:
+                    slists.append(-1)
+                else:
+                    if len(sc) != len(idx):
+                        raise ValueError("one source coordinate per index")
+                    slists.append(len(index))
+                    index.extend(int(v) for v in sc)
+            recs.append(upd_index(chunk_shape, start, count, step, lists, slists, strides))
+        jobs = recs
+    index = [int(v) for v in index]
+    keep, optr, olen, ptrs = [], [], [], []
+    for sp, q in zip(srcs, jobs):
+        if sp is None or isinstance(sp, int):
+            ptrs.append(sp)
+            continue
+        p, k, kp = _buf(sp)
+        keep.append(kp)
+        nd, span = min(q.ndim, 4), int(typesize)
+        if all(q.count[d] > 0 for d in range(nd)):
+            for d in range(nd):
+                sc = index[q.src_list[d]: q.src_list[d] + q.count[d]] if q.src_list[d] >= 0 else [q.count[d] - 1]
+                span += max(sc, default=0) * q.src_stride[d]
+            if all(q.src_stride[d] >= 0 for d in range(nd)) and span > k:
+                raise ValueError("a selection reaches beyond its source")
+        ptrs.append(p.value)
+    for o in olds:
+        if o is None:
+            optr.append(None)
+            olen.append(0)
+            continue
+        p, k, kp = _buf(o)
+        keep.append(kp)
+        optr.append(p.value)
+        olen.append(k)
+    outs, dsts, caps, rcs = _out_buffers(_frame_caps(jobs, typesize))
+    jt = (hb_cblosc_upd_index * n)(*jobs)
+    ix = (ctypes.c_int64 * max(len(index), 1))(*index)
+    fb = None if fill is None else ctypes.create_string_buffer(bytes(fill), typesize)
+    _check(lib().hb_cblosc_update_index_batch(n, jt, ix, len(index), (ctypes.c_void_p * n)(*optr), (ctypes.c_size_t * n)(*olen), (ctypes.c_void_p * n)(*ptrs), dsts, caps,
+                                              rcs, fb, int(shuffle), int(typesize), device if dev is None else dev))
+    return _results(outs, rcs)
+
+
+def update_index_jobs(array_shape, chunk_shape, selection, typesize):
+    """The jobs of `z.oindex[sel_0, sel_1 ...] = data` (and, with triples only, of `z[lo:hi:step, ...] = data`) on a chunked array: (jobs,
+    index, data_shape) with `jobs` a list of (grid index, hb_cblosc_upd_index, byte offset into data) -- exactly ONE per touched chunk, because
+    a job yields its chunk's one new frame -- `index` the index array all of them share, and the shape of `data`, a C-order array with one
+    entry per selection entry.  selection[k] is a (lo, hi, step) triple in items of the whole array, or a sequence of array-level indices in any
+    order.  An index that is repeated in a list keeps its LAST occurrence, which is what numpy assignment does in practice: the earlier
+    occurrences appear in no job (their data is not read).  Per dimension the entries that fall into one chunk are grouped, in the order of
+    their positions in the list, with those positions as the job's src_list; where the positions are consecutive the job has no src_list and
+    its offset points at the first.  The grid is ceil(array_shape / chunk_shape) and the grid index counts its chunks in C order; a chunk at
+    the array's edge keeps the full chunk shape.  Negative or out-of-range indices raise ValueError."""
+    nd = len(chunk_shape)
+    if not (len(array_shape) == len(selection) == nd) or not 1 <= nd <= 4:
+        raise ValueError("array_shape, chunk_shape and selection need the same number of entries, 1 to 4")
+    if any(c < 1 for c in chunk_shape) or any(a < 0 for a in array_shape):
+        raise ValueError("chunk_shape needs positive entries, array_shape none below 0")
+    grid = [-(-a // c) for a, c in zip(array_shape, chunk_shape)]
+    # per dimension its parts: (chunk index, first data position or 0, start inside the chunk or where the indices start in `index`, count,
+    # is a list, where the source coordinates start in `index` or -1)
+    per, data_shape, steps, index = [], [], [], []
+    for sel, a, c in zip(selection, array_shape, chunk_shape):
+        if _is_triple(sel):
+            lo, hi, st = (int(v) for v in sel)
+            if lo < 0 or hi < lo or hi > a or st < 1:
+                raise ValueError("a slice lies outside the array, or its step is below 1")
+            m = (hi - lo + st - 1) // st
+            parts = [p + (False, -1) for p in _step_parts(lo, st, m, c)]
+            steps.append(st)
+        else:
+            sel = [int(v) for v in sel]
+            if any(v < 0 or v >= a for v in sel):
+                raise ValueError("an index lies outside the array (negative indices are not wrapped)")
+            m = len(sel)
+            last = {v: i for i, v in enumerate(sel)}                                 # a repeated index: its last position
+            groups = {}
+            for v, i in sorted(last.items(), key=lambda e: e[1]):
+                groups.setdefault(v // c, []).append((v % c, i))
+            parts = []
+            for ch in sorted(groups):
+                ent = groups[ch]
+                at = len(index)
+                index.extend(v for v, _ in ent)
+                pos = [i for _, i in ent]
+                if pos == list(range(pos[0], pos[0] + len(pos))):
+                    parts.append((ch, pos[0], at, len(ent), True, -1))
+                else:
+                    parts.append((ch, 0, at, len(ent), True, len(index)))
+                    index.extend(pos)
+            steps.append(1)
+        per.append(parts)
+        data_shape.append(m)
+    strides, _ = _c_strides(data_shape, typesize)
+    jobs = []
+    for parts in _odometer(per):
+        f, off = _parts_place(parts, grid, strides)
+        jobs.append((f, upd_index(chunk_shape, [0 if p[4] else p[2] for p in parts], [p[3] for p in parts], steps, [p[2] if p[4] else -1 for p in parts],
+                                  [p[5] for p in parts], strides), off))
+    return jobs, index, data_shape
+
+
+def CBloscUpdateOIndex(frames, array_shape, chunk_shape, selection, data, typesize, shuffle=1, fill=None, dev=None):
+    """`z.oindex[sel_0, sel_1 ...] = data` of a chunked array whose chunks are the C-Blosc-1 frames `frames`, in C order of the chunk grid
+    ceil(array_shape / chunk_shape) (None: a chunk the store does not have, its base is `fill`): `data` is the selection's bytes in C order,
+    one item per combination of selection entries.  One job per touched chunk (update_index_jobs; a repeated index keeps its last
+    occurrence), all of them through one hb_cblosc_update_index_batch call.  Returns {grid index: new frame} for the touched chunks and leaves
+    `frames` as it is -- a frame is immutable, the caller swaps the new ones in; raises the first job's error."""
+    p, n, keep = _buf(data)
+    jobs, index, data_shape = update_index_jobs(array_shape, chunk_shape, selection, typesize)
+    if n != _c_strides(data_shape, typesize)[1]:
+        raise ValueError("data does not hold the selection's items")
+    res = CBloscUpdateIndexBatch([frames[f] for f, _, _ in jobs], [p.value + off for _, _, off in jobs], [q for _, q, _ in jobs], fill, shuffle, typesize, dev, index)
+    for r in res:
+        if isinstance(r, Exception):
+            raise r
+    return {f: r for (f, _, _), r in zip(jobs, res)}
+
+
+def CBloscUpdateSlices(frames, array_shape, chunk_shape, slices, data, typesize, shuffle=1, fill=None, dev=None):
+    """`z[lo_0:hi_0:step_0, lo_1:hi_1:step_1 ...] = data`: CBloscUpdateOIndex with a (lo, hi, step) triple per dimension"""
+    if not all(_is_triple(s) for s in slices):
+        raise ValueError("slices needs a (lo, hi, step) triple per dimension")
+    return CBloscUpdateOIndex(frames, array_shape, chunk_shape, slices, data, typesize, shuffle, fill, dev)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -435,6 +435,62 @@ inline std::vector<Bytes> CBloscUpdateBoxBatch(const std::vector<UpdBox> &boxes,
     for (size_t k = 0; k < nj; k++) out[k].resize(rc[k] > 0 ? (size_t)rc[k] : 0);
     return out;
 }
+// many selection updates of C-Blosc-1 chunk frames through one set of launches (hb_cblosc_update_index_batch): `z[::2, 3::8] = v` and
+// `z.oindex[rows, cols] = v` per touched chunk.  Dimension d of job k is the slice start[d] + i * step[d], i < count[d], or -- where list[d] is
+// not empty -- the chunk-local indices list[d] in that order, none of them twice (count[d], start[d], step[d] are then not looked at);
+// selection item i of the dimension is read at source coordinate i, or at src_list[d][i] where src_list[d] is not empty (as long as list[d]).
+// Every other item is the old frame's (`old`, n bytes), or `fill` (typeSize bytes; nullptr: zeros) where old == nullptr and old_n == 0.
+// out[k] is the NEW frame, rc[k] its byte count or the job's HB_ERR_* code (nothing is thrown per job); the old frame is not changed
+struct UpdIndex {
+    const void *old; size_t old_n; const void *src;
+    std::vector<int64_t> chunk_shape, start, count, step, src_stride;
+    std::vector<std::vector<int64_t>> list, src_list;                      // empty, or one entry per dimension (an empty entry: a slice dimension / no source list)
+};
+inline std::vector<Bytes> CBloscUpdateIndexBatch(const std::vector<UpdIndex> &jobs, std::vector<int64_t> &rc, const void *fill = nullptr, int shuffle = 1, int typeSize = 4,
+                                                 int device = 0) {
+    const size_t nj = jobs.size();
+    std::vector<Bytes> out(nj);
+    rc.assign(nj, 0);
+    if (!nj) return out;
+    std::vector<hb_cblosc_upd_index> jt(nj); std::vector<const void *> old(nj), src(nj); std::vector<void *> dst(nj); std::vector<size_t> on(nj), cap(nj);
+    std::vector<int64_t> index;
+    for (size_t k = 0; k < nj; k++) {
+        const UpdIndex &q = jobs[k];
+        const size_t nd = q.chunk_shape.size();
+        if (nd < 1 || nd > HB_CBLOSC_BOX_MAX_NDIM || q.start.size() != nd || q.count.size() != nd || q.step.size() != nd || q.src_stride.size() != nd ||
+            (!q.list.empty() && q.list.size() != nd) || (!q.src_list.empty() && q.src_list.size() != nd))
+            check(HB_ERR_BAD_ARG);
+        hb_cblosc_upd_index &t = jt[k];
+        t = hb_cblosc_upd_index{};
+        t.ndim = (uint32_t)nd;
+        uint64_t bytes = typeSize > 0 ? (uint64_t)typeSize : 1u;
+        for (size_t d = nd; d-- > 0;) {
+            t.chunk_shape[d] = q.chunk_shape[d]; t.start[d] = q.start[d]; t.count[d] = q.count[d]; t.step[d] = q.step[d]; t.src_stride[d] = q.src_stride[d];
+            t.list[d] = t.src_list[d] = -1;
+            if (!q.list.empty() && !q.list[d].empty()) {
+                const std::vector<int64_t> &l = q.list[d];
+                t.list[d] = (int64_t)index.size(); t.count[d] = (int64_t)l.size(); t.start[d] = 0; t.step[d] = 1;
+                index.insert(index.end(), l.begin(), l.end());
+                if (!q.src_list.empty() && !q.src_list[d].empty()) {
+                    if (q.src_list[d].size() != l.size()) check(HB_ERR_BAD_ARG);
+                    t.src_list[d] = (int64_t)index.size();
+                    index.insert(index.end(), q.src_list[d].begin(), q.src_list[d].end());
+                }
+            } else if (!q.src_list.empty() && !q.src_list[d].empty()) check(HB_ERR_BAD_ARG);
+            const uint64_t m = q.chunk_shape[d] > 0 ? (uint64_t)q.chunk_shape[d] : 0u;
+            bytes = m && bytes > (1ull << 31) / m ? (1ull << 31) : bytes * m;         // (a chunk beyond 2 GiB is refused by the library: no room is needed for it)
+        }
+        old[k] = q.old; on[k] = q.old_n; src[k] = q.src;
+        cap[k] = bytes < (1ull << 31) ? hb_cblosc_bound((size_t)bytes, typeSize) : 16;
+        out[k].resize(cap[k]);
+        dst[k] = out[k].data();
+    }
+    index.push_back(0);                                                    // (one slot at least)
+    check(hb_cblosc_update_index_batch((int)nj, jt.data(), index.data(), (int64_t)index.size() - 1, old.data(), on.data(), src.data(), dst.data(), cap.data(), rc.data(), fill,
+                                       shuffle, typeSize, device));
+    for (size_t k = 0; k < nj; k++) out[k].resize(rc[k] > 0 ? (size_t)rc[k] : 0);
+    return out;
+}
 inline Header GetInfo(const Bytes &data) { return ParseHeader(data); }                                            // blosc.go:306-308
 inline int GetDecompressedSize(const Bytes &data) { return (int)ParseHeader(data).NBytesOrig; }                   // blosc.go:311-317
 

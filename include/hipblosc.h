@@ -794,6 +794,62 @@ int     hb_cblosc_update_boxes_batch_device(int njobs, const hb_cblosc_upd_box *
                                             int shuffle, int typesize, void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
 int     hb_cblosc_update_boxes_batch(int njobs, const hb_cblosc_upd_box *boxes, const void *const *old, const size_t *old_n, const void *const *src,
                                      void *const *dst, const size_t *cap, int64_t *rc, const void *fill, int shuffle, int typesize, int device);
+/* ---- batched C-Blosc-1 selection updates: `z[::2, 3::8] = arr` and `z.oindex[rows, cols] = arr` through ONE set of launches -- the orthogonal
+ *      half of writing, the inverse of hb_cblosc_getindex_frames_batch*.  Everything is as for the box updates above (one job is one chunk:
+ *      one old frame, one source, one NEW frame; frames stay immutable) except what the selected items are.  `index` is a HOST array of nindex
+ *      entries in all three forms, shared by the jobs, as in hb_cblosc_getindex_frames_batch*.
+ *      Selection item (i_0 .. i_{ndim-1}), 0 <= i_k < count[k], is chunk coordinate c_k = list[k] >= 0 ? index[list[k] + i_k] : start[k] + i_k *
+ *      step[k] of C', the chunk after the update.  It is read from d_src[j] + sum_k s_k * src_stride[k] with the source coordinate s_k =
+ *      src_list[k] >= 0 ? index[src_list[k] + i_k] : i_k (64-bit offsets, a stride of 0 allowed, read ONLY at selected items).  src_list exists
+ *      because an unsorted array-level index list puts one chunk's entries at non-consecutive positions of the source, and a chunk can have
+ *      only one job: with it the caller never permutes its data.  Every other item of C' is the BASE, decided as for box updates; "no base"
+ *      holds where every dimension is a slice dimension with start 0, count == chunk_shape[k] and step 1 (a list that happens to be a
+ *      permutation of the whole dimension is not recognised: it gets a base, which is correct, only not the cheapest route).
+ *      A job whose dimensions are all slice dimensions, each with step 1 or count[k] == 1, writes byte for byte and with the same hb_result
+ *      what hb_cblosc_update_boxes_batch_device writes for the box start / count.
+ *      Device form: frame k is byte for byte, and with the same hb_result, what hb_cblosc_compress_dev writes for C' placed at a
+ *      16-byte-aligned address.  Refused per job, decided on the host before the device is looked for, in the box updates' order 1. to 4.;
+ *      its HB_ERR_BAD_ARG group 1. also refuses: the slice batch's geometry rules for a slice dimension (start < 0, step < 1, a last index
+ *      outside the chunk); list[k] < -1 or src_list[k] < -1; src_list[k] >= 0 where list[k] < 0; a list or source list outside [0, nindex]
+ *      (checked without overflow); a chunk index < 0 or >= chunk_shape[k]; a source coordinate < 0 or >= 2^32; A CHUNK INDEX THAT OCCURS
+ *      TWICE IN ONE LIST -- two source items would race for the same bytes, and the contract is a deterministic frame (the mirrors resolve
+ *      repeats before they build jobs: the last occurrence wins, as in numpy).  A job with some count[k] == 0 over an old frame re-encodes
+ *      the old chunk, as an empty box does; of its lists only the bounds in `index` are checked.  A dimension with count[k] == 1 is no list:
+ *      its index and its source coordinate are folded into the job's offsets.
+ *      Device-time failure, the call as a whole and asynchrony: exactly as the box updates -- THE CALLER HAS TO LOOK AT d_results[k] BEFORE IT
+ *      SWAPS d_frame[k] IN.  The call as a whole also refuses with HB_ERR_BAD_ARG (in that group, so behind "no jobs": HB_OK): nindex < 0,
+ *      index == NULL while some job has a list, and more than HB_CBLOSC_BATCH_MAX_WORK table entries, rows of one job, or workgroups of one
+ *      scatter.
+ *      Workspace: at most the box updates' bound for the same chunks and old frames with HB_CBLOSC_UPD_INDEX_JOB_BYTES as the per-job constant,
+ *      plus HB_CBLOSC_UPD_INDEX_ENTRY_BYTES times the sum of count[k] over the list dimensions of the accepted jobs: it grows with the lists'
+ *      lengths, never with rows or items.  0 when the call as a whole would be refused, 256 for njobs == 0.  The query knows no pointers.
+ *      Host form: as hb_cblosc_update_boxes_batch -- the old frames of the carried jobs go up (adjacent ones in one copy), the host packs
+ *      each job's selected source items C-contiguously in selection order (the device call sees src_list == -1 and packed strides) and they
+ *      go up in one copy, the device form runs once, records and frames come down as in hb_cblosc_compress_frames_batch.  A job the batch
+ *      did not carry or that did not end with status 0 is answered on the host: hb_cblosc_decompress of the old frame (or the fill), the naive
+ *      loops, hb_cblosc_compress; rc[k] is exactly what that sequence returns.  The refusals 1. and 2. are rc[k] directly. ---- */
+#define HB_CBLOSC_UPD_INDEX_JOB_BYTES   2048      /* workspace per job beyond the parts named above: the scatter record, prefix and finish words, alignment */
+#define HB_CBLOSC_UPD_INDEX_ENTRY_BYTES 8         /* workspace per list entry of an accepted job: chunk byte offset + source coordinate */
+typedef struct hb_cblosc_upd_index {
+    uint32_t ndim;             /* 1 .. HB_CBLOSC_BOX_MAX_NDIM */
+    uint32_t reserved;         /* 0 */
+    int64_t  chunk_shape[4];   /* items of the chunk, C order */
+    int64_t  start[4], count[4], step[4];   /* dimension k with list[k] < 0: the slice start[k] + i * step[k], rules of hb_cblosc_slice_job */
+    int64_t  list[4];          /* -1: a slice dimension.  >= 0: dimension k takes the count[k] chunk-local indices index[list[k] .. list[k] + count[k]),
+                                  in that order, none of them twice; start[k], step[k] not looked at */
+    int64_t  src_list[4];      /* -1: selection item i of dimension k is source coordinate i.  >= 0 (only where list[k] >= 0): source coordinate
+                                  index[src_list[k] + i] */
+    int64_t  src_stride[4];    /* BYTES between neighbours along dimension k in the source; >= 0; src_stride[ndim-1] == typesize */
+} hb_cblosc_upd_index;         /* entries at k >= ndim are 0 and not looked at */
+size_t  hb_cblosc_update_index_batch_workspace(int njobs, const hb_cblosc_upd_index *jobs, const int64_t *index, int64_t nindex,
+                                               const hb_cblosc_header *old_hdrs, const size_t *old_n, int shuffle, int typesize);
+int     hb_cblosc_update_index_batch_device(int njobs, const hb_cblosc_upd_index *jobs, const int64_t *index, int64_t nindex,
+                                            const hb_cblosc_header *old_hdrs, const void *const *d_old, const size_t *old_n, const void *const *d_src,
+                                            void *const *d_frame, const size_t *cap, const void *fill, int shuffle, int typesize,
+                                            void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
+int     hb_cblosc_update_index_batch(int njobs, const hb_cblosc_upd_index *jobs, const int64_t *index, int64_t nindex, const void *const *old,
+                                     const size_t *old_n, const void *const *src, void *const *dst, const size_t *cap, int64_t *rc, const void *fill,
+                                     int shuffle, int typesize, int device);
 
 #ifdef __cplusplus
 }
