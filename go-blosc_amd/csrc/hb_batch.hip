@@ -28,6 +28,7 @@
 #include "hb_cblosc_enc_box_batch.h"
 #include "hb_cblosc_upd_box_batch.h"
 #include "hb_cblosc_upd_index_batch.h"
+#include "hb_cblosc_upd_point_batch.h"
 #include <vector>
 #include <algorithm>
 #include <cstring>
@@ -1127,6 +1128,94 @@ static int cbiu_host_call(int njobs, const hb_cblosc_upd_index *jobs, const int6
 int hb_cblosc_update_index_batch(int njobs, const hb_cblosc_upd_index *jobs, const int64_t *index, int64_t nindex, const void *const *old, const size_t *old_n,
                                  const void *const *src, void *const *dst, const size_t *cap, int64_t *rc, const void *fill, int shuffle, int typesize, int device) {
     try { return cbiu_host_call(njobs, jobs, index, nindex, old, old_n, src, dst, cap, rc, fill, shuffle, typesize, device); }
+    catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
+}
+
+// Many point updates to new C-Blosc-1 frames (include/hipblosc.h).  cbpu_host_plan (hb_cblosc_upd_point_batch.h) answers what has no chunk and
+// says which jobs the batch carries: their old frames go up (adjacent ones in one copy), their source items are packed in point order and go
+// up in one copy; the device form runs once over points with src == p.  Whatever the batch does not carry, and whatever did not end with
+// status 0 on the device, is answered on the host: hb_cblosc_decompress of the old frame (or the fill), the naive loop, hb_cblosc_compress.
+static int cbpu_host_call(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints, const void *const *old, const size_t *old_n,
+                          const void *const *src, void *const *dst, const size_t *cap, int64_t *rc, const void *fill, int shuffle, int typesize, int device) {
+    if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
+    if (njobs == 0) return HB_OK;
+    if (!jobs || !old || !old_n || !src || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
+    if (cbpu_call_refused(njobs, jobs, points, npoints)) return HB_ERR_BAD_ARG;
+    CbpuHostPlan P;
+    std::vector<hb_cblosc_upd_point> pts;
+    cbpu_host_plan(njobs, jobs, points, npoints, old, old_n, src, dst, typesize, hb_cblosc_accepted(), P, pts);
+    uint8_t table[CBXE_FILL_BYTES];
+    cbxe_fill_table(fill, typesize, table);
+    auto single = [&](int k) {
+        const CbxuGeom &g = P.geom[(size_t)k];
+        const size_t nb = (size_t)g.e.nbytes;
+        std::vector<uint8_t> chunk(nb);
+        if (P.base[(size_t)k] == CBXU_OLD) {                              // the decode's answer comes first
+            hb_cblosc_header h;
+            const int prc = hb_cblosc_parse_header(old[k], old_n[k], &h);
+            if (prc) { rc[k] = prc; return; }
+            if ((int)h.typesize != typesize || (uint64_t)h.nbytes != g.e.nbytes) { rc[k] = HB_ERR_BAD_ARG; return; }
+            const int64_t drc = hb_cblosc_decompress(old[k], old_n[k], chunk.data(), nb, device);
+            if (drc < 0) { rc[k] = drc; return; }
+        } else {
+            for (size_t j = 0; j < nb; j++) chunk[j] = table[j % (size_t)typesize];
+        }
+        if (!src[k] && g.e.src_bytes) { rc[k] = hb_cblosc_compress(nullptr, nb ? nb : 1, dst[k], cap[k], shuffle, typesize, device); return; }      // (no chunk to assemble: its refusal)
+        if (nb && g.e.src_bytes) cbpu_scatter_host(jobs[k], points, typesize, (const uint8_t *)src[k], chunk.data());
+        rc[k] = hb_cblosc_compress(chunk.data(), nb, dst[k], cap[k], shuffle, typesize, device);
+    };
+    const int m = (int)P.carried.size();
+    std::vector<uint8_t> carried((size_t)njobs, 0);
+    for (int k : P.carried) carried[(size_t)k] = 1;
+    for (int k = 0; k < njobs; k++) {
+        if (P.status[(size_t)k]) rc[k] = P.status[(size_t)k];
+        else if (!carried[(size_t)k]) single(k);
+    }
+    if (m == 0) return HB_OK;
+    auto rest_single = [&]() { for (int k : P.carried) single(k); return HB_OK; };
+    if (hb_select_device(device) != HB_OK) return rest_single();
+    std::vector<hb_cblosc_header> hd((size_t)m);
+    std::vector<size_t> on((size_t)m, 0);
+    for (int i = 0; i < m; i++) {
+        const int k = P.carried[(size_t)i];
+        hd[(size_t)i] = P.hd[(size_t)i];
+        on[(size_t)i] = P.base[(size_t)k] == CBXU_OLD ? old_n[k] : 0;
+    }
+    const int64_t npk = (int64_t)pts.size();
+    const size_t wb = hb_cblosc_update_points_batch_workspace(m, P.pb.data(), pts.data(), npk, hd.data(), on.data(), shuffle, typesize);
+    if (!wb) return rest_single();                                       // (a batch beyond the 32-bit limits: one call per chunk is still right)
+    auto fail_all = [&]() { for (int k : P.carried) rc[k] = HB_ERR_HIP; return HB_OK; };
+    Scratch sc(device);
+    uint8_t *d_in = sc.get(P.in_bytes + 256), *d_old = sc.get(P.old_bytes + 256), *d_out = sc.get(P.out_bytes + 256), *d_work = sc.get(wb),
+            *d_res = sc.get((size_t)m * sizeof(hb_result));
+    if (!d_in || !d_old || !d_out || !d_work || !d_res) return fail_all();
+    d_in += (16u - ((uintptr_t)d_in & 15u)) & 15u;                       // (the plan's offsets are multiples of 16: so are the addresses)
+    d_old += (16u - ((uintptr_t)d_old & 15u)) & 15u;
+    std::vector<uint8_t> packed(P.in_bytes, 0);
+    std::vector<const void *> ps((size_t)m), po((size_t)m, nullptr); std::vector<void *> pf((size_t)m);
+    bool first_old = true;
+    for (int i = 0; i < m; i++) {
+        const int k = P.carried[(size_t)i];
+        if (P.geom[(size_t)k].e.src_bytes) cbpu_pack_host(jobs[k], points, typesize, (const uint8_t *)src[k], packed.data() + P.ioff[(size_t)i]);
+        ps[(size_t)i] = d_in + P.ioff[(size_t)i]; pf[(size_t)i] = d_out + P.ooff[(size_t)i];
+        if (P.base[(size_t)k] != CBXU_OLD) continue;
+        po[(size_t)i] = d_old + P.foff[(size_t)i];
+        if (P.span_old) {
+            if (first_old && hipMemcpyAsync(d_old, old[k], P.old_bytes - 64, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
+            first_old = false;
+        } else if (old_n[k] && hipMemcpyAsync(d_old + P.foff[(size_t)i], old[k], old_n[k], hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
+    }
+    if (P.in_bytes && hipMemcpyAsync(d_in, packed.data(), P.in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
+    const int st = hb_cblosc_update_points_batch_device(m, P.pb.data(), pts.data(), npk, hd.data(), po.data(), on.data(), ps.data(), pf.data(), P.caps.data(), fill, shuffle,
+                                                        typesize, d_work, wb, (hb_result *)d_res, nullptr);
+    if (st) { (void)hipStreamSynchronize(nullptr); return rest_single(); }     // (`packed` is pageable: the copy has to be over before it goes)
+    return cbe_host_download(P.carried, pf, d_res, dst, cap, rc, sc, single);
+}
+// (host tables that do not fit into memory: the batch is one the caller has to split -- no exception crosses the C ABI)
+int hb_cblosc_update_points_batch(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints, const void *const *old,
+                                  const size_t *old_n, const void *const *src, void *const *dst, const size_t *cap, int64_t *rc, const void *fill, int shuffle, int typesize,
+                                  int device) {
+    try { return cbpu_host_call(njobs, jobs, points, npoints, old, old_n, src, dst, cap, rc, fill, shuffle, typesize, device); }
     catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
 }
 

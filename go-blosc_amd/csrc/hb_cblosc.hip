@@ -36,6 +36,7 @@
 #include "hb_cblosc_point_batch.h"     // the host side of the batched point reads, the point table, the point gather's thread mapping
 #include "hb_cblosc_enc_box_batch.h"   // the geometry of a source box, the host side of the batched box writes, the gather's index arithmetic
 #include "hb_cblosc_upd_index_batch.h" // the selection updates: refusal, tables, records, and the two scatters' index arithmetic
+#include "hb_cblosc_upd_point_batch.h" // the point updates: refusal, point table, records, and the scatter's thread
 #include "hb_cblosc_upd_box_batch.h"   // the geometry of an update box, the host side of the batched box updates, the overlay's index arithmetic
 
 // ---- the streams of blocks [b0, b0 + nb) (hb_cblosc_getitem_device: the blocks that cover a range; the others' bstarts entries and streams
@@ -1145,6 +1146,8 @@ struct CbiuDeviceIO {
     __device__ __forceinline__ void put(uint8_t *d, uint8_t v) { *d = v; }
     __device__ __forceinline__ uint8_t get(const uint8_t *s) { return *s; }
     __device__ __forceinline__ V16 load16(const uint8_t *s) { return ld16u_nt(s); }
+    // a point table entry (16-byte aligned), whole
+    __device__ __forceinline__ CbpPoint point(const CbpPoint *p) { const u32x4 v = *(const u32x4 *)p; return CbpPoint{v.x, v.y, (uint64_t)v.z | ((uint64_t)v.w << 32)}; }
     // item c of v (c is a constant once the caller's loop is unrolled), TS bytes, to a destination aligned to TS
     template <uint32_t TS>
     __device__ __forceinline__ void item(uint8_t *d, const V16 &v, uint32_t c) {
@@ -1180,6 +1183,19 @@ __global__ __launch_bounds__(256) void k_cbiu_scatter_items(const CbiuJob *__res
     const uint32_t i = hb_owner(blk, njobs, blockIdx.x);
     CbiuDeviceIO io;
     cbiu_thread_items(jobs[i], tab, ts, blockIdx.x - blk[i], threadIdx.x, io);
+}
+
+// ---- batched point updates (hb_cblosc_update_points_batch_device; the host side and the thread are hb_cblosc_upd_point_batch.h): the box
+// updates' launch set with one scatter in the overlay's place, the inverse of the point gather.  One launch over the workgroup prefix of the
+// jobs that have points.  A thread owns one point (cbpu_thread): one 16-byte table load, coalesced over the workgroup, one item load of any
+// alignment from the source, one item store -- a single instruction for typesize 1, 2, 4, 8 and 16, byte by byte for the others.  An item
+// occurs once in a job (the host refuses a repeat), so every chunk byte is stored by at most one thread: the new frame does not depend on
+// the order the threads run in.  No LDS, no atomics. ----
+__global__ __launch_bounds__(256) void k_cbpu_scatter_points(const CbpuJob *__restrict__ jobs, const uint32_t *__restrict__ blk, uint32_t njobs, const CbpPoint *__restrict__ tab,
+                                                              uint32_t ts) {
+    const uint32_t i = hb_owner(blk, njobs, blockIdx.x);
+    CbiuDeviceIO io;
+    cbpu_thread(jobs[i], tab, ts, blockIdx.x - blk[i], threadIdx.x, io);
 }
 
 void hb_launch_match_selfcontained(const uint8_t *src, size_t n, void *desc, uint8_t *records, uint32_t nchunks, int accel, hipStream_t s);   // hb_lz4_enc.hip
@@ -1929,6 +1945,76 @@ int hb_cblosc_update_index_batch_device(int njobs, const hb_cblosc_upd_index *jo
         hb_prof_begin("k_cbiu_scatter_items", s);
         hipLaunchKernelGGL(k_cbiu_scatter_items, dim3((unsigned)B.igroups), dim3(256), 0, s, (const CbiuJob *)(ws + SL.ijobs), (const uint32_t *)(ws + SL.iblk), (uint32_t)ni,
                            (const CbiuPair *)(ws + SL.tab), (uint32_t)typesize);
+        hb_prof_end(s);
+    }
+    // (a base that failed to decode: as in the box updates, the encoder takes any bytes and k_cbxu_finish overrides that frame's record)
+    const int st = cbe_launch_batch(njobs, B.U.X.E, shuffle, typesize, wx + XL.enc, d_results, s);
+    if (st) return st;
+    if (nd) {
+        hb_prof_begin("k_cbxu_finish", s);
+        hipLaunchKernelGGL(k_cbxu_finish, dim3((unsigned)((nd + 63) / 64)), dim3(64), 0, s, (const uint32_t *)(w + L.fin), (const hb_result *)d_dres, d_results, (uint32_t)nd);
+        hb_prof_end(s);
+        HB_HIP_TRY(hipGetLastError());
+    }
+    return HB_OK;
+}
+// ---- many point updates, one set of launches (include/hipblosc.h; the host side is hb_cblosc_upd_point_batch.h) ----
+size_t hb_cblosc_update_points_batch_workspace(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints,
+                                               const hb_cblosc_header *old_hdrs, const size_t *old_n, int shuffle, int typesize) {
+    return cbpu_workspace(njobs, jobs, points, npoints, old_hdrs, old_n, shuffle, typesize, hb_cblosc_accepted());
+}
+
+int hb_cblosc_update_points_batch_device(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints, const hb_cblosc_header *old_hdrs,
+                                         const void *const *d_old, const size_t *old_n, const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill,
+                                         int shuffle, int typesize, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
+    if (njobs == 0) return HB_OK;
+    if (!jobs || !old_hdrs || !d_old || !old_n || !d_src || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
+    uint8_t *w = (uint8_t *)d_work;
+    const unsigned accept = hb_cblosc_accepted();                         // (read once: the query below judges the frames as the call does)
+    CbpuBatch B;
+    const int rc = cbpu_prepare(njobs, jobs, points, npoints, old_hdrs, d_old, old_n, d_src, d_frame, cap, fill, shuffle, typesize, w, accept, B);
+    if (rc) return rc;
+    const CbxuLayout &L = B.U.L;
+    const CbxeLayout &XL = B.U.X.L;
+    const CbpuLayout &SL = B.S;
+    // (the query knows no pointers: it stages every job, decodes every old frame it cannot refuse and counts every scatter record and point,
+    // so this layout never exceeds it; what the sweeps over the points answered is taken from B, not worked out again)
+    const size_t query = cbpu_workspace(njobs, jobs, points, npoints, old_hdrs, old_n, shuffle, typesize, accept, &B);
+    if (!query) return HB_ERR_BAD_ARG;                                    // (the limits are taken as the query takes them)
+    if (work_bytes < query || query < L.total || B.U.X.E.query < B.U.X.E.L.total) return HB_ERR_SHORT_BUFFER;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    const size_t np = B.jobs.size(), nt = B.tab.size(), ng = B.U.X.jobs.size(), nd = B.U.fin.size();
+    // the scatter's records, prefix and table, the finish list, and behind them the gather's records, prefix and fill table, go up in one
+    // copy (the buffer is read before the call returns)
+    std::vector<uint8_t> up(L.box + XL.upload, 0);
+    uint8_t *us = up.data() + L.sel;
+    if (np) { memcpy(us + SL.jobs, B.jobs.data(), np * sizeof(CbpuJob)); memcpy(us + SL.blk, B.blk.data(), (np + 1) * 4); }
+    if (nt) memcpy(us + SL.tab, B.tab.data(), nt * sizeof(CbpPoint));
+    if (nd) memcpy(up.data() + L.fin, B.U.fin.data(), nd * 4);
+    if (ng) memcpy(up.data() + L.box + XL.jobs, B.U.X.jobs.data(), ng * sizeof(CbxeJob));
+    memcpy(up.data() + L.box + XL.gblk, B.U.X.gblk.data(), (ng + 1) * 4);
+    memcpy(up.data() + L.box + XL.fill, B.U.X.table, CBXE_FILL_BYTES);
+    hb_prof_begin("cbpu_upload", s);
+    HB_HIP_TRY(hipMemcpyAsync(w, up.data(), up.size(), hipMemcpyHostToDevice, s));
+    hb_prof_end(s);
+    uint8_t *wx = w + L.box, *ws = w + L.sel;
+    hb_result *d_dres = (hb_result *)(w + L.dres);
+    if (ng) {                                                             // the fill bases
+        hb_prof_begin("k_cbxe_gather", s);
+        hipLaunchKernelGGL(k_cbxe_gather, dim3((unsigned)B.U.ggroups), dim3(256), 0, s, (const CbxeJob *)(wx + XL.jobs), (const uint32_t *)(wx + XL.gblk), (uint32_t)ng,
+                           (const uint8_t *)(wx + XL.fill), (uint32_t)typesize, cbx_recip((uint32_t)typesize));
+        hb_prof_end(s);
+    }
+    if (nd) {                                                             // the old-frame bases, straight into their staged slots
+        const int st = cbb_launch_batch((int)nd, B.U.D, w + L.dec, d_dres, s);
+        if (st) return st;
+    }
+    if (np) {
+        hb_prof_begin("k_cbpu_scatter_points", s);
+        hipLaunchKernelGGL(k_cbpu_scatter_points, dim3((unsigned)B.groups), dim3(256), 0, s, (const CbpuJob *)(ws + SL.jobs), (const uint32_t *)(ws + SL.blk), (uint32_t)np,
+                           (const CbpPoint *)(ws + SL.tab), (uint32_t)typesize);
         hb_prof_end(s);
     }
     // (a base that failed to decode: as in the box updates, the encoder takes any bytes and k_cbxu_finish overrides that frame's record)

@@ -25,6 +25,7 @@ import "C"
 
 import (
 	"fmt"
+	"sort"
 	"unsafe"
 )
 
@@ -2435,4 +2436,272 @@ func CBloscUpdateOIndex(frames [][]byte, arrayShape, chunkShape []int64, selecti
 		res[where[k]] = out[k]
 	}
 	return res, nil
+}
+
+// UpdPoint is one chunk of CBloscUpdatePointBatchHIP: point p puts item Srcs[p] of Src (typeSize bytes at Srcs[p]*typeSize) over item Items[p]
+// of a chunk of ChunkItems items -- the ravelled chunk-local index, no item twice in a job (the library refuses a repeat); many points may
+// name the same source item.  Items and Srcs are as long as each other.  Every other item is the old frame's, Old -- or the fill value where
+// Old is nil.
+type UpdPoint struct {
+	Old, Src    []byte
+	ChunkItems  int64
+	Items, Srcs []int64
+}
+
+// CBloscUpdatePointBatchHIP writes the NEW chunk frames of `z.vindex[r, c] = v` and `z[mask] = v` through ONE set of kernel launches
+// (hb_cblosc_update_points_batch): per touched chunk the old frame is decoded on the device, the points' items are scattered over it, and the
+// chunk is encoded again; frames stay immutable, the caller swaps the new ones in.  The sources (up to the last item a point reads) and the
+// old frames go into one pinned slab, the new frames come back in another; the points of all jobs share one point array.  out[k], errs[k]
+// are what CompressCBlosc gives for the updated chunk, or the job's error.  `fill`: typeSize bytes; nil: zeros.  Without a device every job
+// gets the no-device error: there is no CPU path.  Go memory is borrowed for the call only.  Like the rest of this file: written against the
+// C ABI, it has never met a compiler -- this image has no Go toolchain.
+func CBloscUpdatePointBatchHIP(jobs []UpdPoint, fill []byte, shuffle Shuffle, typeSize int) ([][]byte, []error) {
+	n := len(jobs)
+	out := make([][]byte, n)
+	errs := make([]error, n)
+	if n == 0 {
+		return out, errs
+	}
+	failAll := func(code C.int64_t) ([][]byte, []error) {
+		for k := range jobs {
+			errs[k] = hbError(code)
+		}
+		return out, errs
+	}
+	if !useHIP {
+		return failAll(C.int64_t(C.HB_ERR_NO_DEVICE))
+	}
+	if typeSize < 1 || typeSize > 255 || (fill != nil && len(fill) != typeSize) {
+		return failAll(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	jt := make([]C.hb_cblosc_upd_point_job, n)
+	caps := make([]C.size_t, n)
+	oldN := make([]C.size_t, n)
+	rcs := make([]C.int64_t, n)
+	span := make([]int64, n) // the bytes of Src that go up: first byte to the last byte of the last item a valid point reads
+	var points []C.hb_cblosc_upd_point
+	var inBytes, outBytes C.size_t
+	for k, q := range jobs {
+		if len(q.Items) != len(q.Srcs) {
+			return failAll(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+		jt[k].chunk_items = C.int64_t(q.ChunkItems)
+		jt[k].first, jt[k].count = C.int64_t(len(points)), C.int64_t(len(q.Items))
+		top := int64(-1) // the largest source item
+		valid := true
+		for p := range q.Items {
+			points = append(points, C.hb_cblosc_upd_point{item: C.int64_t(q.Items[p]), src: C.int64_t(q.Srcs[p])})
+			if q.Srcs[p] < 0 || q.Srcs[p] >= (1<<62)/int64(typeSize) {
+				valid = false // (a job the library refuses)
+			} else if q.Srcs[p] > top {
+				top = q.Srcs[p]
+			}
+		}
+		if valid && top >= 0 && q.Src != nil {
+			need := (top + 1) * int64(typeSize)
+			if need > int64(len(q.Src)) {
+				return failAll(C.int64_t(C.HB_ERR_BAD_ARG)) // a point that reaches beyond its source never gets to the library
+			}
+			span[k] = need
+		}
+		caps[k] = 16
+		if q.ChunkItems >= 0 && q.ChunkItems < (1<<31)/int64(typeSize) { // (a chunk beyond 2 GiB is refused by the library: no room is needed for it)
+			caps[k] = C.hb_cblosc_bound(C.size_t(q.ChunkItems*int64(typeSize)), C.int(typeSize))
+		}
+		inBytes += (C.size_t(span[k]) + 15) &^ 15
+		if q.Old != nil {
+			oldN[k] = C.size_t(len(q.Old))
+			inBytes += (oldN[k] + 15) &^ 15
+		}
+		outBytes += caps[k]
+	}
+	npoints := len(points)
+	points = append(points, C.hb_cblosc_upd_point{}) // (one slot at least)
+	ptrBytes := C.size_t(unsafe.Sizeof(uintptr(0)))
+	srcs := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(n) * ptrBytes))[:n:n]
+	olds := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(n) * ptrBytes))[:n:n]
+	dsts := (*[1 << 28]unsafe.Pointer)(C.malloc(C.size_t(n) * ptrBytes))[:n:n]
+	defer C.free(unsafe.Pointer(&srcs[0]))
+	defer C.free(unsafe.Pointer(&olds[0]))
+	defer C.free(unsafe.Pointer(&dsts[0]))
+	slabIn, slabOut := C.hb_host_alloc(inBytes+64), C.hb_host_alloc(outBytes+64)
+	if slabIn == nil || slabOut == nil {
+		C.hb_host_free(slabIn)
+		C.hb_host_free(slabOut)
+		return failAll(C.int64_t(C.HB_ERR_HIP))
+	}
+	defer C.hb_host_free(slabIn)
+	defer C.hb_host_free(slabOut)
+	var io, oo C.size_t
+	for k, q := range jobs {
+		srcs[k] = nil
+		if span[k] > 0 {
+			srcs[k] = unsafe.Add(slabIn, uintptr(io))
+			copy(unsafe.Slice((*byte)(srcs[k]), int(span[k])), q.Src[:span[k]])
+		} else if q.Src != nil {
+			srcs[k] = slabIn // (no item is read; a refused job is refused whatever its source)
+		}
+		io += (C.size_t(span[k]) + 15) &^ 15
+		olds[k] = nil
+		if q.Old != nil {
+			olds[k] = unsafe.Add(slabIn, uintptr(io))
+			copy(unsafe.Slice((*byte)(olds[k]), len(q.Old)), q.Old)
+			io += (oldN[k] + 15) &^ 15
+		}
+		dsts[k] = unsafe.Add(slabOut, uintptr(oo))
+		oo += caps[k]
+	}
+	var fillPtr unsafe.Pointer
+	if fill != nil {
+		fillPtr = C.malloc(C.size_t(typeSize))
+		defer C.free(fillPtr)
+		copy(unsafe.Slice((*byte)(fillPtr), typeSize), fill)
+	}
+	if rc := C.hb_cblosc_update_points_batch(C.int(n), &jt[0], &points[0], C.int64_t(npoints), &olds[0], &oldN[0], &srcs[0], &dsts[0], &caps[0], &rcs[0], fillPtr, C.int(shuffle), C.int(typeSize), C.int(Device)); rc != C.HB_OK {
+		return failAll(C.int64_t(rc))
+	}
+	for k := range jobs {
+		if rcs[k] < 0 {
+			errs[k] = hbError(rcs[k])
+		} else {
+			out[k] = append([]byte(nil), unsafe.Slice((*byte)(dsts[k]), int(rcs[k]))...)
+		}
+	}
+	return out, errs
+}
+
+// UpdatePointJobs gives the jobs of `z.vindex[coords] = data` on a chunked array: exactly ONE per chunk that holds a point, in C order of the
+// grid ceil(arrayShape / chunkShape) -- where[k] is job k's grid index, its Items the ravelled chunk-local coordinates, its Srcs the points'
+// positions in coords.  coords holds one slice per dimension, all of one length; point i is (coords[0][i], coords[1][i] ...).  A coordinate
+// tuple that occurs twice keeps its LAST occurrence, as numpy assignment does in practice: the earlier ones appear in no job.  Negative or
+// out-of-range coordinates are an error.  (Old and Src of the jobs are left nil.)
+func UpdatePointJobs(arrayShape, chunkShape []int64, coords [][]int64) ([]UpdPoint, []int, error) {
+	nd := len(chunkShape)
+	if nd < 1 || nd > int(C.HB_CBLOSC_BOX_MAX_NDIM) || len(arrayShape) != nd || len(coords) != nd {
+		return nil, nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	grid := make([]int64, nd)
+	chunkItems := int64(1)
+	for d := 0; d < nd; d++ {
+		if chunkShape[d] < 1 || arrayShape[d] < 0 || len(coords[d]) != len(coords[0]) {
+			return nil, nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+		grid[d] = (arrayShape[d] + chunkShape[d] - 1) / chunkShape[d]
+		chunkItems *= chunkShape[d]
+	}
+	np := len(coords[0])
+	last := map[[4]int64]int{} // a repeated point: its last position
+	for i := 0; i < np; i++ {
+		var pt [4]int64
+		for d := 0; d < nd; d++ {
+			pt[d] = coords[d][i]
+			if pt[d] < 0 || pt[d] >= arrayShape[d] {
+				return nil, nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG)) // (negative indices are not wrapped)
+			}
+		}
+		last[pt] = i
+	}
+	per := map[int64]*UpdPoint{}
+	var touched []int64
+	for i := 0; i < np; i++ { // in the order of the positions that count
+		var pt [4]int64
+		for d := 0; d < nd; d++ {
+			pt[d] = coords[d][i]
+		}
+		if last[pt] != i {
+			continue
+		}
+		f, item := int64(0), int64(0)
+		for d := 0; d < nd; d++ {
+			f = f*grid[d] + pt[d]/chunkShape[d]
+			item = item*chunkShape[d] + pt[d]%chunkShape[d]
+		}
+		q, ok := per[f]
+		if !ok {
+			q = &UpdPoint{ChunkItems: chunkItems}
+			per[f] = q
+			touched = append(touched, f)
+		}
+		q.Items = append(q.Items, item)
+		q.Srcs = append(q.Srcs, int64(i))
+	}
+	sort.Slice(touched, func(a, b int) bool { return touched[a] < touched[b] })
+	jobs := make([]UpdPoint, 0, len(touched))
+	where := make([]int, 0, len(touched))
+	for _, f := range touched {
+		jobs = append(jobs, *per[f])
+		where = append(where, int(f))
+	}
+	return jobs, where, nil
+}
+
+// CBloscUpdateVIndex is `z.vindex[coords_0, coords_1 ...] = data` of a chunked array whose chunks are the C-Blosc-1 frames `frames`, in C
+// order of the chunk grid ceil(arrayShape / chunkShape); a nil frame is a chunk the store does not have, its base is `fill`.  `data` holds
+// one item per point, or exactly ONE item, a scalar that every point gets.  One job per touched chunk (UpdatePointJobs; a repeated point keeps
+// its last occurrence), all of them through one CBloscUpdatePointBatchHIP call.  It returns the new frames of the touched chunks keyed by their
+// grid index -- none, without a call, where there is no point -- and leaves `frames` as it is; the first job's error ends it.
+func CBloscUpdateVIndex(frames [][]byte, arrayShape, chunkShape []int64, coords [][]int64, data []byte, typeSize int, shuffle Shuffle, fill []byte) (map[int][]byte, error) {
+	if typeSize < 1 {
+		return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	jobs, where, err := UpdatePointJobs(arrayShape, chunkShape, coords)
+	if err != nil {
+		return nil, err
+	}
+	np := len(coords[0])
+	scalar := len(data) == typeSize
+	if len(data) != np*typeSize && !scalar {
+		return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	res := map[int][]byte{}
+	if len(jobs) == 0 {
+		return res, nil
+	}
+	for k := range jobs {
+		if where[k] >= len(frames) {
+			return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+		jobs[k].Old, jobs[k].Src = frames[where[k]], data
+		if scalar {
+			for p := range jobs[k].Srcs {
+				jobs[k].Srcs[p] = 0
+			}
+		}
+	}
+	out, errs := CBloscUpdatePointBatchHIP(jobs, fill, shuffle, typeSize)
+	for k := range jobs {
+		if errs[k] != nil {
+			return nil, errs[k]
+		}
+		res[where[k]] = out[k]
+	}
+	return res, nil
+}
+
+// CBloscUpdateMask is `z[mask] = data`: CBloscUpdateVIndex of the true entries of `mask` -- one entry per item of the whole array, C order --
+// in C order; `data` holds one item per true entry, or a single item.
+func CBloscUpdateMask(frames [][]byte, arrayShape, chunkShape []int64, mask []bool, data []byte, typeSize int, shuffle Shuffle, fill []byte) (map[int][]byte, error) {
+	nd := len(arrayShape)
+	total := int64(1)
+	for _, a := range arrayShape {
+		if a < 0 {
+			return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+		total *= a
+	}
+	if nd < 1 || int64(len(mask)) != total {
+		return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	coords := make([][]int64, nd)
+	for i, m := range mask {
+		if !m {
+			continue
+		}
+		r := int64(i)
+		for d := nd - 1; d >= 0; d-- {
+			coords[d] = append(coords[d], r%arrayShape[d])
+			r /= arrayShape[d]
+		}
+	}
+	return CBloscUpdateVIndex(frames, arrayShape, chunkShape, coords, data, typeSize, shuffle, fill)
 }

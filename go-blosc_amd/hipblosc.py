@@ -112,6 +112,7 @@ EXPORTS = [
     "hb_cblosc_compress_boxes_batch_workspace", "hb_cblosc_compress_boxes_batch_device", "hb_cblosc_compress_boxes_batch",
     "hb_cblosc_update_boxes_batch_workspace", "hb_cblosc_update_boxes_batch_device", "hb_cblosc_update_boxes_batch",
     "hb_cblosc_update_index_batch_workspace", "hb_cblosc_update_index_batch_device", "hb_cblosc_update_index_batch",
+    "hb_cblosc_update_points_batch_workspace", "hb_cblosc_update_points_batch_device", "hb_cblosc_update_points_batch",
     "hb_cblosc_accept_codecs",
     "hb_queue_create", "hb_queue_create_ex", "hb_queue_destroy", "hb_queue_compress", "hb_queue_decompress", "hb_queue_wait",
 ]
@@ -243,6 +244,22 @@ def upd_index(chunk_shape, start, count, step, lists, src_lists, strides):
     return hb_cblosc_upd_index(nd, 0, *[a(*[int(v) for v in seq]) for seq in (chunk_shape, start, count, step, lists, src_lists, strides)])
 
 
+class hb_cblosc_upd_point(ctypes.Structure):
+    """include/hipblosc.h hb_cblosc_upd_point: the chunk-local linear index of the item that is written and the item of the job's source that
+    is read"""
+    _fields_ = [("item", ctypes.c_int64), ("src", ctypes.c_int64)]
+
+
+class hb_cblosc_upd_point_job(ctypes.Structure):
+    """include/hipblosc.h hb_cblosc_upd_point_job: the points written into one chunk -- a range of the call's point array"""
+    _fields_ = [("reserved", ctypes.c_uint32), ("reserved2", ctypes.c_uint32), ("chunk_items", ctypes.c_int64), ("first", ctypes.c_int64), ("count", ctypes.c_int64)]
+
+
+def upd_point_job(chunk_items, first, count):
+    """hb_cblosc_upd_point_job: the job of a chunk of `chunk_items` items that owns points[first : first + count] of the call's point array"""
+    return hb_cblosc_upd_point_job(0, 0, int(chunk_items), int(first), int(count))
+
+
 _lib = None
 
 
@@ -338,6 +355,9 @@ def lib():
             "hb_cblosc_update_index_batch_workspace": (sz, [i32, vp, vp, i64, vp, vp, i32, i32]),
             "hb_cblosc_update_index_batch_device": (i32, [i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
             "hb_cblosc_update_index_batch": (i32, [i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32]),
+            "hb_cblosc_update_points_batch_workspace": (sz, [i32, vp, vp, i64, vp, vp, i32, i32]),
+            "hb_cblosc_update_points_batch_device": (i32, [i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
+            "hb_cblosc_update_points_batch": (i32, [i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32]),
             "hb_cblosc_accept_codecs": (i32, [ctypes.c_uint]),
         }
         for name, (res, args) in sig.items():
@@ -1476,6 +1496,127 @@ def CBloscUpdateSlices(frames, array_shape, chunk_shape, slices, data, typesize,
     if not all(_is_triple(s) for s in slices):
         raise ValueError("slices needs a (lo, hi, step) triple per dimension")
     return CBloscUpdateOIndex(frames, array_shape, chunk_shape, slices, data, typesize, shuffle, fill, dev)
+
+
+def _upd_point_array(points):
+    """the call's point array from (item, src) pairs -- one slot at least -- and its length"""
+    buf = (hb_cblosc_upd_point * max(len(points), 1))()
+    for i, (item, src) in enumerate(points):
+        buf[i].item, buf[i].src = int(item), int(src)
+    return buf, len(points)
+
+
+def CBloscUpdatePointBatch(olds, srcs, jobs, points, fill=None, shuffle=1, typesize=4, dev=None):
+    """Many point updates of chunk frames through one set of launches (include/hipblosc.h hb_cblosc_update_points_batch): jobs[i] is an
+    hb_cblosc_upd_point_job (upd_point_job) that owns points[first : first + count] of `points`, a sequence of (item, src) pairs all jobs
+    share: item `item` of chunk i -- the ravelled chunk-local index, no item twice in a job -- is replaced by item `src` of srcs[i] (a
+    bytes-like object, an address, or None for a job without points).  Every other item of the new chunk is the old frame's olds[i], or
+    `fill` (typesize bytes; None: zeros) where olds[i] is None.  The i-th result is the NEW frame -- what CBloscCompress gives for the updated
+    chunk -- or the job's error (returned, not raised, as CBloscUpdateIndexBatch does).  The old frames are not changed."""
+    jobs = list(jobs)
+    n = len(jobs)
+    if len(srcs) != n or len(olds) != n:
+        raise ValueError("one old frame (or None) and one source per job")
+    if fill is not None and len(fill) != typesize:
+        raise ValueError("fill needs typesize bytes")
+    if n == 0:
+        return []
+    points = [(int(i), int(s)) for i, s in points]
+    keep, optr, olen, ptrs = [], [], [], []
+    for sp, q in zip(srcs, jobs):
+        if sp is None or isinstance(sp, int):
+            ptrs.append(sp)
+            continue
+        p, k, kp = _buf(sp)
+        keep.append(kp)
+        if 0 <= q.first and 0 < q.count <= len(points) - q.first:
+            top = max(s for _, s in points[q.first: q.first + q.count])
+            if (top + 1) * int(typesize) > k:
+                raise ValueError("a point reaches beyond its source")
+        ptrs.append(p.value)
+    for o in olds:
+        if o is None:
+            optr.append(None)
+            olen.append(0)
+            continue
+        p, k, kp = _buf(o)
+        keep.append(kp)
+        optr.append(p.value)
+        olen.append(k)
+    sizes = [q.chunk_items * int(typesize) if q.chunk_items >= 0 else None for q in jobs]
+    outs, dsts, caps, rcs = _out_buffers([lib().hb_cblosc_bound(c, typesize) if c is not None and c < (1 << 31) else 16 for c in sizes])
+    jt = (hb_cblosc_upd_point_job * n)(*jobs)
+    pa, npt = _upd_point_array(points)
+    fb = None if fill is None else ctypes.create_string_buffer(bytes(fill), typesize)
+    _check(lib().hb_cblosc_update_points_batch(n, jt, pa, npt, (ctypes.c_void_p * n)(*optr), (ctypes.c_size_t * n)(*olen), (ctypes.c_void_p * n)(*ptrs), dsts, caps, rcs, fb,
+                                               int(shuffle), int(typesize), device if dev is None else dev))
+    return _results(outs, rcs)
+
+
+def update_point_jobs(array_shape, chunk_shape, coords, typesize):
+    """The jobs of `z.vindex[coords] = data` on a chunked array: (jobs, points) with `jobs` a list of (grid index, hb_cblosc_upd_point_job) --
+    exactly ONE per chunk that holds a point, in C order of the grid ceil(array_shape / chunk_shape), because a job yields its chunk's one new
+    frame -- and `points` the (item, src) pairs all of them share.  coords is a tuple of ndim equal-length integer sequences in items of the
+    whole array; point i is (coords[0][i], coords[1][i] ...), its `item` the ravelled chunk-local coordinate, its `src` i, the point's
+    position in coords.  A coordinate tuple that occurs twice keeps its LAST occurrence, which is what numpy assignment does in practice: the
+    earlier occurrences appear in no job (their data is not read).  A chunk at the array's edge keeps the full chunk shape.  Negative or
+    out-of-range coordinates raise ValueError."""
+    nd = len(chunk_shape)
+    if not (len(array_shape) == len(coords) == nd) or not 1 <= nd <= 4:
+        raise ValueError("array_shape, chunk_shape and coords need the same number of entries, 1 to 4")
+    if any(c < 1 for c in chunk_shape) or any(a < 0 for a in array_shape):
+        raise ValueError("chunk_shape needs positive entries, array_shape none below 0")
+    coords = [[int(v) for v in c] for c in coords]
+    if any(len(c) != len(coords[0]) for c in coords):
+        raise ValueError("the coordinate sequences need the same length")
+    if any(v < 0 or v >= a for c, a in zip(coords, array_shape) for v in c):
+        raise ValueError("a coordinate lies outside the array (negative indices are not wrapped)")
+    grid = [-(-a // c) for a, c in zip(array_shape, chunk_shape)]
+    gstr, (cstr, chunk_items) = _c_strides(grid, 1)[0], _c_strides(chunk_shape, 1)      # in chunks of the grid, in items of the chunk
+    last = {pt: i for i, pt in enumerate(zip(*coords))}                                 # a repeated point: its last position
+    per = {}
+    for pt, i in sorted(last.items(), key=lambda e: e[1]):
+        f = sum(v // m * s for v, m, s in zip(pt, chunk_shape, gstr))
+        per.setdefault(f, []).append((sum(v % m * s for v, m, s in zip(pt, chunk_shape, cstr)), i))
+    jobs, points = [], []
+    for f in sorted(per):
+        jobs.append((f, upd_point_job(chunk_items, len(points), len(per[f]))))
+        points.extend(per[f])
+    return jobs, points
+
+
+def CBloscUpdateVIndex(frames, array_shape, chunk_shape, coords, data, typesize, shuffle=1, fill=None, dev=None):
+    """`z.vindex[coords_0, coords_1 ...] = data` of a chunked array whose chunks are the C-Blosc-1 frames `frames`, in C order of the chunk
+    grid ceil(array_shape / chunk_shape) (None: a chunk the store does not have, its base is `fill`): `data` holds len(coords[0]) items, item
+    i for point i, or exactly ONE item, a scalar that every point gets.  One job per touched chunk (update_point_jobs; a repeated point keeps
+    its last occurrence), all of them through one hb_cblosc_update_points_batch call.  Returns {grid index: new frame} for the touched chunks
+    -- {} without a call where there is no point -- and leaves `frames` as it is: a frame is immutable, the caller swaps the new ones in;
+    raises the first job's error."""
+    p, n, keep = _buf(data)
+    ts = int(typesize)
+    jobs, points = update_point_jobs(array_shape, chunk_shape, coords, ts)
+    npt = len(coords[0])
+    if n != npt * ts and n != ts:
+        raise ValueError("data holds neither one item per point nor a single item")
+    if n == ts:
+        points = [(item, 0) for item, _ in points]
+    if not jobs:
+        return {}
+    res = CBloscUpdatePointBatch([frames[f] for f, _ in jobs], [p.value] * len(jobs), [q for _, q in jobs], points, fill, shuffle, ts, dev)
+    for r in res:
+        if isinstance(r, Exception):
+            raise r
+    return {f: r for (f, _), r in zip(jobs, res)}
+
+
+def CBloscUpdateMask(frames, array_shape, chunk_shape, mask, data, typesize, shuffle=1, fill=None, dev=None):
+    """`z[mask] = data` for a boolean numpy array `mask` of the whole array's shape: CBloscUpdateVIndex of np.nonzero(mask) -- `data` holds
+    one item per true entry in C order, or a single item"""
+    import numpy as np                     # (a mask has no other form)
+    mask = np.asarray(mask, dtype=bool)
+    if mask.shape != tuple(array_shape):
+        raise ValueError("the mask needs the array's shape")
+    return CBloscUpdateVIndex(frames, array_shape, chunk_shape, [c.tolist() for c in np.nonzero(mask)], data, typesize, shuffle, fill, dev)
 
 
 # ---------------------------------------------------------------------------------------------

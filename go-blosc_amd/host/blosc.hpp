@@ -5,6 +5,7 @@
 // meaning and error behaviour as the reference package: blosc.go:49-317, shuffle.go:298-323, codec.go:15-53.
 // Every O(n) operation runs on the MI355X through libhipblosc.so; there is no CPU fallback.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <map>
 #include <memory>
@@ -490,6 +491,127 @@ inline std::vector<Bytes> CBloscUpdateIndexBatch(const std::vector<UpdIndex> &jo
                                        shuffle, typeSize, device));
     for (size_t k = 0; k < nj; k++) out[k].resize(rc[k] > 0 ? (size_t)rc[k] : 0);
     return out;
+}
+// many point updates of C-Blosc-1 chunk frames through one set of launches (hb_cblosc_update_points_batch): `z.vindex[r, c] = v` and
+// `z[mask] = v` per touched chunk.  Point p of job k puts item srcs[p] of `src` over item items[p] of the chunk -- the ravelled chunk-local
+// index, no item twice in a job (the library refuses a repeat); many points may name the same source item.  Every other item is the old
+// frame's (`old`, n bytes), or `fill` (typeSize bytes; nullptr: zeros) where old == nullptr and old_n == 0.
+// out[k] is the NEW frame, rc[k] its byte count or the job's HB_ERR_* code (nothing is thrown per job); the old frame is not changed
+struct UpdPoint {
+    const void *old; size_t old_n; const void *src;
+    int64_t chunk_items;
+    std::vector<int64_t> items, srcs;                                      // as long as each other
+};
+inline std::vector<Bytes> CBloscUpdatePointBatch(const std::vector<UpdPoint> &jobs, std::vector<int64_t> &rc, const void *fill = nullptr, int shuffle = 1, int typeSize = 4,
+                                                 int device = 0) {
+    const size_t nj = jobs.size();
+    std::vector<Bytes> out(nj);
+    rc.assign(nj, 0);
+    if (!nj) return out;
+    std::vector<hb_cblosc_upd_point_job> jt(nj); std::vector<const void *> old(nj), src(nj); std::vector<void *> dst(nj); std::vector<size_t> on(nj), cap(nj);
+    std::vector<hb_cblosc_upd_point> points;
+    for (size_t k = 0; k < nj; k++) {
+        const UpdPoint &q = jobs[k];
+        if (q.items.size() != q.srcs.size()) check(HB_ERR_BAD_ARG);
+        jt[k] = hb_cblosc_upd_point_job{0u, 0u, q.chunk_items, (int64_t)points.size(), (int64_t)q.items.size()};
+        for (size_t i = 0; i < q.items.size(); i++) points.push_back(hb_cblosc_upd_point{q.items[i], q.srcs[i]});
+        const uint64_t ts = typeSize > 0 ? (uint64_t)typeSize : 1u, m = q.chunk_items > 0 ? (uint64_t)q.chunk_items : 0u;
+        const uint64_t bytes = m > (1ull << 31) / ts ? (1ull << 31) : m * ts;        // (a chunk beyond 2 GiB is refused by the library: no room is needed for it)
+        old[k] = q.old; on[k] = q.old_n; src[k] = q.src;
+        cap[k] = bytes < (1ull << 31) ? hb_cblosc_bound((size_t)bytes, typeSize) : 16;
+        out[k].resize(cap[k]);
+        dst[k] = out[k].data();
+    }
+    points.push_back(hb_cblosc_upd_point{0, 0});                           // (one slot at least)
+    check(hb_cblosc_update_points_batch((int)nj, jt.data(), points.data(), (int64_t)points.size() - 1, old.data(), on.data(), src.data(), dst.data(), cap.data(), rc.data(), fill,
+                                        shuffle, typeSize, device));
+    for (size_t k = 0; k < nj; k++) out[k].resize(rc[k] > 0 ? (size_t)rc[k] : 0);
+    return out;
+}
+// the jobs of `z.vindex[coords] = data` on a chunked array: exactly ONE per chunk that holds a point, in C order of the grid
+// ceil(array_shape / chunk_shape) -- `grid` is the chunk's grid index, `items` the ravelled chunk-local coordinates, `srcs` the points'
+// positions in coords.  coords holds one vector per dimension, all of one length; point i is (coords[0][i], coords[1][i] ...).  A coordinate
+// tuple that occurs twice keeps its LAST occurrence, as numpy assignment does in practice: the earlier ones appear in no job.  Negative or
+// out-of-range coordinates throw HB_ERR_BAD_ARG.  (old, old_n, src of the jobs are left empty.)
+struct UpdPointChunk { int64_t grid; UpdPoint job; };
+inline std::vector<UpdPointChunk> UpdatePointJobs(const std::vector<int64_t> &array_shape, const std::vector<int64_t> &chunk_shape, const std::vector<std::vector<int64_t>> &coords) {
+    const size_t nd = chunk_shape.size();
+    if (nd < 1 || nd > HB_CBLOSC_BOX_MAX_NDIM || array_shape.size() != nd || coords.size() != nd) check(HB_ERR_BAD_ARG);
+    std::vector<int64_t> grid(nd);
+    int64_t chunk_items = 1;
+    for (size_t d = 0; d < nd; d++) {
+        if (chunk_shape[d] < 1 || array_shape[d] < 0 || coords[d].size() != coords[0].size()) check(HB_ERR_BAD_ARG);
+        grid[d] = (array_shape[d] + chunk_shape[d] - 1) / chunk_shape[d];
+        chunk_items *= chunk_shape[d];
+    }
+    const size_t np = coords[0].size();
+    std::map<std::vector<int64_t>, size_t> last;                           // a repeated point: its last position
+    std::vector<int64_t> pt(nd);
+    for (size_t i = 0; i < np; i++) {
+        for (size_t d = 0; d < nd; d++) {
+            pt[d] = coords[d][i];
+            if (pt[d] < 0 || pt[d] >= array_shape[d]) check(HB_ERR_BAD_ARG); // (negative indices are not wrapped)
+        }
+        last[pt] = i;
+    }
+    std::map<int64_t, UpdPoint> per;                                       // ordered by grid index
+    for (size_t i = 0; i < np; i++) {                                      // in the order of the positions that count
+        for (size_t d = 0; d < nd; d++) pt[d] = coords[d][i];
+        if (last[pt] != i) continue;
+        int64_t f = 0, item = 0;
+        for (size_t d = 0; d < nd; d++) { f = f * grid[d] + pt[d] / chunk_shape[d]; item = item * chunk_shape[d] + pt[d] % chunk_shape[d]; }
+        UpdPoint &q = per[f];
+        q.items.push_back(item); q.srcs.push_back((int64_t)i);
+    }
+    std::vector<UpdPointChunk> out;
+    for (auto &kv : per) {
+        kv.second.old = nullptr; kv.second.old_n = 0; kv.second.src = nullptr; kv.second.chunk_items = chunk_items;
+        out.push_back(UpdPointChunk{kv.first, std::move(kv.second)});
+    }
+    return out;
+}
+// `z.vindex[coords_0, coords_1 ...] = data` of a chunked array whose chunks are the C-Blosc-1 frames `frames`, in C order of the chunk grid
+// (an empty frame: a chunk the store does not have, its base is `fill`).  `data` holds one item per point, or exactly ONE item, a scalar that
+// every point gets.  One job per touched chunk (UpdatePointJobs), all of them through one CBloscUpdatePointBatch call.  Returns the new frames
+// of the touched chunks keyed by their grid index -- none, without a call, where there is no point -- and leaves `frames` as it is; the first
+// job's error is thrown.
+inline std::map<int64_t, Bytes> CBloscUpdateVIndex(const std::vector<Bytes> &frames, const std::vector<int64_t> &array_shape, const std::vector<int64_t> &chunk_shape,
+                                                   const std::vector<std::vector<int64_t>> &coords, const Bytes &data, int typeSize, int shuffle = 1, const void *fill = nullptr,
+                                                   int device = 0) {
+    std::vector<UpdPointChunk> chunks = UpdatePointJobs(array_shape, chunk_shape, coords);
+    const size_t np = coords[0].size();
+    if (typeSize < 1 || (data.size() != np * (size_t)typeSize && data.size() != (size_t)typeSize)) check(HB_ERR_BAD_ARG);
+    const bool scalar = data.size() == (size_t)typeSize;
+    std::map<int64_t, Bytes> res;
+    if (chunks.empty()) return res;
+    std::vector<UpdPoint> jobs;
+    for (UpdPointChunk &c : chunks) {
+        if (c.grid >= (int64_t)frames.size()) check(HB_ERR_BAD_ARG);
+        const Bytes &f = frames[(size_t)c.grid];
+        c.job.old = f.empty() ? nullptr : f.data(); c.job.old_n = f.size(); c.job.src = data.data();
+        if (scalar) std::fill(c.job.srcs.begin(), c.job.srcs.end(), (int64_t)0);
+        jobs.push_back(c.job);
+    }
+    std::vector<int64_t> rc;
+    std::vector<Bytes> out = CBloscUpdatePointBatch(jobs, rc, fill, shuffle, typeSize, device);
+    for (size_t k = 0; k < jobs.size(); k++) { check(rc[k]); res[chunks[k].grid] = std::move(out[k]); }
+    return res;
+}
+// `z[mask] = data`: CBloscUpdateVIndex of the true entries of `mask` -- one byte per item of the whole array, C order -- in C order; `data`
+// holds one item per true entry, or a single item
+inline std::map<int64_t, Bytes> CBloscUpdateMask(const std::vector<Bytes> &frames, const std::vector<int64_t> &array_shape, const std::vector<int64_t> &chunk_shape,
+                                                 const std::vector<uint8_t> &mask, const Bytes &data, int typeSize, int shuffle = 1, const void *fill = nullptr, int device = 0) {
+    const size_t nd = array_shape.size();
+    uint64_t total = 1;
+    for (int64_t a : array_shape) { if (a < 0) check(HB_ERR_BAD_ARG); total *= (uint64_t)a; }
+    if (nd < 1 || mask.size() != total) check(HB_ERR_BAD_ARG);
+    std::vector<std::vector<int64_t>> coords(nd);
+    for (size_t i = 0; i < mask.size(); i++) {
+        if (!mask[i]) continue;
+        size_t r = i;
+        for (size_t d = nd; d-- > 0;) { coords[d].push_back((int64_t)(r % (size_t)array_shape[d])); r /= (size_t)array_shape[d]; }
+    }
+    return CBloscUpdateVIndex(frames, array_shape, chunk_shape, coords, data, typeSize, shuffle, fill, device);
 }
 inline Header GetInfo(const Bytes &data) { return ParseHeader(data); }                                            // blosc.go:306-308
 inline int GetDecompressedSize(const Bytes &data) { return (int)ParseHeader(data).NBytesOrig; }                   // blosc.go:311-317

@@ -850,6 +850,57 @@ int     hb_cblosc_update_index_batch_device(int njobs, const hb_cblosc_upd_index
 int     hb_cblosc_update_index_batch(int njobs, const hb_cblosc_upd_index *jobs, const int64_t *index, int64_t nindex, const void *const *old,
                                      const size_t *old_n, const void *const *src, void *const *dst, const size_t *cap, int64_t *rc, const void *fill,
                                      int shuffle, int typesize, int device);
+/* ---- batched C-Blosc-1 point updates: `z.vindex[r, c] = v` and `z[mask] = v` through ONE set of launches -- the coordinate half of writing,
+ *      the inverse of hb_cblosc_getpoints_frames_batch*.  Everything is as for the box updates above (one job is one chunk: one old frame, one
+ *      source, one NEW frame; frames stay immutable) except what the written items are.  `points` is a HOST array of npoints entries in all
+ *      three forms, shared by the jobs, as in hb_cblosc_getpoints_frames_batch*; job j owns points[first .. first + count).
+ *      Point p puts the typesize bytes at d_src[j] + src * typesize over item `item` of C', the chunk after the update.  `item` is the
+ *      ravelled chunk-local index: this layer knows chunk_items and not the chunk's shape.  Source offsets are 64-bit, d_src[j] may have any
+ *      alignment, the source is read ONLY at the points' items, and many points may name the same src (a scalar right-hand side is src == 0
+ *      everywhere).  Every other item of C' is the BASE, decided as for box updates: the fill base where d_old[k] == NULL && old_n[k] == 0,
+ *      else the old frame.  There is no "no base" route (points that happen to cover the whole chunk are not recognised: the job gets a
+ *      base, which is correct, only not the cheapest route).  count == 0 over an old frame re-encodes the old chunk; over a fill base it
+ *      writes the all-fill chunk.
+ *      Device form: frame k is byte for byte, and with the same hb_result, what hb_cblosc_compress_dev writes for C' placed at a
+ *      16-byte-aligned address.  Refused per job, decided on the host before the device is looked for, in the box updates' order 1. to 4.;
+ *      its HB_ERR_BAD_ARG group 1. is: a reserved field that is not 0; chunk_items < 0; first < 0, count < 0 or first + count > npoints
+ *      (checked without overflow); item < 0 or item >= chunk_items; src < 0 or (src + 1) * typesize beyond 64 bits; AN ITEM THAT OCCURS TWICE
+ *      IN ONE JOB -- two source items would race for the same bytes, and the contract is a deterministic frame (the mirrors resolve repeats
+ *      before they build jobs: the last occurrence wins, as in numpy).  Group 2. is HB_ERR_DATA_TOO_LARGE for chunk_items * typesize, as for
+ *      the box writes.  The repeat check costs O(count): a bitmap over the chunk's items that is reused from job to job, or, where
+ *      chunk_items > 64 * count, a sorted copy of the items; nothing proportional to the chunk is allocated for a few points in a large chunk.
+ *      Device-time failure, the call as a whole and asynchrony: exactly as the box updates -- THE CALLER HAS TO LOOK AT d_results[k] BEFORE IT
+ *      SWAPS d_frame[k] IN.  The call as a whole also refuses with HB_ERR_BAD_ARG (in that group, so behind "no jobs": HB_OK): npoints < 0,
+ *      points == NULL while some job has count > 0, and more than HB_CBLOSC_BATCH_MAX_WORK points of the accepted jobs or workgroups of the
+ *      scatter.
+ *      Workspace: at most the box updates' bound for the same chunks and old frames with HB_CBLOSC_UPD_POINT_JOB_BYTES as the per-job constant,
+ *      plus HB_CBLOSC_UPD_POINT_BYTES times the points of the accepted jobs: it grows with the points, never with chunk_items.  0 when the
+ *      call as a whole would be refused, 256 for njobs == 0.  The query knows no pointers.
+ *      Host form: as hb_cblosc_update_index_batch -- the old frames of the carried jobs go up (adjacent ones in one copy), the host packs each
+ *      carried job's source items in point order (the device call sees src == p) and they go up in one copy, the device form runs once,
+ *      records and frames come down as in hb_cblosc_compress_frames_batch.  A job the batch did not carry or that did not end with status 0
+ *      is answered on the host: hb_cblosc_decompress of the old frame (or the fill), a naive loop over the points, hb_cblosc_compress; rc[k]
+ *      is exactly what that sequence returns.  The refusals 1. and 2. are rc[k] directly. ---- */
+#define HB_CBLOSC_UPD_POINT_JOB_BYTES   2048      /* workspace per job beyond the box updates' parts: the scatter record, prefix and finish words, alignment */
+#define HB_CBLOSC_UPD_POINT_BYTES       16        /* workspace per point of an accepted job: chunk byte offset + source byte offset */
+typedef struct hb_cblosc_upd_point {
+    int64_t  item;             /* the ravelled chunk-local index of the item that is written: 0 .. chunk_items - 1, once per job */
+    int64_t  src;              /* the item of the job's source that is read: d_src[j] + src * typesize */
+} hb_cblosc_upd_point;
+typedef struct hb_cblosc_upd_point_job {
+    uint32_t reserved, reserved2;   /* 0 */
+    int64_t  chunk_items;      /* items of the chunk */
+    int64_t  first, count;     /* the job's points: points[first .. first + count) */
+} hb_cblosc_upd_point_job;
+size_t  hb_cblosc_update_points_batch_workspace(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints,
+                                                const hb_cblosc_header *old_hdrs, const size_t *old_n, int shuffle, int typesize);
+int     hb_cblosc_update_points_batch_device(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints,
+                                             const hb_cblosc_header *old_hdrs, const void *const *d_old, const size_t *old_n, const void *const *d_src,
+                                             void *const *d_frame, const size_t *cap, const void *fill, int shuffle, int typesize,
+                                             void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
+int     hb_cblosc_update_points_batch(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints,
+                                      const void *const *old, const size_t *old_n, const void *const *src, void *const *dst, const size_t *cap, int64_t *rc,
+                                      const void *fill, int shuffle, int typesize, int device);
 
 #ifdef __cplusplus
 }
