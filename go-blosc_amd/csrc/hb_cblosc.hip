@@ -38,6 +38,7 @@
 #include "hb_cblosc_upd_index_batch.h" // the selection updates: refusal, tables, records, and the two scatters' index arithmetic
 #include "hb_cblosc_upd_point_batch.h" // the point updates: refusal, point table, records, and the scatter's thread
 #include "hb_cblosc_upd_box_batch.h"   // the geometry of an update box, the host side of the batched box updates, the overlay's index arithmetic
+#include "hb_cblosc_point_sel.h"       // the prepared point selections: what a selection keeps, its two builders, the builder kernel's thread, the per-call prepares
 
 // ---- the streams of blocks [b0, b0 + nb) (hb_cblosc_getitem_device: the blocks that cover a range; the others' bstarts entries and streams
 // are never read); stream offsets count from the first of these blocks ----
@@ -1198,6 +1199,47 @@ __global__ __launch_bounds__(256) void k_cbpu_scatter_points(const CbpuJob *__re
     cbpu_thread(jobs[i], tab, ts, blockIdx.x - blk[i], threadIdx.x, io);
 }
 
+// ---- the device builder of a prepared point selection (hb_cblosc_point_sel_create_device; the records, the grouping and the thread are
+// hb_cblosc_point_sel.h).  One launch per group of jobs over the workgroup prefix of the group's jobs; a thread owns one point (cbsel_thread):
+// one 16-byte load of the caller's point, the checks, one 16-byte store of its table entry, the marks of the one or two blocks the item
+// touches in the job's block bitmap, its own bit in the job's item bitmap -- an OR that finds the bit set is a repeat -- and `out + 1` into the
+// job's 64-bit maximum.  Atomic traffic stays low: an OR is skipped where a relaxed load shows its bit already (clustered points share block
+// bits, and a word once raised stays raised), and the maximum is reduced across the wave before lane 0's single atomic.  Bits are only ever
+// set, so a stale load costs an OR and never an answer.  Vector atomics and plain C++; no LDS. ----
+struct CbselDeviceIO {
+    __device__ __forceinline__ hb_cblosc_point load_point(const hb_cblosc_point *p) {
+        const u32x4 v = *(const u32x4 *)p;
+        return hb_cblosc_point{(int64_t)((uint64_t)v.x | ((uint64_t)v.y << 32)), (int64_t)((uint64_t)v.z | ((uint64_t)v.w << 32))};
+    }
+    __device__ __forceinline__ void store_entry(CbpPoint *d, const CbpPoint &e) {
+        u32x4 v; v.x = e.off; v.y = 0u; v.z = (uint32_t)e.out; v.w = (uint32_t)(e.out >> 32);
+        *(u32x4 *)d = v;
+    }
+    __device__ __forceinline__ bool mark(uint32_t *words, uint64_t bit) {
+        uint32_t *w = words + (bit >> 5);
+        const uint32_t m = 1u << ((uint32_t)bit & 31u);
+        if (__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & m) return true;
+        return (atomicOr(w, m) & m) != 0u;
+    }
+    __device__ __forceinline__ void raise(uint32_t *w) {
+        if (!__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicOr(w, 1u);
+    }
+    // (every lane of the wave is here: cbsel_thread has no early exit, and a workgroup is four whole waves)
+    __device__ __forceinline__ void fold_max(uint64_t *w, uint64_t v) {
+        for (int d = 32; d; d >>= 1) {
+            const uint64_t o = (uint64_t)__shfl_xor((unsigned long long)v, d, 64);
+            v = o > v ? o : v;
+        }
+        if ((threadIdx.x & 63u) == 0u && v) atomicMax((unsigned long long *)w, (unsigned long long)v);
+    }
+};
+__global__ __launch_bounds__(256) void k_cbsel_build(const CbselJob *__restrict__ jobs, const uint32_t *__restrict__ blk, uint32_t njobs, const hb_cblosc_point *__restrict__ in,
+                                                      CbpPoint *__restrict__ tab, uint32_t ts, uint64_t out_lim, uint32_t *ibits, uint32_t *bbits, CbselOut *outs) {
+    const uint32_t i = hb_owner(blk, njobs, blockIdx.x);
+    CbselDeviceIO io;
+    cbsel_thread(jobs[i], in, tab, ts, out_lim, ibits, bbits, outs + i, blockIdx.x - blk[i], threadIdx.x, io);
+}
+
 void hb_launch_match_selfcontained(const uint8_t *src, size_t n, void *desc, uint8_t *records, uint32_t nchunks, int accel, hipStream_t s);   // hb_lz4_enc.hip
 bool hb_launch_match_fused_selfcontained(const uint8_t *src, int typesize, void *desc, uint8_t *records, uint32_t nblk, int accel, hipStream_t s);
 void hb_launch_match_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, void *desc, uint8_t *records, uint32_t total_chunks, int accel, hipStream_t s);
@@ -1484,8 +1526,9 @@ int hb_cblosc_getitem_frames_batch_device(int nframes, const hb_cblosc_header *h
 // A prepared batch of boxes, of stepped selections, of index-list selections or of points (CbxBatch) on the device: one upload, the plan and the
 // decoders over the distinct blocks, the gathers -- k_cbx_gather per kind among the jobs with plain rows, k_cbs_gather per kind among those with
 // stepped rows, k_cbi_gather_rows and k_cbi_gather_items per kind among those with an index list, k_cbp_gather per kind among the jobs of
-// points -- and the records.
-static int cbx_launch(const CbxBatch &B, int njobs, void *d_work, hb_result *d_results, void *stream) {
+// points -- and the records.  d_sel_tab: the point table of a prepared selection, which the point gather then reads in place of the batch's own
+// (whose section of the layout is empty).
+static int cbx_launch(const CbxBatch &B, int njobs, void *d_work, hb_result *d_results, void *stream, const CbpPoint *d_sel_tab = nullptr) {
     const CbxLayout &L = B.L;
     hipStream_t s = (hipStream_t)stream;
     uint8_t *w = (uint8_t *)d_work;
@@ -1534,7 +1577,7 @@ static int cbx_launch(const CbxBatch &B, int njobs, void *d_work, hb_result *d_r
                            d_igjob + k0, d_igblk + k0, nk, (const uint8_t *)w);
     });
     const CbpRow *d_prow = cb_at<const CbpRow>(w, L.prow);
-    const CbpPoint *d_ptab = cb_at<const CbpPoint>(w, L.ptab);
+    const CbpPoint *d_ptab = d_sel_tab ? d_sel_tab : cb_at<const CbpPoint>(w, L.ptab);
     const uint32_t *d_pgjob = cb_at<const uint32_t>(w, L.pgjob), *d_pgblk = cb_at<const uint32_t>(w, L.pgblk);
     static const char *const pname[CBG_COUNT] = {"k_cbp_gather_copy", "k_cbp_gather_unshuffle", "k_cbp_gather_bitun", "k_cbp_gather_bitun4"};
     cb_launch_kinds(B.pkind0, B.pkblocks, pname, s, [&](auto K, uint32_t k0, uint32_t nk, uint32_t blocks) {
@@ -1547,12 +1590,12 @@ static int cbx_launch(const CbxBatch &B, int njobs, void *d_work, hb_result *d_r
     HB_HIP_TRY(hipGetLastError());
     return HB_OK;
 }
-// The three N-d `_device` calls: bad argument, then what `prepare` says, then short buffer, then no device; and the launches.  `prepare` fills
-// the batch, `workspace` is the call's own size query.
+// The three N-d `_device` calls, the point batch's and the prepared selection's read: bad argument, then what `prepare` says, then short buffer,
+// then no device; and the launches.  `prepare` fills the batch, `workspace` is the call's own size query, d_sel_tab the prepared selection's table.
 extern "C++" {
 template <class PREPARE, class WORKSPACE>
 static int cbx_device_call(int nframes, int njobs, bool have_all, void *d_work, size_t work_bytes, hb_result *d_results, void *stream, PREPARE prepare,
-                           WORKSPACE workspace) {
+                           WORKSPACE workspace, const CbpPoint *d_sel_tab = nullptr) {
     if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
     if (njobs == 0) return HB_OK;
     if (!have_all || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
@@ -1563,7 +1606,7 @@ static int cbx_device_call(int nframes, int njobs, bool have_all, void *d_work, 
     // (the query knows no capacities and no pointers: where a job was refused for one of them it has counted blocks that this batch leaves out)
     if (work_bytes < (B.ptr_refusals ? workspace(accept) : B.L.total)) return HB_ERR_SHORT_BUFFER;
     if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
-    return cbx_launch(B, njobs, d_work, d_results, stream);
+    return cbx_launch(B, njobs, d_work, d_results, stream, d_sel_tab);
 }
 }
 
@@ -1958,32 +2001,12 @@ int hb_cblosc_update_index_batch_device(int njobs, const hb_cblosc_upd_index *jo
     }
     return HB_OK;
 }
-// ---- many point updates, one set of launches (include/hipblosc.h; the host side is hb_cblosc_upd_point_batch.h) ----
-size_t hb_cblosc_update_points_batch_workspace(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints,
-                                               const hb_cblosc_header *old_hdrs, const size_t *old_n, int shuffle, int typesize) {
-    return cbpu_workspace(njobs, jobs, points, npoints, old_hdrs, old_n, shuffle, typesize, hb_cblosc_accepted());
-}
-
-int hb_cblosc_update_points_batch_device(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints, const hb_cblosc_header *old_hdrs,
-                                         const void *const *d_old, const size_t *old_n, const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill,
-                                         int shuffle, int typesize, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
-    if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
-    if (njobs == 0) return HB_OK;
-    if (!jobs || !old_hdrs || !d_old || !old_n || !d_src || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
-    uint8_t *w = (uint8_t *)d_work;
-    const unsigned accept = hb_cblosc_accepted();                         // (read once: the query below judges the frames as the call does)
-    CbpuBatch B;
-    const int rc = cbpu_prepare(njobs, jobs, points, npoints, old_hdrs, d_old, old_n, d_src, d_frame, cap, fill, shuffle, typesize, w, accept, B);
-    if (rc) return rc;
+// A prepared batch of point updates (CbpuBatch) on the device: one upload, the fill bases, the old-frame bases, the scatter, the encoder and the
+// records.  d_sel_tab: the point table of a prepared selection, which the scatter then reads in place of the batch's own (none is uploaded).
+static int cbpu_launch(const CbpuBatch &B, int njobs, const CbpPoint *d_sel_tab, int shuffle, int typesize, uint8_t *w, hb_result *d_results, void *stream) {
     const CbxuLayout &L = B.U.L;
     const CbxeLayout &XL = B.U.X.L;
     const CbpuLayout &SL = B.S;
-    // (the query knows no pointers: it stages every job, decodes every old frame it cannot refuse and counts every scatter record and point,
-    // so this layout never exceeds it; what the sweeps over the points answered is taken from B, not worked out again)
-    const size_t query = cbpu_workspace(njobs, jobs, points, npoints, old_hdrs, old_n, shuffle, typesize, accept, &B);
-    if (!query) return HB_ERR_BAD_ARG;                                    // (the limits are taken as the query takes them)
-    if (work_bytes < query || query < L.total || B.U.X.E.query < B.U.X.E.L.total) return HB_ERR_SHORT_BUFFER;
-    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
     hipStream_t s = (hipStream_t)stream;
     const size_t np = B.jobs.size(), nt = B.tab.size(), ng = B.U.X.jobs.size(), nd = B.U.fin.size();
     // the scatter's records, prefix and table, the finish list, and behind them the gather's records, prefix and fill table, go up in one
@@ -2014,7 +2037,7 @@ int hb_cblosc_update_points_batch_device(int njobs, const hb_cblosc_upd_point_jo
     if (np) {
         hb_prof_begin("k_cbpu_scatter_points", s);
         hipLaunchKernelGGL(k_cbpu_scatter_points, dim3((unsigned)B.groups), dim3(256), 0, s, (const CbpuJob *)(ws + SL.jobs), (const uint32_t *)(ws + SL.blk), (uint32_t)np,
-                           (const CbpPoint *)(ws + SL.tab), (uint32_t)typesize);
+                           d_sel_tab ? d_sel_tab : (const CbpPoint *)(ws + SL.tab), (uint32_t)typesize);
         hb_prof_end(s);
     }
     // (a base that failed to decode: as in the box updates, the encoder takes any bytes and k_cbxu_finish overrides that frame's record)
@@ -2027,5 +2050,188 @@ int hb_cblosc_update_points_batch_device(int njobs, const hb_cblosc_upd_point_jo
         HB_HIP_TRY(hipGetLastError());
     }
     return HB_OK;
+}
+// ---- many point updates, one set of launches (include/hipblosc.h; the host side is hb_cblosc_upd_point_batch.h) ----
+size_t hb_cblosc_update_points_batch_workspace(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints,
+                                               const hb_cblosc_header *old_hdrs, const size_t *old_n, int shuffle, int typesize) {
+    return cbpu_workspace(njobs, jobs, points, npoints, old_hdrs, old_n, shuffle, typesize, hb_cblosc_accepted());
+}
+
+int hb_cblosc_update_points_batch_device(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints, const hb_cblosc_header *old_hdrs,
+                                         const void *const *d_old, const size_t *old_n, const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill,
+                                         int shuffle, int typesize, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
+    if (njobs == 0) return HB_OK;
+    if (!jobs || !old_hdrs || !d_old || !old_n || !d_src || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
+    uint8_t *w = (uint8_t *)d_work;
+    const unsigned accept = hb_cblosc_accepted();                         // (read once: the query below judges the frames as the call does)
+    CbpuBatch B;
+    const int rc = cbpu_prepare(njobs, jobs, points, npoints, old_hdrs, d_old, old_n, d_src, d_frame, cap, fill, shuffle, typesize, w, accept, B);
+    if (rc) return rc;
+    const CbxuLayout &L = B.U.L;
+    // (the query knows no pointers: it stages every job, decodes every old frame it cannot refuse and counts every scatter record and point,
+    // so this layout never exceeds it; what the sweeps over the points answered is taken from B, not worked out again)
+    const size_t query = cbpu_workspace(njobs, jobs, points, npoints, old_hdrs, old_n, shuffle, typesize, accept, &B);
+    if (!query) return HB_ERR_BAD_ARG;                                    // (the limits are taken as the query takes them)
+    if (work_bytes < query || query < L.total || B.U.X.E.query < B.U.X.E.L.total) return HB_ERR_SHORT_BUFFER;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    return cbpu_launch(B, njobs, nullptr, shuffle, typesize, w, d_results, stream);
+}
+
+// ---- prepared point selections (include/hipblosc.h; the host side, the builders and the per-call prepares are hb_cblosc_point_sel.h) ----
+}  // extern "C"
+struct hb_cblosc_point_sel {
+    CbselPlan P;                         // what it keeps on the host: nothing proportional to the points
+    CbselKnown W;                        // ... and, derived from it once, what the update's stage takes for its sweeps' answers (per job)
+    int device;
+    CbpPoint *d_tab;                     // the table of its jobs on `device`: P.npts entries
+};
+extern "C" {
+static void cbsel_free(hb_cblosc_point_sel *S) {
+    if (S->d_tab) (void)hipFree(S->d_tab);
+    delete S;
+}
+// the selection with its plan begun and its table allocated on the current device
+static int cbsel_new(int njobs, const hb_cblosc_sel_job *jobs, int64_t npoints, int typesize, hb_cblosc_point_sel **out) {
+    hb_cblosc_point_sel *S = new (std::nothrow) hb_cblosc_point_sel{};
+    if (!S) return HB_ERR_BAD_ARG;
+    if (hipGetDevice(&S->device) != hipSuccess) { delete S; return HB_ERR_HIP; }
+    try { cbsel_begin(njobs, jobs, npoints, typesize, S->P); } catch (const std::bad_alloc &) { delete S; return HB_ERR_BAD_ARG; }
+    if (S->P.npts && hipMalloc((void **)&S->d_tab, (size_t)S->P.npts * sizeof(CbpPoint)) != hipSuccess) { S->d_tab = nullptr; delete S; return HB_ERR_HIP; }
+    *out = S;
+    return HB_OK;
+}
+
+int hb_cblosc_point_sel_create(int njobs, const hb_cblosc_sel_job *jobs, const hb_cblosc_point *points, int64_t npoints, int typesize, int device,
+                               hb_cblosc_point_sel **sel) {
+    if (sel) *sel = nullptr;
+    if (cbsel_call_refused(njobs, jobs, points, npoints, typesize, sel)) return HB_ERR_BAD_ARG;
+    if (const int rc = hb_select_device(device)) return rc;
+    hb_cblosc_point_sel *S = nullptr;
+    if (const int rc = cbsel_new(njobs, jobs, npoints, typesize, &S)) return rc;
+    try {
+        std::vector<CbpPoint> tab;
+        cbsel_build_host(S->P, points, tab);
+        cbsel_known(S->P, S->W);
+        if (!tab.empty() && hipMemcpy(S->d_tab, tab.data(), tab.size() * sizeof(CbpPoint), hipMemcpyHostToDevice) != hipSuccess) { cbsel_free(S); return HB_ERR_HIP; }
+    } catch (const std::bad_alloc &) { cbsel_free(S); return HB_ERR_BAD_ARG; }
+    *sel = S;
+    return HB_OK;
+}
+
+int hb_cblosc_point_sel_create_device(int njobs, const hb_cblosc_sel_job *jobs, const hb_cblosc_point *d_points, int64_t npoints, int typesize, void *stream,
+                                      hb_cblosc_point_sel **sel) {
+    if (sel) *sel = nullptr;
+    if (cbsel_call_refused(njobs, jobs, d_points, npoints, typesize, sel) || ((uintptr_t)d_points & 15u)) return HB_ERR_BAD_ARG;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    hipStream_t s = (hipStream_t)stream;
+    hb_cblosc_point_sel *S = nullptr;
+    if (const int rc = cbsel_new(njobs, jobs, npoints, typesize, &S)) return rc;
+    uint8_t *d_grp = nullptr;
+    size_t grp_bytes = 0;
+    int rc = HB_OK;
+    try {
+        CbselGroup G;
+        std::vector<uint8_t> up, down;
+        for (size_t from = 0, nj = S->P.jobs.size(); from < nj && rc == HB_OK;) {
+            from = cbsel_next_group(S->P, from, G);
+            const size_t ng = G.rec.size();
+            if (!ng) break;
+            const CbselGroupLayout &L = G.L;
+            if (L.total > grp_bytes) {                                    // (the groups' memory is the builder's own, freed before it returns)
+                if (d_grp) (void)hipFree(d_grp);
+                d_grp = nullptr; grp_bytes = 0;
+                if (hipMalloc((void **)&d_grp, L.total) != hipSuccess) { d_grp = nullptr; rc = HB_ERR_HIP; break; }
+                grp_bytes = L.total;
+            }
+            // the words and both bitmaps are cleared; the records and their prefix go up in one copy (the buffer is read before the call returns)
+            up.assign(L.out, 0);
+            memcpy(up.data() + L.jobs, G.rec.data(), ng * sizeof(CbselJob));
+            memcpy(up.data() + L.blk, G.blk.data(), (ng + 1) * 4);
+            if (hipMemsetAsync(d_grp + L.out, 0, L.total - L.out, s) != hipSuccess || hipMemcpyAsync(d_grp, up.data(), L.out, hipMemcpyHostToDevice, s) != hipSuccess) { rc = HB_ERR_HIP; break; }
+            hb_prof_begin("k_cbsel_build", s);
+            hipLaunchKernelGGL(k_cbsel_build, dim3(G.blk.back()), dim3(256), 0, s, (const CbselJob *)(d_grp + L.jobs), (const uint32_t *)(d_grp + L.blk), (uint32_t)ng, d_points,
+                               S->d_tab, (uint32_t)typesize, ~0ull / (uint64_t)typesize, (uint32_t *)(d_grp + L.ibits), (uint32_t *)(d_grp + L.bbits), (CbselOut *)(d_grp + L.out));
+            hb_prof_end(s);
+            // the per-job words and the block bitmaps come down in one copy; the item bitmaps stay where they are
+            down.resize(L.ibits - L.out);
+            if (hipGetLastError() != hipSuccess || hipMemcpyAsync(down.data(), d_grp + L.out, down.size(), hipMemcpyDeviceToHost, s) != hipSuccess ||
+                hipStreamSynchronize(s) != hipSuccess) { rc = HB_ERR_HIP; break; }
+            cbsel_take_group(S->P, G, (const CbselOut *)down.data(), (const uint32_t *)(down.data() + (L.bbits - L.out)));
+        }
+        if (rc == HB_OK && hipStreamSynchronize(s) != hipSuccess) rc = HB_ERR_HIP;
+        if (rc == HB_OK) cbsel_known(S->P, S->W);
+    } catch (const std::bad_alloc &) { (void)hipStreamSynchronize(s); rc = HB_ERR_BAD_ARG; }
+    if (d_grp) (void)hipFree(d_grp);
+    if (rc) { cbsel_free(S); return rc; }
+    *sel = S;
+    return HB_OK;
+}
+
+int hb_cblosc_point_sel_destroy(hb_cblosc_point_sel *sel) {
+    if (!sel) return HB_OK;
+    const int dev = sel->device;
+    int cur = -1, rc = HB_OK;
+    // (work enqueued with the selection may still read its table: the device is drained before the table goes)
+    if (hipGetDevice(&cur) != hipSuccess || (cur != dev && hipSetDevice(dev) != hipSuccess) || hipDeviceSynchronize() != hipSuccess) rc = HB_ERR_HIP;
+    cbsel_free(sel);
+    if (cur >= 0 && cur != dev) (void)hipSetDevice(cur);
+    return rc;
+}
+
+int hb_cblosc_point_sel_info(const hb_cblosc_point_sel *sel, int job, hb_cblosc_sel_info *info) {
+    if (!sel || !info || job < 0 || (size_t)job >= sel->P.jobs.size()) return HB_ERR_BAD_ARG;
+    cbsel_info(sel->P.jobs[(size_t)job], *info);
+    return HB_OK;
+}
+
+size_t hb_cblosc_point_sel_device_bytes(const hb_cblosc_point_sel *sel) { return sel ? (size_t)sel->P.npts * sizeof(CbpPoint) : 0; }
+
+// whether the current device is the selection's
+static bool cbsel_on_device(const hb_cblosc_point_sel *sel) {
+    int cur = -1;
+    return hipGetDevice(&cur) == hipSuccess && cur == sel->device;
+}
+
+size_t hb_cblosc_getpoints_sel_workspace(const hb_cblosc_point_sel *sel, int nframes, const hb_cblosc_header *hdrs, const size_t *n, const uint32_t *job_frame) {
+    if (!sel) return 0;
+    return cbsel_read_workspace(sel->P, nframes, hdrs, n, job_frame, hb_cblosc_accepted());
+}
+
+int hb_cblosc_getpoints_sel_device(const hb_cblosc_point_sel *sel, int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n,
+                                   const uint32_t *job_frame, void *const *d_dst, const size_t *cap, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    if (!sel || !job_frame) return HB_ERR_BAD_ARG;
+    const int njobs = (int)sel->P.jobs.size();
+    const int rc = cbx_device_call(
+        nframes, njobs, hdrs && d_frame && n && d_dst && cap && cbsel_on_device(sel), d_work, work_bytes, d_results, stream,
+        [&](CbxBatch &B, unsigned accept) { return cbsel_read_prepare(sel->P, nframes, hdrs, d_frame, n, job_frame, d_dst, cap, true, B, accept); },
+        [&](unsigned accept) { return cbsel_read_workspace(sel->P, nframes, hdrs, n, job_frame, accept); }, sel->d_tab);
+    return rc;
+}
+
+size_t hb_cblosc_update_points_sel_workspace(const hb_cblosc_point_sel *sel, const hb_cblosc_header *old_hdrs, const size_t *old_n, int shuffle, int typesize) {
+    if (!sel) return 0;
+    CbpuBatch B;
+    if (cbsel_update_prepare(sel->P, sel->W, old_hdrs, nullptr, old_n, nullptr, nullptr, nullptr, nullptr, shuffle, typesize, nullptr, hb_cblosc_accepted(), B)) return 0;
+    return B.query;
+}
+
+int hb_cblosc_update_points_sel_device(const hb_cblosc_point_sel *sel, const hb_cblosc_header *old_hdrs, const void *const *d_old, const size_t *old_n,
+                                       const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill, int shuffle, int typesize,
+                                       void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    if (!sel || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2 || typesize != sel->P.typesize) return HB_ERR_BAD_ARG;
+    const int njobs = (int)sel->P.jobs.size();
+    if (njobs == 0) return HB_OK;
+    if (!old_hdrs || !d_old || !old_n || !d_src || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results || !cbsel_on_device(sel)) return HB_ERR_BAD_ARG;
+    uint8_t *w = (uint8_t *)d_work;
+    const unsigned accept = hb_cblosc_accepted();                         // (read once: the query below judges the frames as the call does)
+    CbpuBatch B, Q;
+    const int rc = cbsel_update_prepare(sel->P, sel->W, old_hdrs, d_old, old_n, d_src, d_frame, cap, fill, shuffle, typesize, w, accept, B);
+    if (rc) return rc;
+    // (the query knows no pointers, as the point updates': this layout never exceeds it)
+    if (cbsel_update_prepare(sel->P, sel->W, old_hdrs, nullptr, old_n, nullptr, nullptr, nullptr, nullptr, shuffle, typesize, nullptr, accept, Q) || !Q.query) return HB_ERR_BAD_ARG;
+    if (work_bytes < Q.query || Q.query < B.U.L.total || B.U.X.E.query < B.U.X.E.L.total) return HB_ERR_SHORT_BUFFER;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    return cbpu_launch(B, njobs, sel->d_tab, shuffle, typesize, w, d_results, stream);
 }
 }  // extern "C"

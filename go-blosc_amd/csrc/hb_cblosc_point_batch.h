@@ -65,6 +65,8 @@ static inline bool cbp_call_refused(int njobs, const hb_cblosc_point_job *jobs, 
     return false;
 }
 
+static inline int cbp_finish_(CbxBatch &B, const hb_cblosc_header *hdrs, size_t nf, const std::vector<CbpRow> &jrow, const uint64_t (&kb)[CBG_COUNT],
+                              const uint32_t (&kn)[CBG_COUNT], size_t npj, uint64_t tab_pts, bool fill);
 // HB_OK, or what the call as a whole answers.  d_frame / d_dst / cap == NULL: the workspace query.  fill == false: counts and layout only.
 // A job's touched blocks come from a mark per block of its frame and one sweep over the marked span: O(points + blocks of the frame), no sort of
 // the points.  `mark` is all zero between jobs.
@@ -151,8 +153,16 @@ static inline int cbp_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
         J.b_lo = lo;
         J.dense = B.jruns.size() == first + 1 ? 1u : 0u;
     }
+    return cbp_finish_(B, hdrs, nf, jrow, kb, kn, npj, npts, fill);
+}
+// What cbp_prepare_ above and the prepared selections' read (cbsel_read_prepare_ of hb_cblosc_point_sel.h) end with: the distinct blocks out of
+// the jobs' runs, the layout -- `tab_pts` entries of point table in it: none where the table lies elsewhere -- and, where asked for, the block
+// records, the touch lists and the launch lists.  jrow / kb / kn: per job its row, per kind its workgroups and its jobs; npj: jobs with points.
+static inline int cbp_finish_(CbxBatch &B, const hb_cblosc_header *hdrs, size_t nf, const std::vector<CbpRow> &jrow, const uint64_t (&kb)[CBG_COUNT],
+                              const uint32_t (&kn)[CBG_COUNT], size_t npj, uint64_t tab_pts, bool fill) {
+    const size_t nj = B.jobs.size();
     if (const int rc = cbx_distinct_blocks(B, hdrs)) return rc;
-    B.L = cbx_layout(nf, nj, B.nblk, B.ntouch, B.nstreams, B.stage, 0, 0, 0, npj, npts);
+    B.L = cbx_layout(nf, nj, B.nblk, B.ntouch, B.nstreams, B.stage, 0, 0, 0, npj, tab_pts);
     uint32_t at = 0;
     for (int k = 0; k < CBG_COUNT; k++) { B.pkind0[k] = at; at += kn[k]; B.pkblocks[k] = (uint32_t)kb[k]; }
     B.pkind0[CBG_COUNT] = at;

@@ -173,6 +173,10 @@ struct CbpuStage {
     const CbpuBatch *known;              // a prepare over the same jobs and points whose sweeps' answers are taken as they are (the query inside the call), or NULL
     CbpuScratch scratch;
     size_t kept;                         // the table entries of the jobs counted so far
+    uint32_t at;                         // the next job's first table entry
+    // per job: where its entries start in a point table that lies on the device already (a prepared selection's: hb_cblosc_point_sel.h) --
+    // every answer then comes from `known`, no table is built and the layout has none; NULL: the table is built here
+    const uint32_t *pt0;
     bool has_jobs() const { return jobs != nullptr; }
     void begin(size_t nj) {
         B.geom.assign(nj, CbpuGeom{}); B.swept.assign(nj, 0); B.jobs.clear(); B.tab.clear(); B.blk.assign(1, 0u);
@@ -186,7 +190,7 @@ struct CbpuStage {
     int refusal(size_t k, int ts, CbxuGeom &g) {
         B.tab.resize(kept);
         if (known) { B.geom[k] = known->geom[k]; B.swept[k] = known->swept[k]; }
-        else B.swept[k] = cbpu_refusal(jobs[k], points, npoints, ts, B.geom[k], scratch, fill ? &B.tab : nullptr);
+        else B.swept[k] = cbpu_refusal(jobs[k], points, npoints, ts, B.geom[k], scratch, fill ? &B.tab : nullptr);      // (pt0: always known)
         g = B.geom[k].u;
         return B.swept[k];
     }
@@ -200,15 +204,14 @@ struct CbpuStage {
         return B.groups <= HB_CBLOSC_BATCH_MAX_WORK && B.npts <= HB_CBLOSC_BATCH_MAX_WORK;
     }
     size_t records() const { return 0; }
-    size_t sel_bytes() const { return cbpu_layout(B.nj, B.npts).total; }
+    size_t sel_bytes() const { return cbpu_layout(B.nj, pt0 ? 0u : B.npts).total; }
     void reserve() { B.tab.resize(kept); B.jobs.reserve(B.nj); at = 0; }
     void job(size_t k, const CbxuGeom &, const uint8_t *src, uint8_t *slot) {
         const uint32_t npt = B.geom[k].npt;
-        B.jobs.push_back(CbpuJob{slot, src, CbpRow{at, npt}});
+        B.jobs.push_back(CbpuJob{slot, src, CbpRow{pt0 ? pt0[k] : at, npt}});
         B.blk.push_back(B.blk.back() + (uint32_t)cbp_groups(npt));
         at += npt;
     }
-    uint32_t at;                         // the next job's first table entry
 };
 // What the call as a whole refuses beyond the box updates' refusals, in their HB_ERR_BAD_ARG group (so behind "no jobs": HB_OK): npoints < 0, and
 // no point array while some job has points.  (Too many points or workgroups: the stage counts them.)
@@ -226,7 +229,7 @@ static inline int cbpu_prepare(int njobs, const hb_cblosc_upd_point_job *jobs, c
                                int typesize, uint8_t *work, unsigned accept, CbpuBatch &B, const CbpuBatch *known = nullptr) {
     try {
         if (known && (d_old || known->geom.size() != (size_t)(njobs > 0 ? njobs : 0))) known = nullptr;
-        CbpuStage S{jobs, points, npoints, typesize, d_old != nullptr, B, known, {}, 0, 0};
+        CbpuStage S{jobs, points, npoints, typesize, d_old != nullptr, B, known, {}, 0, 0, nullptr};
         S.begin(0);
         B.S = cbpu_layout(0, 0); B.query = 0;
         if (njobs > 0 && typesize >= 1 && typesize <= 255 && shuffle >= 0 && shuffle <= 2 && cbpu_call_refused(njobs, jobs, points, npoints)) {

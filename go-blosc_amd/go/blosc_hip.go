@@ -2705,3 +2705,269 @@ func CBloscUpdateMask(frames [][]byte, arrayShape, chunkShape []int64, mask []bo
 	}
 	return CBloscUpdateVIndex(frames, arrayShape, chunkShape, coords, data, typeSize, shuffle, fill)
 }
+
+// SelJob is one chunk of a PointSelection: the chunk has ChunkItems items in blocks of BlockSize bytes (the header blocksize of the frames the
+// job will READ; 0: updates or memcpyed frames only) and owns points[First : First+Count] of the selection's point array.
+type SelJob struct {
+	ChunkItems int64
+	BlockSize  uint32
+	First      int64
+	Count      int64
+}
+
+// SelPoint is one point of a PointSelection: the chunk-local linear item index and the point's position -- the destination item of a read, the
+// source item of an update.  It has the layout of hb_cblosc_point: a device array of them serves NewPointSelectionFromDevice as it is.
+type SelPoint struct {
+	Item int64
+	Out  int64
+}
+
+// SelInfo is what a PointSelection keeps of one job (hb_cblosc_sel_info).
+type SelInfo struct {
+	Status        error
+	Unique        bool
+	Count         int64
+	NeedItems     uint64
+	TouchedBlocks int64
+}
+
+// SelSkip as an entry of jobFrame: the job sits the read out (HB_CBLOSC_SEL_SKIP).
+const SelSkip = uint32(0xFFFFFFFF)
+
+// PointSelection is a prepared point selection (hb_cblosc_point_sel): validated, its table on the device, its touched blocks known -- built
+// ONCE from host points or from device points, it serves ReadDevice and UpdateDevice for every set of frames with the chunk geometry of its
+// jobs, with per-call host work of O(jobs + touched blocks) and no per-point upload.  Device pointers are uintptr.  The selection must outlive
+// the work enqueued with it; Close synchronises its device first.
+type PointSelection struct {
+	sel      *C.hb_cblosc_point_sel
+	njobs    int
+	typeSize int
+}
+
+func selJobTable(jobs []SelJob) *C.hb_cblosc_sel_job {
+	n := len(jobs)
+	if n == 0 {
+		n = 1
+	}
+	jt := (*[1 << 26]C.hb_cblosc_sel_job)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(C.hb_cblosc_sel_job{}))))[:n:n]
+	for k, q := range jobs {
+		jt[k].chunk_items, jt[k].blocksize, jt[k].first, jt[k].count = C.int64_t(q.ChunkItems), C.uint32_t(q.BlockSize), C.int64_t(q.First), C.int64_t(q.Count)
+	}
+	return &jt[0]
+}
+
+// NewPointSelection builds a selection from host points (hb_cblosc_point_sel_create): the table goes up once.
+func NewPointSelection(jobs []SelJob, points []SelPoint, typeSize int) (*PointSelection, error) {
+	jt := selJobTable(jobs)
+	defer C.free(unsafe.Pointer(jt))
+	var pp *C.hb_cblosc_point
+	if len(points) > 0 {
+		pa := (*[1 << 27]C.hb_cblosc_point)(C.malloc(C.size_t(len(points)) * 16))[:len(points):len(points)]
+		defer C.free(unsafe.Pointer(&pa[0]))
+		for i, p := range points {
+			pa[i].item, pa[i].out = C.int64_t(p.Item), C.int64_t(p.Out)
+		}
+		pp = &pa[0]
+	}
+	var s *C.hb_cblosc_point_sel
+	if rc := C.hb_cblosc_point_sel_create(C.int(len(jobs)), jt, pp, C.int64_t(len(points)), C.int(typeSize), C.int(Device), &s); rc != C.HB_OK {
+		return nil, hbError(C.int64_t(rc))
+	}
+	return &PointSelection{s, len(jobs), typeSize}, nil
+}
+
+// NewPointSelectionFromDevice builds a selection from npoints SelPoint records in device memory (hb_cblosc_point_sel_create_device), 16-byte
+// aligned, on the current device: table, marks and checks come from one kernel per group of jobs; `stream` is synchronised before it returns.
+func NewPointSelectionFromDevice(jobs []SelJob, dPoints uintptr, npoints int64, typeSize int, stream uintptr) (*PointSelection, error) {
+	jt := selJobTable(jobs)
+	defer C.free(unsafe.Pointer(jt))
+	var s *C.hb_cblosc_point_sel
+	if rc := C.hb_cblosc_point_sel_create_device(C.int(len(jobs)), jt, (*C.hb_cblosc_point)(unsafe.Pointer(dPoints)), C.int64_t(npoints), C.int(typeSize), unsafe.Pointer(stream), &s); rc != C.HB_OK {
+		return nil, hbError(C.int64_t(rc))
+	}
+	return &PointSelection{s, len(jobs), typeSize}, nil
+}
+
+// Close synchronises the selection's device and frees its table.
+func (p *PointSelection) Close() error {
+	s := p.sel
+	p.sel = nil
+	if rc := C.hb_cblosc_point_sel_destroy(s); rc != C.HB_OK {
+		return hbError(C.int64_t(rc))
+	}
+	return nil
+}
+
+// Info answers what the selection keeps of one job.
+func (p *PointSelection) Info(job int) (SelInfo, error) {
+	var i C.hb_cblosc_sel_info
+	if rc := C.hb_cblosc_point_sel_info(p.sel, C.int(job), &i); rc != C.HB_OK {
+		return SelInfo{}, hbError(C.int64_t(rc))
+	}
+	var st error
+	if i.status != 0 {
+		st = hbError(C.int64_t(i.status))
+	}
+	return SelInfo{st, i.unique != 0, int64(i.count), uint64(i.need_items), int64(i.touched_blocks)}, nil
+}
+
+// DeviceBytes is the device memory the selection holds: 16 bytes per point of its jobs.
+func (p *PointSelection) DeviceBytes() uint64 { return uint64(C.hb_cblosc_point_sel_device_bytes(p.sel)) }
+
+// devPtrs copies device addresses (or sizes) into C memory: the C ABI takes HOST arrays of device pointers.
+func devPtrs(v []uintptr) *unsafe.Pointer {
+	n := len(v)
+	if n == 0 {
+		n = 1
+	}
+	a := (*[1 << 28]unsafe.Pointer)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(uintptr(0)))))[:n:n]
+	for k, x := range v {
+		a[k] = unsafe.Pointer(x)
+	}
+	return &a[0]
+}
+
+func cSizes(v []uint64) *C.size_t {
+	n := len(v)
+	if n == 0 {
+		n = 1
+	}
+	a := (*[1 << 28]C.size_t)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(C.size_t(0)))))[:n:n]
+	for k, x := range v {
+		a[k] = C.size_t(x)
+	}
+	return &a[0]
+}
+
+func cHeaders(frames [][]byte) *C.hb_cblosc_header {
+	n := len(frames)
+	if n == 0 {
+		n = 1
+	}
+	a := (*[1 << 26]C.hb_cblosc_header)(C.calloc(C.size_t(n), C.size_t(unsafe.Sizeof(C.hb_cblosc_header{}))))[:n:n]
+	for k, f := range frames {
+		if len(f) >= 16 {
+			C.hb_cblosc_parse_header(unsafe.Pointer(&f[0]), C.size_t(len(f)), &a[k]) // (a header that does not parse is refused job by job)
+		}
+	}
+	return &a[0]
+}
+
+// ReadWorkspace is the workspace of ReadDevice for these frames (hb_cblosc_getpoints_sel_workspace): `headers` holds the first 16 bytes of every
+// frame at least, sizes their lengths; 0 when the call as a whole would be refused.
+func (p *PointSelection) ReadWorkspace(headers [][]byte, sizes []uint64, jobFrame []uint32) uint64 {
+	if len(headers) != len(sizes) || len(jobFrame) != p.njobs || p.njobs == 0 {
+		return 0
+	}
+	hd, ns := cHeaders(headers), cSizes(sizes)
+	defer C.free(unsafe.Pointer(hd))
+	defer C.free(unsafe.Pointer(ns))
+	return uint64(C.hb_cblosc_getpoints_sel_workspace(p.sel, C.int(len(headers)), hd, ns, (*C.uint32_t)(unsafe.Pointer(&jobFrame[0]))))
+}
+
+// ReadDevice enqueues the read (hb_cblosc_getpoints_sel_device): job j reads frame jobFrame[j] -- SelSkip: it sits the call out -- into
+// dDst[j], point p at dDst[j] + Out*typeSize.  dFrames / dDst / dWork / dResults are device addresses; asynchronous on `stream`; the records
+// (one hb_result per job) say what became of each job.
+func (p *PointSelection) ReadDevice(headers [][]byte, dFrames []uintptr, sizes []uint64, jobFrame []uint32, dDst []uintptr, caps []uint64, dWork uintptr, workBytes uint64, dResults uintptr, stream uintptr) error {
+	if len(headers) != len(dFrames) || len(headers) != len(sizes) || len(jobFrame) != p.njobs || len(dDst) != p.njobs || len(caps) != p.njobs {
+		return hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	if p.njobs == 0 {
+		return nil
+	}
+	hd, ns, fr, dst, cp := cHeaders(headers), cSizes(sizes), devPtrs(dFrames), devPtrs(dDst), cSizes(caps)
+	defer C.free(unsafe.Pointer(hd))
+	defer C.free(unsafe.Pointer(ns))
+	defer C.free(unsafe.Pointer(fr))
+	defer C.free(unsafe.Pointer(dst))
+	defer C.free(unsafe.Pointer(cp))
+	rc := C.hb_cblosc_getpoints_sel_device(p.sel, C.int(len(headers)), hd, fr, ns, (*C.uint32_t)(unsafe.Pointer(&jobFrame[0])), dst, cp, unsafe.Pointer(dWork), C.size_t(workBytes),
+		(*C.hb_result)(unsafe.Pointer(dResults)), unsafe.Pointer(stream))
+	if rc != C.HB_OK {
+		return hbError(C.int64_t(rc))
+	}
+	return nil
+}
+
+// UpdateWorkspace is the workspace of UpdateDevice (hb_cblosc_update_points_sel_workspace); oldHeaders[k] is nil where chunk k has no frame yet.
+func (p *PointSelection) UpdateWorkspace(oldHeaders [][]byte, oldSizes []uint64, shuffle Shuffle) uint64 {
+	if len(oldHeaders) != p.njobs || len(oldSizes) != p.njobs {
+		return 0
+	}
+	hd, ns := cHeaders(oldHeaders), cSizes(oldSizes)
+	defer C.free(unsafe.Pointer(hd))
+	defer C.free(unsafe.Pointer(ns))
+	return uint64(C.hb_cblosc_update_points_sel_workspace(p.sel, hd, ns, C.int(shuffle), C.int(p.typeSize)))
+}
+
+// UpdateDevice enqueues the update (hb_cblosc_update_points_sel_device): job k puts item Out of dSrc[k] over item Item of old frame k (dOld[k]
+// == 0 with size 0: the fill base) and writes the NEW frame to dFrame[k].  All jobs of the selection take part.  Asynchronous on `stream`: the
+// caller looks at record k before it swaps frame k in.
+func (p *PointSelection) UpdateDevice(oldHeaders [][]byte, dOld []uintptr, oldSizes []uint64, dSrc, dFrame []uintptr, caps []uint64, fill []byte, shuffle Shuffle, dWork uintptr, workBytes uint64, dResults uintptr, stream uintptr) error {
+	n := p.njobs
+	if len(oldHeaders) != n || len(dOld) != n || len(oldSizes) != n || len(dSrc) != n || len(dFrame) != n || len(caps) != n || (fill != nil && len(fill) != p.typeSize) {
+		return hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	hd, ns, olds, srcs, dsts, cp := cHeaders(oldHeaders), cSizes(oldSizes), devPtrs(dOld), devPtrs(dSrc), devPtrs(dFrame), cSizes(caps)
+	defer C.free(unsafe.Pointer(hd))
+	defer C.free(unsafe.Pointer(ns))
+	defer C.free(unsafe.Pointer(olds))
+	defer C.free(unsafe.Pointer(srcs))
+	defer C.free(unsafe.Pointer(dsts))
+	defer C.free(unsafe.Pointer(cp))
+	var fillPtr unsafe.Pointer
+	if fill != nil {
+		fillPtr = C.CBytes(fill)
+		defer C.free(fillPtr)
+	}
+	rc := C.hb_cblosc_update_points_sel_device(p.sel, hd, olds, ns, srcs, dsts, cp, fillPtr, C.int(shuffle), C.int(p.typeSize), unsafe.Pointer(dWork), C.size_t(workBytes),
+		(*C.hb_result)(unsafe.Pointer(dResults)), unsafe.Pointer(stream))
+	if rc != C.HB_OK {
+		return hbError(C.int64_t(rc))
+	}
+	return nil
+}
+
+// SelJobs makes the jobs of a PointSelection for `z.vindex[coords]` over a grid of chunks: one SelJob per chunk that holds a point, in C order of
+// the grid, the points all of them share (Out: the point's position in coords) and the grid index of every job's chunk.  Repeated coordinates
+// stay in: a read allows them, an update refuses the job.
+func SelJobs(gridShape, chunkShape []int64, coords [][]int64, blockSize uint32) ([]SelJob, []SelPoint, []uint32, error) {
+	nd := len(chunkShape)
+	if nd < 1 || nd > 4 || len(gridShape) != nd || len(coords) != nd {
+		return nil, nil, nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	chunkItems := int64(1)
+	for d := 0; d < nd; d++ {
+		if chunkShape[d] < 1 || gridShape[d] < 0 || len(coords[d]) != len(coords[0]) {
+			return nil, nil, nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+		}
+		chunkItems *= chunkShape[d]
+	}
+	per := map[int64][]SelPoint{}
+	var touched []int64
+	for i := range coords[0] {
+		f, item := int64(0), int64(0)
+		for d := 0; d < nd; d++ {
+			v := coords[d][i]
+			if v < 0 || v >= gridShape[d]*chunkShape[d] {
+				return nil, nil, nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+			}
+			f = f*gridShape[d] + v/chunkShape[d]
+			item = item*chunkShape[d] + v%chunkShape[d]
+		}
+		if _, ok := per[f]; !ok {
+			touched = append(touched, f)
+		}
+		per[f] = append(per[f], SelPoint{item, int64(i)})
+	}
+	sort.Slice(touched, func(a, b int) bool { return touched[a] < touched[b] })
+	var jobs []SelJob
+	var points []SelPoint
+	var frames []uint32
+	for _, f := range touched {
+		jobs = append(jobs, SelJob{chunkItems, blockSize, int64(len(points)), int64(len(per[f]))})
+		points = append(points, per[f]...)
+		frames = append(frames, uint32(f))
+	}
+	return jobs, points, frames, nil
+}

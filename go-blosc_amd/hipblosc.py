@@ -113,6 +113,8 @@ EXPORTS = [
     "hb_cblosc_update_boxes_batch_workspace", "hb_cblosc_update_boxes_batch_device", "hb_cblosc_update_boxes_batch",
     "hb_cblosc_update_index_batch_workspace", "hb_cblosc_update_index_batch_device", "hb_cblosc_update_index_batch",
     "hb_cblosc_update_points_batch_workspace", "hb_cblosc_update_points_batch_device", "hb_cblosc_update_points_batch",
+    "hb_cblosc_point_sel_create", "hb_cblosc_point_sel_create_device", "hb_cblosc_point_sel_destroy", "hb_cblosc_point_sel_info", "hb_cblosc_point_sel_device_bytes",
+    "hb_cblosc_getpoints_sel_workspace", "hb_cblosc_getpoints_sel_device", "hb_cblosc_update_points_sel_workspace", "hb_cblosc_update_points_sel_device",
     "hb_cblosc_accept_codecs",
     "hb_queue_create", "hb_queue_create_ex", "hb_queue_destroy", "hb_queue_compress", "hb_queue_decompress", "hb_queue_wait",
 ]
@@ -260,6 +262,28 @@ def upd_point_job(chunk_items, first, count):
     return hb_cblosc_upd_point_job(0, 0, int(chunk_items), int(first), int(count))
 
 
+SEL_SKIP = 0xFFFFFFFF                      # HB_CBLOSC_SEL_SKIP: a job of a prepared selection sits a read out
+
+
+class hb_cblosc_sel_job(ctypes.Structure):
+    """include/hipblosc.h hb_cblosc_sel_job: one chunk of a prepared point selection -- a range of the selection's point array"""
+    _fields_ = [("chunk_items", ctypes.c_int64), ("blocksize", ctypes.c_uint32), ("reserved", ctypes.c_uint32), ("first", ctypes.c_int64), ("count", ctypes.c_int64)]
+
+
+class hb_cblosc_sel_info(ctypes.Structure):
+    """include/hipblosc.h hb_cblosc_sel_info: what a prepared selection keeps of one job"""
+    _fields_ = [("status", ctypes.c_int32), ("unique", ctypes.c_uint32), ("count", ctypes.c_int64), ("need_items", ctypes.c_uint64), ("touched_blocks", ctypes.c_int64)]
+
+    def astuple(self):
+        return (self.status, self.unique, self.count, self.need_items, self.touched_blocks)
+
+
+def sel_job(chunk_items, blocksize, first, count):
+    """hb_cblosc_sel_job: the job of a chunk of `chunk_items` items in blocks of `blocksize` bytes (0: updates or memcpyed frames only) that
+    owns points[first : first + count] of the selection's point array"""
+    return hb_cblosc_sel_job(int(chunk_items), int(blocksize), 0, int(first), int(count))
+
+
 _lib = None
 
 
@@ -358,6 +382,15 @@ def lib():
             "hb_cblosc_update_points_batch_workspace": (sz, [i32, vp, vp, i64, vp, vp, i32, i32]),
             "hb_cblosc_update_points_batch_device": (i32, [i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
             "hb_cblosc_update_points_batch": (i32, [i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32]),
+            "hb_cblosc_point_sel_create": (i32, [i32, vp, vp, i64, i32, i32, vp]),
+            "hb_cblosc_point_sel_create_device": (i32, [i32, vp, vp, i64, i32, vp, vp]),
+            "hb_cblosc_point_sel_destroy": (i32, [vp]),
+            "hb_cblosc_point_sel_info": (i32, [vp, i32, vp]),
+            "hb_cblosc_point_sel_device_bytes": (sz, [vp]),
+            "hb_cblosc_getpoints_sel_workspace": (sz, [vp, i32, vp, vp, vp]),
+            "hb_cblosc_getpoints_sel_device": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
+            "hb_cblosc_update_points_sel_workspace": (sz, [vp, vp, vp, i32, i32]),
+            "hb_cblosc_update_points_sel_device": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
             "hb_cblosc_accept_codecs": (i32, [ctypes.c_uint]),
         }
         for name, (res, args) in sig.items():
@@ -1623,6 +1656,107 @@ def CBloscUpdateMask(frames, array_shape, chunk_shape, mask, data, typesize, shu
 # batches of small frames in one set of launches (hb_compress_frames_batch / hb_decompress_frames_batch): the i-th result is what
 # Compress / Decompress would have returned for the i-th input -- a frame, or the reference's sentinel error (returned, not raised)
 # ---------------------------------------------------------------------------------------------
+def sel_jobs(grid_shape, chunk_shape, coords, typesize, blocksize):
+    """The jobs of a prepared selection for `z.vindex[coords]` over a chunked array: (jobs, points, frames) with `jobs` a list of
+    hb_cblosc_sel_job -- one per chunk that holds a point, in C order of the grid, grouped as point_jobs groups them --, `points` the
+    (item, out) pairs all of them share (out: the point's position in coords) and `frames` the grid index of every job's chunk: its entry of
+    job_frame for a read, the chunk whose frame it replaces for an update.  blocksize: the header blocksize of the frames the selection will
+    read (0: updates or memcpyed frames only).  Repeated coordinates stay in (a read allows them; an update refuses the job)."""
+    pairs, points = point_jobs(grid_shape, chunk_shape, coords, typesize)
+    chunk_items = _c_strides(chunk_shape, 1)[1]
+    return [sel_job(chunk_items, blocksize, q.first, q.count) for q, _ in pairs], points, [q.frame for q, _ in pairs]
+
+
+def _ptr_array(ptrs, n):
+    return ptrs if isinstance(ptrs, ctypes.Array) else (ctypes.c_void_p * max(n, 1))(*[None if p is None else int(p) for p in ptrs])
+
+
+def _size_array(sizes, n):
+    return sizes if isinstance(sizes, ctypes.Array) else (ctypes.c_size_t * max(n, 1))(*[int(v) for v in sizes])
+
+
+def _header_array(hdrs, n):
+    return hdrs if isinstance(hdrs, ctypes.Array) else (CBloscHeader * max(n, 1))(*hdrs)
+
+
+class PointSelection:
+    """include/hipblosc.h hb_cblosc_point_sel: a point selection built once -- validated, its table on the device, its touched blocks known --
+    that serves reads (read_device) and updates (update_device) of every set of frames with the chunk geometry of its jobs.  Device pointers
+    are plain integers; header, pointer and size arguments are sequences or ctypes arrays.  The selection must outlive the work enqueued with
+    it; close() (or leaving the `with` block) synchronises its device first."""
+
+    def __init__(self, handle, njobs, typesize):
+        self._h, self.njobs, self.typesize = handle, njobs, typesize
+
+    @staticmethod
+    def _job_array(jobs):
+        return jobs if isinstance(jobs, ctypes.Array) else (hb_cblosc_sel_job * max(len(jobs), 1))(*jobs)
+
+    @classmethod
+    def from_points(cls, jobs, points, typesize, dev=None):
+        """jobs: hb_cblosc_sel_job records (sel_job, sel_jobs); points: (item, out) pairs, or an hb_cblosc_point array"""
+        pa, npt = (points, len(points)) if isinstance(points, ctypes.Array) else _point_array(points)
+        h = ctypes.c_void_p()
+        _check(lib().hb_cblosc_point_sel_create(len(jobs), cls._job_array(jobs), pa, npt, int(typesize), device if dev is None else dev, ctypes.byref(h)))
+        return cls(h, len(jobs), int(typesize))
+
+    @classmethod
+    def from_device_points(cls, jobs, ptr, npoints, typesize, stream=None):
+        """ptr: the device address of npoints hb_cblosc_point records {int64 item, int64 out} on the current device, 16-byte aligned"""
+        h = ctypes.c_void_p()
+        _check(lib().hb_cblosc_point_sel_create_device(len(jobs), cls._job_array(jobs), None if not ptr else int(ptr), int(npoints), int(typesize), stream, ctypes.byref(h)))
+        return cls(h, len(jobs), int(typesize))
+
+    def info(self, job):
+        """hb_cblosc_sel_info of one job: status, unique, count, need_items, touched_blocks"""
+        i = hb_cblosc_sel_info()
+        _check(lib().hb_cblosc_point_sel_info(self._h, int(job), ctypes.byref(i)))
+        return i
+
+    def device_bytes(self):
+        return lib().hb_cblosc_point_sel_device_bytes(self._h)
+
+    def read_workspace(self, hdrs, sizes, job_frame):
+        nf = len(hdrs)
+        return lib().hb_cblosc_getpoints_sel_workspace(self._h, nf, _header_array(hdrs, nf), _size_array(sizes, nf), (ctypes.c_uint32 * max(self.njobs, 1))(*job_frame))
+
+    def read_device(self, hdrs, d_frames, sizes, job_frame, d_dsts, caps, d_work, work_bytes, d_results, stream=None):
+        """hb_cblosc_getpoints_sel_device: job j reads frame job_frame[j] (SEL_SKIP: it sits the call out) into d_dsts[j]; asynchronous"""
+        nf, nj = len(hdrs), self.njobs
+        return _check(lib().hb_cblosc_getpoints_sel_device(self._h, nf, _header_array(hdrs, nf), _ptr_array(d_frames, nf), _size_array(sizes, nf),
+                                                           (ctypes.c_uint32 * max(nj, 1))(*job_frame), _ptr_array(d_dsts, nj), _size_array(caps, nj), d_work, work_bytes,
+                                                           d_results, stream))
+
+    def update_workspace(self, old_hdrs, old_sizes, shuffle=1):
+        nj = self.njobs
+        return lib().hb_cblosc_update_points_sel_workspace(self._h, _header_array(old_hdrs, nj), _size_array(old_sizes, nj), shuffle, self.typesize)
+
+    def update_device(self, old_hdrs, d_olds, old_sizes, d_srcs, d_frames, caps, d_work, work_bytes, d_results, fill=None, shuffle=1, stream=None):
+        """hb_cblosc_update_points_sel_device: job k writes d_srcs[k]'s items over old frame k (None with size 0: the fill base) into the new
+        frame d_frames[k]; asynchronous -- look at d_results[k] before a frame is swapped in"""
+        nj = self.njobs
+        fb = None if fill is None else ctypes.create_string_buffer(bytes(fill), self.typesize)
+        return _check(lib().hb_cblosc_update_points_sel_device(self._h, _header_array(old_hdrs, nj), _ptr_array(d_olds, nj), _size_array(old_sizes, nj), _ptr_array(d_srcs, nj),
+                                                               _ptr_array(d_frames, nj), _size_array(caps, nj), fb, shuffle, self.typesize, d_work, work_bytes, d_results, stream))
+
+    def close(self):
+        if self._h is not None:
+            h, self._h = self._h, None
+            _check(lib().hb_cblosc_point_sel_destroy(h))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def CompressBatch(datas, codec=LZ4, level=5, shuffle=Shuffle1, typesize=4, opts=0, dev=None):
     n = len(datas)
     if n == 0:

@@ -613,6 +613,108 @@ inline std::map<int64_t, Bytes> CBloscUpdateMask(const std::vector<Bytes> &frame
     }
     return CBloscUpdateVIndex(frames, array_shape, chunk_shape, coords, data, typeSize, shuffle, fill, device);
 }
+// ---- a prepared point selection (include/hipblosc.h hb_cblosc_point_sel): built once from host points or from device points, it serves
+// hb_cblosc_getpoints_sel_device and hb_cblosc_update_points_sel_device for every set of frames with the chunk geometry of its jobs.  RAII: the
+// destructor synchronises the selection's device and frees its table, so the object must outlive the work enqueued with it.  Device pointers
+// are plain pointers; every call is asynchronous on `stream` and returns the library's code (HB_OK, or what the call as a whole refuses).
+class PointSelection {
+    hb_cblosc_point_sel *sel_ = nullptr;
+    int njobs_ = 0, typeSize_ = 0;
+    PointSelection(hb_cblosc_point_sel *s, int nj, int ts) : sel_(s), njobs_(nj), typeSize_(ts) {}
+
+public:
+    PointSelection() = default;
+    PointSelection(const PointSelection &) = delete;
+    PointSelection &operator=(const PointSelection &) = delete;
+    PointSelection(PointSelection &&o) noexcept : sel_(o.sel_), njobs_(o.njobs_), typeSize_(o.typeSize_) { o.sel_ = nullptr; }
+    PointSelection &operator=(PointSelection &&o) noexcept {
+        if (this != &o) { Close(); sel_ = o.sel_; njobs_ = o.njobs_; typeSize_ = o.typeSize_; o.sel_ = nullptr; }
+        return *this;
+    }
+    ~PointSelection() { Close(); }
+    void Close() { if (sel_) { hb_cblosc_point_sel_destroy(sel_); sel_ = nullptr; } }
+
+    static PointSelection FromPoints(const std::vector<hb_cblosc_sel_job> &jobs, const std::vector<hb_cblosc_point> &points, int typeSize, int device = 0) {
+        hb_cblosc_point_sel *s = nullptr;
+        const hb_cblosc_sel_job none{};                                      // (no jobs: the library still wants an array)
+        check(hb_cblosc_point_sel_create((int)jobs.size(), jobs.empty() ? &none : jobs.data(), points.data(), (int64_t)points.size(),
+                                         typeSize, device, &s));
+        return PointSelection(s, (int)jobs.size(), typeSize);
+    }
+    // d_points: npoints hb_cblosc_point records on the current device, 16-byte aligned; `stream` is synchronised before this returns
+    static PointSelection FromDevicePoints(const std::vector<hb_cblosc_sel_job> &jobs, const hb_cblosc_point *d_points, int64_t npoints, int typeSize, void *stream = nullptr) {
+        hb_cblosc_point_sel *s = nullptr;
+        const hb_cblosc_sel_job none{};                                      // (no jobs: the library still wants an array)
+        check(hb_cblosc_point_sel_create_device((int)jobs.size(), jobs.empty() ? &none : jobs.data(), d_points, npoints, typeSize, stream, &s));
+        return PointSelection(s, (int)jobs.size(), typeSize);
+    }
+    explicit operator bool() const { return sel_ != nullptr; }
+    const hb_cblosc_point_sel *get() const { return sel_; }
+    int Jobs() const { return njobs_; }
+    int TypeSize() const { return typeSize_; }
+    hb_cblosc_sel_info Info(int job) const {
+        hb_cblosc_sel_info i{};
+        check(hb_cblosc_point_sel_info(sel_, job, &i));
+        return i;
+    }
+    size_t DeviceBytes() const { return hb_cblosc_point_sel_device_bytes(sel_); }
+    // job j reads frame job_frame[j] (HB_CBLOSC_SEL_SKIP: it sits the call out); hdrs / d_frame / n have one entry per frame, d_dst / cap one per job
+    size_t ReadWorkspace(const std::vector<hb_cblosc_header> &hdrs, const std::vector<size_t> &n, const std::vector<uint32_t> &job_frame) const {
+        return hb_cblosc_getpoints_sel_workspace(sel_, (int)hdrs.size(), hdrs.data(), n.data(), job_frame.data());
+    }
+    int ReadDevice(const std::vector<hb_cblosc_header> &hdrs, const std::vector<const void *> &d_frame, const std::vector<size_t> &n, const std::vector<uint32_t> &job_frame,
+                   const std::vector<void *> &d_dst, const std::vector<size_t> &cap, void *d_work, size_t work_bytes, hb_result *d_results, void *stream = nullptr) const {
+        if (hdrs.size() != d_frame.size() || hdrs.size() != n.size() || job_frame.size() != (size_t)njobs_ || d_dst.size() != (size_t)njobs_ || cap.size() != (size_t)njobs_)
+            return HB_ERR_BAD_ARG;
+        return hb_cblosc_getpoints_sel_device(sel_, (int)hdrs.size(), hdrs.data(), d_frame.data(), n.data(), job_frame.data(), d_dst.data(), cap.data(), d_work, work_bytes, d_results,
+                                              stream);
+    }
+    // every array has one entry per job of the selection
+    size_t UpdateWorkspace(const std::vector<hb_cblosc_header> &old_hdrs, const std::vector<size_t> &old_n, int shuffle = 1) const {
+        if (old_hdrs.size() != (size_t)njobs_ || old_n.size() != (size_t)njobs_) return 0;
+        return hb_cblosc_update_points_sel_workspace(sel_, old_hdrs.data(), old_n.data(), shuffle, typeSize_);
+    }
+    int UpdateDevice(const std::vector<hb_cblosc_header> &old_hdrs, const std::vector<const void *> &d_old, const std::vector<size_t> &old_n, const std::vector<const void *> &d_src,
+                     const std::vector<void *> &d_frame, const std::vector<size_t> &cap, void *d_work, size_t work_bytes, hb_result *d_results, const void *fill = nullptr,
+                     int shuffle = 1, void *stream = nullptr) const {
+        const size_t nj = (size_t)njobs_;
+        if (old_hdrs.size() != nj || d_old.size() != nj || old_n.size() != nj || d_src.size() != nj || d_frame.size() != nj || cap.size() != nj) return HB_ERR_BAD_ARG;
+        return hb_cblosc_update_points_sel_device(sel_, old_hdrs.data(), d_old.data(), old_n.data(), d_src.data(), d_frame.data(), cap.data(), fill, shuffle, typeSize_, d_work,
+                                                  work_bytes, d_results, stream);
+    }
+};
+// The jobs of a prepared selection for `z.vindex[coords]` over a grid of chunks: one hb_cblosc_sel_job per chunk that holds a point, in C order
+// of the grid; `points` gets the {item, out} records all of them share (out: the point's position in coords), `frames` the grid index of every
+// job's chunk.  Repeated coordinates stay in: a read allows them, an update refuses the job.
+inline std::vector<hb_cblosc_sel_job> SelJobs(const std::vector<int64_t> &grid_shape, const std::vector<int64_t> &chunk_shape, const std::vector<std::vector<int64_t>> &coords,
+                                              uint32_t blocksize, std::vector<hb_cblosc_point> &points, std::vector<uint32_t> &frames) {
+    const size_t nd = chunk_shape.size();
+    if (nd < 1 || nd > 4 || grid_shape.size() != nd || coords.size() != nd) check(HB_ERR_BAD_ARG);
+    int64_t chunk_items = 1;
+    for (size_t d = 0; d < nd; d++) {
+        if (chunk_shape[d] < 1 || grid_shape[d] < 0 || coords[d].size() != coords[0].size()) check(HB_ERR_BAD_ARG);
+        chunk_items *= chunk_shape[d];
+    }
+    std::map<int64_t, std::vector<hb_cblosc_point>> per;
+    for (size_t i = 0; i < coords[0].size(); i++) {
+        int64_t f = 0, item = 0;
+        for (size_t d = 0; d < nd; d++) {
+            const int64_t v = coords[d][i];
+            if (v < 0 || v >= grid_shape[d] * chunk_shape[d]) check(HB_ERR_BAD_ARG);
+            f = f * grid_shape[d] + v / chunk_shape[d];
+            item = item * chunk_shape[d] + v % chunk_shape[d];
+        }
+        per[f].push_back(hb_cblosc_point{item, (int64_t)i});
+    }
+    std::vector<hb_cblosc_sel_job> jobs;
+    points.clear(); frames.clear();
+    for (const auto &e : per) {
+        jobs.push_back(hb_cblosc_sel_job{chunk_items, blocksize, 0u, (int64_t)points.size(), (int64_t)e.second.size()});
+        points.insert(points.end(), e.second.begin(), e.second.end());
+        frames.push_back((uint32_t)e.first);
+    }
+    return jobs;
+}
 inline Header GetInfo(const Bytes &data) { return ParseHeader(data); }                                            // blosc.go:306-308
 inline int GetDecompressedSize(const Bytes &data) { return (int)ParseHeader(data).NBytesOrig; }                   // blosc.go:311-317
 

@@ -901,6 +901,71 @@ int     hb_cblosc_update_points_batch_device(int njobs, const hb_cblosc_upd_poin
 int     hb_cblosc_update_points_batch(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints,
                                       const void *const *old, const size_t *old_n, const void *const *src, void *const *dst, const size_t *cap, int64_t *rc,
                                       const void *fill, int shuffle, int typesize, int device);
+/* ---- prepared C-Blosc-1 point selections: what hb_cblosc_getpoints_frames_batch* and hb_cblosc_update_points_batch* work out from the points on
+ *      every call -- the validation, the 16-byte table entry per point and its upload, the touched blocks, the repeat check -- built ONCE and
+ *      kept.  A frame's block geometry follows from nbytes, typesize and the compressor settings, never from the data, so one selection serves
+ *      every frame of the same chunk shape: the same mask over every time step, the same sample points every iteration, a read-modify-write
+ *      whose reads and writes name the same coordinates.  A selection has one typesize and njobs jobs; a job is one chunk and owns
+ *      points[first .. first + count), hb_cblosc_point records, shared or overlapping ranges allowed.  `out` is the point's position: the
+ *      destination item of a read, the source item of an update (hb_cblosc_upd_point's `src`).
+ *      Building: hb_cblosc_point_sel_create takes HOST points and uploads the table once; hb_cblosc_point_sel_create_device takes DEVICE points
+ *      (the output of a device nonzero, a top-k, a sampler; 16-byte aligned) on the current device, builds table, marks and checks with one
+ *      kernel per group of jobs, and synchronises `stream` before it returns: the caller's points are not needed after either create.  The call as a whole answers HB_ERR_BAD_ARG, before the device is looked for
+ *      (HB_ERR_NO_DEVICE comes after), for: njobs < 0, jobs == NULL, sel == NULL, typesize outside 1..255, npoints < 0, points == NULL while
+ *      some job has count > 0, a reserved field that is not 0, more than HB_CBLOSC_BATCH_MAX_WORK points over all jobs.  *sel is NULL unless
+ *      HB_OK is returned.  A job's status is kept in the selection and answered at every use: HB_ERR_BAD_ARG for first < 0, count < 0,
+ *      first + count > npoints (checked without overflow) or chunk_items < 0; HB_ERR_DATA_TOO_LARGE for chunk_items * typesize as for the
+ *      box writes; HB_ERR_BAD_ARG for an item outside [0, chunk_items), out < 0, (out + 1) * typesize beyond 64 bits.  An item that occurs
+ *      twice does not refuse the job, it clears `unique`: reads allow repeats, updates do not.  Both builders give selections with the same
+ *      hb_cblosc_sel_info for every job and the same behaviour in every call.
+ *      A selection keeps, on its device, the table of its jobs (16 bytes per point) and, on the host, per job its status, count, need_items,
+ *      unique and -- where blocksize != 0 -- the touched blocks as runs: nothing on the host grows with the points.  It is immutable and may
+ *      be used from several threads and streams at once; it MUST OUTLIVE all work enqueued with it, and hb_cblosc_point_sel_destroy
+ *      synchronises its device first.
+ *      Reads (hb_cblosc_getpoints_sel_*): job_frame[j] is the frame job j reads, HB_CBLOSC_SEL_SKIP skips the job (status 0, bytes 0, nothing
+ *      planned or written).  Job j gives exactly the destination bytes and the hb_result that hb_cblosc_getpoints_frames_batch_device gives for
+ *      {job_frame[j], first, count} over the same points.  Refused per job in this order: the header, codec and geometry refusals of
+ *      hb_cblosc_getitem; the job's stored status; HB_ERR_BAD_ARG for header typesize != the selection's, nbytes / typesize != chunk_items, or
+ *      a frame that is not memcpyed whose header blocksize != the job's blocksize; HB_ERR_SHORT_BUFFER for cap[j] < need_items * typesize;
+ *      HB_ERR_BAD_ARG for a NULL d_frame[f], or a NULL d_dst[j] with bytes to write.  The call as a whole: as the point batch, and
+ *      HB_ERR_BAD_ARG for sel == NULL, job_frame == NULL, job_frame[j] >= nframes that is not the skip value, or a current device that is
+ *      not the selection's.  Workspace: the point batch's bound without its HB_CBLOSC_POINT_BATCH_POINT_BYTES term.
+ *      Updates (hb_cblosc_update_points_sel_*): the arrays are indexed by the selection's jobs and all jobs take part.  Frame k is byte for
+ *      byte, and with the same hb_result, what hb_cblosc_update_points_batch_device gives for {chunk_items, first, count} over the points read
+ *      as {item, src = out}.  In the box updates' refusal group 1. a job answers HB_ERR_BAD_ARG where its stored status is HB_ERR_BAD_ARG,
+ *      `unique` is 0 or the old frame's nbytes / typesize != chunk_items (a stored HB_ERR_DATA_TOO_LARGE is group 2.).  A `typesize` that is
+ *      not the selection's is HB_ERR_BAD_ARG for the call as a whole, as are sel == NULL and a current device that is not the selection's.
+ *      Per-call host work is O(jobs + touched blocks); no table is built or uploaded. ---- */
+#define HB_CBLOSC_SEL_SKIP 0xFFFFFFFFu           /* job_frame[j]: the job sits this call out */
+typedef struct hb_cblosc_point_sel hb_cblosc_point_sel;
+typedef struct hb_cblosc_sel_job {
+    int64_t  chunk_items;      /* nbytes / typesize of every frame this job will meet */
+    uint32_t blocksize;        /* header blocksize of the frames it will READ; 0: updates (or memcpyed frames) only */
+    uint32_t reserved;         /* 0 */
+    int64_t  first, count;     /* points[first .. first + count) */
+} hb_cblosc_sel_job;
+typedef struct hb_cblosc_sel_info {
+    int32_t  status;           /* the job's stored status */
+    uint32_t unique;           /* 1: no item occurs twice (0 for a refused job) */
+    int64_t  count;            /* the job's points */
+    uint64_t need_items;       /* max out + 1: a read needs cap >= need_items * typesize (0 for a refused job or no points) */
+    int64_t  touched_blocks;   /* blocks of `blocksize` bytes that hold a byte of a selected item (0 where blocksize == 0) */
+} hb_cblosc_sel_info;
+int     hb_cblosc_point_sel_create(int njobs, const hb_cblosc_sel_job *jobs, const hb_cblosc_point *points, int64_t npoints, int typesize, int device,
+                                   hb_cblosc_point_sel **sel);
+int     hb_cblosc_point_sel_create_device(int njobs, const hb_cblosc_sel_job *jobs, const hb_cblosc_point *d_points, int64_t npoints, int typesize,
+                                          void *stream, hb_cblosc_point_sel **sel);
+int     hb_cblosc_point_sel_destroy(hb_cblosc_point_sel *sel);      /* NULL: HB_OK */
+int     hb_cblosc_point_sel_info(const hb_cblosc_point_sel *sel, int job, hb_cblosc_sel_info *info);
+size_t  hb_cblosc_point_sel_device_bytes(const hb_cblosc_point_sel *sel);
+size_t  hb_cblosc_getpoints_sel_workspace(const hb_cblosc_point_sel *sel, int nframes, const hb_cblosc_header *hdrs, const size_t *n, const uint32_t *job_frame);
+int     hb_cblosc_getpoints_sel_device(const hb_cblosc_point_sel *sel, int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n,
+                                       const uint32_t *job_frame, void *const *d_dst, const size_t *cap, void *d_work, size_t work_bytes,
+                                       hb_result *d_results, void *stream);
+size_t  hb_cblosc_update_points_sel_workspace(const hb_cblosc_point_sel *sel, const hb_cblosc_header *old_hdrs, const size_t *old_n, int shuffle, int typesize);
+int     hb_cblosc_update_points_sel_device(const hb_cblosc_point_sel *sel, const hb_cblosc_header *old_hdrs, const void *const *d_old, const size_t *old_n,
+                                           const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill, int shuffle, int typesize,
+                                           void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
 
 #ifdef __cplusplus
 }
