@@ -39,6 +39,7 @@
 #include "hb_cblosc_upd_point_batch.h" // the point updates: refusal, point table, records, and the scatter's thread
 #include "hb_cblosc_upd_box_batch.h"   // the geometry of an update box, the host side of the batched box updates, the overlay's index arithmetic
 #include "hb_cblosc_point_sel.h"       // the prepared point selections: what a selection keeps, its two builders, the builder kernel's thread, the per-call prepares
+#include "hb_cblosc_array_sel.h"       // selections from device masks and coordinate arrays: the geometry, the row arithmetic, the bodies of the kernels' threads
 
 // ---- the streams of blocks [b0, b0 + nb) (hb_cblosc_getitem_device: the blocks that cover a range; the others' bstarts entries and streams
 // are never read); stream offsets count from the first of these blocks ----
@@ -1240,6 +1241,148 @@ __global__ __launch_bounds__(256) void k_cbsel_build(const CbselJob *__restrict_
     cbsel_thread(jobs[i], in, tab, ts, out_lim, ibits, bbits, outs + i, blockIdx.x - blk[i], threadIdx.x, io);
 }
 
+// ---- selections from a device mask or device coordinate arrays of the whole array (hb_cblosc_point_sel_create_mask_device / _coords_device;
+// the geometry, the row arithmetic and the bodies of the threads are hb_cblosc_array_sel.h).  Every dependency between workgroups is a kernel
+// boundary.  Mask: k_cbas_mask_count (a wave per chunk row: its selected bytes), the two prefix sums over the row counts -- chunk-major and
+// array order -- by k_cbas_tiles / k_cbas_scan / k_cbas_apply, k_cbas_chunks ({first, count} per chunk: what comes down), k_cbas_mask_emit (a
+// wave per row with a selected byte: ballot, mbcnt rank, one 16-byte store per point).  Coordinates: k_cbas_coord_bucket (a thread per point:
+// its slot from its chunk's counter, large groups of a wave on one chunk sharing the atomic add), the prefix sum over the counters,
+// k_cbas_coord_place.  No LDS beyond the scans' four words. ----
+#define CBAS_MERGE_MIN 8u                // lanes of a wave on one chunk that share an atomic add (take_slot)
+struct CbasDeviceIO {
+    __device__ __forceinline__ uint32_t load8(const uint8_t *p) { return *p; }
+    __device__ __forceinline__ CbasVec load16(const uint8_t *p) { const u32x4 v = *(const u32x4 *)p; return CbasVec{v.x, v.y, v.z, v.w}; }
+    __device__ __forceinline__ uint32_t load32(const uint32_t *p) { return *p; }
+    __device__ __forceinline__ void store32(uint32_t *p, uint32_t v) { *p = v; }
+    __device__ __forceinline__ int64_t load_i64(const int64_t *p) { return *p; }
+    __device__ __forceinline__ void store_pair(uint32_t *p, uint32_t a, uint32_t b) { u32x2 v; v.x = a; v.y = b; *(u32x2 *)p = v; }
+    __device__ __forceinline__ void store_point(hb_cblosc_point *p, const hb_cblosc_point &pt) {
+        u32x4 v; v.x = (uint32_t)pt.item; v.y = (uint32_t)((uint64_t)pt.item >> 32); v.z = (uint32_t)pt.out; v.w = (uint32_t)((uint64_t)pt.out >> 32);
+        *(u32x4 *)p = v;
+    }
+    __device__ __forceinline__ CbasRec load_rec(const CbasRec *p) { const u32x4 v = *(const u32x4 *)p; return CbasRec{v.x, v.y, v.z, v.w}; }
+    __device__ __forceinline__ void store_rec(CbasRec *p, const CbasRec &r) { u32x4 v; v.x = r.chunk; v.y = r.slot; v.z = r.item; v.w = r.pad; *(u32x4 *)p = v; }
+    // (every lane of the wave is here: the kernel's only exit in front of it is the whole wave's)
+    __device__ __forceinline__ void row_sum(uint32_t *p, uint32_t v) {
+        for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d, 64);
+        if ((threadIdx.x & 63u) == 0u) *p = v;
+    }
+    __device__ __forceinline__ void raise(uint32_t *w) {
+        if (!__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicOr(w, 1u);
+    }
+    // One atomic add per point serialises where many points fall into one chunk (262144 points of one chunk: 3.0 ms of bucket against 0.14 ms
+    // for the same points over 256 chunks).  So, while the first lane that still waits has at least CBAS_MERGE_MIN lanes of its wave with it on
+    // the same chunk, that group takes its slots with ONE add: the leader adds the group's size and every member gets the answer plus its
+    // rank in the group.  At most 64 / CBAS_MERGE_MIN rounds; whoever is left adds for itself.  (The lanes that are here are the wave's
+    // active ones: ballots, the shuffles from the leader and the loop's exits are uniform among them.)
+    __device__ __forceinline__ uint32_t take_slot(uint32_t *counters, uint32_t chunk) {
+        const uint32_t lane = threadIdx.x & 63u;
+        uint32_t slot = 0;
+        bool waits = true;
+        for (uint32_t round = 0; round < 64u / CBAS_MERGE_MIN; round++) {
+            const uint64_t open = __ballot(waits);
+            if (!open) break;
+            const int leader = __ffsll((unsigned long long)open) - 1;
+            const uint32_t c = __shfl(chunk, leader, 64);
+            const bool mine = waits && chunk == c;
+            const uint64_t peers = __ballot(mine);
+            const uint32_t n = (uint32_t)__popcll(peers);
+            if (n < CBAS_MERGE_MIN) break;
+            uint32_t base = 0;
+            if (lane == (uint32_t)leader) base = atomicAdd(counters + c, n);
+            base = __shfl(base, leader, 64);
+            if (mine) {
+                slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(peers >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)peers, 0u));
+                waits = false;
+            }
+        }
+        if (waits) slot = atomicAdd(counters + chunk, 1u);
+        return slot;
+    }
+};
+#define CBAS_ROWS_PER_GROUP 4u           // a wave per chunk row, four waves per workgroup
+__global__ __launch_bounds__(256) void k_cbas_mask_count(CbasGeom g, const uint8_t *__restrict__ mask, uint32_t *__restrict__ counts) {
+    const uint32_t row = blockIdx.x * CBAS_ROWS_PER_GROUP + (threadIdx.x >> 6);
+    if (row >= g.nrows) return;                                           // (the whole wave)
+    CbasDeviceIO io;
+    cbas_count_thread(g, mask, counts, row, threadIdx.x & 63u, io);
+}
+__global__ __launch_bounds__(256) void k_cbas_mask_emit(CbasGeom g, const uint8_t *__restrict__ mask, const uint32_t *__restrict__ scan_cm, const uint32_t *__restrict__ scan_ar,
+                                                         hb_cblosc_point *__restrict__ pts) {
+    const uint32_t row = blockIdx.x * CBAS_ROWS_PER_GROUP + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (row >= g.nrows) return;
+    const uint32_t pos = scan_cm[row], n = scan_cm[row + 1u] - pos;
+    if (!n) return;                                                       // (most rows of a sparse mask end here)
+    CbasDeviceIO io;
+    const CbasRow R = cbas_row(g, row);
+    const uint32_t out = scan_ar[R.arow];
+    // (the row has n selected bytes, so the walk ends inside it; a mask that changed since the count neither walks on nor writes past the row's n entries)
+    for (uint32_t step = 0, run = 0; run < n && step * 64u < R.len; step++) {
+        const bool pred = cbas_emit_pred(mask, R, step, lane, io);
+        const uint64_t ballot = __ballot(pred);
+        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(ballot >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ballot, 0u));
+        cbas_emit_store(pts, R, pos + run, out + run, n - run, step, lane, pred, rank, io);
+        run += (uint32_t)__popcll(ballot);
+    }
+}
+// the exclusive prefix of v over the workgroup's 256 threads and its total; s_w: four words of LDS, free again when it returns
+__device__ __forceinline__ uint32_t cbas_block_excl(uint32_t v, uint32_t *s_w, uint32_t &total) {
+    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
+    uint32_t inc = v;
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t o = __shfl_up(inc, d, 64);
+        if (lane >= (uint32_t)d) inc += o;
+    }
+    if (lane == 63u) s_w[w] = inc;
+    __syncthreads();
+    uint32_t base = 0;
+    total = 0;
+    for (uint32_t k = 0; k < 4u; k++) { const uint32_t x = s_w[k]; base += k < w ? x : 0u; total += x; }
+    __syncthreads();
+    return base + inc - v;
+}
+// blockIdx.y: the order (0: as the counts lie; 1: array order, the mask form's second sum); its tile sums and prefixes lie ntiles words further on
+__global__ __launch_bounds__(256) void k_cbas_tiles(CbasGeom g, const uint32_t *__restrict__ counts, uint32_t n, uint32_t ntiles, uint32_t *__restrict__ tile_sum) {
+    __shared__ uint32_t s_w[4];
+    CbasDeviceIO io;
+    uint32_t total;
+    cbas_block_excl(cbas_tile_thread(g, counts, blockIdx.y, n, blockIdx.x, threadIdx.x, io), s_w, total);
+    if (threadIdx.x == 0u) tile_sum[(size_t)blockIdx.y * ntiles + blockIdx.x] = total;
+}
+// one workgroup per order: the exclusive prefix of the tile sums
+__global__ __launch_bounds__(256) void k_cbas_scan(const uint32_t *__restrict__ tile_sum, uint32_t *__restrict__ tile_pre, uint32_t ntiles) {
+    __shared__ uint32_t s_w[4];
+    tile_sum += (size_t)blockIdx.x * ntiles; tile_pre += (size_t)blockIdx.x * ntiles;
+    uint32_t carry = 0;
+    for (uint32_t base = 0; base < ntiles; base += 256u) {                // (uniform: every thread takes every barrier)
+        const uint32_t i = base + threadIdx.x;
+        uint32_t total;
+        const uint32_t excl = cbas_block_excl(i < ntiles ? tile_sum[i] : 0u, s_w, total);
+        if (i < ntiles) tile_pre[i] = carry + excl;
+        carry += total;
+    }
+}
+__global__ __launch_bounds__(256) void k_cbas_apply(CbasGeom g, const uint32_t *__restrict__ counts, uint32_t n, uint32_t ntiles, const uint32_t *__restrict__ tile_pre,
+                                                     uint32_t *__restrict__ out0, uint32_t *__restrict__ out1) {
+    __shared__ uint32_t s_w[4];
+    CbasDeviceIO io;
+    uint32_t total;
+    const uint32_t excl = cbas_block_excl(cbas_tile_thread(g, counts, blockIdx.y, n, blockIdx.x, threadIdx.x, io), s_w, total);
+    cbas_apply_thread(g, counts, blockIdx.y, n, blockIdx.x, threadIdx.x, tile_pre[(size_t)blockIdx.y * ntiles + blockIdx.x] + excl, blockIdx.y ? out1 : out0, io);
+}
+__global__ __launch_bounds__(256) void k_cbas_chunks(CbasGeom g, const uint32_t *__restrict__ scan_cm, uint32_t *__restrict__ pairs) {
+    CbasDeviceIO io;
+    cbas_chunk_thread(g, scan_cm, pairs, blockIdx.x * 256u + threadIdx.x, io);
+}
+__global__ __launch_bounds__(256) void k_cbas_coord_bucket(CbasGeom g, CbasCoords X, uint32_t npoints, uint32_t *counters, uint32_t *flag, CbasRec *__restrict__ rec) {
+    CbasDeviceIO io;
+    cbas_bucket_thread(g, X, npoints, blockIdx.x * 256u + threadIdx.x, counters, flag, rec, io);
+}
+__global__ __launch_bounds__(256) void k_cbas_coord_place(const CbasRec *__restrict__ rec, const uint32_t *__restrict__ first, hb_cblosc_point *__restrict__ pts, uint32_t npoints) {
+    CbasDeviceIO io;
+    cbas_place_thread(rec, first, pts, npoints, blockIdx.x * 256u + threadIdx.x, io);
+}
+
 void hb_launch_match_selfcontained(const uint8_t *src, size_t n, void *desc, uint8_t *records, uint32_t nchunks, int accel, hipStream_t s);   // hb_lz4_enc.hip
 bool hb_launch_match_fused_selfcontained(const uint8_t *src, int typesize, void *desc, uint8_t *records, uint32_t nblk, int accel, hipStream_t s);
 void hb_launch_match_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, void *desc, uint8_t *records, uint32_t total_chunks, int accel, hipStream_t s);
@@ -2085,8 +2228,9 @@ struct hb_cblosc_point_sel {
     CbselKnown W;                        // ... and, derived from it once, what the update's stage takes for its sweeps' answers (per job)
     int device;
     CbpPoint *d_tab;                     // the table of its jobs on `device`: P.npts entries
+    bool from_array;                     // built from a mask or coordinates of a whole array:
+    std::vector<uint32_t> chunks;        // ... the chunk of every job, in C order of the grid
 };
-extern "C" {
 static void cbsel_free(hb_cblosc_point_sel *S) {
     if (S->d_tab) (void)hipFree(S->d_tab);
     delete S;
@@ -2101,30 +2245,10 @@ static int cbsel_new(int njobs, const hb_cblosc_sel_job *jobs, int64_t npoints, 
     *out = S;
     return HB_OK;
 }
-
-int hb_cblosc_point_sel_create(int njobs, const hb_cblosc_sel_job *jobs, const hb_cblosc_point *points, int64_t npoints, int typesize, int device,
-                               hb_cblosc_point_sel **sel) {
-    if (sel) *sel = nullptr;
-    if (cbsel_call_refused(njobs, jobs, points, npoints, typesize, sel)) return HB_ERR_BAD_ARG;
-    if (const int rc = hb_select_device(device)) return rc;
-    hb_cblosc_point_sel *S = nullptr;
-    if (const int rc = cbsel_new(njobs, jobs, npoints, typesize, &S)) return rc;
-    try {
-        std::vector<CbpPoint> tab;
-        cbsel_build_host(S->P, points, tab);
-        cbsel_known(S->P, S->W);
-        if (!tab.empty() && hipMemcpy(S->d_tab, tab.data(), tab.size() * sizeof(CbpPoint), hipMemcpyHostToDevice) != hipSuccess) { cbsel_free(S); return HB_ERR_HIP; }
-    } catch (const std::bad_alloc &) { cbsel_free(S); return HB_ERR_BAD_ARG; }
-    *sel = S;
-    return HB_OK;
-}
-
-int hb_cblosc_point_sel_create_device(int njobs, const hb_cblosc_sel_job *jobs, const hb_cblosc_point *d_points, int64_t npoints, int typesize, void *stream,
-                                      hb_cblosc_point_sel **sel) {
-    if (sel) *sel = nullptr;
-    if (cbsel_call_refused(njobs, jobs, d_points, npoints, typesize, sel) || ((uintptr_t)d_points & 15u)) return HB_ERR_BAD_ARG;
-    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
-    hipStream_t s = (hipStream_t)stream;
+// the device builder behind the checks of its callers (the call is not refused as a whole, a device is there, *sel is NULL): the groups of
+// jobs through k_cbsel_build, one after the other; synchronises `s`
+static int cbsel_create_from_device(int njobs, const hb_cblosc_sel_job *jobs, const hb_cblosc_point *d_points, int64_t npoints, int typesize, hipStream_t s,
+                                    hb_cblosc_point_sel **sel) {
     hb_cblosc_point_sel *S = nullptr;
     if (const int rc = cbsel_new(njobs, jobs, npoints, typesize, &S)) return rc;
     uint8_t *d_grp = nullptr;
@@ -2165,6 +2289,200 @@ int hb_cblosc_point_sel_create_device(int njobs, const hb_cblosc_sel_job *jobs, 
     if (d_grp) (void)hipFree(d_grp);
     if (rc) { cbsel_free(S); return rc; }
     *sel = S;
+    return HB_OK;
+}
+
+// ---- selections from device masks and coordinate arrays (include/hipblosc.h; hb_cblosc_array_sel.h) ----
+// the builder's own device memory: one allocation of sections, each 256-byte aligned, and the temporary points
+struct CbasMem {
+    uint8_t *d_work = nullptr;
+    hb_cblosc_point *d_pts = nullptr;
+    ~CbasMem() { if (d_work) (void)hipFree(d_work); if (d_pts) (void)hipFree(d_pts); }
+};
+// exclusive prefix sums of the n words at `counts` into out0 (and, in array order, out1 where orders == 2; else out1 is not looked at): n + 1 words each
+static void cbas_scan_launch(const CbasGeom &g, const uint32_t *counts, uint32_t n, uint32_t orders, uint32_t *tile_sum, uint32_t *tile_pre, uint32_t *out0, uint32_t *out1, hipStream_t s) {
+    const uint32_t ntiles = cbas_ntiles(n);
+    hb_prof_begin("k_cbas_tiles", s);
+    hipLaunchKernelGGL(k_cbas_tiles, dim3(ntiles, orders), dim3(256), 0, s, g, counts, n, ntiles, tile_sum);
+    hb_prof_end(s);
+    hb_prof_begin("k_cbas_scan", s);
+    hipLaunchKernelGGL(k_cbas_scan, dim3(orders), dim3(256), 0, s, (const uint32_t *)tile_sum, tile_pre, ntiles);
+    hb_prof_end(s);
+    hb_prof_begin("k_cbas_apply", s);
+    hipLaunchKernelGGL(k_cbas_apply, dim3(ntiles, orders), dim3(256), 0, s, g, counts, n, ntiles, (const uint32_t *)tile_pre, out0, out1);
+    hb_prof_end(s);
+}
+// the jobs of the chunks with points over the temporary points -> the selection, which remembers its chunks
+static int cbas_finish(const std::vector<hb_cblosc_sel_job> &jobs, std::vector<uint32_t> &chunks, const hb_cblosc_point *d_pts, int64_t npoints, int typesize, hipStream_t s,
+                       hb_cblosc_point_sel **sel) {
+    if (jobs.size() > (size_t)0x7FFFFFFF) return HB_ERR_BAD_ARG;
+    const int rc = cbsel_create_from_device((int)jobs.size(), jobs.data(), d_pts, npoints, typesize, s, sel);
+    if (rc) return rc;
+    (*sel)->from_array = true;
+    (*sel)->chunks.swap(chunks);
+    return HB_OK;
+}
+static int cbas_create_mask(const CbasGeom &g, int64_t chunk_items, uint32_t blocksize, const uint8_t *d_mask, int typesize, hipStream_t s, hb_cblosc_point_sel **sel) {
+    CbasMem M;
+    const uint32_t nrows = g.nrows, ntiles = cbas_ntiles(nrows);
+    size_t o = 0;
+    auto take = [&](size_t b) { size_t at = o; o += cb_align(b); return at; };
+    const size_t o_counts = take((size_t)nrows * 4), o_cm = take(((size_t)nrows + 1) * 4), o_ar = take(((size_t)nrows + 1) * 4), o_tsum = take((size_t)ntiles * 8),
+                 o_tpre = take((size_t)ntiles * 8), o_pairs = take((size_t)g.nchunks * 8);
+    if (hipMalloc((void **)&M.d_work, o) != hipSuccess) { M.d_work = nullptr; return HB_ERR_HIP; }
+    uint8_t *w = M.d_work;
+    uint32_t *counts = (uint32_t *)(w + o_counts), *scan_cm = (uint32_t *)(w + o_cm), *scan_ar = (uint32_t *)(w + o_ar), *pairs = (uint32_t *)(w + o_pairs);
+    const uint32_t row_groups = (uint32_t)(((uint64_t)nrows + CBAS_ROWS_PER_GROUP - 1u) / CBAS_ROWS_PER_GROUP);
+    hb_prof_begin("k_cbas_mask_count", s);
+    hipLaunchKernelGGL(k_cbas_mask_count, dim3(row_groups), dim3(256), 0, s, g, d_mask, counts);
+    hb_prof_end(s);
+    cbas_scan_launch(g, counts, nrows, 2u, (uint32_t *)(w + o_tsum), (uint32_t *)(w + o_tpre), scan_cm, scan_ar, s);
+    hb_prof_begin("k_cbas_chunks", s);
+    hipLaunchKernelGGL(k_cbas_chunks, dim3((g.nchunks + 255u) / 256u), dim3(256), 0, s, g, (const uint32_t *)scan_cm, pairs);
+    hb_prof_end(s);
+    // the per-chunk records come down: the one download that grows with the grid
+    std::vector<uint32_t> down((size_t)g.nchunks * 2);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(down.data(), pairs, down.size() * 4, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+        return HB_ERR_HIP;
+    std::vector<hb_cblosc_sel_job> jobs;
+    std::vector<uint32_t> chunks;
+    cbas_jobs(g.nchunks, down.data(), down.data() + 1, 2, chunk_items, blocksize, jobs, chunks);
+    const uint64_t npts = jobs.empty() ? 0u : (uint64_t)jobs.back().first + (uint64_t)jobs.back().count;
+    if (npts > HB_CBLOSC_BATCH_MAX_WORK) return HB_ERR_BAD_ARG;
+    if (npts) {
+        if (hipMalloc((void **)&M.d_pts, (size_t)npts * sizeof(hb_cblosc_point)) != hipSuccess) { M.d_pts = nullptr; return HB_ERR_HIP; }
+        hb_prof_begin("k_cbas_mask_emit", s);
+        hipLaunchKernelGGL(k_cbas_mask_emit, dim3(row_groups), dim3(256), 0, s, g, d_mask, (const uint32_t *)scan_cm, (const uint32_t *)scan_ar, M.d_pts);
+        hb_prof_end(s);
+        if (hipGetLastError() != hipSuccess) { (void)hipStreamSynchronize(s); return HB_ERR_HIP; }
+    }
+    return cbas_finish(jobs, chunks, M.d_pts, (int64_t)npts, typesize, s, sel);      // (it synchronises `s`: the temporary memory may go)
+}
+static int cbas_create_coords(const CbasGeom &g, int64_t chunk_items, uint32_t blocksize, const int64_t *const *d_coords, int ndim, uint32_t npoints, int typesize, hipStream_t s,
+                              hb_cblosc_point_sel **sel) {
+    CbasMem M;
+    const uint32_t nchunks = g.nchunks, ntiles = cbas_ntiles(nchunks);
+    size_t o = 0;
+    auto take = [&](size_t b) { size_t at = o; o += cb_align(b); return at; };
+    // [counters | their prefix, n + 1 words | the flag word] lie together: they come down in one copy
+    const size_t o_cnt = 0, o_first = (size_t)nchunks * 4, o_flag = o_first + ((size_t)nchunks + 1) * 4, head = o_flag + 4;
+    take(head);
+    const size_t o_tsum = take((size_t)ntiles * 4), o_tpre = take((size_t)ntiles * 4), o_rec = take((size_t)npoints * sizeof(CbasRec));
+    if (hipMalloc((void **)&M.d_work, o) != hipSuccess) { M.d_work = nullptr; return HB_ERR_HIP; }
+    if (hipMalloc((void **)&M.d_pts, (size_t)npoints * sizeof(hb_cblosc_point)) != hipSuccess) { M.d_pts = nullptr; return HB_ERR_HIP; }
+    uint8_t *w = M.d_work;
+    uint32_t *counters = (uint32_t *)(w + o_cnt), *first = (uint32_t *)(w + o_first), *flag = (uint32_t *)(w + o_flag);
+    CbasRec *rec = (CbasRec *)(w + o_rec);
+    CbasCoords X{};
+    for (int k = 0; k < ndim; k++) X.p[(4 - ndim) + k] = d_coords[k];
+    if (hipMemsetAsync(w, 0, head, s) != hipSuccess) return HB_ERR_HIP;
+    const uint32_t groups = (uint32_t)(((uint64_t)npoints + 255u) / 256u);
+    hb_prof_begin("k_cbas_coord_bucket", s);
+    hipLaunchKernelGGL(k_cbas_coord_bucket, dim3(groups), dim3(256), 0, s, g, X, npoints, counters, flag, rec);
+    hb_prof_end(s);
+    cbas_scan_launch(g, counters, nchunks, 1u, (uint32_t *)(w + o_tsum), (uint32_t *)(w + o_tpre), first, nullptr, s);
+    std::vector<uint32_t> down(head / 4);
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(down.data(), w, head, hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return HB_ERR_HIP;
+    if (down[o_flag / 4]) return HB_ERR_BAD_ARG;                          // a coordinate outside the array
+    hb_prof_begin("k_cbas_coord_place", s);
+    hipLaunchKernelGGL(k_cbas_coord_place, dim3(groups), dim3(256), 0, s, (const CbasRec *)rec, (const uint32_t *)first, M.d_pts, npoints);
+    hb_prof_end(s);
+    if (hipGetLastError() != hipSuccess) { (void)hipStreamSynchronize(s); return HB_ERR_HIP; }
+    std::vector<hb_cblosc_sel_job> jobs;
+    std::vector<uint32_t> chunks;
+    cbas_jobs(nchunks, down.data() + o_first / 4, down.data() + o_cnt / 4, 1, chunk_items, blocksize, jobs, chunks);
+    return cbas_finish(jobs, chunks, M.d_pts, (int64_t)npoints, typesize, s, sel);
+}
+// a selection of no jobs (an empty array, no points)
+static int cbas_create_empty(int typesize, hipStream_t s, hb_cblosc_point_sel **sel) {
+    std::vector<hb_cblosc_sel_job> jobs;
+    std::vector<uint32_t> chunks;
+    return cbas_finish(jobs, chunks, nullptr, 0, typesize, s, sel);
+}
+extern "C" {
+int hb_cblosc_point_sel_create(int njobs, const hb_cblosc_sel_job *jobs, const hb_cblosc_point *points, int64_t npoints, int typesize, int device,
+                               hb_cblosc_point_sel **sel) {
+    if (sel) *sel = nullptr;
+    if (cbsel_call_refused(njobs, jobs, points, npoints, typesize, sel)) return HB_ERR_BAD_ARG;
+    if (const int rc = hb_select_device(device)) return rc;
+    hb_cblosc_point_sel *S = nullptr;
+    if (const int rc = cbsel_new(njobs, jobs, npoints, typesize, &S)) return rc;
+    try {
+        std::vector<CbpPoint> tab;
+        cbsel_build_host(S->P, points, tab);
+        cbsel_known(S->P, S->W);
+        if (!tab.empty() && hipMemcpy(S->d_tab, tab.data(), tab.size() * sizeof(CbpPoint), hipMemcpyHostToDevice) != hipSuccess) { cbsel_free(S); return HB_ERR_HIP; }
+    } catch (const std::bad_alloc &) { cbsel_free(S); return HB_ERR_BAD_ARG; }
+    *sel = S;
+    return HB_OK;
+}
+
+int hb_cblosc_point_sel_create_device(int njobs, const hb_cblosc_sel_job *jobs, const hb_cblosc_point *d_points, int64_t npoints, int typesize, void *stream,
+                                      hb_cblosc_point_sel **sel) {
+    if (sel) *sel = nullptr;
+    if (cbsel_call_refused(njobs, jobs, d_points, npoints, typesize, sel) || ((uintptr_t)d_points & 15u)) return HB_ERR_BAD_ARG;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    return cbsel_create_from_device(njobs, jobs, d_points, npoints, typesize, (hipStream_t)stream, sel);
+}
+
+int hb_cblosc_point_sel_create_mask_device(const hb_cblosc_sel_array *a, const void *d_mask, int typesize, void *stream, hb_cblosc_point_sel **sel) {
+    if (sel) *sel = nullptr;
+    CbasGeom g;
+    int64_t chunk_items;
+    bool empty;
+    const int refused = cbas_refusal(a, typesize, 0, sel, g, chunk_items, empty);
+    if (refused == HB_ERR_BAD_ARG || (!empty && !d_mask)) return HB_ERR_BAD_ARG;      // (every HB_ERR_BAD_ARG comes before HB_ERR_DATA_TOO_LARGE)
+    if (refused) return refused;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    try {
+        if (empty) return cbas_create_empty(typesize, (hipStream_t)stream, sel);
+        return cbas_create_mask(g, chunk_items, a->blocksize, (const uint8_t *)d_mask, typesize, (hipStream_t)stream, sel);
+    } catch (const std::bad_alloc &) { (void)hipStreamSynchronize((hipStream_t)stream); return HB_ERR_BAD_ARG; }
+}
+
+int hb_cblosc_point_sel_create_coords_device(const hb_cblosc_sel_array *a, const int64_t *const *d_coords, int64_t npoints, int typesize, void *stream,
+                                             hb_cblosc_point_sel **sel) {
+    if (sel) *sel = nullptr;
+    CbasGeom g;
+    int64_t chunk_items;
+    bool empty;
+    const int refused = cbas_refusal(a, typesize, npoints, sel, g, chunk_items, empty);
+    if (refused == HB_ERR_BAD_ARG || cbas_coords_refused(a, d_coords, npoints)) return HB_ERR_BAD_ARG;
+    if (refused) return refused;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    try {
+        if (npoints == 0) return cbas_create_empty(typesize, (hipStream_t)stream, sel);
+        if (empty) return HB_ERR_BAD_ARG;                                 // (a point of an array without items lies outside it)
+        return cbas_create_coords(g, chunk_items, a->blocksize, d_coords, a->ndim, (uint32_t)npoints, typesize, (hipStream_t)stream, sel);
+    } catch (const std::bad_alloc &) { (void)hipStreamSynchronize((hipStream_t)stream); return HB_ERR_BAD_ARG; }
+}
+
+int hb_cblosc_point_sel_njobs(const hb_cblosc_point_sel *sel) { return sel ? (int)sel->P.jobs.size() : HB_ERR_BAD_ARG; }
+int64_t hb_cblosc_point_sel_npoints(const hb_cblosc_point_sel *sel) { return sel ? (int64_t)sel->P.npts : (int64_t)HB_ERR_BAD_ARG; }
+int hb_cblosc_point_sel_job_chunks(const hb_cblosc_point_sel *sel, uint32_t *chunk, int n) {
+    if (!sel || !chunk || !sel->from_array || n < 0 || (size_t)n != sel->P.jobs.size()) return HB_ERR_BAD_ARG;
+    for (size_t j = 0; j < sel->chunks.size(); j++) chunk[j] = sel->chunks[j];
+    return HB_OK;
+}
+// the job's table entries come down as they lie and become {item, out} again (an entry holds both times the typesize)
+int hb_cblosc_point_sel_job_points(const hb_cblosc_point_sel *sel, int job, hb_cblosc_point *points, int64_t n) {
+    if (!sel || job < 0 || (size_t)job >= sel->P.jobs.size()) return HB_ERR_BAD_ARG;
+    const CbselEntry &E = sel->P.jobs[(size_t)job];
+    if (E.status || n != E.count || (n > 0 && !points)) return HB_ERR_BAD_ARG;
+    if (n == 0) return HB_OK;
+    const int dev = sel->device;
+    int cur = -1, rc = HB_OK;
+    if (hipGetDevice(&cur) != hipSuccess || (cur != dev && hipSetDevice(dev) != hipSuccess)) return HB_ERR_HIP;
+    static_assert(sizeof(hb_cblosc_point) == sizeof(CbpPoint), "the entries come down into the caller's points");
+    if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(points, sel->d_tab + E.pt0, (size_t)n * sizeof(CbpPoint), hipMemcpyDeviceToHost) != hipSuccess) rc = HB_ERR_HIP;
+    if (cur != dev) (void)hipSetDevice(cur);
+    if (rc) return rc;
+    const uint64_t ts = (uint64_t)sel->P.typesize;
+    for (int64_t p = 0; p < n; p++) {
+        CbpPoint e;
+        memcpy(&e, points + p, sizeof e);
+        points[p] = hb_cblosc_point{(int64_t)(e.off / ts), (int64_t)(e.out / ts)};
+    }
     return HB_OK;
 }
 

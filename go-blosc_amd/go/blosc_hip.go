@@ -2788,6 +2788,103 @@ func NewPointSelectionFromDevice(jobs []SelJob, dPoints uintptr, npoints int64, 
 	return &PointSelection{s, len(jobs), typeSize}, nil
 }
 
+// selArray is hb_cblosc_sel_array of an array of arrayShape items in chunks of chunkShape items (1 to 4 entries each, the same number).
+func selArray(arrayShape, chunkShape []int64, blockSize uint32) (C.hb_cblosc_sel_array, error) {
+	var a C.hb_cblosc_sel_array
+	nd := len(arrayShape)
+	if nd < 1 || nd > 4 || len(chunkShape) != nd {
+		return a, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	a.ndim, a.blocksize = C.int32_t(nd), C.uint32_t(blockSize)
+	for k := 0; k < nd; k++ {
+		a.array_shape[k], a.chunk_shape[k] = C.int64_t(arrayShape[k]), C.int64_t(chunkShape[k])
+	}
+	return a, nil
+}
+
+// NewPointSelectionFromDeviceMask builds the selection of `z[mask]` from a mask on the current device
+// (hb_cblosc_point_sel_create_mask_device): one byte per item of the whole array, C order, any alignment; a byte that is not 0 selects its
+// item.  It is the selection SelJobs + NewPointSelection give for the mask's true entries, bucketed on the device; JobChunks are its chunks.
+// `stream` is synchronised before it returns: the mask may go then.
+func NewPointSelectionFromDeviceMask(arrayShape, chunkShape []int64, dMask uintptr, typeSize int, blockSize uint32, stream uintptr) (*PointSelection, error) {
+	a, err := selArray(arrayShape, chunkShape, blockSize)
+	if err != nil {
+		return nil, err
+	}
+	var s *C.hb_cblosc_point_sel
+	if rc := C.hb_cblosc_point_sel_create_mask_device(&a, unsafe.Pointer(dMask), C.int(typeSize), unsafe.Pointer(stream), &s); rc != C.HB_OK {
+		return nil, hbError(C.int64_t(rc))
+	}
+	return &PointSelection{s, int(C.hb_cblosc_point_sel_njobs(s)), typeSize}, nil
+}
+
+// NewPointSelectionFromDeviceCoords builds the selection of `z.vindex[coords]` from coordinates on the current device
+// (hb_cblosc_point_sel_create_coords_device): dCoords[k] is the device address of npoints int64 values, 8-byte aligned; point i is
+// (dCoords[0][i], ...) and its Out is i.  A coordinate outside the array is an error (negative indices are not wrapped).
+func NewPointSelectionFromDeviceCoords(arrayShape, chunkShape []int64, dCoords []uintptr, npoints int64, typeSize int, blockSize uint32, stream uintptr) (*PointSelection, error) {
+	a, err := selArray(arrayShape, chunkShape, blockSize)
+	if err != nil {
+		return nil, err
+	}
+	if len(dCoords) != len(arrayShape) {
+		return nil, hbError(C.int64_t(C.HB_ERR_BAD_ARG))
+	}
+	ptrs := (*[4]*C.int64_t)(C.calloc(4, C.size_t(unsafe.Sizeof(uintptr(0)))))
+	defer C.free(unsafe.Pointer(ptrs))
+	for k, p := range dCoords {
+		ptrs[k] = (*C.int64_t)(unsafe.Pointer(p))
+	}
+	var s *C.hb_cblosc_point_sel
+	if rc := C.hb_cblosc_point_sel_create_coords_device(&a, &ptrs[0], C.int64_t(npoints), C.int(typeSize), unsafe.Pointer(stream), &s); rc != C.HB_OK {
+		return nil, hbError(C.int64_t(rc))
+	}
+	return &PointSelection{s, int(C.hb_cblosc_point_sel_njobs(s)), typeSize}, nil
+}
+
+// JobChunks is the chunk (C order of the grid) of every job of a selection built from a device mask or device coordinates: the job's entry of
+// jobFrame for a read, the chunk whose frame it replaces for an update.
+func (p *PointSelection) JobChunks() ([]uint32, error) {
+	n := p.njobs
+	if n == 0 {
+		n = 1
+	}
+	buf := (*[1 << 28]C.uint32_t)(C.calloc(C.size_t(n), 4))[:n:n]
+	defer C.free(unsafe.Pointer(&buf[0]))
+	if rc := C.hb_cblosc_point_sel_job_chunks(p.sel, &buf[0], C.int(p.njobs)); rc != C.HB_OK {
+		return nil, hbError(C.int64_t(rc))
+	}
+	out := make([]uint32, p.njobs)
+	for k := range out {
+		out[k] = uint32(buf[k])
+	}
+	return out, nil
+}
+
+// JobPoints copies the table entries of one job from the device, as {item, out} in the table's order: for tests and debugging.
+func (p *PointSelection) JobPoints(job int) ([][2]int64, error) {
+	var info C.hb_cblosc_sel_info
+	if rc := C.hb_cblosc_point_sel_info(p.sel, C.int(job), &info); rc != C.HB_OK {
+		return nil, hbError(C.int64_t(rc))
+	}
+	n := int(info.count)
+	if n == 0 {
+		return nil, nil
+	}
+	buf := unsafe.Slice((*C.hb_cblosc_point)(C.calloc(C.size_t(n), 16)), n)
+	defer C.free(unsafe.Pointer(&buf[0]))
+	if rc := C.hb_cblosc_point_sel_job_points(p.sel, C.int(job), &buf[0], C.int64_t(n)); rc != C.HB_OK {
+		return nil, hbError(C.int64_t(rc))
+	}
+	out := make([][2]int64, n)
+	for k := range out {
+		out[k] = [2]int64{int64(buf[k].item), int64(buf[k].out)}
+	}
+	return out, nil
+}
+
+// NPoints is the number of entries of the selection's table.
+func (p *PointSelection) NPoints() int64 { return int64(C.hb_cblosc_point_sel_npoints(p.sel)) }
+
 // Close synchronises the selection's device and frees its table.
 func (p *PointSelection) Close() error {
 	s := p.sel

@@ -115,6 +115,8 @@ EXPORTS = [
     "hb_cblosc_update_points_batch_workspace", "hb_cblosc_update_points_batch_device", "hb_cblosc_update_points_batch",
     "hb_cblosc_point_sel_create", "hb_cblosc_point_sel_create_device", "hb_cblosc_point_sel_destroy", "hb_cblosc_point_sel_info", "hb_cblosc_point_sel_device_bytes",
     "hb_cblosc_getpoints_sel_workspace", "hb_cblosc_getpoints_sel_device", "hb_cblosc_update_points_sel_workspace", "hb_cblosc_update_points_sel_device",
+    "hb_cblosc_point_sel_create_mask_device", "hb_cblosc_point_sel_create_coords_device", "hb_cblosc_point_sel_njobs", "hb_cblosc_point_sel_npoints",
+    "hb_cblosc_point_sel_job_chunks", "hb_cblosc_point_sel_job_points",
     "hb_cblosc_accept_codecs",
     "hb_queue_create", "hb_queue_create_ex", "hb_queue_destroy", "hb_queue_compress", "hb_queue_decompress", "hb_queue_wait",
 ]
@@ -284,6 +286,21 @@ def sel_job(chunk_items, blocksize, first, count):
     return hb_cblosc_sel_job(int(chunk_items), int(blocksize), 0, int(first), int(count))
 
 
+class hb_cblosc_sel_array(ctypes.Structure):
+    """include/hipblosc.h hb_cblosc_sel_array: the whole array a device mask or device coordinates select from, and how it is chunked"""
+    _fields_ = [("ndim", ctypes.c_int32), ("blocksize", ctypes.c_uint32), ("array_shape", ctypes.c_int64 * 4), ("chunk_shape", ctypes.c_int64 * 4)]
+
+
+def sel_array(array_shape, chunk_shape, blocksize=0):
+    """hb_cblosc_sel_array of an array of `array_shape` items in chunks of `chunk_shape` items whose frames have `blocksize`-byte blocks (0:
+    updates or memcpyed frames only)"""
+    nd = len(array_shape)
+    if nd != len(chunk_shape) or not 1 <= nd <= 4:
+        raise ValueError("array_shape and chunk_shape need the same number of entries, 1 to 4")
+    pad = [0] * (4 - nd)
+    return hb_cblosc_sel_array(nd, int(blocksize), (ctypes.c_int64 * 4)(*[int(v) for v in array_shape], *pad), (ctypes.c_int64 * 4)(*[int(v) for v in chunk_shape], *pad))
+
+
 _lib = None
 
 
@@ -391,6 +408,12 @@ def lib():
             "hb_cblosc_getpoints_sel_device": (i32, [vp, i32, vp, vp, vp, vp, vp, vp, vp, sz, vp, vp]),
             "hb_cblosc_update_points_sel_workspace": (sz, [vp, vp, vp, i32, i32]),
             "hb_cblosc_update_points_sel_device": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, sz, vp, vp]),
+            "hb_cblosc_point_sel_create_mask_device": (i32, [vp, vp, i32, vp, vp]),
+            "hb_cblosc_point_sel_create_coords_device": (i32, [vp, vp, i64, i32, vp, vp]),
+            "hb_cblosc_point_sel_njobs": (i32, [vp]),
+            "hb_cblosc_point_sel_npoints": (i64, [vp]),
+            "hb_cblosc_point_sel_job_chunks": (i32, [vp, vp, i32]),
+            "hb_cblosc_point_sel_job_points": (i32, [vp, i32, vp, i64]),
             "hb_cblosc_accept_codecs": (i32, [ctypes.c_uint]),
         }
         for name, (res, args) in sig.items():
@@ -1686,7 +1709,10 @@ class PointSelection:
     it; close() (or leaving the `with` block) synchronises its device first."""
 
     def __init__(self, handle, njobs, typesize):
-        self._h, self.njobs, self.typesize = handle, njobs, typesize
+        self._h, self.typesize = handle, typesize
+        self.njobs = lib().hb_cblosc_point_sel_njobs(handle)
+        assert njobs is None or njobs == self.njobs
+        self.npoints = lib().hb_cblosc_point_sel_npoints(handle)           # the entries of its table
 
     @staticmethod
     def _job_array(jobs):
@@ -1706,6 +1732,38 @@ class PointSelection:
         h = ctypes.c_void_p()
         _check(lib().hb_cblosc_point_sel_create_device(len(jobs), cls._job_array(jobs), None if not ptr else int(ptr), int(npoints), int(typesize), stream, ctypes.byref(h)))
         return cls(h, len(jobs), int(typesize))
+
+    @classmethod
+    def from_device_mask(cls, array_shape, chunk_shape, ptr, typesize, blocksize=0, stream=None):
+        """`z[mask]` for a mask on the current device: ptr is the device address of one byte per item of the whole array, C order, any
+        alignment; a byte that is not 0 selects its item.  The selection sel_jobs + from_points give for np.nonzero(mask), bucketed on the
+        device; job_chunks() are its chunks.  Synchronises `stream`: the mask may go when this returns."""
+        a, h = sel_array(array_shape, chunk_shape, blocksize), ctypes.c_void_p()
+        _check(lib().hb_cblosc_point_sel_create_mask_device(ctypes.byref(a), None if not ptr else int(ptr), int(typesize), stream, ctypes.byref(h)))
+        return cls(h, None, int(typesize))
+
+    @classmethod
+    def from_device_coords(cls, array_shape, chunk_shape, ptrs, npoints, typesize, blocksize=0, stream=None):
+        """`z.vindex[coords]` for coordinates on the current device: ptrs are ndim device addresses of npoints int64 values each, 8-byte
+        aligned; point i is (ptrs[0][i], ...), its `out` is i.  A coordinate outside the array raises (negative indices are not wrapped)."""
+        a, h = sel_array(array_shape, chunk_shape, blocksize), ctypes.c_void_p()
+        pa = (ctypes.c_void_p * 4)(*[None if not p else int(p) for p in ptrs])
+        _check(lib().hb_cblosc_point_sel_create_coords_device(ctypes.byref(a), pa, int(npoints), int(typesize), stream, ctypes.byref(h)))
+        return cls(h, None, int(typesize))
+
+    def job_chunks(self):
+        """the chunk number (C order of the grid) of every job of a selection built from a mask or coordinates of a whole array: the job's
+        entry of job_frame for a read, the chunk whose frame it replaces for an update"""
+        out = (ctypes.c_uint32 * max(self.njobs, 1))()
+        _check(lib().hb_cblosc_point_sel_job_chunks(self._h, out, self.njobs))
+        return list(out[:self.njobs])
+
+    def job_points(self, job):
+        """the table entries of one job as (item, out) pairs, in the table's order, copied from the device: for tests and debugging"""
+        n = self.info(job).count
+        pts = (hb_cblosc_point * max(n, 1))()
+        _check(lib().hb_cblosc_point_sel_job_points(self._h, int(job), pts, n))
+        return [(p.item, p.out) for p in pts[:n]]
 
     def info(self, job):
         """hb_cblosc_sel_info of one job: status, unique, count, need_items, touched_blocks"""

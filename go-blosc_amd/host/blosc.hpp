@@ -613,7 +613,8 @@ inline std::map<int64_t, Bytes> CBloscUpdateMask(const std::vector<Bytes> &frame
     }
     return CBloscUpdateVIndex(frames, array_shape, chunk_shape, coords, data, typeSize, shuffle, fill, device);
 }
-// ---- a prepared point selection (include/hipblosc.h hb_cblosc_point_sel): built once from host points or from device points, it serves
+// ---- a prepared point selection (include/hipblosc.h hb_cblosc_point_sel): built once from host points, from device points, or from a device
+// mask or device coordinate arrays of the whole array, it serves
 // hb_cblosc_getpoints_sel_device and hb_cblosc_update_points_sel_device for every set of frames with the chunk geometry of its jobs.  RAII: the
 // destructor synchronises the selection's device and frees its table, so the object must outlive the work enqueued with it.  Device pointers
 // are plain pointers; every call is asynchronous on `stream` and returns the library's code (HB_OK, or what the call as a whole refuses).
@@ -648,8 +649,52 @@ public:
         check(hb_cblosc_point_sel_create_device((int)jobs.size(), jobs.empty() ? &none : jobs.data(), d_points, npoints, typeSize, stream, &s));
         return PointSelection(s, (int)jobs.size(), typeSize);
     }
+    // hb_cblosc_sel_array of an array of array_shape items in chunks of chunk_shape items (1 to 4 entries each, the same number)
+    static hb_cblosc_sel_array SelArray(const std::vector<int64_t> &array_shape, const std::vector<int64_t> &chunk_shape, uint32_t blocksize) {
+        const size_t nd = array_shape.size();
+        if (nd < 1 || nd > 4 || chunk_shape.size() != nd) check(HB_ERR_BAD_ARG);
+        hb_cblosc_sel_array a{};
+        a.ndim = (int32_t)nd; a.blocksize = blocksize;
+        for (size_t d = 0; d < nd; d++) { a.array_shape[d] = array_shape[d]; a.chunk_shape[d] = chunk_shape[d]; }
+        return a;
+    }
+    // `z[mask]` for a mask on the current device: one byte per item of the whole array, C order, any alignment.  The selection SelJobs +
+    // FromPoints give for the mask's true entries, bucketed on the device; JobChunks() are its chunks.  `stream` is synchronised before this
+    // returns: the mask may go then.
+    static PointSelection FromDeviceMask(const std::vector<int64_t> &array_shape, const std::vector<int64_t> &chunk_shape, const void *d_mask, int typeSize, uint32_t blocksize = 0,
+                                         void *stream = nullptr) {
+        const hb_cblosc_sel_array a = SelArray(array_shape, chunk_shape, blocksize);
+        hb_cblosc_point_sel *s = nullptr;
+        check(hb_cblosc_point_sel_create_mask_device(&a, d_mask, typeSize, stream, &s));
+        return PointSelection(s, hb_cblosc_point_sel_njobs(s), typeSize);
+    }
+    // `z.vindex[coords]` for coordinates on the current device: d_coords[k] points to npoints int64 values, 8-byte aligned; point i's `out` is i
+    static PointSelection FromDeviceCoords(const std::vector<int64_t> &array_shape, const std::vector<int64_t> &chunk_shape, const std::vector<const int64_t *> &d_coords,
+                                           int64_t npoints, int typeSize, uint32_t blocksize = 0, void *stream = nullptr) {
+        const hb_cblosc_sel_array a = SelArray(array_shape, chunk_shape, blocksize);
+        if (d_coords.size() != array_shape.size()) check(HB_ERR_BAD_ARG);
+        hb_cblosc_point_sel *s = nullptr;
+        check(hb_cblosc_point_sel_create_coords_device(&a, d_coords.data(), npoints, typeSize, stream, &s));
+        return PointSelection(s, hb_cblosc_point_sel_njobs(s), typeSize);
+    }
     explicit operator bool() const { return sel_ != nullptr; }
     const hb_cblosc_point_sel *get() const { return sel_; }
+    // the chunk (C order of the grid) of every job of a selection built from a mask or coordinates: job_frame for a read, the chunk to swap for an update
+    std::vector<uint32_t> JobChunks() const {
+        std::vector<uint32_t> c((size_t)(njobs_ > 0 ? njobs_ : 1));
+        check(hb_cblosc_point_sel_job_chunks(sel_, c.data(), njobs_));
+        c.resize((size_t)njobs_);
+        return c;
+    }
+    int64_t NPoints() const { return sel_ ? hb_cblosc_point_sel_npoints(sel_) : 0; }      // the entries of its table
+    // the table entries of one job as {item, out}, in the table's order, copied from the device: for tests and debugging
+    std::vector<hb_cblosc_point> JobPoints(int job) const {
+        const int64_t n = Info(job).count;
+        std::vector<hb_cblosc_point> p((size_t)(n > 0 ? n : 1));
+        check(hb_cblosc_point_sel_job_points(sel_, job, p.data(), n));
+        p.resize((size_t)n);
+        return p;
+    }
     int Jobs() const { return njobs_; }
     int TypeSize() const { return typeSize_; }
     hb_cblosc_sel_info Info(int job) const {

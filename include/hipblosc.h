@@ -909,8 +909,10 @@ int     hb_cblosc_update_points_batch(int njobs, const hb_cblosc_upd_point_job *
  *      points[first .. first + count), hb_cblosc_point records, shared or overlapping ranges allowed.  `out` is the point's position: the
  *      destination item of a read, the source item of an update (hb_cblosc_upd_point's `src`).
  *      Building: hb_cblosc_point_sel_create takes HOST points and uploads the table once; hb_cblosc_point_sel_create_device takes DEVICE points
- *      (the output of a device nonzero, a top-k, a sampler; 16-byte aligned) on the current device, builds table, marks and checks with one
- *      kernel per group of jobs, and synchronises `stream` before it returns: the caller's points are not needed after either create.  The call as a whole answers HB_ERR_BAD_ARG, before the device is looked for
+ *      -- CHUNK-LOCAL records {item, out}, already grouped into one range per job, 16-byte aligned; array-level input (a device mask, the
+ *      coordinates of a device nonzero, a top-k, a sampler) goes to hb_cblosc_point_sel_create_mask_device / _coords_device below -- on the
+ *      current device, builds table, marks and checks with one kernel per group of jobs, and synchronises `stream` before it returns: the
+ *      caller's points are not needed after either create.  The call as a whole answers HB_ERR_BAD_ARG, before the device is looked for
  *      (HB_ERR_NO_DEVICE comes after), for: njobs < 0, jobs == NULL, sel == NULL, typesize outside 1..255, npoints < 0, points == NULL while
  *      some job has count > 0, a reserved field that is not 0, more than HB_CBLOSC_BATCH_MAX_WORK points over all jobs.  *sel is NULL unless
  *      HB_OK is returned.  A job's status is kept in the selection and answered at every use: HB_ERR_BAD_ARG for first < 0, count < 0,
@@ -966,6 +968,45 @@ size_t  hb_cblosc_update_points_sel_workspace(const hb_cblosc_point_sel *sel, co
 int     hb_cblosc_update_points_sel_device(const hb_cblosc_point_sel *sel, const hb_cblosc_header *old_hdrs, const void *const *d_old, const size_t *old_n,
                                            const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill, int shuffle, int typesize,
                                            void *d_work, size_t work_bytes, hb_result *d_results, void *stream);
+
+/* ---- selections from device masks and device coordinate arrays of the WHOLE array: the same hb_cblosc_point_sel that the mirrors' sel_jobs
+ *      followed by hb_cblosc_point_sel_create gives, with everything proportional to the points done on the device.  The array has `ndim`
+ *      dimensions of array_shape items in chunks of chunk_shape items; the grid is ceil(array_shape[k] / chunk_shape[k]) per dimension, chunks
+ *      are numbered in C order of the grid, every job's chunk_items is the product of chunk_shape (edge chunks are full chunks, as the writers
+ *      make them) and `item` is ravelled over chunk_shape.  There is one job per chunk that holds a point, in increasing chunk number;
+ *      hb_cblosc_point_sel_job_chunks gives the chunk number of every job: its entry of job_frame for a read, the chunk to swap for an update.
+ *      Mask form: d_mask holds one byte per array item in C order over array_shape, contiguous, at any alignment; a byte that is not 0 selects
+ *      its item; `out` is the item's C-order rank among the selected ones (np.nonzero's order), and a job's table entries are in increasing
+ *      item.  Coordinate form: d_coords is a HOST array of ndim DEVICE pointers to npoints int64 values each, 8-byte aligned; point i is
+ *      (d_coords[0][i], ...), its `out` is i; the order of a job's table entries is not specified; a repeated point clears `unique`.
+ *      HB_ERR_BAD_ARG, before the device is looked for: a == NULL, sel == NULL, ndim outside 1 .. HB_CBLOSC_BOX_MAX_NDIM, chunk_shape[k] < 1 or
+ *      array_shape[k] < 0 at k < ndim, an entry that is not 0 at k >= ndim, typesize outside 1..255, d_mask == NULL with a non-empty array,
+ *      npoints < 0, d_coords == NULL or a NULL or misaligned entry of it with npoints > 0, more than HB_CBLOSC_BATCH_MAX_WORK array items,
+ *      chunk rows (the runs of one chunk's items along the last dimension), chunks or points (all products checked without overflow).  Then
+ *      HB_ERR_DATA_TOO_LARGE for prod chunk_shape * typesize beyond the box writes' limit, then HB_ERR_NO_DEVICE.  Found on the device: a
+ *      coordinate < 0 or >= array_shape[k] (negative indices are not wrapped) answers HB_ERR_BAD_ARG.  *sel is NULL unless HB_OK is returned.
+ *      An empty array, a mask without a selected item and npoints == 0 give a selection with 0 jobs.  Both calls run on the current device,
+ *      synchronise `stream` before they return -- the caller's mask or coordinates may be freed right after -- and free their temporary device
+ *      memory (per chunk row 12 bytes, per chunk 8 to 12, per point 16 to 32) before they return.  A device allocation that fails answers
+ *      HB_ERR_HIP; a host allocation that fails answers HB_ERR_BAD_ARG, as in hb_cblosc_point_sel_create.
+ *      hb_cblosc_point_sel_njobs and _npoints answer for any selection (HB_ERR_BAD_ARG for NULL); _job_chunks answers HB_ERR_BAD_ARG for
+ *      n != njobs, a NULL argument, or a selection that was not built from an array.
+ *      hb_cblosc_point_sel_job_points copies the table entries of one job of any selection to the host, as {item, out} in the table's order: a
+ *      look at what a builder made, for tests and for debugging, not a hot path (it drains the selection's device first).  HB_ERR_BAD_ARG: a
+ *      NULL selection, a job outside 0 .. njobs - 1, a job with a stored status, n != the job's count, NULL points with n > 0. ---- */
+typedef struct hb_cblosc_sel_array {
+    int32_t  ndim;             /* 1 .. HB_CBLOSC_BOX_MAX_NDIM */
+    uint32_t blocksize;        /* hb_cblosc_sel_job.blocksize of every job: header blocksize of the frames to READ; 0: updates / memcpyed only */
+    int64_t  array_shape[4];   /* items of the whole array, >= 0 */
+    int64_t  chunk_shape[4];   /* items of a chunk, >= 1 */
+} hb_cblosc_sel_array;         /* entries at k >= ndim are 0 */
+int     hb_cblosc_point_sel_create_mask_device(const hb_cblosc_sel_array *a, const void *d_mask, int typesize, void *stream, hb_cblosc_point_sel **sel);
+int     hb_cblosc_point_sel_create_coords_device(const hb_cblosc_sel_array *a, const int64_t *const *d_coords, int64_t npoints, int typesize, void *stream,
+                                                 hb_cblosc_point_sel **sel);
+int     hb_cblosc_point_sel_njobs(const hb_cblosc_point_sel *sel);
+int64_t hb_cblosc_point_sel_npoints(const hb_cblosc_point_sel *sel);    /* the table's entries */
+int     hb_cblosc_point_sel_job_chunks(const hb_cblosc_point_sel *sel, uint32_t *chunk, int n);
+int     hb_cblosc_point_sel_job_points(const hb_cblosc_point_sel *sel, int job, hb_cblosc_point *points, int64_t n);
 
 #ifdef __cplusplus
 }
