@@ -580,6 +580,7 @@ int64_t hb_cblosc_getitem(const void *frame, size_t n, int64_t start, int64_t ni
 }
 
 int64_t hb_cblosc_compress(const void *src, size_t n, void *dst, size_t cap, int shuffle, int typesize, int device) {
+    CbPolicyPin pin;                                                       // (hb_cblosc_set_compressor: one policy for the device call and for every one-frame call behind it)
     if ((!src && n) || !dst) return HB_ERR_BAD_ARG;
     if (typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
     int rc = select_device(device);

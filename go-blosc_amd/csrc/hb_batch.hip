@@ -874,6 +874,7 @@ static int cbe_host_download(const std::vector<int> &idx, const std::vector<void
 // hb_cblosc_compress, so that rc[k] is its answer in every case.
 int hb_cblosc_compress_frames_batch(int nframes, const void *const *src, const size_t *n, void *const *dst, const size_t *cap, int64_t *rc,
                                     int shuffle, int typesize, int device) {
+    CbPolicyPin pin;                                                       // (hb_cblosc_set_compressor: one policy for the device call and for every one-frame call behind it)
     if (nframes < 0) return HB_ERR_BAD_ARG;
     if (nframes == 0) return HB_OK;
     if (!src || !n || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
@@ -911,6 +912,7 @@ int hb_cblosc_compress_frames_batch(int nframes, const void *const *src, const s
 // device, is answered by hb_cblosc_compress for the chunk assembled on the host.
 static int cbxe_host_call(int nframes, const hb_cblosc_src_box *boxes, const void *const *src, void *const *dst, const size_t *cap, int64_t *rc, const void *fill,
                           int shuffle, int typesize, int device) {
+    CbPolicyPin pin;                                                       // (hb_cblosc_set_compressor: one policy for the device call and for every one-frame call behind it)
     if (nframes < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
     if (nframes == 0) return HB_OK;
     if (!boxes || !src || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
@@ -967,6 +969,7 @@ int hb_cblosc_compress_boxes_batch(int nframes, const hb_cblosc_src_box *boxes, 
 // status 0 on the device, is answered on the host: hb_cblosc_decompress of the old frame (or the fill), the naive overlay, hb_cblosc_compress.
 static int cbxu_host_call(int njobs, const hb_cblosc_upd_box *boxes, const void *const *old, const size_t *old_n, const void *const *src, void *const *dst,
                           const size_t *cap, int64_t *rc, const void *fill, int shuffle, int typesize, int device) {
+    CbPolicyPin pin;                                                       // (hb_cblosc_set_compressor: one policy for the device call and for every one-frame call behind it)
     if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
     if (njobs == 0) return HB_OK;
     if (!boxes || !old || !old_n || !src || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
@@ -1052,6 +1055,7 @@ int hb_cblosc_update_boxes_batch(int njobs, const hb_cblosc_upd_box *boxes, cons
 // frame (or the fill), the naive loops, hb_cblosc_compress.
 static int cbiu_host_call(int njobs, const hb_cblosc_upd_index *jobs, const int64_t *index, int64_t nindex, const void *const *old, const size_t *old_n,
                           const void *const *src, void *const *dst, const size_t *cap, int64_t *rc, const void *fill, int shuffle, int typesize, int device) {
+    CbPolicyPin pin;                                                       // (hb_cblosc_set_compressor: one policy for the device call and for every one-frame call behind it)
     if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
     if (njobs == 0) return HB_OK;
     if (!jobs || !old || !old_n || !src || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
@@ -1137,6 +1141,7 @@ int hb_cblosc_update_index_batch(int njobs, const hb_cblosc_upd_index *jobs, con
 // status 0 on the device, is answered on the host: hb_cblosc_decompress of the old frame (or the fill), the naive loop, hb_cblosc_compress.
 static int cbpu_host_call(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints, const void *const *old, const size_t *old_n,
                           const void *const *src, void *const *dst, const size_t *cap, int64_t *rc, const void *fill, int shuffle, int typesize, int device) {
+    CbPolicyPin pin;                                                       // (hb_cblosc_set_compressor: one policy for the device call and for every one-frame call behind it)
     if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
     if (njobs == 0) return HB_OK;
     if (!jobs || !old || !old_n || !src || !dst || !cap || !rc) return HB_ERR_BAD_ARG;

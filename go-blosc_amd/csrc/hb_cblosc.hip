@@ -1015,6 +1015,7 @@ __global__ __launch_bounds__(64) void k_cbe_finish(const CbEncPlan *plan, const 
 __device__ __forceinline__ void cbe_memcpy_header(uint8_t *frame, uint32_t nbytes, uint32_t ts, uint32_t flags, hb_result *result) {
     const uint32_t cbytes = 16u + nbytes;
     uint32_t bs = nbytes - nbytes % ts; if (bs == 0u) bs = nbytes ? 1u : 0u;
+    if (bs > (1u << 29)) bs = (1u << 29) - (1u << 29) % ts;               // (level 0 writes this frame at any size: c-blosc refuses a blocksize above (INT_MAX - 16) / 3)
     frame[0] = 2; frame[1] = 1; frame[2] = (uint8_t)flags; frame[3] = (uint8_t)ts;
     for (int q = 0; q < 4; q++) { frame[4 + q] = (uint8_t)(nbytes >> (8 * q)); frame[8 + q] = (uint8_t)(bs >> (8 * q)); frame[12 + q] = (uint8_t)(cbytes >> (8 * q)); }
     result->status = HB_OK; result->bytes = cbytes; result->total_bytes = cbytes; result->flags = 0; result->reserved = 0;
@@ -1383,11 +1384,11 @@ __global__ __launch_bounds__(256) void k_cbas_coord_place(const CbasRec *__restr
     cbas_place_thread(rec, first, pts, npoints, blockIdx.x * 256u + threadIdx.x, io);
 }
 
-void hb_launch_match_selfcontained(const uint8_t *src, size_t n, void *desc, uint8_t *records, uint32_t nchunks, int accel, hipStream_t s);   // hb_lz4_enc.hip
-bool hb_launch_match_fused_selfcontained(const uint8_t *src, int typesize, void *desc, uint8_t *records, uint32_t nblk, int accel, hipStream_t s);
-void hb_launch_match_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, void *desc, uint8_t *records, uint32_t total_chunks, int accel, hipStream_t s);
-bool hb_launch_match_fused_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, int typesize, void *desc, uint8_t *records, uint32_t total_items, int accel,
-                                               hipStream_t s);
+void hb_launch_match_selfcontained(const uint8_t *src, size_t n, void *desc, uint8_t *records, uint32_t nchunks, int ways, int accel, hipStream_t s);   // hb_lz4_enc.hip
+bool hb_launch_match_fused_selfcontained(const uint8_t *src, int typesize, void *desc, uint8_t *records, uint32_t nblk, int ways, int accel, hipStream_t s);
+void hb_launch_match_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, void *desc, uint8_t *records, uint32_t total_chunks, int ways, int accel, hipStream_t s);
+bool hb_launch_match_fused_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, int typesize, void *desc, uint8_t *records, uint32_t total_items, int ways,
+                                               int accel, hipStream_t s);
 
 struct CbEncLayout { size_t plan, tiles, desc, records, filtered, total; uint32_t blocksize, nsplit, nblocks, nfull, nchunks, ntiles; };
 static CbEncLayout cbe_layout(size_t n, int shuffle, int typesize) {
@@ -1453,7 +1454,37 @@ static void cb_launch_blocks(const hb_cblosc_header *hdr, const uint8_t *d_frame
 static std::atomic<unsigned> g_cb_accept{CB_ACCEPT_DEFAULT};
 unsigned hb_cblosc_accepted() { return g_cb_accept.load(std::memory_order_relaxed); }
 
+// what the writers below compress with (include/hipblosc.h, hb_cblosc_set_compressor): one word, codec << 8 | clevel.  Every writer entry
+// point reads it once, before anything is sized or launched, and hands it down to its encode site (hb_cblosc_compress_dev, cbe_launch_batch).
+// A host form pins the word it read for its thread while it runs (CbPolicyPin, hb_common.h): the device forms and the one-frame calls it
+// answers the rest with then read that word, whatever another thread sets meanwhile.
+#define CB_POLICY_DEFAULT ((unsigned)HB_LZ4 << 8 | 5u)
+static std::atomic<unsigned> g_cb_policy{CB_POLICY_DEFAULT};
+static thread_local int t_cb_policy_pin = -1;
+unsigned hb_cblosc_policy() { return t_cb_policy_pin >= 0 ? (unsigned)t_cb_policy_pin : g_cb_policy.load(std::memory_order_relaxed); }
+CbPolicyPin::CbPolicyPin() : prev(t_cb_policy_pin) { t_cb_policy_pin = (int)hb_cblosc_policy(); }
+CbPolicyPin::~CbPolicyPin() { t_cb_policy_pin = prev; }
+// the matcher of a policy word: candidates per bucket and skip acceleration (hb_level_policy, the table of the go-blosc-format frames too);
+// level 0: no matcher at all, the frame is memcpyed
+struct CbMatcher { bool store; int ways, accel; };
+static inline CbMatcher cb_matcher(unsigned policy) {
+    CbMatcher m{(policy & 255u) == 0u, 1, 64};
+    if (!m.store) hb_level_policy((int)(policy >> 8), (int)(policy & 255u), m.ways, m.accel);
+    return m;
+}
+
 extern "C" {
+
+int hb_cblosc_set_compressor(int codec, int clevel) {
+    if ((codec != HB_LZ4 && codec != HB_LZ4HC) || clevel < 0 || clevel > 9) return HB_ERR_BAD_ARG;
+    return (int)g_cb_policy.exchange((unsigned)codec << 8 | (unsigned)clevel, std::memory_order_relaxed);
+}
+int hb_cblosc_get_compressor(int *codec, int *clevel) {
+    const unsigned p = g_cb_policy.load(std::memory_order_relaxed);
+    if (codec) *codec = (int)(p >> 8);
+    if (clevel) *clevel = (int)(p & 255u);
+    return HB_OK;
+}
 
 int hb_cblosc_accept_codecs(unsigned mask) {
     if (!cb_accept_valid(mask)) return HB_ERR_BAD_ARG;
@@ -1817,6 +1848,7 @@ size_t hb_cblosc_compress_workspace(size_t n, int shuffle, int typesize) { retur
 // shuffle: 0 none, 1 byte shuffle, 2 bit shuffle (c-blosc's BLOSC_NOSHUFFLE / BLOSC_SHUFFLE / BLOSC_BITSHUFFLE).  Asynchronous on `stream`.
 int hb_cblosc_compress_dev(const void *d_src, size_t n, void *d_frame, size_t cap, int shuffle, int typesize, void *d_work, size_t work_bytes,
                            hb_result *d_result, void *stream) {
+    const CbMatcher M = cb_matcher(hb_cblosc_policy());                   // (read once: one call, one policy)
     if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
     if ((!d_src && n) || !d_frame || !d_work || ((uintptr_t)d_work & 255u) || !d_result) return HB_ERR_BAD_ARG;
     if (typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
@@ -1832,7 +1864,7 @@ int hb_cblosc_compress_dev(const void *d_src, size_t n, void *d_frame, size_t ca
     uint8_t *records = w + L.records, *filtered = w + L.filtered;
     const bool unshuf = shuffle == 1 && typesize > 1, bits = shuffle == 2;
     const uint32_t flags = (unshuf ? CB_FLAG_SHUFFLE : 0u) | (bits ? CB_FLAG_BITSHUFFLE : 0u) | (L.nsplit == 1u ? CB_FLAG_DONTSPLIT : 0u) | (1u << 5);
-    if (n < HB_CHUNK) {
+    if (n < HB_CHUNK || M.store) {                                        // (level 0: blosc_compress's memcpyed frame, at every size)
         if (n) HB_HIP_TRY(hipMemcpyAsync((uint8_t *)d_frame + 16, d_src, n, hipMemcpyDeviceToDevice, s));
         hipLaunchKernelGGL(k_cbe_memcpy_header, dim3(1), dim3(1), 0, s, (uint8_t *)d_frame, (uint32_t)n, (uint32_t)typesize, flags | CB_FLAG_MEMCPY | CB_FLAG_DONTSPLIT, d_result);
         HB_HIP_TRY(hipGetLastError());
@@ -1862,8 +1894,8 @@ int hb_cblosc_compress_dev(const void *d_src, size_t n, void *d_frame, size_t ca
     const uint32_t fused_nblk = fuse ? L.nfull : 0u;
     if (L.nchunks) {
         hb_prof_begin("k_match", s);
-        if (fuse) hb_launch_match_fused_selfcontained((const uint8_t *)d_src, typesize, desc, records, L.nfull, 64, s);
-        else hb_launch_match_selfcontained(fsrc, (size_t)L.nchunks * HB_CHUNK, desc, records, L.nchunks, 64, s);
+        if (fuse) hb_launch_match_fused_selfcontained((const uint8_t *)d_src, typesize, desc, records, L.nfull, M.ways, M.accel, s);
+        else hb_launch_match_selfcontained(fsrc, (size_t)L.nchunks * HB_CHUNK, desc, records, L.nchunks, M.ways, M.accel, s);
         hb_prof_end(s);
         hb_prof_begin("k_cbe_pack", s);
         hipLaunchKernelGGL(k_cbe_tiles, dim3(L.ntiles), dim3(256), 0, s, desc, L.nchunks, L.nsplit, fused_nblk, tiles);
@@ -1877,13 +1909,22 @@ int hb_cblosc_compress_dev(const void *d_src, size_t n, void *d_frame, size_t ca
     return HB_OK;
 }
 // everything of a batched encode behind cbe_prepare: upload, map, filter, matchers, tiles, scan, pack, finish over the workspace `w` that B was
-// laid out for.  hb_cblosc_compress_frames_batch_device and hb_cblosc_compress_boxes_batch_device both end here.
-static int cbe_launch_batch(int nframes, const CbeBatch &B, int shuffle, int typesize, uint8_t *w, hb_result *d_results, hipStream_t s) {
+// laid out for.  Every batched writer ends here, with the policy word its entry point read.  Level 0: every frame that would have gone to a
+// matcher is memcpyed instead, as hb_cblosc_compress_dev writes it -- the frame records change their route on their way up, nothing but the
+// upload and k_cbeb_finish is launched (one wavefront copies a frame: chunk-sized frames), and the layout, made for the matchers, is more
+// than enough.
+static int cbe_launch_batch(int nframes, const CbeBatch &B, int shuffle, int typesize, unsigned policy, uint8_t *w, hb_result *d_results, hipStream_t s) {
     const CbeLayout &L = B.L;
     const size_t nf = (size_t)nframes;
+    const CbMatcher M = cb_matcher(policy);
     // the frame records, the matcher's records, the prefixes and the cleared plans go up in one copy (the buffer is read before the call returns)
     std::vector<uint8_t> up(L.upload, 0);
     memcpy(up.data() + L.frames, B.tab.data(), nf * sizeof(CbeFrame));
+    if (M.store) {
+        CbeFrame *t = (CbeFrame *)(up.data() + L.frames);
+        for (size_t k = 0; k < nf; k++)
+            if (t[k].mode == CBE_PLAIN || t[k].mode == CBE_FUSED) { t[k].mode = CBE_MEMCPY; t[k].flags |= CB_FLAG_MEMCPY | CB_FLAG_DONTSPLIT; }
+    }
     memcpy(up.data() + L.bf, B.bf.data(), nf * sizeof(BatchFrame));
     memcpy(up.data() + L.pre, B.pre.data(), nf * 8);
     memcpy(up.data() + L.plans, B.plans.data(), nf * sizeof(CbEncPlan));
@@ -1897,13 +1938,13 @@ static int cbe_launch_batch(int nframes, const CbeBatch &B, int shuffle, int typ
     uint32_t *d_map = (uint32_t *)(w + L.map), *d_tiles = (uint32_t *)(w + L.tiles);
     CbChunkDesc *d_desc = (CbChunkDesc *)(w + L.desc);
     uint8_t *d_records = w + L.records;
-    const uint32_t plain = (uint32_t)B.plain_chunks, fused = (uint32_t)B.fused_chunks, ntiles = (uint32_t)B.ntiles;
-    if (B.map_chunks) {
+    const uint32_t plain = M.store ? 0u : (uint32_t)B.plain_chunks, fused = M.store ? 0u : (uint32_t)B.fused_chunks, ntiles = M.store ? 0u : (uint32_t)B.ntiles;
+    if (B.map_chunks && !M.store) {
         hb_prof_begin("k_cbeb_map", s);
         hipLaunchKernelGGL(k_cbeb_map, dim3((unsigned)nframes), dim3(64), 0, s, d_frames, d_map);
         hb_prof_end(s);
     }
-    if (B.fblocks) {
+    if (B.fblocks && !M.store) {
         hb_prof_begin("k_cbeb_filter", s);
         if (shuffle == 2) hipLaunchKernelGGL(k_cbeb_filter<true>, dim3((unsigned)B.fblocks), dim3(256), 0, s, d_frames, d_fblk, (uint32_t)nframes, w);
         else hipLaunchKernelGGL(k_cbeb_filter<false>, dim3((unsigned)B.fblocks), dim3(256), 0, s, d_frames, d_fblk, (uint32_t)nframes, w);
@@ -1911,14 +1952,14 @@ static int cbe_launch_batch(int nframes, const CbeBatch &B, int shuffle, int typ
     }
     if (fused) {
         hb_prof_begin("k_match_fused", s);
-        hb_launch_match_fused_selfcontained_batch(d_bf, d_map, typesize, d_desc + plain, d_records + (size_t)plain * HB_RSTRIDE, fused, 64, s);
+        hb_launch_match_fused_selfcontained_batch(d_bf, d_map, typesize, d_desc + plain, d_records + (size_t)plain * HB_RSTRIDE, fused, M.ways, M.accel, s);
         hb_prof_end(s);
     }
     if (plain) {
         hb_prof_begin("k_match", s);
         // with a filter the whole blocks of these frames lie chunk after chunk in one area: one long buffer of self-contained chunks, no map
-        if (B.filtered) hb_launch_match_selfcontained(w + L.filt, (size_t)plain * HB_CHUNK, d_desc, d_records, plain, 64, s);
-        else hb_launch_match_selfcontained_batch(d_bf, d_map, d_desc, d_records, plain, 64, s);
+        if (B.filtered) hb_launch_match_selfcontained(w + L.filt, (size_t)plain * HB_CHUNK, d_desc, d_records, plain, M.ways, M.accel, s);
+        else hb_launch_match_selfcontained_batch(d_bf, d_map, d_desc, d_records, plain, M.ways, M.accel, s);
         hb_prof_end(s);
     }
     if (ntiles) {
@@ -1948,6 +1989,7 @@ size_t hb_cblosc_compress_frames_batch_workspace(int nframes, const size_t *n, i
 
 int hb_cblosc_compress_frames_batch_device(int nframes, const void *const *d_src, const size_t *n, void *const *d_frame, const size_t *cap, int shuffle, int typesize,
                                            void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    const unsigned policy = hb_cblosc_policy();                           // (hb_cblosc_set_compressor, read once: one call, one policy)
     if (nframes < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
     if (nframes == 0) return HB_OK;
     if (!d_src || !n || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
@@ -1958,7 +2000,7 @@ int hb_cblosc_compress_frames_batch_device(int nframes, const void *const *d_src
     const CbeLayout &L = B.L;
     if (work_bytes < B.query || B.query < L.total) return HB_ERR_SHORT_BUFFER;      // (the layout never exceeds the query: hb_cblosc_enc_batch.h)
     if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
-    return cbe_launch_batch(nframes, B, shuffle, typesize, w, d_results, (hipStream_t)stream);
+    return cbe_launch_batch(nframes, B, shuffle, typesize, policy, w, d_results, (hipStream_t)stream);
 }
 
 // ---- many source boxes, one set of launches (include/hipblosc.h; the host side is hb_cblosc_enc_box_batch.h) ----
@@ -1968,6 +2010,7 @@ size_t hb_cblosc_compress_boxes_batch_workspace(int nframes, const hb_cblosc_src
 
 int hb_cblosc_compress_boxes_batch_device(int nframes, const hb_cblosc_src_box *boxes, const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill,
                                           int shuffle, int typesize, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    const unsigned policy = hb_cblosc_policy();                           // (hb_cblosc_set_compressor, read once: one call, one policy)
     if (nframes < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
     if (nframes == 0) return HB_OK;
     if (!boxes || !d_src || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
@@ -1997,7 +2040,7 @@ int hb_cblosc_compress_boxes_batch_device(int nframes, const hb_cblosc_src_box *
                            (const uint8_t *)(w + L.fill), (uint32_t)typesize, cbx_recip((uint32_t)typesize));
         hb_prof_end(s);
     }
-    return cbe_launch_batch(nframes, B.E, shuffle, typesize, w + L.enc, d_results, s);
+    return cbe_launch_batch(nframes, B.E, shuffle, typesize, policy, w + L.enc, d_results, s);
 }
 
 // ---- many update boxes, one set of launches (include/hipblosc.h; the host side is hb_cblosc_upd_box_batch.h) ----
@@ -2008,6 +2051,7 @@ size_t hb_cblosc_update_boxes_batch_workspace(int njobs, const hb_cblosc_upd_box
 int hb_cblosc_update_boxes_batch_device(int njobs, const hb_cblosc_upd_box *boxes, const hb_cblosc_header *old_hdrs, const void *const *d_old, const size_t *old_n,
                                         const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill, int shuffle, int typesize,
                                         void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    const unsigned policy = hb_cblosc_policy();                           // (hb_cblosc_set_compressor, read once: one call, one policy)
     if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
     if (njobs == 0) return HB_OK;
     if (!boxes || !old_hdrs || !d_old || !old_n || !d_src || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
@@ -2056,7 +2100,7 @@ int hb_cblosc_update_boxes_batch_device(int njobs, const hb_cblosc_upd_box *boxe
     }
     // (the encoder reads the staged bytes of a base that failed to decode: they lie inside the workspace and may be anything, and the encoder
     // takes any bytes; k_cbxu_finish then overrides that frame's record)
-    const int st = cbe_launch_batch(njobs, B.X.E, shuffle, typesize, wx + XL.enc, d_results, s);
+    const int st = cbe_launch_batch(njobs, B.X.E, shuffle, typesize, policy, wx + XL.enc, d_results, s);
     if (st) return st;
     if (nd) {
         hb_prof_begin("k_cbxu_finish", s);
@@ -2076,6 +2120,7 @@ size_t hb_cblosc_update_index_batch_workspace(int njobs, const hb_cblosc_upd_ind
 int hb_cblosc_update_index_batch_device(int njobs, const hb_cblosc_upd_index *jobs, const int64_t *index, int64_t nindex, const hb_cblosc_header *old_hdrs,
                                         const void *const *d_old, const size_t *old_n, const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill,
                                         int shuffle, int typesize, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    const unsigned policy = hb_cblosc_policy();                           // (hb_cblosc_set_compressor, read once: one call, one policy)
     if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
     if (njobs == 0) return HB_OK;
     if (!jobs || !old_hdrs || !d_old || !old_n || !d_src || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
@@ -2134,7 +2179,7 @@ int hb_cblosc_update_index_batch_device(int njobs, const hb_cblosc_upd_index *jo
         hb_prof_end(s);
     }
     // (a base that failed to decode: as in the box updates, the encoder takes any bytes and k_cbxu_finish overrides that frame's record)
-    const int st = cbe_launch_batch(njobs, B.U.X.E, shuffle, typesize, wx + XL.enc, d_results, s);
+    const int st = cbe_launch_batch(njobs, B.U.X.E, shuffle, typesize, policy, wx + XL.enc, d_results, s);
     if (st) return st;
     if (nd) {
         hb_prof_begin("k_cbxu_finish", s);
@@ -2146,7 +2191,7 @@ int hb_cblosc_update_index_batch_device(int njobs, const hb_cblosc_upd_index *jo
 }
 // A prepared batch of point updates (CbpuBatch) on the device: one upload, the fill bases, the old-frame bases, the scatter, the encoder and the
 // records.  d_sel_tab: the point table of a prepared selection, which the scatter then reads in place of the batch's own (none is uploaded).
-static int cbpu_launch(const CbpuBatch &B, int njobs, const CbpPoint *d_sel_tab, int shuffle, int typesize, uint8_t *w, hb_result *d_results, void *stream) {
+static int cbpu_launch(const CbpuBatch &B, int njobs, const CbpPoint *d_sel_tab, int shuffle, int typesize, unsigned policy, uint8_t *w, hb_result *d_results, void *stream) {
     const CbxuLayout &L = B.U.L;
     const CbxeLayout &XL = B.U.X.L;
     const CbpuLayout &SL = B.S;
@@ -2184,7 +2229,7 @@ static int cbpu_launch(const CbpuBatch &B, int njobs, const CbpPoint *d_sel_tab,
         hb_prof_end(s);
     }
     // (a base that failed to decode: as in the box updates, the encoder takes any bytes and k_cbxu_finish overrides that frame's record)
-    const int st = cbe_launch_batch(njobs, B.U.X.E, shuffle, typesize, wx + XL.enc, d_results, s);
+    const int st = cbe_launch_batch(njobs, B.U.X.E, shuffle, typesize, policy, wx + XL.enc, d_results, s);
     if (st) return st;
     if (nd) {
         hb_prof_begin("k_cbxu_finish", s);
@@ -2203,6 +2248,7 @@ size_t hb_cblosc_update_points_batch_workspace(int njobs, const hb_cblosc_upd_po
 int hb_cblosc_update_points_batch_device(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints, const hb_cblosc_header *old_hdrs,
                                          const void *const *d_old, const size_t *old_n, const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill,
                                          int shuffle, int typesize, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    const unsigned policy = hb_cblosc_policy();                           // (hb_cblosc_set_compressor, read once: one call, one policy)
     if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
     if (njobs == 0) return HB_OK;
     if (!jobs || !old_hdrs || !d_old || !old_n || !d_src || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
@@ -2218,7 +2264,7 @@ int hb_cblosc_update_points_batch_device(int njobs, const hb_cblosc_upd_point_jo
     if (!query) return HB_ERR_BAD_ARG;                                    // (the limits are taken as the query takes them)
     if (work_bytes < query || query < L.total || B.U.X.E.query < B.U.X.E.L.total) return HB_ERR_SHORT_BUFFER;
     if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
-    return cbpu_launch(B, njobs, nullptr, shuffle, typesize, w, d_results, stream);
+    return cbpu_launch(B, njobs, nullptr, shuffle, typesize, policy, w, d_results, stream);
 }
 
 // ---- prepared point selections (include/hipblosc.h; the host side, the builders and the per-call prepares are hb_cblosc_point_sel.h) ----
@@ -2537,6 +2583,7 @@ size_t hb_cblosc_update_points_sel_workspace(const hb_cblosc_point_sel *sel, con
 int hb_cblosc_update_points_sel_device(const hb_cblosc_point_sel *sel, const hb_cblosc_header *old_hdrs, const void *const *d_old, const size_t *old_n,
                                        const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill, int shuffle, int typesize,
                                        void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    const unsigned policy = hb_cblosc_policy();                           // (hb_cblosc_set_compressor, read once: one call, one policy)
     if (!sel || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2 || typesize != sel->P.typesize) return HB_ERR_BAD_ARG;
     const int njobs = (int)sel->P.jobs.size();
     if (njobs == 0) return HB_OK;
@@ -2550,6 +2597,6 @@ int hb_cblosc_update_points_sel_device(const hb_cblosc_point_sel *sel, const hb_
     if (cbsel_update_prepare(sel->P, sel->W, old_hdrs, nullptr, old_n, nullptr, nullptr, nullptr, nullptr, shuffle, typesize, nullptr, accept, Q) || !Q.query) return HB_ERR_BAD_ARG;
     if (work_bytes < Q.query || Q.query < B.U.L.total || B.U.X.E.query < B.U.X.E.L.total) return HB_ERR_SHORT_BUFFER;
     if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
-    return cbpu_launch(B, njobs, sel->d_tab, shuffle, typesize, w, d_results, stream);
+    return cbpu_launch(B, njobs, sel->d_tab, shuffle, typesize, policy, w, d_results, stream);
 }
 }  // extern "C"

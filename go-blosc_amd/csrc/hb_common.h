@@ -183,9 +183,27 @@ struct Scratch {     // RAII over pool buffers for one host-API call
 int hb_select_device(int device);                        // hipSetDevice with the ABI's error codes
 unsigned hb_dbg_plane_mask();                            // hb_debug_plane_mask(): byte planes the fused LZ4 kernels work on (timing only)
 
+// Search depth and skip acceleration from (codec, level), level 1..9 -- the one table behind Options.Level of the go-blosc-format frames
+// (hb_lz4_enc.hip, enc_policy) and behind hb_cblosc_set_compressor (hb_cblosc.hip).  LZ4: one candidate per bucket (lz4.CompressBlock); the
+// reference ignores the level there (codec.go:63-66), here it is a speed knob that never changes validity: 1-3 skip harder (a step without a
+// hit widens the stride by 128 bytes), 4-6 the default (64), 7-9 no skipping.  LZ4HC: codec.go:96-106 maps level <= 3 / <= 5 / <= 7 / else
+// to lz4.Level1 / 5 / 7 / 9; here 1 / 2 / 4 / 4 candidates per bucket, no skipping.
+static inline void hb_level_policy(int codec, int level, int &ways, int &accel) {
+    ways = 1; accel = 64;
+    if (codec == HB_LZ4HC) { ways = level <= 3 ? 1 : (level <= 5 ? 2 : 4); accel = 0; }
+    else if (codec == HB_LZ4) accel = level <= 3 ? 128 : (level <= 6 ? 64 : 0);
+}
 // ---- internal launch API shared between translation units ----
 // hb_cblosc.hip: the header / geometry / range refusals of the C-Blosc-1 getitem entry points; *bytes = nitems * typesize
 unsigned hb_cblosc_accepted();        // the mask of hb_cblosc_accept_codecs (hb_cblosc.hip): read once per entry point
+unsigned hb_cblosc_policy();          // the word of hb_cblosc_set_compressor (hb_cblosc.hip), codec << 8 | clevel: read once per writer entry point
+struct CbPolicyPin {                  // a host form of a writer: the word it read stays this thread's answer of hb_cblosc_policy() while it runs
+    int prev;
+    CbPolicyPin();
+    ~CbPolicyPin();
+    CbPolicyPin(const CbPolicyPin &) = delete;
+    CbPolicyPin &operator=(const CbPolicyPin &) = delete;
+};
 int hb_cblosc_getitem_prepare(const hb_cblosc_header *hdr, size_t n, int64_t start, int64_t nitems, uint64_t *bytes);
 int hb_launch_filter(int op, uint8_t *d_dst, const uint8_t *d_src, size_t n, int typesize, hipStream_t s);
 // same, but every kernel returns immediately unless *gate != 0 (gate is read on the device)

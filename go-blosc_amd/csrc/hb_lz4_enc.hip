@@ -1390,15 +1390,12 @@ __global__ __launch_bounds__(STITCH_THREADS) void k_sn_pack(const ChunkDesc *__r
 // ----------------------------------------------------------------------------------------------
 // launch
 // ----------------------------------------------------------------------------------------------
-// Search depth and skip acceleration from (codec, level).  LZ4: one candidate (lz4.CompressBlock); the reference ignores the level
-// there (codec.go:63-66), here it is a speed knob that never changes validity: 1-3 skip harder, 4-6 the default, 7-9 no skipping.
-// LZ4HC: codec.go:96-106 maps level <= 3 / <= 5 / <= 7 / else to lz4.Level1 / 5 / 7 / 9; here 1 / 2 / 4 / 4 candidates per
-// bucket, no skipping.  Snappy has no levels (codec.go:232-235).
+// Search depth and skip acceleration from (codec, level): hb_level_policy (hb_common.h) has the table.  Outside it: Snappy has no levels
+// (codec.go:232-235), and a bare LZ4 block (no frame) keeps the default stride whatever the level.
 static inline void enc_policy(const hb_enc_args &a, int &ways, int &accel) {
     const int level = a.level < 1 ? 1 : (a.level > 9 ? 9 : a.level);          // blosc.go:277-282
     ways = 1; accel = 64;
-    if (a.codec == HB_LZ4HC) { ways = level <= 3 ? 1 : (level <= 5 ? 2 : 4); accel = 0; }
-    else if (a.codec == HB_LZ4 && a.frame) accel = level <= 3 ? 128 : (level <= 6 ? 64 : 0);
+    if (a.codec == HB_LZ4HC || (a.codec == HB_LZ4 && a.frame)) hb_level_policy(a.codec, level, ways, accel);
 }
 
 #define HB_LAUNCH_FUSED(TS, W, SN) hipLaunchKernelGGL((k_match_fused<TS, W, SN>), dim3(grid), dim3(64), 0, s, a.src, desc, records, nblk, hb_dbg_plane_mask(), accel, bf, chunk_frame, total_items)
@@ -1430,32 +1427,45 @@ static void launch_match(const hb_enc_args &a, unsigned grid, ChunkDesc *desc, u
 // keep their workgroup id mod 8 (XCD), so every frame starts at a multiple of 8 * typesize (the gap chunks belong to no frame)
 static inline uint32_t batch_granule(bool fused_ts, int typesize) { return fused_ts ? 8u * (uint32_t)typesize : 1u; }
 
-// every HB_CHUNK bytes of src become an LZ4 block of their own (hb_cblosc.hip): records + descriptors only, nothing is stitched
-void hb_launch_match_selfcontained(const uint8_t *src, size_t n, void *desc, uint8_t *records, uint32_t nchunks, int accel, hipStream_t s) {
+// every HB_CHUNK bytes of src become an LZ4 block of their own (hb_cblosc.hip): records + descriptors only, nothing is stitched.
+// ways / accel: hb_level_policy's, as the writer's entry point read them (hb_cblosc_set_compressor); (1, 64) is the default.
+#define HB_LAUNCH_MATCH_SELF(W) hipLaunchKernelGGL((k_match<W, 2>), dim3(grid), dim3(64), 0, s, src, (uint64_t)n, (ChunkDesc *)desc, records, nchunks, 0, 0, accel, bf, chunk_frame)
+static void launch_match_self(const uint8_t *src, size_t n, void *desc, uint8_t *records, uint32_t nchunks, int ways, int accel, const BatchFrame *bf, const uint32_t *chunk_frame,
+                              hipStream_t s) {
     const unsigned grid = nchunks < 256u * 256u ? nchunks : 256u * 256u;
-    hipLaunchKernelGGL((k_match<1, 2>), dim3(grid), dim3(64), 0, s, src, (uint64_t)n, (ChunkDesc *)desc, records, nchunks, 0, 0, accel, (const BatchFrame *)nullptr, (const uint32_t *)nullptr);
+    if (ways == 1) HB_LAUNCH_MATCH_SELF(1);
+    else if (ways == 2) HB_LAUNCH_MATCH_SELF(2);
+    else HB_LAUNCH_MATCH_SELF(4);
+}
+#define HB_LAUNCH_FUSED_SELF(TS, W) hipLaunchKernelGGL((k_match_fused<TS, W, 2>), dim3(grid), dim3(64), 0, s, src, (ChunkDesc *)desc, records, nblk, 0xFFFFFFFFu, accel, bf, chunk_frame, total_items)
+#define HB_LAUNCH_FUSED_SELF_WAYS(TS) do { if (ways == 1) HB_LAUNCH_FUSED_SELF(TS, 1); else if (ways == 2) HB_LAUNCH_FUSED_SELF(TS, 2); else HB_LAUNCH_FUSED_SELF(TS, 4); } while (0)
+static bool launch_match_fused_self(unsigned grid, const uint8_t *src, int typesize, void *desc, uint8_t *records, uint32_t nblk, int ways, int accel, const BatchFrame *bf,
+                                    const uint32_t *chunk_frame, uint32_t total_items, hipStream_t s) {
+    switch (typesize) {
+    case 2: HB_LAUNCH_FUSED_SELF_WAYS(2); return true;
+    case 4: HB_LAUNCH_FUSED_SELF_WAYS(4); return true;
+    case 8: HB_LAUNCH_FUSED_SELF_WAYS(8); return true;
+    default: return false;
+    }
+}
+void hb_launch_match_selfcontained(const uint8_t *src, size_t n, void *desc, uint8_t *records, uint32_t nchunks, int ways, int accel, hipStream_t s) {
+    launch_match_self(src, n, desc, records, nchunks, ways, accel, nullptr, nullptr, s);
 }
 
 // the same with the byte shuffle fused (typesize 2 / 4 / 8): chunk (plane j, element block b) lands at index j * nblk + b
-bool hb_launch_match_fused_selfcontained(const uint8_t *src, int typesize, void *desc, uint8_t *records, uint32_t nblk, int accel, hipStream_t s) {
+bool hb_launch_match_fused_selfcontained(const uint8_t *src, int typesize, void *desc, uint8_t *records, uint32_t nblk, int ways, int accel, hipStream_t s) {
     const uint64_t items = (uint64_t)nblk * (uint64_t)typesize;
     const unsigned grid = (unsigned)(items < 256u * 256u ? items : 256u * 256u);
-    switch (typesize) {
-    case 2: hipLaunchKernelGGL((k_match_fused<2, 1, 2>), dim3(grid), dim3(64), 0, s, src, (ChunkDesc *)desc, records, nblk, 0xFFFFFFFFu, accel, (const BatchFrame *)nullptr, (const uint32_t *)nullptr, 0u); return true;
-    case 4: hipLaunchKernelGGL((k_match_fused<4, 1, 2>), dim3(grid), dim3(64), 0, s, src, (ChunkDesc *)desc, records, nblk, 0xFFFFFFFFu, accel, (const BatchFrame *)nullptr, (const uint32_t *)nullptr, 0u); return true;
-    case 8: hipLaunchKernelGGL((k_match_fused<8, 1, 2>), dim3(grid), dim3(64), 0, s, src, (ChunkDesc *)desc, records, nblk, 0xFFFFFFFFu, accel, (const BatchFrame *)nullptr, (const uint32_t *)nullptr, 0u); return true;
-    default: return false;
-    }
+    return launch_match_fused_self(grid, src, typesize, desc, records, nblk, ways, accel, nullptr, nullptr, 0u, s);
 }
 
 // the two self-contained matchers over the flat chunk space of a batch (hb_cblosc.hip, hb_cblosc_compress_frames_batch_device): frame k's
 // chunks start at bf[k].chunk0, chunk_frame says whose every chunk is.  The grid of the fused launch as hb_launch_lz4_encode_batch sizes it.
-void hb_launch_match_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, void *desc, uint8_t *records, uint32_t total_chunks, int accel, hipStream_t s) {
-    const unsigned grid = total_chunks < 256u * 256u ? total_chunks : 256u * 256u;
-    hipLaunchKernelGGL((k_match<1, 2>), dim3(grid), dim3(64), 0, s, (const uint8_t *)nullptr, (uint64_t)0, (ChunkDesc *)desc, records, total_chunks, 0, 0, accel, bf, chunk_frame);
+void hb_launch_match_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, void *desc, uint8_t *records, uint32_t total_chunks, int ways, int accel, hipStream_t s) {
+    launch_match_self(nullptr, 0, desc, records, total_chunks, ways, accel, bf, chunk_frame, s);
 }
-bool hb_launch_match_fused_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, int typesize, void *desc, uint8_t *records, uint32_t total_items, int accel,
-                                               hipStream_t s) {
+bool hb_launch_match_fused_selfcontained_batch(const BatchFrame *bf, const uint32_t *chunk_frame, int typesize, void *desc, uint8_t *records, uint32_t total_items, int ways,
+                                               int accel, hipStream_t s) {
     if (typesize != 2 && typesize != 4 && typesize != 8) return false;
     const uint32_t granule = batch_granule(true, typesize);
     unsigned grid = total_items < 256u * 256u ? total_items : 256u * 256u;
@@ -1465,12 +1475,7 @@ bool hb_launch_match_fused_selfcontained_batch(const BatchFrame *bf, const uint3
         if (grid > 256u * 256u) grid = 256u * 256u;
         if (grid == 0) grid = total_items;
     }
-    switch (typesize) {
-    case 2: hipLaunchKernelGGL((k_match_fused<2, 1, 2>), dim3(grid), dim3(64), 0, s, (const uint8_t *)nullptr, (ChunkDesc *)desc, records, 0u, 0xFFFFFFFFu, accel, bf, chunk_frame, total_items); break;
-    case 4: hipLaunchKernelGGL((k_match_fused<4, 1, 2>), dim3(grid), dim3(64), 0, s, (const uint8_t *)nullptr, (ChunkDesc *)desc, records, 0u, 0xFFFFFFFFu, accel, bf, chunk_frame, total_items); break;
-    default: hipLaunchKernelGGL((k_match_fused<8, 1, 2>), dim3(grid), dim3(64), 0, s, (const uint8_t *)nullptr, (ChunkDesc *)desc, records, 0u, 0xFFFFFFFFu, accel, bf, chunk_frame, total_items); break;
-    }
-    return true;
+    return launch_match_fused_self(grid, nullptr, typesize, desc, records, 0u, ways, accel, bf, chunk_frame, total_items, s);
 }
 
 int hb_launch_lz4_encode(const hb_enc_args &a, hipStream_t s) {

@@ -581,6 +581,26 @@ func CBloscAcceptCodecs(mask uint) (uint, error) {
 	return uint(rc), nil
 }
 
+// CBloscSetCompressor chooses the compressor and level of CompressCBlosc and of every batched C-Blosc-1 writer below
+// (hb_cblosc_set_compressor; blosc_set_compressor and clevel of c-blosc): codec LZ4 or LZ4HC -- both write codec format 1, as c-blosc does --
+// and level 0..9.  LZ4: one candidate per bucket, the search skips harder at levels 1-3 and not at all at 7-9; LZ4HC: 1 / 2 / 4 candidates at
+// levels 1-3 / 4-5 / 6-9; level 0 writes memcpyed frames.  The default is (LZ4, 5).  Process-wide and safe to call from any goroutine: every
+// writer reads the setting once per call.  Returns the previous setting; any other codec or level is refused and changes nothing.
+func CBloscSetCompressor(codec Codec, level int) (Codec, int, error) {
+	rc := C.hb_cblosc_set_compressor(C.int(codec), C.int(level))
+	if rc < 0 {
+		return 0, 0, hbError(C.int64_t(rc))
+	}
+	return Codec(rc >> 8), int(rc & 255), nil
+}
+
+// CBloscGetCompressor returns the compressor and level the C-Blosc-1 writers use (hb_cblosc_get_compressor).
+func CBloscGetCompressor() (Codec, int) {
+	var c, l C.int
+	C.hb_cblosc_get_compressor(&c, &l)
+	return Codec(c), int(l)
+}
+
 // DecompressCBlosc reads a C-Blosc-1 frame with LZ4 / LZ4HC streams (or a memcpyed one), and BloscLZ streams once CBloscAcceptCodecs(0x3)
 // has been called; other codec formats: ErrInvalidCodec.
 func DecompressCBlosc(frame []byte) ([]byte, error) {

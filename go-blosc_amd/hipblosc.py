@@ -117,7 +117,7 @@ EXPORTS = [
     "hb_cblosc_getpoints_sel_workspace", "hb_cblosc_getpoints_sel_device", "hb_cblosc_update_points_sel_workspace", "hb_cblosc_update_points_sel_device",
     "hb_cblosc_point_sel_create_mask_device", "hb_cblosc_point_sel_create_coords_device", "hb_cblosc_point_sel_njobs", "hb_cblosc_point_sel_npoints",
     "hb_cblosc_point_sel_job_chunks", "hb_cblosc_point_sel_job_points",
-    "hb_cblosc_accept_codecs",
+    "hb_cblosc_accept_codecs", "hb_cblosc_set_compressor", "hb_cblosc_get_compressor",
     "hb_queue_create", "hb_queue_create_ex", "hb_queue_destroy", "hb_queue_compress", "hb_queue_decompress", "hb_queue_wait",
 ]
 
@@ -415,6 +415,8 @@ def lib():
             "hb_cblosc_point_sel_job_chunks": (i32, [vp, vp, i32]),
             "hb_cblosc_point_sel_job_points": (i32, [vp, i32, vp, i64]),
             "hb_cblosc_accept_codecs": (i32, [ctypes.c_uint]),
+            "hb_cblosc_set_compressor": (i32, [i32, i32]),
+            "hb_cblosc_get_compressor": (i32, [vp, vp]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -810,6 +812,20 @@ def CBloscAcceptCodecs(mask):
     """Which C-Blosc-1 codec formats the CBlosc* calls decode (include/hipblosc.h hb_cblosc_accept_codecs): 0x2 = LZ4 / LZ4HC (the default),
     0x3 adds BloscLZ.  Process-wide; returns the previous mask."""
     return _check(lib().hb_cblosc_accept_codecs(int(mask)))
+
+
+def CBloscSetCompressor(codec, clevel):
+    """Which compressor and level the CBlosc* writers use (include/hipblosc.h hb_cblosc_set_compressor): codec LZ4 or LZ4HC, clevel 0..9, the
+    default (LZ4, 5); clevel 0 writes memcpyed frames.  Process-wide, read once per call; returns the previous (codec, clevel)."""
+    prev = _check(lib().hb_cblosc_set_compressor(int(codec), int(clevel)))
+    return prev >> 8, prev & 255
+
+
+def CBloscGetCompressor():
+    """The (codec, clevel) the CBlosc* writers use (include/hipblosc.h hb_cblosc_get_compressor)."""
+    c, l = ctypes.c_int(), ctypes.c_int()
+    _check(lib().hb_cblosc_get_compressor(ctypes.byref(c), ctypes.byref(l)))
+    return c.value, l.value
 
 
 def CBloscDecompress(frame):

@@ -11,6 +11,7 @@
 #include <memory>
 #include <mutex>
 #include <stdexcept>
+#include <utility>
 #include <string>
 #include <vector>
 
@@ -155,6 +156,10 @@ inline std::vector<Bytes> GetItemBatch(const std::vector<Bytes> &frames, const s
 // which C-Blosc-1 codec formats the CBlosc* calls decode (hb_cblosc_accept_codecs): 0x2 = LZ4 / LZ4HC (the default), 0x3 adds BloscLZ; process-wide;
 // returns the previous mask, throws for any other mask
 inline unsigned CBloscAcceptCodecs(unsigned mask) { return (unsigned)check(hb_cblosc_accept_codecs(mask)); }
+// which compressor and level the CBlosc* writers use (hb_cblosc_set_compressor): codec HB_LZ4 or HB_LZ4HC, clevel 0..9 (0: memcpyed frames), the default
+// (HB_LZ4, 5); process-wide, read once per call; returns the previous setting packed as codec << 8 | clevel, throws for anything else
+inline int CBloscSetCompressor(int codec, int clevel) { return (int)check(hb_cblosc_set_compressor(codec, clevel)); }
+inline std::pair<int, int> CBloscGetCompressor() { int c = 0, l = 0; check(hb_cblosc_get_compressor(&c, &l)); return {c, l}; }
 // many C-Blosc-1 frames through one set of launches (hb_cblosc_decompress_frames_batch): out[k] is what hb_cblosc_decompress gives for frames[k],
 // rc[k] the byte count or its HB_ERR_* code (nothing is thrown per frame)
 inline std::vector<Bytes> CBloscDecompressBatch(const std::vector<Bytes> &frames, std::vector<int64_t> &rc, int device = 0) {

@@ -353,7 +353,8 @@ int     hb_cblosc_parse_header(const void *frame, size_t n, hb_cblosc_header *ou
  * hb_cblosc_getitem*, hb_cblosc_getitem_frames_batch*, hb_cblosc_getbox_frames_batch*, hb_cblosc_getslice_frames_batch*, device and host forms and their workspace queries) reads once
  * per call.  With bit 0 set a BloscLZ frame gets exactly the refusals, in the same order, that an LZ4 frame with the same header gets; wherever the
  * comments below say "codec format != 1" read "a codec format the mask does not name".  Opt-in, because HB_ERR_INVALID_CODEC for
- * BloscLZ is an answer callers may route on (to a CPU decoder).  Writing is not touched: hb_cblosc_compress* writes LZ4. */
+ * BloscLZ is an answer callers may route on (to a CPU decoder).  Writing is not touched: hb_cblosc_compress* writes LZ4 (hb_cblosc_set_compressor
+ * below chooses how hard it searches; its threading rule is this one). */
 int     hb_cblosc_accept_codecs(unsigned mask);
 size_t  hb_cblosc_decompress_workspace(size_t nbytes, size_t blocksize, size_t typesize);
 int     hb_cblosc_decompress_dev(const hb_cblosc_header *hdr, const void *d_frame, size_t n, void *d_dst, size_t cap,
@@ -650,6 +651,26 @@ size_t  hb_cblosc_compress_workspace(size_t n, int shuffle, int typesize);
 int     hb_cblosc_compress_dev(const void *d_src, size_t n, void *d_frame, size_t cap, int shuffle, int typesize,
                                void *d_work, size_t work_bytes, hb_result *d_result, void *stream);
 int64_t hb_cblosc_compress(const void *src, size_t n, void *dst, size_t cap, int shuffle, int typesize, int device);
+/* which compressor and level the writers use: blosc_set_compressor() and the clevel argument of c-blosc, cname / clevel of python-blosc
+ * and numcodecs.  codec: HB_LZ4 or HB_LZ4HC (both write codec format 1, as c-blosc does: every reader of the frames above reads them);
+ * clevel 0..9.  The default is (HB_LZ4, 5).
+ *      HB_LZ4:   one candidate per hash bucket; a search step without a match widens the stride by 128 bytes at levels 1-3, by 64 at 4-6, not
+ *                at all at 7-9.
+ *      HB_LZ4HC: 1 / 2 / 4 candidates per bucket at levels 1-3 / 4-5 / 6-9, the longest match wins; the stride never widens.
+ *      clevel 0: the memcpyed frame (header + the bytes, what blosc_compress writes at level 0 and what n < 4096 gets at every level), no
+ *                matcher runs; in a batch every frame of the call is memcpyed.
+ * Levels that map to the same row write the same bytes.  hb_cblosc_set_compressor returns the previous setting packed as codec << 8 | clevel
+ * (so that a caller can put it back), or HB_ERR_BAD_ARG -- and no change -- for any other codec or a level outside 0..9.
+ * hb_cblosc_get_compressor stores the setting; either pointer may be NULL; it returns HB_OK.
+ * Process-wide and thread-safe, under the rule of hb_cblosc_accept_codecs: an atomic word that every writer entry point
+ * (hb_cblosc_compress*, hb_cblosc_compress_frames_batch*, hb_cblosc_compress_boxes_batch*, hb_cblosc_update_boxes_batch*,
+ * hb_cblosc_update_index_batch*, hb_cblosc_update_points_batch*, hb_cblosc_update_points_sel_device; device and host forms) reads once per
+ * call, before anything is sized or launched: one call uses one policy throughout -- a host form also for the one-frame calls it answers the
+ * rest of its batch with -- and a setter call on another thread takes effect for calls that begin after it.  "Byte for byte what
+ * hb_cblosc_compress_dev writes" in the batch contracts below means: under the same setting.  hb_cblosc_bound and every workspace query do
+ * not depend on the setting: a workspace sized under one setting serves a call under any other.  Reading is not touched. */
+int     hb_cblosc_set_compressor(int codec, int clevel);
+int     hb_cblosc_get_compressor(int *codec, int *clevel);
 /* ---- batched C-Blosc-1 encode: many inputs through ONE set of launches (upload, chunk map, filter, the matcher launch or launches, tile sums,
  *      one scan workgroup per frame, pack, finish -- the same launches for 4 frames and for 4096).  One shuffle / typesize for the whole batch:
  *      an array has one dtype and one filter.
