@@ -67,6 +67,9 @@ struct DecCtx {
 #define DEC_STAGE_DEPTH 4                // 16-byte vectors a lane has under way when a unit fills LDS from the stream (stage(), the literal-run unit); 1: load, wait, write, one at a time
 #endif
 #define DEC_NO_UNIT 0xFFFFFFFFu
+#ifndef DEC_PLANE_CMP
+#define DEC_PLANE_CMP 1                  // the plane of a unit of a byte-shuffled frame by compares, not by a division (0: d0 / ne)
+#endif
 // What a unit fetched ahead for the unit its wave takes next (k_dec_indexed: `it + gridDim.x`), so that a unit does not begin with three
 // memory round trips in a row behind the acknowledgements of the 64 byte stores before it (entries, first window, first parse):
 //   e   : that unit's two index entries, read through the scalar data cache at the head of the unit before it;
@@ -187,7 +190,17 @@ __device__ __forceinline__ void dec_unit(const DecCtx &c, const uint32_t u, uint
     if (rem != HB_IDX_AT_TOKEN && tokpos >= n_src) ok = false;
     if (bun4 && ((d0 | d1) & 31u)) ok = false;              // fused un-filter works on whole 32-byte windows
     const uint32_t ne = ush ? nbytes / (uint32_t)ush : 1u;  // bytes per plane
+#if DEC_PLANE_CMP
+    // my plane, min(d0 / ne, ush): counted with one compare per plane where the typesize is a compile-time constant (a division by a
+    // run-time value is two dozen scalar instructions); ush itself -- no plane, the check below fails -- where d0 lies behind the last one
+    uint32_t pj = 0u;
+    if constexpr (USH > 0) {
+#pragma unroll
+        for (uint32_t k = 1; k <= (uint32_t)USH; k++) pj += d0 >= k * ne ? 1u : 0u;          // (k * ne <= nbytes: 32 bits hold it)
+    } else if (ush) pj = d0 / ne;
+#else
     const uint32_t pj = ush ? d0 / ne : 0u;                 // my plane
+#endif
     if (ush && (pj >= (uint32_t)ush || d1 > (pj + 1u) * ne)) ok = false;   // a unit never straddles two planes
     uint8_t *const udst = ush ? dst + (size_t)(d0 - pj * ne) * (uint32_t)ush + pj : dst + d0;
     if (!ok) { if (lane == 0) atomicExch(&plan->fail, 1u); return; }
@@ -383,9 +396,9 @@ __device__ __forceinline__ void dec_unit(const DecCtx &c, const uint32_t u, uint
             stage(si);
         }
 #if DEC_LEAN
-        const bool stop = dec_fill_lean(s_in, (uint32_t)shw, staged, slen, si, nq, s_tq, lane, last_ntok);
+        const dec_stop_t stop = dec_fill_lean(s_in, (uint32_t)shw, staged, slen, si, nq, s_tq, lane, last_ntok);
         bool rewound = false;
-        ok = dec_drain<true>(s_in, shw, s_out, outlen, 0u, di, si, nq, s_tq, stop, rewound, lane);
+        ok = dec_drain<true>(s_in, shw, s_out, outlen, 0u, di, si, nq, s_tq, stop != 0, rewound, lane);
 #else
         const bool stop = dec_fill(s_in, (uint32_t)shw, staged, slen, si, nq, s_tq, lane);
         bool rewound = false;

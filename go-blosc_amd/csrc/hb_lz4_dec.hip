@@ -29,6 +29,10 @@
 #include "hb_dec_common.h"
 #include "hb_dec_unit.h"      // dec_plan_check, DecCtx, dec_unit
 
+#ifndef DEC_ORDER_LEAN
+#define DEC_ORDER_LEAN 1                 // k_dec_indexed's unit order: only the order in use, pass number and stride product carried from pass to pass (0: both orders, divided out of `it` per unit)
+#endif
+
 size_t hb_lz4_dec_workspace(size_t n_out) { return 256 + hb_lz4_region_workspace(n_out); }
 
 __global__ void k_dec_plan(const uint8_t *__restrict__ index, uint64_t index_bytes, uint64_t n_src, uint64_t cap,
@@ -69,6 +73,65 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEC_WAVES)))
     // units are independent.
     const uint32_t P = plan->stride;                        // computed once by k_dec_plan
     const uint32_t mgrp = (nunits + 7u) / 8u;
+    DecCtx c; c.src = src; c.n_src = n_src; c.dst = dst; c.ent = ent; c.plan = plan; c.nbytes = nbytes; c.nunits = nunits; c.bun4 = bun4; c.ush = ush;
+    DecPre pre; pre.u = DEC_NO_UNIT; pre.win = 0u;
+#if DEC_ORDER_LEAN
+    // Only the order in use is evaluated, and what changes from pass to pass is carried along instead of being divided out of `it` again
+    // (the decoder's fullest pipe is the scalar unit, DESIGN 5.2: per unit this was a 64-bit product and modulo, two divisions by run-time
+    // values and two reads of the grid size, about 70 scalar instructions of the unit's 1900):
+    //   pass = it / gridDim.x           counts up;
+    //   kp   = (it >> 3) * P mod mgrp   moves by ((gridDim.x >> 3) * P) mod mgrp per pass.  32-bit products: gridDim.x >> 3 <= 2^13 and
+    //                                   P mod mgrp < 2^17 (nbytes is 32 bits wide, so there are at most 2^20 units).
+    // The launcher's grids are multiples of 8, and of 8 * typesize for a frame with a fused un-shuffle (whose planes are whole units).  Under any
+    // other grid or geometry the units are taken in index order: any order that visits every unit once is correct.  That includes a
+    // byte-shuffled frame that misses the fused order (units no multiple of the typesize, or a grid that is neither a multiple of
+    // 8 * typesize nor covers all units): it had the strided order before and has the index order now, which spreads its planes less evenly
+    // over the XCDs -- hb_launch_lz4_decode builds no such launch, so this is not measured; carrying kp in the fused instances as well cost
+    // the <4,0> instance five more spilled scalar registers (36 against the 31 it may have).
+    // (nunits != 0, so mgrp != 0 below: dec_plan_check leaves the mode at DEC_SERIAL for an index without units, and the kernel has returned.)
+    const uint32_t grid = gridDim.x;
+    const bool fused_order = ush && nunits % (uint32_t)ush == 0u && (grid % (8u * (uint32_t)ush) == 0u || grid >= nunits);
+    const uint32_t nit = fused_order ? nunits : mgrp * 8u;      // work items: the fused order has no padding (whole groups of `ush` units)
+    const bool kp_steps = !ush && (grid & 7u) == 0u;
+    uint32_t kp = 0u, dkp = 0u;
+    if (kp_steps) {
+        const uint32_t Pm = P % mgrp;
+        kp = ((blockIdx.x >> 3) * Pm) % mgrp;
+        dkp = ((grid >> 3) * Pm) % mgrp;
+    }
+    // the unit of work item `it` of pass `ps`, or DEC_NO_UNIT (padding of the last group of 8, a masked plane, past the end)
+    auto unit_at = [&](const uint32_t it, const uint32_t ps, const uint32_t kpv) __attribute__((always_inline)) -> uint32_t {
+        if (fused_order) {
+            // fused un-shuffle: the `ush` units that make up one 4096-element block write interleaved bytes of the same
+            // lines, so they get workgroup ids that are equal mod 8 (same XCD under round-robin placement: the
+            // partial lines meet in one L2) and run close in time; the plane rotates with the pass (planes differ in
+            // cost).  Within a group of 8 blocks, work item (plane j, block b % 8) has index j * 8 + b % 8.
+            const uint32_t T = (uint32_t)ush, nblk = nunits / T;
+            const uint32_t grp = it / (8u * T), r = it % (8u * T);
+            uint32_t b = grp * 8u + (r & 7u), j = ((r >> 3) + ps) % T;
+            if (grp * 8u + 8u > nblk) {                         // ragged last group: plain (b, j) order
+                const uint32_t k = it - grp * 8u * T, nb = nblk - grp * 8u;
+                b = grp * 8u + k % nb; j = k / nb;
+            }
+            if (!((plane_mask >> j) & 1u)) return DEC_NO_UNIT;  // hb_debug_plane_mask: per-plane timing
+            return j * nblk + b;
+        }
+        const uint32_t u = kp_steps ? kpv * 8u + ((it + (it >> 3)) & 7u) : it;
+        return u < nunits ? u : DEC_NO_UNIT;
+    };
+    for (uint32_t it = blockIdx.x, ps = 0u; it < nit;) {
+        const uint32_t it2 = it + grid, ps2 = ps + 1u;
+        uint32_t kp2 = kp + dkp;
+        if (kp2 >= mgrp) kp2 -= mgrp;
+        const uint32_t u = unit_at(it, ps, kp);
+        if (u != DEC_NO_UNIT) {
+            // the unit this wave takes next is known now: this one fetches ahead for it (DecPre)
+            const uint32_t u_next = (DEC_PREFETCH && it2 < nit) ? unit_at(it2, ps2, kp2) : DEC_NO_UNIT;
+            dec_unit<USH, BUN4>(c, u, s_in, s_out, s_tq, lane, u_next, pre);
+        }
+        it = it2; ps = ps2; kp = kp2;
+    }
+#else
     // the unit of work item `it`, or DEC_NO_UNIT (padding of the last group of 8, a masked plane, past the end)
     auto unit_of = [&](const uint32_t it) __attribute__((always_inline)) -> uint32_t {
         if (it >= mgrp * 8u) return DEC_NO_UNIT;
@@ -76,10 +139,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEC_WAVES)))
         const bool fused_order = ush && nunits % (uint32_t)ush == 0u && (gridDim.x % (8u * (uint32_t)ush) == 0u || gridDim.x >= nunits);
         if (fused_order ? it >= nunits : u >= nunits) return DEC_NO_UNIT;
         if (fused_order) {
-            // fused un-shuffle: the `ush` units that make up one 4096-element block write interleaved bytes of the same
-            // lines, so they get workgroup ids that are equal mod 8 (same XCD under round-robin placement: the
-            // partial lines meet in one L2) and run close in time; the plane rotates with the pass (planes differ in
-            // cost).  Within a group of 8 blocks, work item (plane j, block b % 8) has index j * 8 + b % 8.
             const uint32_t T = (uint32_t)ush, nblk = nunits / T;
             const uint32_t grp = it / (8u * T), r = it % (8u * T);
             uint32_t b = grp * 8u + (r & 7u), j = ((r >> 3) + it / gridDim.x) % T;
@@ -92,8 +151,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEC_WAVES)))
         }
         return u;
     };
-    DecCtx c; c.src = src; c.n_src = n_src; c.dst = dst; c.ent = ent; c.plan = plan; c.nbytes = nbytes; c.nunits = nunits; c.bun4 = bun4; c.ush = ush;
-    DecPre pre; pre.u = DEC_NO_UNIT; pre.win = 0u;
     for (uint32_t it = blockIdx.x; it < mgrp * 8u; it += gridDim.x) {
         const uint32_t u = unit_of(it);
         if (u == DEC_NO_UNIT) continue;
@@ -101,6 +158,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(DEC_WAVES)))
         const uint32_t u_next = DEC_PREFETCH ? unit_of(it + gridDim.x) : DEC_NO_UNIT;
         dec_unit<USH, BUN4>(c, u, s_in, s_out, s_tq, lane, u_next, pre);
     }
+#endif
 }
 
 // ---- batches of frames (hb_decompress_frames_batch_dev): the indexed decoder over the units of ALL frames of a batch ----
