@@ -41,6 +41,9 @@ __device__ __forceinline__ uint32_t hb_select_lane(unsigned long long mask, uint
     asm("v_cndmask_b32 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(mask));
     return r;
 }
+// a wave-uniform integer pinned to a scalar register, its origin hidden from the optimiser (which otherwise may fold it into an operation that only
+// the vector unit has and compute everything that follows per lane)
+__device__ __forceinline__ int hb_sgpr(int x) { asm("" : "+s"(x)); return x; }
 
 // all lanes of the wave have finished their LDS traffic up to here, and the compiler may not
 // move LDS accesses across this point (single-wave producer/consumer through LDS).

@@ -75,11 +75,13 @@ def main():
     ap.add_argument("--nofusion", action="store_true", help="HB_OPT_NO_FUSION: separate filter passes (A/B of the fused kernels)")
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--out", default="")
+    ap.add_argument("--passes", type=int, default=1, help="run the whole list of builds this many times, one after the other (rows `name#pK` from the second pass on): "
+                                                          "the difference between a build's own passes is the yardstick for a difference between builds")
     a = ap.parse_args()
     if a.child:
         return child(a)
     res = {}
-    for name in a.names or ["-"]:
+    for key, name in [(n if k == 0 else f"{n}#p{k + 1}", n) for k in range(a.passes) for n in (a.names or ["-"])]:
         env = dict(os.environ)
         if name != "-":
             env["HIPBLOSC_LIB"] = os.path.join(ROOT, "go-blosc_amd", "lib", f"libhipblosc_{name}.so")
@@ -90,20 +92,22 @@ def main():
             cmd.append("--nofusion")
         r = subprocess.run(cmd, env=env, capture_output=True, text=True)
         if r.returncode != 0:
-            res[name] = {"error": (r.stderr or r.stdout)[-600:]}
+            res[key] = {"error": (r.stderr or r.stdout)[-600:]}
         else:
-            res[name] = json.loads(r.stdout.strip().splitlines()[-1])
-        row = res[name]
+            res[key] = json.loads(r.stdout.strip().splitlines()[-1])
+        row = res[key]
         for case, v in row.items():
             if case == "error":
-                print(f"{name:24s} ERROR {v}", flush=True)
-                continue
+                print(f"{key:24s} ERROR {v}", flush=True)
+                break
             st = v["stages"]
             keys = ["filter_shuffle", "filter_bitshuffle", "k_match_fused", "k_match", "k_tiles", "k_scan", "k_stitch", "k_dec_plan", "k_dec_indexed", "k_dec_serial"]
             if a.no_trailer:
                 keys = list(st.keys())                                   # the discovery's kernels too
             s = " ".join(f"{k[2:] if k.startswith('k_') else k}={st[k]:.3f}" for k in keys if k in st)
-            print(f"{name:24s} {case:10s} ok={int(v['ok'])} par={v['parallel']} ratio={v['ratio']:.4f} step={v['ms_step']:.3f}ms {v['GBps']:.0f}GB/s | {s}", flush=True)
+            print(f"{key:24s} {case:10s} ok={int(v['ok'])} par={v['parallel']} ratio={v['ratio']:.4f} step={v['ms_step']:.3f}ms {v['GBps']:.0f}GB/s | {s}", flush=True)
+        if "error" in row:
+            break                                         # a crashed build (a GPU fault, say): nothing more is started on the GPU in this call
     if a.out:
         os.makedirs(os.path.dirname(a.out) or ".", exist_ok=True)
         json.dump(res, open(a.out, "w"), indent=1)

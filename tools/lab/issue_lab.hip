@@ -97,6 +97,44 @@ __global__ __launch_bounds__(64) void k_v_cndmask_vcc_set(Stamp *st, uint32_t *s
     END(0u, v0 ^ v1 ^ v2 ^ v3 ^ v4 ^ v5 ^ v6 ^ v7);
 }
 
+// ---- other shapes of the VCC select (the probes above are one shape: destination = first source, VCC never written by a compare) ----
+// the short form with a destination distinct from both sources
+#define I_CNDM_D(k) "v_cndmask_b32_e32 %" #k ", %8, %9, vcc\n"
+V_KERNEL(k_v_cndmask_dst, I_CNDM_D, "memory")
+// the VOP3 encoding with vcc named as the mask
+#define I_CNDM_E64(k) "v_cndmask_b32_e64 %" #k ", %" #k ", %8, vcc\n"
+V_KERNEL(k_v_cndmask_e64_vcc, I_CNDM_E64, "memory")
+// the short form with VCC written by a vector compare at the head of every iteration (as the compiler's code does: v_cmp, then the selects)
+__global__ __launch_bounds__(64) void k_v_cndmask_vcmp(Stamp *st, uint32_t *sink, uint32_t a, uint32_t b, int iters) {
+    uint32_t v0 = threadIdx.x, v1 = v0 + 1, v2 = v0 + 2, v3 = v0 + 3, v4 = v0 + 4, v5 = v0 + 5, v6 = v0 + 6, v7 = v0 + 7;
+    const uint32_t va = a + threadIdx.x, vb = b ^ threadIdx.x;
+    BEGIN();
+    for (int it = 0; it < iters; it++)
+        asm volatile("v_cmp_lt_u32_e32 vcc, %0, %9\n" R128(I_CNDM) : "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3), "+v"(v4), "+v"(v5), "+v"(v6), "+v"(v7)
+                     : "v"(va), "v"(vb) : "vcc", "memory");
+    END(0u, v0 ^ v1 ^ v2 ^ v3 ^ v4 ^ v5 ^ v6 ^ v7);
+}
+// (a kernel whose iteration is a given string of 128 instructions on the same operands as V_KERNEL's)
+#define V_KERNEL_STR(NAME, BODY, ...)                                                                                            \
+    __global__ __launch_bounds__(64) void NAME(Stamp *st, uint32_t *sink, uint32_t a, uint32_t b, int iters) {                   \
+        uint32_t v0 = threadIdx.x, v1 = v0 + 1, v2 = v0 + 2, v3 = v0 + 3, v4 = v0 + 4, v5 = v0 + 5, v6 = v0 + 6, v7 = v0 + 7;    \
+        const uint32_t va = a + threadIdx.x, vb = b ^ threadIdx.x;                                                               \
+        BEGIN();                                                                                                                 \
+        for (int it = 0; it < iters; it++)                                                                                       \
+            asm volatile(BODY : "+v"(v0), "+v"(v1), "+v"(v2), "+v"(v3), "+v"(v4), "+v"(v5), "+v"(v6), "+v"(v7)                   \
+                         : "v"(va), "v"(vb) : __VA_ARGS__);                                                                      \
+        END(0u, v0 ^ v1 ^ v2 ^ v3 ^ v4 ^ v5 ^ v6 ^ v7);                                                                          \
+    }
+// one compare into VCC per select, as in a chain of `x = c ? a : b` on different conditions: 64 pairs per iteration
+#define I_CMP_CNDM(k) "v_cmp_lt_u32_e32 vcc, %" #k ", %9\nv_cndmask_b32_e32 %" #k ", %" #k ", %8, vcc\n"
+#define R64(I) R8(I) R8(I) R8(I) R8(I) R8(I) R8(I) R8(I) R8(I)
+V_KERNEL_STR(k_v_cmp_cndmask_pairs, R64(I_CMP_CNDM), "vcc", "memory")
+// the short form interleaved 1:1 with independent v_and_b32: selects on accumulators 0..3, ands on 4..7, 64 of each per iteration
+#define I_CA(k, j) "v_cndmask_b32_e32 %" #k ", %" #k ", %8, vcc\nv_and_b32 %" #j ", %8, %" #j "\n"
+#define CA4 I_CA(0, 4) I_CA(1, 5) I_CA(2, 6) I_CA(3, 7)
+#define CA64 CA4 CA4 CA4 CA4 CA4 CA4 CA4 CA4 CA4 CA4 CA4 CA4 CA4 CA4 CA4 CA4
+V_KERNEL_STR(k_v_cndmask_and_mix, CA64, "memory")
+
 // 64-bit shift: 8 accumulator pairs
 #define I_LSHR64(k) "v_lshrrev_b64 %" #k ", %8, %" #k "\n"
 __global__ __launch_bounds__(64) void k_v_lshrrev_b64(Stamp *st, uint32_t *sink, uint32_t a, uint32_t b, int iters) {
@@ -199,6 +237,9 @@ static const Probe PROBES[] = {
     {"v_cndmask_b32 sgpr pair mask", "vector", k_v_cndmask_sgpr}, {"v_and_b32 sgpr operand", "vector", k_v_and_sgpr}, {"v_lshrrev_b64", "vector", k_v_lshrrev_b64},
     {"v_ffbl_b32", "vector", k_v_ffbl}, {"v_cmp_eq_u32 vcc", "vector", k_v_cmp_vcc}, {"v_cmp_eq_u32 sgpr pair", "vector", k_v_cmp_sgpr},
     {"v_readlane_b32", "vector", k_v_readlane},
+    {"v_cndmask_b32_e32 vcc, destination distinct from both sources", "vector", k_v_cndmask_dst}, {"v_cndmask_b32_e64 with vcc named as the mask", "vector", k_v_cndmask_e64_vcc},
+    {"v_cndmask_b32_e32 vcc (set by one v_cmp per iteration)", "vector", k_v_cndmask_vcmp}, {"v_cmp_lt_u32 vcc + v_cndmask_b32_e32 vcc, pairs", "vector", k_v_cmp_cndmask_pairs},
+    {"v_cndmask_b32_e32 vcc + v_and_b32, 1:1", "vector", k_v_cndmask_and_mix},
     {"s_and_b64", "scalar", k_s_and_b64}, {"s_add_i32", "scalar", k_s_add_i32}, {"s_bcnt1_i32_b64", "scalar", k_s_bcnt1_i32_b64},
     {"s_cselect_b64", "scalar", k_s_cselect_b64}, {"s_bitset1_b64", "scalar", k_s_bitset1_b64},
     {"s_cbranch_scc taken", "branch", k_s_cbranch_taken}, {"s_cbranch_scc not taken", "branch", k_s_cbranch_not_taken},
