@@ -963,18 +963,81 @@ int hb_cblosc_compress_boxes_batch(int nframes, const hb_cblosc_src_box *boxes, 
     catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
 }
 
-// Many update boxes to new C-Blosc-1 frames (include/hipblosc.h).  cbxu_host_plan (hb_cblosc_upd_box_batch.h) answers what has no chunk and says
-// which jobs the batch carries: their old frames go up (adjacent ones in one copy), their boxes are packed C-contiguously, items only, and
-// go up in one copy; the device form runs once with the packed strides.  Whatever the batch does not carry, and whatever did not end with
-// status 0 on the device, is answered on the host: hb_cblosc_decompress of the old frame (or the fill), the naive overlay, hb_cblosc_compress.
-static int cbxu_host_call(int njobs, const hb_cblosc_upd_box *boxes, const void *const *old, const size_t *old_n, const void *const *src, void *const *dst,
-                          const size_t *cap, int64_t *rc, const void *fill, int shuffle, int typesize, int device) {
+// Many updates to new C-Blosc-1 frames (include/hipblosc.h): boxes, selections and points go one way.  The kind's plan (cbxu_host_plan_ of
+// hb_cblosc_upd_box_batch.h behind each) answers what has no chunk and says which jobs the batch carries: their old frames go up (adjacent
+// ones in one copy), their source items are packed, items only, and go up in one copy; the device form runs once over the packed jobs.
+// Whatever the batch does not carry, and whatever did not end with status 0 on the device, is answered on the host: hb_cblosc_decompress of
+// the old frame (or the fill), the kind's naive loops, hb_cblosc_compress.
+// A kind says what differs: `refused` (what the call as a whole refuses beyond the common arguments), `plan`, `scatter` (the naive loops over a
+// chunk that holds the base), `pack` (one carried job's items as they go up), and `workspace` / `run` (the device form over the packed jobs).
+extern "C++" {
+struct CbxuHostKind {                    // boxes: packed C-contiguously, the device form gets the packed strides
+    typedef CbxuHostPlan Plan;
+    const hb_cblosc_upd_box *jobs;
+    bool refused(int) const { return false; }
+    void plan(int njobs, const void *const *old, const size_t *old_n, const void *const *src, void *const *dst, int typesize, unsigned accept, Plan &P) {
+        cbxu_host_plan(njobs, jobs, old, old_n, src, dst, typesize, accept, P);
+    }
+    void scatter(const Plan &P, int k, int, const uint8_t *src, uint8_t *chunk) const { cbxu_overlay_host(P.geom[(size_t)k], src, chunk); }
+    void pack(const Plan &P, int k, int, const uint8_t *src, uint8_t *out) const { cbxe_pack_box(P.geom[(size_t)k].e, src, out); }
+    size_t workspace(int m, const Plan &P, const size_t *on, int shuffle, int typesize) const {
+        return hb_cblosc_update_boxes_batch_workspace(m, P.pb.data(), P.hd.data(), on, shuffle, typesize);
+    }
+    int run(int m, const Plan &P, const void *const *po, const size_t *on, const void *const *ps, void *const *pf, const void *fill, int shuffle, int typesize, void *d_work,
+            size_t wb, hb_result *d_res) const {
+        return hb_cblosc_update_boxes_batch_device(m, P.pb.data(), P.hd.data(), po, on, ps, pf, P.caps.data(), fill, shuffle, typesize, d_work, wb, d_res, nullptr);
+    }
+};
+struct CbiuHostKind {                    // selections: packed C-contiguously in selection order, the device form gets the packed strides and no source list
+    typedef CbiuHostPlan Plan;
+    const hb_cblosc_upd_index *jobs;
+    const int64_t *index;
+    int64_t nindex;
+    bool refused(int njobs) const { return cbiu_call_refused(njobs, jobs, index, nindex); }
+    void plan(int njobs, const void *const *old, const size_t *old_n, const void *const *src, void *const *dst, int typesize, unsigned accept, Plan &P) {
+        cbiu_host_plan(njobs, jobs, index, nindex, old, old_n, src, dst, typesize, accept, P);
+    }
+    void scatter(const Plan &, int k, int typesize, const uint8_t *src, uint8_t *chunk) const { cbiu_scatter_host(jobs[k], index, typesize, src, chunk); }
+    void pack(const Plan &, int k, int typesize, const uint8_t *src, uint8_t *out) const { cbiu_pack_host(jobs[k], index, typesize, src, out); }
+    size_t workspace(int m, const Plan &P, const size_t *on, int shuffle, int typesize) const {
+        return hb_cblosc_update_index_batch_workspace(m, P.pb.data(), index, nindex, P.hd.data(), on, shuffle, typesize);
+    }
+    int run(int m, const Plan &P, const void *const *po, const size_t *on, const void *const *ps, void *const *pf, const void *fill, int shuffle, int typesize, void *d_work,
+            size_t wb, hb_result *d_res) const {
+        return hb_cblosc_update_index_batch_device(m, P.pb.data(), index, nindex, P.hd.data(), po, on, ps, pf, P.caps.data(), fill, shuffle, typesize, d_work, wb, d_res, nullptr);
+    }
+};
+struct CbpuHostKind {                    // points: packed in point order, the device form runs over `pts` (the carried jobs' points, src == p)
+    typedef CbpuHostPlan Plan;
+    const hb_cblosc_upd_point_job *jobs;
+    const hb_cblosc_upd_point *points;
+    int64_t npoints;
+    std::vector<hb_cblosc_upd_point> pts;
+    bool refused(int njobs) const { return cbpu_call_refused(njobs, jobs, points, npoints); }
+    void plan(int njobs, const void *const *old, const size_t *old_n, const void *const *src, void *const *dst, int typesize, unsigned accept, Plan &P) {
+        cbpu_host_plan(njobs, jobs, points, npoints, old, old_n, src, dst, typesize, accept, P, pts);
+    }
+    void scatter(const Plan &, int k, int typesize, const uint8_t *src, uint8_t *chunk) const { cbpu_scatter_host(jobs[k], points, typesize, src, chunk); }
+    void pack(const Plan &, int k, int typesize, const uint8_t *src, uint8_t *out) const { cbpu_pack_host(jobs[k], points, typesize, src, out); }
+    size_t workspace(int m, const Plan &P, const size_t *on, int shuffle, int typesize) const {
+        return hb_cblosc_update_points_batch_workspace(m, P.pb.data(), pts.data(), (int64_t)pts.size(), P.hd.data(), on, shuffle, typesize);
+    }
+    int run(int m, const Plan &P, const void *const *po, const size_t *on, const void *const *ps, void *const *pf, const void *fill, int shuffle, int typesize, void *d_work,
+            size_t wb, hb_result *d_res) const {
+        return hb_cblosc_update_points_batch_device(m, P.pb.data(), pts.data(), (int64_t)pts.size(), P.hd.data(), po, on, ps, pf, P.caps.data(), fill, shuffle, typesize, d_work,
+                                                    wb, d_res, nullptr);
+    }
+};
+template <class KIND>
+static int cbu_host_call(KIND kind, int njobs, const void *const *old, const size_t *old_n, const void *const *src, void *const *dst, const size_t *cap, int64_t *rc,
+                         const void *fill, int shuffle, int typesize, int device) {
     CbPolicyPin pin;                                                       // (hb_cblosc_set_compressor: one policy for the device call and for every one-frame call behind it)
     if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
     if (njobs == 0) return HB_OK;
-    if (!boxes || !old || !old_n || !src || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
-    CbxuHostPlan P;
-    cbxu_host_plan(njobs, boxes, old, old_n, src, dst, typesize, hb_cblosc_accepted(), P);
+    if (!kind.jobs || !old || !old_n || !src || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
+    if (kind.refused(njobs)) return HB_ERR_BAD_ARG;
+    typename KIND::Plan P;
+    kind.plan(njobs, old, old_n, src, dst, typesize, hb_cblosc_accepted(), P);
     uint8_t table[CBXE_FILL_BYTES];
     cbxe_fill_table(fill, typesize, table);
     auto single = [&](int k) {
@@ -988,11 +1051,11 @@ static int cbxu_host_call(int njobs, const hb_cblosc_upd_box *boxes, const void 
             if ((int)h.typesize != typesize || (uint64_t)h.nbytes != g.e.nbytes) { rc[k] = HB_ERR_BAD_ARG; return; }
             const int64_t drc = hb_cblosc_decompress(old[k], old_n[k], chunk.data(), nb, device);
             if (drc < 0) { rc[k] = drc; return; }
-        } else if (P.base[(size_t)k] == CBXU_FILL) {
+        } else if (P.base[(size_t)k] == CBXU_FILL) {                      // (else no base: the job writes every byte.  Points always have a base -- cbpu_refusal -- so theirs is "else: fill")
             for (size_t j = 0; j < nb; j++) chunk[j] = table[j % (size_t)typesize];
         }
         if (!src[k] && g.e.src_bytes) { rc[k] = hb_cblosc_compress(nullptr, nb ? nb : 1, dst[k], cap[k], shuffle, typesize, device); return; }      // (no chunk to assemble: its refusal)
-        if (nb) cbxu_overlay_host(g, (const uint8_t *)src[k], chunk.data());
+        if (nb && g.e.src_bytes) kind.scatter(P, k, typesize, (const uint8_t *)src[k], chunk.data());
         rc[k] = hb_cblosc_compress(chunk.data(), nb, dst[k], cap[k], shuffle, typesize, device);
     };
     const int m = (int)P.carried.size();
@@ -1005,14 +1068,12 @@ static int cbxu_host_call(int njobs, const hb_cblosc_upd_box *boxes, const void 
     if (m == 0) return HB_OK;
     auto rest_single = [&]() { for (int k : P.carried) single(k); return HB_OK; };
     if (hb_select_device(device) != HB_OK) return rest_single();
-    std::vector<hb_cblosc_header> hd((size_t)m);
     std::vector<size_t> on((size_t)m, 0);
     for (int i = 0; i < m; i++) {
         const int k = P.carried[(size_t)i];
-        hd[(size_t)i] = P.hd[(size_t)i];
-        on[(size_t)i] = P.base[(size_t)k] == CBXU_OLD ? old_n[k] : 0;     // (a whole box: its old frame is not looked at, here or there)
+        on[(size_t)i] = P.base[(size_t)k] == CBXU_OLD ? old_n[k] : 0;     // (no base: its old frame is not looked at, here or there)
     }
-    const size_t wb = hb_cblosc_update_boxes_batch_workspace(m, P.pb.data(), hd.data(), on.data(), shuffle, typesize);
+    const size_t wb = kind.workspace(m, P, on.data(), shuffle, typesize);
     if (!wb) return rest_single();                                       // (a batch beyond the 32-bit limits: one call per chunk is still right)
     auto fail_all = [&]() { for (int k : P.carried) rc[k] = HB_ERR_HIP; return HB_OK; };
     Scratch sc(device);
@@ -1026,7 +1087,7 @@ static int cbxu_host_call(int njobs, const hb_cblosc_upd_box *boxes, const void 
     bool first_old = true;
     for (int i = 0; i < m; i++) {
         const int k = P.carried[(size_t)i];
-        cbxe_pack_box(P.geom[(size_t)k].e, (const uint8_t *)src[k], packed.data() + P.ioff[(size_t)i]);
+        if (P.geom[(size_t)k].e.src_bytes) kind.pack(P, k, typesize, (const uint8_t *)src[k], packed.data() + P.ioff[(size_t)i]);
         ps[(size_t)i] = d_in + P.ioff[(size_t)i]; pf[(size_t)i] = d_out + P.ooff[(size_t)i];
         if (P.base[(size_t)k] != CBXU_OLD) continue;
         po[(size_t)i] = d_old + P.foff[(size_t)i];
@@ -1036,192 +1097,28 @@ static int cbxu_host_call(int njobs, const hb_cblosc_upd_box *boxes, const void 
         } else if (old_n[k] && hipMemcpyAsync(d_old + P.foff[(size_t)i], old[k], old_n[k], hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
     }
     if (P.in_bytes && hipMemcpyAsync(d_in, packed.data(), P.in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-    const int st = hb_cblosc_update_boxes_batch_device(m, P.pb.data(), hd.data(), po.data(), on.data(), ps.data(), pf.data(), P.caps.data(), fill, shuffle, typesize,
-                                                       d_work, wb, (hb_result *)d_res, nullptr);
+    const int st = kind.run(m, P, po.data(), on.data(), ps.data(), pf.data(), fill, shuffle, typesize, d_work, wb, (hb_result *)d_res);
     if (st) { (void)hipStreamSynchronize(nullptr); return rest_single(); }     // (`packed` is pageable: the copy has to be over before it goes)
     return cbe_host_download(P.carried, pf, d_res, dst, cap, rc, sc, single);
 }
+}  // extern "C++"
 // (host tables that do not fit into memory: the batch is one the caller has to split -- no exception crosses the C ABI)
 int hb_cblosc_update_boxes_batch(int njobs, const hb_cblosc_upd_box *boxes, const void *const *old, const size_t *old_n, const void *const *src, void *const *dst,
                                  const size_t *cap, int64_t *rc, const void *fill, int shuffle, int typesize, int device) {
-    try { return cbxu_host_call(njobs, boxes, old, old_n, src, dst, cap, rc, fill, shuffle, typesize, device); }
+    try { return cbu_host_call(CbxuHostKind{boxes}, njobs, old, old_n, src, dst, cap, rc, fill, shuffle, typesize, device); }
     catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
 }
-
-// Many selection updates to new C-Blosc-1 frames (include/hipblosc.h).  cbiu_host_plan (hb_cblosc_upd_index_batch.h) answers what has no chunk
-// and says which jobs the batch carries: their old frames go up (adjacent ones in one copy), their selected source items are packed
-// C-contiguously in selection order and go up in one copy; the device form runs once with the packed strides and no source list.  Whatever
-// the batch does not carry, and whatever did not end with status 0 on the device, is answered on the host: hb_cblosc_decompress of the old
-// frame (or the fill), the naive loops, hb_cblosc_compress.
-static int cbiu_host_call(int njobs, const hb_cblosc_upd_index *jobs, const int64_t *index, int64_t nindex, const void *const *old, const size_t *old_n,
-                          const void *const *src, void *const *dst, const size_t *cap, int64_t *rc, const void *fill, int shuffle, int typesize, int device) {
-    CbPolicyPin pin;                                                       // (hb_cblosc_set_compressor: one policy for the device call and for every one-frame call behind it)
-    if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
-    if (njobs == 0) return HB_OK;
-    if (!jobs || !old || !old_n || !src || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
-    if (cbiu_call_refused(njobs, jobs, index, nindex)) return HB_ERR_BAD_ARG;
-    CbiuHostPlan P;
-    cbiu_host_plan(njobs, jobs, index, nindex, old, old_n, src, dst, typesize, hb_cblosc_accepted(), P);
-    uint8_t table[CBXE_FILL_BYTES];
-    cbxe_fill_table(fill, typesize, table);
-    auto single = [&](int k) {
-        const CbxuGeom &g = P.geom[(size_t)k];
-        const size_t nb = (size_t)g.e.nbytes;
-        std::vector<uint8_t> chunk(nb);
-        if (P.base[(size_t)k] == CBXU_OLD) {                              // the decode's answer comes first
-            hb_cblosc_header h;
-            const int prc = hb_cblosc_parse_header(old[k], old_n[k], &h);
-            if (prc) { rc[k] = prc; return; }
-            if ((int)h.typesize != typesize || (uint64_t)h.nbytes != g.e.nbytes) { rc[k] = HB_ERR_BAD_ARG; return; }
-            const int64_t drc = hb_cblosc_decompress(old[k], old_n[k], chunk.data(), nb, device);
-            if (drc < 0) { rc[k] = drc; return; }
-        } else if (P.base[(size_t)k] == CBXU_FILL) {
-            for (size_t j = 0; j < nb; j++) chunk[j] = table[j % (size_t)typesize];
-        }
-        if (!src[k] && g.e.src_bytes) { rc[k] = hb_cblosc_compress(nullptr, nb ? nb : 1, dst[k], cap[k], shuffle, typesize, device); return; }      // (no chunk to assemble: its refusal)
-        if (nb && g.e.src_bytes) cbiu_scatter_host(jobs[k], index, typesize, (const uint8_t *)src[k], chunk.data());
-        rc[k] = hb_cblosc_compress(chunk.data(), nb, dst[k], cap[k], shuffle, typesize, device);
-    };
-    const int m = (int)P.carried.size();
-    std::vector<uint8_t> carried((size_t)njobs, 0);
-    for (int k : P.carried) carried[(size_t)k] = 1;
-    for (int k = 0; k < njobs; k++) {
-        if (P.status[(size_t)k]) rc[k] = P.status[(size_t)k];
-        else if (!carried[(size_t)k]) single(k);
-    }
-    if (m == 0) return HB_OK;
-    auto rest_single = [&]() { for (int k : P.carried) single(k); return HB_OK; };
-    if (hb_select_device(device) != HB_OK) return rest_single();
-    std::vector<hb_cblosc_header> hd((size_t)m);
-    std::vector<size_t> on((size_t)m, 0);
-    for (int i = 0; i < m; i++) {
-        const int k = P.carried[(size_t)i];
-        hd[(size_t)i] = P.hd[(size_t)i];
-        on[(size_t)i] = P.base[(size_t)k] == CBXU_OLD ? old_n[k] : 0;     // (a whole chunk: its old frame is not looked at, here or there)
-    }
-    const size_t wb = hb_cblosc_update_index_batch_workspace(m, P.pb.data(), index, nindex, hd.data(), on.data(), shuffle, typesize);
-    if (!wb) return rest_single();                                       // (a batch beyond the 32-bit limits: one call per chunk is still right)
-    auto fail_all = [&]() { for (int k : P.carried) rc[k] = HB_ERR_HIP; return HB_OK; };
-    Scratch sc(device);
-    uint8_t *d_in = sc.get(P.in_bytes + 256), *d_old = sc.get(P.old_bytes + 256), *d_out = sc.get(P.out_bytes + 256), *d_work = sc.get(wb),
-            *d_res = sc.get((size_t)m * sizeof(hb_result));
-    if (!d_in || !d_old || !d_out || !d_work || !d_res) return fail_all();
-    d_in += (16u - ((uintptr_t)d_in & 15u)) & 15u;                       // (the plan's offsets are multiples of 16: so are the addresses)
-    d_old += (16u - ((uintptr_t)d_old & 15u)) & 15u;
-    std::vector<uint8_t> packed(P.in_bytes, 0);
-    std::vector<const void *> ps((size_t)m), po((size_t)m, nullptr); std::vector<void *> pf((size_t)m);
-    bool first_old = true;
-    for (int i = 0; i < m; i++) {
-        const int k = P.carried[(size_t)i];
-        if (P.geom[(size_t)k].e.src_bytes) cbiu_pack_host(jobs[k], index, typesize, (const uint8_t *)src[k], packed.data() + P.ioff[(size_t)i]);
-        ps[(size_t)i] = d_in + P.ioff[(size_t)i]; pf[(size_t)i] = d_out + P.ooff[(size_t)i];
-        if (P.base[(size_t)k] != CBXU_OLD) continue;
-        po[(size_t)i] = d_old + P.foff[(size_t)i];
-        if (P.span_old) {
-            if (first_old && hipMemcpyAsync(d_old, old[k], P.old_bytes - 64, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-            first_old = false;
-        } else if (old_n[k] && hipMemcpyAsync(d_old + P.foff[(size_t)i], old[k], old_n[k], hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-    }
-    if (P.in_bytes && hipMemcpyAsync(d_in, packed.data(), P.in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-    const int st = hb_cblosc_update_index_batch_device(m, P.pb.data(), index, nindex, hd.data(), po.data(), on.data(), ps.data(), pf.data(), P.caps.data(), fill, shuffle,
-                                                       typesize, d_work, wb, (hb_result *)d_res, nullptr);
-    if (st) { (void)hipStreamSynchronize(nullptr); return rest_single(); }     // (`packed` is pageable: the copy has to be over before it goes)
-    return cbe_host_download(P.carried, pf, d_res, dst, cap, rc, sc, single);
-}
-// (host tables that do not fit into memory: the batch is one the caller has to split -- no exception crosses the C ABI)
 int hb_cblosc_update_index_batch(int njobs, const hb_cblosc_upd_index *jobs, const int64_t *index, int64_t nindex, const void *const *old, const size_t *old_n,
                                  const void *const *src, void *const *dst, const size_t *cap, int64_t *rc, const void *fill, int shuffle, int typesize, int device) {
-    try { return cbiu_host_call(njobs, jobs, index, nindex, old, old_n, src, dst, cap, rc, fill, shuffle, typesize, device); }
+    try { return cbu_host_call(CbiuHostKind{jobs, index, nindex}, njobs, old, old_n, src, dst, cap, rc, fill, shuffle, typesize, device); }
     catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
 }
-
-// Many point updates to new C-Blosc-1 frames (include/hipblosc.h).  cbpu_host_plan (hb_cblosc_upd_point_batch.h) answers what has no chunk and
-// says which jobs the batch carries: their old frames go up (adjacent ones in one copy), their source items are packed in point order and go
-// up in one copy; the device form runs once over points with src == p.  Whatever the batch does not carry, and whatever did not end with
-// status 0 on the device, is answered on the host: hb_cblosc_decompress of the old frame (or the fill), the naive loop, hb_cblosc_compress.
-static int cbpu_host_call(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints, const void *const *old, const size_t *old_n,
-                          const void *const *src, void *const *dst, const size_t *cap, int64_t *rc, const void *fill, int shuffle, int typesize, int device) {
-    CbPolicyPin pin;                                                       // (hb_cblosc_set_compressor: one policy for the device call and for every one-frame call behind it)
-    if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
-    if (njobs == 0) return HB_OK;
-    if (!jobs || !old || !old_n || !src || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
-    if (cbpu_call_refused(njobs, jobs, points, npoints)) return HB_ERR_BAD_ARG;
-    CbpuHostPlan P;
-    std::vector<hb_cblosc_upd_point> pts;
-    cbpu_host_plan(njobs, jobs, points, npoints, old, old_n, src, dst, typesize, hb_cblosc_accepted(), P, pts);
-    uint8_t table[CBXE_FILL_BYTES];
-    cbxe_fill_table(fill, typesize, table);
-    auto single = [&](int k) {
-        const CbxuGeom &g = P.geom[(size_t)k];
-        const size_t nb = (size_t)g.e.nbytes;
-        std::vector<uint8_t> chunk(nb);
-        if (P.base[(size_t)k] == CBXU_OLD) {                              // the decode's answer comes first
-            hb_cblosc_header h;
-            const int prc = hb_cblosc_parse_header(old[k], old_n[k], &h);
-            if (prc) { rc[k] = prc; return; }
-            if ((int)h.typesize != typesize || (uint64_t)h.nbytes != g.e.nbytes) { rc[k] = HB_ERR_BAD_ARG; return; }
-            const int64_t drc = hb_cblosc_decompress(old[k], old_n[k], chunk.data(), nb, device);
-            if (drc < 0) { rc[k] = drc; return; }
-        } else {
-            for (size_t j = 0; j < nb; j++) chunk[j] = table[j % (size_t)typesize];
-        }
-        if (!src[k] && g.e.src_bytes) { rc[k] = hb_cblosc_compress(nullptr, nb ? nb : 1, dst[k], cap[k], shuffle, typesize, device); return; }      // (no chunk to assemble: its refusal)
-        if (nb && g.e.src_bytes) cbpu_scatter_host(jobs[k], points, typesize, (const uint8_t *)src[k], chunk.data());
-        rc[k] = hb_cblosc_compress(chunk.data(), nb, dst[k], cap[k], shuffle, typesize, device);
-    };
-    const int m = (int)P.carried.size();
-    std::vector<uint8_t> carried((size_t)njobs, 0);
-    for (int k : P.carried) carried[(size_t)k] = 1;
-    for (int k = 0; k < njobs; k++) {
-        if (P.status[(size_t)k]) rc[k] = P.status[(size_t)k];
-        else if (!carried[(size_t)k]) single(k);
-    }
-    if (m == 0) return HB_OK;
-    auto rest_single = [&]() { for (int k : P.carried) single(k); return HB_OK; };
-    if (hb_select_device(device) != HB_OK) return rest_single();
-    std::vector<hb_cblosc_header> hd((size_t)m);
-    std::vector<size_t> on((size_t)m, 0);
-    for (int i = 0; i < m; i++) {
-        const int k = P.carried[(size_t)i];
-        hd[(size_t)i] = P.hd[(size_t)i];
-        on[(size_t)i] = P.base[(size_t)k] == CBXU_OLD ? old_n[k] : 0;
-    }
-    const int64_t npk = (int64_t)pts.size();
-    const size_t wb = hb_cblosc_update_points_batch_workspace(m, P.pb.data(), pts.data(), npk, hd.data(), on.data(), shuffle, typesize);
-    if (!wb) return rest_single();                                       // (a batch beyond the 32-bit limits: one call per chunk is still right)
-    auto fail_all = [&]() { for (int k : P.carried) rc[k] = HB_ERR_HIP; return HB_OK; };
-    Scratch sc(device);
-    uint8_t *d_in = sc.get(P.in_bytes + 256), *d_old = sc.get(P.old_bytes + 256), *d_out = sc.get(P.out_bytes + 256), *d_work = sc.get(wb),
-            *d_res = sc.get((size_t)m * sizeof(hb_result));
-    if (!d_in || !d_old || !d_out || !d_work || !d_res) return fail_all();
-    d_in += (16u - ((uintptr_t)d_in & 15u)) & 15u;                       // (the plan's offsets are multiples of 16: so are the addresses)
-    d_old += (16u - ((uintptr_t)d_old & 15u)) & 15u;
-    std::vector<uint8_t> packed(P.in_bytes, 0);
-    std::vector<const void *> ps((size_t)m), po((size_t)m, nullptr); std::vector<void *> pf((size_t)m);
-    bool first_old = true;
-    for (int i = 0; i < m; i++) {
-        const int k = P.carried[(size_t)i];
-        if (P.geom[(size_t)k].e.src_bytes) cbpu_pack_host(jobs[k], points, typesize, (const uint8_t *)src[k], packed.data() + P.ioff[(size_t)i]);
-        ps[(size_t)i] = d_in + P.ioff[(size_t)i]; pf[(size_t)i] = d_out + P.ooff[(size_t)i];
-        if (P.base[(size_t)k] != CBXU_OLD) continue;
-        po[(size_t)i] = d_old + P.foff[(size_t)i];
-        if (P.span_old) {
-            if (first_old && hipMemcpyAsync(d_old, old[k], P.old_bytes - 64, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-            first_old = false;
-        } else if (old_n[k] && hipMemcpyAsync(d_old + P.foff[(size_t)i], old[k], old_n[k], hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-    }
-    if (P.in_bytes && hipMemcpyAsync(d_in, packed.data(), P.in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-    const int st = hb_cblosc_update_points_batch_device(m, P.pb.data(), pts.data(), npk, hd.data(), po.data(), on.data(), ps.data(), pf.data(), P.caps.data(), fill, shuffle,
-                                                        typesize, d_work, wb, (hb_result *)d_res, nullptr);
-    if (st) { (void)hipStreamSynchronize(nullptr); return rest_single(); }     // (`packed` is pageable: the copy has to be over before it goes)
-    return cbe_host_download(P.carried, pf, d_res, dst, cap, rc, sc, single);
-}
-// (host tables that do not fit into memory: the batch is one the caller has to split -- no exception crosses the C ABI)
 int hb_cblosc_update_points_batch(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints, const void *const *old,
                                   const size_t *old_n, const void *const *src, void *const *dst, const size_t *cap, int64_t *rc, const void *fill, int shuffle, int typesize,
                                   int device) {
-    try { return cbpu_host_call(njobs, jobs, points, npoints, old, old_n, src, dst, cap, rc, fill, shuffle, typesize, device); }
+    try { return cbu_host_call(CbpuHostKind{jobs, points, npoints, {}}, njobs, old, old_n, src, dst, cap, rc, fill, shuffle, typesize, device); }
     catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
 }
+
 
 }  // extern "C"

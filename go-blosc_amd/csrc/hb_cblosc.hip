@@ -2043,61 +2043,40 @@ int hb_cblosc_compress_boxes_batch_device(int nframes, const hb_cblosc_src_box *
     return cbe_launch_batch(nframes, B.E, shuffle, typesize, policy, w + L.enc, d_results, s);
 }
 
-// ---- many update boxes, one set of launches (include/hipblosc.h; the host side is hb_cblosc_upd_box_batch.h) ----
-size_t hb_cblosc_update_boxes_batch_workspace(int njobs, const hb_cblosc_upd_box *boxes, const hb_cblosc_header *old_hdrs, const size_t *old_n, int shuffle, int typesize) {
-    return cbxu_workspace(njobs, boxes, old_hdrs, old_n, shuffle, typesize, hb_cblosc_accepted());
-}
-
-int hb_cblosc_update_boxes_batch_device(int njobs, const hb_cblosc_upd_box *boxes, const hb_cblosc_header *old_hdrs, const void *const *d_old, const size_t *old_n,
-                                        const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill, int shuffle, int typesize,
-                                        void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
-    const unsigned policy = hb_cblosc_policy();                           // (hb_cblosc_set_compressor, read once: one call, one policy)
-    if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
-    if (njobs == 0) return HB_OK;
-    if (!boxes || !old_hdrs || !d_old || !old_n || !d_src || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
-    uint8_t *w = (uint8_t *)d_work;
-    const unsigned accept = hb_cblosc_accepted();                         // (read once: the query below judges the frames as the call does)
-    CbxuBatch B;
-    const int rc = cbxu_prepare(njobs, boxes, old_hdrs, d_old, old_n, d_src, d_frame, cap, fill, shuffle, typesize, w, accept, B);
-    if (rc) return rc;
+// ---- the update batches: boxes, selections, points and prepared point selections go one way.  Each is the box updates' batch (CbxuBatch: fill
+// bases, old-frame bases, the encoder) plus a stage that puts the source's items over the staged bases. ----
+// A prepared update batch on the device: one upload under `label` (the stage's records by `put`, the finish list, and behind them the gather's
+// records, prefix and fill table: the buffer is read before the call returns), the fill bases and the whole chunks that are not read where
+// they lie, the old-frame bases straight into their staged slots, the stage's launches by `scatter`, the encoder and the records.
+extern "C++" {
+template <class PUT, class SCATTER>
+static int cbu_launch(const CbxuBatch &B, int njobs, int shuffle, int typesize, unsigned policy, uint8_t *w, hb_result *d_results, hipStream_t s, const char *label, PUT put,
+                      SCATTER scatter) {
     const CbxuLayout &L = B.L;
     const CbxeLayout &XL = B.X.L;
-    // (the query knows no pointers: it stages every job and decodes every old frame it cannot refuse, so this layout never exceeds it)
-    const size_t query = cbxu_workspace(njobs, boxes, old_hdrs, old_n, shuffle, typesize, accept);
-    if (!query) return HB_ERR_BAD_ARG;                                    // (the limits are taken as the query takes them)
-    if (work_bytes < query || query < L.total || B.X.E.query < B.X.E.L.total) return HB_ERR_SHORT_BUFFER;
-    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t no = B.jobs.size(), ng = B.X.jobs.size(), nd = B.fin.size();
-    // the overlay's records, prefix and finish list, and behind them the gather's records, prefix and fill table, go up in one copy (the
-    // buffer is read before the call returns)
+    const size_t ng = B.X.jobs.size(), nd = B.fin.size();
     std::vector<uint8_t> up(L.box + XL.upload, 0);
-    if (no) memcpy(up.data() + L.jobs, B.jobs.data(), no * sizeof(CbxuJob));
-    if (no) memcpy(up.data() + L.oblk, B.oblk.data(), (no + 1) * 4);
+    put(up.data());
     if (nd) memcpy(up.data() + L.fin, B.fin.data(), nd * 4);
     if (ng) memcpy(up.data() + L.box + XL.jobs, B.X.jobs.data(), ng * sizeof(CbxeJob));
     memcpy(up.data() + L.box + XL.gblk, B.X.gblk.data(), (ng + 1) * 4);
     memcpy(up.data() + L.box + XL.fill, B.X.table, CBXE_FILL_BYTES);
-    hb_prof_begin("cbxu_upload", s);
+    hb_prof_begin(label, s);
     HB_HIP_TRY(hipMemcpyAsync(w, up.data(), up.size(), hipMemcpyHostToDevice, s));
     hb_prof_end(s);
     uint8_t *wx = w + L.box;
     hb_result *d_dres = (hb_result *)(w + L.dres);
-    if (ng) {                                                             // the fill bases, and the whole boxes that are not read where they lie
+    if (ng) {
         hb_prof_begin("k_cbxe_gather", s);
         hipLaunchKernelGGL(k_cbxe_gather, dim3((unsigned)B.ggroups), dim3(256), 0, s, (const CbxeJob *)(wx + XL.jobs), (const uint32_t *)(wx + XL.gblk), (uint32_t)ng,
                            (const uint8_t *)(wx + XL.fill), (uint32_t)typesize, cbx_recip((uint32_t)typesize));
         hb_prof_end(s);
     }
-    if (nd) {                                                             // the old-frame bases, straight into their staged slots
+    if (nd) {
         const int st = cbb_launch_batch((int)nd, B.D, w + L.dec, d_dres, s);
         if (st) return st;
     }
-    if (no) {
-        hb_prof_begin("k_cbxu_overlay", s);
-        hipLaunchKernelGGL(k_cbxu_overlay, dim3((unsigned)B.ogroups), dim3(256), 0, s, (const CbxuJob *)(w + L.jobs), (const uint32_t *)(w + L.oblk), (uint32_t)no);
-        hb_prof_end(s);
-    }
+    scatter(w, s);
     // (the encoder reads the staged bytes of a base that failed to decode: they lie inside the workspace and may be anything, and the encoder
     // takes any bytes; k_cbxu_finish then overrides that frame's record)
     const int st = cbe_launch_batch(njobs, B.X.E, shuffle, typesize, policy, wx + XL.enc, d_results, s);
@@ -2110,6 +2089,113 @@ int hb_cblosc_update_boxes_batch_device(int njobs, const hb_cblosc_upd_box *boxe
     }
     return HB_OK;
 }
+}
+// the stages: the box updates' overlay, the selection updates' two scatters, the point updates' scatter
+static int cbxu_launch(const CbxuBatch &B, int njobs, int shuffle, int typesize, unsigned policy, uint8_t *w, hb_result *d_results, void *stream) {
+    const CbxuLayout &L = B.L;
+    const size_t no = B.jobs.size();
+    return cbu_launch(
+        B, njobs, shuffle, typesize, policy, w, d_results, (hipStream_t)stream, "cbxu_upload",
+        [&](uint8_t *up) {
+            if (no) { memcpy(up + L.jobs, B.jobs.data(), no * sizeof(CbxuJob)); memcpy(up + L.oblk, B.oblk.data(), (no + 1) * 4); }
+        },
+        [&](uint8_t *w, hipStream_t s) {
+            if (!no) return;
+            hb_prof_begin("k_cbxu_overlay", s);
+            hipLaunchKernelGGL(k_cbxu_overlay, dim3((unsigned)B.ogroups), dim3(256), 0, s, (const CbxuJob *)(w + L.jobs), (const uint32_t *)(w + L.oblk), (uint32_t)no);
+            hb_prof_end(s);
+        });
+}
+static int cbiu_launch(const CbiuBatch &B, int njobs, int shuffle, int typesize, unsigned policy, uint8_t *w, hb_result *d_results, void *stream) {
+    const CbiuLayout &SL = B.S;
+    const size_t sel = B.U.L.sel, nr = B.rjobs.size(), ni = B.ijobs.size(), nt = B.tab.size();
+    return cbu_launch(
+        B.U, njobs, shuffle, typesize, policy, w, d_results, (hipStream_t)stream, "cbiu_upload",
+        [&](uint8_t *up) {
+            uint8_t *us = up + sel;
+            if (nr) { memcpy(us + SL.rjobs, B.rjobs.data(), nr * sizeof(CbiuJob)); memcpy(us + SL.rblk, B.rblk.data(), (nr + 1) * 4); }
+            if (ni) { memcpy(us + SL.ijobs, B.ijobs.data(), ni * sizeof(CbiuJob)); memcpy(us + SL.iblk, B.iblk.data(), (ni + 1) * 4); }
+            if (nt) memcpy(us + SL.tab, B.tab.data(), nt * sizeof(CbiuPair));
+        },
+        [&](uint8_t *w, hipStream_t s) {
+            uint8_t *ws = w + sel;
+            if (nr) {
+                hb_prof_begin("k_cbiu_scatter_rows", s);
+                hipLaunchKernelGGL(k_cbiu_scatter_rows, dim3((unsigned)B.rgroups), dim3(256), 0, s, (const CbiuJob *)(ws + SL.rjobs), (const uint32_t *)(ws + SL.rblk), (uint32_t)nr,
+                                   (const CbiuPair *)(ws + SL.tab));
+                hb_prof_end(s);
+            }
+            if (ni) {
+                hb_prof_begin("k_cbiu_scatter_items", s);
+                hipLaunchKernelGGL(k_cbiu_scatter_items, dim3((unsigned)B.igroups), dim3(256), 0, s, (const CbiuJob *)(ws + SL.ijobs), (const uint32_t *)(ws + SL.iblk), (uint32_t)ni,
+                                   (const CbiuPair *)(ws + SL.tab), (uint32_t)typesize);
+                hb_prof_end(s);
+            }
+        });
+}
+// (d_sel_tab: the point table of a prepared selection, which the scatter then reads in place of the batch's own -- none is uploaded)
+static int cbpu_launch(const CbpuBatch &B, int njobs, const CbpPoint *d_sel_tab, int shuffle, int typesize, unsigned policy, uint8_t *w, hb_result *d_results, void *stream) {
+    const CbpuLayout &SL = B.S;
+    const size_t sel = B.U.L.sel, np = B.jobs.size(), nt = B.tab.size();
+    return cbu_launch(
+        B.U, njobs, shuffle, typesize, policy, w, d_results, (hipStream_t)stream, "cbpu_upload",
+        [&](uint8_t *up) {
+            uint8_t *us = up + sel;
+            if (np) { memcpy(us + SL.jobs, B.jobs.data(), np * sizeof(CbpuJob)); memcpy(us + SL.blk, B.blk.data(), (np + 1) * 4); }
+            if (nt) memcpy(us + SL.tab, B.tab.data(), nt * sizeof(CbpPoint));
+        },
+        [&](uint8_t *w, hipStream_t s) {
+            if (!np) return;
+            uint8_t *ws = w + sel;
+            hb_prof_begin("k_cbpu_scatter_points", s);
+            hipLaunchKernelGGL(k_cbpu_scatter_points, dim3((unsigned)B.groups), dim3(256), 0, s, (const CbpuJob *)(ws + SL.jobs), (const uint32_t *)(ws + SL.blk), (uint32_t)np,
+                               d_sel_tab ? d_sel_tab : (const CbpPoint *)(ws + SL.tab), (uint32_t)typesize);
+            hb_prof_end(s);
+        });
+}
+// The four update `_device` calls: bad argument (njobs < 0 also stands for whatever else the caller refuses at that point), no jobs, missing
+// pointers (`have_all`, asked only once there are jobs), then what `prepare` says, then the query -- it knows no pointers: it stages every job,
+// decodes every old frame it cannot refuse and counts every record of the stage, so the layout never exceeds it; 0: the limits, taken as the
+// query takes them -- then short buffer, then no device; and `launch`.
+extern "C++" {
+static inline const CbxuBatch &cbu_base(const CbxuBatch &B) { return B; }
+template <class BATCH>
+static inline const CbxuBatch &cbu_base(const BATCH &B) { return B.U; }      // (the selection and point updates' batches hold the box updates')
+template <class BATCH, class HAVE, class PREPARE, class QUERY, class LAUNCH>
+static int cbu_device_call(int njobs, int shuffle, int typesize, HAVE have_all, void *d_work, size_t work_bytes, hb_result *d_results, PREPARE prepare, QUERY query,
+                           LAUNCH launch) {
+    const unsigned policy = hb_cblosc_policy();                           // (hb_cblosc_set_compressor, read once: one call, one policy)
+    if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
+    if (njobs == 0) return HB_OK;
+    if (!have_all() || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
+    uint8_t *w = (uint8_t *)d_work;
+    const unsigned accept = hb_cblosc_accepted();                         // (read once: the query below judges the frames as the call does)
+    BATCH B;
+    const int rc = prepare(B, w, accept);
+    if (rc) return rc;
+    const size_t q = query(B, accept);
+    if (!q) return HB_ERR_BAD_ARG;
+    const CbxuBatch &U = cbu_base(B);
+    if (work_bytes < q || q < U.L.total || U.X.E.query < U.X.E.L.total) return HB_ERR_SHORT_BUFFER;
+    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
+    return launch(B, policy, w);
+}
+}
+
+// ---- many update boxes, one set of launches (include/hipblosc.h; the host side is hb_cblosc_upd_box_batch.h) ----
+size_t hb_cblosc_update_boxes_batch_workspace(int njobs, const hb_cblosc_upd_box *boxes, const hb_cblosc_header *old_hdrs, const size_t *old_n, int shuffle, int typesize) {
+    return cbxu_workspace(njobs, boxes, old_hdrs, old_n, shuffle, typesize, hb_cblosc_accepted());
+}
+
+int hb_cblosc_update_boxes_batch_device(int njobs, const hb_cblosc_upd_box *boxes, const hb_cblosc_header *old_hdrs, const void *const *d_old, const size_t *old_n,
+                                        const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill, int shuffle, int typesize,
+                                        void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
+    return cbu_device_call<CbxuBatch>(
+        njobs, shuffle, typesize, [&] { return boxes && old_hdrs && d_old && old_n && d_src && d_frame && cap; }, d_work, work_bytes, d_results,
+        [&](CbxuBatch &B, uint8_t *w, unsigned accept) { return cbxu_prepare(njobs, boxes, old_hdrs, d_old, old_n, d_src, d_frame, cap, fill, shuffle, typesize, w, accept, B); },
+        [&](const CbxuBatch &, unsigned accept) { return cbxu_workspace(njobs, boxes, old_hdrs, old_n, shuffle, typesize, accept); },
+        [&](const CbxuBatch &B, unsigned policy, uint8_t *w) { return cbxu_launch(B, njobs, shuffle, typesize, policy, w, d_results, stream); });
+}
 
 // ---- many selection updates, one set of launches (include/hipblosc.h; the host side is hb_cblosc_upd_index_batch.h) ----
 size_t hb_cblosc_update_index_batch_workspace(int njobs, const hb_cblosc_upd_index *jobs, const int64_t *index, int64_t nindex, const hb_cblosc_header *old_hdrs,
@@ -2120,125 +2206,15 @@ size_t hb_cblosc_update_index_batch_workspace(int njobs, const hb_cblosc_upd_ind
 int hb_cblosc_update_index_batch_device(int njobs, const hb_cblosc_upd_index *jobs, const int64_t *index, int64_t nindex, const hb_cblosc_header *old_hdrs,
                                         const void *const *d_old, const size_t *old_n, const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill,
                                         int shuffle, int typesize, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
-    const unsigned policy = hb_cblosc_policy();                           // (hb_cblosc_set_compressor, read once: one call, one policy)
-    if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
-    if (njobs == 0) return HB_OK;
-    if (!jobs || !old_hdrs || !d_old || !old_n || !d_src || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
-    uint8_t *w = (uint8_t *)d_work;
-    const unsigned accept = hb_cblosc_accepted();                         // (read once: the query below judges the frames as the call does)
-    CbiuBatch B;
-    const int rc = cbiu_prepare(njobs, jobs, index, nindex, old_hdrs, d_old, old_n, d_src, d_frame, cap, fill, shuffle, typesize, w, accept, B);
-    if (rc) return rc;
-    const CbxuLayout &L = B.U.L;
-    const CbxeLayout &XL = B.U.X.L;
-    const CbiuLayout &SL = B.S;
-    // (the query knows no pointers: it stages every job, decodes every old frame it cannot refuse and counts every scatter record and table
-    // entry, so this layout never exceeds it)
-    const size_t query = cbiu_workspace(njobs, jobs, index, nindex, old_hdrs, old_n, shuffle, typesize, accept);
-    if (!query) return HB_ERR_BAD_ARG;                                    // (the limits are taken as the query takes them)
-    if (work_bytes < query || query < L.total || B.U.X.E.query < B.U.X.E.L.total) return HB_ERR_SHORT_BUFFER;
-    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t nr = B.rjobs.size(), ni = B.ijobs.size(), nt = B.tab.size(), ng = B.U.X.jobs.size(), nd = B.U.fin.size();
-    // the scatters' records, prefixes and tables, the finish list, and behind them the gather's records, prefix and fill table, go up in one
-    // copy (the buffer is read before the call returns)
-    std::vector<uint8_t> up(L.box + XL.upload, 0);
-    uint8_t *us = up.data() + L.sel;
-    if (nr) { memcpy(us + SL.rjobs, B.rjobs.data(), nr * sizeof(CbiuJob)); memcpy(us + SL.rblk, B.rblk.data(), (nr + 1) * 4); }
-    if (ni) { memcpy(us + SL.ijobs, B.ijobs.data(), ni * sizeof(CbiuJob)); memcpy(us + SL.iblk, B.iblk.data(), (ni + 1) * 4); }
-    if (nt) memcpy(us + SL.tab, B.tab.data(), nt * sizeof(CbiuPair));
-    if (nd) memcpy(up.data() + L.fin, B.U.fin.data(), nd * 4);
-    if (ng) memcpy(up.data() + L.box + XL.jobs, B.U.X.jobs.data(), ng * sizeof(CbxeJob));
-    memcpy(up.data() + L.box + XL.gblk, B.U.X.gblk.data(), (ng + 1) * 4);
-    memcpy(up.data() + L.box + XL.fill, B.U.X.table, CBXE_FILL_BYTES);
-    hb_prof_begin("cbiu_upload", s);
-    HB_HIP_TRY(hipMemcpyAsync(w, up.data(), up.size(), hipMemcpyHostToDevice, s));
-    hb_prof_end(s);
-    uint8_t *wx = w + L.box, *ws = w + L.sel;
-    hb_result *d_dres = (hb_result *)(w + L.dres);
-    if (ng) {                                                             // the fill bases, and the whole chunks that are not read where they lie
-        hb_prof_begin("k_cbxe_gather", s);
-        hipLaunchKernelGGL(k_cbxe_gather, dim3((unsigned)B.U.ggroups), dim3(256), 0, s, (const CbxeJob *)(wx + XL.jobs), (const uint32_t *)(wx + XL.gblk), (uint32_t)ng,
-                           (const uint8_t *)(wx + XL.fill), (uint32_t)typesize, cbx_recip((uint32_t)typesize));
-        hb_prof_end(s);
-    }
-    if (nd) {                                                             // the old-frame bases, straight into their staged slots
-        const int st = cbb_launch_batch((int)nd, B.U.D, w + L.dec, d_dres, s);
-        if (st) return st;
-    }
-    if (nr) {
-        hb_prof_begin("k_cbiu_scatter_rows", s);
-        hipLaunchKernelGGL(k_cbiu_scatter_rows, dim3((unsigned)B.rgroups), dim3(256), 0, s, (const CbiuJob *)(ws + SL.rjobs), (const uint32_t *)(ws + SL.rblk), (uint32_t)nr,
-                           (const CbiuPair *)(ws + SL.tab));
-        hb_prof_end(s);
-    }
-    if (ni) {
-        hb_prof_begin("k_cbiu_scatter_items", s);
-        hipLaunchKernelGGL(k_cbiu_scatter_items, dim3((unsigned)B.igroups), dim3(256), 0, s, (const CbiuJob *)(ws + SL.ijobs), (const uint32_t *)(ws + SL.iblk), (uint32_t)ni,
-                           (const CbiuPair *)(ws + SL.tab), (uint32_t)typesize);
-        hb_prof_end(s);
-    }
-    // (a base that failed to decode: as in the box updates, the encoder takes any bytes and k_cbxu_finish overrides that frame's record)
-    const int st = cbe_launch_batch(njobs, B.U.X.E, shuffle, typesize, policy, wx + XL.enc, d_results, s);
-    if (st) return st;
-    if (nd) {
-        hb_prof_begin("k_cbxu_finish", s);
-        hipLaunchKernelGGL(k_cbxu_finish, dim3((unsigned)((nd + 63) / 64)), dim3(64), 0, s, (const uint32_t *)(w + L.fin), (const hb_result *)d_dres, d_results, (uint32_t)nd);
-        hb_prof_end(s);
-        HB_HIP_TRY(hipGetLastError());
-    }
-    return HB_OK;
+    return cbu_device_call<CbiuBatch>(
+        njobs, shuffle, typesize, [&] { return jobs && old_hdrs && d_old && old_n && d_src && d_frame && cap; }, d_work, work_bytes, d_results,
+        [&](CbiuBatch &B, uint8_t *w, unsigned accept) {
+            return cbiu_prepare(njobs, jobs, index, nindex, old_hdrs, d_old, old_n, d_src, d_frame, cap, fill, shuffle, typesize, w, accept, B);
+        },
+        [&](const CbiuBatch &, unsigned accept) { return cbiu_workspace(njobs, jobs, index, nindex, old_hdrs, old_n, shuffle, typesize, accept); },
+        [&](const CbiuBatch &B, unsigned policy, uint8_t *w) { return cbiu_launch(B, njobs, shuffle, typesize, policy, w, d_results, stream); });
 }
-// A prepared batch of point updates (CbpuBatch) on the device: one upload, the fill bases, the old-frame bases, the scatter, the encoder and the
-// records.  d_sel_tab: the point table of a prepared selection, which the scatter then reads in place of the batch's own (none is uploaded).
-static int cbpu_launch(const CbpuBatch &B, int njobs, const CbpPoint *d_sel_tab, int shuffle, int typesize, unsigned policy, uint8_t *w, hb_result *d_results, void *stream) {
-    const CbxuLayout &L = B.U.L;
-    const CbxeLayout &XL = B.U.X.L;
-    const CbpuLayout &SL = B.S;
-    hipStream_t s = (hipStream_t)stream;
-    const size_t np = B.jobs.size(), nt = B.tab.size(), ng = B.U.X.jobs.size(), nd = B.U.fin.size();
-    // the scatter's records, prefix and table, the finish list, and behind them the gather's records, prefix and fill table, go up in one
-    // copy (the buffer is read before the call returns)
-    std::vector<uint8_t> up(L.box + XL.upload, 0);
-    uint8_t *us = up.data() + L.sel;
-    if (np) { memcpy(us + SL.jobs, B.jobs.data(), np * sizeof(CbpuJob)); memcpy(us + SL.blk, B.blk.data(), (np + 1) * 4); }
-    if (nt) memcpy(us + SL.tab, B.tab.data(), nt * sizeof(CbpPoint));
-    if (nd) memcpy(up.data() + L.fin, B.U.fin.data(), nd * 4);
-    if (ng) memcpy(up.data() + L.box + XL.jobs, B.U.X.jobs.data(), ng * sizeof(CbxeJob));
-    memcpy(up.data() + L.box + XL.gblk, B.U.X.gblk.data(), (ng + 1) * 4);
-    memcpy(up.data() + L.box + XL.fill, B.U.X.table, CBXE_FILL_BYTES);
-    hb_prof_begin("cbpu_upload", s);
-    HB_HIP_TRY(hipMemcpyAsync(w, up.data(), up.size(), hipMemcpyHostToDevice, s));
-    hb_prof_end(s);
-    uint8_t *wx = w + L.box, *ws = w + L.sel;
-    hb_result *d_dres = (hb_result *)(w + L.dres);
-    if (ng) {                                                             // the fill bases
-        hb_prof_begin("k_cbxe_gather", s);
-        hipLaunchKernelGGL(k_cbxe_gather, dim3((unsigned)B.U.ggroups), dim3(256), 0, s, (const CbxeJob *)(wx + XL.jobs), (const uint32_t *)(wx + XL.gblk), (uint32_t)ng,
-                           (const uint8_t *)(wx + XL.fill), (uint32_t)typesize, cbx_recip((uint32_t)typesize));
-        hb_prof_end(s);
-    }
-    if (nd) {                                                             // the old-frame bases, straight into their staged slots
-        const int st = cbb_launch_batch((int)nd, B.U.D, w + L.dec, d_dres, s);
-        if (st) return st;
-    }
-    if (np) {
-        hb_prof_begin("k_cbpu_scatter_points", s);
-        hipLaunchKernelGGL(k_cbpu_scatter_points, dim3((unsigned)B.groups), dim3(256), 0, s, (const CbpuJob *)(ws + SL.jobs), (const uint32_t *)(ws + SL.blk), (uint32_t)np,
-                           d_sel_tab ? d_sel_tab : (const CbpPoint *)(ws + SL.tab), (uint32_t)typesize);
-        hb_prof_end(s);
-    }
-    // (a base that failed to decode: as in the box updates, the encoder takes any bytes and k_cbxu_finish overrides that frame's record)
-    const int st = cbe_launch_batch(njobs, B.U.X.E, shuffle, typesize, policy, wx + XL.enc, d_results, s);
-    if (st) return st;
-    if (nd) {
-        hb_prof_begin("k_cbxu_finish", s);
-        hipLaunchKernelGGL(k_cbxu_finish, dim3((unsigned)((nd + 63) / 64)), dim3(64), 0, s, (const uint32_t *)(w + L.fin), (const hb_result *)d_dres, d_results, (uint32_t)nd);
-        hb_prof_end(s);
-        HB_HIP_TRY(hipGetLastError());
-    }
-    return HB_OK;
-}
+
 // ---- many point updates, one set of launches (include/hipblosc.h; the host side is hb_cblosc_upd_point_batch.h) ----
 size_t hb_cblosc_update_points_batch_workspace(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints,
                                                const hb_cblosc_header *old_hdrs, const size_t *old_n, int shuffle, int typesize) {
@@ -2248,24 +2224,16 @@ size_t hb_cblosc_update_points_batch_workspace(int njobs, const hb_cblosc_upd_po
 int hb_cblosc_update_points_batch_device(int njobs, const hb_cblosc_upd_point_job *jobs, const hb_cblosc_upd_point *points, int64_t npoints, const hb_cblosc_header *old_hdrs,
                                          const void *const *d_old, const size_t *old_n, const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill,
                                          int shuffle, int typesize, void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
-    const unsigned policy = hb_cblosc_policy();                           // (hb_cblosc_set_compressor, read once: one call, one policy)
-    if (njobs < 0 || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2) return HB_ERR_BAD_ARG;
-    if (njobs == 0) return HB_OK;
-    if (!jobs || !old_hdrs || !d_old || !old_n || !d_src || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results) return HB_ERR_BAD_ARG;
-    uint8_t *w = (uint8_t *)d_work;
-    const unsigned accept = hb_cblosc_accepted();                         // (read once: the query below judges the frames as the call does)
-    CbpuBatch B;
-    const int rc = cbpu_prepare(njobs, jobs, points, npoints, old_hdrs, d_old, old_n, d_src, d_frame, cap, fill, shuffle, typesize, w, accept, B);
-    if (rc) return rc;
-    const CbxuLayout &L = B.U.L;
-    // (the query knows no pointers: it stages every job, decodes every old frame it cannot refuse and counts every scatter record and point,
-    // so this layout never exceeds it; what the sweeps over the points answered is taken from B, not worked out again)
-    const size_t query = cbpu_workspace(njobs, jobs, points, npoints, old_hdrs, old_n, shuffle, typesize, accept, &B);
-    if (!query) return HB_ERR_BAD_ARG;                                    // (the limits are taken as the query takes them)
-    if (work_bytes < query || query < L.total || B.U.X.E.query < B.U.X.E.L.total) return HB_ERR_SHORT_BUFFER;
-    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
-    return cbpu_launch(B, njobs, nullptr, shuffle, typesize, policy, w, d_results, stream);
+    return cbu_device_call<CbpuBatch>(
+        njobs, shuffle, typesize, [&] { return jobs && old_hdrs && d_old && old_n && d_src && d_frame && cap; }, d_work, work_bytes, d_results,
+        [&](CbpuBatch &B, uint8_t *w, unsigned accept) {
+            return cbpu_prepare(njobs, jobs, points, npoints, old_hdrs, d_old, old_n, d_src, d_frame, cap, fill, shuffle, typesize, w, accept, B);
+        },
+        // (what the sweeps over the points answered is taken from B, not worked out again)
+        [&](const CbpuBatch &B, unsigned accept) { return cbpu_workspace(njobs, jobs, points, npoints, old_hdrs, old_n, shuffle, typesize, accept, &B); },
+        [&](const CbpuBatch &B, unsigned policy, uint8_t *w) { return cbpu_launch(B, njobs, nullptr, shuffle, typesize, policy, w, d_results, stream); });
 }
+
 
 // ---- prepared point selections (include/hipblosc.h; the host side, the builders and the per-call prepares are hb_cblosc_point_sel.h) ----
 }  // extern "C"
@@ -2583,20 +2551,16 @@ size_t hb_cblosc_update_points_sel_workspace(const hb_cblosc_point_sel *sel, con
 int hb_cblosc_update_points_sel_device(const hb_cblosc_point_sel *sel, const hb_cblosc_header *old_hdrs, const void *const *d_old, const size_t *old_n,
                                        const void *const *d_src, void *const *d_frame, const size_t *cap, const void *fill, int shuffle, int typesize,
                                        void *d_work, size_t work_bytes, hb_result *d_results, void *stream) {
-    const unsigned policy = hb_cblosc_policy();                           // (hb_cblosc_set_compressor, read once: one call, one policy)
-    if (!sel || typesize < 1 || typesize > 255 || shuffle < 0 || shuffle > 2 || typesize != sel->P.typesize) return HB_ERR_BAD_ARG;
-    const int njobs = (int)sel->P.jobs.size();
-    if (njobs == 0) return HB_OK;
-    if (!old_hdrs || !d_old || !old_n || !d_src || !d_frame || !cap || !d_work || ((uintptr_t)d_work & 255u) || !d_results || !cbsel_on_device(sel)) return HB_ERR_BAD_ARG;
-    uint8_t *w = (uint8_t *)d_work;
-    const unsigned accept = hb_cblosc_accepted();                         // (read once: the query below judges the frames as the call does)
-    CbpuBatch B, Q;
-    const int rc = cbsel_update_prepare(sel->P, sel->W, old_hdrs, d_old, old_n, d_src, d_frame, cap, fill, shuffle, typesize, w, accept, B);
-    if (rc) return rc;
-    // (the query knows no pointers, as the point updates': this layout never exceeds it)
-    if (cbsel_update_prepare(sel->P, sel->W, old_hdrs, nullptr, old_n, nullptr, nullptr, nullptr, nullptr, shuffle, typesize, nullptr, accept, Q) || !Q.query) return HB_ERR_BAD_ARG;
-    if (work_bytes < Q.query || Q.query < B.U.L.total || B.U.X.E.query < B.U.X.E.L.total) return HB_ERR_SHORT_BUFFER;
-    if (hb_init() != HB_OK) return HB_ERR_NO_DEVICE;
-    return cbpu_launch(B, njobs, sel->d_tab, shuffle, typesize, policy, w, d_results, stream);
+    const int njobs = sel && typesize == sel->P.typesize ? (int)sel->P.jobs.size() : -1;      // (-1: refused with the bad arguments)
+    return cbu_device_call<CbpuBatch>(
+        njobs, shuffle, typesize, [&] { return old_hdrs && d_old && old_n && d_src && d_frame && cap && cbsel_on_device(sel); }, d_work, work_bytes, d_results,
+        [&](CbpuBatch &B, uint8_t *w, unsigned accept) {
+            return cbsel_update_prepare(sel->P, sel->W, old_hdrs, d_old, old_n, d_src, d_frame, cap, fill, shuffle, typesize, w, accept, B);
+        },
+        [&](const CbpuBatch &, unsigned accept) {                         // (a second prepare, without pointers)
+            CbpuBatch Q;
+            return cbsel_update_prepare(sel->P, sel->W, old_hdrs, nullptr, old_n, nullptr, nullptr, nullptr, nullptr, shuffle, typesize, nullptr, accept, Q) ? (size_t)0 : Q.query;
+        },
+        [&](const CbpuBatch &B, unsigned policy, uint8_t *w) { return cbpu_launch(B, njobs, sel->d_tab, shuffle, typesize, policy, w, d_results, stream); });
 }
 }  // extern "C"

@@ -484,6 +484,37 @@ def _results(outs, rcs):
     return [bytes(o[:rc]) if rc >= 0 else _BY_CODE.get(int(rc), HipBloscError)(f"code {rc}") for o, rc in zip(outs, rcs)]
 
 
+def _old_arrays(olds, keep):
+    """the pointer and size arrays of the old frames of an update batch -- olds[i] is a bytes-like object (its keepalive is appended to `keep`)
+    or None, the chunk the store does not have yet: no pointer, no bytes"""
+    bufs = [None if o is None else _buf(o) for o in olds]
+    keep.extend(b[2] for b in bufs if b is not None)
+    n = len(bufs)
+    return (ctypes.c_void_p * n)(*[b and b[0].value for b in bufs]), (ctypes.c_size_t * n)(*[b[1] if b else 0 for b in bufs])
+
+
+def _update_call(olds, srcs, jobs, what, fill, shuffle, typesize, dev, stage):
+    """What the update batches share: one old frame (or None) and one source per job (a `what`), a fill of typesize bytes, nothing to do for
+    no jobs; then the kind's part -- stage(jobs, keep) -> (the library's call, its arguments between the job count and the old frames, the
+    source pointers, the new frames' capacities), which checks that no job reaches beyond its source -- the old frames, the call and the
+    jobs' results."""
+    jobs = list(jobs)
+    n = len(jobs)
+    if len(srcs) != n or len(olds) != n:
+        raise ValueError(f"one old frame (or None) and one source per {what}")
+    if fill is not None and len(fill) != typesize:
+        raise ValueError("fill needs typesize bytes")
+    if n == 0:
+        return []
+    keep = []
+    call, middle, ptrs, caps = stage(jobs, keep)
+    optr, olen = _old_arrays(olds, keep)
+    outs, dsts, caps, rcs = _out_buffers(caps)
+    fb = None if fill is None else ctypes.create_string_buffer(bytes(fill), typesize)
+    _check(call(n, *middle, optr, olen, ptrs, dsts, caps, rcs, fb, int(shuffle), int(typesize), device if dev is None else dev))
+    return _results(outs, rcs)
+
+
 def _odometer(spans):
     """every index vector of an N-d grid in C order (the last dimension fastest); spans[k] is a range, or a count for range(count).  One empty
     vector for no dimensions, none where a dimension is empty."""
@@ -1346,31 +1377,9 @@ def CBloscUpdateBoxBatch(olds, srcs, boxes, fill=None, shuffle=1, typesize=4, de
     (typesize bytes; None: zeros) where olds[i] is None: the store has no such chunk yet.  A box that covers its whole chunk never looks at
     olds[i].  The i-th result is the NEW frame -- what CBloscCompress gives for the updated chunk -- or the job's error (returned, not raised,
     as CBloscCompressBoxBatch does).  The old frames are not changed."""
-    boxes = list(boxes)
-    n = len(boxes)
-    if len(srcs) != n or len(olds) != n:
-        raise ValueError("one old frame (or None) and one source per box")
-    if fill is not None and len(fill) != typesize:
-        raise ValueError("fill needs typesize bytes")
-    if n == 0:
-        return []
-    keep, optr, olen = [], [], []
-    ptrs = _box_sources(srcs, boxes, typesize, keep)
-    for o in olds:
-        if o is None:
-            optr.append(None)
-            olen.append(0)
-            continue
-        p, k, kp = _buf(o)
-        keep.append(kp)
-        optr.append(p.value)
-        olen.append(k)
-    outs, dsts, caps, rcs = _out_buffers(_frame_caps(boxes, typesize))
-    bt = (hb_cblosc_upd_box * n)(*boxes)
-    fb = None if fill is None else ctypes.create_string_buffer(bytes(fill), typesize)
-    _check(lib().hb_cblosc_update_boxes_batch(n, bt, (ctypes.c_void_p * n)(*optr), (ctypes.c_size_t * n)(*olen), ptrs, dsts, caps, rcs, fb, int(shuffle), int(typesize),
-                                              device if dev is None else dev))
-    return _results(outs, rcs)
+    def stage(boxes, keep):
+        return lib().hb_cblosc_update_boxes_batch, ((hb_cblosc_upd_box * len(boxes))(*boxes),), _box_sources(srcs, boxes, typesize, keep), _frame_caps(boxes, typesize)
+    return _update_call(olds, srcs, boxes, "box", fill, shuffle, typesize, dev, stage)
 
 
 def update_jobs(array_shape, chunk_shape, region, typesize):
@@ -1424,67 +1433,48 @@ def CBloscUpdateIndexBatch(olds, srcs, jobs, fill=None, shuffle=1, typesize=4, d
     records (upd_index) over that index array instead, as update_index_jobs makes them.  Every other item of the new chunk is the old
     frame's olds[i], or `fill` (typesize bytes; None: zeros) where olds[i] is None.  The i-th result is the NEW frame -- what CBloscCompress
     gives for the updated chunk -- or the job's error (returned, not raised, as CBloscUpdateBoxBatch does).  The old frames are not changed."""
-    jobs = list(jobs)
-    n = len(jobs)
-    if len(srcs) != n or len(olds) != n:
-        raise ValueError("one old frame (or None) and one source per job")
-    if fill is not None and len(fill) != typesize:
-        raise ValueError("fill needs typesize bytes")
-    if n == 0:
-        return []
-    if index is None:
-        index, recs = [], []
-        for chunk_shape, sel, strides in jobs:
-            start, count, step, lists, slists = [], [], [], [], []
-            for sl in sel:
-                if _is_triple(sl):
-                    start.append(sl[0]); count.append(sl[1]); step.append(sl[2]); lists.append(-1); slists.append(-1)
-                    continue
-                idx, sc = sl if _is_pair(sl) else (sl, None)
-                idx = [int(v) for v in idx]
-                start.append(0); count.append(len(idx)); step.append(1); lists.append(len(index))
-                index.extend(idx)
-                if sc is None:
-                    slists.append(-1)
-                else:
-                    if len(sc) != len(idx):
-                        raise ValueError("one source coordinate per index")
-                    slists.append(len(index))
-                    index.extend(int(v) for v in sc)
-            recs.append(upd_index(chunk_shape, start, count, step, lists, slists, strides))
-        jobs = recs
-    index = [int(v) for v in index]
-    keep, optr, olen, ptrs = [], [], [], []
-    for sp, q in zip(srcs, jobs):
-        if sp is None or isinstance(sp, int):
-            ptrs.append(sp)
-            continue
-        p, k, kp = _buf(sp)
-        keep.append(kp)
-        nd, span = min(q.ndim, 4), int(typesize)
-        if all(q.count[d] > 0 for d in range(nd)):
-            for d in range(nd):
-                sc = index[q.src_list[d]: q.src_list[d] + q.count[d]] if q.src_list[d] >= 0 else [q.count[d] - 1]
-                span += max(sc, default=0) * q.src_stride[d]
-            if all(q.src_stride[d] >= 0 for d in range(nd)) and span > k:
-                raise ValueError("a selection reaches beyond its source")
-        ptrs.append(p.value)
-    for o in olds:
-        if o is None:
-            optr.append(None)
-            olen.append(0)
-            continue
-        p, k, kp = _buf(o)
-        keep.append(kp)
-        optr.append(p.value)
-        olen.append(k)
-    outs, dsts, caps, rcs = _out_buffers(_frame_caps(jobs, typesize))
-    jt = (hb_cblosc_upd_index * n)(*jobs)
-    ix = (ctypes.c_int64 * max(len(index), 1))(*index)
-    fb = None if fill is None else ctypes.create_string_buffer(bytes(fill), typesize)
-    _check(lib().hb_cblosc_update_index_batch(n, jt, ix, len(index), (ctypes.c_void_p * n)(*optr), (ctypes.c_size_t * n)(*olen), (ctypes.c_void_p * n)(*ptrs), dsts, caps,
-                                              rcs, fb, int(shuffle), int(typesize), device if dev is None else dev))
-    return _results(outs, rcs)
+    def stage(jobs, keep, index=index):
+        if index is None:
+            index, recs = [], []
+            for chunk_shape, sel, strides in jobs:
+                start, count, step, lists, slists = [], [], [], [], []
+                for sl in sel:
+                    if _is_triple(sl):
+                        start.append(sl[0]); count.append(sl[1]); step.append(sl[2]); lists.append(-1); slists.append(-1)
+                        continue
+                    idx, sc = sl if _is_pair(sl) else (sl, None)
+                    idx = [int(v) for v in idx]
+                    start.append(0); count.append(len(idx)); step.append(1); lists.append(len(index))
+                    index.extend(idx)
+                    if sc is None:
+                        slists.append(-1)
+                    else:
+                        if len(sc) != len(idx):
+                            raise ValueError("one source coordinate per index")
+                        slists.append(len(index))
+                        index.extend(int(v) for v in sc)
+                recs.append(upd_index(chunk_shape, start, count, step, lists, slists, strides))
+            jobs = recs
+        index = [int(v) for v in index]
+        ptrs = []
+        for sp, q in zip(srcs, jobs):
+            if sp is None or isinstance(sp, int):
+                ptrs.append(sp)
+                continue
+            p, k, kp = _buf(sp)
+            keep.append(kp)
+            nd, span = min(q.ndim, 4), int(typesize)
+            if all(q.count[d] > 0 for d in range(nd)):
+                for d in range(nd):
+                    sc = index[q.src_list[d]: q.src_list[d] + q.count[d]] if q.src_list[d] >= 0 else [q.count[d] - 1]
+                    span += max(sc, default=0) * q.src_stride[d]
+                if all(q.src_stride[d] >= 0 for d in range(nd)) and span > k:
+                    raise ValueError("a selection reaches beyond its source")
+            ptrs.append(p.value)
+        n = len(jobs)
+        middle = (hb_cblosc_upd_index * n)(*jobs), (ctypes.c_int64 * max(len(index), 1))(*index), len(index)
+        return lib().hb_cblosc_update_index_batch, middle, (ctypes.c_void_p * n)(*ptrs), _frame_caps(jobs, typesize)
+    return _update_call(olds, srcs, jobs, "job", fill, shuffle, typesize, dev, stage)
 
 
 def update_index_jobs(array_shape, chunk_shape, selection, typesize):
@@ -1585,44 +1575,26 @@ def CBloscUpdatePointBatch(olds, srcs, jobs, points, fill=None, shuffle=1, types
     bytes-like object, an address, or None for a job without points).  Every other item of the new chunk is the old frame's olds[i], or
     `fill` (typesize bytes; None: zeros) where olds[i] is None.  The i-th result is the NEW frame -- what CBloscCompress gives for the updated
     chunk -- or the job's error (returned, not raised, as CBloscUpdateIndexBatch does).  The old frames are not changed."""
-    jobs = list(jobs)
-    n = len(jobs)
-    if len(srcs) != n or len(olds) != n:
-        raise ValueError("one old frame (or None) and one source per job")
-    if fill is not None and len(fill) != typesize:
-        raise ValueError("fill needs typesize bytes")
-    if n == 0:
-        return []
-    points = [(int(i), int(s)) for i, s in points]
-    keep, optr, olen, ptrs = [], [], [], []
-    for sp, q in zip(srcs, jobs):
-        if sp is None or isinstance(sp, int):
-            ptrs.append(sp)
-            continue
-        p, k, kp = _buf(sp)
-        keep.append(kp)
-        if 0 <= q.first and 0 < q.count <= len(points) - q.first:
-            top = max(s for _, s in points[q.first: q.first + q.count])
-            if (top + 1) * int(typesize) > k:
-                raise ValueError("a point reaches beyond its source")
-        ptrs.append(p.value)
-    for o in olds:
-        if o is None:
-            optr.append(None)
-            olen.append(0)
-            continue
-        p, k, kp = _buf(o)
-        keep.append(kp)
-        optr.append(p.value)
-        olen.append(k)
-    sizes = [q.chunk_items * int(typesize) if q.chunk_items >= 0 else None for q in jobs]
-    outs, dsts, caps, rcs = _out_buffers([lib().hb_cblosc_bound(c, typesize) if c is not None and c < (1 << 31) else 16 for c in sizes])
-    jt = (hb_cblosc_upd_point_job * n)(*jobs)
-    pa, npt = _upd_point_array(points)
-    fb = None if fill is None else ctypes.create_string_buffer(bytes(fill), typesize)
-    _check(lib().hb_cblosc_update_points_batch(n, jt, pa, npt, (ctypes.c_void_p * n)(*optr), (ctypes.c_size_t * n)(*olen), (ctypes.c_void_p * n)(*ptrs), dsts, caps, rcs, fb,
-                                               int(shuffle), int(typesize), device if dev is None else dev))
-    return _results(outs, rcs)
+    def stage(jobs, keep):
+        pts = [(int(i), int(s)) for i, s in points]
+        ptrs = []
+        for sp, q in zip(srcs, jobs):
+            if sp is None or isinstance(sp, int):
+                ptrs.append(sp)
+                continue
+            p, k, kp = _buf(sp)
+            keep.append(kp)
+            if 0 <= q.first and 0 < q.count <= len(pts) - q.first:
+                top = max(s for _, s in pts[q.first: q.first + q.count])
+                if (top + 1) * int(typesize) > k:
+                    raise ValueError("a point reaches beyond its source")
+            ptrs.append(p.value)
+        n = len(jobs)
+        sizes = [q.chunk_items * int(typesize) if q.chunk_items >= 0 else None for q in jobs]
+        caps = [lib().hb_cblosc_bound(c, typesize) if c is not None and c < (1 << 31) else 16 for c in sizes]
+        middle = ((hb_cblosc_upd_point_job * n)(*jobs),) + _upd_point_array(pts)
+        return lib().hb_cblosc_update_points_batch, middle, (ctypes.c_void_p * n)(*ptrs), caps
+    return _update_call(olds, srcs, jobs, "job", fill, shuffle, typesize, dev, stage)
 
 
 def update_point_jobs(array_shape, chunk_shape, coords, typesize):
