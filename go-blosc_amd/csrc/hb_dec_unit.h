@@ -419,7 +419,16 @@ __device__ __forceinline__ void dec_unit(const DecCtx &c, const uint32_t u, uint
         else if (at_token) ok = ok && rem1 == HB_IDX_AT_TOKEN;
         else ok = ok && rem1 == rem && tok1 == tokpos;
     }
-    if (!ok) { if (lane == 0) atomicExch(&plan->fail, 1u); wave_sync(); return; }
+    if (!ok) {
+        // One more shape is a good end (looked at here, off the path every unit takes): the block's last sequence has no literals and stands
+        // behind a match that fills the last unit.  The unit then stopped at a token (only a unit that ran to its end does) with its output
+        // complete and one byte of its slice left: that token, 0x00 -- no literals, no match announced -- which is the block's last byte
+        // (last: s1 == n_src, so slice byte si is src[n_src - 1]).  This rescues a failed `si == slen` and nothing else ONLY because at_token
+        // has one writer, the `stop` branch of the loop above, which is reached with ok still true and ends the loop: no parse error, bounds
+        // failure or refused match leaves at_token set.  Whoever gives at_token a second writer has to give this test a flag of its own.
+        const bool final0 = last && at_token && di == outlen && si + 1u == slen && DEC_LD_BYTE(c.src + c.n_src - 1u) == 0u;
+        if (!final0) { if (lane == 0) atomicExch(&plan->fail, 1u); wave_sync(); return; }
+    }
     wave_sync();
     pf_issue();
     if (bun4) {                                             // fused bit-unshuffle: every window in place

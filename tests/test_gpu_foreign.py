@@ -122,6 +122,16 @@ def test_foreign_frames_need_the_larger_workspace(hb, O):
             hip.hipFree(ptr)
 
 
+def rebuilt_index_place(n):
+    """(offset in the workspace, bytes) of the index that a one-frame decode of n bytes rebuilds for a frame without trailer (its place: tools/region_debug.py
+    --save-index).  Shared with tests/test_gpu_indexed_lz4.py."""
+    al = lambda v: (v + 255) & ~255
+    bound = n + n // 255 + 16
+    nr_cap = min(max(bound // 8192 + 2, min(bound, 8 << 20) // 4096 + 2), 16384)                 # rg_max_regions (csrc/hb_lz4_region.h)
+    off_idx = al(n) + 256 + 256 + al(64) + al(nr_cap * 64) + al(nr_cap * 4) + al(nr_cap * 256 * 8)
+    return off_idx, 32 + 16 * ((n + 4095) // 4096 + 1)
+
+
 def test_rebuilt_index_is_the_same_from_stored_tokens_and_from_bucket_records(hb, O):
     # An own frame without the trailer, decoded through the device-pointer API twice: with the small workspace the index is rebuilt from the
     # discovery's bucket records (k_rg_index_fast) + the wave walk, with the larger one from the tokens the first parse stored (k_rg_index_tok,
@@ -130,16 +140,11 @@ def test_rebuilt_index_is_the_same_from_stored_tokens_and_from_bucket_records(hb
     hip = devmem.hip()
     H2D, D2H, dmalloc = devmem.H2D, devmem.D2H, devmem.dmalloc
 
-    al = lambda v: (v + 255) & ~255
     for x, shuffle, ts in ((O.synth(O.D_F32, (48 << 20) // 4), 1, 4), (O.synth(O.D_I32, (24 << 20) // 4), 2, 4), (O.synth(O.D_F64, (32 << 20) // 8), 1, 8)):
         f = np.frombuffer(hb.Compress(x.tobytes(), hb.LZ4, 5, shuffle, ts, opts=0), np.uint8)
         n = x.nbytes
         small, large = L.hb_decompress_frame_workspace(n), L.hb_decompress_frame_workspace_foreign(n)
-        bound = n + n // 255 + 16
-        nr_cap = min(max(bound // 8192 + 2, min(bound, 8 << 20) // 4096 + 2), 16384)                 # rg_max_regions (csrc/hb_lz4_region.h)
-        off_idx = al(n) + 256 + 256 + al(64) + al(nr_cap * 64) + al(nr_cap * 4) + al(nr_cap * 256 * 8)
-        nun = (n + 4095) // 4096
-        idx_bytes = 32 + 16 * (nun + 1)
+        off_idx, idx_bytes = rebuilt_index_place(n)
         d_frame, d_out, d_res, d_work = dmalloc(f.size + 64), dmalloc(n), dmalloc(64), dmalloc(large)
         try:
             assert hip.hipMemcpy(d_frame, f.ctypes.data, f.size, H2D) == 0

@@ -99,3 +99,51 @@ def random_block(rng, target_out, regime_len=1 << 20, align=1, min_final=0):
     if lit >= 15: s += _ext(lit - 15)
     s += rng.integers(0, 256, lit, dtype=np.uint8).tobytes()
     return bytes(s), produced + lit
+
+
+def random_unit_local_block(rng, target_out, regime_len=1 << 20, unit=4096):
+    """random_block's sibling for decoders that work unit by unit (the indexed decoder and its restart index, tests/tools/lz4_index_gen.py):
+    the same regimes and draws, but every match is clipped so that its source and its end stay inside the `unit`-byte unit of output it
+    begins in -- a match that would begin on a unit's first byte, or within the last 3 bytes of one, gets the literals in front of it
+    lengthened until it does not.  Matches that end exactly on a unit's last byte and offsets that reach exactly to its first are therefore
+    common.  Decodes to exactly `target_out` bytes; the last sequence is literal-only and may be empty.  Returns (sequences, final) for
+    build_stream() / expand(): what the block decodes to is the builder's arithmetic."""
+    seqs = []
+    produced = 0
+    regimes = ("dense", "runs", "literal", "far", "mixed", "periodic", "huge")
+    limit = max(target_out - int(rng.integers(0, 30)), 0)           # where the last match ends at the latest: 0 to 29 final literals, or more
+    while True:
+        regime = regimes[int(rng.integers(0, len(regimes)))]
+        stop = min(limit, produced + int(rng.integers(regime_len // 4, regime_len * 2)))
+        period_tok = None
+        while produced < stop or produced == limit:
+            if regime == "dense":
+                lit = int(rng.integers(0, 3)); ml = int(rng.integers(4, 16)); off = int(rng.integers(1, 4096))
+            elif regime == "runs":
+                lit = int(rng.integers(0, 8)); ml = int(rng.integers(4, 6000)); off = int(rng.integers(1, 40))
+            elif regime == "literal":
+                lit = int(rng.integers(100, 70000)); ml = int(rng.integers(4, 12)); off = int(rng.integers(1, 65536))
+            elif regime == "far":
+                lit = int(rng.integers(0, 20)); ml = int(rng.integers(4, 300)); off = int(rng.integers(30000, 65536))
+            elif regime == "periodic":
+                if period_tok is None:
+                    period_tok = (int(rng.integers(0, 7)), int(rng.integers(3000, 5000)), int(rng.integers(1, 3)))
+                lit, ml, off = period_tok
+            elif regime == "huge":
+                lit = int(rng.integers(0, 3)) * int(rng.integers(0, 600000)); ml = int(rng.integers(4, 900000)); off = int(rng.integers(1, 65536))
+            else:
+                lit = int(rng.integers(0, 40)); ml = int(rng.integers(4, 80)); off = int(rng.integers(1, 65536))
+            lit = min(lit, max(stop - produced, 0) + 16)            # (a regime is cut to its length: several meet in one unit)
+            pos = produced + lit
+            while True:                                             # where the match may begin
+                first = pos // unit * unit
+                room = min(first + unit, limit) - pos
+                if limit - pos < 4:
+                    final = rng.integers(0, 256, target_out - produced, dtype=np.uint8).tobytes()
+                    return seqs, final
+                if room < 4: pos += room
+                elif pos == first: pos += 1
+                else: break
+            lit, ml, off = pos - produced, min(ml, room), max(1, min(off, pos - first))
+            seqs.append((rng.integers(0, 256, lit, dtype=np.uint8).tobytes(), off, ml))
+            produced += lit + ml
