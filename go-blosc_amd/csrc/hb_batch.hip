@@ -32,6 +32,7 @@
 #include <vector>
 #include <algorithm>
 #include <cstring>
+#include <type_traits>
 
 namespace {
 
@@ -368,9 +369,9 @@ int hb_decompress_frames_batch_dev(int nframes, const hb_header *hdrs, const voi
     return HB_OK;
 }
 
-// ---- host pointers: what a Go caller with many small []byte has.  Stages through cached device buffers (one upload and one download
-// per frame: PCIe- and call-overhead-bound -- the device-resident rate is bench.py's `small_frame_batches`), per-frame outcome in rc[]
-// exactly as hb_compress_frame / hb_decompress_frame would return it.  Frames the batch does not carry (Snappy / ZSTD) take one call each. ----
+// ---- host pointers: what a Go caller with many small []byte has.  Stages through cached device buffers (PCIe- and call-overhead-bound -- the
+// device-resident rate is bench.py's `small_frame_batches`), per-frame outcome in rc[] exactly as hb_compress_frame / hb_decompress_frame would
+// return it.  Frames the batch does not carry (Snappy / ZSTD) take one call each. ----
 namespace {
 // gathers `m` byte ranges into one contiguous buffer (frames of a batch before ONE download): job blockIdx.y
 struct PackJob { const uint8_t *src; uint64_t dst_off; uint64_t n; };
@@ -381,15 +382,210 @@ __global__ __launch_bounds__(256) void k_bt_pack(const PackJob *__restrict__ job
     for (uint64_t off = (uint64_t)wave * 16384u; off < j.n; off += (uint64_t)nw * 16384u)
         wave_copy_g2g(out + j.dst_off + off, j.src + off, (uint32_t)std::min<uint64_t>(16384u, j.n - off), lane);
 }
-// Host buffers that follow each other EXACTLY (buffer k + 1 starts where buffer k ends: slices of one array, a Go shim's staging slab) go up
-// in ONE copy instead of one per frame (a copy call costs ~7 us: 4096 frames of 100 KB spent 28 ms there, 6.9 GB/s host to host).  Nothing
-// but the buffers themselves is read: adjacency has to be exact.
-bool exactly_adjacent(const std::vector<int> &idx, const void *const *p, const size_t *len) {
-    for (size_t i = 0; i + 1 < idx.size(); i++)
-        if ((const uint8_t *)p[idx[i]] + len[idx[i]] != (const uint8_t *)p[idx[i + 1]]) return false;
-    return idx.size() > 1;
 }
+
+extern "C++" {
+namespace {
+// ---- The staging of every batch host form: the batch counterpart of hb_api.hip's staged_call (DESIGN.md "Batch host staging"). ----
+// everything in `list` gets one answer: the value `a`, or what a(k) writes
+template <class A>
+int answer_all(const std::vector<int> &list, int64_t *rc, A a) {
+    for (int k : list) { if constexpr (std::is_invocable_v<A, int>) a(k); else rc[k] = a; }
+    return HB_OK;
 }
+struct UpItem { const void *p; size_t n, off; };     // `n` host bytes at `p` to `off` in a device buffer
+struct BatchStage {
+    Scratch sc;
+    uint8_t *d_in = nullptr, *d_old = nullptr, *d_out = nullptr, *d_work = nullptr, *d_res = nullptr;
+    std::vector<hb_result> res;          // what records() brought down
+    explicit BatchStage(int device) : sc(device) {}
+    // The pool buffers, always taken in this order (the pool is first-fit): input, [old frames], output, workspace, `nrec` result records; 256 bytes
+    // behind input, old frames and output.  align16: d_in / d_old start at a multiple of 16 (plans whose offsets are: so are the addresses).
+    // old_bytes: of the second input, or NULL where a form has none.
+    bool take(size_t in_bytes, size_t out_bytes, size_t work_bytes, size_t nrec, bool align16 = false, const size_t *old_bytes = nullptr) {
+        const bool olds = old_bytes != nullptr;
+        d_in = sc.get(in_bytes + 256);
+        if (olds) d_old = sc.get(*old_bytes + 256);
+        d_out = sc.get(out_bytes + 256); d_work = sc.get(work_bytes); d_res = sc.get(nrec * sizeof(hb_result));
+        if (!d_in || (olds && !d_old) || !d_out || !d_work || !d_res) return false;
+        if (align16) { d_in += (16u - ((uintptr_t)d_in & 15u)) & 15u; if (olds) d_old += (16u - ((uintptr_t)d_old & 15u)) & 15u; }
+        res.resize(nrec);
+        return true;
+    }
+    // a span (hb_upload_plan of hb_host_stage.h) goes up in one copy, anything else one copy per item that has bytes
+    bool upload(uint8_t *d, const std::vector<UpItem> &items, bool span) {
+        if (span) {
+            size_t total = 0;
+            for (const UpItem &u : items) total += u.n;
+            return hipMemcpyAsync(d, items[0].p, total, hipMemcpyHostToDevice, nullptr) == hipSuccess;
+        }
+        for (const UpItem &u : items)
+            if (u.n && hipMemcpyAsync(d + u.off, u.p, u.n, hipMemcpyHostToDevice, nullptr) != hipSuccess) return false;
+        return true;
+    }
+    void wait_uploads() { (void)hipStreamSynchronize(nullptr); }       // (a pageable source that goes away: its copy has to be over first)
+    bool zero_out(size_t bytes) { return !bytes || hipMemsetAsync(d_out, 0, bytes, nullptr) == hipSuccess; }
+    bool records() { return hipMemcpy(res.data(), d_res, res.size() * sizeof(hb_result), hipMemcpyDeviceToHost) == hipSuccess; }
+    template <class SINGLE>
+    static constexpr bool answers = !std::is_same_v<SINGLE, std::nullptr_t>;      // a form passes its one-call answerer, or nullptr where it has none
+
+    // Frames of an encode come down.  idx[i]: the caller's input that carried frame i; pf[i]: its frame on the device; pick(r): the bytes it has.
+    // Many small frames are packed on the device, come down in ONE copy and are dealt out by the host (a copy call per frame costs more than the
+    // bytes it moves below ~256 KiB; never more than `pack_max` bytes in all); large frames one copy each, straight into the caller's buffers.
+    // `single` (or nullptr) answers an input whose frame did not end with status 0; without one that status is the answer.
+    template <class PICK, class SINGLE>
+    int download_frames(const std::vector<int> &idx, const std::vector<void *> &pf, void *const *dst, const size_t *cap, int64_t *rc, PICK pick, SINGLE single,
+                        size_t pack_max = (size_t)-1) {
+        const int m = (int)idx.size();
+        if (!records()) return answer_all(idx, rc, HB_ERR_HIP);
+        size_t total_out = 0;
+        std::vector<size_t> outs((size_t)m, 0), poff((size_t)m, 0);
+        for (int i = 0; i < m; i++) {
+            const int k = idx[(size_t)i];
+            const hb_result &r = res[(size_t)i];
+            if (r.status) { rc[k] = r.status; continue; }
+            const size_t out = pick(r);
+            if (out > cap[k]) { rc[k] = HB_ERR_SHORT_BUFFER; continue; }      // (what the one-frame call answers when the frame does not fit)
+            outs[(size_t)i] = out; poff[(size_t)i] = total_out; total_out += out; rc[k] = (int64_t)out;
+        }
+        const bool packed = m >= 16 && total_out / (size_t)m < ((size_t)256 << 10) && total_out <= pack_max;
+        if (packed && total_out) {
+            std::vector<PackJob> jobs((size_t)m);
+            size_t mx = 0;
+            for (int i = 0; i < m; i++) { jobs[(size_t)i] = PackJob{(const uint8_t *)pf[(size_t)i], (uint64_t)poff[(size_t)i], (uint64_t)outs[(size_t)i]}; mx = std::max(mx, outs[(size_t)i]); }
+            uint8_t *d_pack = sc.get(total_out + 256), *d_jobs = sc.get((size_t)m * sizeof(PackJob));
+            std::vector<uint8_t> host(total_out);
+            bool good = d_pack && d_jobs && hipMemcpyAsync(d_jobs, jobs.data(), (size_t)m * sizeof(PackJob), hipMemcpyHostToDevice, nullptr) == hipSuccess;
+            for (int j0 = 0; good && j0 < m; j0 += 65535) {
+                const unsigned ny = (unsigned)std::min(65535, m - j0), gx = (unsigned)std::min<size_t>(16, (mx + 65535) / 65536);
+                hipLaunchKernelGGL(k_bt_pack, dim3(gx ? gx : 1, ny), dim3(256), 0, nullptr, (const PackJob *)d_jobs + j0, d_pack);
+            }
+            good = good && hipMemcpy(host.data(), d_pack, total_out, hipMemcpyDeviceToHost) == hipSuccess;
+            for (int i = 0; i < m; i++) {
+                const int k = idx[(size_t)i];
+                if (rc[k] < 0) continue;
+                if (good) memcpy(dst[k], host.data() + poff[(size_t)i], outs[(size_t)i]); else rc[k] = HB_ERR_HIP;
+            }
+        } else if (!each<SINGLE>(idx, pf, dst, rc, [&](int i) { return outs[(size_t)i]; })) return HB_OK;
+        if constexpr (answers<SINGLE>) for (int i = 0; i < m; i++) if (res[(size_t)i].status) single(idx[(size_t)i]);
+        return HB_OK;
+    }
+    // Results of a decode come down.  A destination span (hb_download_plan) whose every frame decoded to its `want[i]` bytes comes down in one
+    // copy; else one copy per frame (a failed frame's buffer must keep what the caller had in it).  `single` as above.
+    template <class SINGLE>
+    int download_span_or_each(const std::vector<int> &idx, const std::vector<void *> &pd, void *const *dst, const size_t *want, bool span, size_t span_bytes, int64_t *rc,
+                              SINGLE single) {
+        const int m = (int)idx.size();
+        if (!records()) return answer_all(idx, rc, HB_ERR_HIP);
+        bool all_ok = true;
+        for (int i = 0; i < m; i++) {
+            const hb_result &r = res[(size_t)i];
+            rc[idx[(size_t)i]] = r.status ? (int64_t)r.status : (int64_t)r.bytes;
+            all_ok = all_ok && !r.status && r.bytes == want[i];
+        }
+        if (span && all_ok) {
+            if (span_bytes && hipMemcpy(dst[idx[0]], d_out, span_bytes, hipMemcpyDeviceToHost) != hipSuccess) return answer_all(idx, rc, HB_ERR_HIP);
+            return HB_OK;
+        }
+        if (!each<SINGLE>(idx, pd, dst, rc, [&](int i) { return (size_t)rc[idx[(size_t)i]]; })) return HB_OK;
+        if constexpr (answers<SINGLE>) for (int i = 0; i < m; i++) if (res[(size_t)i].status) single(idx[(size_t)i]);
+        return HB_OK;
+    }
+    // Packed jobs come down: the records, then `out_bytes` of the output buffer in one copy; job i of the records lies at ooff[i] in it.
+    // place(i, r, from) takes a job that ended with status 0 to the caller's buffer, failed(i, r) answers any other.  false: a HIP call failed.
+    template <class PLACE, class FAILED>
+    bool download_jobs(size_t out_bytes, const size_t *ooff, PLACE place, FAILED failed) {
+        if (!records()) return false;
+        std::vector<uint8_t> host(out_bytes);
+        if (out_bytes && hipMemcpy(host.data(), d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return false;
+        for (size_t i = 0; i < res.size(); i++) {
+            if (res[i].status != HB_OK) failed(i, res[i]); else place(i, res[i], host.data() + ooff[i]);
+        }
+        return true;
+    }
+
+private:
+    // one copy per item whose rc is a size (> 0 bytes), and the wait for them; false: the wait failed, and rc[] says so (with an answerer
+    // behind it for all, else for those that had no status of their own)
+    template <class SINGLE, class LEN>
+    bool each(const std::vector<int> &idx, const std::vector<void *> &from, void *const *dst, int64_t *rc, LEN len) {
+        for (int i = 0; i < (int)idx.size(); i++) {
+            const int k = idx[(size_t)i];
+            if (rc[k] < 0 || !len(i)) continue;
+            if (hipMemcpyAsync(dst[k], from[(size_t)i], len(i), hipMemcpyDeviceToHost, nullptr) != hipSuccess) rc[k] = HB_ERR_HIP;
+        }
+        if (hipStreamSynchronize(nullptr) == hipSuccess) return true;
+        for (int k : idx) if (answers<SINGLE> || rc[k] >= 0) rc[k] = HB_ERR_HIP;
+        return false;
+    }
+};
+
+// The go-blosc-format plan of the getitem host form, in the struct of cbg_host_plan (hb_cblosc_getitem_batch.h): a frame that does not parse
+// keeps its record, which the device form refuses job by job; a frame that is not read by a job the device can take does not go up.
+void gi_host_plan(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_getitem_job *jobs, void *const *dst, const size_t *cap, int typesize_override,
+                  GetitemHostPlanOf<hb_header> &P) {
+    const size_t nf = (size_t)nframes, nj = (size_t)njobs;
+    P.hd.assign(nf, hb_header{}); P.carried.assign(nj, 0); P.idx.clear(); P.ioff.assign(nf, 0); P.ooff.assign(nj, 0); P.nb.assign(nj, 0);
+    P.in_bytes = P.out_bytes = 0; P.span_in = false; P.any = false;
+    std::vector<uint8_t> parsed(nf, 0), used(nf, 0);
+    for (size_t k = 0; k < nf; k++)
+        parsed[k] = frame[k] && n[k] >= HB_HEADER_SIZE && hb_parse_header(frame[k], n[k], &P.hd[k]) == HB_OK && !hb_frame_host_codec(P.hd[k]);
+    for (size_t j = 0; j < nj; j++) {
+        const hb_getitem_job &q = jobs[j];
+        int ts = 1;
+        if (!parsed[q.frame] || hb_getitem_check(&P.hd[q.frame], n[q.frame], q.start, q.nitems, typesize_override, 0, &ts) != HB_OK) continue;
+        P.nb[j] = (size_t)q.nitems * (size_t)ts;
+        if (cap[j] < P.nb[j] || (!dst[j] && P.nb[j])) { P.nb[j] = 0; continue; }
+        P.ooff[j] = P.out_bytes; P.out_bytes += P.nb[j];
+        used[q.frame] = 1; P.any = true;
+    }
+    hb_upload_plan_frames(P, nframes, frame, n, used);
+    for (size_t j = 0; j < nj; j++) P.carried[j] = P.nb[j] || (dst[j] && used[jobs[j].frame]);
+}
+
+// Many ranges of many frames, either format: the plan says which frames go up and where each job's bytes lie in the packed device buffer, the
+// device form runs once, and whatever did not end with status 0 on the device -- refusals, hand-overs, frames the device does not decode --
+// is answered by `single`, the one-call function, so that rc[j] is its answer in every case.  plan(P); query(hd) -> workspace bytes (0: a
+// batch beyond the 32-bit limits, one call per job is still right); run(hd, pf, pd, d_work, wb, d_res).  flags (or NULL): hb_result.flags per job.
+template <class HDR, class PLAN, class QUERY, class RUN, class SINGLE>
+int getitem_host_call(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_getitem_job *jobs, void *const *dst, const size_t *cap, int64_t *rc,
+                      uint32_t *flags, int device, PLAN plan, QUERY query, RUN run, SINGLE single) {
+    if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
+    if (njobs == 0) return HB_OK;
+    if (!frame || !n || !jobs || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
+    for (int j = 0; j < njobs; j++)
+        if (jobs[j].frame >= (uint32_t)nframes || jobs[j].reserved != 0u) return HB_ERR_BAD_ARG;
+    std::vector<int> all((size_t)njobs);
+    for (int j = 0; j < njobs; j++) all[(size_t)j] = j;
+    GetitemHostPlanOf<HDR> P;
+    plan(P);
+    if (!P.any || hb_select_device(device) != HB_OK) return answer_all(all, rc, single);
+    const size_t wb = query(P.hd.data());
+    if (!wb) return answer_all(all, rc, single);
+    auto fail = [&](int64_t st) { return answer_all(all, rc, [&](int j) { rc[j] = st; if (flags) flags[j] = 0; }); };
+    BatchStage S(device);
+    if (!S.take(P.in_bytes, P.out_bytes, wb, (size_t)njobs)) return fail(HB_ERR_HIP);
+    // (a frame that is not uploaded keeps a NULL pointer: its jobs end with a status on the device and are answered one by one)
+    std::vector<const void *> pf((size_t)nframes, nullptr);
+    std::vector<UpItem> up;
+    for (int k : P.idx) { pf[(size_t)k] = S.d_in + P.ioff[(size_t)k]; up.push_back(UpItem{frame[k], n[k], P.ioff[(size_t)k]}); }
+    if (!S.upload(S.d_in, up, P.span_in)) return fail(HB_ERR_HIP);
+    std::vector<void *> pd((size_t)njobs, nullptr);
+    for (int j = 0; j < njobs; j++) if (P.carried[(size_t)j]) pd[(size_t)j] = S.d_out + P.ooff[(size_t)j];
+    const int st = run(P.hd.data(), pf.data(), pd.data(), S.d_work, wb, (hb_result *)S.d_res);
+    if (st) return fail(st);
+    const bool down = S.download_jobs(
+        P.out_bytes, P.ooff.data(),
+        [&](size_t j, const hb_result &r, const uint8_t *from) {
+            if (r.bytes) memcpy(dst[j], from, (size_t)r.bytes);
+            rc[j] = (int64_t)r.bytes;
+            if (flags) flags[j] = r.flags;
+        },
+        [&](size_t j, const hb_result &) { single((int)j); });
+    return down ? HB_OK : fail(HB_ERR_HIP);
+}
+}  // namespace
+}  // extern "C++"
 
 int hb_compress_frames_batch(int nframes, const void *const *src, const size_t *n, void *const *dst, const size_t *cap, int64_t *rc,
                              int codec, int level, int shuffle, int typesize, unsigned opts, int device) {
@@ -405,68 +601,24 @@ int hb_compress_frames_batch(int nframes, const void *const *src, const size_t *
     }
     const int m = (int)idx.size();
     if (m == 0) return HB_OK;
-    size_t in_bytes = 0, out_bytes = 0;
-    std::vector<size_t> ns((size_t)m), caps((size_t)m), ioff((size_t)m), ooff((size_t)m);
+    size_t out_bytes = 0;
+    std::vector<size_t> ns((size_t)m), caps((size_t)m), ooff((size_t)m);
     for (int i = 0; i < m; i++) {
         ns[(size_t)i] = n[idx[(size_t)i]]; caps[(size_t)i] = hb_frame_bound(ns[(size_t)i]) + 64;
-        ioff[(size_t)i] = in_bytes; ooff[(size_t)i] = out_bytes;
-        in_bytes += al256(ns[(size_t)i] + 16); out_bytes += al256(caps[(size_t)i]);
+        ooff[(size_t)i] = out_bytes; out_bytes += al256(caps[(size_t)i]);
     }
-    Scratch sc(device);
+    const HbUpload U = hb_upload_plan(idx, src, n, 16, 256);
     const size_t wb = hb_compress_frames_batch_workspace(m, ns.data(), typesize);
-    const bool span_in = exactly_adjacent(idx, src, n);
-    if (span_in) { in_bytes = 0; for (int i = 0; i < m; i++) { ioff[(size_t)i] = in_bytes; in_bytes += ns[(size_t)i]; } }      // the device copy mirrors the host span
-    uint8_t *d_in = sc.get(in_bytes + 256), *d_out = sc.get(out_bytes + 256), *d_work = sc.get(wb), *d_res = sc.get((size_t)m * sizeof(hb_result));
-    if (!d_in || !d_out || !d_work || !d_res) { for (int k : idx) rc[k] = HB_ERR_HIP; return HB_OK; }
+    BatchStage S(device);
+    if (!S.take(U.bytes, out_bytes, wb, (size_t)m)) return answer_all(idx, rc, HB_ERR_HIP);
     std::vector<const void *> ps((size_t)m); std::vector<void *> pf((size_t)m);
-    if (span_in && hipMemcpyAsync(d_in, src[idx[0]], in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) { for (int k : idx) rc[k] = HB_ERR_HIP; return HB_OK; }
-    for (int i = 0; i < m; i++) {
-        ps[(size_t)i] = d_in + ioff[(size_t)i]; pf[(size_t)i] = d_out + ooff[(size_t)i];
-        if (!span_in && hipMemcpyAsync(d_in + ioff[(size_t)i], src[idx[(size_t)i]], ns[(size_t)i], hipMemcpyHostToDevice, nullptr) != hipSuccess) { for (int k : idx) rc[k] = HB_ERR_HIP; return HB_OK; }
-    }
-    st = hb_compress_frames_batch_dev(m, ps.data(), ns.data(), pf.data(), caps.data(), codec, level, shuffle, typesize, opts, d_work, wb, (hb_result *)d_res, nullptr);
-    if (st) { for (int k : idx) rc[k] = st; return HB_OK; }
-    std::vector<hb_result> res((size_t)m);
-    if (hipMemcpy(res.data(), d_res, (size_t)m * sizeof(hb_result), hipMemcpyDeviceToHost) != hipSuccess) { for (int k : idx) rc[k] = HB_ERR_HIP; return HB_OK; }
-    // download: many small frames are packed on the device, come down in ONE copy and are dealt out by the host (a copy call per frame
-    // costs more than the bytes it moves below ~256 KiB); large frames one copy each, straight into the caller's buffers
-    size_t total_out = 0;
-    std::vector<size_t> outs((size_t)m, 0), poff((size_t)m, 0);
-    for (int i = 0; i < m; i++) {
-        const int k = idx[(size_t)i];
-        const hb_result &r = res[(size_t)i];
-        if (r.status) { rc[k] = r.status; continue; }
-        const size_t out = (opts & HB_OPT_INDEX_TRAILER) ? r.total_bytes : r.bytes;
-        if (out > cap[k]) { rc[k] = HB_ERR_SHORT_BUFFER; continue; }
-        outs[(size_t)i] = out; poff[(size_t)i] = total_out; total_out += out; rc[k] = (int64_t)out;
-    }
-    const bool packed = m >= 16 && total_out / (size_t)m < ((size_t)256 << 10) && total_out <= out_bytes;
-    if (packed && total_out) {
-        std::vector<PackJob> jobs((size_t)m);
-        size_t mx = 0;
-        for (int i = 0; i < m; i++) { jobs[(size_t)i] = PackJob{(const uint8_t *)pf[(size_t)i], (uint64_t)poff[(size_t)i], (uint64_t)outs[(size_t)i]}; mx = std::max(mx, outs[(size_t)i]); }
-        uint8_t *d_pack = sc.get(total_out + 256), *d_jobs = sc.get((size_t)m * sizeof(PackJob));
-        std::vector<uint8_t> host(total_out);
-        bool good = d_pack && d_jobs && hipMemcpyAsync(d_jobs, jobs.data(), (size_t)m * sizeof(PackJob), hipMemcpyHostToDevice, nullptr) == hipSuccess;
-        for (int j0 = 0; good && j0 < m; j0 += 65535) {
-            const unsigned ny = (unsigned)std::min(65535, m - j0), gx = (unsigned)std::min<size_t>(16, (mx + 65535) / 65536);
-            hipLaunchKernelGGL(k_bt_pack, dim3(gx ? gx : 1, ny), dim3(256), 0, nullptr, (const PackJob *)d_jobs + j0, d_pack);
-        }
-        good = good && hipMemcpy(host.data(), d_pack, total_out, hipMemcpyDeviceToHost) == hipSuccess;
-        for (int i = 0; i < m; i++) {
-            const int k = idx[(size_t)i];
-            if (rc[k] < 0) continue;
-            if (good) memcpy(dst[k], host.data() + poff[(size_t)i], outs[(size_t)i]); else rc[k] = HB_ERR_HIP;
-        }
-        return HB_OK;
-    }
-    for (int i = 0; i < m; i++) {
-        const int k = idx[(size_t)i];
-        if (rc[k] < 0) continue;
-        if (hipMemcpyAsync(dst[k], pf[(size_t)i], outs[(size_t)i], hipMemcpyDeviceToHost, nullptr) != hipSuccess) rc[k] = HB_ERR_HIP;
-    }
-    if (hipStreamSynchronize(nullptr) != hipSuccess) { for (int k : idx) if (rc[k] >= 0) rc[k] = HB_ERR_HIP; }
-    return HB_OK;
+    std::vector<UpItem> up((size_t)m);
+    for (int i = 0; i < m; i++) { ps[(size_t)i] = S.d_in + U.off[(size_t)i]; pf[(size_t)i] = S.d_out + ooff[(size_t)i]; up[(size_t)i] = UpItem{src[idx[(size_t)i]], ns[(size_t)i], U.off[(size_t)i]}; }
+    if (!S.upload(S.d_in, up, U.span)) return answer_all(idx, rc, HB_ERR_HIP);
+    st = hb_compress_frames_batch_dev(m, ps.data(), ns.data(), pf.data(), caps.data(), codec, level, shuffle, typesize, opts, S.d_work, wb, (hb_result *)S.d_res, nullptr);
+    if (st) return answer_all(idx, rc, st);
+    // (a frame's status is its answer: there is no other answerer.  The packed copy never holds more than the output buffer did.)
+    return S.download_frames(idx, pf, dst, cap, rc, [&](const hb_result &r) { return (size_t)((opts & HB_OPT_INDEX_TRAILER) ? r.total_bytes : r.bytes); }, nullptr, out_bytes);
 }
 
 int hb_decompress_frames_batch(int nframes, const void *const *frame, const size_t *n, void *const *dst, const size_t *cap, int64_t *rc,
@@ -485,130 +637,37 @@ int hb_decompress_frames_batch(int nframes, const void *const *frame, const size
     }
     const int m = (int)idx.size();
     if (m == 0) return HB_OK;
-    size_t in_bytes = 0, out_bytes = 0;
-    std::vector<size_t> ns((size_t)m), caps((size_t)m), ioff((size_t)m), ooff((size_t)m);
-    for (int i = 0; i < m; i++) {
-        ns[(size_t)i] = n[idx[(size_t)i]]; caps[(size_t)i] = hd[(size_t)i].nbytes;
-        ioff[(size_t)i] = in_bytes; ooff[(size_t)i] = out_bytes;
-        in_bytes += al256(ns[(size_t)i] + 64); out_bytes += al256(caps[(size_t)i] + 64);
-    }
-    Scratch sc(device);
+    std::vector<size_t> ns((size_t)m), caps((size_t)m);
+    for (int i = 0; i < m; i++) { ns[(size_t)i] = n[idx[(size_t)i]]; caps[(size_t)i] = hd[(size_t)i].nbytes; }
+    const HbUpload U = hb_upload_plan(idx, frame, n, 64, 256);
+    const HbDownload D = hb_download_plan(idx, dst, caps.data(), cap, 64, 256);
     const size_t wb = hb_decompress_frames_batch_workspace(m, hd.data());
-    // frames that follow each other exactly go up in one copy (see hb_compress_frames_batch); destinations that follow each other inside
-    // their own capacities (dst[k+1] in [dst[k] + nbytes, dst[k] + cap[k]]) get a device image of the same layout and come down in one
-    // copy: the bytes between two results lie inside the first one's buffer, which the caller handed over for writing (they are zeroed)
-    const bool span_in = exactly_adjacent(idx, frame, n);
-    if (span_in) { in_bytes = 0; for (int i = 0; i < m; i++) { ioff[(size_t)i] = in_bytes; in_bytes += ns[(size_t)i]; } }
-    bool span_out = m > 1;
-    for (int i = 0; span_out && i + 1 < m; i++) {
-        const uint8_t *a = (const uint8_t *)dst[idx[(size_t)i]], *b = (const uint8_t *)dst[idx[(size_t)i + 1]];
-        span_out = a && b && b >= a + hd[(size_t)i].nbytes && b <= a + cap[idx[(size_t)i]];
-    }
-    size_t span_bytes = 0;
-    if (span_out) {
-        const uint8_t *base = (const uint8_t *)dst[idx[0]];
-        for (int i = 0; i < m; i++) ooff[(size_t)i] = (size_t)((const uint8_t *)dst[idx[(size_t)i]] - base);
-        span_bytes = ooff[(size_t)m - 1] + hd[(size_t)m - 1].nbytes;
-        out_bytes = span_bytes + 64;
-    }
-    uint8_t *d_in = sc.get(in_bytes + 256), *d_out = sc.get(out_bytes + 256), *d_work = sc.get(wb), *d_res = sc.get((size_t)m * sizeof(hb_result));
-    if (!d_in || !d_out || !d_work || !d_res) { for (int k : idx) rc[k] = HB_ERR_HIP; return HB_OK; }
+    BatchStage S(device);
+    if (!S.take(U.bytes, D.bytes, wb, (size_t)m)) return answer_all(idx, rc, HB_ERR_HIP);
     std::vector<const void *> pf((size_t)m); std::vector<void *> pd((size_t)m);
-    if (span_in && hipMemcpyAsync(d_in, frame[idx[0]], in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) { for (int k : idx) rc[k] = HB_ERR_HIP; return HB_OK; }
-    if (span_out && hipMemsetAsync(d_out, 0, span_bytes, nullptr) != hipSuccess) { for (int k : idx) rc[k] = HB_ERR_HIP; return HB_OK; }
-    for (int i = 0; i < m; i++) {
-        pf[(size_t)i] = d_in + ioff[(size_t)i]; pd[(size_t)i] = d_out + ooff[(size_t)i];
-        if (!span_in && hipMemcpyAsync(d_in + ioff[(size_t)i], frame[idx[(size_t)i]], ns[(size_t)i], hipMemcpyHostToDevice, nullptr) != hipSuccess) { for (int k : idx) rc[k] = HB_ERR_HIP; return HB_OK; }
-    }
-    st = hb_decompress_frames_batch_dev(m, hd.data(), pf.data(), ns.data(), pd.data(), caps.data(), typesize_override, d_work, wb, (hb_result *)d_res, nullptr);
-    if (st) { for (int k : idx) rc[k] = st; return HB_OK; }
-    std::vector<hb_result> res((size_t)m);
-    if (hipMemcpy(res.data(), d_res, (size_t)m * sizeof(hb_result), hipMemcpyDeviceToHost) != hipSuccess) { for (int k : idx) rc[k] = HB_ERR_HIP; return HB_OK; }
-    bool all_ok = true;
-    for (int i = 0; i < m; i++) { const hb_result &r = res[(size_t)i]; rc[idx[(size_t)i]] = r.status ? (int64_t)r.status : (int64_t)r.bytes; all_ok = all_ok && !r.status && r.bytes == hd[(size_t)i].nbytes; }
-    if (span_out && all_ok) {                                           // (a failed frame's buffer must keep what the caller had in it: copy per frame then)
-        if (span_bytes && hipMemcpy(dst[idx[0]], d_out, span_bytes, hipMemcpyDeviceToHost) != hipSuccess) { for (int k : idx) rc[k] = HB_ERR_HIP; }
-        return HB_OK;
-    }
-    for (int i = 0; i < m; i++) {
-        const int k = idx[(size_t)i];
-        if (rc[k] <= 0) continue;
-        if (hipMemcpyAsync(dst[k], pd[(size_t)i], (size_t)rc[k], hipMemcpyDeviceToHost, nullptr) != hipSuccess) rc[k] = HB_ERR_HIP;
-    }
-    if (hipStreamSynchronize(nullptr) != hipSuccess) { for (int k : idx) if (rc[k] >= 0) rc[k] = HB_ERR_HIP; }
-    return HB_OK;
+    std::vector<UpItem> up((size_t)m);
+    for (int i = 0; i < m; i++) { pf[(size_t)i] = S.d_in + U.off[(size_t)i]; pd[(size_t)i] = S.d_out + D.off[(size_t)i]; up[(size_t)i] = UpItem{frame[idx[(size_t)i]], ns[(size_t)i], U.off[(size_t)i]}; }
+    if (!S.upload(S.d_in, up, U.span) || !S.zero_out(D.span_bytes)) return answer_all(idx, rc, HB_ERR_HIP);
+    st = hb_decompress_frames_batch_dev(m, hd.data(), pf.data(), ns.data(), pd.data(), caps.data(), typesize_override, S.d_work, wb, (hb_result *)S.d_res, nullptr);
+    if (st) return answer_all(idx, rc, st);
+    return S.download_span_or_each(idx, pd, dst, caps.data(), D.span, D.span_bytes, rc, nullptr);
 }
 
-// Many ranges of many frames (include/hipblosc.h): the frames that a job reads go up once each, the device form runs once, the result records
-// come down in one copy and the ranges in one copy (their device buffer is packed: job j's bytes follow job j - 1's).  Whatever did not end
-// with status 0 on the device -- refusals, hand-overs, ZSTD frames -- is answered by hb_getitem_frame, so that rc[j] is its answer in every case.
+// Many ranges of many frames (include/hipblosc.h): getitem_host_call over the go-blosc-format plan; hb_getitem_frame answers what is left.
 int hb_getitem_frames_batch(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_getitem_job *jobs, void *const *dst, const size_t *cap,
                             int64_t *rc, uint32_t *flags, int typesize_override, int device) {
-    if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
-    if (njobs == 0) return HB_OK;
-    if (!frame || !n || !jobs || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
-    for (int j = 0; j < njobs; j++)
-        if (jobs[j].frame >= (uint32_t)nframes || jobs[j].reserved != 0u) return HB_ERR_BAD_ARG;
-    auto single = [&](int j) {
-        const hb_getitem_job &q = jobs[j];
-        rc[j] = hb_getitem_frame(frame[q.frame], n[q.frame], q.start, q.nitems, dst[j], cap[j], typesize_override, device);
-        if (flags) flags[j] = rc[j] >= 0 ? hb_last_result_flags() : 0u;
-    };
-    auto all_single = [&]() { for (int j = 0; j < njobs; j++) single(j); return HB_OK; };
-    // headers (a frame that does not parse keeps a zeroed record, which the device form refuses job by job), and which frames are read at all
-    std::vector<hb_header> hd((size_t)nframes, hb_header{});
-    std::vector<uint8_t> parsed((size_t)nframes, 0), used((size_t)nframes, 0);
-    for (int k = 0; k < nframes; k++)
-        parsed[(size_t)k] = frame[k] && n[k] >= HB_HEADER_SIZE && hb_parse_header(frame[k], n[k], &hd[(size_t)k]) == HB_OK && !hb_frame_host_codec(hd[(size_t)k]);
-    // bytes of every job the device can take: place in the packed destination
-    std::vector<size_t> ooff((size_t)njobs, 0), nb((size_t)njobs, 0);
-    size_t out_bytes = 0;
-    bool any = false;
-    for (int j = 0; j < njobs; j++) {
-        const hb_getitem_job &q = jobs[j];
-        int ts = 1;
-        if (!parsed[q.frame] || hb_getitem_check(&hd[q.frame], n[q.frame], q.start, q.nitems, typesize_override, 0, &ts) != HB_OK) continue;
-        nb[(size_t)j] = (size_t)q.nitems * (size_t)ts;
-        if (cap[j] < nb[(size_t)j] || (!dst[j] && nb[(size_t)j])) { nb[(size_t)j] = 0; continue; }
-        ooff[(size_t)j] = out_bytes; out_bytes += nb[(size_t)j];
-        used[q.frame] = 1; any = true;
-    }
-    if (!any || hb_select_device(device) != HB_OK) return all_single();
-    std::vector<int> idx;
-    for (int k = 0; k < nframes; k++) if (used[(size_t)k]) idx.push_back(k);
-    const bool span_in = exactly_adjacent(idx, frame, n);
-    std::vector<size_t> ioff((size_t)nframes, 0);
-    size_t in_bytes = 0;
-    for (int k : idx) { ioff[(size_t)k] = in_bytes; in_bytes += span_in ? n[k] : al256(n[k] + 64); }
-    const size_t wb = hb_getitem_frames_batch_workspace(nframes, hd.data(), n, njobs, jobs, typesize_override);
-    if (!wb) return all_single();                                       // (a batch beyond the 32-bit limits: one call per job is still right)
-    Scratch sc(device);
-    uint8_t *d_in = sc.get(in_bytes + 256), *d_out = sc.get(out_bytes + 256), *d_work = sc.get(wb), *d_res = sc.get((size_t)njobs * sizeof(hb_result));
-    auto fail_all = [&]() { for (int j = 0; j < njobs; j++) { rc[j] = HB_ERR_HIP; if (flags) flags[j] = 0; } return HB_OK; };
-    if (!d_in || !d_out || !d_work || !d_res) return fail_all();
-    if (span_in && hipMemcpyAsync(d_in, frame[idx[0]], in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-    std::vector<const void *> pf((size_t)nframes, nullptr);
-    for (int k : idx) {
-        pf[(size_t)k] = d_in + ioff[(size_t)k];
-        if (!span_in && hipMemcpyAsync(d_in + ioff[(size_t)k], frame[k], n[k], hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-    }
-    // (a frame that is not uploaded keeps a NULL pointer: its jobs end with a status on the device and are answered one by one)
-    std::vector<void *> pd((size_t)njobs, nullptr);
-    for (int j = 0; j < njobs; j++) if (nb[(size_t)j] || (dst[j] && used[jobs[j].frame])) pd[(size_t)j] = d_out + ooff[(size_t)j];
-    const int st = hb_getitem_frames_batch_device(nframes, hd.data(), pf.data(), n, njobs, jobs, pd.data(), cap, typesize_override, d_work, wb, (hb_result *)d_res, nullptr);
-    if (st) { for (int j = 0; j < njobs; j++) { rc[j] = st; if (flags) flags[j] = 0; } return HB_OK; }
-    std::vector<hb_result> res((size_t)njobs);
-    if (hipMemcpy(res.data(), d_res, (size_t)njobs * sizeof(hb_result), hipMemcpyDeviceToHost) != hipSuccess) return fail_all();
-    std::vector<uint8_t> host(out_bytes);
-    if (out_bytes && hipMemcpy(host.data(), d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail_all();
-    for (int j = 0; j < njobs; j++) {
-        const hb_result &r = res[(size_t)j];
-        if (r.status != HB_OK) { single(j); continue; }
-        if (r.bytes) memcpy(dst[j], host.data() + ooff[(size_t)j], (size_t)r.bytes);
-        rc[j] = (int64_t)r.bytes;
-        if (flags) flags[j] = r.flags;
-    }
-    return HB_OK;
+    return getitem_host_call<hb_header>(
+        nframes, frame, n, njobs, jobs, dst, cap, rc, flags, device,
+        [&](GetitemHostPlanOf<hb_header> &P) { gi_host_plan(nframes, frame, n, njobs, jobs, dst, cap, typesize_override, P); },
+        [&](const hb_header *hd) { return hb_getitem_frames_batch_workspace(nframes, hd, n, njobs, jobs, typesize_override); },
+        [&](const hb_header *hd, const void *const *pf, void *const *pd, void *d_work, size_t wb, hb_result *d_res) {
+            return hb_getitem_frames_batch_device(nframes, hd, pf, n, njobs, jobs, pd, cap, typesize_override, d_work, wb, d_res, nullptr);
+        },
+        [&](int j) {
+            const hb_getitem_job &q = jobs[j];
+            rc[j] = hb_getitem_frame(frame[q.frame], n[q.frame], q.start, q.nitems, dst[j], cap[j], typesize_override, device);
+            if (flags) flags[j] = rc[j] >= 0 ? hb_last_result_flags() : 0u;
+        });
 }
 
 // Many C-Blosc-1 frames (include/hipblosc.h).  cbb_host_plan (hb_cblosc_batch.h) says which frames the batch carries and where they lie; whatever
@@ -626,97 +685,42 @@ int hb_cblosc_decompress_frames_batch(int nframes, const void *const *frame, con
     for (int k : P.idx) carried[(size_t)k] = 1;
     for (int k = 0; k < nframes; k++) if (!carried[(size_t)k]) single(k);
     if (m == 0) return HB_OK;
-    auto rest_single = [&]() { for (int k : P.idx) single(k); return HB_OK; };
-    if (hb_select_device(device) != HB_OK) return rest_single();
+    if (hb_select_device(device) != HB_OK) return answer_all(P.idx, rc, single);
     const size_t wb = hb_cblosc_decompress_frames_batch_workspace(m, P.hd.data(), P.ns.data());
-    if (!wb) return rest_single();                                       // (a batch beyond the 32-bit limits: one call per frame is still right)
-    auto fail_all = [&]() { for (int k : P.idx) rc[k] = HB_ERR_HIP; return HB_OK; };
-    Scratch sc(device);
-    uint8_t *d_in = sc.get(P.in_bytes + 256), *d_out = sc.get(P.out_bytes + 256), *d_work = sc.get(wb), *d_res = sc.get((size_t)m * sizeof(hb_result));
-    if (!d_in || !d_out || !d_work || !d_res) return fail_all();
-    if (P.span_in && hipMemcpyAsync(d_in, frame[P.idx[0]], P.in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-    if (P.span_out && P.span_bytes && hipMemsetAsync(d_out, 0, P.span_bytes, nullptr) != hipSuccess) return fail_all();
+    if (!wb) return answer_all(P.idx, rc, single);                      // (a batch beyond the 32-bit limits: one call per frame is still right)
+    BatchStage S(device);
+    if (!S.take(P.in_bytes, P.out_bytes, wb, (size_t)m)) return answer_all(P.idx, rc, HB_ERR_HIP);
     std::vector<const void *> pf((size_t)m); std::vector<void *> pd((size_t)m);
-    for (int i = 0; i < m; i++) {
-        pf[(size_t)i] = d_in + P.ioff[(size_t)i]; pd[(size_t)i] = d_out + P.ooff[(size_t)i];
-        if (!P.span_in && hipMemcpyAsync(d_in + P.ioff[(size_t)i], frame[P.idx[(size_t)i]], P.ns[(size_t)i], hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-    }
-    const int st = hb_cblosc_decompress_frames_batch_device(m, P.hd.data(), pf.data(), P.ns.data(), pd.data(), P.caps.data(), d_work, wb, (hb_result *)d_res, nullptr);
-    if (st) { for (int k : P.idx) rc[k] = st; return HB_OK; }
-    std::vector<hb_result> res((size_t)m);
-    if (hipMemcpy(res.data(), d_res, (size_t)m * sizeof(hb_result), hipMemcpyDeviceToHost) != hipSuccess) return fail_all();
-    bool all_ok = true;
-    for (int i = 0; i < m; i++) all_ok = all_ok && res[(size_t)i].status == HB_OK;
-    if (P.span_out && all_ok) {                                           // (a failed frame's buffer must keep what the caller had in it: copy per frame then)
-        if (P.span_bytes && hipMemcpy(dst[P.idx[0]], d_out, P.span_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail_all();
-        for (int i = 0; i < m; i++) rc[P.idx[(size_t)i]] = (int64_t)res[(size_t)i].bytes;
-        return HB_OK;
-    }
-    for (int i = 0; i < m; i++) {
-        const int k = P.idx[(size_t)i];
-        const hb_result &r = res[(size_t)i];
-        rc[k] = r.status ? (int64_t)r.status : (int64_t)r.bytes;
-        if (r.status == HB_OK && r.bytes && hipMemcpyAsync(dst[k], pd[(size_t)i], (size_t)r.bytes, hipMemcpyDeviceToHost, nullptr) != hipSuccess) rc[k] = HB_ERR_HIP;
-    }
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return fail_all();
-    for (int i = 0; i < m; i++) if (res[(size_t)i].status != HB_OK) single(P.idx[(size_t)i]);
-    return HB_OK;
+    std::vector<UpItem> up((size_t)m);
+    for (int i = 0; i < m; i++) { pf[(size_t)i] = S.d_in + P.ioff[(size_t)i]; pd[(size_t)i] = S.d_out + P.ooff[(size_t)i]; up[(size_t)i] = UpItem{frame[P.idx[(size_t)i]], P.ns[(size_t)i], P.ioff[(size_t)i]}; }
+    if (!S.upload(S.d_in, up, P.span_in) || !S.zero_out(P.span_bytes)) return answer_all(P.idx, rc, HB_ERR_HIP);
+    const int st = hb_cblosc_decompress_frames_batch_device(m, P.hd.data(), pf.data(), P.ns.data(), pd.data(), P.caps.data(), S.d_work, wb, (hb_result *)S.d_res, nullptr);
+    if (st) return answer_all(P.idx, rc, st);
+    return S.download_span_or_each(P.idx, pd, dst, P.caps.data(), P.span_out, P.span_bytes, rc, single);
 }
 
-// Many ranges of many C-Blosc-1 frames (include/hipblosc.h).  cbg_host_plan (hb_cblosc_getitem_batch.h) says which jobs the batch carries, which
-// frames go up and where each job's bytes lie in the packed device buffer: every frame a carried job reads goes up once, the device form runs
-// once, the records come down in one copy and the ranges in one copy.  Whatever did not end with status 0 on the device is answered by
-// hb_cblosc_getitem, so that rc[j] is its answer in every case.
+// Many ranges of many C-Blosc-1 frames (include/hipblosc.h): getitem_host_call over cbg_host_plan (hb_cblosc_getitem_batch.h); hb_cblosc_getitem
+// answers what is left.
 int hb_cblosc_getitem_frames_batch(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_getitem_job *jobs, void *const *dst, const size_t *cap,
                                    int64_t *rc, int device) {
-    if (nframes < 0 || njobs < 0) return HB_ERR_BAD_ARG;
-    if (njobs == 0) return HB_OK;
-    if (!frame || !n || !jobs || !dst || !cap || !rc) return HB_ERR_BAD_ARG;
-    for (int j = 0; j < njobs; j++)
-        if (jobs[j].frame >= (uint32_t)nframes || jobs[j].reserved != 0u) return HB_ERR_BAD_ARG;
-    auto single = [&](int j) {
-        const hb_getitem_job &q = jobs[j];
-        rc[j] = hb_cblosc_getitem(frame[q.frame], n[q.frame], q.start, q.nitems, dst[j], cap[j], device);
-    };
-    auto all_single = [&]() { for (int j = 0; j < njobs; j++) single(j); return HB_OK; };
-    CbgHostPlan P;
-    cbg_host_plan(nframes, frame, n, njobs, jobs, dst, cap, P, hb_cblosc_accepted());
-    if (!P.any || hb_select_device(device) != HB_OK) return all_single();
-    const size_t wb = hb_cblosc_getitem_frames_batch_workspace(nframes, P.hd.data(), n, njobs, jobs);
-    if (!wb) return all_single();                                       // (a batch beyond the 32-bit limits: one call per job is still right)
-    Scratch sc(device);
-    uint8_t *d_in = sc.get(P.in_bytes + 256), *d_out = sc.get(P.out_bytes + 256), *d_work = sc.get(wb), *d_res = sc.get((size_t)njobs * sizeof(hb_result));
-    auto fail_all = [&]() { for (int j = 0; j < njobs; j++) rc[j] = HB_ERR_HIP; return HB_OK; };
-    if (!d_in || !d_out || !d_work || !d_res) return fail_all();
-    if (P.span_in && hipMemcpyAsync(d_in, frame[P.idx[0]], P.in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-    // (a frame that is not uploaded keeps a NULL pointer: its jobs end with a status on the device and are answered one by one)
-    std::vector<const void *> pf((size_t)nframes, nullptr);
-    for (int k : P.idx) {
-        pf[(size_t)k] = d_in + P.ioff[(size_t)k];
-        if (!P.span_in && hipMemcpyAsync(d_in + P.ioff[(size_t)k], frame[k], n[k], hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-    }
-    std::vector<void *> pd((size_t)njobs, nullptr);
-    for (int j = 0; j < njobs; j++) if (P.carried[(size_t)j]) pd[(size_t)j] = d_out + P.ooff[(size_t)j];
-    const int st = hb_cblosc_getitem_frames_batch_device(nframes, P.hd.data(), pf.data(), n, njobs, jobs, pd.data(), cap, d_work, wb, (hb_result *)d_res, nullptr);
-    if (st) { for (int j = 0; j < njobs; j++) rc[j] = st; return HB_OK; }
-    std::vector<hb_result> res((size_t)njobs);
-    if (hipMemcpy(res.data(), d_res, (size_t)njobs * sizeof(hb_result), hipMemcpyDeviceToHost) != hipSuccess) return fail_all();
-    std::vector<uint8_t> host(P.out_bytes);
-    if (P.out_bytes && hipMemcpy(host.data(), d_out, P.out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail_all();
-    for (int j = 0; j < njobs; j++) {
-        const hb_result &r = res[(size_t)j];
-        if (r.status != HB_OK) { single(j); continue; }
-        if (r.bytes) memcpy(dst[j], host.data() + P.ooff[(size_t)j], (size_t)r.bytes);
-        rc[j] = (int64_t)r.bytes;
-    }
-    return HB_OK;
+    return getitem_host_call<hb_cblosc_header>(
+        nframes, frame, n, njobs, jobs, dst, cap, rc, nullptr, device,
+        [&](CbgHostPlan &P) { cbg_host_plan(nframes, frame, n, njobs, jobs, dst, cap, P, hb_cblosc_accepted()); },
+        [&](const hb_cblosc_header *hd) { return hb_cblosc_getitem_frames_batch_workspace(nframes, hd, n, njobs, jobs); },
+        [&](const hb_cblosc_header *hd, const void *const *pf, void *const *pd, void *d_work, size_t wb, hb_result *d_res) {
+            return hb_cblosc_getitem_frames_batch_device(nframes, hd, pf, n, njobs, jobs, pd, cap, d_work, wb, d_res, nullptr);
+        },
+        [&](int j) {
+            const hb_getitem_job &q = jobs[j];
+            rc[j] = hb_cblosc_getitem(frame[q.frame], n[q.frame], q.start, q.nitems, dst[j], cap[j], device);
+        });
 }
 
 // Many boxes of many C-Blosc-1 frames (include/hipblosc.h).  cbx_host_plan (hb_cblosc_box_batch.h) answers what the host refuses and says which
-// jobs the batch carries, which frames go up and where each box lies, C-contiguous, in the packed device buffer: every frame a carried job
-// reads goes up once, the device form runs once over the carried jobs, the records come down in one copy and the packed boxes in one copy, and
-// the rows are placed at their strides here.  No job is answered row by row.  The stepped selections of hb_cblosc_getslice_frames_batch go the
-// same way with their own plan, query and device form (`plan`, `query`, `run`).
+// jobs the batch carries, which frames go up and where each box lies, C-contiguous, in the packed device buffer: the device form runs once over
+// the carried jobs, and the rows are placed at their strides here.  No job is answered row by row: a job that did not end with status 0 keeps
+// that status, and its destination the caller's bytes.  The stepped selections of hb_cblosc_getslice_frames_batch go the same way with their
+// own plan, query and device form (`plan`, `query`, `run`).
 extern "C++" {
 struct CbxPlaceRows {                    // carried job i of the plan: its packed box to the caller's strides
     template <class PLAN_>
@@ -735,38 +739,32 @@ static int cbx_host_call(int nframes, const void *const *frame, const size_t *n,
     for (int j = 0; j < njobs; j++) rc[j] = P.status[(size_t)j];
     const int m = (int)P.carried.size();
     if (m == 0) return HB_OK;
-    auto all = [&](int64_t st) { for (int j : P.carried) rc[j] = st; return HB_OK; };
     const int sel = hb_select_device(device);
-    if (sel != HB_OK) return all(sel);
+    if (sel != HB_OK) return answer_all(P.carried, rc, sel);
     const size_t wb = query(nframes, P.hd.data(), n, m, P.pj.data());
-    if (!wb) return all(HB_ERR_BAD_ARG);                                // (a batch beyond the 32-bit limits: the caller has to split it)
-    Scratch sc(device);
-    uint8_t *d_in = sc.get(P.in_bytes + 256), *d_out = sc.get(P.out_bytes + 256), *d_work = sc.get(wb), *d_res = sc.get((size_t)m * sizeof(hb_result));
-    if (!d_in || !d_out || !d_work || !d_res) return all(HB_ERR_HIP);
-    if (P.span_in && hipMemcpyAsync(d_in, frame[P.idx[0]], P.in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return all(HB_ERR_HIP);
+    if (!wb) return answer_all(P.carried, rc, HB_ERR_BAD_ARG);          // (a batch beyond the 32-bit limits: the caller has to split it)
+    BatchStage S(device);
+    if (!S.take(P.in_bytes, P.out_bytes, wb, (size_t)m)) return answer_all(P.carried, rc, HB_ERR_HIP);
     std::vector<const void *> pf((size_t)nframes, nullptr);
-    for (int k : P.idx) {
-        pf[(size_t)k] = d_in + P.ioff[(size_t)k];
-        if (!P.span_in && hipMemcpyAsync(d_in + P.ioff[(size_t)k], frame[k], n[k], hipMemcpyHostToDevice, nullptr) != hipSuccess) return all(HB_ERR_HIP);
-    }
+    std::vector<UpItem> up;
+    for (int k : P.idx) { pf[(size_t)k] = S.d_in + P.ioff[(size_t)k]; up.push_back(UpItem{frame[k], n[k], P.ioff[(size_t)k]}); }
+    if (!S.upload(S.d_in, up, P.span_in)) return answer_all(P.carried, rc, HB_ERR_HIP);
     std::vector<void *> pd((size_t)m);
-    for (int i = 0; i < m; i++) pd[(size_t)i] = d_out + P.ooff[(size_t)i];
-    const int st = run(nframes, P.hd.data(), pf.data(), n, m, P.pj.data(), pd.data(), P.caps.data(), d_work, wb, (hb_result *)d_res, nullptr);
-    if (st) return all(st);
-    std::vector<hb_result> res((size_t)m);
-    if (hipMemcpy(res.data(), d_res, (size_t)m * sizeof(hb_result), hipMemcpyDeviceToHost) != hipSuccess) return all(HB_ERR_HIP);
-    std::vector<uint8_t> host(P.out_bytes);
-    if (P.out_bytes && hipMemcpy(host.data(), d_out, P.out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return all(HB_ERR_HIP);
-    for (int i = 0; i < m; i++) {
-        const hb_result &r = res[(size_t)i];
-        const int j = P.carried[(size_t)i];
-        if (r.status != HB_OK) { rc[j] = r.status; continue; }          // (a failed job's destination keeps the caller's bytes)
-        if (r.bytes) place(P, (size_t)i, host.data() + P.ooff[(size_t)i], (uint8_t *)dst[j]);
-        rc[j] = (int64_t)r.bytes;
-    }
-    return HB_OK;
+    for (int i = 0; i < m; i++) pd[(size_t)i] = S.d_out + P.ooff[(size_t)i];
+    const int st = run(nframes, P.hd.data(), pf.data(), n, m, P.pj.data(), pd.data(), P.caps.data(), S.d_work, wb, (hb_result *)S.d_res, nullptr);
+    if (st) return answer_all(P.carried, rc, st);
+    const bool down = S.download_jobs(
+        P.out_bytes, P.ooff.data(),
+        [&](size_t i, const hb_result &r, const uint8_t *from) {
+            const int j = P.carried[i];
+            if (r.bytes) place(P, i, from, (uint8_t *)dst[j]);
+            rc[j] = (int64_t)r.bytes;
+        },
+        [&](size_t i, const hb_result &r) { rc[P.carried[i]] = r.status; });
+    return down ? HB_OK : answer_all(P.carried, rc, HB_ERR_HIP);
 }
 }  // extern "C++"
+
 // (host tables that do not fit into memory: the batch is one the caller has to split, as for cbx_prepare -- no exception crosses the C ABI)
 int hb_cblosc_getbox_frames_batch(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_cblosc_box_job *jobs, void *const *dst, const size_t *cap,
                                   int64_t *rc, int device) {
@@ -816,59 +814,6 @@ int hb_cblosc_getpoints_frames_batch(int nframes, const void *const *frame, cons
     } catch (const std::bad_alloc &) { return HB_ERR_BAD_ARG; }
 }
 
-// The records and the frames of a batched C-Blosc-1 encode come down (both host forms end here): the records in one copy; many small frames are
-// packed on the device and come down in ONE copy, large ones one copy each, as in hb_compress_frames_batch.  idx[i]: the caller's input that
-// carried frame i; pf[i]: its frame on the device.  `single` answers an input whose frame did not end with status 0.
-extern "C++" {
-template <class SINGLE>
-static int cbe_host_download(const std::vector<int> &idx, const std::vector<void *> &pf, const uint8_t *d_res, void *const *dst, const size_t *cap, int64_t *rc, Scratch &sc,
-                             SINGLE single) {
-    const int m = (int)idx.size();
-    auto fail_all = [&]() { for (int k : idx) rc[k] = HB_ERR_HIP; return HB_OK; };
-    std::vector<hb_result> res((size_t)m);
-    if (hipMemcpy(res.data(), d_res, (size_t)m * sizeof(hb_result), hipMemcpyDeviceToHost) != hipSuccess) return fail_all();
-    // download as in hb_compress_frames_batch: many small frames are packed on the device and come down in ONE copy, large ones one copy each
-    size_t total_out = 0;
-    std::vector<size_t> outs((size_t)m, 0), poff((size_t)m, 0);
-    std::vector<uint8_t> again((size_t)m, 0);
-    for (int i = 0; i < m; i++) {
-        const int k = idx[(size_t)i];
-        const hb_result &r = res[(size_t)i];
-        if (r.status) { again[(size_t)i] = 1; rc[k] = r.status; continue; }
-        if (r.bytes > cap[k]) { rc[k] = HB_ERR_SHORT_BUFFER; continue; }  // (what hb_cblosc_compress answers when the frame does not fit)
-        outs[(size_t)i] = (size_t)r.bytes; poff[(size_t)i] = total_out; total_out += (size_t)r.bytes; rc[k] = (int64_t)r.bytes;
-    }
-    const bool packed = m >= 16 && total_out / (size_t)m < ((size_t)256 << 10);
-    if (packed && total_out) {
-        std::vector<PackJob> jobs((size_t)m);
-        size_t mx = 0;
-        for (int i = 0; i < m; i++) { jobs[(size_t)i] = PackJob{(const uint8_t *)pf[(size_t)i], (uint64_t)poff[(size_t)i], (uint64_t)outs[(size_t)i]}; mx = std::max(mx, outs[(size_t)i]); }
-        uint8_t *d_pack = sc.get(total_out + 256), *d_jobs = sc.get((size_t)m * sizeof(PackJob));
-        std::vector<uint8_t> host(total_out);
-        bool good = d_pack && d_jobs && hipMemcpyAsync(d_jobs, jobs.data(), (size_t)m * sizeof(PackJob), hipMemcpyHostToDevice, nullptr) == hipSuccess;
-        for (int j0 = 0; good && j0 < m; j0 += 65535) {
-            const unsigned ny = (unsigned)std::min(65535, m - j0), gx = (unsigned)std::min<size_t>(16, (mx + 65535) / 65536);
-            hipLaunchKernelGGL(k_bt_pack, dim3(gx ? gx : 1, ny), dim3(256), 0, nullptr, (const PackJob *)d_jobs + j0, d_pack);
-        }
-        good = good && hipMemcpy(host.data(), d_pack, total_out, hipMemcpyDeviceToHost) == hipSuccess;
-        for (int i = 0; i < m; i++) {
-            const int k = idx[(size_t)i];
-            if (rc[k] < 0) continue;
-            if (good) memcpy(dst[k], host.data() + poff[(size_t)i], outs[(size_t)i]); else rc[k] = HB_ERR_HIP;
-        }
-    } else {
-        for (int i = 0; i < m; i++) {
-            const int k = idx[(size_t)i];
-            if (rc[k] < 0) continue;
-            if (hipMemcpyAsync(dst[k], pf[(size_t)i], outs[(size_t)i], hipMemcpyDeviceToHost, nullptr) != hipSuccess) rc[k] = HB_ERR_HIP;
-        }
-        if (hipStreamSynchronize(nullptr) != hipSuccess) return fail_all();
-    }
-    for (int i = 0; i < m; i++) if (again[(size_t)i]) single(idx[(size_t)i]);
-    return HB_OK;
-}
-}  // extern "C++"
-
 // Many inputs to C-Blosc-1 frames (include/hipblosc.h).  cbe_host_plan (hb_cblosc_enc_batch.h) says which inputs the batch carries and where they
 // and their frames lie on the device; whatever it does not carry, and whatever did not end with status 0 on the device, is answered by
 // hb_cblosc_compress, so that rc[k] is its answer in every case.
@@ -886,24 +831,18 @@ int hb_cblosc_compress_frames_batch(int nframes, const void *const *src, const s
     for (int k : P.idx) carried[(size_t)k] = 1;
     for (int k = 0; k < nframes; k++) if (!carried[(size_t)k]) single(k);
     if (m == 0) return HB_OK;
-    auto rest_single = [&]() { for (int k : P.idx) single(k); return HB_OK; };
-    if (hb_select_device(device) != HB_OK) return rest_single();
+    if (hb_select_device(device) != HB_OK) return answer_all(P.idx, rc, single);
     const size_t wb = hb_cblosc_compress_frames_batch_workspace(m, P.ns.data(), shuffle, typesize);
-    if (!wb) return rest_single();                                       // (a batch beyond the 32-bit limits: one call per input is still right)
-    auto fail_all = [&]() { for (int k : P.idx) rc[k] = HB_ERR_HIP; return HB_OK; };
-    Scratch sc(device);
-    uint8_t *d_in = sc.get(P.in_bytes + 256), *d_out = sc.get(P.out_bytes + 256), *d_work = sc.get(wb), *d_res = sc.get((size_t)m * sizeof(hb_result));
-    if (!d_in || !d_out || !d_work || !d_res) return fail_all();
-    d_in += (16u - ((uintptr_t)d_in & 15u)) & 15u;                       // (the plan's offsets are multiples of 16: so are the addresses)
-    if (P.span_in && hipMemcpyAsync(d_in, src[P.idx[0]], P.in_bytes - 64, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
+    if (!wb) return answer_all(P.idx, rc, single);                      // (a batch beyond the 32-bit limits: one call per input is still right)
+    BatchStage S(device);
+    if (!S.take(P.in_bytes, P.out_bytes, wb, (size_t)m, true)) return answer_all(P.idx, rc, HB_ERR_HIP);
     std::vector<const void *> ps((size_t)m); std::vector<void *> pf((size_t)m);
-    for (int i = 0; i < m; i++) {
-        ps[(size_t)i] = d_in + P.ioff[(size_t)i]; pf[(size_t)i] = d_out + P.ooff[(size_t)i];
-        if (!P.span_in && P.ns[(size_t)i] && hipMemcpyAsync(d_in + P.ioff[(size_t)i], src[P.idx[(size_t)i]], P.ns[(size_t)i], hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-    }
-    const int st = hb_cblosc_compress_frames_batch_device(m, ps.data(), P.ns.data(), pf.data(), P.caps.data(), shuffle, typesize, d_work, wb, (hb_result *)d_res, nullptr);
-    if (st) { for (int k : P.idx) rc[k] = st; return HB_OK; }
-    return cbe_host_download(P.idx, pf, d_res, dst, cap, rc, sc, single);
+    std::vector<UpItem> up((size_t)m);
+    for (int i = 0; i < m; i++) { ps[(size_t)i] = S.d_in + P.ioff[(size_t)i]; pf[(size_t)i] = S.d_out + P.ooff[(size_t)i]; up[(size_t)i] = UpItem{src[P.idx[(size_t)i]], P.ns[(size_t)i], P.ioff[(size_t)i]}; }
+    if (!S.upload(S.d_in, up, P.span_in)) return answer_all(P.idx, rc, HB_ERR_HIP);
+    const int st = hb_cblosc_compress_frames_batch_device(m, ps.data(), P.ns.data(), pf.data(), P.caps.data(), shuffle, typesize, S.d_work, wb, (hb_result *)S.d_res, nullptr);
+    if (st) return answer_all(P.idx, rc, st);
+    return S.download_frames(P.idx, pf, dst, cap, rc, [](const hb_result &r) { return (size_t)r.bytes; }, single);
 }
 
 // Many source boxes to C-Blosc-1 frames (include/hipblosc.h).  cbxe_host_plan (hb_cblosc_enc_box_batch.h) answers what has no assembled chunk
@@ -935,27 +874,24 @@ static int cbxe_host_call(int nframes, const hb_cblosc_src_box *boxes, const voi
         else if (!carried[(size_t)k]) single(k);
     }
     if (m == 0) return HB_OK;
-    auto rest_single = [&]() { for (int k : P.carried) single(k); return HB_OK; };
-    if (hb_select_device(device) != HB_OK) return rest_single();
+    if (hb_select_device(device) != HB_OK) return answer_all(P.carried, rc, single);
     const size_t wb = hb_cblosc_compress_boxes_batch_workspace(m, P.pb.data(), shuffle, typesize);
-    if (!wb) return rest_single();                                       // (a batch beyond the 32-bit limits: one call per chunk is still right)
-    auto fail_all = [&]() { for (int k : P.carried) rc[k] = HB_ERR_HIP; return HB_OK; };
-    Scratch sc(device);
-    uint8_t *d_in = sc.get(P.in_bytes + 256), *d_out = sc.get(P.out_bytes + 256), *d_work = sc.get(wb), *d_res = sc.get((size_t)m * sizeof(hb_result));
-    if (!d_in || !d_out || !d_work || !d_res) return fail_all();
-    d_in += (16u - ((uintptr_t)d_in & 15u)) & 15u;                       // (the plan's offsets are multiples of 16: so are the addresses)
+    if (!wb) return answer_all(P.carried, rc, single);                  // (a batch beyond the 32-bit limits: one call per chunk is still right)
+    BatchStage S(device);
+    if (!S.take(P.in_bytes, P.out_bytes, wb, (size_t)m, true)) return answer_all(P.carried, rc, HB_ERR_HIP);
     std::vector<uint8_t> packed(P.in_bytes, 0);
     std::vector<const void *> ps((size_t)m); std::vector<void *> pf((size_t)m);
     for (int i = 0; i < m; i++) {
         const int k = P.carried[(size_t)i];
         cbxe_pack_box(P.geom[(size_t)k], (const uint8_t *)src[k], packed.data() + P.ioff[(size_t)i]);
-        ps[(size_t)i] = d_in + P.ioff[(size_t)i]; pf[(size_t)i] = d_out + P.ooff[(size_t)i];
+        ps[(size_t)i] = S.d_in + P.ioff[(size_t)i]; pf[(size_t)i] = S.d_out + P.ooff[(size_t)i];
     }
-    if (P.in_bytes && hipMemcpyAsync(d_in, packed.data(), P.in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-    const int st = hb_cblosc_compress_boxes_batch_device(m, P.pb.data(), ps.data(), pf.data(), P.caps.data(), fill, shuffle, typesize, d_work, wb, (hb_result *)d_res, nullptr);
-    if (st) { (void)hipStreamSynchronize(nullptr); return rest_single(); }     // (`packed` is pageable: the copy has to be over before it goes)
-    return cbe_host_download(P.carried, pf, d_res, dst, cap, rc, sc, single);
+    if (!S.upload(S.d_in, {UpItem{packed.data(), P.in_bytes, 0}}, false)) return answer_all(P.carried, rc, HB_ERR_HIP);
+    const int st = hb_cblosc_compress_boxes_batch_device(m, P.pb.data(), ps.data(), pf.data(), P.caps.data(), fill, shuffle, typesize, S.d_work, wb, (hb_result *)S.d_res, nullptr);
+    if (st) { S.wait_uploads(); return answer_all(P.carried, rc, single); }
+    return S.download_frames(P.carried, pf, dst, cap, rc, [](const hb_result &r) { return (size_t)r.bytes; }, single);
 }
+
 // (host tables that do not fit into memory: the batch is one the caller has to split -- no exception crosses the C ABI)
 int hb_cblosc_compress_boxes_batch(int nframes, const hb_cblosc_src_box *boxes, const void *const *src, void *const *dst, const size_t *cap, int64_t *rc, const void *fill,
                                    int shuffle, int typesize, int device) {
@@ -1066,40 +1002,40 @@ static int cbu_host_call(KIND kind, int njobs, const void *const *old, const siz
         else if (!carried[(size_t)k]) single(k);
     }
     if (m == 0) return HB_OK;
-    auto rest_single = [&]() { for (int k : P.carried) single(k); return HB_OK; };
-    if (hb_select_device(device) != HB_OK) return rest_single();
+    if (hb_select_device(device) != HB_OK) return answer_all(P.carried, rc, single);
     std::vector<size_t> on((size_t)m, 0);
     for (int i = 0; i < m; i++) {
         const int k = P.carried[(size_t)i];
         on[(size_t)i] = P.base[(size_t)k] == CBXU_OLD ? old_n[k] : 0;     // (no base: its old frame is not looked at, here or there)
     }
     const size_t wb = kind.workspace(m, P, on.data(), shuffle, typesize);
-    if (!wb) return rest_single();                                       // (a batch beyond the 32-bit limits: one call per chunk is still right)
-    auto fail_all = [&]() { for (int k : P.carried) rc[k] = HB_ERR_HIP; return HB_OK; };
-    Scratch sc(device);
-    uint8_t *d_in = sc.get(P.in_bytes + 256), *d_old = sc.get(P.old_bytes + 256), *d_out = sc.get(P.out_bytes + 256), *d_work = sc.get(wb),
-            *d_res = sc.get((size_t)m * sizeof(hb_result));
-    if (!d_in || !d_old || !d_out || !d_work || !d_res) return fail_all();
-    d_in += (16u - ((uintptr_t)d_in & 15u)) & 15u;                       // (the plan's offsets are multiples of 16: so are the addresses)
-    d_old += (16u - ((uintptr_t)d_old & 15u)) & 15u;
+    if (!wb) return answer_all(P.carried, rc, single);                  // (a batch beyond the 32-bit limits: one call per chunk is still right)
+    BatchStage S(device);
+    if (!S.take(P.in_bytes, P.out_bytes, wb, (size_t)m, true, &P.old_bytes)) return answer_all(P.carried, rc, HB_ERR_HIP);
     std::vector<uint8_t> packed(P.in_bytes, 0);
     std::vector<const void *> ps((size_t)m), po((size_t)m, nullptr); std::vector<void *> pf((size_t)m);
-    bool first_old = true;
+    std::vector<UpItem> olds;
+    for (int i = 0; i < m; i++) {
+        const int k = P.carried[(size_t)i];
+        ps[(size_t)i] = S.d_in + P.ioff[(size_t)i]; pf[(size_t)i] = S.d_out + P.ooff[(size_t)i];
+        if (P.base[(size_t)k] != CBXU_OLD) continue;
+        po[(size_t)i] = S.d_old + P.foff[(size_t)i];
+        olds.push_back(UpItem{old[k], old_n[k], P.foff[(size_t)i]});
+    }
+    // a job's items are packed, then its old frame goes up (a span: all of it with the first one), so that the copies run while the host packs
+    size_t at = 0;
     for (int i = 0; i < m; i++) {
         const int k = P.carried[(size_t)i];
         if (P.geom[(size_t)k].e.src_bytes) kind.pack(P, k, typesize, (const uint8_t *)src[k], packed.data() + P.ioff[(size_t)i]);
-        ps[(size_t)i] = d_in + P.ioff[(size_t)i]; pf[(size_t)i] = d_out + P.ooff[(size_t)i];
         if (P.base[(size_t)k] != CBXU_OLD) continue;
-        po[(size_t)i] = d_old + P.foff[(size_t)i];
-        if (P.span_old) {
-            if (first_old && hipMemcpyAsync(d_old, old[k], P.old_bytes - 64, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-            first_old = false;
-        } else if (old_n[k] && hipMemcpyAsync(d_old + P.foff[(size_t)i], old[k], old_n[k], hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
+        const bool up = P.span_old ? (at != 0 || S.upload(S.d_old, olds, true)) : S.upload(S.d_old, {olds[at]}, false);
+        if (!up) return answer_all(P.carried, rc, HB_ERR_HIP);
+        at++;
     }
-    if (P.in_bytes && hipMemcpyAsync(d_in, packed.data(), P.in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail_all();
-    const int st = kind.run(m, P, po.data(), on.data(), ps.data(), pf.data(), fill, shuffle, typesize, d_work, wb, (hb_result *)d_res);
-    if (st) { (void)hipStreamSynchronize(nullptr); return rest_single(); }     // (`packed` is pageable: the copy has to be over before it goes)
-    return cbe_host_download(P.carried, pf, d_res, dst, cap, rc, sc, single);
+    if (!S.upload(S.d_in, {UpItem{packed.data(), P.in_bytes, 0}}, false)) return answer_all(P.carried, rc, HB_ERR_HIP);
+    const int st = kind.run(m, P, po.data(), on.data(), ps.data(), pf.data(), fill, shuffle, typesize, S.d_work, wb, (hb_result *)S.d_res);
+    if (st) { S.wait_uploads(); return answer_all(P.carried, rc, single); }
+    return S.download_frames(P.carried, pf, dst, cap, rc, [](const hb_result &r) { return (size_t)r.bytes; }, single);
 }
 }  // extern "C++"
 // (host tables that do not fit into memory: the batch is one the caller has to split -- no exception crosses the C ABI)

@@ -7,6 +7,7 @@
 #include <vector>
 #include "../../include/hipblosc.h"
 #include "hb_format.h"
+#include "hb_host_stage.h"
 
 #if defined(__HIPCC__)
 #define CB_HD __host__ __device__
@@ -260,9 +261,8 @@ static inline int cbb_prepare(int nframes, const hb_cblosc_header *hdrs, const v
 }
 
 // ---- the host form: which frames the batch carries and where they and their outputs lie in the device buffers ----
-// Frames that follow each other exactly in host memory go up in one copy (the device image mirrors the span), every other frame lies at a
-// 16-byte-aligned offset with 64 bytes of slack.  Destinations that follow each other inside their own capacities (dst[k+1] in
-// [dst[k] + nbytes, dst[k] + cap[k]]) get a device image of the same layout and come down in one copy.
+// The frames lie as hb_upload_plan says (hb_host_stage.h; 64 bytes of slack, 16-byte-aligned offsets), the outputs as hb_download_plan says
+// (64 bytes of slack, 256-byte-aligned offsets).
 struct CbbHostPlan {
     std::vector<int> idx;                // the frames the batch carries, in order
     std::vector<hb_cblosc_header> hd;
@@ -284,25 +284,10 @@ static inline void cbb_host_plan(int nframes, const void *const *frame, const si
     }
     const size_t m = P.idx.size();
     if (m == 0) return;
-    P.ns.resize(m); P.caps.resize(m); P.ioff.resize(m); P.ooff.resize(m);
-    P.span_in = m > 1;
-    for (size_t i = 0; P.span_in && i + 1 < m; i++)
-        P.span_in = (const uint8_t *)frame[P.idx[i]] + n[P.idx[i]] == (const uint8_t *)frame[P.idx[i + 1]];
-    P.span_out = m > 1;
-    for (size_t i = 0; P.span_out && i + 1 < m; i++) {
-        const uint8_t *a = (const uint8_t *)dst[P.idx[i]], *b = (const uint8_t *)dst[P.idx[i + 1]];
-        P.span_out = a && b && b >= a + P.hd[i].nbytes && b <= a + cap[P.idx[i]];
-    }
-    for (size_t i = 0; i < m; i++) {
-        P.ns[i] = n[P.idx[i]]; P.caps[i] = P.hd[i].nbytes;
-        P.ioff[i] = P.in_bytes; P.ooff[i] = P.out_bytes;
-        P.in_bytes += P.span_in ? P.ns[i] : (P.ns[i] + 64 + 15) & ~(size_t)15;
-        P.out_bytes += cb_align(P.caps[i] + 64);
-    }
-    if (P.span_out) {
-        const uint8_t *base = (const uint8_t *)dst[P.idx[0]];
-        for (size_t i = 0; i < m; i++) P.ooff[i] = (size_t)((const uint8_t *)dst[P.idx[i]] - base);
-        P.span_bytes = P.ooff[m - 1] + P.hd[m - 1].nbytes;
-        P.out_bytes = P.span_bytes + 64;
-    }
+    P.ns.resize(m); P.caps.resize(m);
+    for (size_t i = 0; i < m; i++) { P.ns[i] = n[P.idx[i]]; P.caps[i] = P.hd[i].nbytes; }
+    HbUpload U = hb_upload_plan(P.idx, frame, n, 64, 16);
+    HbDownload D = hb_download_plan(P.idx, dst, P.caps.data(), cap, 64, 256);
+    P.span_in = U.span; P.in_bytes = U.bytes; P.ioff.swap(U.off);
+    P.span_out = D.span; P.out_bytes = D.bytes; P.span_bytes = D.span_bytes; P.ooff.swap(D.off);
 }

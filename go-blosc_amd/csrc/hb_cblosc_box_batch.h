@@ -499,8 +499,8 @@ static inline size_t cbx_workspace(int nframes, const hb_cblosc_header *hdrs, co
 }
 
 // ---- the host form: what each job is answered with before the device is asked, which jobs the batch carries (with their boxes C-contiguous
-// in one packed device buffer: job i's bytes follow those of the carried jobs before it), which frames go up and where.  Frames that follow
-// each other exactly in host memory go up in one copy. ----
+// in one packed device buffer: job i's bytes follow those of the carried jobs before it), which frames go up and where (hb_upload_plan of
+// hb_host_stage.h; 64 bytes of slack, 256-byte-aligned offsets). ----
 template <class JOB>
 struct CbxHostPlanOf {
     std::vector<hb_cblosc_header> hd;    // per frame; a frame that does not parse keeps a zeroed record
@@ -519,15 +519,6 @@ template <class JOB>
 static inline void cbx_host_plan_reset(CbxHostPlanOf<JOB> &P, size_t nf, size_t nj) {
     P.hd.assign(nf, hb_cblosc_header{}); P.status.assign(nj, 0); P.carried.clear(); P.pj.clear(); P.geom.clear(); P.ooff.clear(); P.caps.clear(); P.idx.clear(); P.ioff.assign(nf, 0);
     P.in_bytes = P.out_bytes = 0; P.span_in = false;
-}
-// the frames that go up (used[k]: a carried job reads frame k) and where
-template <class JOB>
-static inline void cbx_host_plan_frames(CbxHostPlanOf<JOB> &P, int nframes, const void *const *frame, const size_t *n, const std::vector<uint8_t> &used) {
-    for (int k = 0; k < nframes; k++) if (used[(size_t)k]) P.idx.push_back(k);
-    P.span_in = P.idx.size() > 1;
-    for (size_t i = 0; P.span_in && i + 1 < P.idx.size(); i++)
-        P.span_in = (const uint8_t *)frame[P.idx[i]] + n[P.idx[i]] == (const uint8_t *)frame[P.idx[i + 1]];
-    for (int k : P.idx) { P.ioff[(size_t)k] = P.in_bytes; P.in_bytes += P.span_in ? n[k] : cb_align(n[k] + 64); }
 }
 static inline const int64_t *cbx_extent(const hb_cblosc_box_job &q) { return q.shape; }      // the items per dimension that a job writes
 // (`refuse`: cbx_refusal, or cbs_refusal of hb_cblosc_slice_batch.h, as for cbx_prepare_)
@@ -554,7 +545,7 @@ static inline void cbx_host_plan_(int nframes, const void *const *frame, const s
         P.out_bytes += (size_t)g.bytes;
         used[q.frame] = 1;
     }
-    cbx_host_plan_frames(P, nframes, frame, n, used);
+    hb_upload_plan_frames(P, nframes, frame, n, used);
 }
 static inline void cbx_host_plan(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_cblosc_box_job *jobs, void *const *dst, const size_t *cap,
                                  CbxHostPlan &P, unsigned accept = CB_ACCEPT_DEFAULT) {

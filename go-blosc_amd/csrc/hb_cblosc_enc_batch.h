@@ -211,9 +211,9 @@ static inline int cbe_prepare(int nframes, const void *const *d_src, const size_
 }
 
 // ---- the host form: which inputs the batch carries and where they and their frames lie in the device buffers ----
-// Inputs that follow each other exactly in host memory go up in one copy (the device image mirrors the span) -- only while every input's
-// offset in it stays 16-byte aligned, so that each frame takes the route hb_cblosc_compress takes from its aligned staging buffer; every other
-// input lies at a 16-byte-aligned offset with 64 bytes of slack.  Every frame gets hb_cblosc_bound + 64 bytes, as hb_cblosc_compress gives it.
+// The inputs lie as hb_upload_plan says (hb_host_stage.h; 64 bytes of slack, 16-byte-aligned offsets) -- a span only while every input's
+// offset in it stays 16-byte aligned, so that each frame takes the route hb_cblosc_compress takes from its aligned staging buffer.  Every frame
+// gets hb_cblosc_bound + 64 bytes, as hb_cblosc_compress gives it.
 struct CbeHostPlan {
     std::vector<int> idx;                // the inputs the batch carries, in order
     std::vector<size_t> ns, caps, ioff, ooff;
@@ -227,20 +227,13 @@ static inline void cbe_host_plan(int nframes, const void *const *src, const size
         if ((src[k] || !n[k]) && dst[k] && !cbe_too_large(n[k])) P.idx.push_back(k);      // (the others are hb_cblosc_compress's to answer)
     const size_t m = P.idx.size();
     if (m == 0) return;
-    P.ns.resize(m); P.caps.resize(m); P.ioff.resize(m); P.ooff.resize(m);
-    P.span_in = m > 1;
-    size_t at = 0;
-    for (size_t i = 0; P.span_in && i < m; i++) {
-        const int k = P.idx[i];
-        if (!src[k] || at % 16 != 0) { P.span_in = false; break; }
-        if (i + 1 < m && (const uint8_t *)src[k] + n[k] != (const uint8_t *)src[P.idx[i + 1]]) { P.span_in = false; break; }
-        at += n[k];
-    }
+    P.ns.resize(m); P.caps.resize(m); P.ooff.resize(m);
     for (size_t i = 0; i < m; i++) {
         P.ns[i] = n[P.idx[i]]; P.caps[i] = cbe_bound(P.ns[i], typesize) + 64;
-        P.ioff[i] = P.in_bytes; P.ooff[i] = P.out_bytes;
-        P.in_bytes += P.span_in ? P.ns[i] : (P.ns[i] + 64 + 15) & ~(size_t)15;
+        P.ooff[i] = P.out_bytes;
         P.out_bytes += cb_align(P.caps[i]);
     }
-    if (P.span_in) P.in_bytes += 64;                                       // (slack behind the last input, as every other input has it)
+    HbUpload U = hb_upload_plan(P.idx, src, n, 64, 16, 16);
+    P.span_in = U.span; P.ioff.swap(U.off);
+    P.in_bytes = U.bytes + (U.span ? 64 : 0);                              // (slack behind the last input, as every other input has it)
 }

@@ -277,17 +277,19 @@ static inline size_t cbg_workspace(int nframes, const hb_cblosc_header *hdrs, co
 }
 
 // ---- the host form: which jobs the batch carries, which frames go up and where, and where each job's bytes lie in the packed device buffer ----
-// Frames that follow each other exactly in host memory go up in one copy (the device image mirrors the span), every other frame lies at a
-// 256-byte-aligned offset with 64 bytes of slack.  Job j's bytes follow those of the carried jobs before it.
-struct CbgHostPlan {
-    std::vector<hb_cblosc_header> hd;    // per frame; a frame that does not parse keeps a zeroed record, which the device form refuses job by job
-    std::vector<uint8_t> carried;        // per job
+// The frames lie as hb_upload_plan says (hb_host_stage.h; 64 bytes of slack, 256-byte-aligned offsets).  Job j's bytes follow those of the
+// carried jobs before it.  The go-blosc-format form fills the same plan over its own header type (hb_batch.hip).
+template <class HDR>
+struct GetitemHostPlanOf {
+    std::vector<HDR> hd;                 // per frame; a frame that does not parse keeps a zeroed record, which the device form refuses job by job
+    std::vector<uint8_t> carried;        // per job: the device form gets a destination for it
     std::vector<int> idx;                // the frames that a carried job reads, in order
     std::vector<size_t> ioff;            // per frame
     std::vector<size_t> ooff, nb;        // per job
     size_t in_bytes, out_bytes;
     bool span_in, any;
 };
+typedef GetitemHostPlanOf<hb_cblosc_header> CbgHostPlan;
 static inline void cbg_host_plan(int nframes, const void *const *frame, const size_t *n, int njobs, const hb_getitem_job *jobs, void *const *dst, const size_t *cap,
                                  CbgHostPlan &P, unsigned accept = CB_ACCEPT_DEFAULT) {
     const size_t nf = (size_t)nframes, nj = (size_t)njobs;
@@ -306,9 +308,5 @@ static inline void cbg_host_plan(int nframes, const void *const *frame, const si
         P.carried[j] = 1; P.nb[j] = (size_t)r.bytes; P.ooff[j] = P.out_bytes; P.out_bytes += (size_t)r.bytes;
         used[q.frame] = 1; P.any = true;
     }
-    for (int k = 0; k < nframes; k++) if (used[(size_t)k]) P.idx.push_back(k);
-    P.span_in = P.idx.size() > 1;
-    for (size_t i = 0; P.span_in && i + 1 < P.idx.size(); i++)
-        P.span_in = (const uint8_t *)frame[P.idx[i]] + n[P.idx[i]] == (const uint8_t *)frame[P.idx[i + 1]];
-    for (int k : P.idx) { P.ioff[(size_t)k] = P.in_bytes; P.in_bytes += P.span_in ? n[k] : cb_align(n[k] + 64); }
+    hb_upload_plan_frames(P, nframes, frame, n, used);
 }

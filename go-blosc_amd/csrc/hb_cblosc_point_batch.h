@@ -223,7 +223,7 @@ static inline void cbp_host_plan(int nframes, const void *const *frame, const si
         P.out_bytes += (size_t)S.bytes;
         used[q.frame] = 1;
     }
-    cbx_host_plan_frames(P, nframes, frame, n, used);
+    hb_upload_plan_frames(P, nframes, frame, n, used);
 }
 // job q's items, packed in the order of its points, to their places in the caller's array
 static inline void cbp_place(const hb_cblosc_point_job &q, const hb_cblosc_point *points, uint32_t ts, const uint8_t *packed, uint8_t *dst) {

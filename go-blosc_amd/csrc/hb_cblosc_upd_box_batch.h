@@ -294,8 +294,8 @@ static inline size_t cbxu_workspace(int njobs, const hb_cblosc_upd_box *boxes, c
 
 // ---- the host form ----
 // Which jobs the batch carries, with the strides of their packed boxes, and where the old frames, the packed boxes and the new frames lie in
-// the device buffers: old frames that follow each other exactly in host memory mirror their span (one copy), every other one lies at a
-// 16-byte-aligned offset with 64 bytes of slack; packed boxes and frames as in CbxeHostPlan.  An old frame that is not read (no base) is not
+// the device buffers: the old frames as hb_upload_plan says (hb_host_stage.h; 64 bytes of slack, 16-byte-aligned offsets); packed boxes and
+// frames as in CbxeHostPlan.  An old frame that is not read (no base) is not
 // dereferenced.
 template <class JOB>
 struct CbxuHostPlanOf {
@@ -339,24 +339,14 @@ static inline void cbxu_host_plan_(int njobs, const void *const *old, const size
     // the old frames that go up
     const size_t m = P.carried.size();
     P.foff.assign(m, 0);
-    size_t nold = 0;
-    const uint8_t *prev_end = nullptr;
-    bool span = true;
-    for (size_t i = 0; i < m; i++) {
-        const int k = P.carried[i];
-        if (P.base[(size_t)k] != CBXU_OLD) continue;
-        if (nold && (const uint8_t *)old[k] != prev_end) span = false;
-        prev_end = (const uint8_t *)old[k] + old_n[k];
-        nold++;
-    }
-    P.span_old = span && nold > 1;
-    for (size_t i = 0; i < m; i++) {
-        const int k = P.carried[i];
-        if (P.base[(size_t)k] != CBXU_OLD) continue;
-        P.foff[i] = P.old_bytes;
-        P.old_bytes += P.span_old ? old_n[k] : (old_n[k] + 64 + 15) & ~(size_t)15;
-    }
-    if (P.span_old) P.old_bytes += 64;
+    std::vector<int> olds;
+    std::vector<size_t> at;
+    for (size_t i = 0; i < m; i++)
+        if (P.base[(size_t)P.carried[i]] == CBXU_OLD) { olds.push_back(P.carried[i]); at.push_back(i); }
+    const HbUpload U = hb_upload_plan(olds, old, old_n, 64, 16);
+    P.span_old = U.span;
+    P.old_bytes = U.bytes + (U.span ? 64 : 0);                             // (slack behind the last old frame, as every other one has it)
+    for (size_t j = 0; j < at.size(); j++) P.foff[at[j]] = U.off[j];
 }
 static inline void cbxu_host_plan(int njobs, const hb_cblosc_upd_box *boxes, const void *const *old, const size_t *old_n, const void *const *src, void *const *dst,
                                   int typesize, unsigned accept, CbxuHostPlan &P) {

@@ -246,6 +246,58 @@ int main() {
         for (uint8_t *p : own) std::free(p);
         std::free(slab); std::free(oslab);
     }
+    // ---- hb_host_stage.h: which inputs go up in one copy and where, which destinations come down in one copy and from where ----
+    {
+        static uint8_t buf[4096];
+        static const size_t pairs[2][2] = {{64, 16}, {16, 256}};            // (slack, alignment)
+        for (int pi = 0; pi < 2; pi++) {
+            const size_t slack = pairs[pi][0], al = pairs[pi][1];
+            auto slot = [&](size_t n) { return (n + slack + al - 1) / al * al; };
+            // no item
+            HbUpload U = hb_upload_plan({}, nullptr, nullptr, slack, al);
+            REQUIRE(!U.span && U.bytes == 0 && U.off.empty());
+            HbDownload D = hb_download_plan({}, nullptr, nullptr, nullptr, slack, al);
+            REQUIRE(!D.span && D.bytes == 0 && D.span_bytes == 0 && D.off.empty());
+            // one item: no span (items 1 and 2 of the arrays are the ones carried below; item 0 is never looked at)
+            const void *p[4] = {nullptr, buf + 100, buf + 100 + 37, buf + 100 + 37};
+            size_t len[4] = {7, 37, 41, 0};
+            U = hb_upload_plan({1}, p, len, slack, al);
+            REQUIRE(!U.span && U.off.size() == 1 && U.off[0] == 0 && U.bytes == slot(37));
+            // two exactly adjacent
+            U = hb_upload_plan({1, 2}, p, len, slack, al);
+            REQUIRE(U.span && U.off[0] == 0 && U.off[1] == 37 && U.bytes == 37 + 41);
+            U = hb_upload_plan({1, 2}, p, len, slack, al, 16);               // ... but the second offset is no multiple of 16
+            REQUIRE(!U.span && U.off[0] == 0 && U.off[1] == slot(37) && U.bytes == slot(37) + slot(41));
+            // two with a one-byte gap
+            p[2] = buf + 100 + 38;
+            U = hb_upload_plan({1, 2}, p, len, slack, al);
+            REQUIRE(!U.span && U.off[0] == 0 && U.off[1] == slot(37) && U.bytes == slot(37) + slot(41));
+            // adjacent with a zero-length member in the middle
+            p[2] = buf + 100 + 37; p[3] = buf + 100 + 37; len[2] = 0; len[3] = 41;
+            U = hb_upload_plan({1, 2, 3}, p, len, slack, al);
+            REQUIRE(U.span && U.off[0] == 0 && U.off[1] == 37 && U.off[2] == 37 && U.bytes == 37 + 41);
+            p[3] = buf + 100 + 36;                                            // (the same three, the last one a byte early)
+            U = hb_upload_plan({1, 2, 3}, p, len, slack, al);
+            REQUIRE(!U.span && U.off[0] == 0 && U.off[1] == slot(37) && U.off[2] == slot(37) + slot(0) && U.bytes == slot(37) + slot(0) + slot(41));
+            // destinations: nbytes 30 and 50, the first with a capacity of 40
+            void *d[3] = {nullptr, buf + 1000, nullptr};
+            const size_t nb[2] = {30, 50}, cap[3] = {0, 40, 50};
+            d[2] = buf + 1000 + 30;                                           // at dst + nbytes exactly
+            D = hb_download_plan({1, 2}, d, nb, cap, slack, al);
+            REQUIRE(D.span && D.off[0] == 0 && D.off[1] == 30 && D.span_bytes == 80 && D.bytes == 80 + slack);
+            d[2] = buf + 1000 + 40;                                           // at dst + cap exactly
+            D = hb_download_plan({1, 2}, d, nb, cap, slack, al);
+            REQUIRE(D.span && D.off[0] == 0 && D.off[1] == 40 && D.span_bytes == 90 && D.bytes == 90 + slack);
+            d[2] = buf + 1000 + 41;                                           // one byte beyond the capacity
+            D = hb_download_plan({1, 2}, d, nb, cap, slack, al);
+            REQUIRE(!D.span && D.off[0] == 0 && D.off[1] == slot(30) && D.span_bytes == 0 && D.bytes == slot(30) + slot(50));
+            d[2] = buf + 1000 + 29;                                           // (and one byte inside the first result)
+            D = hb_download_plan({1, 2}, d, nb, cap, slack, al);
+            REQUIRE(!D.span && D.off[0] == 0 && D.off[1] == slot(30) && D.span_bytes == 0 && D.bytes == slot(30) + slot(50));
+            D = hb_download_plan({1}, d, nb, cap, slack, al);                 // one destination: no span
+            REQUIRE(!D.span && D.off[0] == 0 && D.span_bytes == 0 && D.bytes == slot(30));
+        }
+    }
     std::puts("cblosc batch host code ok under ASan + UBSan");
     return 0;
 }
