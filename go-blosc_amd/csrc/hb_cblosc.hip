@@ -16,13 +16,16 @@
 // Blocks and streams are independent, so there is no discovery problem here: k_cb_plan lists the streams (one lane per block
 // walks its cbytes fields), k_cb_streams puts one wavefront on every stream (streams are 8-256 KiB, hundreds to thousands per
 // frame), k_cb_unfilter undoes the per-block filter.  LZ4 / LZ4HC and memcpyed frames, and -- once hb_cblosc_accept_codecs(0x3)
-// has said so -- BloscLZ (the same decoder behind bz_walk, hb_lz4_region.h); the other codec formats are entropy coders.
+// has said so -- BloscLZ (the same decoder behind bz_walk, hb_lz4_region.h), and with bit 4 of that mask zstd: a stream is one Zstandard
+// frame, Huffman literals and FSE sequences decoded by one wavefront (hb_zstd_dec.h, cb_decode_zstd_stream); zlib and snappy are not read
+// (DESIGN.md §7).
 // ONE stream-decode kernel serves every path: k_cb_streams<SPACE, WHICH>, a loop over the permuted stream order with the LZ4, the
-// BloscLZ or the small (LDS-resident) decoder as its body.  A SPACE says who owns stream i -- the one frame of the call (CbOneSpace),
+// BloscLZ, the small (LDS-resident) or the zstd decoder as its body.  A SPACE says who owns stream i -- the one frame of the call (CbOneSpace),
 // a frame of a batch (CbbSpace), a block record of a getitem / box / slice / update batch (CbgSpace) -- and cb_launch_streams launches
-// what the owners need, small, then LZ4, then BloscLZ, with cb_decode_schedule's grids (hb_cblosc_batch.h), under the profile stage
-// names k_cb_decode[_small|_blz], k_cbb_decode[...] and k_cbg_decode[...] of the three families.
+// what the owners need, small, then LZ4, then BloscLZ, then zstd, with cb_decode_schedule's grids (hb_cblosc_batch.h), under the profile
+// stage names k_cb_decode[_small|_blz|_zstd], k_cbb_decode[...] and k_cbg_decode[...] of the three families.
 #include "hb_sym_decode.h"
+#include "hb_zstd_dec.h"
 
 #include <atomic>
 #include <cstring>
@@ -65,7 +68,7 @@ __device__ __forceinline__ void cb_plan_block(const uint8_t *__restrict__ frame,
         p += 4u;
         // (longer than LZ4's worst case: no LZ4 stream of this output.  BloscLZ has no such bound -- literal runs may be as short as one byte, two
         // stream bytes per output byte, and the library decodes that: there the frame's own end is the only limit)
-        if (cb == 0u || cb > 0x7FFFFFFFu || (uint64_t)p + cb > cbytes || (!cb_is_blosclz(flags) && cb > neblock + neblock / 255u + 16u)) { bad = true; break; }
+        if (cb == 0u || cb > 0x7FFFFFFFu || (uint64_t)p + cb > cbytes || (cb_is_lz4(flags) && cb > neblock + neblock / 255u + 16u)) { bad = true; break; }
         CbStream st; st.src = p; st.csize = cb; st.dst = idx * blocksize + s * neblock; st.usize = neblock;
         out[s] = st;
         p += cb;
@@ -155,10 +158,129 @@ __device__ __forceinline__ void cb_decode_small_stream(const uint8_t *__restrict
     const uint32_t t0 = st.usize & ~15u;
     if (t0 + (uint32_t)lane < st.usize) o[t0 + lane] = s_out[t0 + lane];
 }
+// ---- zstd streams (codec format 4; accepted once hb_cblosc_accept_codecs has set bit 4): one wavefront per stream, zstd block by zstd block.
+// The format logic is hb_zstd_dec.h, the same functions the host runs serially: one lane parses the headers and builds the FSE tables in LDS
+// (ZsState), the wave fills the Huffman table, four lanes (one for a single stream) decode the Huffman streams, one lane decodes up to 64
+// sequences into a queue and has checked every length and offset by then, and the wave executes the queue: literal runs and matches are
+// wave-wide copies straight in global memory.  Huffman literals wait in the tail of the stream's own output (the no-overlap argument is at the
+// top of hb_zstd_dec.h), so the decoder needs no workspace of its own.  A match may copy bytes this wave stored a moment ago: it reads them
+// only behind sy_sync() (hb_sym_decode.h: every store of the wave has reached the cache the CU reads through, later loads are not started
+// early) -- once per match whose source reaches above `synced`, the output position at the last such wait, not once per sequence. ----
+__device__ __forceinline__ void zs_wave_fill(uint8_t *d, uint32_t v, uint32_t n, int lane) {
+    uint32_t head = (uint32_t)((4u - ((uintptr_t)d & 3u)) & 3u);
+    if (head > n) head = n;
+    if ((uint32_t)lane < head) d[lane] = (uint8_t)v;
+    const uint32_t body = (n - head) >> 2, w = v * 0x01010101u;
+    for (uint32_t i = lane; i < body; i += 64) *(uint32_t *)(d + head + 4u * i) = w;
+    const uint32_t done = head + 4u * body;
+    if (done + (uint32_t)lane < n) d[done + lane] = (uint8_t)v;
+}
+// `len` literals of the block at hand to out + o; `used`: how many went out before
+__device__ __forceinline__ void zs_wave_literals(const uint8_t *src, uint8_t *out, uint32_t lt, uint32_t lat, uint32_t used, uint32_t o, uint32_t len, int lane) {
+    if (len == 0u) return;
+    if (lt == ZS_LIT_RLE) zs_wave_fill(out + o, src[lat], len, lane);
+    else wave_copy_g2g(out + o, (lt == ZS_LIT_RAW ? src : (const uint8_t *)out) + lat + used, len, lane);      // (the tail: o <= lat + used, a copy downwards, chunk by chunk)
+}
+// An overlapping match (off < ml) repeats the `off` bytes in front of it: byte k is byte k % off of them.  The first 256 bytes go out four
+// per lane as one word (one modulo per lane, then a wrap-around count); the rest is copied from what the match has written itself, a whole
+// number of periods back, so that every pass is a copy without overlap, at least doubles what is there, and moves 16 bytes per lane -- a
+// run of 128 KiB (off 1) is ten passes.  The caller has waited for the bytes in front of o; every pass waits for the pass before it.
+__device__ __forceinline__ void zs_wave_overlap(uint8_t *out, uint32_t o, uint32_t off, uint32_t ml, int lane) {
+    const uint32_t from = o - off, n1 = ml < 256u ? ml : 256u, k = 4u * (uint32_t)lane;
+    if (k < n1) {
+        const uint32_t m = n1 - k < 4u ? n1 - k : 4u;
+        uint32_t i = k % off, v = 0u;
+        for (uint32_t j = 0; j < m; j++) { v |= (uint32_t)out[from + i] << (8u * j); i = i + 1u == off ? 0u : i + 1u; }
+        if (m == 4u) st4u(out + o + k, v);
+        else for (uint32_t j = 0; j < m; j++) out[o + k + j] = (uint8_t)(v >> (8u * j));
+    }
+    for (uint32_t done = n1; done < ml; ) {                                     // (every pass at least doubles `done`: log2(ml / 256) + 1 passes)
+        sy_sync();
+        const uint32_t back = (off + done) / off * off;                         // a multiple of the period, done < back <= off + done: the source starts at or behind o - off
+        const uint32_t len = ml - done < back ? ml - done : back;
+        wave_copy_g2g(out + o + done, out + o + done - back, len, lane);
+        done += len;
+    }
+}
+// one compressed block; S->ip at its content, S->produced = o.  false: refused.
+__device__ __forceinline__ bool zs_wave_block(ZsState *S, const uint8_t *src, uint8_t *out, const uint32_t U, const uint32_t block_end, uint32_t &o, uint32_t &synced, int lane) {
+    const uint32_t block_out = o;
+    if (lane == 0) S->ok = zs_literals_header(S, src, U) ? 1u : 0u;
+    wave_sync();
+    if (!RFL(S->ok)) return false;
+    const uint32_t lt = RFL(S->lit_type), lsize = RFL(S->lit_size), lat = RFL(S->lit_at), ns = RFL(S->nstreams);
+    if (RFL(S->lit_new_tree)) { zs_huf_fill(S, (uint32_t)lane, 64u); wave_sync(); }
+    if (ns) {
+        bool good = true;
+        if ((uint32_t)lane < ns)
+            good = zs_huf_stream(S->huf, S->huf_log, src + S->hs_at[lane], S->hs_n[lane], out + lat + S->hs_cnt[0] * (uint32_t)lane, S->hs_cnt[lane]);
+        if (hb_ballot(!good)) return false;
+        sy_sync();                                                              // the literals are read back below
+    }
+    if (lane == 0) S->ok = zs_sequences_header(S, src, block_end) ? 1u : 0u;
+    wave_sync();
+    if (!RFL(S->ok)) return false;
+    const uint32_t nseq = RFL(S->nseq);
+    uint32_t used = 0u;
+    for (uint32_t done = 0u; done < nseq; done += ZS_QUEUE) {                   // (nseq / 64 passes)
+        if (lane == 0) { bool k; S->produced = o; zs_seq_batch(S, src, U, &k); S->ok = k ? 1u : 0u; }
+        wave_sync();
+        if (!RFL(S->ok)) return false;
+        const uint32_t cnt = nseq - done < ZS_QUEUE ? nseq - done : ZS_QUEUE;
+        for (uint32_t q = 0; q < cnt; q++) {
+            const uint32_t ll = RFL(S->q_ll[q]), ml = RFL(S->q_ml[q]), off = RFL(S->q_off[q]);
+            zs_wave_literals(src, out, lt, lat, used, o, ll, lane);
+            used += ll; o += ll;
+            const uint32_t from = o - off;
+            if (from + (ml < off ? ml : off) > synced) { sy_sync(); synced = o; }      // the source holds bytes stored since the last wait
+            if (off >= ml) wave_copy_g2g(out + o, out + from, ml, lane);
+            else zs_wave_overlap(out, o, off, ml, lane);
+            o += ml;
+        }
+        wave_sync();
+    }
+    const uint32_t tail = lsize - used;                                         // the literals behind the last sequence
+    if (tail > U - o) return false;
+    zs_wave_literals(src, out, lt, lat, used, o, tail, lane);
+    o += tail;
+    if (lt == ZS_LIT_HUF) { sy_sync(); synced = o; }                            // (the next block's tail may be written over bytes this copy read)
+    return o - block_out <= ZS_BLOCK_MAX;
+}
+__device__ __forceinline__ void cb_decode_zstd_stream(const uint8_t *__restrict__ frame, CbPlan *plan, const CbStream st, uint8_t *dst, ZsState *S, int lane) {
+    if (st.usize == 0u) return;
+    if (st.csize == st.usize) { wave_copy_g2g(dst + st.dst, frame + st.src, st.usize, lane); return; }      // stored
+    const uint8_t *src = frame + st.src;
+    uint8_t *out = dst + st.dst;
+    const uint32_t N = st.csize, U = st.usize;
+    wave_sync();
+    if (lane == 0) S->ok = (N <= 0x7FFFFFFFu && zs_frame_header(S, src, N, U)) ? 1u : 0u;
+    wave_sync();
+    bool ok = RFL(S->ok) != 0u, last = false;
+    uint32_t o = 0u, synced = 0u;
+    for (uint32_t nb = 0u; ok && !last && nb <= N / 3u; nb++) {                 // (a block takes 3 bytes at least)
+        if (lane == 0) { S->produced = o; S->ok = zs_block_header(S, src, N, U) ? 1u : 0u; }
+        wave_sync();
+        if (!RFL(S->ok)) { ok = false; break; }
+        const uint32_t type = RFL(S->b_type), size = RFL(S->b_size), ip = RFL(S->ip);
+        last = RFL(S->b_last) != 0u;
+        wave_sync();
+        if (type == 0u) { wave_copy_g2g(out + o, src + ip, size, lane); o += size; if (lane == 0) S->ip = ip + size; }
+        else if (type == 1u) { zs_wave_fill(out + o, src[ip], size, lane); o += size; if (lane == 0) S->ip = ip + 1u; }
+        else ok = zs_wave_block(S, src, out, U, ip + size, o, synced, lane);
+        wave_sync();
+    }
+    if (ok) {
+        if (lane == 0) { S->produced = o; S->ok = (last && zs_frame_end(S, N, U)) ? 1u : 0u; }
+        wave_sync();
+        ok = RFL(S->ok) != 0u;
+    }
+    if (!ok && lane == 0) atomicExch(&plan->fail, 1u);
+    wave_sync();
+}
 // ---- who owns stream i: a space gives the unified loop below the wave-uniform context of a stream -- the compressed frame, the plan to read
-// and to fail, where the decoded bytes go, whether the owner's codec is BloscLZ, whether its streams are at most one chunk ("small": an LZ4
+// and to fail, where the decoded bytes go, the owner's codec format (each decoder passes the other codecs' owners by), whether its streams are at most one chunk ("small": an LZ4
 // owner only).  The owner index and the fail word come out of vector loads and go through RFL: the bodies above contain wave_sync. ----
-struct CbCtx { const uint8_t *frame; CbPlan *plan; uint8_t *target; bool blz, small; };
+struct CbCtx { const uint8_t *frame; CbPlan *plan; uint8_t *target; uint32_t codec; bool small; };
 // What the batches' spaces look up -- frame and block records, stream prefixes -- went up before the launch and nobody writes it while a kernel
 // runs.  It is read through the constant address space, so that these wave-uniform reads are scalar loads: a `const T *__restrict__` kernel
 // argument gets that by itself, a pointer inside an argument struct carries no such promise (as vector loads they cost k_cbb_decode 6 %:
@@ -168,9 +290,9 @@ template <class T>
 __device__ __forceinline__ CB_RO(T) *cb_ro(const T *p) { return (CB_RO(T) *)(uintptr_t)p; }
 // one frame (hb_cblosc_decompress_dev, hb_cblosc_getitem_device): what the host decided, for every stream
 struct CbOneSpace {
-    const uint8_t *frame; CbPlan *plan; uint8_t *target; int blz, small;
+    const uint8_t *frame; CbPlan *plan; uint8_t *target; int codec, small;
     static constexpr bool one_plan = true;                                 // one owner: the kernel tests its fail word once, on entry (per stream: +2.7 % on k_cb_decode, second_build_ms of the same file)
-    __device__ __forceinline__ CbCtx operator()(uint32_t) const { return CbCtx{frame, plan, target, blz != 0, small != 0}; }
+    __device__ __forceinline__ CbCtx operator()(uint32_t) const { return CbCtx{frame, plan, target, (uint32_t)codec, small != 0}; }
 };
 // a batch of whole frames: the frame that owns the stream -- its staged copy, or its destination when there is no filter to undo
 struct CbbSpace {
@@ -179,7 +301,7 @@ struct CbbSpace {
     __device__ __forceinline__ CbCtx operator()(uint32_t i) const {
         const uint32_t k = RFL(hb_owner(cb_ro(str0), nframes, i));
         CB_RO(CbbFrame) &F = cb_ro(frames)[k];
-        return CbCtx{F.frame, plans + k, F.stage_off ? work + F.stage_off : F.dst, cb_is_blosclz(F.flags), F.small != 0u};
+        return CbCtx{F.frame, plans + k, F.stage_off ? work + F.stage_off : F.dst, F.flags >> 5, F.small != 0u};
     }
 };
 // a batch of block records (the getitem, box, slice and update batches): the record's own plan, its staged copy as the target (also without a
@@ -191,15 +313,16 @@ struct CbgSpace {
         const uint32_t x = RFL(hb_owner(cb_ro(str0), nblk, i));
         CB_RO(CbgBlock) &K = cb_ro(blocks)[x];
         CB_RO(CbgFrame) &F = cb_ro(frames)[K.frame];
-        return CbCtx{F.frame, plans + x, work + K.stage_off, cb_is_blosclz(F.flags), F.small != 0u};
+        return CbCtx{F.frame, plans + x, work + K.stage_off, F.flags >> 5, F.small != 0u};
     }
 };
 // The one stream-decode kernel: one wavefront per stream of the space, in the permuted order (cb_stream_of) over all of it; the host's grids
 // are cb_decode_schedule's.  WHICH is the decoder: LZ4 (stored streams of LZ4 owners are copied here; with the small decoder launched, the
 // short streams of small owners are left to it), BloscLZ (the same decoder behind bz_walk, hb_lz4_region.h, stored streams included: an owner
-// has one codec, so each of the two passes the other's owners by), or the small decoder (small owners only: it selects by that and by size).
+// has one codec, so each passes the others' owners by), the small decoder (small owners only: it selects by that and by size), or zstd
+// (cb_decode_zstd_stream above, stored streams of zstd owners included).
 // In a batch a stream is skipped once its owner's plan has failed -- one value for the whole wave: nobody is left behind at a wave_sync.
-enum { CBW_LZ4 = 0, CBW_BLZ, CBW_SMALL };
+enum { CBW_LZ4 = 0, CBW_BLZ, CBW_SMALL, CBW_ZSTD };
 template <class SPACE, int WHICH>
 __global__ __launch_bounds__(64) void k_cb_streams(SPACE sp, const CbStream *__restrict__ streams, uint32_t nstreams, int small_launched, uint32_t P) {
     __shared__ __attribute__((aligned(16))) uint2 s_tq[DTQ];
@@ -216,10 +339,14 @@ __global__ __launch_bounds__(64) void k_cb_streams(SPACE sp, const CbStream *__r
             __shared__ __attribute__((aligned(16))) uint8_t s_out[CB_SMALL + 64];
             if (!c.small) continue;
             cb_decode_small_stream(c.frame, c.plan, cb_load_stream(streams, i), c.target, s_in, s_out, s_tq, lane);
+        } else if constexpr (WHICH == CBW_ZSTD) {
+            __shared__ __attribute__((aligned(16))) ZsState s_zs;
+            if (c.codec != CB_CODEC_ZSTD) continue;
+            cb_decode_zstd_stream(c.frame, c.plan, cb_load_stream(streams, i), c.target, &s_zs, lane);
         } else {
             __shared__ __attribute__((aligned(16))) uint8_t s_win[RG_PWIN + 128];
             __shared__ __attribute__((aligned(16))) uint8_t s_d[SY_IMG + 64];
-            if (c.blz != (WHICH == CBW_BLZ)) continue;
+            if (c.codec != (WHICH == CBW_BLZ ? CB_CODEC_BLOSCLZ : CB_CODEC_LZ4)) continue;
             cb_decode_stream<WHICH == CBW_BLZ ? RG_BLOSCLZ : RG_LZ4>(c.frame, c.plan, cb_load_stream(streams, i), c.target, WHICH == CBW_LZ4 && small_launched && c.small,
                                                                      s_win, s_tq, s_d, lane);
         }
@@ -237,10 +364,10 @@ static inline void cb_with_kind(int k, F &&f) {
     default: f(std::integral_constant<int, 3>{}); break;
     }
 }
-// The decoder launches of a space: the small decoder, LZ4, BloscLZ, each when an owner needs it, under the stage names of the family.
+// The decoder launches of a space: the small decoder, LZ4, BloscLZ, zstd, each when an owner needs it, under the stage names of the family.
 template <class SPACE>
-static void cb_launch_streams(const SPACE &sp, const CbStream *streams, uint32_t nstreams, uint32_t any_small, uint32_t any_lz4, uint32_t any_blz, uint32_t nsplit_all,
-                              const char *name_small, const char *name_lz4, const char *name_blz, hipStream_t s) {
+static void cb_launch_streams(const SPACE &sp, const CbStream *streams, uint32_t nstreams, uint32_t any_small, uint32_t any_lz4, uint32_t any_blz, uint32_t any_zstd, uint32_t nsplit_all,
+                              const char *name_small, const char *name_lz4, const char *name_blz, const char *name_zstd, hipStream_t s) {
     const CbSchedule S = cb_decode_schedule(nstreams, nsplit_all, any_small);
     auto launch = [&](auto which, uint32_t grid, const char *name) {
         hb_prof_begin(name, s);
@@ -250,6 +377,7 @@ static void cb_launch_streams(const SPACE &sp, const CbStream *streams, uint32_t
     if (any_small) launch(std::integral_constant<int, CBW_SMALL>{}, S.grid_small, name_small);
     if (any_lz4) launch(std::integral_constant<int, CBW_LZ4>{}, S.grid_lz4, name_lz4);      // (any owner can have stored streams: it runs next to the small one)
     if (any_blz) launch(std::integral_constant<int, CBW_BLZ>{}, S.grid_blz, name_blz);
+    if (any_zstd) launch(std::integral_constant<int, CBW_ZSTD>{}, S.grid_blz, name_zstd);      // (no workspace of its own: the grid needs no cap)
 }
 
 // ---- what the launch code of the read batches shares (the getitem batch and cbx_launch below) ----
@@ -1426,9 +1554,11 @@ static void cb_launch_blocks(const hb_cblosc_header *hdr, const uint8_t *d_frame
     hipLaunchKernelGGL(k_cb_plan, dim3((nblocks + 63) / 64), dim3(64), 0, s, d_frame, (uint64_t)n, hdr->nbytes, blocksize, hdr->cbytes, ts, flags, plan, streams, b0, nblocks);
     hb_prof_end(s);
     const bool blz = hdr->codec_format == CB_CODEC_BLOSCLZ;              // (accepted by the caller: hb_cblosc_accept_codecs)  One codec per frame: its decoder alone
-    const bool small = !blz && blocksize / nsplit <= HB_CHUNK;           // streams of at most one chunk: the LDS-resident decoder takes them
-    if (!blz && !small) { hb_prof_begin("k_cb_decode_small", s); hb_prof_end(s); }      // (every LZ4 frame reports the same stages, this one empty here: the rate tools' tables key on them)
-    cb_launch_streams(CbOneSpace{d_frame, plan, target, blz, small}, streams, nstreams, small, !blz, blz, nsplit, "k_cb_decode_small", "k_cb_decode", "k_cb_decode_blz", s);
+    const bool zstd = hdr->codec_format == CB_CODEC_ZSTD;
+    const bool small = !blz && !zstd && blocksize / nsplit <= HB_CHUNK;           // streams of at most one chunk: the LDS-resident decoder takes them
+    if (!blz && !zstd && !small) { hb_prof_begin("k_cb_decode_small", s); hb_prof_end(s); }      // (every LZ4 frame reports the same stages, this one empty here: the rate tools' tables key on them)
+    cb_launch_streams(CbOneSpace{d_frame, plan, target, (int)hdr->codec_format, small}, streams, nstreams, small, !blz && !zstd, blz, zstd, nsplit, "k_cb_decode_small", "k_cb_decode", "k_cb_decode_blz",
+                      "k_cb_decode_zstd", s);
     if (filtered) {
         hb_prof_begin("k_cb_unfilter", s);
         if (unshuf)
@@ -1556,8 +1686,8 @@ static int cbb_launch_batch(int nframes, const CbbBatch &B, uint8_t *w, hb_resul
         hb_prof_begin("k_cbb_plan", s);
         hipLaunchKernelGGL(k_cbb_plan, dim3((nblocks + 63u) / 64u), dim3(64), 0, s, d_frames, d_plans, d_blk0, (uint32_t)nframes, nblocks, d_streams);
         hb_prof_end(s);
-        cb_launch_streams(CbbSpace{d_frames, d_plans, d_str0, (uint32_t)nframes, w}, d_streams, nstreams, B.any_small, B.any_lz4, B.any_blz, B.nsplit_all,
-                          "k_cbb_decode_small", "k_cbb_decode", "k_cbb_decode_blz", s);
+        cb_launch_streams(CbbSpace{d_frames, d_plans, d_str0, (uint32_t)nframes, w}, d_streams, nstreams, B.any_small, B.any_lz4, B.any_blz, B.any_zstd, B.nsplit_all,
+                          "k_cbb_decode_small", "k_cbb_decode", "k_cbb_decode_blz", "k_cbb_decode_zstd", s);
     }
     for (int k = 0; k < CBK_COUNT; k++) {
         const uint32_t k0 = B.kind0[k], nk = B.kind0[k + 1] - k0, blocks = B.kblocks[k];
@@ -1642,13 +1772,13 @@ int hb_cblosc_getitem_device(const hb_cblosc_header *hdr, const void *d_frame, s
 
 // The plan and the stream decoders over the block records of a batch (hb_cblosc_getitem_frames_batch_device and hb_cblosc_getbox_frames_batch_device
 // build the same records): k_cbg_plan, then one decoder launch per kind that occurs (stages k_cbg_decode_small / k_cbg_decode / k_cbg_decode_blz).
-static void cbg_launch_decoders(uint32_t nblk, uint32_t nstreams, uint32_t any_small, uint32_t nsplit_all, uint32_t any_lz4, uint32_t any_blz, const CbgFrame *d_frames,
+static void cbg_launch_decoders(uint32_t nblk, uint32_t nstreams, uint32_t any_small, uint32_t nsplit_all, uint32_t any_lz4, uint32_t any_blz, uint32_t any_zstd, const CbgFrame *d_frames,
                                 const CbgBlock *d_blocks, CbPlan *d_plans, const uint32_t *d_str0, CbStream *d_streams, uint8_t *w, hipStream_t s) {
     hb_prof_begin("k_cbg_plan", s);
     hipLaunchKernelGGL(k_cbg_plan, dim3((nblk + 63u) / 64u), dim3(64), 0, s, d_frames, d_blocks, d_plans, nblk, d_streams);
     hb_prof_end(s);
-    cb_launch_streams(CbgSpace{d_frames, d_blocks, d_plans, d_str0, nblk, w}, d_streams, nstreams, any_small, any_lz4, any_blz, nsplit_all,
-                      "k_cbg_decode_small", "k_cbg_decode", "k_cbg_decode_blz", s);
+    cb_launch_streams(CbgSpace{d_frames, d_blocks, d_plans, d_str0, nblk, w}, d_streams, nstreams, any_small, any_lz4, any_blz, any_zstd, nsplit_all,
+                      "k_cbg_decode_small", "k_cbg_decode", "k_cbg_decode_blz", "k_cbg_decode_zstd", s);
 }
 
 // ---- many ranges of many frames, one set of launches (include/hipblosc.h; the host side is hb_cblosc_getitem_batch.h) ----
@@ -1684,7 +1814,7 @@ int hb_cblosc_getitem_frames_batch_device(int nframes, const hb_cblosc_header *h
     CbPlan *d_plans = cb_at<CbPlan>(w, L.plans);
     const uint32_t *d_gjob = cb_at<const uint32_t>(w, L.gjob), *d_gblk = cb_at<const uint32_t>(w, L.gblk);
     if (B.nstreams)
-        cbg_launch_decoders((uint32_t)B.nblk, (uint32_t)B.nstreams, B.any_small, B.nsplit_all, B.any_lz4, B.any_blz, d_frames, d_blocks, d_plans, cb_at<const uint32_t>(w, L.str0),
+        cbg_launch_decoders((uint32_t)B.nblk, (uint32_t)B.nstreams, B.any_small, B.nsplit_all, B.any_lz4, B.any_blz, B.any_zstd, d_frames, d_blocks, d_plans, cb_at<const uint32_t>(w, L.str0),
                             cb_at<CbStream>(w, L.streams), w, s);
     static const char *const gname[CBG_COUNT] = {"k_cbg_gather_copy", "k_cbg_gather_unshuffle", "k_cbg_gather_bitun", "k_cbg_gather_bitun4"};
     cb_launch_kinds(B.kind0, B.kblocks, gname, s, [&](auto K, uint32_t k0, uint32_t nk, uint32_t blocks) {
@@ -1722,7 +1852,7 @@ static int cbx_launch(const CbxBatch &B, int njobs, void *d_work, hb_result *d_r
     CbPlan *d_plans = cb_at<CbPlan>(w, L.plans);
     const CbxTouch *d_touch = cb_at<const CbxTouch>(w, L.touch);
     if (B.nstreams)
-        cbg_launch_decoders((uint32_t)B.nblk, (uint32_t)B.nstreams, B.any_small, B.nsplit_all, B.any_lz4, B.any_blz, d_frames, d_blocks, d_plans, cb_at<const uint32_t>(w, L.str0),
+        cbg_launch_decoders((uint32_t)B.nblk, (uint32_t)B.nstreams, B.any_small, B.nsplit_all, B.any_lz4, B.any_blz, B.any_zstd, d_frames, d_blocks, d_plans, cb_at<const uint32_t>(w, L.str0),
                             cb_at<CbStream>(w, L.streams), w, s);
     const uint32_t *d_gjob = cb_at<const uint32_t>(w, L.gjob), *d_gblk = cb_at<const uint32_t>(w, L.gblk);
     static const char *const gname[CBG_COUNT] = {"k_cbx_gather_copy", "k_cbx_gather_unshuffle", "k_cbx_gather_bitun", "k_cbx_gather_bitun4"};
