@@ -42,7 +42,7 @@ CB_HD static inline uint32_t cb_stream_of(uint32_t it, uint32_t mgrp, uint32_t P
 // stream makes room for the next one.  Long streams: as many passes per workgroup as a block has streams (nsplit_all: the nsplit every owner
 // shares, else 1), fewer while that leaves under 2048 workgroups -- with the rotation by the pass number a workgroup decodes one stream of
 // each plane, and all workgroups live about equally long.  Where the small decoder runs too, the LZ4 launch keeps its shape.
-struct CbSchedule { uint32_t P, grid_small, grid_lz4, grid_blz; };      // grid_blz: the launches without a small decoder beside them, BloscLZ and zstd
+struct CbSchedule { uint32_t P, grid_small, grid_lz4, grid_blz; };      // grid_blz: the launches without a small decoder beside them, BloscLZ, zstd and zlib
 static inline CbSchedule cb_decode_schedule(uint32_t nstreams, uint32_t nsplit_all, uint32_t any_small) {
     const uint32_t mgrp = (nstreams + 7u) / 8u;
     uint32_t P = mgrp / 4u + 1u;                                            // coprime to the groups of 8 streams, about a quarter turn
@@ -63,18 +63,27 @@ static inline CbSchedule cb_decode_schedule(uint32_t nstreams, uint32_t nsplit_a
 // that one call judges all its frames alike.  Every codec check of the C-Blosc-1 side is cb_codec_refused(). ----
 #define CB_CODEC_BLOSCLZ   0u
 #define CB_CODEC_LZ4       1u
+#define CB_CODEC_ZLIB      3u
 #define CB_CODEC_ZSTD      4u
 #define CB_ACCEPT_DEFAULT  0x2u      // LZ4 / LZ4HC
 #define CB_ACCEPT_BLOSCLZ  0x3u      // ... and BloscLZ
 #define CB_ACCEPT_ZSTD     0x10u     // bit 4: zstd, next to either of the two
-static inline bool cb_accept_valid(unsigned mask) { return (mask & ~CB_ACCEPT_ZSTD) == CB_ACCEPT_DEFAULT || (mask & ~CB_ACCEPT_ZSTD) == CB_ACCEPT_BLOSCLZ; }
+#define CB_ACCEPT_ZLIB     0x100u    // zlib, next to any of those: above the eight codec-format bits (bit 3, its own, is pinned as refused), so asked by name below
+static inline bool cb_accept_valid(unsigned mask) {
+    const unsigned base = mask & ~(CB_ACCEPT_ZSTD | CB_ACCEPT_ZLIB);
+    return base == CB_ACCEPT_DEFAULT || base == CB_ACCEPT_BLOSCLZ;
+}
 // a frame with streams (not memcpyed): HB_OK, or HB_ERR_INVALID_CODEC for a codec format the mask does not name.  hb_cblosc_header.codec_format
 // decides, as it always has; the records that go to the device carry it in the flags' three high bits (cb_record_flags), where the header has
 // it too -- so a record built by hand with the two at odds is decoded as what it was accepted as.
-static inline int cb_codec_refused(const hb_cblosc_header &h, unsigned accept) { return (h.codec_format < 8u && ((accept >> h.codec_format) & 1u)) ? HB_OK : HB_ERR_INVALID_CODEC; }
+static inline int cb_codec_refused(const hb_cblosc_header &h, unsigned accept) {
+    if (h.codec_format == CB_CODEC_ZLIB) return (accept & CB_ACCEPT_ZLIB) ? HB_OK : HB_ERR_INVALID_CODEC;
+    return (h.codec_format < 8u && ((accept >> h.codec_format) & 1u)) ? HB_OK : HB_ERR_INVALID_CODEC;
+}
 static inline uint32_t cb_record_flags(const hb_cblosc_header &h) { return (h.flags & 0x1Fu) | ((h.codec_format & 7u) << 5); }
 CB_HD static inline bool cb_is_blosclz(uint32_t flags) { return (flags >> 5) == CB_CODEC_BLOSCLZ; }
 CB_HD static inline bool cb_is_zstd(uint32_t flags) { return (flags >> 5) == CB_CODEC_ZSTD; }
+CB_HD static inline bool cb_is_zlib(uint32_t flags) { return (flags >> 5) == CB_CODEC_ZLIB; }
 CB_HD static inline bool cb_is_lz4(uint32_t flags) { return (flags >> 5) == CB_CODEC_LZ4; }
 
 static inline size_t cb_align(size_t b) { return (b + 255) & ~(size_t)255; }
@@ -171,7 +180,7 @@ struct CbbBatch {
     uint64_t nblocks, nstreams;
     size_t stage;
     uint32_t any_small, nsplit_all;      // some frame's streams are at most one chunk; the nsplit that all frames with streams share, else 1
-    uint32_t any_lz4, any_blz, any_zstd; // some frame with streams is LZ4 / BloscLZ / zstd: one decoder launch per codec that occurs
+    uint32_t any_lz4, any_blz, any_zstd, any_zlib; // some frame with streams is LZ4 / BloscLZ / zstd / zlib: one decoder launch per codec that occurs
     CbbLayout L;
 };
 
@@ -184,7 +193,7 @@ static inline uint32_t cbb_grid(uint64_t items, uint32_t per_group, uint32_t mos
 static inline int cbb_prepare(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, void *const *d_dst, const size_t *cap,
                               CbbBatch &B, unsigned accept = CB_ACCEPT_DEFAULT) {
     if (nframes < 0) return HB_ERR_BAD_ARG;
-    B.nblocks = 0; B.nstreams = 0; B.stage = 0; B.any_small = 0; B.nsplit_all = 0; B.any_lz4 = 0; B.any_blz = 0; B.any_zstd = 0;
+    B.nblocks = 0; B.nstreams = 0; B.stage = 0; B.any_small = 0; B.nsplit_all = 0; B.any_lz4 = 0; B.any_blz = 0; B.any_zstd = 0; B.any_zlib = 0;
     for (int k = 0; k < CBK_COUNT; k++) B.kblocks[k] = 0;
     for (int k = 0; k <= CBK_COUNT; k++) B.kind0[k] = 0;
     B.L = cbb_layout(0, 0, 0);
@@ -219,7 +228,7 @@ static inline int cbb_prepare(int nframes, const hb_cblosc_header *hdrs, const v
             F.nsplit = cb_nsplit(h.flags, ts, bs);
             F.b0 = 0; F.nblocks = (uint32_t)(((uint64_t)h.nbytes + bs - 1) / bs);
             F.stream0 = (uint32_t)B.nstreams;
-            if (cb_is_blosclz(F.flags)) B.any_blz = 1; else if (cb_is_zstd(F.flags)) B.any_zstd = 1; else B.any_lz4 = 1;
+            if (cb_is_blosclz(F.flags)) B.any_blz = 1; else if (cb_is_zstd(F.flags)) B.any_zstd = 1; else if (cb_is_zlib(F.flags)) B.any_zlib = 1; else B.any_lz4 = 1;
             F.small = cb_is_lz4(F.flags) && bs / F.nsplit <= HB_CHUNK ? 1u : 0u;                // (the small decoder is LZ4's: it selects by this and by size alone)
             B.nblocks += F.nblocks;
             B.nstreams += (uint64_t)F.nblocks * F.nsplit;

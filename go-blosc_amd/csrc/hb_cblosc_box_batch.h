@@ -247,7 +247,7 @@ struct CbxBatch {
     std::vector<uint32_t> pgjob, pgblk;
     uint32_t pkind0[CBG_COUNT + 1], pkblocks[CBG_COUNT];
     uint64_t nblk, nstreams, stage, ntouch;
-    uint32_t any_small, nsplit_all, any_lz4, any_blz, any_zstd;
+    uint32_t any_small, nsplit_all, any_lz4, any_blz, any_zstd, any_zlib;
     int ptr_refusals;                    // jobs refused for their capacity or a pointer: the workspace query counts their blocks, this batch does not
     CbxLayout L;
 };
@@ -259,7 +259,7 @@ CB_HD static inline uint32_t cbs_items_per_unit(uint32_t ts) { return 16u % ts ?
 // ---- what cbx_prepare_ below and cbp_prepare_ (hb_cblosc_point_batch.h) share: the empty batch, a frame's record, a job's gather kind, the
 // table of distinct blocks out of the jobs' runs, and the block records and touch lists ----
 static inline void cbx_reset(CbxBatch &B) {
-    B.nblk = 0; B.nstreams = 0; B.stage = 0; B.ntouch = 0; B.any_small = 0; B.nsplit_all = 0; B.ptr_refusals = 0; B.any_lz4 = 0; B.any_blz = 0; B.any_zstd = 0;
+    B.nblk = 0; B.nstreams = 0; B.stage = 0; B.ntouch = 0; B.any_small = 0; B.nsplit_all = 0; B.ptr_refusals = 0; B.any_lz4 = 0; B.any_blz = 0; B.any_zstd = 0; B.any_zlib = 0;
     for (int k = 0; k < CBG_COUNT; k++) B.kblocks[k] = 0;
     for (int k = 0; k <= CBG_COUNT; k++) B.kind0[k] = 0;
     for (int k = 0; k < CBG_COUNT; k++) B.skblocks[k] = 0;
@@ -310,7 +310,7 @@ static inline int cbx_distinct_blocks(CbxBatch &B, const hb_cblosc_header *hdrs)
         B.stage += full * cb_align((size_t)h.blocksize + 64) + (tail ? cb_align((size_t)(h.nbytes % h.blocksize) + 64) : 0u);
         if (B.nblk > HB_CBLOSC_BATCH_MAX_WORK || B.nstreams > HB_CBLOSC_BATCH_MAX_WORK) return HB_ERR_BAD_ARG;
         if (F.small) B.any_small = 1;
-        if (cb_is_blosclz(F.flags)) B.any_blz = 1; else if (cb_is_zstd(F.flags)) B.any_zstd = 1; else B.any_lz4 = 1;
+        if (cb_is_blosclz(F.flags)) B.any_blz = 1; else if (cb_is_zstd(F.flags)) B.any_zstd = 1; else if (cb_is_zlib(F.flags)) B.any_zlib = 1; else B.any_lz4 = 1;
         B.nsplit_all = B.nsplit_all == 0 || B.nsplit_all == F.nsplit ? F.nsplit : 1u;
     }
     if (B.nsplit_all == 0) B.nsplit_all = 1;

@@ -126,7 +126,7 @@ struct CbgBatch {
     uint32_t kblocks[CBG_COUNT];         // workgroups of kind k
     uint64_t nblk, nstreams, stage;
     uint32_t any_small, nsplit_all;      // some covered frame's streams are at most one chunk; the nsplit that all covered frames share, else 1
-    uint32_t any_lz4, any_blz, any_zstd;         // some covered frame with streams is LZ4 / BloscLZ / zstd: one decoder launch per codec that occurs
+    uint32_t any_lz4, any_blz, any_zstd, any_zlib;         // some covered frame with streams is LZ4 / BloscLZ / zstd / zlib: one decoder launch per codec that occurs
     int ptr_refusals;                    // jobs refused for their capacity or a pointer: the workspace query counts their blocks, this batch does not
     CbgLayout L;
 };
@@ -140,7 +140,7 @@ static inline uint32_t cbg_bsize(const hb_cblosc_header &h, uint32_t b) {
 // (nothing whose size depends on the number of blocks is allocated).
 static inline int cbg_prepare_(int nframes, const hb_cblosc_header *hdrs, const void *const *d_frame, const size_t *n, int njobs, const hb_getitem_job *jobs,
                                void *const *d_dst, const size_t *cap, bool fill, CbgBatch &B, unsigned accept) {
-    B.nblk = 0; B.nstreams = 0; B.stage = 0; B.any_small = 0; B.nsplit_all = 0; B.ptr_refusals = 0; B.any_lz4 = 0; B.any_blz = 0; B.any_zstd = 0;
+    B.nblk = 0; B.nstreams = 0; B.stage = 0; B.any_small = 0; B.nsplit_all = 0; B.ptr_refusals = 0; B.any_lz4 = 0; B.any_blz = 0; B.any_zstd = 0; B.any_zlib = 0;
     for (int k = 0; k < CBG_COUNT; k++) B.kblocks[k] = 0;
     for (int k = 0; k <= CBG_COUNT; k++) B.kind0[k] = 0;
     B.frames.clear(); B.jobs.clear(); B.runs.clear(); B.blocks.clear(); B.str0.clear(); B.gjob.clear(); B.gblk.clear();
@@ -215,7 +215,7 @@ static inline int cbg_prepare_(int nframes, const hb_cblosc_header *hdrs, const 
         B.stage += full * cb_align((size_t)h.blocksize + 64) + (tail ? cb_align((size_t)(h.nbytes % h.blocksize) + 64) : 0u);
         if (B.nblk > HB_CBLOSC_BATCH_MAX_WORK || B.nstreams > HB_CBLOSC_BATCH_MAX_WORK) return HB_ERR_BAD_ARG;
         if (F.small) B.any_small = 1;
-        if (cb_is_blosclz(F.flags)) B.any_blz = 1; else if (cb_is_zstd(F.flags)) B.any_zstd = 1; else B.any_lz4 = 1;
+        if (cb_is_blosclz(F.flags)) B.any_blz = 1; else if (cb_is_zstd(F.flags)) B.any_zstd = 1; else if (cb_is_zlib(F.flags)) B.any_zlib = 1; else B.any_lz4 = 1;
         B.nsplit_all = B.nsplit_all == 0 || B.nsplit_all == F.nsplit ? F.nsplit : 1u;
     }
     if (B.nsplit_all == 0) B.nsplit_all = 1;

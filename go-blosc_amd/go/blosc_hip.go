@@ -570,7 +570,7 @@ func CompressCBlosc(data []byte, shuffle Shuffle, typeSize int) ([]byte, error) 
 }
 
 // CBloscAcceptCodecs says which C-Blosc-1 codec formats DecompressCBlosc, CBloscDecompressBatchHIP and CBloscGetItemBatchHIP decode
-// (hb_cblosc_accept_codecs): bit k = codec format k.  0x2 (LZ4 / LZ4HC) is the default, bit 4 adds zstd (0x12, and 0x13 next to BloscLZ), 0x3 adds BloscLZ -- what blosc_compress() and
+// (hb_cblosc_accept_codecs): bit k = codec format k.  0x2 (LZ4 / LZ4HC) is the default, bit 4 adds zstd (0x12, and 0x13 next to BloscLZ), 0x100 adds zlib to any of those (0x102, 0x103, 0x112, 0x113), 0x3 adds BloscLZ -- what blosc_compress() and
 // python-blosc write unless told otherwise; any other mask is refused and changes nothing.  Process-wide and safe to call from any
 // goroutine; returns the previous mask.  Opt-in because ErrInvalidCodec for a BloscLZ frame is an answer a caller may route on.
 func CBloscAcceptCodecs(mask uint) (uint, error) {

@@ -841,7 +841,7 @@ def CBloscParseHeader(frame):
 
 def CBloscAcceptCodecs(mask):
     """Which C-Blosc-1 codec formats the CBlosc* calls decode (include/hipblosc.h hb_cblosc_accept_codecs): 0x2 = LZ4 / LZ4HC (the default),
-    0x3 adds BloscLZ, bit 4 adds zstd to either (0x12, 0x13).  Process-wide; returns the previous mask; any other mask raises."""
+    0x3 adds BloscLZ, bit 4 adds zstd to either (0x12, 0x13), 0x100 adds zlib to any of the four (0x102, 0x103, 0x112, 0x113).  Process-wide; returns the previous mask; any other mask raises."""
     return _check(lib().hb_cblosc_accept_codecs(int(mask)))
 
 

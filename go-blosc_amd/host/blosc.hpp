@@ -153,7 +153,7 @@ inline std::vector<Bytes> GetItemBatch(const std::vector<Bytes> &frames, const s
     for (size_t j = 0; j < nj; j++) out[j].resize(rc[j] > 0 ? (size_t)rc[j] : 0);
     return out;
 }
-// which C-Blosc-1 codec formats the CBlosc* calls decode (hb_cblosc_accept_codecs): 0x2 = LZ4 / LZ4HC (the default), 0x3 adds BloscLZ, bit 4 adds zstd to either (0x12, 0x13); process-wide;
+// which C-Blosc-1 codec formats the CBlosc* calls decode (hb_cblosc_accept_codecs): 0x2 = LZ4 / LZ4HC (the default), 0x3 adds BloscLZ, bit 4 adds zstd to either (0x12, 0x13), 0x100 adds zlib to any of the four (0x102, 0x103, 0x112, 0x113); process-wide;
 // returns the previous mask, throws for any other mask
 inline unsigned CBloscAcceptCodecs(unsigned mask) { return (unsigned)check(hb_cblosc_accept_codecs(mask)); }
 // which compressor and level the CBlosc* writers use (hb_cblosc_set_compressor): codec HB_LZ4 or HB_LZ4HC, clevel 0..9 (0: memcpyed frames), the default

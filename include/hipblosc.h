@@ -340,7 +340,8 @@ int64_t hb_queue_wait(hb_queue *q, int64_t ticket);
  *      filter per block) -- what go-blosc's README.md:20 claims to be compatible with and blosc.go does not implement.  Codec
  *      formats LZ4 / LZ4HC and memcpyed frames -- and BloscLZ (codec format 0, what blosc_compress() and python-blosc write by
  *      default) once hb_cblosc_accept_codecs(0x3) has been called, and zstd (codec format 4: one complete Zstandard frame per stream,
- *      what numcodecs / zarr write for cname='zstd') once bit 4 is set (0x12 / 0x13); byte shuffle, bit shuffle or none, any typesize.  Not a seam of
+ *      what numcodecs / zarr write for cname='zstd') once bit 4 is set (0x12 / 0x13), and zlib (codec format 3: one complete zlib stream, RFC 1950, per
+ *      stream; cname='zlib') once 0x100 is set; byte shuffle, bit shuffle or none, any typesize.  Not a seam of
  *      the reference (it has none for this): an extension next to hb_decompress_frame. ---- */
 typedef struct hb_cblosc_header {
     uint8_t  version, versionlz, flags, typesize;   /* flags: 0x01 shuffle, 0x02 memcpyed, 0x04 bitshuffle, 0x10 not split */
@@ -349,18 +350,22 @@ typedef struct hb_cblosc_header {
 } hb_cblosc_header;
 int     hb_cblosc_parse_header(const void *frame, size_t n, hb_cblosc_header *out);          /* host-only */
 /* which C-Blosc-1 codec formats the hb_cblosc_* entry points accept: bit k = codec format k.  Default 0x2 (LZ4 / LZ4HC).
- * Accepted masks: 0x2, 0x3 (adds BloscLZ), 0x12 and 0x13 (bit 4 adds zstd to either); anything else HB_ERR_BAD_ARG and no change.  Returns
- * the previous mask.
+ * Accepted masks: 0x2, 0x3 (adds BloscLZ), 0x12 and 0x13 (bit 4 adds zstd to either), and each of the four with 0x100, which adds zlib:
+ * 0x102, 0x103, 0x112, 0x113.  zlib's bit is not bit 3: it lies above the eight codec-format bits, and 0x8 / 0xA / 0x1A stay refused.  Anything
+ * else HB_ERR_BAD_ARG and no change.  Returns the previous mask.
  * Process-wide and thread-safe: an atomic word that every entry point (hb_cblosc_decompress*, hb_cblosc_decompress_frames_batch*,
  * hb_cblosc_getitem*, hb_cblosc_getitem_frames_batch*, hb_cblosc_getbox_frames_batch*, hb_cblosc_getslice_frames_batch*, device and host forms and their workspace queries) reads once
  * per call -- every reader below, the prepared selections and the old-frame side of the update batches included.  With bit 0 set a BloscLZ frame,
- * with bit 4 set a zstd frame gets exactly the refusals, in the same order, that an LZ4 frame with the same header gets; wherever the
+ * with bit 4 set a zstd frame, with 0x100 set a zlib frame gets exactly the refusals, in the same order, that an LZ4 frame with the same header gets; wherever the
  * comments below say "codec format != 1" read "a codec format the mask does not name".  Opt-in, because HB_ERR_INVALID_CODEC for
  * BloscLZ or zstd is an answer callers may route on (to a CPU decoder).  A zstd stream must be ONE zstd frame that ends at the stream's end and
  * decodes to the stream's size, without a dictionary; anything else is HB_ERR_DECOMPRESSION_FAILED for its frame (its block, in the batches of
  * block records) alone (DESIGN.md §3.5 "ZSTD streams": what is stricter than libzstd).  The zstd decoder needs no workspace of its own -- Huffman
  * literals wait in the tail of the stream's output -- so every workspace query answers for a zstd frame what it answers for the LZ4 frame with the
- * same header: HB_CBLOSC_ZSTD_SLOTS literal areas, none.  Writing is not touched: hb_cblosc_compress* writes LZ4 (hb_cblosc_set_compressor
+ * same header: HB_CBLOSC_ZSTD_SLOTS literal areas, none.  A zlib stream must be what zlib's uncompress() decodes to exactly the stream's size: header
+ * without a preset dictionary, stored / fixed / dynamic blocks, the Adler-32 of the plain bytes, which the device computes and holds against
+ * the trailer as c-blosc does; bytes behind the trailer are ignored as there; anything else is HB_ERR_DECOMPRESSION_FAILED for its frame (its
+ * block) alone (DESIGN.md §3.5 "zlib streams").  Its literals are inline: no workspace query grows for a zlib frame either.  Writing is not touched: hb_cblosc_compress* writes LZ4 (hb_cblosc_set_compressor
  * below chooses how hard it searches; its threading rule is this one). */
 #define HB_CBLOSC_ZSTD_SLOTS 0
 int     hb_cblosc_accept_codecs(unsigned mask);
@@ -370,7 +375,7 @@ int     hb_cblosc_decompress_dev(const hb_cblosc_header *hdr, const void *d_fram
 /* host pointers: returns the decoded bytes (== nbytes of the header) or HB_ERR_*: HB_ERR_INVALID_CODEC for the codec formats
  * that hb_cblosc_accept_codecs has not named (LZ4 alone by default), HB_ERR_DECOMPRESSION_FAILED for anything blosc_decompress()
  * answers with a negative number (BloscLZ: DESIGN.md §3.5 lists where the device is stricter than blosclz_decompress: nowhere; zstd: the same
- * section lists where it is stricter than ZSTD_decompress) */
+ * section lists where it is stricter than ZSTD_decompress; zlib: nowhere) */
 int64_t hb_cblosc_decompress(const void *frame, size_t n, void *dst, size_t cap, int device);
 /* ---- batched C-Blosc-1 decode: many whole frames through ONE set of launches (plan, the stream decoders, one un-filter per kind that occurs,
  *      one copy for the memcpyed frames, finish -- the same launches for 4 frames and for 4096).  What a chunked array store holds is one
