@@ -26,6 +26,7 @@
 // stage names k_cb_decode[_small|_blz|_zstd|_zlib], k_cbb_decode[...] and k_cbg_decode[...] of the three families.
 #include "hb_sym_decode.h"
 #include "hb_zstd_dec.h"
+#include "hb_zstd_enc.h"
 #include "hb_zlib_dec.h"
 
 #include <atomic>
@@ -1200,6 +1201,26 @@ __global__ __launch_bounds__(1024) void k_cbe_scan(uint32_t *tile_sum, uint32_t 
     __shared__ uint32_t s[1024];
     cbe_scan(tile_sum, ntiles, plan, s);
 }
+// plane j of one element block of the fused route (HB_CHUNK elements of nsplit = typesize = 2 / 4 / 8 bytes at e, 16-byte aligned: the fused
+// route asks for it) to dst: the chunk that route never materialised.  One wavefront; k_cbe_pack stores it into the frame, k_cbe_zstd into LDS.
+__device__ __forceinline__ void cbe_gather_plane(uint8_t *dst, const uint8_t *__restrict__ e, uint32_t j, uint32_t nsplit, int lane) {
+    const uint32_t per = 16u / nsplit;                                                     // elements per 16 bytes
+    const uint32_t nv = HB_CHUNK * nsplit / 16u;                                           // 512 / 1024 / 2048 vectors: 8 / 16 / 32 per lane
+    for (uint32_t i0 = lane; i0 < nv; i0 += 64u * 8u) {                                    // 8 loads in flight per lane
+        u32x4 v[8];
+#pragma unroll
+        for (int q = 0; q < 8; q++) v[q] = *(const u32x4 *)(e + 16u * (size_t)(i0 + 64u * q));
+#pragma unroll
+        for (int q = 0; q < 8; q++) {
+            const uint32_t i = i0 + 64u * q;
+            const uint32_t wv[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
+            uint64_t o = 0;
+            for (uint32_t kk = 0; kk < per; kk++) { const uint32_t byte = kk * nsplit + j; o |= (uint64_t)((wv[byte >> 2] >> (8u * (byte & 3u))) & 255u) << (8u * kk); }
+            uint8_t *dp = dst + i * per;
+            if (per == 8u) st8u(dp, o); else if (per == 4u) st4u(dp, (uint32_t)o); else { dp[0] = (uint8_t)o; dp[1] = (uint8_t)(o >> 8); }
+        }
+    }
+}
 // one wavefront per chunk writes { cbytes, block or chunk }; the first chunk of a block also writes the block's bstarts entry.
 // 1024 chunks per workgroup of 16 wavefronts: latency-bound small copies, so as many of them in flight as the chip takes.
 __device__ __forceinline__ void cbe_pack(const CbChunkDesc *__restrict__ desc, const uint8_t *__restrict__ records, const uint8_t *__restrict__ filtered,
@@ -1224,25 +1245,9 @@ __device__ __forceinline__ void cbe_pack(const CbChunkDesc *__restrict__ desc, c
         const uint32_t cb = stored ? HB_CHUNK : d.enc_len;
         if (lane < 4) frame[at + lane] = (uint8_t)(cb >> (8 * lane));
         if (lane == 0 && c % nsplit == 0u) { const uint32_t b = c / nsplit; for (int q = 0; q < 4; q++) frame[16u + 4u * b + q] = (uint8_t)(at >> (8 * q)); }
-        if (stored && fused_nblk) {                                    // no filtered buffer: plane j of element block b, gathered from the input
-            const uint8_t *e = filtered + (size_t)(c / nsplit) * HB_CHUNK * nsplit;           // (16-byte aligned: the fused path asks for it)
-            const uint32_t j = c % nsplit, per = 16u / nsplit;                                // nsplit = typesize = 2 / 4 / 8: elements per 16 bytes
-            const uint32_t nv = HB_CHUNK * nsplit / 16u;                                       // 512 / 1024 / 2048 vectors: 8 / 16 / 32 per lane
-            for (uint32_t i0 = lane; i0 < nv; i0 += 64u * 8u) {                                // 8 loads in flight per lane
-                u32x4 v[8];
-#pragma unroll
-                for (int q = 0; q < 8; q++) v[q] = *(const u32x4 *)(e + 16u * (size_t)(i0 + 64u * q));
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const uint32_t i = i0 + 64u * q;
-                    const uint32_t wv[4] = {v[q].x, v[q].y, v[q].z, v[q].w};
-                    uint64_t o = 0;
-                    for (uint32_t kk = 0; kk < per; kk++) { const uint32_t byte = kk * nsplit + j; o |= (uint64_t)((wv[byte >> 2] >> (8u * (byte & 3u))) & 255u) << (8u * kk); }
-                    uint8_t *dp = frame + at + 4u + i * per;
-                    if (per == 8u) st8u(dp, o); else if (per == 4u) st4u(dp, (uint32_t)o); else { dp[0] = (uint8_t)o; dp[1] = (uint8_t)(o >> 8); }
-                }
-            }
-        } else wave_copy_g2g(frame + at + 4u, stored ? filtered + (size_t)c * HB_CHUNK : records + (size_t)ci * HB_RSTRIDE, cb, lane);
+        if (stored && fused_nblk)                                      // no filtered buffer: plane j of element block b, gathered from the input
+            cbe_gather_plane(frame + at + 4u, filtered + (size_t)(c / nsplit) * HB_CHUNK * nsplit, c % nsplit, nsplit, lane);
+        else wave_copy_g2g(frame + at + 4u, stored ? filtered + (size_t)c * HB_CHUNK : records + (size_t)ci * HB_RSTRIDE, cb, lane);
     }
 }
 __global__ __launch_bounds__(1024) void k_cbe_pack(const CbChunkDesc *__restrict__ desc, const uint8_t *__restrict__ records, const uint8_t *__restrict__ filtered,
@@ -1356,6 +1361,129 @@ __global__ __launch_bounds__(64) void k_cbeb_finish(const CbeFrame *__restrict__
     }
     const uint8_t *last = F.tail_off ? work + F.tail_off : F.src + (size_t)F.nfull * F.blocksize;
     cbe_finish(plans + k, last, F.nbytes, F.blocksize, F.typesize, F.flags, F.nfull, 16u + 4u * F.nblocks, F.dst, F.cap, r, lane);
+}
+
+// ---- writing zstd streams (hb_cblosc_set_stream_format).  The format, the choices and the serial statement are hb_zstd_enc.h's; this is the
+// same computation with one wavefront per chunk, between the matcher and the tile sums: the chunk's record (a self-contained LZ4 block) or,
+// for a chunk the matcher could not shrink, its plain bytes become one zstd frame, written back over the record slot with enc_len set; a frame
+// of HB_CHUNK bytes or more is not written and enc_len = HB_CHUNK marks the chunk stored, so tiles, scan, pack and finish stay as they are.
+// Parallel: the record / plane load, the literal copy, the length codes, the histogram (LDS atomics), the (count, value) order, the code
+// length sums (a wave scan per Huffman stream, literals dealt out in contiguous slices) and the Huffman bit images (atomicOr into the zeroed
+// image: literal i of a stream of T bits lies at [T - incl(i), T - excl(i))).  One lane: the LZ4 parse, the tree, its description, the
+// headers and the FSE chain of the sequences.
+// frames != NULL: the batch -- workgroup x is chunk x % 1024 of tile x / 1024 of the flat tile space, its frame's descriptors, records, route
+// and stored-chunk source (work + fsrc_off, or the frame's input) are the frame record's, as k_cbeb_pack takes them. ----
+struct alignas(16) CbeZstdLds {
+    ZsEncState S;
+    alignas(16) uint32_t img[HB_CHUNK / 4u + 8u];                         // the record on its way in, the zstd frame on its way out
+};
+__global__ __launch_bounds__(64) void k_cbe_zstd(const CbeFrame *__restrict__ frames, const uint32_t *__restrict__ tile0, uint32_t nframes, CbChunkDesc *desc, uint8_t *records,
+                                                 const uint8_t *filtered, uint32_t nchunks, uint32_t nsplit, uint32_t fused_nblk) {
+    __shared__ CbeZstdLds Z;
+    const int lane = threadIdx.x;
+    uint32_t c = blockIdx.x;
+    if (frames) {
+        const uint32_t tile = blockIdx.x >> 10;
+        const CbeFrame &F = frames[hb_owner(tile0, nframes, tile)];
+        c = (tile - F.tile0) * 1024u + (blockIdx.x & 1023u);
+        nchunks = F.nchunks; nsplit = F.nsplit; fused_nblk = F.mode == CBE_FUSED ? F.nfull : 0u;
+        desc += F.desc0; records += (size_t)F.desc0 * HB_RSTRIDE;
+        filtered = F.fsrc_off ? filtered + F.fsrc_off : F.src;
+    }
+    if (c >= nchunks) return;
+    ZsEncState *S = &Z.S;
+    uint8_t *out = (uint8_t *)Z.img;
+    const uint32_t ci = cb_desc_index(c, nsplit, fused_nblk);
+    CbChunkDesc *dsc = desc + ci;
+    uint8_t *rec = records + (size_t)ci * HB_RSTRIDE;                     // (16-byte aligned: the records' area is, and HB_RSTRIDE is a multiple)
+    const uint32_t enc_len = dsc->enc_len;
+    const bool stored = enc_len >= HB_CHUNK;
+    if (!stored) {                                                        // (the vectors end inside the slot: enc_len < HB_CHUNK < HB_RSTRIDE)
+        for (uint32_t i = lane; i < (enc_len + 15u) / 16u; i += 64u) *(u32x4 *)(out + 16u * i) = *(const u32x4 *)(rec + 16u * i);
+        wave_sync();
+        if (lane == 0) S->use_huf = zse_parse(S, out, enc_len, HB_CHUNK) ? 1u : 0u;
+        wave_sync();
+        if (!S->use_huf) { if (lane == 0) dsc->enc_len = HB_CHUNK; return; }      // (not a block of this chunk: the plain bytes go out)
+        zse_copy_lits(S, out, (uint32_t)lane, 64u);
+        zse_seq_codes(S, (uint32_t)lane, 64u);
+    } else {
+        if (fused_nblk) cbe_gather_plane(S->lit, filtered + (size_t)(c / nsplit) * HB_CHUNK * nsplit, c % nsplit, nsplit, lane);
+        else {
+            const uint8_t *p = filtered + (size_t)c * HB_CHUNK;
+            for (uint32_t i = lane; i < HB_CHUNK / 16u; i += 64u) *(u32x4 *)(S->lit + 16u * i) = ld16u(p + 16u * i);
+        }
+        if (lane == 0) zse_plain(S, HB_CHUNK);
+    }
+    for (uint32_t s = lane; s < 256u; s += 64u) S->cnt[s] = 0u;
+    wave_sync();
+    const uint32_t nlit = S->nlit;
+    for (uint32_t i = lane; i < nlit; i += 64u) atomicAdd(&S->cnt[S->lit[i]], 1u);
+    wave_sync();
+    if (lane == 0) zse_alphabet(S);
+    wave_sync();
+    const uint32_t fh = 7u;                                               // the frame header of HB_CHUNK bytes: magic, descriptor, two bytes of size
+    uint32_t total = 0u;                                                  // (wave-uniform) the frame's length, 0: the chunk is stored
+    if (S->nsym == 1u) {
+        if (lane == 0) { zse_frame_header(out, HB_CHUNK, HB_CHUNK); zse_block_header(out, fh, 1u, HB_CHUNK); out[fh + 3u] = S->lit[0]; }
+        total = fh + 4u;
+    } else {
+        zse_rank(S, (uint32_t)lane, 64u);
+        wave_sync();
+        if (lane == 0) { S->tree_n = 0u; if (zse_lengths(S)) zse_tree(S); zse_lit_split(S); }
+        wave_sync();
+        const uint32_t nstreams = S->nstreams, have_tree = S->tree_n, seg = S->scnt[0];
+        uint32_t pre[4];                                                  // the code bits of stream k in front of my slice (k is unrolled: registers)
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            uint32_t sum = 0u;
+            if ((uint32_t)k < nstreams && have_tree) {
+                const uint32_t n = S->scnt[k], per = (n + 63u) / 64u, a = min((uint32_t)lane * per, n), e = min(a + per, n);
+                const uint8_t *p = S->lit + (uint32_t)k * seg;
+                for (uint32_t i = a; i < e; i++) sum += S->len[p[i]];
+            }
+            const uint32_t incl = wave_incl_scan_dpp(sum);
+            pre[k] = incl - sum;
+            const uint32_t bits = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+            if (lane == 0) S->sbits[k] = bits;
+        }
+        for (uint32_t i = lane; i < HB_CHUNK / 4u + 8u; i += 64u) Z.img[i] = 0u;
+        wave_sync();
+        if (lane == 0) { zse_frame_header(out, HB_CHUNK, HB_CHUNK); if (!zse_lit_header(S, out, fh + 3u, HB_CHUNK)) S->lit_end = 0u; }
+        wave_sync();
+        if (S->lit_end) {
+            if (S->use_huf) {
+#pragma unroll
+                for (int k = 0; k < 4; k++) {
+                    if ((uint32_t)k >= nstreams) continue;
+                    const uint32_t n = S->scnt[k], per = (n + 63u) / 64u, a = min((uint32_t)lane * per, n), e = min(a + per, n);
+                    const uint8_t *p = S->lit + (uint32_t)k * seg;
+                    const uint32_t top = 8u * S->sat[k] + S->sbits[k];    // the marker's bit; everything below ends inside the stream's bytes
+                    uint32_t pos = top - pre[k];
+                    for (uint32_t i = a; i < e; i++) {
+                        const uint32_t sym = p[i];
+                        pos -= S->len[sym];
+                        const uint64_t v = (uint64_t)S->code[sym] << (pos & 31u);
+                        atomicOr(&Z.img[pos >> 5], (uint32_t)v);
+                        if (v >> 32) atomicOr(&Z.img[(pos >> 5) + 1u], (uint32_t)(v >> 32));
+                    }
+                    if (lane == 0) atomicOr(&Z.img[top >> 5], 1u << (top & 31u));
+                }
+            } else for (uint32_t i = lane; i < nlit; i += 64u) out[S->lit_at + i] = S->lit[i];
+            wave_sync();
+            if (lane == 0) {
+                const uint32_t end = zse_sequences(S, out, S->lit_end, HB_CHUNK);
+                if (end && end < HB_CHUNK) zse_block_header(out, fh, 2u, end - fh - 3u);
+                S->lit_end = end < HB_CHUNK ? end : 0u;
+            }
+            wave_sync();
+            total = S->lit_end;
+        }
+    }
+    wave_sync();
+    if (total) {                                                          // (nothing reads the slot any more: the record was taken into LDS first)
+        for (uint32_t i = lane; i < (total + 15u) / 16u; i += 64u) *(u32x4 *)(rec + 16u * i) = *(const u32x4 *)(out + 16u * i);
+        if (lane == 0) dsc->enc_len = total;
+    } else if (!stored && lane == 0) dsc->enc_len = HB_CHUNK;
 }
 
 // ---- batched box writes (hb_cblosc_compress_boxes_batch_device; the host side and the index arithmetic are hb_cblosc_enc_box_batch.h): the
@@ -1720,7 +1848,8 @@ static void cb_launch_blocks(const hb_cblosc_header *hdr, const uint8_t *d_frame
 static std::atomic<unsigned> g_cb_accept{CB_ACCEPT_DEFAULT};
 unsigned hb_cblosc_accepted() { return g_cb_accept.load(std::memory_order_relaxed); }
 
-// what the writers below compress with (include/hipblosc.h, hb_cblosc_set_compressor): one word, codec << 8 | clevel.  Every writer entry
+// what the writers below compress with (include/hipblosc.h, hb_cblosc_set_compressor, hb_cblosc_set_stream_format): one word,
+// format << 16 | codec << 8 | clevel, the LZ4 stream format kept as 0 and zstd as HB_CB_FORMAT_ZSTD.  Every writer entry
 // point reads it once, before anything is sized or launched, and hands it down to its encode site (hb_cblosc_compress_dev, cbe_launch_batch).
 // A host form pins the word it read for its thread while it runs (CbPolicyPin, hb_common.h): the device forms and the one-frame calls it
 // answers the rest with then read that word, whatever another thread sets meanwhile.
@@ -1732,24 +1861,55 @@ CbPolicyPin::CbPolicyPin() : prev(t_cb_policy_pin) { t_cb_policy_pin = (int)hb_c
 CbPolicyPin::~CbPolicyPin() { t_cb_policy_pin = prev; }
 // the matcher of a policy word: candidates per bucket and skip acceleration (hb_level_policy, the table of the go-blosc-format frames too);
 // level 0: no matcher at all, the frame is memcpyed
-struct CbMatcher { bool store; int ways, accel; };
+// zstd: the streams of a frame that goes through the matcher are written as zstd frames (k_cbe_zstd) and the header names that format
+struct CbMatcher { bool store; int ways, accel; bool zstd; };
 static inline CbMatcher cb_matcher(unsigned policy) {
-    CbMatcher m{(policy & 255u) == 0u, 1, 64};
-    if (!m.store) hb_level_policy((int)(policy >> 8), (int)(policy & 255u), m.ways, m.accel);
+    CbMatcher m{(policy & 255u) == 0u, 1, 64, false};
+    if (!m.store) { hb_level_policy((int)((policy >> 8) & 255u), (int)(policy & 255u), m.ways, m.accel); m.zstd = (policy >> 16) == (unsigned)HB_CB_FORMAT_ZSTD; }
     return m;
+}
+// the codec bits 5-7 of a written header's flags: c-blosc's format number of the streams
+#define CB_FLAGS_LZ4  (1u << 5)
+#define CB_FLAGS_ZSTD 0x80u
+// the zstd stage of both encode sites, between the matcher and the tile sums.  One frame: `grid` = its chunks, frames == NULL; a batch: `grid` =
+// 1024 x its tiles, the frame records say the rest (k_cbe_zstd).  stored_src: where k_cbe_pack / k_cbeb_pack take a stored chunk from.
+static void cbe_zstd_stage(const CbeFrame *d_frames, const uint32_t *d_tile0, uint32_t nframes, uint32_t grid, CbChunkDesc *desc, uint8_t *records, const uint8_t *stored_src,
+                           uint32_t nchunks, uint32_t nsplit, uint32_t fused_nblk, hipStream_t s) {
+    hb_prof_begin("k_cbe_zstd", s);
+    hipLaunchKernelGGL(k_cbe_zstd, dim3(grid), dim3(64), 0, s, d_frames, d_tile0, nframes, desc, records, stored_src, nchunks, nsplit, fused_nblk);
+    hb_prof_end(s);
 }
 
 extern "C" {
 
 int hb_cblosc_set_compressor(int codec, int clevel) {
     if ((codec != HB_LZ4 && codec != HB_LZ4HC) || clevel < 0 || clevel > 9) return HB_ERR_BAD_ARG;
-    return (int)g_cb_policy.exchange((unsigned)codec << 8 | (unsigned)clevel, std::memory_order_relaxed);
+    unsigned old = g_cb_policy.load(std::memory_order_relaxed);           // (the stream format's bits stay)
+    while (!g_cb_policy.compare_exchange_weak(old, (old & ~0xFFFFu) | (unsigned)codec << 8 | (unsigned)clevel, std::memory_order_relaxed)) {}
+    return (int)(old & 0xFFFFu);
 }
 int hb_cblosc_get_compressor(int *codec, int *clevel) {
     const unsigned p = g_cb_policy.load(std::memory_order_relaxed);
-    if (codec) *codec = (int)(p >> 8);
+    if (codec) *codec = (int)((p >> 8) & 255u);
     if (clevel) *clevel = (int)(p & 255u);
     return HB_OK;
+}
+int hb_cblosc_set_stream_format(int codec_format) {
+    if (codec_format != HB_CB_FORMAT_LZ4 && codec_format != HB_CB_FORMAT_ZSTD) return HB_ERR_BAD_ARG;
+    const unsigned bits = codec_format == HB_CB_FORMAT_ZSTD ? (unsigned)HB_CB_FORMAT_ZSTD << 16 : 0u;
+    unsigned old = g_cb_policy.load(std::memory_order_relaxed);           // (the compressor's bits stay)
+    while (!g_cb_policy.compare_exchange_weak(old, (old & 0xFFFFu) | bits, std::memory_order_relaxed)) {}
+    return (old >> 16) ? (int)(old >> 16) : HB_CB_FORMAT_LZ4;
+}
+int hb_cblosc_get_stream_format(void) {
+    const unsigned p = g_cb_policy.load(std::memory_order_relaxed);
+    return (p >> 16) ? (int)(p >> 16) : HB_CB_FORMAT_LZ4;
+}
+// the serial statement of k_cbe_zstd (hb_zstd_enc.h, zs_encode_from_lz4), host only: what the tests without a device hold the writer to
+size_t hb_cblosc_zstd_stream_from_lz4(const void *lz4, size_t n, size_t usize, void *dst, size_t cap) {
+    if (!lz4 || !dst) return 0;
+    std::vector<uint8_t> state(sizeof(ZsEncState));
+    return zs_encode_from_lz4((const uint8_t *)lz4, n, usize, (uint8_t *)dst, cap, (ZsEncState *)state.data());
 }
 
 #ifdef CB_ZLIB_LAB_NO_ADLER
@@ -2134,8 +2294,10 @@ int hb_cblosc_compress_dev(const void *d_src, size_t n, void *d_frame, size_t ca
     CbChunkDesc *desc = (CbChunkDesc *)(w + L.desc);
     uint8_t *records = w + L.records, *filtered = w + L.filtered;
     const bool unshuf = shuffle == 1 && typesize > 1, bits = shuffle == 2;
-    const uint32_t flags = (unshuf ? CB_FLAG_SHUFFLE : 0u) | (bits ? CB_FLAG_BITSHUFFLE : 0u) | (L.nsplit == 1u ? CB_FLAG_DONTSPLIT : 0u) | (1u << 5);
-    if (n < HB_CHUNK || M.store) {                                        // (level 0: blosc_compress's memcpyed frame, at every size)
+    const bool memcpyed = n < HB_CHUNK || M.store;                        // (such a frame names LZ4 under either stream format, as it always did)
+    const uint32_t flags = (unshuf ? CB_FLAG_SHUFFLE : 0u) | (bits ? CB_FLAG_BITSHUFFLE : 0u) | (L.nsplit == 1u ? CB_FLAG_DONTSPLIT : 0u) |
+                           (M.zstd && !memcpyed ? CB_FLAGS_ZSTD : CB_FLAGS_LZ4);
+    if (memcpyed) {                                        // (level 0: blosc_compress's memcpyed frame, at every size)
         if (n) HB_HIP_TRY(hipMemcpyAsync((uint8_t *)d_frame + 16, d_src, n, hipMemcpyDeviceToDevice, s));
         hipLaunchKernelGGL(k_cbe_memcpy_header, dim3(1), dim3(1), 0, s, (uint8_t *)d_frame, (uint32_t)n, (uint32_t)typesize, flags | CB_FLAG_MEMCPY | CB_FLAG_DONTSPLIT, d_result);
         HB_HIP_TRY(hipGetLastError());
@@ -2168,6 +2330,7 @@ int hb_cblosc_compress_dev(const void *d_src, size_t n, void *d_frame, size_t ca
         if (fuse) hb_launch_match_fused_selfcontained((const uint8_t *)d_src, typesize, desc, records, L.nfull, M.ways, M.accel, s);
         else hb_launch_match_selfcontained(fsrc, (size_t)L.nchunks * HB_CHUNK, desc, records, L.nchunks, M.ways, M.accel, s);
         hb_prof_end(s);
+        if (M.zstd) cbe_zstd_stage(nullptr, nullptr, 0u, L.nchunks, desc, records, fsrc, L.nchunks, L.nsplit, fused_nblk, s);
         hb_prof_begin("k_cbe_pack", s);
         hipLaunchKernelGGL(k_cbe_tiles, dim3(L.ntiles), dim3(256), 0, s, desc, L.nchunks, L.nsplit, fused_nblk, tiles);
         hipLaunchKernelGGL(k_cbe_scan, dim3(1), dim3(1024), 0, s, tiles, L.ntiles, plan);
@@ -2195,6 +2358,11 @@ static int cbe_launch_batch(int nframes, const CbeBatch &B, int shuffle, int typ
         CbeFrame *t = (CbeFrame *)(up.data() + L.frames);
         for (size_t k = 0; k < nf; k++)
             if (t[k].mode == CBE_PLAIN || t[k].mode == CBE_FUSED) { t[k].mode = CBE_MEMCPY; t[k].flags |= CB_FLAG_MEMCPY | CB_FLAG_DONTSPLIT; }
+    }
+    if (M.zstd) {                                                         // (the frames that go through the matcher: their headers name the streams' format)
+        CbeFrame *t = (CbeFrame *)(up.data() + L.frames);
+        for (size_t k = 0; k < nf; k++)
+            if (t[k].mode == CBE_PLAIN || t[k].mode == CBE_FUSED) t[k].flags = (t[k].flags & ~0xE0u) | CB_FLAGS_ZSTD;
     }
     memcpy(up.data() + L.bf, B.bf.data(), nf * sizeof(BatchFrame));
     memcpy(up.data() + L.pre, B.pre.data(), nf * 8);
@@ -2233,6 +2401,7 @@ static int cbe_launch_batch(int nframes, const CbeBatch &B, int shuffle, int typ
         else hb_launch_match_selfcontained_batch(d_bf, d_map, d_desc, d_records, plain, M.ways, M.accel, s);
         hb_prof_end(s);
     }
+    if (ntiles && M.zstd) cbe_zstd_stage(d_frames, d_tile0, (uint32_t)nframes, ntiles * 1024u, d_desc, d_records, w, 0u, 0u, 0u, s);
     if (ntiles) {
         hb_prof_begin("k_cbeb_tiles", s);
         hipLaunchKernelGGL(k_cbeb_tiles, dim3(ntiles), dim3(256), 0, s, d_frames, d_tile0, (uint32_t)nframes, (const CbChunkDesc *)d_desc, d_tiles);

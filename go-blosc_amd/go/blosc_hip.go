@@ -601,6 +601,27 @@ func CBloscGetCompressor() (Codec, int) {
 	return Codec(c), int(l)
 }
 
+// The stream formats of the C-Blosc-1 writers: c-blosc's codec-format numbers (HB_CB_FORMAT_LZ4, HB_CB_FORMAT_ZSTD).
+const (
+	CBloscFormatLZ4  = 1
+	CBloscFormatZstd = 4
+)
+
+// CBloscSetStreamFormat chooses the format of the streams that CompressCBlosc and every batched C-Blosc-1 writer write
+// (hb_cblosc_set_stream_format): CBloscFormatLZ4, the default, or CBloscFormatZstd -- one zstd frame per stream with Huffman-coded literals,
+// read back after CBloscAcceptCodecs(0x12).  Orthogonal to CBloscSetCompressor; process-wide, every writer reads it once per call.  Returns
+// the previous format; any other value is refused and changes nothing.
+func CBloscSetStreamFormat(format int) (int, error) {
+	rc := C.hb_cblosc_set_stream_format(C.int(format))
+	if rc < 0 {
+		return 0, hbError(C.int64_t(rc))
+	}
+	return int(rc), nil
+}
+
+// CBloscGetStreamFormat returns the stream format the C-Blosc-1 writers use (hb_cblosc_get_stream_format).
+func CBloscGetStreamFormat() int { return int(C.hb_cblosc_get_stream_format()) }
+
 // DecompressCBlosc reads a C-Blosc-1 frame with LZ4 / LZ4HC streams (or a memcpyed one), and BloscLZ streams once CBloscAcceptCodecs(0x3)
 // has been called; other codec formats: ErrInvalidCodec.
 func DecompressCBlosc(frame []byte) ([]byte, error) {

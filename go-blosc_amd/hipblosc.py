@@ -118,6 +118,7 @@ EXPORTS = [
     "hb_cblosc_point_sel_create_mask_device", "hb_cblosc_point_sel_create_coords_device", "hb_cblosc_point_sel_njobs", "hb_cblosc_point_sel_npoints",
     "hb_cblosc_point_sel_job_chunks", "hb_cblosc_point_sel_job_points",
     "hb_cblosc_accept_codecs", "hb_cblosc_set_compressor", "hb_cblosc_get_compressor",
+    "hb_cblosc_set_stream_format", "hb_cblosc_get_stream_format", "hb_cblosc_zstd_stream_from_lz4",
     "hb_queue_create", "hb_queue_create_ex", "hb_queue_destroy", "hb_queue_compress", "hb_queue_decompress", "hb_queue_wait",
 ]
 
@@ -417,6 +418,9 @@ def lib():
             "hb_cblosc_accept_codecs": (i32, [ctypes.c_uint]),
             "hb_cblosc_set_compressor": (i32, [i32, i32]),
             "hb_cblosc_get_compressor": (i32, [vp, vp]),
+            "hb_cblosc_set_stream_format": (i32, [i32]),
+            "hb_cblosc_get_stream_format": (i32, []),
+            "hb_cblosc_zstd_stream_from_lz4": (ctypes.c_size_t, [vp, ctypes.c_size_t, ctypes.c_size_t, vp, ctypes.c_size_t]),
         }
         for name, (res, args) in sig.items():
             f = getattr(L, name)
@@ -857,6 +861,21 @@ def CBloscGetCompressor():
     c, l = ctypes.c_int(), ctypes.c_int()
     _check(lib().hb_cblosc_get_compressor(ctypes.byref(c), ctypes.byref(l)))
     return c.value, l.value
+
+
+CB_FORMAT_LZ4, CB_FORMAT_ZSTD = 1, 4                 # enum HB_CB_FORMAT_* of include/hipblosc.h: c-blosc's codec-format numbers
+
+
+def CBloscSetStreamFormat(codec_format):
+    """Which format the streams of the frames the CBlosc* writers write have (include/hipblosc.h hb_cblosc_set_stream_format): CB_FORMAT_LZ4
+    (the default) or CB_FORMAT_ZSTD -- one zstd frame per stream, Huffman-coded literals; read such frames back after CBloscAcceptCodecs(0x12).
+    Orthogonal to CBloscSetCompressor.  Process-wide, read once per call; returns the previous format."""
+    return _check(lib().hb_cblosc_set_stream_format(int(codec_format)))
+
+
+def CBloscGetStreamFormat():
+    """The stream format the CBlosc* writers use (include/hipblosc.h hb_cblosc_get_stream_format)."""
+    return int(lib().hb_cblosc_get_stream_format())
 
 
 def CBloscDecompress(frame):

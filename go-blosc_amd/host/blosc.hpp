@@ -160,6 +160,10 @@ inline unsigned CBloscAcceptCodecs(unsigned mask) { return (unsigned)check(hb_cb
 // (HB_LZ4, 5); process-wide, read once per call; returns the previous setting packed as codec << 8 | clevel, throws for anything else
 inline int CBloscSetCompressor(int codec, int clevel) { return (int)check(hb_cblosc_set_compressor(codec, clevel)); }
 inline std::pair<int, int> CBloscGetCompressor() { int c = 0, l = 0; check(hb_cblosc_get_compressor(&c, &l)); return {c, l}; }
+// which format the streams of the frames the CBlosc* writers write have (hb_cblosc_set_stream_format): HB_CB_FORMAT_LZ4 (the default) or HB_CB_FORMAT_ZSTD,
+// orthogonal to the compressor and level; process-wide, read once per call; returns the previous format, throws for anything else
+inline int CBloscSetStreamFormat(int codec_format) { return (int)check(hb_cblosc_set_stream_format(codec_format)); }
+inline int CBloscGetStreamFormat() { return hb_cblosc_get_stream_format(); }
 // many C-Blosc-1 frames through one set of launches (hb_cblosc_decompress_frames_batch): out[k] is what hb_cblosc_decompress gives for frames[k],
 // rc[k] the byte count or its HB_ERR_* code (nothing is thrown per frame)
 inline std::vector<Bytes> CBloscDecompressBatch(const std::vector<Bytes> &frames, std::vector<int64_t> &rc, int device = 0) {

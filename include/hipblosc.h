@@ -365,7 +365,7 @@ int     hb_cblosc_parse_header(const void *frame, size_t n, hb_cblosc_header *ou
  * same header: HB_CBLOSC_ZSTD_SLOTS literal areas, none.  A zlib stream must be what zlib's uncompress() decodes to exactly the stream's size: header
  * without a preset dictionary, stored / fixed / dynamic blocks, the Adler-32 of the plain bytes, which the device computes and holds against
  * the trailer as c-blosc does; bytes behind the trailer are ignored as there; anything else is HB_ERR_DECOMPRESSION_FAILED for its frame (its
- * block) alone (DESIGN.md §3.5 "zlib streams").  Its literals are inline: no workspace query grows for a zlib frame either.  Writing is not touched: hb_cblosc_compress* writes LZ4 (hb_cblosc_set_compressor
+ * block) alone (DESIGN.md §3.5 "zlib streams").  Its literals are inline: no workspace query grows for a zlib frame either.  Writing is not touched: hb_cblosc_compress* writes LZ4 or, under hb_cblosc_set_stream_format, zstd (hb_cblosc_set_compressor
  * below chooses how hard it searches; its threading rule is this one). */
 #define HB_CBLOSC_ZSTD_SLOTS 0
 int     hb_cblosc_accept_codecs(unsigned mask);
@@ -685,6 +685,29 @@ int64_t hb_cblosc_compress(const void *src, size_t n, void *dst, size_t cap, int
  * not depend on the setting: a workspace sized under one setting serves a call under any other.  Reading is not touched. */
 int     hb_cblosc_set_compressor(int codec, int clevel);
 int     hb_cblosc_get_compressor(int *codec, int *clevel);
+/* which format the streams of the written frames have: HB_CB_FORMAT_LZ4 (the default: LZ4 blocks, the bytes written before this setting
+ * existed) or HB_CB_FORMAT_ZSTD (one Zstandard frame per stream, RFC 8878; the header's codec bits say 4, c-blosc reads the frames with its
+ * zstd).  The values are c-blosc's codec-format numbers, the bit numbers of hb_cblosc_accept_codecs.  The setting is orthogonal to
+ * hb_cblosc_set_compressor: (codec, clevel) chooses how the matcher searches under either format, the format how its sequences are written
+ * down.  Under HB_CB_FORMAT_ZSTD one more kernel (k_cbe_zstd, one wavefront per 4096-byte stream) runs between the matcher and the pack: the
+ * literals get a Huffman code (11 bits at the most, a tree per stream, described by direct or FSE-compressed weights), the sequences go out
+ * with the predefined FSE tables, offsets as offset + 3; a stream of one byte value is an RLE block; a stream that does not get smaller
+ * than 4096 bytes is stored, as before.  Level 0 and inputs below 4096 bytes write the memcpyed frame of the LZ4 format, byte for byte; the
+ * last, shorter block stays one stored stream; block sizes, hb_cblosc_bound and every workspace query are the same under both formats.
+ * The subset, the tie-breaks and the serial statement of the kernel are csrc/hb_zstd_enc.h's (DESIGN.md 3.5 "Writing zstd streams").
+ * hb_cblosc_set_stream_format returns the previous format, or HB_ERR_BAD_ARG -- and no change -- for any other value; it leaves the
+ * compressor and level alone, as hb_cblosc_set_compressor leaves the format alone (they share one atomic word: the threading rule above
+ * holds for both, a call uses one format throughout).  READING zstd frames stays opt-in: a caller who writes them calls
+ * hb_cblosc_accept_codecs(0x12) to read them back with this library.
+ * hb_cblosc_zstd_stream_from_lz4 is the writer's serial statement, on the host: lz4 is one stream as the LZ4 format writes it (an LZ4 block
+ * of n bytes that decodes to usize <= 65535 bytes with at most 4096 literals and 1024 sequences, or, when n == usize <= 4096, the plain bytes
+ * of a stored stream); it returns the length of the zstd frame written to dst, or 0 when that would not be smaller than usize or than cap
+ * (the stream is stored).  Stream i of a frame written under HB_CB_FORMAT_ZSTD is this function of stream i of the frame written under
+ * HB_CB_FORMAT_LZ4 with the same compressor. */
+enum { HB_CB_FORMAT_LZ4 = 1, HB_CB_FORMAT_ZSTD = 4 };
+int     hb_cblosc_set_stream_format(int codec_format);
+int     hb_cblosc_get_stream_format(void);
+size_t  hb_cblosc_zstd_stream_from_lz4(const void *lz4, size_t n, size_t usize, void *dst, size_t cap);
 /* ---- batched C-Blosc-1 encode: many inputs through ONE set of launches (upload, chunk map, filter, the matcher launch or launches, tile sums,
  *      one scan workgroup per frame, pack, finish -- the same launches for 4 frames and for 4096).  One shuffle / typesize for the whole batch:
  *      an array has one dtype and one filter.
